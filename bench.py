@@ -40,8 +40,9 @@ Extra objects on the JSON line:
                 job, both precisions), cfg5 (the 64-chunk batch with the cross terms of the hi + lo products on the block-scaled
                 fp8 MFMA, opt-in levels 1 and 2, next to the default path).
   strong_scaling_cfg4  BASELINE config 4 itself: 512 chunks sharded over the N ranks (512 / N each), logits all-gathered.
-  timed_region  the K steps are repeated until the timed region holds >= 2 s of GPU work (clocks and temperatures settle);
-                ms_per_step = region / (K x repeats).  rccl_ranks = ranks counted by an RCCL all-reduce (the process group
+  timed_region  exactly K timed steps, ms_per_step = region / K, the clock started with the track pipeline full; before
+                them, untimed pre-heat steps are added to the W warm-up steps until those hold >= --min-seconds (2 s) of GPU
+                work (clocks and temperatures settle).  rccl_ranks = ranks counted by an RCCL all-reduce (the process group
                 is brought up at N = 1 as well, so every run exercises the N > 1 code path).
   host_inclusive  the headline job with the waveforms starting in pinned HOST memory (PCIe-inclusive rate; never `value`).
   cpu_baseline  the CPU oracle's Audio2Beats (torch fp32, SDPA attention like the reference) on ONE 300 s track on this
@@ -115,6 +116,37 @@ def log(msg):
     print(f"[bench +{time.perf_counter() - _T0:6.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, last, workload):
+    """--dump-outputs: what the last timed step handed to its caller, one DIR/<name>.npy per array.  Tracks: the beat and
+    downbeat times (seconds, float64) of every track, as Audio2Beats.many returns them.  Forward: the beat and downbeat logits
+    (float32, chunks x frames) of BeatThis.forward.  Outputs over DUMP_MAX_BYTES keep a fixed, seeded sample of their rows."""
+    import numpy as np
+
+    if last is None:
+        raise SystemExit("bench.py: --dump-outputs needs at least one timed step (--steps >= 1)")
+    if workload == "tracks":
+        arrays = {}
+        for i, (beats, downbeats) in enumerate(last):
+            arrays[f"track{i:03d}_beats"] = np.asarray(beats, dtype=np.float64)
+            arrays[f"track{i:03d}_downbeats"] = np.asarray(downbeats, dtype=np.float64)
+    else:
+        arrays = {k: last[k].detach().float().cpu().numpy() for k in ("beat", "downbeat")}
+        total = sum(a.nbytes for a in arrays.values())
+        if total > DUMP_MAX_BYTES:
+            n = arrays["beat"].shape[0]
+            keep = max(1, n * DUMP_MAX_BYTES // total)
+            rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+            arrays = {k: a[rows] for k, a in arrays.items()}
+            arrays["sampled_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"outputs of the last timed step: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values())} bytes -> {out_dir}")
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -148,7 +180,11 @@ def main():
                          "(1, the library's default: chosen by the flip-soak rule, DESIGN.md section 3), in the frontend as well (2, "
                          "round 5's default), nowhere = three-term P.V of rounds 3 - 4 (0)")
     ap.add_argument("--min-seconds", type=float, default=2.0,
-                    help="the K timed steps are repeated until the timed region is at least this long (0: exactly K steps)")
+                    help="untimed pre-heat: steps are added to the W warm-up steps until those are at least this long (0: W only); "
+                         "the timed region is always exactly K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB (a fixed, seeded sample of larger outputs)")
     ap.add_argument("--watchdog", type=int, default=900, help="seconds after which a stuck run dumps its stacks and exits")
     ap.add_argument("--share-gpu", action="store_true",
                     help="development / tests: all N ranks run on cuda:0 and the collectives go over gloo -- the N > 1 code path of "
@@ -364,31 +400,54 @@ def main():
     drain()
     fence()
     tw = (time.perf_counter() - tw) / max(1, args.warmup)
-    # The K steps are timed `repeats` times back to back so that the region holds >= --min-seconds of GPU work (0.3 s of
-    # a 20-step default run is over before clocks and temperatures have settled); every rank uses the same count.
-    repeats = 1
+    # Untimed pre-heat: the warm-up is extended until it holds >= --min-seconds of GPU work (0.3 s of a 20-step default run
+    # is over before clocks and temperatures have settled), so that the K timed steps start in the steady state; every rank
+    # uses the same count.  The timed region itself is always exactly K steps.
+    preheat = 0
     if args.min_seconds > 0 and args.warmup > 0:
-        est = torch.tensor([tw * args.steps], dtype=torch.float64, device=dev)
+        est = torch.tensor([tw], dtype=torch.float64, device=dev)
         if use_dist:
             all_reduce(est, dist.ReduceOp.MIN)
-        repeats = max(1, int(-(-args.min_seconds // max(float(est.item()), 1e-6))))
-    log(f"timed region: {args.steps} steps x {repeats}")
+        preheat = max(0, int(-(-args.min_seconds // max(float(est.item()), 1e-6))) - args.warmup)
+    if preheat:
+        log(f"pre-heat: {preheat} untimed steps")
+        for _ in range(preheat):
+            step()
+        drain()
+        fence()
+    log(f"timed region: {args.steps} steps")
     # package energy over the timed region from the SMU's accumulator (tools/smi.py: rsmi_dev_energy_count_get), read right
     # before the first and right after the last step's fence -- joules are what this path is bound by
     from tools.smi import EnergyMeter
 
     meter = EnergyMeter(dev)
-    meter.start()
-    t0 = time.perf_counter()
-    for i_step in range(args.steps * repeats):
+
+    def timed_step(i_step):
         if rank == args.fail_rank and i_step == args.fail_step:
             raise RuntimeError(f"--fail-rank {rank}: raising inside timed step {i_step} (test of the N > 1 failure rule)")
+        return step()
+
+    ret, i_first = None, 0
+    if args.workload == "tracks" and args.steps > 0:
+        # The tracks are pipelined (step i + 1 is enqueued before the host part of step i is collected), and the clock starts
+        # in that steady state rather than on an idle GPU: one untimed step is put in flight, timed step 1 is enqueued behind
+        # it, and the clock starts once the untimed step's result has been collected (a wait on that step's own copy event).
+        # The region then holds the K steps' GPU work back to back and ends with the host part of the last one.
         step()
+        ret, i_first = timed_step(0), 1
+    meter.start()
+    t0 = time.perf_counter()
+    for i_step in range(i_first, args.steps):
+        ret = timed_step(i_step)
     last = drain()
     fence()
     elapsed = time.perf_counter() - t0
     joules = meter.stop()
-    n_timed = args.steps * repeats
+    n_timed = args.steps
+    if last is None:   # (--workload forward: step() returns its own result, drain() has nothing pending)
+        last = ret
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, args.workload)
     energy = {"available": False, "reason": meter.why}
     if joules is not None:
         jt = torch.tensor([joules[0]], dtype=torch.float64, device=dev)
@@ -982,7 +1041,7 @@ def main():
             "stress_weights": stress, "host_inclusive": host_inclusive, "configs": configs,
             "strong_scaling_cfg4": strong, "rccl_ranks": rccl_ranks,
             "rccl_note": "--share-gpu: all ranks on cuda:0, gloo collectives (development run of the N > 1 path, not a measurement)" if args.share_gpu else dist_note,
-            "timed_region": {"steps": args.steps, "repeats": repeats, "steps_timed": n_timed, "seconds": round(elapsed, 3),
+            "timed_region": {"steps": args.steps, "preheat_steps": preheat, "steps_timed": n_timed, "seconds": round(elapsed, 3),
                              "per_rank_ms_per_step": per_rank_ms},
             "breakdown": breakdown, **p16_legs,
         }

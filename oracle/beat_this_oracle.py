@@ -11,8 +11,8 @@ Pinning status: the reference's own tests hold no numerical fixtures for this pa
 the reference code itself, run in the build container by ``oracle/make_golden.py``
 (unmodified ``/root/reference`` + the three third-party stand-ins in
 ``oracle/shims``) and committed under ``tests/golden/``.  ``tests/test_oracle.py``
-checks this restatement against those fixtures everywhere, and against the live
-reference whenever ``/root/reference`` exists.  The third-party leaves (torchaudio
+checks this restatement against those fixtures everywhere (the reference itself is
+needed only to regenerate them).  The third-party leaves (torchaudio
 2.3.1 MelSpectrogram, rotary-embedding-torch 0.6.4, soxr 0.3.7) are absent from the
 image: their restatement is "parity unpinned" (SURVEY.md 8c).
 

@@ -105,3 +105,12 @@ FINAL0_CASES = {
     "e2e": dict(weight_seed=1, style="lively", seconds=40.0, audio_seed=13),
     "outlier": dict(weight_seed=1, frames=1500, input_seed=3),
 }
+
+# oracle/make_golden_live.py -> tests/golden/reference_live.npz (test_oracle.py's checks of the oracle against the reference
+# package itself: a short chunk + the state-dict key order, the log-mel of 3 s of audio, and the 1500-frame chunk that
+# tools/port_speed.py times)
+LIVE_CASES = {
+    "forward": dict(hparams="small0", weight_seed=5, style="lively", frames=700, input_seed=9),
+    "logmel": dict(seconds=3.0, audio_seed=2),
+    "port_chunk": dict(hparams="small0", weight_seed=1, style="lively", frames=1500, input_seed=5),
+}

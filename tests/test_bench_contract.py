@@ -38,5 +38,29 @@ def test_track_arithmetic_matches_split_piece():
 
 def test_command_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True).stdout
-    for flag in ("--gpus", "--steps", "--warmup", "--prec", "--workload", "--tracks"):
+    for flag in ("--gpus", "--steps", "--warmup", "--prec", "--workload", "--tracks", "--dump-outputs"):
         assert flag in out
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    import numpy as np
+    import torch
+
+    b = _bench()
+    tracks = [(np.array([0.5, 1.0, 1.5]), np.array([0.5])), (np.array([0.25]), np.array([], dtype=np.float64))]
+    b.dump_outputs(str(tmp_path / "tr"), tracks, "tracks")
+    assert sorted(os.listdir(tmp_path / "tr")) == ["track000_beats.npy", "track000_downbeats.npy", "track001_beats.npy",
+                                                   "track001_downbeats.npy"]
+    got = np.load(tmp_path / "tr" / "track000_beats.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, tracks[0][0])
+    r = {"beat": torch.randn(4, 1500, dtype=torch.float16), "downbeat": torch.randn(4, 1500)}
+    b.dump_outputs(str(tmp_path / "fw"), r, "forward")
+    beat = np.load(tmp_path / "fw" / "beat.npy")
+    assert beat.dtype == np.float32 and beat.shape == (4, 1500) and np.array_equal(beat, r["beat"].float().numpy())
+    # larger than the cap: a fixed, seeded sample of the rows, the same on every call
+    b.DUMP_MAX_BYTES = 4 * 1500 * 4 * 2 // 2
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), r, "forward")
+    rows = np.load(tmp_path / "s1" / "sampled_rows.npy")
+    assert len(rows) == 2 and np.array_equal(rows, np.load(tmp_path / "s2" / "sampled_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "downbeat.npy"), r["downbeat"].numpy()[rows.astype(int)])

@@ -10,8 +10,6 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import have_reference
-
 LOGIT_TOL_F32 = 1e-3
 
 
@@ -42,16 +40,18 @@ def _state():
 
 @needs_ckpt
 def test_oracle_matches_live_reference_on_the_trained_checkpoint():
-    """CPU: the oracle restatement against the unmodified reference with the TRAINED weights (one 1500-frame chunk)."""
-    if not have_reference():
-        pytest.skip("needs /root/reference (build container only)")
+    """CPU: the oracle restatement against the unmodified reference with the TRAINED weights (one 1500-frame chunk); the
+    reference's package is imported from ``$BEAT_THIS_REFERENCE`` (a checkout of it, as for oracle/make_golden.py)."""
+    reference = os.environ.get("BEAT_THIS_REFERENCE", "")
+    if not os.path.isdir(os.path.join(reference, "beat_this")):
+        pytest.skip("needs a checkout of the reference: set $BEAT_THIS_REFERENCE")
     import sys
 
     from beat_this_amd import weights as W
     from oracle import beat_this_oracle as O
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path[:0] = [os.path.join(root, "oracle", "shims"), "/root/reference"]
+    sys.path[:0] = [os.path.join(root, "oracle", "shims"), reference]
     from beat_this.inference import load_model as ref_load_model
 
     _, sd = _state()
