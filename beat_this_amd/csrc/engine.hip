@@ -26,6 +26,8 @@ static int bt_set_error(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+// (the C entry points of the other sources report through the same bt_last_error)
+int bt_set_error_external(int code, const char* msg) { return bt_set_error(code, msg); }
 
 // Optional per-launch timing with HIP events on the caller's stream (bench.py roofline leg); state lives in the engine
 // handle (reentrant per handle, like everything else).  Off by default: a normal bt_forward records nothing and never

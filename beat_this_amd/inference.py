@@ -486,9 +486,10 @@ class Audio2Beats(Audio2Frames):
         spect, frame_off = self.signal2spect_many(signals, sr)
         # float16="f32x3": the range flags of the forward slices are collected, not waited for; ``result()`` looks at them
         # once the batch's device-to-host copy has arrived and repeats the batch on the exact fp32 path if one fired
-        if self.frames2beats.type != "minimal":
-            # the DBN (madmom) runs on the host right away and needs final logits: the range flags are looked at -- and the
-            # batch repeated on the exact path if one fired -- before it sees them (checks=None: the synchronous guard)
+        native_dbn = isinstance(self.frames2beats, Postprocessor) and self.frames2beats.type == "dbn"
+        if self.frames2beats.type != "minimal" and not native_dbn:
+            # a DBN-type post-processor of another kind runs on the host right away and needs final logits: the range
+            # flags are looked at -- and the batch repeated on the exact path if one fired -- before it sees them (checks=None: the synchronous guard)
             beat, down = self.spect2frames_batch(spect, frame_off)
 
             class _Done:
@@ -498,7 +499,7 @@ class Audio2Beats(Audio2Frames):
                           for k in range(len(signals))])
         checks = [] if isinstance(self.model, BeatThis) and self.model.fp32_split_gemms and not self.float16 else None
         beat, down = self.spect2frames_batch(spect, frame_off, checks=checks)
-        pending = self.frames2beats.ragged_async(beat, down, frame_off)
+        pending = self.frames2beats.ragged_async(beat, down, frame_off)   # (minimal or this library's DBN: both on the device)
         pending.logits = (beat, down, frame_off)   # framewise logits of the batch (concatenated), for callers that want them
         if checks:
             return _GuardedPending(pending, checks, lambda: self._many_exact_async(signals, sr))

@@ -5,8 +5,9 @@ go to the host where deduplicate_peaks / nearest-beat snapping / unique run in C
 (bt_postprocess_host, float64 like numpy).  No thread pool.  Logits that live in host memory (the
 reference accepts CPU tensors, postprocessor.py:58-83) get the same peak mask from the library's host entry
 point (bt_peaks_host).  ``ragged`` (extension) post-processes many tracks stored back to back with one launch
-and one device-to-host copy.  "dbn" defers to madmom exactly like the reference (not installed here; out of
-scope, SURVEY.md 2 #5)."""
+and one device-to-host copy.  "dbn": madmom's DBNDownBeatTrackingProcessor with the reference's arguments, restated in the
+library (csrc/dbn.hip: the Viterbi of every track and bar length in one launch; bt_dbn_host for host logits); madmom is
+never imported."""
 from __future__ import annotations
 
 import ctypes as C
@@ -69,16 +70,93 @@ class PendingBeats:
         return out
 
 
+# DBNDownBeatTrackingProcessor(beats_per_bar=[3, 4], min_bpm=55.0, max_bpm=215.0, fps=fps, transition_lambda=100)
+# (postprocessor.py:31-37) with madmom's defaults for the rest
+DBN_PARAMS = dict(beats_per_bar=(3, 4), min_bpm=55.0, max_bpm=215.0, num_tempi=60, transition_lambda=100.0,
+                  observation_lambda=16.0, threshold=0.05)
+
+
+def dbn_tables(fps: float, **kw) -> np.ndarray:
+    """The library's DBN tables (bt_dbn_tables, layout in include/beat_this_amd.h) as a uint8 host array; a parameter
+    set the kernel cannot run raises ValueError."""
+    p = dict(DBN_PARAMS, **kw)
+    beats = np.ascontiguousarray(p["beats_per_bar"], dtype=np.int32)
+    size = C.c_size_t(0)
+    lib = _lib.lib()
+    args = (float(fps), float(p["min_bpm"]), float(p["max_bpm"]), int(p["num_tempi"]), float(p["transition_lambda"]),
+            float(p["observation_lambda"]), float(p["threshold"]), beats.ctypes.data, len(beats))
+    _lib.check(lib.bt_dbn_tables(*args, None, C.byref(size)))
+    blob = np.zeros(size.value, dtype=np.uint8)
+    _lib.check(lib.bt_dbn_tables(*args, blob.ctypes.data, C.byref(size)))
+    return blob
+
+
+class DBN:
+    """``Postprocessor.dbn``: the callable madmom's processor is -- act (T, 2) float64 -> (N, 2) rows (beat time,
+    beat number in the bar) -- on the library's host decoder."""
+
+    def __init__(self, tables: np.ndarray, fps: float):
+        self.tables, self.fps = tables, fps
+
+    def __call__(self, act):
+        act = np.ascontiguousarray(act, dtype=np.float64)
+        if act.ndim != 2 or act.shape[1] != 2:
+            raise ValueError(f"expected a (T, 2) activation, got shape {act.shape}")
+        rows = np.zeros((max(len(act), 1), 2), dtype=np.int32)
+        n = C.c_int32(0)
+        _lib.check(_lib.lib().bt_dbn_host_act(self.tables.ctypes.data, act.ctypes.data, len(act), rows.ctypes.data, C.byref(n)))
+        return _dbn_rows(rows[: n.value], self.fps)
+
+
+def _dbn_rows(rows: np.ndarray, fps: float) -> np.ndarray:
+    """(frame, beat number) int32 rows -> madmom's output: float64 (frame / fps, beat number)"""
+    return np.vstack((rows[:, 0].astype(np.int64) / float(fps), rows[:, 1].astype(np.float64))).T
+
+
+def _split_rows(out: np.ndarray, fps: float):
+    res = _dbn_rows(out, fps)
+    return res[:, 0].copy(), res[res[:, 1] == 1][:, 0].copy()
+
+
+class PendingDBN:
+    """Handle of an enqueued DBN ``Postprocessor.ragged_async`` call; ``result()`` -> [(beats, downbeats)] per track."""
+
+    def __init__(self, host, done, frame_off, fps, owner=None, keep=None):
+        self._host, self._done, self._frame_off, self._fps = host, done, frame_off, fps
+        self._owner, self._keep, self._out = owner, keep, None
+
+    def result(self):
+        if self._out is not None:
+            return self._out
+        n = len(self._frame_off) - 1
+        if self._host is None:
+            self._out = [(np.zeros(0), np.zeros(0)) for _ in range(n)]
+            return self._out
+        self._done.synchronize()
+        host = self._host.numpy()
+        out = []
+        for k in range(n):
+            lo = n + 2 * int(self._frame_off[k])
+            out.append(_split_rows(host[lo: lo + 2 * int(host[k])].reshape(-1, 2), self._fps))
+        if self._owner is not None:
+            self._owner.__dict__.setdefault("_pin_pool", []).append(self._host._base if self._host._base is not None else self._host)
+        self._host = self._keep = None
+        self._out = out
+        return out
+
+
+_DBN_LOCK = threading.Lock()
+
+
 class Postprocessor:
     def __init__(self, type: str = "minimal", fps: int = 50):
         assert type in ["minimal", "dbn"]
         self.type = type
         self.fps = fps
         if type == "dbn":
-            from madmom.features.downbeats import DBNDownBeatTrackingProcessor
-
-            self.dbn = DBNDownBeatTrackingProcessor(beats_per_bar=[3, 4], min_bpm=55.0, max_bpm=215.0, fps=self.fps,
-                                                    transition_lambda=100)
+            self._dbn_tables = dbn_tables(fps)
+            self._dbn_dev = {}   # device -> uploaded tables
+            self.dbn = DBN(self._dbn_tables, fps)
 
     def __call__(self, beat: torch.Tensor, downbeat: torch.Tensor, padding_mask: torch.Tensor | None = None):
         batched = beat.ndim != 1
@@ -142,6 +220,8 @@ class Postprocessor:
         """``ragged`` split in two: everything up to the (asynchronous, pinned-memory) device-to-host copy is enqueued
         now; ``.result()`` waits for that copy and runs the host step.  A caller with several batches enqueues batch
         i + 1 before collecting batch i, so the GPU never idles during the host step."""
+        if self.type == "dbn":
+            return self._dbn_ragged_async(beat, downbeat, frame_off)
         assert self.type == "minimal"
         _lib.require_gpu(beat, "beat logits")
         frame_off = np.asarray(frame_off, dtype=np.int64)
@@ -183,17 +263,78 @@ class Postprocessor:
         return torch.empty((max(size, 1 << 16),), dtype=torch.int32, pin_memory=True)
 
     def postp_dbn(self, beat, downbeat, padding_mask=None):
-        if padding_mask is None:
-            padding_mask = torch.ones_like(beat, dtype=torch.bool)
-        eps = 1e-5
-        bp = beat.double().sigmoid() * (1 - eps) + eps / 2
-        dp = downbeat.double().sigmoid() * (1 - eps) + eps / 2
+        B = beat.shape[0]
+        if beat.is_cuda:
+            # unpad by the mask (a gather) and decode all tracks with one launch triple
+            if padding_mask is None:
+                b1, d1 = beat.reshape(-1), downbeat.reshape(-1)
+                frame_off = np.arange(B + 1, dtype=np.int64) * beat.shape[1]
+            else:
+                m = padding_mask.bool().to(beat.device)
+                b1, d1 = beat[m], downbeat[m]
+                frame_off = np.concatenate([[0], np.cumsum(padding_mask.bool().sum(1).cpu().numpy())]).astype(np.int64)
+            out = self._dbn_ragged_async(b1, d1, frame_off).result()
+            return tuple(o[0] for o in out), tuple(o[1] for o in out)
         out_b, out_d = [], []
-        for b in range(beat.shape[0]):
-            m = padding_mask[b].bool()
-            pb, pd = bp[b][m].cpu().numpy(), dp[b][m].cpu().numpy()
-            act = np.vstack((np.maximum(pb - pd, eps / 2), pd)).T
-            res = self.dbn(act)
-            out_b.append(res[:, 0])
-            out_d.append(res[res[:, 1] == 1][:, 0])
+        for b in range(B):
+            lb, ld = beat[b], downbeat[b]
+            if padding_mask is not None:
+                m = padding_mask[b].bool()
+                lb, ld = lb[m], ld[m]
+            lb = np.ascontiguousarray(lb.double().numpy())
+            ld = np.ascontiguousarray(ld.double().numpy())
+            rows = np.zeros((max(len(lb), 1), 2), dtype=np.int32)
+            n = C.c_int32(0)
+            _lib.check(_lib.lib().bt_dbn_host(self._dbn_tables.ctypes.data, lb.ctypes.data, ld.ctypes.data, len(lb),
+                                              rows.ctypes.data, C.byref(n)))
+            bt, dt = _split_rows(rows[: n.value], self.fps)
+            out_b.append(bt)
+            out_d.append(dt)
         return tuple(out_b), tuple(out_d)
+
+    def _dbn_device_tables(self, dev) -> torch.Tensor:
+        with _DBN_LOCK:
+            t = self._dbn_dev.get(dev)
+            if t is None:
+                t = self._dbn_dev[dev] = torch.from_numpy(self._dbn_tables).to(dev)
+            return t
+
+    def _dbn_ragged_async(self, beat, downbeat, frame_off) -> PendingDBN:
+        """DBN decode of the tracks ``frame_off[k]:frame_off[k+1]`` of the 1-D device tensors: one bt_dbn_decode (three
+        launches) and one device-to-host copy of [row counts | rows]."""
+        _lib.require_gpu(beat, "beat logits")
+        frame_off = np.asarray(frame_off, dtype=np.int64)
+        n = len(frame_off) - 1
+        total = int(frame_off[-1])
+        if n == 0 or total == 0:
+            return PendingDBN(None, None, frame_off, self.fps)
+        dev = beat.device
+        b1, d1 = beat.reshape(-1), downbeat.reshape(-1)
+        f64 = b1.dtype == torch.float64 or d1.dtype == torch.float64
+        dt = torch.float64 if f64 else torch.float32
+        if (b1.dtype == d1.dtype == dt and b1.is_contiguous() and d1.is_contiguous() and b1.numel() == total
+                and b1.untyped_storage().data_ptr() == d1.untyped_storage().data_ptr()
+                and d1.data_ptr() == b1.data_ptr() + b1.element_size() * total):
+            logits = b1   # (the batched forward writes both rows into one buffer)
+        else:
+            logits = torch.cat([b1.to(dt), d1.to(dt)])   # (fp16 / bf16 -> fp32 is exact, as is the reference's .double())
+        spans = np.empty((n, 4), dtype=np.int32)
+        spans[:, 0] = frame_off[:-1]
+        spans[:, 1] = total + frame_off[:-1]
+        spans[:, 2] = frame_off[1:] - frame_off[:-1]
+        spans[:, 3] = frame_off[:-1]
+        lib = _lib.lib()
+        tables = self._dbn_tables.ctypes.data
+        size = n + 2 * total
+        with torch.cuda.device(dev):
+            d_tab = self._dbn_device_tables(dev)
+            ws = torch.empty((lib.bt_dbn_workspace_bytes(tables, n, total),), dtype=torch.uint8, device=dev)
+            buf = torch.empty((size,), dtype=torch.int32, device=dev)
+            d_spans = _lib.upload(spans, dev)
+            _lib.check(lib.bt_dbn_decode(_lib.stream_ptr(dev), tables, d_tab.data_ptr(), logits.data_ptr(), int(f64),
+                                         d_spans.data_ptr(), n, total, buf.data_ptr(), ws.data_ptr(), ws.numel()))
+            host = self._pinned(size)
+            host[:size].copy_(buf, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+        return PendingDBN(host[:size], done, frame_off, self.fps, owner=self, keep=(buf, logits, d_spans, ws))

@@ -285,6 +285,44 @@ int bt_peaks_batch(void* stream, const float* d_logits, const int32_t* d_spans, 
  * postprocessor.py:58-83); idx must hold n entries */
 int bt_peaks_host(const float* logits, int64_t n, int32_t* idx, int32_t* count);
 
+/* DBN post-processing (Postprocessor(type="dbn"), postprocessor.py:28-37,138-173; csrc/dbn.hip): madmom's
+ * DBNDownBeatTrackingProcessor restated -- one bar HMM per entry of beats_per_bar, float64 Viterbi, the `correct` step.
+ *
+ * bt_dbn_tables: the state / transition / observation tables of one parameter set (reference: fps 50, bpm 55..215,
+ * num_tempi 60, transition_lambda 100, observation_lambda 16, threshold 0.05, beats_per_bar {3, 4}) in HOST memory.
+ * tables == NULL: *bytes = the size of the blob.  Otherwise *bytes (>= that size) bytes at tables are filled; upload them
+ * as they are for the device entry points.  Parameter sets the kernel cannot run (more than 255 beat intervals, more
+ * than 8192 states per HMM, more than 1536 tempo transitions, more than 4 HMMs or 16 beats per bar) return BT_ERR_ARG.
+ * Blob layout (little endian, no padding): int32 magic "DBN1", K (intervals), n_hmm, states per beat, nnz, reserved;
+ * int32 beats[4], num_states[4]; double init[4] (log(1 / num_states)), observation_lambda - 1, threshold;
+ * int32 intervals[256], first[256] (first state of each interval inside a beat), band_ptr[258], band_from[1536];
+ * double logp[1536]; uint8 cnt[16][256] -- 25712 bytes.  The tempo transitions into the first state of interval j are the entries
+ * band_ptr[j] .. band_ptr[j+1]-1 (from the last state of interval band_from[e] of the previous beat, log probability
+ * logp[e], ascending from-interval); cnt[b][j] = the leading states of interval j in beat b whose observation pointer
+ * is >= 1 (2 in beat 0, 1 elsewhere). */
+int bt_dbn_tables(double fps, double min_bpm, double max_bpm, int num_tempi, double transition_lambda,
+                  double observation_lambda, double threshold, const int32_t* beats_per_bar, int n_hmm, void* tables,
+                  size_t* bytes);
+/* device workspace of bt_dbn_decode for n_tracks tracks of total_frames frames (and of bt_dbn_viterbi: n_tracks = 1) */
+size_t bt_dbn_workspace_bytes(const void* tables, int n_tracks, int64_t total_frames);
+/* ragged DBN decode of n_tracks tracks: track k's beat logits at d_logits[d_spans[4 k]], its downbeat logits at
+ * d_logits[d_spans[4 k + 1]], d_spans[4 k + 2] frames each, d_spans[4 k + 3] = the frames of the tracks before it
+ * (total_frames = their sum).  d_logits: float32, or float64 when f64 = 1.  tables: the host blob, d_tables: its device
+ * copy.  d_out (n_tracks + 2 total_frames int32): d_out[k] = row count of track k, its rows (frame, beat number in the
+ * bar; 1 = downbeat) at d_out + n_tracks + 2 d_spans[4 k + 3].  Three launches on the stream, no synchronisation. */
+int bt_dbn_decode(void* stream, const void* tables, const void* d_tables, const void* d_logits, int f64,
+                  const int32_t* d_spans, int n_tracks, int64_t total_frames, int32_t* d_out, void* d_ws, size_t ws_bytes);
+/* the Viterbi of HMM `hmm` alone on given log densities d_dens [n][3] (observation pointer 0, 1, 2): d_path [n] state
+ * indices (left untouched when *d_log_prob is -inf), d_log_prob the path's log probability */
+int bt_dbn_viterbi(void* stream, const void* tables, const void* d_tables, int hmm, const double* d_dens, int64_t n,
+                   int32_t* d_path, double* d_log_prob, void* d_ws, size_t ws_bytes);
+/* HOST: the same recursion in C++ (bit-identical: same fp64 operations in the same order) */
+int bt_dbn_viterbi_host(const void* tables, int hmm, const double* dens, int64_t n, int32_t* path, double* log_prob);
+/* HOST: DBN decode of one track whose logits live in host memory (float64; rows as bt_dbn_decode, at most n of them) */
+int bt_dbn_host(const void* tables, const double* beat, const double* downbeat, int64_t n, int32_t* rows, int32_t* n_rows);
+/* HOST: the same from a combined activation act [n][2] (madmom's processor input: beat-not-downbeat, downbeat) */
+int bt_dbn_host_act(const void* tables, const double* act, int64_t n, int32_t* rows, int32_t* n_rows);
+
 /* HOST: deduplicate_peaks(peaks, width) on its own (postprocessor.py:176-197): groups of ascending frame indices not more than
  * `width` apart (measured from the running mean) are replaced by their mean; out must hold n doubles */
 int bt_deduplicate_peaks_host(const int32_t* idx, int n, double width, double* out, int32_t* n_out);
