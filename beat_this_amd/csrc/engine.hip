@@ -15,11 +15,6 @@
 #include "common.h"
 #include "kernels.h"
 
-// BT_PREC_F32X3 attention kernel of the forward (bt_attn_frag_args.x3): 4 = two query blocks per wave on the hand-scheduled
-// key loop (round 4), 2 = the compiler-scheduled 64-key-tile kernel of round 3 (kept for A/B builds: -DBT_X3_ATTN=2)
-#ifndef BT_X3_ATTN
-#define BT_X3_ATTN 4
-#endif
 
 static thread_local std::string g_err;
 static int bt_set_error(int code, const std::string& msg) {
@@ -76,8 +71,6 @@ struct Workspace {
   float* ssq[2];  // [D / 64][B T] partial row sums of squares of the main residual stream (ping-pong)
   int* status;    // BT_PREC_F32X3 range flag: the FIRST word of the workspace (include/beat_this_amd.h)
   int* fix_mask;  // BT_PREC_F32X3: overflow map of the attention launches, [(sequences x heads)][nbp] words (attn2.hip)
-  int x3_gemm_fp8;              // BT_OPT_X3_GEMM_FP8 of this forward
-  int x3_attn, x3_attn_front;   // bt_attn_frag_args.x3 of this forward's attention launches, main layers / frontend (kernel choice + BT_X3_P16)
   size_t total;
 };
 
@@ -91,8 +84,6 @@ Workspace carve(char* base, int B, int T, int D, int ff_mult, int prec) {
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return base ? base + o : (char*)nullptr; };
   Workspace w;
   w.status = (int*)take(256);
-  w.x3_attn = w.x3_attn_front = BT_X3_ATTN;
-  w.x3_gemm_fp8 = 0;
   w.xa = (float*)take(bt * 1024 * 4);
   w.xb = (float*)take(bt * 1024 * 4);
   w.xm = (float*)take(bt * D * 4);
@@ -119,6 +110,189 @@ Workspace carve(char* base, int B, int T, int D, int ff_mult, int prec) {
   return w;
 }
 
+// frontend activations ping-pong between ws.xa and ws.xb: the stem writes front_x(ws, 0), block blk reads front_x(ws, blk)
+// and writes front_x(ws, blk + 1), frontend.linear reads front_x(ws, 3)
+inline float* front_x(const Workspace& ws, int i) { return i & 1 ? ws.xb : ws.xa; }
+
+// ---- parameter blocks of the stage kernels (bt_forward_stages and bt_forward_unit) -------------------------------------
+StemP stem_params(const bt_model_desc& d, const float* spect, float* x, int B, int T) {
+  StemP p;
+  p.spect = spect; p.x = x; p.bn1_scale = d.bn1_scale; p.bn1_shift = d.bn1_shift;
+  p.w = d.stem_w; p.bias = d.stem_b; p.B = B; p.T = T;
+  return p;
+}
+
+// frontend conv of block blk on gemm.hip (weight slot wp); out is fp32 unless out_f32 is false (then the compute dtype)
+GemmP conv_params(const bt_model_desc& d, int blk, int wp, const float* in, void* out, int B, int T, bool out_f32) {
+  const int C = 32 << blk, F = 32 >> blk;
+  GemmP g;
+  memset(&g, 0, sizeof g);
+  g.A = in; g.W = d.conv_w[blk][wp]; g.M = B * T * (F / 2); g.N = 2 * C; g.K = 6 * C;
+  g.epi = GEMM_EPI_STORE; g.flags = GEMM_F_CONV | GEMM_F_A_F32 | GEMM_F_BIAS | GEMM_F_GELU | (out_f32 ? GEMM_F_OUT_F32 : 0);
+  g.bias = d.conv_b[blk]; g.out = out; g.ldo = 2 * C;
+  g.conv_C2 = 2 * C; g.conv_T = T; g.conv_F = F / 2;
+  return g;
+}
+
+// frontend conv of block blk on gemm3 (LDS-DMA ring on the half / hl32 shadow of x that the time-direction half leaves in
+// ws.hid); out_half: the output is only the half shadow (read by frontend.linear on gemm3)
+Gemm3P conv3_params(const bt_model_desc& d, const Workspace& ws, int blk, int B, int T, bool x3, bool out_half) {
+  const int C = 32 << blk, F = 32 >> blk;
+  float* out = front_x(ws, blk + 1);
+  Gemm3P g;
+  memset(&g, 0, sizeof g);
+  g.A = ws.hid; g.lda = 2 * C; g.M = B * T * (F / 2); g.K = 6 * C; g.N = 2 * C;
+  g.W = x3 ? d.conv_w_x3[blk] : d.conv_w[blk][BT_PREC_HALF];
+  g.epi = G3_RESID; g.no_resid = 1; g.gelu = 1; g.bias = d.conv_b[blk]; g.ldx = 2 * C;
+  g.conv_C2 = 2 * C; g.conv_T = T; g.conv_F = F / 2; g.x3 = x3; g.status = ws.status;
+  g.x = out_half ? nullptr : out; g.xb = out_half ? (void*)out : nullptr;
+  return g;
+}
+
+// frontend.linear on gemm.hip: fp32 out, optional half shadow xb and row statistics ssq_out of it
+GemmP linear_params(const bt_model_desc& d, int wp, const float* in, float* out, void* xb, float* ssq_out, int B, int T) {
+  GemmP g;
+  memset(&g, 0, sizeof g);
+  g.A = in; g.lda = 1024; g.W = d.lin_w[wp]; g.M = B * T; g.N = d.transformer_dim; g.K = 1024;
+  g.epi = GEMM_EPI_STORE; g.flags = GEMM_F_A_F32 | GEMM_F_BIAS | GEMM_F_OUT_F32;
+  g.bias = d.lin_b; g.out = out; g.ldo = d.transformer_dim; g.xb = xb; g.ssq_out = ssq_out;
+  return g;
+}
+
+// frontend.linear on gemm3 (half A written by the last conv block): ws.xm, its half / hl32 (out_f8: hl8) shadow and the
+// statistics the first main layer reads
+Gemm3P linear3_params(const bt_model_desc& d, const Workspace& ws, int B, int T, bool x3, bool out_f8) {
+  const int D = d.transformer_dim;
+  Gemm3P g;
+  memset(&g, 0, sizeof g);
+  g.A = front_x(ws, 3); g.lda = 1024; g.M = B * T; g.K = 1024; g.W = x3 ? d.lin_w_x3 : d.lin_w[BT_PREC_HALF]; g.N = D;
+  g.epi = G3_RESID; g.no_resid = 1; g.bias = d.lin_b; g.x = ws.xm; g.ldx = D; g.xb = ws.xmb; g.ssq_out = ws.ssq[0];
+  g.x3 = x3 ? 1 | (out_f8 ? G3_X3_OUT_F8 : 0) : 0; g.status = ws.status;
+  return g;
+}
+
+HeadP head_params(const bt_model_desc& d, const float* x, const float* w, int prenorm, float* beat, float* downbeat, int M,
+                  int* status) {
+  HeadP p;
+  p.x = x; p.w = w; p.b0 = d.head_b[0]; p.b1 = d.head_b[1];
+  p.beat = beat; p.downbeat = downbeat; p.M = M; p.D = d.transformer_dim; p.sum_head = d.sum_head; p.prenorm = prenorm;
+  p.status = status;
+  return p;
+}
+
+// row map of an attention launch (AttnP / AttnFragP): F = 1: sequences = chunks of T tokens; F > 1: the time direction of
+// a frontend block, sequences = (b, f) over rows kept in (b, t, f) order
+template <class P>
+void attn_rows(P& a, int B, int T, int F) {
+  a.n_seq = B * F; a.L = T; a.o_div = F; a.o_outer = (long)T * F; a.o_inner = F > 1 ? 1 : 0; a.o_tok = F;
+}
+
+// ---- the route: which kernel runs each step of a forward ---------------------------------------------------------------
+// How a bt_pair_weights runs outside the fragment-major main layers (frontend halves, generic main layers, units)
+struct PairRoute {
+  bool ff_fused;   // feed-forward half on fused.hip (else FF1 + FF2 on gemm.hip)
+  bool outff;      // fused2.hip: the whole frequency half; the time half's out-projection + FF
+  bool split;      // x3: the fused2.hip kernels on (hi, lo) weight streams (else their fp32 form)
+  bool time_frag;  // time half: QKV on qkv_front.hip + attention on attn2.hip (else QKV gemm + attn.hip flash)
+};
+
+// A main layer on gemm3 + attn2 (half or x3).  The hl8 flags (x3, BT_OPT_X3_GEMM_FP8) name the operands that travel in
+// that form (gemm3.hip X3 = 2).
+struct FragLayer {
+  bool qkv8;   // QKV reads the shadow of x in hl8 (written so by frontend.linear or the previous layer's FF2)
+  bool out8;   // the attention writes hl8 rows, the out-projection reads them
+  bool ff8;    // FF1 / FF2 on hl8: the out-projection's shadow and FF1's hidden activation are hl8
+  bool next8;  // FF2 leaves the shadow in hl8 for the next layer's QKV
+  bool tail;   // half: out-projection + FF1 + FF2 in one tail.hip launch
+};
+
+enum { LAYERS_GENERIC, LAYERS_FRAG_HALF, LAYERS_FRAG_X3 };
+
+struct Route {
+  bool x3;                      // BT_PREC_F32X3
+  int fp;                       // fused kernels' precision = slot of the [prec] weights (BT_PREC_F32 under x3)
+  int gp, wp;                   // plain GEMMs and attn.hip: launch precision / weight slot (x3: BT_PREC_F32X3 / [hi | lo] half)
+  int x3_attn, x3_attn_front;   // AttnFragP.x3 of the main layers' / the frontend's attention (0 outside x3)
+  bool half_shadow;             // the main residual stream has a half shadow in ws.xmb
+  int layers;                   // LAYERS_*
+  struct Block { PairRoute freq, time; bool conv3; } blk[3];
+  bool lin3, lin_f8;            // frontend.linear on gemm3; it leaves the shadow in hl8
+  struct Layer { PairRoute pair; FragLayer frag; } layer[BT_MAX_LAYERS];
+};
+
+// The one place that looks at weight pointers, *_supported() predicates, shapes and engine options (no HIP calls).
+// prec: the forward's (bt_forward_unit: BT_PREC_F32 or BT_PREC_HALF); first: the stage the forward enters at.
+// Arithmetic: exact, half or x3 (fp32 activations, hi + lo operands on the fp16 matrix cores).
+// Pair halves:  ff_fused: dim <= 128 and w_ff_frag.  outff: ff_fused, w_outff_frag and w_attnff_frag; the frequency half
+//   has no other form (pack.py always supplies them for the frontend): without them it is an error.  split: x3,
+//   w_outff_frag_x3 and w_attnff_frag_x3.  time_frag: half with ff_fused and w_qkv_frag, or x3 with outff, split and
+//   w_qkv_frag_x3; its attention's fp32 output feeds outff, or else the out-projection gemm + fused FF.
+// Main layers:  frag x3: x3, D >= 128, D % 128 == 0, B T ff_mult D * 4 < 2^31 and w_*_x3 in every layer; hl8 operands
+//   where BT_OPT_X3_GEMM_FP8 asks (1: FF, 2: also out-projection and QKV) and the w_*_f8 exist -- QKV only behind a
+//   producer that writes hl8: frontend.linear on gemm3, or an FF2 whose own layer has w_ff2_f8.  frag half: half, D >= 128,
+//   D % 128 == 0, B T ff_mult D * 2 < 2^31; tail when w_tail_frag and layer_tail_supported.  generic: otherwise; it
+//   reads half_shadow (half, D >= 128, D % 64 == 0: the shadow is maintained by the gemm2 / gemm3 epilogues only).
+// Frontend conv:  conv3 (gemm3): partial transformers, 2 C >= 128 (the first conv, N = 64, only pays 4 us for the 12 us
+//   its shadow write costs), main layers on frag half, or frag x3 with the time half's split; the time half's outff and
+//   gemm3_supported.  It reads the shadow of x (half, or hl32 from the (hi, lo) kernel) that the time half's outff kernel
+//   writes into ws.hid, and that kernel writes it exactly when conv3 holds.  Else gemm.hip; the last block's output is
+//   half when lin3 (same rounding point as the fp32 -> half conversion of linear's A operand, half the bytes both ways).
+// frontend.linear:  lin3 (gemm3): frag half, or frag x3 with lin_w_x3 and the last conv on gemm3 (only that form writes
+//   the hl32 planes lin3 reads); gemm3_supported.  Else gemm.hip (+ the hl32 shadow pass under frag x3).
+// Attention (x3): 4 = launch_attn_frag picks the 64-key kernel or two query blocks per wave on the hand-scheduled key
+//   loop; + BT_X3_P16 in the main layers when BT_OPT_X3_ATTN_P16 is 1 or 2, in the frontend when it is >= 2.
+Route plan_route(const bt_engine& e, int B, int T, int prec, int first, const Workspace& ws) {
+  const bt_model_desc& d = e.d;
+  const int D = d.transformer_dim;
+  Route r;
+  r.x3 = prec == BT_PREC_F32X3;
+  r.fp = r.x3 ? BT_PREC_F32 : prec;
+  r.gp = prec;
+  r.wp = r.x3 ? BT_PREC_HALF : prec;
+  r.x3_attn = r.x3 ? 4 | ((e.x3_attn_p16 == 1 || e.x3_attn_p16 == 2) ? BT_X3_P16 : 0) : 0;   // (3: the frontend only -- a soak variant)
+  r.x3_attn_front = r.x3 ? 4 | (e.x3_attn_p16 >= 2 ? BT_X3_P16 : 0) : 0;
+  auto pair = [&](const bt_pair_weights& w) {
+    PairRoute p;
+    p.ff_fused = w.dim <= 128 && w.w_ff_frag[r.fp];
+    p.outff = p.ff_fused && w.w_outff_frag[r.fp] && w.w_attnff_frag[r.fp];
+    p.split = r.x3 && w.w_outff_frag_x3 && w.w_attnff_frag_x3;
+    p.time_frag = r.x3 ? p.outff && p.split && w.w_qkv_frag_x3 : p.ff_fused && r.fp == BT_PREC_HALF && w.w_qkv_frag;
+    return p;
+  };
+
+  r.half_shadow = prec == BT_PREC_HALF && D >= 128 && D % 64 == 0;
+  const long wide = (long)B * T * d.ff_mult * D;   // (elements of the widest activation: 32-bit byte offsets)
+  bool frag_x3 = r.x3 && D >= 128 && D % 128 == 0 && wide * 4 < 0x7fffffffL;
+  for (int l = 0; frag_x3 && l < d.n_layers; ++l)
+    frag_x3 = d.layers[l].w_qkvg_x3 && d.layers[l].w_out_x3 && d.layers[l].w_ff1_x3 && d.layers[l].w_ff2_x3;
+  const bool frag_half = r.half_shadow && D % 128 == 0 && wide * 2 < 0x7fffffffL;
+  r.layers = frag_x3 ? LAYERS_FRAG_X3 : frag_half ? LAYERS_FRAG_HALF : LAYERS_GENERIC;
+
+  const bool lin3_fits = (frag_half || (frag_x3 && d.lin_w_x3)) && gemm3_supported(linear3_params(d, ws, B, T, frag_x3, false));
+  for (int blk = 0; blk < 3; ++blk) {
+    Route::Block& rb = r.blk[blk];
+    rb.freq = pair(d.front[blk][0]);
+    rb.time = pair(d.front[blk][1]);
+    const Gemm3P cg = conv3_params(d, ws, blk, B, T, frag_x3, blk == 2 && lin3_fits);
+    rb.conv3 = d.partial_transformers && rb.time.outff && (frag_x3 ? rb.time.split : frag_half) && cg.N >= 128 && cg.W &&
+               gemm3_supported(cg);
+  }
+  r.lin3 = lin3_fits && (!frag_x3 || r.blk[2].conv3);
+  r.lin_f8 = r.lin3 && frag_x3 && e.x3_gemm_fp8 >= 2 && d.n_layers > 0 && d.layers[0].w_qkvg_f8;
+
+  for (int l = 0; l < d.n_layers; ++l) {
+    const bt_pair_weights& w = d.layers[l];
+    FragLayer& f = r.layer[l].frag;
+    r.layer[l].pair = pair(w);
+    f.qkv8 = l == 0 ? first == 0 && r.lin_f8 : r.layer[l - 1].frag.next8;
+    f.out8 = frag_x3 && e.x3_gemm_fp8 >= 2 && w.w_out_f8;
+    f.ff8 = frag_x3 && e.x3_gemm_fp8 >= 1 && w.w_ff1_f8 && w.w_ff2_f8;
+    f.next8 = frag_x3 && e.x3_gemm_fp8 >= 2 && l + 1 < d.n_layers && d.layers[l + 1].w_qkvg_f8 && w.w_ff2_f8;
+    f.tail = frag_half && w.w_tail_frag && layer_tail_supported(D, d.ff_mult * D);
+  }
+  return r;
+}
+
 #define CHECK_RC(what)                                                         \
   if (_rc != 0) {                                                              \
     char buf[160];                                                             \
@@ -131,30 +305,157 @@ Workspace carve(char* base, int B, int T, int D, int ff_mult, int prec) {
 #define LAUNCH_CAT(cat, st, expr, what) \
   do { int _rc; { prof::Scope _ps(pf, cat, st); _rc = (expr); } CHECK_RC(what) } while (0)
 
-// mode 0: main transformer (sequences = chunks, tokens = frames)
-// mode 1: frequency direction (sequences = (b,t), tokens = f)      -- attnff_fused_kernel only
-// mode 2: time direction      (sequences = (b,f), tokens = t)      -- rows permuted around attn_flash
-// Main transformer layer in BT_PREC_HALF on the gemm3 / attn2 kernels.  ws.ssq[0] holds the partial row sums of
-// squares of x on entry and on exit (written by the producer of x: frontend.linear or the previous FF2), ws.ssq[1]
-// those of x after the attention half.
-int run_layer_half(prof::State* pf, const bt_pair_weights& pw, const float* rope, const Workspace& ws, int B, int T,
-                   int ff_mult, hipStream_t s) {
+// ---- enqueue: launches in the order and form the route gives -------------------------------------------------------------
+// The pair halves below work on the residual stream x of M = B T F rows of C = pw.dim; xs: its half shadow (main layers
+// with Route::half_shadow) or null.
+
+int check_rows(long M) {
+  return M > 0x7fffffffL ? bt_set_error(BT_ERR_ARG, "batch too large for one forward call") : BT_OK;
+}
+
+// x += to_out(ws.ao)  (gemm.hip)
+int out_proj(prof::State* pf, const bt_pair_weights& pw, const Route& r, float* x, void* xs, const Workspace& ws, long M,
+             hipStream_t s) {
+  const int C = pw.dim;
+  GemmP g;
+  memset(&g, 0, sizeof g);
+  g.A = ws.ao; g.lda = C; g.W = pw.w_out[r.wp]; g.M = (int)M; g.N = C; g.K = C;
+  g.epi = GEMM_EPI_RESID; g.flags = 0; g.x = x; g.ldx = C; g.xb = xs;
+  LAUNCH_CAT(CAT_OUT, s, launch_gemm(g, r.gp, s), "out-proj gemm");
+  return BT_OK;
+}
+
+// q|k|v|gates = RMSNorm(x) . W^T, RoPE, sigmoid (gemm.hip); ws.ao = attention (attn.hip flash).  Row map: attn_rows
+int qkv_attn(prof::State* pf, const bt_pair_weights& pw, const Route& r, const float* rope, float* x, void* xs,
+             const Workspace& ws, int B, int T, int F, hipStream_t s) {
+  const int C = pw.dim, H = pw.heads;
+  GemmP g;
+  memset(&g, 0, sizeof g);
+  g.A = xs ? xs : (const void*)x; g.lda = C; g.W = pw.w_qkvg[r.wp]; g.M = B * T * F; g.N = 3 * C + H; g.K = C;
+  g.epi = GEMM_EPI_QKV; g.flags = GEMM_F_RMS | (xs ? 0 : GEMM_F_A_F32) | (F > 1 ? GEMM_F_ROWMAP : 0);
+  g.bias = pw.b_gates; g.out = ws.qkv; g.ldo = 3 * C; g.gates = ws.gates; g.inner = C; g.heads = H;
+  g.rope = rope; g.map_T = T; g.map_F = F; g.pdiv = F; g.pmod = T;
+  LAUNCH_CAT(CAT_QKV, s, launch_gemm(g, r.gp, s), "qkv gemm");
+  AttnP a;
+  memset(&a, 0, sizeof a);
+  a.qkv = ws.qkv; a.ld = 3 * C; a.gates = ws.gates; a.out = ws.ao; a.heads = H; a.inner = C;
+  attn_rows(a, B, T, F);
+  LAUNCH_CAT(CAT_ATTN_FLASH, s, launch_attn_flash(a, r.gp, s), F > 1 ? "time attention" : "attention");
+  return BT_OK;
+}
+
+// x += FeedForward(x): fused.hip, or FF1 + FF2 on gemm.hip (hidden width ff_mult C)
+int ff_half(prof::State* pf, const bt_pair_weights& pw, const PairRoute& pr, const Route& r, float* x, void* xs,
+            const Workspace& ws, long M, int ff_mult, hipStream_t s) {
+  const int C = pw.dim, HID = ff_mult * C;
+  if (pr.ff_fused) {
+    FusedFFP ff;
+    ff.x = x; ff.M = M; ff.C = C; ff.wfrag = pw.w_ff_frag[r.fp]; ff.b1 = pw.b_ff1; ff.b2 = pw.b_ff2; ff.xb = xs;
+    LAUNCH_CAT(CAT_FF_FUSED, s, launch_ff_fused(ff, r.fp, s), "fused feed-forward");
+    return BT_OK;
+  }
+  // h = gelu(RMSNorm(x) . W1^T + b1);  x += h . W2^T + b2
+  GemmP g;
+  memset(&g, 0, sizeof g);
+  g.A = xs ? xs : (const void*)x; g.lda = C; g.W = pw.w_ff1[r.wp]; g.M = (int)M; g.N = HID; g.K = C;
+  g.epi = GEMM_EPI_STORE; g.flags = GEMM_F_RMS | (xs ? 0 : GEMM_F_A_F32) | GEMM_F_BIAS | GEMM_F_GELU;
+  g.bias = pw.b_ff1; g.out = ws.hid; g.ldo = HID;
+  LAUNCH_CAT(CAT_FF1, s, launch_gemm(g, r.gp, s), "ff1 gemm");
+  memset(&g, 0, sizeof g);
+  g.A = ws.hid; g.lda = HID; g.W = pw.w_ff2[r.wp]; g.M = (int)M; g.N = C; g.K = HID;
+  g.epi = GEMM_EPI_RESID; g.flags = GEMM_F_BIAS; g.bias = pw.b_ff2; g.x = x; g.ldx = C; g.xb = xs;
+  LAUNCH_CAT(CAT_FF2, s, launch_gemm(g, r.gp, s), "ff2 gemm");
+  return BT_OK;
+}
+
+// main layer or leaf on the generic kernels (sequences = chunks): the attention half and / or the feed-forward half
+int generic_layer(prof::State* pf, const bt_pair_weights& pw, const PairRoute& pr, const Route& r, const float* rope, float* x,
+                  void* xs, const Workspace& ws, int B, int T, int ff_mult, bool attn, bool ff, hipStream_t s) {
+  const long M = (long)B * T;
+  if (int rc = check_rows(M)) return rc;
+  if (attn) {
+    if (int rc = qkv_attn(pf, pw, r, rope, x, xs, ws, B, T, 1, s)) return rc;
+    if (int rc = out_proj(pf, pw, r, x, xs, ws, M, s)) return rc;
+  }
+  return ff ? ff_half(pf, pw, pr, r, x, xs, ws, M, ff_mult, s) : BT_OK;
+}
+
+// frequency-direction half of a frontend block (sequences = (b, t), tokens = f): attention + FF in one register-resident
+// kernel
+int freq_half(prof::State* pf, const bt_pair_weights& pw, const PairRoute& pr, const Route& r, const float* rope, float* x,
+              int B, int T, int F, hipStream_t s) {
+  const long M = (long)B * T * F;
+  if (int rc = check_rows(M)) return rc;
+  if (!pr.outff) return bt_set_error(BT_ERR_ARG, "frequency-direction half needs bt_pair_weights.w_attnff_frag");
+  FusedAttnFFP f;
+  f.x = x; f.M = M; f.C = pw.dim; f.b_gates = pw.b_gates; f.rope = rope;
+  f.wfrag = pr.split ? pw.w_attnff_frag_x3 : pw.w_attnff_frag[r.fp]; f.b1 = pw.b_ff1; f.b2 = pw.b_ff2;
+  LAUNCH_CAT(CAT_ATTN_FREQ_FUSED, s, launch_attnff_fused(f, pr.split ? BT_PREC_F32X3 : r.fp, s),
+             "fused frequency attention + feed-forward");
+  return BT_OK;
+}
+
+// time-direction half of a frontend block (sequences = (b, f), tokens = t).  shadow: where the out-projection + FF kernel
+// writes the half / hl32 shadow of the new x (the A operand of the block's conv on gemm3), or null
+int time_half(prof::State* pf, const bt_pair_weights& pw, const PairRoute& pr, const Route& r, const float* rope, float* x,
+              const Workspace& ws, int B, int T, int F, void* shadow, hipStream_t s) {
+  const long M = (long)B * T * F;
+  if (int rc = check_rows(M)) return rc;
+  if (pr.time_frag) {   // fragment-major QKV straight from the projection (x3: hi + lo blocks), flash attention on it
+    QkvFrontP qp;
+    memset(&qp, 0, sizeof qp);
+    qp.x = x; qp.B = B; qp.T = T; qp.F = F; qp.C = pw.dim; qp.wfrag = r.x3 ? pw.w_qkv_frag_x3 : pw.w_qkv_frag;
+    qp.b_gates = pw.b_gates; qp.rope = rope;
+    qp.q = ws.qf; qp.k = ws.kf; qp.v = ws.vf; qp.gates = ws.gates_h; qp.nbp = ws.nbp;
+    qp.x3 = r.x3; qp.status = ws.status;
+    LAUNCH_CAT(CAT_QKV, s, launch_qkv_front(qp, s), "frontend qkv projection");
+    AttnFragP a;
+    memset(&a, 0, sizeof a);
+    a.q = ws.qf; a.k = ws.kf; a.v = ws.vf; a.gates = ws.gates_h; a.out = ws.ao; a.heads = pw.heads; a.inner = pw.dim;
+    a.nbp = ws.nbp; attn_rows(a, B, T, F);
+    a.x3 = r.x3_attn_front; a.out_f32 = 1; a.status = ws.status; a.fix_mask = ws.fix_mask;
+    LAUNCH_CAT(CAT_ATTN_FLASH, s, launch_attn_frag(a, s), "time attention");
+  } else if (int rc = qkv_attn(pf, pw, r, rope, x, nullptr, ws, B, T, F, s)) {
+    return rc;
+  }
+  if (pr.outff) {   // x += to_out(ws.ao); x += FF(x) in one launch
+    FusedOutFFP f;
+    f.x = x; f.M = M; f.C = pw.dim; f.ao = ws.ao; f.wfrag = pr.split ? pw.w_outff_frag_x3 : pw.w_outff_frag[r.fp];
+    f.b1 = pw.b_ff1; f.b2 = pw.b_ff2; f.xb = shadow; f.abl = 0;
+    LAUNCH_CAT(CAT_FF_FUSED, s, launch_outff_fused(f, pr.split ? BT_PREC_F32X3 : r.fp, s), "fused out-projection + feed-forward");
+    return BT_OK;
+  }
+  if (int rc = out_proj(pf, pw, r, x, nullptr, ws, M, s)) return rc;
+  return ff_half(pf, pw, pr, r, x, nullptr, ws, M, 4, s);
+}
+
+// Main transformer layer on the gemm3 / attn2 kernels, half or hi + lo (gemm3.hip X3, attn2.hip attn_frag_x3_kernel: the
+// fp32 residual stream ws.xm is shadowed by hl32 planes in ws.xmb, the attention output and the hidden activation travel
+// as hl32 planes, q / k / v as 4 KB [hi | lo] fragment blocks; operands in hl8 where the route says so).  ws.ssq[0] holds
+// the partial row sums of squares of x on entry and on exit (written by the producer of x: frontend.linear or the previous
+// FF2), ws.ssq[1] those of x after the attention half.
+int frag_layer(prof::State* pf, const bt_pair_weights& pw, const FragLayer& f, const Route& r, const float* rope,
+               const Workspace& ws, int B, int T, int ff_mult, hipStream_t s) {
   const int D = pw.dim, H = pw.heads, HID = ff_mult * D;
   const int M = B * T;
   const int parts = D / 64;
+  int* status = r.x3 ? ws.status : nullptr;
+  // weight of a GEMM: half, hl32 or hl8
+  auto w = [&](const void* const* half, const void* hl32, const void* hl8, bool f8) { return !r.x3 ? half[BT_PREC_HALF] : f8 ? hl8 : hl32; };
   Gemm3P g;
   memset(&g, 0, sizeof g);
-  g.A = ws.xmb; g.lda = D; g.M = M; g.K = D; g.W = pw.w_qkvg[BT_PREC_HALF]; g.N = 3 * D + H; g.epi = G3_QKV;
-  g.ssq_in = ws.ssq[0]; g.ssq_parts = parts;
+  g.A = ws.xmb; g.lda = D; g.M = M; g.K = D; g.W = w(pw.w_qkvg, pw.w_qkvg_x3, pw.w_qkvg_f8, f.qkv8); g.N = 3 * D + H; g.epi = G3_QKV;
+  g.ssq_in = ws.ssq[0]; g.ssq_parts = parts; g.x3 = r.x3 | (f.qkv8 ? G3_X3_F8 : 0); g.status = status;
   g.n_seq = B; g.L = T; g.nblk = (T + 31) / 32; g.nbp = ws.nbp; g.heads = H; g.inner = D; g.rope = rope;
   g.qf = ws.qf; g.kf = ws.kf; g.vf = ws.vf; g.gates = ws.gates_h; g.b_gates = pw.b_gates;
-  LAUNCH_CAT(CAT_QKV, s, launch_gemm3(g, s), "qkv gemm");
+  LAUNCH_CAT(CAT_QKV, s, launch_gemm3(g, s), r.x3 ? "qkv gemm (hi + lo)" : "qkv gemm");
   AttnFragP a;
   memset(&a, 0, sizeof a);
-  a.q = ws.qf; a.k = ws.kf; a.v = ws.vf; a.gates = ws.gates_h; a.out = ws.ao; a.n_seq = B; a.L = T; a.heads = H;
-  a.inner = D; a.nbp = ws.nbp; a.o_div = 1; a.o_outer = T; a.o_inner = 0; a.o_tok = 1;
-  LAUNCH_CAT(CAT_ATTN_FLASH, s, launch_attn_frag(a, s), "attention");
-  if (pw.w_tail_frag && layer_tail_supported(D, HID)) {
+  a.q = ws.qf; a.k = ws.kf; a.v = ws.vf; a.gates = ws.gates_h; a.out = ws.ao; a.heads = H; a.inner = D; a.nbp = ws.nbp;
+  attn_rows(a, B, T, 1);
+  a.x3 = r.x3_attn; a.out_f32 = f.out8 ? 2 : 0; a.status = status; a.fix_mask = ws.fix_mask;
+  LAUNCH_CAT(CAT_ATTN_FLASH, s, launch_attn_frag(a, s), r.x3 ? "attention (hi + lo)" : "attention");
+  if (f.tail) {
     // out-projection + FF1 + FF2 in ONE launch: x, its half shadow and the statistics of the new x written once
     LayerTailP t;
     t.x = ws.xm; t.M = M; t.C = D; t.hidden = HID; t.ao = ws.ao; t.wfrag = pw.w_tail_frag; t.b1 = pw.b_ff1; t.b2 = pw.b_ff2;
@@ -163,179 +464,55 @@ int run_layer_half(prof::State* pf, const bt_pair_weights& pw, const float* rope
     return BT_OK;
   }
   memset(&g, 0, sizeof g);
-  g.A = ws.ao; g.lda = D; g.M = M; g.K = D; g.W = pw.w_out[BT_PREC_HALF]; g.N = D; g.epi = G3_RESID;
+  g.A = ws.ao; g.lda = D; g.M = M; g.K = D; g.W = w(pw.w_out, pw.w_out_x3, pw.w_out_f8, f.out8); g.N = D; g.epi = G3_RESID;
+  g.x3 = r.x3 | (f.out8 ? G3_X3_F8 : 0) | (f.ff8 ? G3_X3_OUT_F8 : 0); g.status = status;
   g.x = ws.xm; g.ldx = D; g.xb = ws.xmb; g.ssq_out = ws.ssq[1];
-  LAUNCH_CAT(CAT_OUT, s, launch_gemm3(g, s), "out-proj gemm");
+  LAUNCH_CAT(CAT_OUT, s, launch_gemm3(g, s), r.x3 ? "out-proj gemm (hi + lo)" : "out-proj gemm");
   memset(&g, 0, sizeof g);
-  g.A = ws.xmb; g.lda = D; g.M = M; g.K = D; g.W = pw.w_ff1[BT_PREC_HALF]; g.N = HID; g.epi = G3_FF1;
+  g.A = ws.xmb; g.lda = D; g.M = M; g.K = D; g.W = w(pw.w_ff1, pw.w_ff1_x3, pw.w_ff1_f8, f.ff8); g.N = HID; g.epi = G3_FF1;
+  g.x3 = r.x3 | (f.ff8 ? G3_X3_F8 | G3_X3_OUT_F8 : 0); g.status = status;
   g.bias = pw.b_ff1; g.ssq_in = ws.ssq[1]; g.ssq_parts = parts; g.out = ws.hid; g.ldo = HID;
-  LAUNCH_CAT(CAT_FF1, s, launch_gemm3(g, s), "ff1 gemm");
+  LAUNCH_CAT(CAT_FF1, s, launch_gemm3(g, s), r.x3 ? "ff1 gemm (hi + lo)" : "ff1 gemm");
   memset(&g, 0, sizeof g);
-  g.A = ws.hid; g.lda = HID; g.M = M; g.K = HID; g.W = pw.w_ff2[BT_PREC_HALF]; g.N = D; g.epi = G3_RESID;
+  g.A = ws.hid; g.lda = HID; g.M = M; g.K = HID; g.W = w(pw.w_ff2, pw.w_ff2_x3, pw.w_ff2_f8, f.ff8); g.N = D; g.epi = G3_RESID;
+  g.x3 = r.x3 | (f.ff8 ? G3_X3_F8 : 0) | (f.next8 ? G3_X3_OUT_F8 : 0); g.status = status;
   g.bias = pw.b_ff2; g.x = ws.xm; g.ldx = D; g.xb = ws.xmb; g.ssq_out = ws.ssq[0];
-  LAUNCH_CAT(CAT_FF2, s, launch_gemm3(g, s), "ff2 gemm");
+  LAUNCH_CAT(CAT_FF2, s, launch_gemm3(g, s), r.x3 ? "ff2 gemm (hi + lo)" : "ff2 gemm");
   return BT_OK;
 }
 
-// Main transformer layer in BT_PREC_F32X3 on the same kernels with hi + lo operands (gemm3.hip X3, attn2.hip
-// attn_frag_x3_kernel): the fp32 residual stream ws.xm is shadowed by hl32 planes (ws.xmb), the attention output and
-// the hidden activation travel as hl32 planes, q / k / v as 4 KB [hi | lo] fragment blocks; statistics as in the half layer.
-// xmb_f8: the shadow of the residual stream this layer finds is hl8 (BT_OPT_X3_GEMM_FP8 = 2: written by the previous layer's FF2 or
-// by frontend.linear); next_f8: this layer's FF2 leaves it in that form for the next one
-int run_layer_x3(prof::State* pf, const bt_pair_weights& pw, const float* rope, const Workspace& ws, int B, int T,
-                 int ff_mult, hipStream_t s, bool xmb_f8 = false, bool next_f8 = false) {
-  const int D = pw.dim, H = pw.heads, HID = ff_mult * D;
-  const int M = B * T;
-  const int parts = D / 64;
-  Gemm3P g;
-  memset(&g, 0, sizeof g);
-  g.A = ws.xmb; g.lda = D; g.M = M; g.K = D; g.W = xmb_f8 ? pw.w_qkvg_f8 : pw.w_qkvg_x3; g.N = 3 * D + H; g.epi = G3_QKV;
-  g.ssq_in = ws.ssq[0]; g.ssq_parts = parts; g.x3 = 1 | (xmb_f8 ? G3_X3_F8 : 0); g.status = ws.status;
-  g.n_seq = B; g.L = T; g.nblk = (T + 31) / 32; g.nbp = ws.nbp; g.heads = H; g.inner = D; g.rope = rope;
-  g.qf = ws.qf; g.kf = ws.kf; g.vf = ws.vf; g.gates = ws.gates_h; g.b_gates = pw.b_gates;
-  LAUNCH_CAT(CAT_QKV, s, launch_gemm3(g, s), "qkv gemm (hi + lo)");
-  AttnFragP a;
-  memset(&a, 0, sizeof a);
-  a.q = ws.qf; a.k = ws.kf; a.v = ws.vf; a.gates = ws.gates_h; a.out = ws.ao; a.n_seq = B; a.L = T; a.heads = H;
-  a.inner = D; a.nbp = ws.nbp; a.o_div = 1; a.o_outer = T; a.o_inner = 0; a.o_tok = 1;
-  // BT_OPT_X3_GEMM_FP8 = 2: out-projection (and QKV) on hl8 operands as well -- the attention writes its rows in that form
-  const bool out8 = ws.x3_gemm_fp8 >= 2 && pw.w_out_f8;
-  a.x3 = ws.x3_attn; a.out_f32 = out8 ? 2 : 0; a.status = ws.status; a.fix_mask = ws.fix_mask;   // (which x3 attention kernel / arithmetic: attn2.hip launch_attn_frag)
-  LAUNCH_CAT(CAT_ATTN_FLASH, s, launch_attn_frag(a, s), "attention (hi + lo)");
-  // BT_OPT_X3_GEMM_FP8 >= 1: the feed-forward GEMMs on hl8 operands (fp8 cross terms): the out-projection leaves its shadow of
-  // the residual stream in that form, FF1 its hidden activation; FF2's shadow feeds the next layer's QKV and stays hl32
-  const bool ff8 = ws.x3_gemm_fp8 >= 1 && pw.w_ff1_f8 && pw.w_ff2_f8;
-  memset(&g, 0, sizeof g);
-  g.A = ws.ao; g.lda = D; g.M = M; g.K = D; g.W = out8 ? pw.w_out_f8 : pw.w_out_x3; g.N = D; g.epi = G3_RESID; g.status = ws.status;
-  g.x3 = 1 | (out8 ? G3_X3_F8 : 0) | (ff8 ? G3_X3_OUT_F8 : 0);
-  g.x = ws.xm; g.ldx = D; g.xb = ws.xmb; g.ssq_out = ws.ssq[1];
-  LAUNCH_CAT(CAT_OUT, s, launch_gemm3(g, s), "out-proj gemm (hi + lo)");
-  memset(&g, 0, sizeof g);
-  g.A = ws.xmb; g.lda = D; g.M = M; g.K = D; g.W = ff8 ? pw.w_ff1_f8 : pw.w_ff1_x3; g.N = HID; g.epi = G3_FF1; g.status = ws.status;
-  g.x3 = 1 | (ff8 ? G3_X3_F8 | G3_X3_OUT_F8 : 0);
-  g.bias = pw.b_ff1; g.ssq_in = ws.ssq[1]; g.ssq_parts = parts; g.out = ws.hid; g.ldo = HID;
-  LAUNCH_CAT(CAT_FF1, s, launch_gemm3(g, s), "ff1 gemm (hi + lo)");
-  memset(&g, 0, sizeof g);
-  g.A = ws.hid; g.lda = HID; g.M = M; g.K = HID; g.W = ff8 ? pw.w_ff2_f8 : pw.w_ff2_x3; g.N = D; g.epi = G3_RESID; g.status = ws.status;
-  g.x3 = 1 | (ff8 ? G3_X3_F8 : 0) | (next_f8 ? G3_X3_OUT_F8 : 0);
-  g.bias = pw.b_ff2; g.x = ws.xm; g.ldx = D; g.xb = ws.xmb; g.ssq_out = ws.ssq[0];
-  LAUNCH_CAT(CAT_FF2, s, launch_gemm3(g, s), "ff2 gemm (hi + lo)");
-  return BT_OK;
-}
-
-// half shadow of the residual stream written by the fused out-projection + FF kernel (time-direction half; A operand of
-// the following frontend conv on gemm3)
-inline bool pair_fused2_ok(const bt_pair_weights& pw, int prec) {
-  return pw.dim <= 128 && pw.w_ff_frag[prec] && pw.w_outff_frag[prec] && pw.w_attnff_frag[prec];
-}
-
-// part (mode 0 only; bt_forward_unit): 0 = the whole pair, 1 = the attention half (x += Attention(x)) only, 2 = the
-// feed-forward half (x += FeedForward(x)) only
-int run_pair(prof::State* pf, const bt_pair_weights& pw, const float* rope, float* x, void* xshadow, const Workspace& ws,
-             int B, int T, int F, int mode, int prec, hipStream_t s, void* out_shadow = nullptr, int ff_mult = 4,
-             bool x3 = false, int part = 0) {
-  const int C = pw.dim, H = pw.heads, HID = ff_mult * C;
-  // BT_PREC_F32X3: prec is BT_PREC_F32 for everything but the plain GEMMs, which take the [hi | lo] half weights
-  const int gp = x3 ? BT_PREC_F32X3 : prec, wp = x3 ? BT_PREC_HALF : prec;
-  const long M = (long)B * T * F;
-  if (M > 0x7fffffffL) return bt_set_error(BT_ERR_ARG, "batch too large for one forward call");
-  GemmP g;
-  // main layers in half mode read the half shadow of x (half the operand bytes, no conversion in the k-loop)
-  const bool shadow = xshadow != nullptr && prec == BT_PREC_HALF;
-  const bool fused_ok = C <= 128 && pw.w_ff_frag[prec];
-  const bool fused2_ok = fused_ok && pw.w_outff_frag[prec] && pw.w_attnff_frag[prec];
-  // BT_PREC_F32X3: the register-chained halves on (hi, lo) operands too when their split streams were packed
-  const bool f2x3 = x3 && pw.w_outff_frag_x3 && pw.w_attnff_frag_x3;
-  auto outff = [&]() -> int {  // x += to_out(ws.ao); x += FF(x) in one launch
-    FusedOutFFP f;
-    f.x = x; f.M = M; f.C = C; f.ao = ws.ao; f.wfrag = f2x3 ? pw.w_outff_frag_x3 : pw.w_outff_frag[prec];
-    f.b1 = pw.b_ff1; f.b2 = pw.b_ff2; f.xb = out_shadow; f.abl = 0;
-    LAUNCH_CAT(CAT_FF_FUSED, s, launch_outff_fused(f, f2x3 ? BT_PREC_F32X3 : prec, s), "fused out-projection + feed-forward");
-    return BT_OK;
-  };
-  if (mode == 1 && fused2_ok) {  // whole frequency-direction half (attention + FF) in one register-resident kernel
-    FusedAttnFFP f;
-    f.x = x; f.M = M; f.C = C; f.b_gates = pw.b_gates; f.rope = rope;
-    f.wfrag = f2x3 ? pw.w_attnff_frag_x3 : pw.w_attnff_frag[prec]; f.b1 = pw.b_ff1; f.b2 = pw.b_ff2;
-    LAUNCH_CAT(CAT_ATTN_FREQ_FUSED, s, launch_attnff_fused(f, f2x3 ? BT_PREC_F32X3 : prec, s),
-               "fused frequency attention + feed-forward");
+// stem, the three partial-transformer + conv blocks, frontend.linear: ws.xm (+ shadow and statistics as the layers' route
+// reads them)
+int frontend(prof::State* pf, const bt_model_desc& d, const Route& r, const float* spect, const Workspace& ws, int B, int T,
+             hipStream_t s) {
+  const StemP sp = stem_params(d, spect, front_x(ws, 0), B, T);
+  LAUNCH_CAT(CAT_STEM, s, launch_stem(sp, s), "stem");
+  for (int blk = 0; blk < 3; ++blk) {
+    const Route::Block& rb = r.blk[blk];
+    float* x = front_x(ws, blk);
+    if (d.partial_transformers) {
+      if (int rc = freq_half(pf, d.front[blk][0], rb.freq, r, d.rope, x, B, T, 32 >> blk, s)) return rc;
+      if (int rc = time_half(pf, d.front[blk][1], rb.time, r, d.rope, x, ws, B, T, 32 >> blk, rb.conv3 ? ws.hid : nullptr, s))
+        return rc;
+    }
+    if (rb.conv3) {
+      const Gemm3P g = conv3_params(d, ws, blk, B, T, r.layers == LAYERS_FRAG_X3, blk == 2 && r.lin3);
+      LAUNCH_CAT(CAT_CONV, s, launch_gemm3(g, s), "frontend conv gemm");
+    } else {
+      const GemmP g = conv_params(d, blk, r.wp, x, front_x(ws, blk + 1), B, T, !(blk == 2 && r.lin3));
+      LAUNCH_CAT(CAT_CONV, s, launch_gemm(g, r.gp, s), "frontend conv gemm");
+    }
+  }
+  if (r.lin3) {
+    const Gemm3P g = linear3_params(d, ws, B, T, r.layers == LAYERS_FRAG_X3, r.lin_f8);
+    LAUNCH_CAT(CAT_LINEAR, s, launch_gemm3(g, s), "frontend linear gemm");
     return BT_OK;
   }
-  if (mode == 1)  // (pack.py always supplies the fused-half weight streams for the frontend's pairs)
-    return bt_set_error(BT_ERR_ARG, "frequency-direction half needs bt_pair_weights.w_attnff_frag");
-  // BT_PREC_F32X3 time direction on the fragment-major kernels: hi + lo QKV blocks straight from the projection, the
-  // attention's fp32 output feeds the (hi, lo) out-projection + FF kernel
-  const bool t2x3 = mode == 2 && f2x3 && fused2_ok && pw.w_qkv_frag_x3 && ws.qf;
-  if (part == 2) {
-    // (feed-forward half only: nothing of the attention half runs)
-  } else if (mode == 2 && fused_ok && ((prec == BT_PREC_HALF && pw.w_qkv_frag) || t2x3)) {
-    // time direction: fragment-major QKV straight from the projection, flash attention on it
-    QkvFrontP qp;
-    memset(&qp, 0, sizeof qp);
-    qp.x = x; qp.B = B; qp.T = T; qp.F = F; qp.C = C; qp.wfrag = t2x3 ? pw.w_qkv_frag_x3 : pw.w_qkv_frag;
-    qp.b_gates = pw.b_gates; qp.rope = rope;
-    qp.q = ws.qf; qp.k = ws.kf; qp.v = ws.vf; qp.gates = ws.gates_h; qp.nbp = ws.nbp;
-    qp.x3 = t2x3; qp.status = ws.status;
-    LAUNCH_CAT(CAT_QKV, s, launch_qkv_front(qp, s), "frontend qkv projection");
-    AttnFragP a;
-    memset(&a, 0, sizeof a);
-    a.q = ws.qf; a.k = ws.kf; a.v = ws.vf; a.gates = ws.gates_h; a.out = ws.ao; a.n_seq = B * F; a.L = T; a.heads = H;
-    a.inner = C; a.nbp = ws.nbp; a.o_div = F; a.o_outer = (long)T * F; a.o_inner = 1; a.o_tok = F;
-    a.x3 = t2x3 ? ws.x3_attn_front : 0; a.out_f32 = 1; a.status = ws.status; a.fix_mask = ws.fix_mask;
-    LAUNCH_CAT(CAT_ATTN_FLASH, s, launch_attn_frag(a, s), "time attention");
-    if (fused2_ok) return outff();
-    memset(&g, 0, sizeof g);
-    g.A = ws.ao; g.lda = C; g.W = pw.w_out[wp]; g.M = (int)M; g.N = C; g.K = C;
-    g.epi = GEMM_EPI_RESID; g.flags = 0; g.x = x; g.ldx = C; g.xb = nullptr;
-    LAUNCH_CAT(CAT_OUT, s, launch_gemm(g, gp, s), "out-proj gemm");
-  } else {
-  // ---- q|k|v|gates = RMSNorm(x) . W^T, RoPE, sigmoid ------------------------------------
-  memset(&g, 0, sizeof g);
-  g.A = shadow ? xshadow : (const void*)x; g.lda = C; g.W = pw.w_qkvg[wp]; g.M = (int)M; g.N = 3 * C + H; g.K = C;
-  g.epi = GEMM_EPI_QKV; g.flags = GEMM_F_RMS | (shadow ? 0 : GEMM_F_A_F32) | (mode == 2 ? GEMM_F_ROWMAP : 0);
-  g.bias = pw.b_gates; g.out = ws.qkv; g.ldo = 3 * C; g.gates = ws.gates; g.inner = C; g.heads = H;
-  g.rope = rope; g.map_T = T; g.map_F = F;
-  if (mode == 0) { g.pdiv = 1; g.pmod = T; }
-  else if (mode == 1) { g.pdiv = 1; g.pmod = F; }
-  else { g.pdiv = F; g.pmod = T; }
-  LAUNCH_CAT(CAT_QKV, s, launch_gemm(g, gp, s), "qkv gemm");
-  // ---- attention ------------------------------------------------------------------------
-  AttnP a;
-  memset(&a, 0, sizeof a);
-  a.qkv = ws.qkv; a.ld = 3 * C; a.gates = ws.gates; a.out = ws.ao; a.heads = H; a.inner = C;
-  if (mode == 2) {
-    a.n_seq = B * F; a.L = T; a.o_div = F; a.o_outer = (long)T * F; a.o_inner = 1; a.o_tok = F;
-    LAUNCH_CAT(CAT_ATTN_FLASH, s, launch_attn_flash(a, gp, s), "time attention");
-  } else {
-    a.n_seq = B; a.L = T; a.o_div = 1; a.o_outer = T; a.o_inner = 0; a.o_tok = 1;
-    LAUNCH_CAT(CAT_ATTN_FLASH, s, launch_attn_flash(a, gp, s), "attention");
-  }
-  if (mode == 2 && fused2_ok) return outff();
-  // ---- x += ao . Wout^T -------------------------------------------------------------------
-  memset(&g, 0, sizeof g);
-  g.A = ws.ao; g.lda = C; g.W = pw.w_out[wp]; g.M = (int)M; g.N = C; g.K = C;
-  g.epi = GEMM_EPI_RESID; g.flags = 0; g.x = x; g.ldx = C; g.xb = shadow ? xshadow : nullptr;
-  LAUNCH_CAT(CAT_OUT, s, launch_gemm(g, gp, s), "out-proj gemm");
-  }
-  if (part == 1) return BT_OK;
-  if (fused_ok) {
-    FusedFFP ff;
-    ff.x = x; ff.M = M; ff.C = C; ff.wfrag = pw.w_ff_frag[prec]; ff.b1 = pw.b_ff1; ff.b2 = pw.b_ff2;
-    ff.xb = shadow ? xshadow : nullptr;
-    LAUNCH_CAT(CAT_FF_FUSED, s, launch_ff_fused(ff, prec, s), "fused feed-forward");
-    return BT_OK;
-  }
-  // ---- h = gelu(RMSNorm(x) . W1^T + b1) ------------------------------------------------------
-  memset(&g, 0, sizeof g);
-  g.A = shadow ? xshadow : (const void*)x; g.lda = C; g.W = pw.w_ff1[wp]; g.M = (int)M; g.N = HID; g.K = C;
-  g.epi = GEMM_EPI_STORE; g.flags = GEMM_F_RMS | (shadow ? 0 : GEMM_F_A_F32) | GEMM_F_BIAS | GEMM_F_GELU;
-  g.bias = pw.b_ff1; g.out = ws.hid; g.ldo = HID;
-  LAUNCH_CAT(CAT_FF1, s, launch_gemm(g, gp, s), "ff1 gemm");
-  // ---- x += h . W2^T + b2 ---------------------------------------------------------------------
-  memset(&g, 0, sizeof g);
-  g.A = ws.hid; g.lda = HID; g.W = pw.w_ff2[wp]; g.M = (int)M; g.N = C; g.K = HID;
-  g.epi = GEMM_EPI_RESID; g.flags = GEMM_F_BIAS; g.bias = pw.b_ff2; g.x = x; g.ldx = C; g.xb = shadow ? xshadow : nullptr;
-  LAUNCH_CAT(CAT_FF2, s, launch_gemm(g, gp, s), "ff2 gemm");
+  const GemmP g = linear_params(d, r.wp, front_x(ws, 3), ws.xm, r.half_shadow ? ws.xmb : nullptr,
+                                r.layers == LAYERS_FRAG_HALF ? ws.ssq[0] : nullptr, B, T);
+  LAUNCH_CAT(CAT_LINEAR, s, launch_gemm(g, r.gp, s), "frontend linear gemm");
+  if (r.layers == LAYERS_FRAG_X3)
+    LAUNCH_CAT(CAT_LINEAR, s, launch_shadow_ssq(ws.xm, ws.xmb, ws.ssq[0], (long)B * T, d.transformer_dim, s, 1), "hl32 shadow of the residual stream");
   return BT_OK;
 }
 
@@ -416,155 +593,55 @@ int bt_forward_stages(bt_engine* e, void* stream, int prec, int first, int last,
   const bt_model_desc& d = e->d;
   prof::State* pf = &e->prof;
   const int D = d.transformer_dim;
-  Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec);
+  const Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec);
   if (ws.total > ws_bytes) return bt_set_error(BT_ERR_WORKSPACE, "workspace too small");
-  ws.x3_attn = BT_X3_ATTN | ((e->x3_attn_p16 == 1 || e->x3_attn_p16 == 2) ? BT_X3_P16 : 0);   // (3: the frontend only -- a soak variant)
-  ws.x3_attn_front = BT_X3_ATTN | (e->x3_attn_p16 >= 2 ? BT_X3_P16 : 0);
-  ws.x3_gemm_fp8 = e->x3_gemm_fp8;
+  if (prec == BT_PREC_F32X3 && BT_HALF_IS_BF16) return bt_set_error(BT_ERR_ARG, "BT_PREC_F32X3 needs an IEEE fp16 build");
+  const Route r = plan_route(*e, B, T, prec, first, ws);
   hipStream_t s = (hipStream_t)stream;
-  const bool x3 = prec == BT_PREC_F32X3;
-  if (x3) {
-    if (BT_HALF_IS_BF16) return bt_set_error(BT_ERR_ARG, "BT_PREC_F32X3 needs an IEEE fp16 build");
-    prec = BT_PREC_F32;
-    // range flag of this forward (first word of the workspace): cleared here; bit 0 is ORed by the gemm3 / attention / QKV
-    // kernels when a value beyond the fp16 range goes through a split, bit 1 by whatever ends the call (head, final norm,
-    // stage exit) when its output is not finite -- which is where an overflow in any other splitting kernel ends up
-    LAUNCH(launch_clear_words(ws.status, 1, s), "clearing the range flag");
-  }
-  const int gp = x3 ? BT_PREC_F32X3 : prec, wp = x3 ? BT_PREC_HALF : prec;   // plain GEMMs: launch / weight precision
-
-  // the half shadow of the main residual stream is maintained by the gemm2 / gemm3 epilogues only
-  const bool use_shadow = prec == BT_PREC_HALF && D >= 128 && D % 64 == 0;
-  // main layers on gemm3 + fragment-major attention (needs q | k | v column blocks that are whole 128-tiles)
-  const bool fast_layers = use_shadow && D % 128 == 0 && (long)B * T * d.ff_mult * D * 2 < 0x7fffffffL;
-  // BT_PREC_F32X3 on the same kernels (hl32 operands): needs the hl32 weights of every layer
-  bool fast_x3 = x3 && D >= 128 && D % 128 == 0 && (long)B * T * d.ff_mult * D * 4 < 0x7fffffffL;
-  for (int l = 0; fast_x3 && l < d.n_layers; ++l)
-    fast_x3 = d.layers[l].w_qkvg_x3 && d.layers[l].w_out_x3 && d.layers[l].w_ff1_x3 && d.layers[l].w_ff2_x3;
-
-  // frontend.linear on gemm3 (half A written by the last conv block) when its shape fits
-  bool lin3 = false;
-  if (fast_layers || (fast_x3 && d.lin_w_x3)) {
-    Gemm3P g;
-    memset(&g, 0, sizeof g);
-    g.lda = 1024; g.M = B * T; g.K = 1024; g.N = D; g.epi = G3_RESID; g.ldx = D; g.x = ws.xm; g.x3 = fast_x3;
-    lin3 = gemm3_supported(g);
-  }
+  // range flag of this forward (first word of the workspace): cleared here; bit 0 is ORed by the gemm3 / attention / QKV
+  // kernels when a value beyond the fp16 range goes through a split, bit 1 by whatever ends the call (head, final norm,
+  // stage exit) when its output is not finite -- which is where an overflow in any other splitting kernel ends up
+  if (r.x3) LAUNCH(launch_clear_words(ws.status, 1, s), "clearing the range flag");
+  int* status = r.x3 ? ws.status : nullptr;
 
   const size_t xm_bytes = (size_t)B * T * D * 4;
-  bool xmb_f8 = false;   // the shadow of the main residual stream is hl8 (BT_OPT_X3_GEMM_FP8 = 2) when the first layer starts
   if (first == 2) {  // task_heads on a normalised [B,T,D] input
     if (!d.head_w_raw) return bt_set_error(BT_ERR_ARG, "stage entry at task_heads needs head_w_raw");
-    HeadP hp;
-    hp.x = d_spect; hp.w = d.head_w_raw; hp.b0 = d.head_b[0]; hp.b1 = d.head_b[1];
-    hp.beat = d_beat; hp.downbeat = d_downbeat; hp.M = B * T; hp.D = D; hp.sum_head = d.sum_head; hp.prenorm = 1;
-    hp.status = nullptr;
+    const HeadP hp = head_params(d, d_spect, d.head_w_raw, 1, d_beat, d_downbeat, B * T, nullptr);
     LAUNCH_CAT(CAT_HEAD, s, launch_head(hp, s), "head");
     return BT_OK;
   }
   if (first == 1) {  // transformer_blocks on a [B,T,D] input: the residual stream and what its producer would have left
     if (hipMemcpyAsync(ws.xm, d_spect, xm_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
       return bt_set_error(BT_ERR_HIP, "copy of the stage input");
-    if (use_shadow) LAUNCH_CAT(CAT_LINEAR, s, launch_shadow_ssq(ws.xm, ws.xmb, fast_layers ? ws.ssq[0] : nullptr, (long)B * T, D, s), "stage entry");
-    if (fast_x3) LAUNCH_CAT(CAT_LINEAR, s, launch_shadow_ssq(ws.xm, ws.xmb, ws.ssq[0], (long)B * T, D, s, 1), "stage entry");
+    if (r.half_shadow)
+      LAUNCH_CAT(CAT_LINEAR, s, launch_shadow_ssq(ws.xm, ws.xmb, r.layers == LAYERS_FRAG_HALF ? ws.ssq[0] : nullptr, (long)B * T, D, s), "stage entry");
+    if (r.layers == LAYERS_FRAG_X3) LAUNCH_CAT(CAT_LINEAR, s, launch_shadow_ssq(ws.xm, ws.xmb, ws.ssq[0], (long)B * T, D, s, 1), "stage entry");
   }
-  if (first == 0) {
-  StemP sp;
-  sp.spect = d_spect; sp.x = ws.xa; sp.bn1_scale = d.bn1_scale; sp.bn1_shift = d.bn1_shift;
-  sp.w = d.stem_w; sp.bias = d.stem_b; sp.B = B; sp.T = T;
-  LAUNCH_CAT(CAT_STEM, s, launch_stem(sp, s), "stem");
-
-  float* x = ws.xa;
-  float* xn = ws.xb;
-  for (int blk = 0; blk < 3; ++blk) {
-    const int C = 32 << blk, F = 32 >> blk;
-    // conv of this block on gemm3 (LDS-DMA ring on the half shadow of x that the time-direction half leaves in ws.hid)
-    Gemm3P cg;
-    memset(&cg, 0, sizeof cg);
-    cg.A = ws.hid; cg.lda = 2 * C; cg.M = B * T * (F / 2); cg.K = 6 * C; cg.N = 2 * C;
-    cg.W = fast_x3 ? d.conv_w_x3[blk] : d.conv_w[blk][BT_PREC_HALF];
-    cg.epi = G3_RESID; cg.no_resid = 1; cg.gelu = 1; cg.bias = d.conv_b[blk]; cg.ldx = 2 * C;
-    cg.conv_C2 = 2 * C; cg.conv_T = T; cg.conv_F = F / 2; cg.x3 = fast_x3; cg.status = ws.status;
-    const bool to_bf16 = blk == 2 && lin3;  // the last block's output is read by frontend.linear (gemm3) only
-    cg.x = to_bf16 ? nullptr : xn; cg.xb = to_bf16 ? (void*)xn : nullptr;
-    // (the first conv, N = 64, works as well but only pays 4 us for the 12 us its shadow write costs: it stays on gemm.hip)
-    // x3: the shadow is the hl32 form written by the (hi, lo) out-projection + FF kernel of the time-direction half
-    const bt_pair_weights& tw = d.front[blk][1];
-    const bool conv3 = d.partial_transformers && cg.N >= 128 && cg.W &&
-                       (fast_x3 ? (pair_fused2_ok(tw, prec) && tw.w_outff_frag_x3 && tw.w_attnff_frag_x3)
-                                : (fast_layers && pair_fused2_ok(tw, prec))) &&
-                       gemm3_supported(cg);
-    // (x3: frontend.linear on gemm3 reads hl32 planes, which only the gemm3 form of the last convolution writes)
-    if (blk == 2 && fast_x3 && !conv3) lin3 = false;
-    if (d.partial_transformers) {
-      int rc = run_pair(pf, d.front[blk][0], d.rope, x, nullptr, ws, B, T, F, 1, prec, s, nullptr, 4, x3);
-      if (rc) return rc;
-      rc = run_pair(pf, d.front[blk][1], d.rope, x, nullptr, ws, B, T, F, 2, prec, s, conv3 ? ws.hid : nullptr, 4, x3);
-      if (rc) return rc;
-    }
-    if (conv3) {
-      LAUNCH_CAT(CAT_CONV, s, launch_gemm3(cg, s), "frontend conv gemm");
-      std::swap(x, xn);
-      continue;
-    }
-    GemmP g;
-    memset(&g, 0, sizeof g);
-    g.A = x; g.W = d.conv_w[blk][wp]; g.M = B * T * (F / 2); g.N = 2 * C; g.K = 6 * C;
-    g.epi = GEMM_EPI_STORE; g.flags = GEMM_F_CONV | GEMM_F_A_F32 | GEMM_F_BIAS | GEMM_F_GELU | GEMM_F_OUT_F32;
-    // the last block's output is read by frontend.linear only: half when that runs on gemm3 (same rounding point as
-    // the fp32 -> half conversion of its A operand, half the bytes both ways)
-    if (blk == 2 && lin3) g.flags &= ~GEMM_F_OUT_F32;
-    g.bias = d.conv_b[blk]; g.out = xn; g.ldo = 2 * C;
-    g.conv_C2 = 2 * C; g.conv_T = T; g.conv_F = F / 2;
-    LAUNCH_CAT(CAT_CONV, s, launch_gemm(g, gp, s), "frontend conv gemm");
-    std::swap(x, xn);
-  }
-  if (lin3) {
-    Gemm3P g;
-    memset(&g, 0, sizeof g);
-    g.A = x; g.lda = 1024; g.M = B * T; g.K = 1024; g.W = fast_x3 ? d.lin_w_x3 : d.lin_w[BT_PREC_HALF]; g.N = D; g.epi = G3_RESID;
-    g.no_resid = 1; g.bias = d.lin_b; g.x = ws.xm; g.ldx = D; g.xb = ws.xmb; g.ssq_out = ws.ssq[0];
-    xmb_f8 = fast_x3 && ws.x3_gemm_fp8 >= 2 && d.n_layers > 0 && d.layers[0].w_qkvg_f8;   // (layer 0's QKV reads it in that form)
-    g.x3 = fast_x3 ? 1 | (xmb_f8 ? G3_X3_OUT_F8 : 0) : 0; g.status = ws.status;
-    LAUNCH_CAT(CAT_LINEAR, s, launch_gemm3(g, s), "frontend linear gemm");
-  } else {
-    GemmP g;
-    memset(&g, 0, sizeof g);
-    g.A = x; g.lda = 1024; g.W = d.lin_w[wp]; g.M = B * T; g.N = D; g.K = 1024;
-    g.epi = GEMM_EPI_STORE; g.flags = GEMM_F_A_F32 | GEMM_F_BIAS | GEMM_F_OUT_F32;
-    g.bias = d.lin_b; g.out = ws.xm; g.ldo = D; g.xb = use_shadow ? ws.xmb : nullptr;
-    g.ssq_out = fast_layers ? ws.ssq[0] : nullptr;
-    LAUNCH_CAT(CAT_LINEAR, s, launch_gemm(g, gp, s), "frontend linear gemm");
-    if (fast_x3) LAUNCH_CAT(CAT_LINEAR, s, launch_shadow_ssq(ws.xm, ws.xmb, ws.ssq[0], (long)B * T, D, s, 1), "hl32 shadow of the residual stream");
-  }
-  }  // first == 0
+  if (first == 0)
+    if (int rc = frontend(pf, d, r, d_spect, ws, B, T, s)) return rc;
   if (last == 0) {
     if (hipMemcpyAsync(d_out, ws.xm, xm_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
       return bt_set_error(BT_ERR_HIP, "copy of the stage output");
     // (x3: not every operand-splitting kernel of the frontend raises the flag itself -- what they all do is turn an operand
     // beyond the fp16 range into inf / NaN, which the stage's exit looks for like the head does for the logits)
-    if (x3) LAUNCH_CAT(CAT_HEAD, s, launch_finite_rows(ws.xm, (long)B * T, D, ws.status, s), "range check of the stage output");
+    if (r.x3) LAUNCH_CAT(CAT_HEAD, s, launch_finite_rows(ws.xm, (long)B * T, D, ws.status, s), "range check of the stage output");
     return BT_OK;
   }
   for (int l = 0; l < d.n_layers; ++l) {
-    // (hl8 shadow for the next layer's QKV: only when that layer has the weights for it)
-    const bool next_f8 = fast_x3 && ws.x3_gemm_fp8 >= 2 && l + 1 < d.n_layers && d.layers[l + 1].w_qkvg_f8 && d.layers[l].w_ff2_f8;
-    int rc = fast_x3 ? run_layer_x3(pf, d.layers[l], d.rope, ws, B, T, d.ff_mult, s, xmb_f8, next_f8)
-             : fast_layers ? run_layer_half(pf, d.layers[l], d.rope, ws, B, T, d.ff_mult, s)
-                         : run_pair(pf, d.layers[l], d.rope, ws.xm, use_shadow ? ws.xmb : nullptr, ws, B, T, 1, 0, prec, s, nullptr,
-                                    d.ff_mult, x3);
+    const Route::Layer& rl = r.layer[l];
+    const int rc = r.layers == LAYERS_GENERIC
+                       ? generic_layer(pf, d.layers[l], rl.pair, r, d.rope, ws.xm, r.half_shadow ? ws.xmb : nullptr, ws, B, T,
+                                       d.ff_mult, true, true, s)
+                       : frag_layer(pf, d.layers[l], rl.frag, r, d.rope, ws, B, T, d.ff_mult, s);
     if (rc) return rc;
-    xmb_f8 = next_f8;
   }
   if (last == 1) {
     if (!d.norm_out_g) return bt_set_error(BT_ERR_ARG, "stage exit after transformer_blocks needs norm_out_g");
-    LAUNCH_CAT(CAT_HEAD, s, launch_norm_out(ws.xm, d.norm_out_g, d_out, (long)B * T, D, s, x3 ? ws.status : nullptr), "final norm");
+    LAUNCH_CAT(CAT_HEAD, s, launch_norm_out(ws.xm, d.norm_out_g, d_out, (long)B * T, D, s, status), "final norm");
     return BT_OK;
   }
-  HeadP hp;
-  hp.x = ws.xm; hp.w = d.head_w; hp.b0 = d.head_b[0]; hp.b1 = d.head_b[1];
-  hp.beat = d_beat; hp.downbeat = d_downbeat; hp.M = B * T; hp.D = D; hp.sum_head = d.sum_head; hp.prenorm = 0;
-  hp.status = x3 ? ws.status : nullptr;
+  const HeadP hp = head_params(d, ws.xm, d.head_w, 0, d_beat, d_downbeat, B * T, status);
   LAUNCH_CAT(CAT_HEAD, s, launch_head(hp, s), "head");
   return BT_OK;
 }
@@ -579,8 +656,10 @@ int bt_forward_unit(bt_engine* e, void* stream, int prec, int unit, int index, c
   if (prec != BT_PREC_F32 && prec != BT_PREC_HALF) return bt_set_error(BT_ERR_ARG, "unknown precision");
   prof::State* pf = &e->prof;
   const int D = d.transformer_dim;
-  Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec);
+  const Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec);
   if (ws.total > ws_bytes) return bt_set_error(BT_ERR_WORKSPACE, "workspace too small");
+  // (the units run the route's pair forms on the generic kernels: no shadows, no fragment-major main layers)
+  const Route r = plan_route(*e, B, T, prec, 0, ws);
   hipStream_t s = (hipStream_t)stream;
   const bool block_unit = unit == BT_UNIT_PARTIAL || unit == BT_UNIT_CONV;
   const bool layer_unit = unit == BT_UNIT_ATTN || unit == BT_UNIT_FF;
@@ -595,51 +674,41 @@ int bt_forward_unit(bt_engine* e, void* stream, int prec, int unit, int index, c
   };
   switch (unit) {
     case BT_UNIT_STEM: {
-      StemP sp;
-      sp.spect = d_in; sp.x = d_out; sp.bn1_scale = d.bn1_scale; sp.bn1_shift = d.bn1_shift;
-      sp.w = d.stem_w; sp.bias = d.stem_b; sp.B = B; sp.T = T;
+      const StemP sp = stem_params(d, d_in, d_out, B, T);
       LAUNCH_CAT(CAT_STEM, s, launch_stem(sp, s), "stem");
       return BT_OK;
     }
     case BT_UNIT_PARTIAL: {
       if (!d.partial_transformers) return bt_set_error(BT_ERR_ARG, "this model has no partial transformers");
-      const int F = 32 >> index;
+      const Route::Block& rb = r.blk[index];
       if (int rc = copy_in((size_t)B * T * 1024 * 4)) return rc;
-      if (int rc = run_pair(pf, d.front[index][0], d.rope, d_out, nullptr, ws, B, T, F, 1, prec, s)) return rc;
-      return run_pair(pf, d.front[index][1], d.rope, d_out, nullptr, ws, B, T, F, 2, prec, s);
+      if (int rc = freq_half(pf, d.front[index][0], rb.freq, r, d.rope, d_out, B, T, 32 >> index, s)) return rc;
+      return time_half(pf, d.front[index][1], rb.time, r, d.rope, d_out, ws, B, T, 32 >> index, nullptr, s);
     }
     case BT_UNIT_CONV: {
-      const int C = 32 << index, F = 32 >> index;
-      GemmP g;
-      memset(&g, 0, sizeof g);
-      g.A = d_in; g.W = d.conv_w[index][prec]; g.M = B * T * (F / 2); g.N = 2 * C; g.K = 6 * C;
-      g.epi = GEMM_EPI_STORE; g.flags = GEMM_F_CONV | GEMM_F_A_F32 | GEMM_F_BIAS | GEMM_F_GELU | GEMM_F_OUT_F32;
-      g.bias = d.conv_b[index]; g.out = d_out; g.ldo = 2 * C;
-      g.conv_C2 = 2 * C; g.conv_T = T; g.conv_F = F / 2;
-      LAUNCH_CAT(CAT_CONV, s, launch_gemm(g, prec, s), "frontend conv gemm");
+      const GemmP g = conv_params(d, index, r.wp, d_in, d_out, B, T, true);
+      LAUNCH_CAT(CAT_CONV, s, launch_gemm(g, r.gp, s), "frontend conv gemm");
       return BT_OK;
     }
     case BT_UNIT_LINEAR: {
-      GemmP g;
-      memset(&g, 0, sizeof g);
-      g.A = d_in; g.lda = 1024; g.W = d.lin_w[prec]; g.M = B * T; g.N = D; g.K = 1024;
-      g.epi = GEMM_EPI_STORE; g.flags = GEMM_F_A_F32 | GEMM_F_BIAS | GEMM_F_OUT_F32;
-      g.bias = d.lin_b; g.out = d_out; g.ldo = D;
-      LAUNCH_CAT(CAT_LINEAR, s, launch_gemm(g, prec, s), "frontend linear gemm");
+      const GemmP g = linear_params(d, r.wp, d_in, d_out, nullptr, nullptr, B, T);
+      LAUNCH_CAT(CAT_LINEAR, s, launch_gemm(g, r.gp, s), "frontend linear gemm");
       return BT_OK;
     }
     case BT_UNIT_ATTN:
     case BT_UNIT_FF: {
       if (int rc = copy_in((size_t)B * T * D * 4)) return rc;
-      return run_pair(pf, d.layers[index], d.rope, d_out, nullptr, ws, B, T, 1, 0, prec, s, nullptr, d.ff_mult, false,
-                      unit == BT_UNIT_ATTN ? 1 : 2);
+      return generic_layer(pf, d.layers[index], r.layer[index].pair, r, d.rope, d_out, nullptr, ws, B, T, d.ff_mult,
+                           unit == BT_UNIT_ATTN, unit == BT_UNIT_FF, s);
     }
     case BT_UNIT_FRONT_ATTN:
     case BT_UNIT_FRONT_FF: {
-      // a leaf of a partial transformer on its own: [sequences, tokens, C] rows like a main layer's (mode 0), generic kernels
+      // a leaf of a partial transformer on its own: [sequences, tokens, C] rows like a main layer's, generic kernels
       const bt_pair_weights& pw = d.front[index >> 1][index & 1];
+      const Route::Block& rb = r.blk[index >> 1];
       if (int rc = copy_in((size_t)B * T * pw.dim * 4)) return rc;
-      return run_pair(pf, pw, d.rope, d_out, nullptr, ws, B, T, 1, 0, prec, s, nullptr, 4, false, unit == BT_UNIT_FRONT_ATTN ? 1 : 2);
+      return generic_layer(pf, pw, index & 1 ? rb.time : rb.freq, r, d.rope, d_out, nullptr, ws, B, T, 4,
+                           unit == BT_UNIT_FRONT_ATTN, unit == BT_UNIT_FRONT_FF, s);
     }
     case BT_UNIT_NORM:
       if (!d.norm_out_g) return bt_set_error(BT_ERR_ARG, "bt_model_desc.norm_out_g is not set");
