@@ -24,6 +24,7 @@ HEADERS = ["common.h", "chain.h", "kernels.h", "attn_x3_loop.inc", "attn_hq2_loo
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
 ABI_VERSION = 600   # BT_ABI_VERSION of include/beat_this_amd.h this binding was written against
 PREC_F32, PREC_HALF, PREC_F32X3 = 0, 1, 3   # (2 was the withdrawn e4m3 experiment)
+OPT_X3_ATTN_P16, OPT_X3_GEMM_FP8, OPT_WS_GUARD = 1, 2, 3   # BT_OPT_* (bt_engine_set_option)
 MAX_LAYERS = 32
 PROFILE_CATEGORIES = ["stem", "qkv_gemm", "attn_flash", "out_gemm", "ff1_gemm", "ff2_gemm", "conv_gemm",
                       "linear_gemm", "head", "ff_fused", "attn_freq_fused", "layer_tail"]
@@ -117,6 +118,7 @@ EXPORTS = {
     "bt_engine_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "bt_engine_get_option": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "bt_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "bt_workspace_regions": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "bt_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                              C.c_void_p, C.c_void_p]),
     "bt_forward_stages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,

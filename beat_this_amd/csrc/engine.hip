@@ -56,6 +56,7 @@ struct bt_engine {
   std::vector<int> warm;   // (precision << 8 | chunks) that ran plainly once: the kernels a shape selects are loaded / configured before they are recorded
   int x3_attn_p16 = 1;   // BT_OPT_X3_ATTN_P16 (default chosen by the flip-soak rule: DESIGN.md section 3)
   int x3_gemm_fp8 = 0;   // BT_OPT_X3_GEMM_FP8
+  int ws_guard = 0;      // BT_OPT_WS_GUARD: bytes left unused after every region of the forward's workspace (tests)
 };
 enum { CAT_STEM = 0, CAT_QKV, CAT_ATTN_FLASH, CAT_OUT, CAT_FF1, CAT_FF2, CAT_CONV, CAT_LINEAR,
        CAT_HEAD, CAT_FF_FUSED, CAT_ATTN_FREQ_FUSED, CAT_LAYER_TAIL, CAT_COUNT };
@@ -74,14 +75,22 @@ struct Workspace {
   size_t total;
 };
 
-Workspace carve(char* base, int B, int T, int D, int ff_mult, int prec) {
+// guard: bytes left unused after every region (BT_OPT_WS_GUARD; 0 = the packed layout).  regions, when given, receives the
+// [begin, begin + requested bytes) range of each region in order (bt_workspace_regions).
+Workspace carve(char* base, int B, int T, int D, int ff_mult, int prec, size_t guard = 0,
+                std::vector<int64_t>* regions = nullptr) {
   const bool x3 = prec == BT_PREC_F32X3;
   if (x3) prec = BT_PREC_F32;   // (fp32 activations; hl32 planes = 4 bytes per element as well)
   const size_t es = prec == BT_PREC_F32 ? 4 : 2;
   const size_t bt = (size_t)B * T;
   const size_t dmax = std::max<size_t>(1024, D);
   size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return base ? base + o : (char*)nullptr; };
+  auto take = [&](size_t bytes) {
+    size_t o = off;
+    off += align_up(bytes, 256) + guard;
+    if (regions) { regions->push_back((int64_t)o); regions->push_back((int64_t)(o + bytes)); }
+    return base ? base + o : (char*)nullptr;
+  };
   Workspace w;
   w.status = (int*)take(256);
   w.xa = (float*)take(bt * 1024 * 4);
@@ -561,18 +570,30 @@ int bt_engine_set_option(bt_engine* e, int option, int value) {
   std::lock_guard<std::mutex> lock(e->mu);
   if (option == BT_OPT_X3_ATTN_P16 && value >= 0 && value <= 3) { if (e->x3_attn_p16 != value) drop_graphs(e); e->x3_attn_p16 = value; return BT_OK; }
   if (option == BT_OPT_X3_GEMM_FP8 && value >= 0 && value <= 2) { if (e->x3_gemm_fp8 != value) drop_graphs(e); e->x3_gemm_fp8 = value; return BT_OK; }
+  if (option == BT_OPT_WS_GUARD && value >= 0 && value % 256 == 0) { if (e->ws_guard != value) drop_graphs(e); e->ws_guard = value; return BT_OK; }
   return bt_set_error(BT_ERR_ARG, "unknown engine option / value");
 }
 int bt_engine_get_option(const bt_engine* e, int option, int* value) {
   if (!e || !value) return bt_set_error(BT_ERR_ARG, "null argument");
   if (option == BT_OPT_X3_ATTN_P16) { *value = e->x3_attn_p16; return BT_OK; }
   if (option == BT_OPT_X3_GEMM_FP8) { *value = e->x3_gemm_fp8; return BT_OK; }
+  if (option == BT_OPT_WS_GUARD) { *value = e->ws_guard; return BT_OK; }
   return bt_set_error(BT_ERR_ARG, "unknown engine option");
 }
 
 size_t bt_workspace_bytes(const bt_engine* e, int B, int T, int prec) {
   if (!e || B <= 0 || T <= 0) return 0;
-  return carve(nullptr, B, T, e->d.transformer_dim, e->d.ff_mult, prec).total;
+  return carve(nullptr, B, T, e->d.transformer_dim, e->d.ff_mult, prec, (size_t)e->ws_guard).total;
+}
+
+int bt_workspace_regions(const bt_engine* e, int B, int T, int prec, int64_t* begin_end, int max) {
+  if (!e || B <= 0 || T <= 0 || max < 0 || (max > 0 && !begin_end)) return bt_set_error(BT_ERR_ARG, "bad argument to bt_workspace_regions");
+  if (prec != BT_PREC_F32 && prec != BT_PREC_HALF && prec != BT_PREC_F32X3) return bt_set_error(BT_ERR_ARG, "unknown precision");
+  std::vector<int64_t> r;
+  carve(nullptr, B, T, e->d.transformer_dim, e->d.ff_mult, prec, (size_t)e->ws_guard, &r);
+  const int n = (int)(r.size() / 2);
+  for (int i = 0; i < std::min(n, max); ++i) { begin_end[2 * i] = r[2 * i]; begin_end[2 * i + 1] = r[2 * i + 1]; }
+  return n;
 }
 
 int bt_forward(bt_engine* e, void* stream, int prec, const float* d_spect, int B, int T, void* d_ws, size_t ws_bytes,
@@ -593,7 +614,7 @@ int bt_forward_stages(bt_engine* e, void* stream, int prec, int first, int last,
   const bt_model_desc& d = e->d;
   prof::State* pf = &e->prof;
   const int D = d.transformer_dim;
-  const Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec);
+  const Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec, (size_t)e->ws_guard);
   if (ws.total > ws_bytes) return bt_set_error(BT_ERR_WORKSPACE, "workspace too small");
   if (prec == BT_PREC_F32X3 && BT_HALF_IS_BF16) return bt_set_error(BT_ERR_ARG, "BT_PREC_F32X3 needs an IEEE fp16 build");
   const Route r = plan_route(*e, B, T, prec, first, ws);
@@ -656,7 +677,7 @@ int bt_forward_unit(bt_engine* e, void* stream, int prec, int unit, int index, c
   if (prec != BT_PREC_F32 && prec != BT_PREC_HALF) return bt_set_error(BT_ERR_ARG, "unknown precision");
   prof::State* pf = &e->prof;
   const int D = d.transformer_dim;
-  const Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec);
+  const Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec, (size_t)e->ws_guard);
   if (ws.total > ws_bytes) return bt_set_error(BT_ERR_WORKSPACE, "workspace too small");
   // (the units run the route's pair forms on the generic kernels: no shadows, no fragment-major main layers)
   const Route r = plan_route(*e, B, T, prec, 0, ws);

@@ -371,12 +371,13 @@ class Engine:
 
     MAX_WORKSPACES = 4
     SHRINK_AFTER = 8   # consecutive requests of < 1/4 of a stream's workspace before it is given back
-    OPTIONS = {"x3_attn_p16": 1, "x3_gemm_fp8": 2}   # name -> BT_OPT_* of include/beat_this_amd.h
+    OPTIONS = {"x3_attn_p16": 1, "x3_gemm_fp8": 2, "ws_guard": 3}   # name -> BT_OPT_* of include/beat_this_amd.h
 
     def set_options(self, opts: dict) -> None:
         """Arithmetic variants of the engine (bt_engine_set_option), e.g. ``{"x3_attn_p16": 0}`` for the three-term P.V of
         rounds 3 - 4 everywhere, ``1`` (default) for P16 in the main layers only, ``2`` main layers + frontend (round 5's default);
-        ``{"x3_gemm_fp8": 1 | 2}`` for BASELINE config 5 (fp8 cross terms in the feed-forward / in all main-layer GEMMs).  Captured forwards are dropped: a graph replays the kernels it was recorded with."""
+        ``{"x3_gemm_fp8": 1 | 2}`` for BASELINE config 5 (fp8 cross terms in the feed-forward / in all main-layer GEMMs). ``{"ws_guard": bytes}`` leaves that many unused bytes after every region of the
+        forward's workspace (tests: a kernel writing past its region then hits bytes nothing else owns).  Captured forwards are dropped: a graph replays the kernels it was recorded with."""
         for name in opts:
             if name not in self.OPTIONS:
                 raise ValueError(f"unknown engine option {name!r} (known: {sorted(self.OPTIONS)})")

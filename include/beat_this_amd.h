@@ -192,13 +192,23 @@ void bt_engine_destroy(bt_engine* e);
  *                       the 1e-3 gate, reported beside the default (bench.py: configs.cfg5; flip rates: DESIGN.md section 3):
  *                       measured at level 2 -4 % forward time, 1.7e-4 .. 2.5e-4 on the logits against the oracle (default 7e-5),
  *                       1.1 x (outlier weights) to 14 x (freshly initialised) the default's beat flips over the 96-track soak.
- *                       Activations beyond 3584 (hl8's range) raise the range flag like those beyond 65504 on the default path. */
+ *                       Activations beyond 3584 (hl8's range) raise the range flag like those beyond 65504 on the default path.
+ *   BT_OPT_WS_GUARD     0 (default): the workspace regions of bt_forward / bt_forward_stages / bt_forward_unit lie back to back.
+ *                       A multiple of 256: that many bytes are left unused after every region (bt_workspace_regions), and
+ *                       bt_workspace_bytes (so bt_audio2beats_plan's forward_bytes) counts them -- a test sets it to see
+ *                       a kernel that writes past its region.  Kernels and launches are the same for every value. */
 #define BT_OPT_X3_ATTN_P16 1
 #define BT_OPT_X3_GEMM_FP8 2
+#define BT_OPT_WS_GUARD 3
 int bt_engine_set_option(bt_engine* e, int option, int value);
 int bt_engine_get_option(const bt_engine* e, int option, int* value);
 /* bytes of scratch bt_forward needs for a [B,T,128] batch (its first int32 is the BT_PREC_F32X3 range flag) */
 size_t bt_workspace_bytes(const bt_engine* e, int B, int T, int prec);
+/* the regions bt_forward carves out of that workspace, in address order (region 0 is the 256-byte status block that holds the
+ * range flag): begin_end[2 i], begin_end[2 i + 1] = byte offsets of region i's start and of the end of the bytes it asks for
+ * (before the 256-byte alignment and the BT_OPT_WS_GUARD gap).  Writes at most `max` regions; returns their total count, or a
+ * negative BT_ERR_* code. */
+int bt_workspace_regions(const bt_engine* e, int B, int T, int prec, int64_t* begin_end, int max);
 
 /* BeatThis.forward (beat_tracker.py:188-192): d_spect [B,T,128] fp32 ->
  * d_beat, d_downbeat [B,T] fp32 logits (SumHead applied).  Any T <= bt_model_desc.rope_len (the reference's chunks have

@@ -194,3 +194,81 @@ def unfrag_x3(fr, L, kind):
     """inverse of frag_x3 -> float64 [SH, L, 32]"""
     u = unfrag_qk if kind == "qk" else unfrag_v
     return u(fr[:, :, 0].contiguous(), L).double() + u(fr[:, :, 1].contiguous(), L).double()
+
+
+# ---- guard bands and poisoned memory (tests/test_gpu_guard.py) -------------------------------------------------------
+GUARD_BAND = 2 << 20   # bytes on each side of a guarded buffer: more than a whole 128-row tile of 2048 fp32 columns (1 MiB)
+POISONS = (0xFF, 0x7B)  # 0xFF: NaN in fp32 / fp16 / bf16, -1 as int32;  0x7B: large finite (fp32 ~1.3e36, fp16 61280, bf16 ~1.3e36)
+
+
+class Guarded:
+    """One device uint8 allocation [band | payload (rounded up to 256 bytes) | band]; ``t`` is the payload as a typed tensor
+    of ``shape`` (256-byte aligned: the band is a multiple of 256 and torch's allocations are 512-aligned)."""
+
+    def __init__(self, shape, dtype, band=GUARD_BAND):
+        shape = tuple(int(s) for s in shape)
+        self.nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty(0, dtype=dtype).element_size()
+        self.band = band
+        self.raw = torch.empty(band + (self.nbytes + 255) // 256 * 256 + band, dtype=torch.uint8, device=dev())
+        self.pattern = None
+        self.t = self.raw[band:band + self.nbytes].view(dtype).view(shape)
+        assert self.t.data_ptr() % 256 == 0
+
+    def fill(self, pattern_byte, data=None, payload_byte=None):
+        """every byte (payload and bands) = pattern_byte; then ``data``, if given, goes into the payload, or else
+        ``payload_byte``, if given, fills it (a buffer that may only be poisoned outside its payload)"""
+        self.raw.fill_(pattern_byte)
+        self.pattern = pattern_byte
+        if data is not None:
+            self.t.copy_(data.reshape(self.t.shape))
+        elif payload_byte is not None:
+            self.t.view(torch.uint8).view(-1).fill_(payload_byte)
+        return self
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def bands_intact(self, what="buffer"):
+        """None, or a message naming the first damaged byte of a band and its distance from the payload"""
+        lo = self.raw[:self.band]
+        hi = self.raw[self.band + self.nbytes:]
+        for name, part, base in (("leading", lo, 0), ("trailing", hi, self.band + self.nbytes)):
+            bad = torch.nonzero(part != self.pattern)
+            if bad.numel():
+                off = base + int(bad[0])
+                dist = self.band - off if name == "leading" else off - (self.band + self.nbytes)
+                return (f"{what}: {name} band damaged at byte {off} of the allocation, {dist} bytes "
+                        f"{'before' if name == 'leading' else 'after'} the {self.nbytes}-byte payload "
+                        f"({int(bad.shape[0])} bytes differ from 0x{self.pattern:02X})")
+        return None
+
+
+def assert_intact(*named):
+    """named: (name, Guarded) pairs -> fails naming every damaged band"""
+    bad = [m for m in (g.bands_intact(n) for n, g in named) if m]
+    assert not bad, "; ".join(bad)
+
+
+def workspace_regions(h, B, T, prec):
+    """bt_workspace_regions: [(begin, end of the requested bytes)] of the forward's workspace regions"""
+    from beat_this_amd import _lib
+
+    n = _lib.lib().bt_workspace_regions(h, B, T, prec, None, 0)
+    _lib.check(min(n, 0))
+    buf = (C.c_int64 * (2 * n))()
+    assert _lib.lib().bt_workspace_regions(h, B, T, prec, buf, n) == n
+    return [(buf[2 * i], buf[2 * i + 1]) for i in range(n)]
+
+
+def gaps_intact(raw, pattern, regions, total, what="workspace"):
+    """raw: the workspace's bytes (uint8).  None, or a message naming the first workspace region whose gap behind it (alignment
+    slack + BT_OPT_WS_GUARD bytes, up to the next region / the end of the workspace) no longer holds the fill byte"""
+    raw = raw.view(-1)
+    ends = [b for b, _ in regions[1:]] + [total]
+    for i, ((b, e), nxt) in enumerate(zip(regions, ends)):
+        if nxt > e:
+            bad = torch.nonzero(raw[e:nxt] != pattern)
+            if bad.numel():
+                return (f"{what}: gap behind region {i} [{b}, {e}) damaged {int(bad[0])} bytes past its end "
+                        f"({int(bad.shape[0])} of {nxt - e} bytes differ from 0x{pattern:02X})")
+    return None
