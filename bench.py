@@ -2,19 +2,25 @@
 """Benchmark of the beat_this inference hot path on MI355X (driver contract).
 
     python bench.py --gpus N --steps K --warmup W        (N > 1 re-launches itself under torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full (+ the side legs below, after the timed steps)
+
+A plain run does what the headline needs and nothing else: set-up, settling, W warm-up steps and pre-heat, the K timed steps,
+--dump-outputs, and the JSON line with value, ms_per_step, timed_region, energy and rccl_ranks.  The objects that take runs of
+their own (parity, roofline + breakdown, cpu_baseline, every path / config / latency / stress / frontend / strong-scaling leg)
+are measured with --full only and are null otherwise; --no-cpu-baseline and --no-extras drop parts of a --full run.
 
 Headline workload = BASELINE.json's metric: final0-shaped BeatThis, 5-minute (300 s) synthetic 44.1 kHz mono tracks
 through ``Audio2Beats`` -- GPU resampler -> log-mel -> chunk gather -> BeatThis.forward -> keep_first aggregation -> peak
 picking -> device-to-host copy of the peak indices -> C++ host post-processing -- audio in, beat / downbeat times out, in the
 precision of the API's DEFAULT (``float16=False``): BT_PREC_F32X3, fp32 activations with every product on three fp16 MFMAs
 over hi + lo operand halves -- the path that carries north_star's gate (logits within 1e-3 of the CPU reference, identical
-beats), which the in-run `parity` object shows on every run.  One step = one batch of TRACKS_PER_GPU = 6 tracks (66 chunks
-of 1500 frames; BASELINE config 4's per-GPU share is 64) on every rank, waveforms resident in HBM when the timed region
+beats), which the in-run `parity` object of a --full run shows.  One step = one batch of TRACKS_PER_GPU = 6 tracks (66
+chunks of 1500 frames; BASELINE config 4's per-GPU share is 64) on every rank, waveforms resident in HBM when the timed region
 starts; step i + 1 is enqueued before the host part of step i is collected (Audio2Beats.many_async).  For N > 1 every
 rank processes its own tracks and the framewise logits are all-gathered (RCCL) inside the step -- weak scaling.
 value = N * 6 * 300 audio-seconds / step time (max over ranks).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (all but timed_region with --full only):
   parity        GPU logits / beats of track 0 against the CPU oracle run on the same waveform (the run cpu_baseline times):
                 max |logit difference|, beat / downbeat frame flips.
   roofline      dominant launch category of the forward (attention, MFMA bound): algorithmic FLOP per launch / average
@@ -172,8 +178,13 @@ def main():
     ap.add_argument("--chunks", type=int, default=16, help="--workload forward: chunks per GPU per step")
     ap.add_argument("--slice", type=int, default=0, help="chunks per forward launch (0 = the library default)")
     ap.add_argument("--streams", type=int, default=0, help="streams the forward slices of a step run on (0 = the library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side legs (other precisions, latency, configs, frontend)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure everything besides the headline as well: parity against the CPU oracle, "
+                         "roofline and per-launch breakdown, cpu_baseline and the side legs (without it they are null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline and the legs that run behind it (parity, other precisions, latency, stress weights)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the side legs (other precisions, latency, configs, frontend, strong scaling)")
     ap.add_argument("--no-dist", action="store_true", help="N = 1 without bringing up the RCCL process group")
     ap.add_argument("--x3-p16", type=int, default=1, choices=[0, 1, 2],
                     help="BT_OPT_X3_ATTN_P16 of the default precision: probabilities enter P.V as fp16 hi parts in the main layers only "
@@ -474,7 +485,7 @@ def main():
 
     # ---- BASELINE config 4 as written: 512 chunks sharded over the ranks, logits all-gathered (strong scaling) ------------
     strong = None
-    if args.workload == "tracks" and not args.no_extras:
+    if args.full and args.workload == "tracks" and not args.no_extras:
         log("strong-scaling leg (512 chunks / N)")
         per = 512 // world
         xs = torch.from_numpy(np.stack([W.synthetic_spect(CHUNK_FRAMES, seed=50000 + 512 * rank + i) for i in range(min(per, 64))])).to(dev)
@@ -561,12 +572,6 @@ def main():
                                 "tflops": round(fl[name] * chunks / (t_step * 1e-3) / 1e12, 2)}
             return bd
 
-        # ---- roofline leg: per-kernel HIP-event timing of the same workload ------------------------------------------
-        log("roofline leg")
-        if args.workload == "tracks":
-            breakdown = profile_forward(lambda: a2b.many(tracks, TRACK_SR), 2, chunks_per_step)
-        else:
-            breakdown = profile_forward(step, 3, chunks_per_step)
         def soak_of(scheme):
             """what the committed flip soak (tools/flip_soak.py: many 300 s tracks x 3 weight styles against the fp32 CPU oracle)
             says about `scheme`: flips per 1000 beat / downbeat decisions, next to the exact fp32 MFMA path's -- the rule the
@@ -630,10 +635,18 @@ def main():
                 r["whole_step_frac"] = round(FLOP_PER_CHUNK * chunks / (step_ms * 1e-3) / 1e12 / peak, 4)
             return r
 
-        roofline = roofline_of(breakdown, args.prec, chunks_per_step, ms_per_step)
+        roofline = breakdown = None
+        if args.full:
+            # ---- roofline leg: per-kernel HIP-event timing of the same workload --------------------------------------
+            log("roofline leg")
+            if args.workload == "tracks":
+                breakdown = profile_forward(lambda: a2b.many(tracks, TRACK_SR), 2, chunks_per_step)
+            else:
+                breakdown = profile_forward(step, 3, chunks_per_step)
+            roofline = roofline_of(breakdown, args.prec, chunks_per_step, ms_per_step)
 
         frontend = forward_only = host_inclusive = configs = None
-        if args.workload == "tracks" and not args.no_extras:
+        if args.full and args.workload == "tracks" and not args.no_extras:
             # ---- HBM-bound stages: events around each stage on torch's current stream (the launch stream) -------------
             def timed(fn, reps=5):
                 fn()
@@ -806,7 +819,7 @@ def main():
         # ---- CPU baseline + in-run parity: the oracle's Audio2Beats on track 0, bounded sample ------------------------
         cpu = parity = half_path = fp32_exact_path = f32x3_path = latency = stress = None
         p16_legs = {}
-        if world == 1 and not args.no_cpu_baseline and args.workload == "tracks":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "tracks":
             from oracle import beat_this_oracle as O
 
             log("cpu baseline: thread probe")
@@ -1031,7 +1044,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": {"half": half_desc, "f32": "f32", "f32x3": "f32 activations, f16x3 products (3 x f16 MFMA on hi+lo operand halves, f32 accumulate)" + {0: "", 1: "; main-layer attention P.V: 2 x, probabilities as fp16 hi parts", 2: "; attention P.V: 2 x, probabilities as fp16 hi parts (opt-in level 2)"}[args.x3_p16]}[args.prec],
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": workload, "tracks_per_gpu": args.tracks if args.workload == "tracks" else None,
                        "chunks_per_gpu": chunks_per_step, "global_chunks": world * chunks_per_step,
                        "parallelism": f"track-sharded x{world}, framewise logits all-gathered" if args.workload == "tracks"

@@ -1,9 +1,12 @@
 """bench.py's bookkeeping on CPU: the algorithmic FLOP table must reproduce SURVEY.md 8d / Appendix B, the track arithmetic
 must match split_piece, and the command line must expose the driver contract."""
 import importlib.util
+import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 from conftest import ROOT
 
@@ -38,7 +41,7 @@ def test_track_arithmetic_matches_split_piece():
 
 def test_command_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True).stdout
-    for flag in ("--gpus", "--steps", "--warmup", "--prec", "--workload", "--tracks", "--dump-outputs"):
+    for flag in ("--gpus", "--steps", "--warmup", "--prec", "--workload", "--tracks", "--dump-outputs", "--full"):
         assert flag in out
 
 
@@ -64,3 +67,26 @@ def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
     rows = np.load(tmp_path / "s1" / "sampled_rows.npy")
     assert len(rows) == 2 and np.array_equal(rows, np.load(tmp_path / "s2" / "sampled_rows.npy"))
     assert np.array_equal(np.load(tmp_path / "s1" / "downbeat.npy"), r["downbeat"].numpy()[rows.astype(int)])
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_run_measures_the_headline_only(tmp_path):
+    """without --full the line carries the headline and its timed region, every side leg is null, and --dump-outputs still
+    writes the last timed step's outputs"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--tracks", "2",
+                        "--min-seconds", "0", "--watchdog", "240", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=280, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 3
+    assert d["timed_region"]["steps_timed"] == 3
+    for k in ("parity", "roofline", "breakdown", "cpu_baseline", "half_path", "fp32_exact_path", "latency", "stress_weights",
+              "frontend", "forward_only", "host_inclusive", "configs", "strong_scaling_cfg4"):
+        assert d[k] is None, k
+    assert not [k for k in d if k.startswith("value_p16")]
+    for leg in ("roofline leg", "cpu baseline", "strong-scaling leg"):
+        assert leg not in r.stderr
+    assert sorted(os.listdir(tmp_path / "out")) == [f"track{i:03d}_{k}.npy" for i in range(2) for k in ("beats", "downbeats")]

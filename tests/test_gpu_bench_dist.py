@@ -20,7 +20,7 @@ BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share
 
 @pytest.mark.timeout(420)
 def test_two_ranks_on_one_gpu_run_the_distributed_bench():
-    r = subprocess.run(BENCH, capture_output=True, text=True, timeout=400, cwd=ROOT)
+    r = subprocess.run(BENCH + ["--full"], capture_output=True, text=True, timeout=400, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)

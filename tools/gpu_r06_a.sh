@@ -9,7 +9,7 @@ rm -f gpurun_out/test_report.jsonl
 timeout 1500 python -m pytest tests -q -m gpu -x 2>&1 | tail -15 > $O/pytest_gpu.txt
 cat $O/pytest_gpu.txt
 cp gpurun_out/test_report.jsonl $O/parity_report.jsonl 2>/dev/null
-timeout 900 python bench.py 2>$O/bench.err > $O/bench.json
+timeout 900 python bench.py --full 2>$O/bench.err > $O/bench.json
 tail -3 $O/bench.err
 python - <<PY
 import json
@@ -24,7 +24,7 @@ export BT_DEV=1
 for i in 1 2 3; do
   for l in tools/variants/lib_hidwrap.so ""; do
     if [ -n "$l" ]; then export BT_LIB_PATH=$R/$l; else unset BT_LIB_PATH; fi
-    python bench.py --no-cpu-baseline --no-extras --steps 30 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-extras --steps 30 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 b = d['breakdown']

@@ -9,7 +9,7 @@ timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -25 > $O/pytest_gpu.tx
 cat $O/pytest_gpu.txt
 cp gpurun_out/test_report.jsonl $O/parity_report.jsonl 2>/dev/null
 bash tools/latency_profile.sh 2>&1 | grep -v amdgpu.ids | tee $O/latency_trace.txt
-timeout 900 python bench.py 2>$O/bench.err > $O/bench.json
+timeout 900 python bench.py --full 2>$O/bench.err > $O/bench.json
 tail -3 $O/bench.err
 python - <<PY
 import json

@@ -12,7 +12,7 @@ P=$R/gpurun_out/prof_r06
 mkdir -p $P
 export TMPDIR=/tmp
 cd /tmp
-B="python $R/bench.py --no-cpu-baseline --no-extras --no-dist --watchdog 150 --min-seconds 0"
+B="python $R/bench.py --full --no-cpu-baseline --no-extras --no-dist --watchdog 150 --min-seconds 0"
 FWDX="$B --workload forward --chunks 16 --prec f32x3 --steps 8 --warmup 2"
 run() { name=$1; shift; timeout 240 rocprofv3 "$@" > $P/$name.log 2>&1; echo "$name $?"; }
 export BT_DEV=1 BT_LIB_PATH=$R/tools/variants/lib_hidwrap.so

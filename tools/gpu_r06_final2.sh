@@ -9,7 +9,7 @@ if [ "$1" = "soak" ]; then
   rm -f gpurun_out/flip_soak/*.json
   timeout 2400 python tools/flip_soak.py gpu --tracks 96 --tag r06 --schemes exact,x3,x3p16m,x3p16f,x3p16,half 2>&1 | grep -v amdgpu.ids | tee $O/flip_soak_gpu.txt
 else
-  timeout 1200 python bench.py 2>$O/bench.err > $O/bench.json
+  timeout 1200 python bench.py --full 2>$O/bench.err > $O/bench.json
   tail -3 $O/bench.err
   python - <<PY
 import json

@@ -6,7 +6,7 @@ cd $R
 O=$R/gpurun_out/r06world8
 mkdir -p $O
 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 \
-  --share-gpu --steps 6 --warmup 2 --min-seconds 0 --no-cpu-baseline 2>$O/bench.err > $O/bench.json
+  --share-gpu --steps 6 --warmup 2 --min-seconds 0 --full --no-cpu-baseline 2>$O/bench.err > $O/bench.json
 echo "exit $?"; grep -v "amdgpu.ids\|socket.cpp" $O/bench.err | tail -12
 python - <<PY
 import json

@@ -9,7 +9,7 @@ O=$R/gpurun_out/prof_r06
 rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-B="python $R/bench.py --no-cpu-baseline --no-extras --no-dist --watchdog 150 --min-seconds 0"
+B="python $R/bench.py --full --no-cpu-baseline --no-extras --no-dist --watchdog 150 --min-seconds 0"
 HEAD="$B --steps 5 --warmup 1 --prec half"   # (bench.py's default precision is f32x3 since round 4: the half legs say so)
 HEADX="$B --steps 5 --warmup 1 --prec f32x3"
 FWD="$B --workload forward --chunks 16 --prec half --steps 10 --warmup 2"

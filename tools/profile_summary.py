@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "prof_r06")
 RND = sys.argv[2] if len(sys.argv) > 2 else "r06"
 out_dir = os.path.join(ROOT, "profiles")
-B = "python bench.py --no-cpu-baseline --no-extras --no-dist --min-seconds 0"
+B = "python bench.py --full --no-cpu-baseline --no-extras --no-dist --min-seconds 0"
 CMD = {"head": f"{B} --steps 5 --warmup 1 --prec half", "head1s": f"{B} --steps 5 --warmup 1 --prec half --streams 1   (the launch "
        "configuration of bench.py's roofline legs: whole 66-chunk launches on one stream)",
        "fwd": f"{B} --workload forward --chunks 16 --prec half --steps 10 --warmup 2",
