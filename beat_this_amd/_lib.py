@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "engine.hip"]
+           "tail.hip", "dbn.hip", "metrics.hip", "engine.hip"]
 HEADERS = ["common.h", "chain.h", "kernels.h", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
@@ -171,6 +171,11 @@ EXPORTS = {
     "bt_dbn_viterbi_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "bt_dbn_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32)]),
     "bt_dbn_host_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32)]),
+    "bt_beat_metrics_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64]),
+    "bt_beat_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                  C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bt_beat_metrics_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_double, C.c_void_p]),
 }
 
 
@@ -182,7 +187,9 @@ HIPCC_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-ml
 # (a wave has 256 architectural VGPRs + 256 AGPRs), so it is compiled without -amdgpu-mfma-vgpr-form
 FLAGS_BY_SOURCE = {"tail.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                    # the DBN's Viterbi must repeat madmom's fp64 adds exactly: no multiply-add contraction anywhere in it
-                   "dbn.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
+                   "dbn.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
+                   # the metrics repeat numpy's fp64 operations one by one (interp midpoints, distances, ratios)
+                   "metrics.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
 # compile-time switches: BT_DEV_BUILD=1 in the environment of build() compiles the development instrumentation (per-wave timing
 # dumps, ablation variants read by tools/*_probe.py) into the kernels; release builds contain none of it
 EXTRA_DEFINES = (["-DBT_DEV"] if os.environ.get("BT_DEV_BUILD") == "1" else []) + os.environ.get("BT_DEFINES", "").split()

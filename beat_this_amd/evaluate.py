@@ -1,0 +1,175 @@
+"""Paper metrics of a model on spectrogram bundles: the equivalent of the reference's launch_scripts/compute_paper_metrics.py
+(README "Reproducing metrics from the paper") without Lightning, pandas or mir_eval.
+
+    python -m beat_this_amd.evaluate --models final0.ckpt --bundle data/audio/spectrograms/gtzan.npz \\
+        --annotations data/annotations [--dbn] [--eval-trim-beats 5] [--dump-predictions preds.npz]
+
+Each bundle is one dataset (its file stem, e.g. ``gtzan``), holding ``<stem>/track`` spectrograms as the reference's
+preprocessing writes them; the beats of piece ``<stem>`` are read from ``<annotations>/<dataset>/annotations/beats/<stem>.beats``
+(dataset.py:108-124).  Predictions go through predict_bundle and the Postprocessor (minimal or DBN), and beats and downbeats are
+scored in one bt_beat_metrics call each (metrics.py)."""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+FPS = 50
+TARGET_KEYS = ("F-measure", "Cemgil", "CMLt", "AMLt")
+
+
+def load_beat_annotations(path):
+    """A beat_this_annotations ``.beats`` file -> (beats, downbeats) float64 arrays, read as dataset.py:117-124 does: one column
+    of beat times, or beat times and beat numbers, the downbeats being the beats numbered 1.  A one-column file has no
+    downbeats.  (A file of a single two-column line is read as one beat and its number; the reference's np.loadtxt would
+    take it for two beat times.)"""
+    a = np.loadtxt(path, ndmin=2)
+    if a.shape[1] == 1:
+        return np.ascontiguousarray(a[:, 0], dtype=np.float64), np.zeros(0, np.float64)
+    beats = np.ascontiguousarray(a[:, 0], dtype=np.float64)
+    return beats, beats[a[:, 1].astype(int) == 1]
+
+
+def _bundle_pieces(bundle, names):
+    """the ``<stem>/track`` spectrograms of a bundle -> [(key, stem)]"""
+    keys = [k for k in bundle.files if k.endswith("/track")]
+    if names is not None:
+        wanted = {n if n.endswith("/track") else f"{n}/track" for n in names}
+        keys = [k for k in keys if k in wanted]
+    return [(k, k[: -len("/track")]) for k in keys]
+
+
+def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float16=True, dbn=False, eval_trim_beats=5,
+                    device="cuda", spect2frames=None):
+    """Predict and score every piece of one bundle (or of a list of bundles, one dataset each).
+
+    checkpoint: what Spect2Frames accepts (a local checkpoint file or a loaded checkpoint dict); ``spect2frames``: an
+    existing Spect2Frames to use instead.  names: bundle keys (``<stem>`` or ``<stem>/track``) to evaluate, default all.
+    float16: any precision Spect2Frames accepts; the default True mirrors the reference, whose evaluation runs under
+    precision="16-mixed" (compute_paper_metrics.py:203-209).  eval_trim_beats: trim_beats' min_beat_time for truth and
+    predictions.
+
+    -> dict: "piece" (``<dataset>/<stem>/track.npy``, the reference's spect_path), "dataset" (per piece), "metrics" (per-piece
+    arrays under the script's keys F-measure_beat, Cemgil_beat, CMLt_beat, AMLt_beat and the _downbeat ones; "Cemgil" is the
+    mean of mir_eval's (cemgil, cemgil_max) pair, as the script reports it), "averaged" and "dataset_metrics" (the means
+    the script prints), "predictions" ([(beats, downbeats)]), "truth" ([(beats, downbeats)] within [0, frames / fps)) and
+    "raw" (beat_metrics_many's full output for "beat" and "downbeat")."""
+    from .bundle import SpectBundle, predict_bundle
+    from .inference import Spect2Frames
+    from .metrics import beat_metrics_many
+    from .postprocessor import Postprocessor
+
+    s2f = spect2frames if spect2frames is not None else Spect2Frames(checkpoint, device, float16=float16)
+    post = Postprocessor(type="dbn" if dbn else "minimal", fps=FPS)
+    paths = [bundle_path] if isinstance(bundle_path, (str, os.PathLike)) else list(bundle_path)
+    pieces, datasets, preds, truths = [], [], [], []
+    for path in paths:
+        dataset = os.path.splitext(os.path.basename(os.fspath(path)))[0]
+        with SpectBundle(path) as bundle:
+            todo = _bundle_pieces(bundle, names)
+            stems = dict(todo)
+            for key, beat, down in predict_bundle(s2f, bundle, [k for k, _ in todo]):
+                stem = stems[key]
+                frames = bundle[key].shape[0]
+                beats, downbeats = post(beat, down)
+                ann = os.path.join(annotation_root, dataset, "annotations", "beats", stem + ".beats")
+                tb, td = load_beat_annotations(ann)
+                end = frames / FPS   # prepare_annotations (dataset.py:535-547): truth inside [0, frames / fps)
+                truths.append((tb[(tb >= 0) & (tb < end)], td[(td >= 0) & (td < end)]))
+                preds.append((np.asarray(beats, np.float64), np.asarray(downbeats, np.float64)))
+                pieces.append(f"{dataset}/{stem}/track.npy")
+                datasets.append(dataset)
+    raw = {}
+    metrics = {}
+    for t, target in enumerate(("beat", "downbeat")):
+        res = beat_metrics_many([x[t] for x in truths], [x[t] for x in preds], eval_trim_beats=eval_trim_beats,
+                                device=s2f.device)
+        raw[target] = res
+        metrics[f"F-measure_{target}"] = res["F-measure"]
+        metrics[f"Cemgil_{target}"] = res["Cemgil_reported"]
+        metrics[f"CMLt_{target}"] = res["CMLt"]
+        metrics[f"AMLt_{target}"] = res["AMLt"]
+    dataset = np.asarray(datasets)
+    averaged = {k: np.mean(v) for k, v in metrics.items()}
+    dataset_metrics = {k: {d: np.mean(v[dataset == d]) for d in np.unique(dataset)} for k, v in metrics.items()}
+    return dict(piece=np.asarray(pieces), dataset=dataset, metrics=metrics, averaged=averaged, dataset_metrics=dataset_metrics,
+                predictions=preds, truth=truths, raw=raw)
+
+
+def write_predictions(fn, preds, piece):
+    """compute_paper_metrics.py's write_predictions: name -> [beat time, beat number] rows"""
+    from .utils import infer_beat_numbers
+
+    np.savez(fn, **{name: np.vstack([beats, infer_beat_numbers(beats, downbeats)]).T
+                    for name, (beats, downbeats) in zip(piece, preds)})
+
+
+PRECISIONS = {"half": True, "f32x3": False, "exact": "exact"}
+
+
+def get_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(
+        prog="python -m beat_this_amd.evaluate",
+        description="Computes predictions for given models on spectrogram bundles, prints the paper's metrics, and "
+                    "optionally dumps predictions to a given file (the reference's compute_paper_metrics.py).",
+        epilog="Not supported: --aggregation-type k-fold, choosing a datasplit from the reference's split files (it needs "
+               "pandas and the Lightning datamodule: pass the bundles and --names to choose pieces instead), and the "
+               "rwc_<subset> dataset names (an rwc bundle is reported as one dataset, 'rwc').")
+    p.add_argument("--models", type=str, nargs="+", required=True, help="local checkpoint files to use")
+    p.add_argument("--bundle", type=str, nargs="+", required=True,
+                   help="spectrogram bundles (.npz, one dataset each, named by the file stem) holding <stem>/track entries")
+    p.add_argument("--annotations", type=str, required=True,
+                   help="annotation root: beats are read from <root>/<dataset>/annotations/beats/<stem>.beats")
+    p.add_argument("--names", type=str, nargs="+", default=None, help="evaluate only these pieces (<stem>)")
+    p.add_argument("--gpu", type=int, default=0, help="index of the ROCm device")
+    p.add_argument("--eval-trim-beats", "--eval_trim_beats", dest="eval_trim_beats", metavar="SECONDS", type=float,
+                   default=5.0, help="skip the first given seconds per piece in evaluating (default: %(default)s)")
+    p.add_argument("--dbn", default=False, action=argparse.BooleanOptionalAction, help="madmom-style DBN post-processing")
+    p.add_argument("--precision", choices=tuple(PRECISIONS), default="half",
+                   help="model precision: half (the reference's 16-mixed evaluation, default), f32x3 or exact fp32")
+    p.add_argument("--aggregation-type", choices=("mean-std",), default="mean-std",
+                   help="aggregation for multiple models (mean-std only; k-fold is not supported)")
+    p.add_argument("--dump-predictions", metavar="FILENAME", type=str, default=None,
+                   help="file to write predictions to, in .npz format (optional; single model only)")
+    return p
+
+
+def main(argv=None) -> int:
+    args = get_parser().parse_args(argv)
+    device = f"cuda:{args.gpu}"
+    kw = dict(float16=PRECISIONS[args.precision], dbn=args.dbn, eval_trim_beats=args.eval_trim_beats, device=device,
+              names=args.names)
+    if len(args.models) == 1:
+        print("Single model prediction for", args.models[0])
+        print("Computing predictions ...")
+        res = evaluate_bundle(args.models[0], args.bundle, args.annotations, **kw)
+        print("Metrics")
+        for k, v in res["averaged"].items():
+            print(f"{k}: {v}")
+        print("Dataset metrics")
+        for k, v in res["dataset_metrics"].items():
+            print(k)
+            for d, value in v.items():
+                print(f"{d}: {value}")
+            print("------")
+        if args.dump_predictions:
+            write_predictions(args.dump_predictions, res["predictions"], res["piece"])
+        return 0
+    if args.dump_predictions:
+        print("cannot dump predictions when doing inference for multiple models")
+        return 0
+    all_metrics = []
+    for ckpt in args.models:
+        print("Computing predictions ...")
+        all_metrics.append(evaluate_bundle(ckpt, args.bundle, args.annotations, **kw)["averaged"])
+    print("Metrics")
+    for k in all_metrics[0]:
+        vals = [m[k] for m in all_metrics]
+        print(f"{k}: {round(np.mean(vals), 3)} +- {round(np.std(vals), 3)}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

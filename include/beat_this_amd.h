@@ -333,6 +333,40 @@ int bt_dbn_host(const void* tables, const double* beat, const double* downbeat, 
 /* HOST: the same from a combined activation act [n][2] (madmom's processor input: beat-not-downbeat, downbeat) */
 int bt_dbn_host_act(const void* tables, const double* act, int64_t n, int32_t* rows, int32_t* n_rows);
 
+/* Beat-tracking metrics (the reference's Metrics, pl_module.py:320-339, behind launch_scripts/compute_paper_metrics.py;
+ * csrc/metrics.hip): mir_eval.beat's trim_beats, f_measure, cemgil and continuity restated from mir_eval's published
+ * algorithm (0.7 / 0.8: beat.py trim_beats, validate, _get_reference_beat_variations, f_measure, cemgil, continuity;
+ * util.py match_events, _fast_hit_windows, f_measure, validate_events), fp64 throughout.  Not pinned against mir_eval.
+ *
+ * Tracks come in CSR form: track k's reference beats are ref[ref_off[k] .. ref_off[k + 1]), its estimates
+ * est[est_off[k] .. est_off[k + 1]) (int64 offsets, n_tracks + 1 of each).  Both are trimmed to the events >= min_beat_time
+ * (trim_beats; -INFINITY keeps all), then scored with the match window f_window (reference 0.07 s), cemgil_sigma (0.04 s)
+ * and the continuity thresholds phase_thr / period_thr (0.175, 0.175).  Output: n_tracks rows of BT_METRICS_COLS doubles
+ *   F, P, R, Cemgil, CemgilMax, CMLc, CMLt, AMLc, AMLt, n_ref_trimmed, n_est_trimmed, status
+ * (F, Cemgil, CMLc .. AMLt as mir_eval returns them; P and R the precision and recall behind F).  status 0: a valid track.
+ * Otherwise the OR of BT_METRICS_* bits (reference array; << 3 for the estimates) and the 9 metrics are NaN: where
+ * mir_eval's validate raises (an event not finite, a kept event after 30000 s, kept events decreasing; the kept events must
+ * be a suffix of the array, as they are in any sorted one), unusable offsets, or -- device only -- estimates whose nearest
+ * annotation is not monotone (distinct events closer than the rounding of their distances; bt_beat_metrics_host scores those). */
+#define BT_METRICS_COLS 12
+#define BT_METRICS_NONFINITE 1
+#define BT_METRICS_UNSORTED 2
+#define BT_METRICS_LATE 4
+#define BT_METRICS_NEAREST 64
+#define BT_METRICS_OFFSETS 128
+/* device workspace of bt_beat_metrics (today it depends on n_tracks only) */
+size_t bt_beat_metrics_workspace_bytes(int n_tracks, int64_t total_ref, int64_t total_est);
+/* ragged metrics of n_tracks tracks, all pointers device memory, d_out n_tracks x BT_METRICS_COLS doubles.  Two launches on the
+ * stream, no synchronisation. */
+int bt_beat_metrics(void* stream, const double* d_ref, const int64_t* d_ref_off, const double* d_est, const int64_t* d_est_off,
+                    int n_tracks, double min_beat_time, double f_window, double cemgil_sigma, double phase_thr,
+                    double period_thr, void* d_ws, size_t ws_bytes, double* d_out);
+/* HOST: the same rows from host memory, by mir_eval's sequential loops (Cemgil may differ from the device's in the last bits:
+ * the device sums in a tree and its exp is not glibc's; every other column is bit-identical) */
+int bt_beat_metrics_host(const double* ref, const int64_t* ref_off, const double* est, const int64_t* est_off, int n_tracks,
+                         double min_beat_time, double f_window, double cemgil_sigma, double phase_thr, double period_thr,
+                         double* out);
+
 /* HOST: deduplicate_peaks(peaks, width) on its own (postprocessor.py:176-197): groups of ascending frame indices not more than
  * `width` apart (measured from the running mean) are replaced by their mean; out must hold n doubles */
 int bt_deduplicate_peaks_host(const int32_t* idx, int n, double width, double* out, int32_t* n_out);
