@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "metrics.hip", "engine.hip"]
+           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "engine.hip"]
 HEADERS = ["common.h", "chain.h", "kernels.h", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
@@ -176,6 +176,13 @@ EXPORTS = {
                                   C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bt_beat_metrics_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
                                        C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "bt_bce_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "bt_bce_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                              C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bt_bce_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int]),
+    "bt_bce_loss_host": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -189,7 +196,9 @@ FLAGS_BY_SOURCE = {"tail.hip": ["-Xclang", "-target-feature", "-Xclang", "-packe
                    # the DBN's Viterbi must repeat madmom's fp64 adds exactly: no multiply-add contraction anywhere in it
                    "dbn.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # the metrics repeat numpy's fp64 operations one by one (interp midpoints, distances, ratios)
-                   "metrics.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
+                   "metrics.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
+                   # the losses' fp32 terms must have the same bits on the host and the device (bt_bce_loss_host)
+                   "loss.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
 # compile-time switches: BT_DEV_BUILD=1 in the environment of build() compiles the development instrumentation (per-wave timing
 # dumps, ablation variants read by tools/*_probe.py) into the kernels; release builds contain none of it
 EXTRA_DEFINES = (["-DBT_DEV"] if os.environ.get("BT_DEV_BUILD") == "1" else []) + os.environ.get("BT_DEFINES", "").split()

@@ -2,15 +2,18 @@
 (README "Reproducing metrics from the paper") without Lightning, pandas or mir_eval.
 
     python -m beat_this_amd.evaluate --models final0.ckpt --bundle data/audio/spectrograms/gtzan.npz \\
-        --annotations data/annotations [--dbn] [--eval-trim-beats 5] [--dump-predictions preds.npz]
+        --annotations data/annotations [--dbn] [--eval-trim-beats 5] [--loss] [--dump-predictions preds.npz]
 
 Each bundle is one dataset (its file stem, e.g. ``gtzan``), holding ``<stem>/track`` spectrograms as the reference's
 preprocessing writes them; the beats of piece ``<stem>`` are read from ``<annotations>/<dataset>/annotations/beats/<stem>.beats``
 (dataset.py:108-124).  Predictions go through predict_bundle and the Postprocessor (minimal or DBN), and beats and downbeats are
-scored in one bt_beat_metrics call each (metrics.py)."""
+scored in one bt_beat_metrics call each (metrics.py).  With ``--loss`` the test loss of the reference's PLBeatThis.test_step
+(pl_module.py:99-114, 222-229) joins the metrics: the checkpoint's loss pair (loss.losses_from_hparams) on framewise targets
+built as the reference's prepare_annotations builds them, each piece scored alone in one bt_bce_loss call per target."""
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import sys
 
@@ -32,6 +35,45 @@ def load_beat_annotations(path):
     return beats, beats[a[:, 1].astype(int) == 1]
 
 
+def framewise_targets(path, frames, has_downbeats=None, fps=FPS):
+    """A ``.beats`` file -> (beat, downbeat, downbeat_mask) as the reference's dataset builds them for a whole piece
+    (dataset.py:108-142, prepare_annotations 512-535 with start 0 and end ``frames``): float32 arrays of ``frames`` with a 1 at
+    round(time * fps) for every beat inside [0, frames), and at the beats numbered 1 for the downbeats.  ``has_downbeats``:
+    the dataset's info.json flag; None: a two-column file has downbeats.  downbeat_mask is 1.0 or 0.0 (a piece without
+    downbeats does not count for the downbeat loss)."""
+    a = np.loadtxt(path, ndmin=2)
+    times = a[:, 0]
+    values = a[:, 1].astype(int) if a.shape[1] > 1 else np.zeros(times.size, int)
+    if has_downbeats is None:
+        has_downbeats = a.shape[1] > 1
+    f = np.round(times * fps).astype(int)
+    keep = (f >= 0) & (f < frames)
+    beat = np.zeros(frames, np.float32)
+    down = np.zeros(frames, np.float32)
+    beat[f[keep]] = 1
+    down[f[keep & (values == 1)]] = 1
+    return beat, down, np.float32(1.0 if has_downbeats else 0.0)
+
+
+def _has_downbeats(annotation_root, dataset):
+    """the ``has_downbeats`` flag of <annotations>/<dataset>/info.json, or None when there is no such file"""
+    path = os.path.join(annotation_root, dataset, "info.json")
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        return bool(json.load(f)["has_downbeats"])
+
+
+def _checkpoint_hparams(checkpoint):
+    if isinstance(checkpoint, dict):
+        return checkpoint.get("hyper_parameters", {})
+    if checkpoint is None:
+        return {}
+    from .inference import load_checkpoint
+
+    return load_checkpoint(checkpoint, "cpu").get("hyper_parameters", {})
+
+
 def _bundle_pieces(bundle, names):
     """the ``<stem>/track`` spectrograms of a bundle -> [(key, stem)]"""
     keys = [k for k in bundle.files if k.endswith("/track")]
@@ -42,7 +84,7 @@ def _bundle_pieces(bundle, names):
 
 
 def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float16=True, dbn=False, eval_trim_beats=5,
-                    device="cuda", spect2frames=None):
+                    device="cuda", spect2frames=None, loss=False, hyper_parameters=None):
     """Predict and score every piece of one bundle (or of a list of bundles, one dataset each).
 
     checkpoint: what Spect2Frames accepts (a local checkpoint file or a loaded checkpoint dict); ``spect2frames``: an
@@ -53,7 +95,9 @@ def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float1
 
     -> dict: "piece" (``<dataset>/<stem>/track.npy``, the reference's spect_path), "dataset" (per piece), "metrics" (per-piece
     arrays under the script's keys F-measure_beat, Cemgil_beat, CMLt_beat, AMLt_beat and the _downbeat ones; "Cemgil" is the
-    mean of mir_eval's (cemgil, cemgil_max) pair, as the script reports it), "averaged" and "dataset_metrics" (the means
+    mean of mir_eval's (cemgil, cemgil_max) pair, as the script reports it; with ``loss`` also loss_beat, loss_downbeat and
+    loss_total, the checkpoint's test loss per piece -- the loss type and pos_weights from ``hyper_parameters``, default the
+    checkpoint's), "averaged" and "dataset_metrics" (the means
     the script prints), "predictions" ([(beats, downbeats)]), "truth" ([(beats, downbeats)] within [0, frames / fps)) and
     "raw" (beat_metrics_many's full output for "beat" and "downbeat")."""
     from .bundle import SpectBundle, predict_bundle
@@ -65,8 +109,10 @@ def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float1
     post = Postprocessor(type="dbn" if dbn else "minimal", fps=FPS)
     paths = [bundle_path] if isinstance(bundle_path, (str, os.PathLike)) else list(bundle_path)
     pieces, datasets, preds, truths = [], [], [], []
+    logits, targets = [], []
     for path in paths:
         dataset = os.path.splitext(os.path.basename(os.fspath(path)))[0]
+        has_db = _has_downbeats(annotation_root, dataset) if loss else None
         with SpectBundle(path) as bundle:
             todo = _bundle_pieces(bundle, names)
             stems = dict(todo)
@@ -81,6 +127,9 @@ def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float1
                 preds.append((np.asarray(beats, np.float64), np.asarray(downbeats, np.float64)))
                 pieces.append(f"{dataset}/{stem}/track.npy")
                 datasets.append(dataset)
+                if loss:
+                    logits.append((beat, down))
+                    targets.append(framewise_targets(ann, frames, has_db))
     raw = {}
     metrics = {}
     for t, target in enumerate(("beat", "downbeat")):
@@ -91,6 +140,15 @@ def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float1
         metrics[f"Cemgil_{target}"] = res["Cemgil_reported"]
         metrics[f"CMLt_{target}"] = res["CMLt"]
         metrics[f"AMLt_{target}"] = res["AMLt"]
+    if loss:
+        from .loss import losses_from_hparams, piece_losses
+
+        hp = _checkpoint_hparams(checkpoint) if hyper_parameters is None else hyper_parameters
+        beat_loss, downbeat_loss = losses_from_hparams(hp)
+        metrics["loss_beat"] = piece_losses(beat_loss, [b for b, _ in logits], [t[0] for t in targets], names=pieces)
+        metrics["loss_downbeat"] = piece_losses(downbeat_loss, [d for _, d in logits], [t[1] for t in targets],
+                                                masks=[np.full(t[1].size, t[2], np.float32) for t in targets], names=pieces)
+        metrics["loss_total"] = metrics["loss_beat"] + metrics["loss_downbeat"]
     dataset = np.asarray(datasets)
     averaged = {k: np.mean(v) for k, v in metrics.items()}
     dataset_metrics = {k: {d: np.mean(v[dataset == d]) for d in np.unique(dataset)} for k, v in metrics.items()}
@@ -131,6 +189,9 @@ def get_parser() -> argparse.ArgumentParser:
                    help="model precision: half (the reference's 16-mixed evaluation, default), f32x3 or exact fp32")
     p.add_argument("--aggregation-type", choices=("mean-std",), default="mean-std",
                    help="aggregation for multiple models (mean-std only; k-fold is not supported)")
+    p.add_argument("--loss", default=False, action=argparse.BooleanOptionalAction,
+                   help="also report the checkpoint's test loss (loss_beat, loss_downbeat, loss_total; its loss_type and "
+                        "pos_weights) as the reference's test step logs it")
     p.add_argument("--dump-predictions", metavar="FILENAME", type=str, default=None,
                    help="file to write predictions to, in .npz format (optional; single model only)")
     return p
@@ -141,6 +202,8 @@ def main(argv=None) -> int:
     device = f"cuda:{args.gpu}"
     kw = dict(float16=PRECISIONS[args.precision], dbn=args.dbn, eval_trim_beats=args.eval_trim_beats, device=device,
               names=args.names)
+    if args.loss:
+        kw["loss"] = True
     if len(args.models) == 1:
         print("Single model prediction for", args.models[0])
         print("Computing predictions ...")

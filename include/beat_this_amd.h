@@ -367,6 +367,46 @@ int bt_beat_metrics_host(const double* ref, const int64_t* ref_off, const double
                          double min_beat_time, double f_window, double cemgil_sigma, double phase_thr, double period_thr,
                          double* out);
 
+/* Training losses (the reference's beat_this/model/loss.py: MaskedBCELoss, ShiftTolerantBCELoss, SplittedShiftTolerantBCELoss;
+ * csrc/loss.hip) with their gradients in the logits.  Rows come in CSR form: row r is elements
+ * offsets[r] .. offsets[r + 1] of logits, targets and mask (int64 offsets, n_rows + 1 of them; a (B, T) batch has equal
+ * steps).  kind BT_LOSS_*; tolerance in [0, BT_LOSS_MAX_TOLERANCE] (ignored by the masked loss); a row of T frames has
+ * T - 4 tolerance output frames (T for the masked loss) and needs T >= 1 + 4 tolerance.  Element types BT_LOSS_F32 / _F16 /
+ * _BF16 for the logits, _F32 / _F16 for the targets, _F32 / _U8 (bool) for the mask (mask NULL: all ones).  Terms are
+ * evaluated in fp32 (torch's formula with pos_weight) and summed in fp64, each row by segments of BT_LOSS_SEGMENT frames with
+ * fixed trees: the bits of a row do not depend on the other rows or the launch geometry. */
+#define BT_LOSS_MASKED 0
+#define BT_LOSS_SHIFT_TOLERANT 1
+#define BT_LOSS_SPLITTED 2
+#define BT_LOSS_F32 0
+#define BT_LOSS_F16 1
+#define BT_LOSS_BF16 2
+#define BT_LOSS_U8 3
+#define BT_LOSS_MAX_TOLERANCE 32
+#define BT_LOSS_SEGMENT 256
+/* device workspace of bt_bce_loss for n_rows rows of at most max_len frames (0: arguments out of range) */
+size_t bt_bce_loss_workspace_bytes(int n_rows, int64_t max_len);
+/* the loss of a ragged batch, all pointers device memory.  min_len / max_len: bounds of the rows' lengths the caller knows on
+ * the host (checked against the tolerance here; a row outside them gets a NaN sum and count -1 on the device).  pos_weight, or
+ * the fp32 scalar at d_pos_weight when that is not NULL.  Outputs, each optional: d_row_sum (n_rows doubles: the row's sum of
+ * weighted terms), d_row_count (n_rows int64: its output frames), d_loss (one scalar of loss_dtype: the sum over all rows
+ * divided by the count over all rows, the reference's mean), d_grad (fp32 per element: d(row sum)/d(logit), 0 where no window
+ * takes the frame), d_terms (fp32 per element: the frame's weighted term, 0 outside the output frames).  Two launches on the
+ * stream, no synchronisation, no atomics. */
+int bt_bce_loss(void* stream, int kind, int tolerance, float pos_weight, const float* d_pos_weight, const void* d_logits,
+                int logit_dtype, const void* d_targets, int target_dtype, const void* d_mask, int mask_dtype,
+                const int64_t* d_offsets, int n_rows, int64_t min_len, int64_t max_len, void* d_ws, size_t ws_bytes,
+                double* d_row_sum, int64_t* d_row_count, void* d_loss, int loss_dtype, float* d_grad, float* d_terms);
+/* backward of the mean: d_grad_in[i] = d_grad[i] * (*d_grad_output / count), written as grad_in_dtype (BT_LOSS_F32 / _F16 /
+ * _BF16); d_grad_output is one scalar of grad_output_dtype in device memory.  One launch, no synchronisation. */
+int bt_bce_loss_backward(void* stream, const float* d_grad, int64_t n, const void* d_grad_output, int grad_output_dtype,
+                         int64_t count, void* d_grad_in, int grad_in_dtype);
+/* HOST: the same from host memory, with the same fp32 terms, gathers and fp64 trees (row sums, terms and gradients bit-identical
+ * to the device's); *total (optional) = the mean.  Rows shorter than 1 + 4 tolerance are refused with BT_ERR_ARG. */
+int bt_bce_loss_host(int kind, int tolerance, float pos_weight, const void* logits, int logit_dtype, const void* targets,
+                     int target_dtype, const void* mask, int mask_dtype, const int64_t* offsets, int n_rows, double* row_sum,
+                     int64_t* row_count, double* total, float* grad, float* terms);
+
 /* HOST: deduplicate_peaks(peaks, width) on its own (postprocessor.py:176-197): groups of ascending frame indices not more than
  * `width` apart (measured from the running mean) are replaced by their mean; out must hold n doubles */
 int bt_deduplicate_peaks_host(const int32_t* idx, int n, double width, double* out, int32_t* n_out);
