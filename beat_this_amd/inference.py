@@ -32,7 +32,7 @@ import torch
 from . import _lib
 from .model import BeatThis
 from .pack import Engine
-from .postprocessor import Postprocessor
+from .postprocessor import PendingBeats, Postprocessor, _host_post
 from .preprocessing import LogMelSpect, load_audio
 from .utils import replace_state_dict_key, save_beat_tsv
 
@@ -43,10 +43,12 @@ CONCURRENT_SLICE_CHUNKS = 32  # ... from this many chunks on
 _SIDE_STREAMS: dict = {}
 
 
-def _side_streams(dev, n):
-    key = (torch.device(dev).index, n)
+def _side_streams(main, n):
+    """The ``n`` side streams of a batch issued on the stream ``main``: every caller stream has its own, so host threads on
+    their own streams never share one -- nor the workspace the engine keeps per stream."""
+    key = (main, n)
     if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = [torch.cuda.Stream(dev) for _ in range(n)]
+        _SIDE_STREAMS[key] = [torch.cuda.Stream(main.device) for _ in range(n)]
     return _SIDE_STREAMS[key]
 
 
@@ -155,15 +157,14 @@ USE_ONE_CALL = True  # Audio2Beats.__call__: one track = ONE library call (bt_au
 ONE_CALL_MAX_CHUNKS = 96   # longer tracks (> 47 minutes) take the sliced path
 
 
-def _graphed_forward(model, spect: torch.Tensor, starts: np.ndarray, T: int):
+def _graphed_forward(model, spect: torch.Tensor, starts: np.ndarray, T: int, prec):
     """The chunks of one piece through a captured forward (pack.Engine.graph_forward): the chunk gather writes straight into
     the graph's input buffer and the aggregation reads the graph's logits -- no launches from the host but three, no copies.
-    -> (beat, downbeat, device starts), or None when the model is not a BeatThis on its fused path, the piece is too long,
-    graphs are off, or the range guard of BT_PREC_F32X3 fired (the caller then takes the ordinary path, fallback included)."""
+    -> (beat, downbeat, device starts), or None when the model is not a BeatThis on its fused path, the piece is too long or
+    graphs are off.  The range flag of BT_PREC_F32X3 is looked at now: if it fired, the piece runs on the exact path instead."""
     if not USE_GRAPHS or not isinstance(model, BeatThis) or len(starts) > Engine.GRAPH_MAX_CHUNKS or _model_hooked(model):
         return None
     eng = model.engine()
-    prec = model._precision()
     entry = eng.graph_forward(len(starts), T, prec)
     if entry is None:
         return None
@@ -174,7 +175,8 @@ def _graphed_forward(model, spect: torch.Tensor, starts: np.ndarray, T: int):
                                               entry.x.data_ptr()))
         entry.replay()
         if prec == _lib.PREC_F32X3 and int(entry.flag.item()) != 0:
-            return None   # (operands beyond the fp16 range: the ordinary path repeats the piece and counts the fallback)
+            eng._count_fallback()   # (operands beyond the fp16 range)
+            return _chunk_logits(model, spect, starts, T, _lib.PREC_F32, None)
     return entry.beat, entry.down, d_starts
 
 
@@ -184,20 +186,42 @@ def _model_hooked(model) -> bool:
     return _hooked_below(model) or bool(model._forward_hooks or model._forward_pre_hooks)
 
 
-def _run_batched(model, chunks: torch.Tensor):
-    """model over (B,T,128) in equal slices of at most MAX_CHUNKS_PER_LAUNCH -> beat, downbeat (B,T)."""
+def _run_batched(model, chunks: torch.Tensor, prec=None, checks=None):
+    """model over (B,T,128) in equal slices of at most MAX_CHUNKS_PER_LAUNCH -> beat, downbeat (B,T).  A BeatThis without
+    hooks runs at ``prec`` with ``checks`` (BeatThis._run); any other model through its forward."""
     B = chunks.shape[0]
     step = -(-B // max(1, -(-B // MAX_CHUNKS_PER_LAUNCH)))
-    outs = [model(chunks[i: i + step]) for i in range(0, B, step)]
+    if isinstance(model, BeatThis) and not _model_hooked(model):
+        outs = [model._run(chunks[i: i + step], 0, 2, prec=prec, checks=checks) for i in range(0, B, step)]
+    else:
+        outs = [(o["beat"], o["downbeat"]) for o in (model(chunks[i: i + step]) for i in range(0, B, step))]
     if len(outs) == 1:
-        return outs[0]["beat"], outs[0]["downbeat"]
-    return torch.cat([o["beat"] for o in outs]), torch.cat([o["downbeat"] for o in outs])
+        return outs[0]
+    return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+
+
+def _chunk_logits(model, spect: torch.Tensor, starts: np.ndarray, T: int, prec, checks):
+    """The chunks of one piece gathered and run through ``model`` (_run_batched) -> (beat, downbeat, device starts)."""
+    chunks, d_starts = _gather_chunks(spect, starts, T)
+    cb, cd = _run_batched(model, chunks, prec, checks)
+    return cb.float().contiguous(), cd.float().contiguous(), d_starts
+
+
+def _model_precision(model):
+    """BT_PREC_* a BeatThis runs at now (autocast, ``fp32_split_gemms``); None for any other model."""
+    return model._precision() if isinstance(model, BeatThis) else None
 
 
 def split_predict_aggregate(spect: torch.Tensor, chunk_size: int, border_size: int, overlap_mode: str,
                             model) -> dict:
     """Chunk a (T,128) piece, predict, aggregate (inference.py:188-230).  ``model`` is any callable
     (B,T,128) -> {"beat": (B,T), "downbeat": (B,T)}; all chunks go through it as ONE batch."""
+    return _split_predict(spect, chunk_size, border_size, overlap_mode, model, _model_precision(model), None)
+
+
+def _split_predict(spect, chunk_size, border_size, overlap_mode, model, prec, checks) -> dict:
+    """``split_predict_aggregate`` at precision ``prec`` (_model_precision); ``checks``: see Engine.forward_stages (a piece
+    whose range flags are collected does not take the captured forward, which looks at its flag at once)."""
     _lib.require_gpu(spect, "spectrogram")
     if spect.dim() != 2 or spect.shape[1] != 128:
         raise ValueError(f"expected a (frames, 128) spectrogram, got {tuple(spect.shape)}")
@@ -208,13 +232,8 @@ def split_predict_aggregate(spect: torch.Tensor, chunk_size: int, border_size: i
         return {"beat": empty, "downbeat": empty.clone()}
     starts = chunk_starts(n, chunk_size, border_size)
     T = chunk_length(n, chunk_size, border_size)
-    fast = _graphed_forward(model, spect, starts, T) if overlap_mode == "keep_first" else None
-    if fast is not None:
-        cb, cd, d_starts = fast
-    else:
-        chunks, d_starts = _gather_chunks(spect, starts, T)
-        cb, cd = _run_batched(model, chunks)
-        cb, cd = cb.float().contiguous(), cd.float().contiguous()
+    fast = _graphed_forward(model, spect, starts, T, prec) if overlap_mode == "keep_first" and checks is None else None
+    cb, cd, d_starts = fast if fast is not None else _chunk_logits(model, spect, starts, T, prec, checks)
     if overlap_mode != "keep_first":  # "keep_last": reference-compatible torch glue
         preds = [{"beat": cb[i], "downbeat": cd[i]} for i in range(len(starts))]
         beat, down = aggregate_prediction(preds, starts, n, chunk_size, border_size, overlap_mode, spect.device)
@@ -408,7 +427,7 @@ class Audio2Beats(Audio2Frames):
         beat_logits, downbeat_logits = super().__call__(signal, sr)
         return self.frames2beats(beat_logits, downbeat_logits)
 
-    def _one_call(self, signal, sr, exact=False):
+    def _one_call(self, signal, sr):
         """``__call__`` as ONE library call (bt_audio2beats_enqueue, include/beat_this_amd.h): the mono mix and the upload of the
         waveform happen here like in ``signal2spect`` (inference.py:269-277), then resampler, log-mel, chunk gather, the forward
         (a hipGraph the library captures itself), aggregation, peak picking and the device-to-host copy of the peak frames are
@@ -433,45 +452,42 @@ class Audio2Beats(Audio2Frames):
         g = gcd(sr, 22050)
         up, down = 22050 // g, sr // g
         eng = model.engine()
-        if eng._h_prof_on() or eng._deferred is not None:
+        n_in = int(signal.shape[0])
+        if eng.profiling or n_in == 0:
             return None
         with torch.inference_mode(), torch.autocast(enabled=self.float16, device_type=dev.type):
-            prec = _lib.PREC_F32 if exact else model._precision()
+            first = model._precision()
         lib = _lib.lib()
-        plan = _lib.A2BPlan()
-        n_in = int(signal.shape[0])
-        if n_in == 0:
-            return None
-        _lib.check(lib.bt_audio2beats_plan(eng._h, n_in, up, down, prec, C.byref(plan)))
-        if plan.B > ONE_CALL_MAX_CHUNKS:
-            return None
-        eng.ensure_positions(plan.T)
-        with torch.cuda.device(dev):
-            # (from_numpy + one H2D copy: torch.tensor(array, device=...) copies the 5 MB of a 30 s file on the host first)
-            wave = torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32)).to(dev) if not isinstance(signal, torch.Tensor) \
-                else signal.to(dev, torch.float32).contiguous()
-            if self.spect.device != dev:
-                self.spect.to(dev)
-            h, half = _resample_filter(up, down, dev) if up != down else (None, 0)
-            ws = eng._a2b_workspace(plan.ws_bytes)
+        # BT_PREC_F32X3: if an operand left the fp16 range of a hi part, the exact fp32 path repeats the call
+        for prec in (first, _lib.PREC_F32):
+            plan = _lib.A2BPlan()
+            _lib.check(lib.bt_audio2beats_plan(eng._h, n_in, up, down, prec, C.byref(plan)))
+            if plan.B > ONE_CALL_MAX_CHUNKS:
+                return None
+            eng.ensure_positions(plan.T)
             host = self.frames2beats._pinned(plan.result_words)
-            _lib.check(lib.bt_audio2beats_enqueue(eng._h, _lib.stream_ptr(dev), prec, C.byref(self.spect._get_tables()),
-                                                  wave.data_ptr(), n_in, up, down, _lib.ptr(h), half, ws.data_ptr(), ws.numel(),
-                                                  host.data_ptr(), int(USE_GRAPHS and plan.T == Engine.GRAPH_T)))
-            torch.cuda.current_stream(dev).synchronize()
-        res = host.numpy()
-        n = int(plan.n_frames)
-        nb, nd, flag = int(res[2 * n]), int(res[2 * n + 1]), int(res[2 * n + 2])
-        out = None
-        if flag == 0:
-            from .postprocessor import _host_post
-
-            out = _host_post(res[:nb], res[n: n + nd], self.frames2beats.fps)
-        self.frames2beats.__dict__.setdefault("_pin_pool", []).append(host)
-        if flag != 0:   # BT_PREC_F32X3: an operand left the fp16 range of a hi part -- the exact fp32 path repeats the call
-            eng.last_fallbacks += 1
-            return self._one_call(signal, sr, exact=True)
-        return out
+            try:
+                with torch.cuda.device(dev):
+                    # (from_numpy + one H2D copy: torch.tensor(array, device=...) copies the 5 MB of a 30 s file on the host first)
+                    wave = torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32)).to(dev) \
+                        if not isinstance(signal, torch.Tensor) else signal.to(dev, torch.float32).contiguous()
+                    if self.spect.device != dev:
+                        self.spect.to(dev)
+                    h, half = _resample_filter(up, down, dev) if up != down else (None, 0)
+                    ws = eng._a2b_workspace(plan.ws_bytes)
+                    _lib.check(lib.bt_audio2beats_enqueue(eng._h, _lib.stream_ptr(dev), prec, C.byref(self.spect._get_tables()),
+                                                          wave.data_ptr(), n_in, up, down, _lib.ptr(h), half, ws.data_ptr(),
+                                                          ws.numel(), host.data_ptr(), int(USE_GRAPHS and plan.T == Engine.GRAPH_T)))
+                    torch.cuda.current_stream(dev).synchronize()
+                res = host.numpy()
+                n = int(plan.n_frames)
+                nb, nd = int(res[2 * n]), int(res[2 * n + 1])
+                if int(res[2 * n + 2]) == 0:   # (the range flag)
+                    return _host_post(res[:nb], res[n: n + nd], self.frames2beats.fps)
+            finally:
+                self.frames2beats._return_pinned(host)
+            eng._count_fallback()
+        return None
 
     def many(self, signals, sr):
         """Extension: [(beats, downbeats)] (seconds, float64 arrays as ``__call__`` returns them) for a list of waveforms
@@ -482,54 +498,51 @@ class Audio2Beats(Audio2Frames):
     def many_async(self, signals, sr):
         """``many`` without the final wait: all GPU work and the device-to-host copy of the peak indices are enqueued;
         ``.result()`` of the returned handle waits for the copy and runs the host step.  Submitting batch i + 1 before
-        collecting batch i keeps the GPU busy during the host step (bench.py does)."""
+        collecting batch i keeps the GPU busy during the host step (bench.py does).  ``.logits``: the batch's framewise
+        logits (beat, downbeat, frame_off), concatenated."""
         spect, frame_off = self.signal2spect_many(signals, sr)
-        # float16="f32x3": the range flags of the forward slices are collected, not waited for; ``result()`` looks at them
-        # once the batch's device-to-host copy has arrived and repeats the batch on the exact fp32 path if one fired
-        native_dbn = isinstance(self.frames2beats, Postprocessor) and self.frames2beats.type == "dbn"
-        if self.frames2beats.type != "minimal" and not native_dbn:
-            # a DBN-type post-processor of another kind runs on the host right away and needs final logits: the range
-            # flags are looked at -- and the batch repeated on the exact path if one fired -- before it sees them (checks=None: the synchronous guard)
-            beat, down = self.spect2frames_batch(spect, frame_off)
+        return self._frames2beats_async(spect, frame_off)
 
-            class _Done:
-                def __init__(s, out): s.out, s.logits = out, (beat, down, frame_off)
-                def result(s): return s.out
-            return _Done([self.frames2beats(beat[frame_off[k]: frame_off[k + 1]], down[frame_off[k]: frame_off[k + 1]])
-                          for k in range(len(signals))])
-        checks = [] if isinstance(self.model, BeatThis) and self.model.fp32_split_gemms and not self.float16 else None
-        beat, down = self.spect2frames_batch(spect, frame_off, checks=checks)
-        pending = self.frames2beats.ragged_async(beat, down, frame_off)   # (minimal or this library's DBN: both on the device)
-        pending.logits = (beat, down, frame_off)   # framewise logits of the batch (concatenated), for callers that want them
+    def _frames2beats_async(self, spect, frame_off, prec=None):
+        """``many_async`` from the spectrogram on, at precision ``prec`` (None: the model's, read once here)."""
+        post = self.frames2beats
+        on_device = post.type == "minimal" or (isinstance(post, Postprocessor) and post.type == "dbn")
+        with torch.inference_mode(), torch.autocast(enabled=self.float16, device_type=self.device.type):
+            if prec is None:
+                prec = _model_precision(self.model)
+            # float16="f32x3" with a post-processor on the device: the range flags of the forwards are collected, not waited
+            # for; ``result()`` looks at them once the batch's device-to-host copy has arrived and repeats the batch on the
+            # exact fp32 path if one fired.  A DBN-type post-processor of another kind runs on the host right away and needs
+            # final logits: checks=None, the flags are looked at -- and the batch repeated if one fired -- before it sees them.
+            checks = [] if on_device and prec == _lib.PREC_F32X3 else None
+            beat, down = _batch_predict(spect, frame_off, 1500, 6, self.model, prec, checks)
+        if on_device:
+            pending = post.ragged_async(beat, down, frame_off)
+        else:
+            pending = PendingBeats([post(beat[frame_off[k]: frame_off[k + 1]], down[frame_off[k]: frame_off[k + 1]])
+                                    for k in range(len(frame_off) - 1)])
+        pending.logits = (beat, down, frame_off)
         if checks:
-            return _GuardedPending(pending, checks, lambda: self._many_exact_async(signals, sr))
+            return _GuardedPending(pending, self.model.engine(), checks,
+                                   lambda: self._frames2beats_async(spect, frame_off, _lib.PREC_F32))
         return pending
-
-    def _many_exact_async(self, signals, sr):
-        """``many_async`` on the exact fp32 MFMA path (the repeat of a BT_PREC_F32X3 batch whose range flag fired)."""
-        old = self.model.fp32_split_gemms
-        self.model.fp32_split_gemms = False
-        try:
-            return self.many_async(signals, sr)
-        finally:
-            self.model.fp32_split_gemms = old
 
 
 class _GuardedPending:
-    """A pending ``many_async`` result of the BT_PREC_F32X3 path: ``result()`` also evaluates the forward slices' range
-    flags (they arrived with / before the peak indices) and repeats the batch on the exact path when one fired."""
+    """A pending ``many_async`` result of the BT_PREC_F32X3 path: ``result()`` also evaluates the forwards' range flags
+    (they arrived with / before the peak indices) and repeats the batch on the exact path when one fired."""
 
-    def __init__(self, inner, checks, redo):
-        self.inner, self.checks, self.redo = inner, checks, redo
+    def __init__(self, inner, eng, checks, redo):
+        self.inner, self.eng, self.checks, self.redo = inner, eng, checks, redo
         self.logits = inner.logits
 
     def result(self):
         out = self.inner.result()
-        if self.checks and any(eng.range_exceeded(chk) for eng, chk in self.checks):
+        if self.checks and self.eng.range_exceeded(self.checks):
             self.inner = self.redo()           # (the exact path: no flags of its own)
             self.logits = self.inner.logits    # ... and its logits replace the overflowed ones
             out = self.inner.result()
-        self.checks = None
+        self.checks = self.redo = None   # (the repeat holds the batch's spectrogram)
         return out
 
 
@@ -564,28 +577,23 @@ def batch_predict_aggregate(spect: torch.Tensor, frame_off, chunk_size: int, bor
     ``chunk_size - 2 border_size`` frames share one chunk table: their chunks are gathered slice by slice
     (MAX_CHUNKS_PER_LAUNCH) straight into the model and aggregated by one launch; shorter pieces (one odd-length chunk
     each) go through ``split_predict_aggregate`` one by one.
-    A ``BeatThis`` with ``fp32_split_gemms`` (BT_PREC_F32X3) runs its forward slices without waiting for their range flags
-    (``Engine.deferred_range_checks``): with ``checks=None`` the flags are looked at before returning and the batch is
-    repeated on the exact fp32 path if one fired; a caller that passes a list gets ``(engine, flags)`` appended instead and
-    evaluates them itself (``Audio2Beats.many_async``)."""
-    guard = isinstance(model, BeatThis) and model._precision() == _lib.PREC_F32X3
-    if guard:
-        eng = model.engine()
-        eng.ensure_positions(chunk_size)   # (the rotary table cannot grow while range checks are pending: grow it first)
-        with eng.deferred_range_checks() as flags:
-            out = batch_predict_aggregate(spect, frame_off, chunk_size, border_size, _Unguarded(model))
-        if checks is not None:
-            checks.append((eng, flags))
+    A ``BeatThis`` with ``fp32_split_gemms`` (BT_PREC_F32X3) runs its forwards without waiting for their range flags: with
+    ``checks=None`` the flags are looked at before returning and the batch is repeated on the exact fp32 path if one fired;
+    a caller that passes a list gets the flags appended instead (Engine.forward_stages) and evaluates them itself with
+    ``model.engine().range_exceeded`` (``Audio2Beats.many_async``)."""
+    return _batch_predict(spect, frame_off, chunk_size, border_size, model, _model_precision(model), checks)
+
+
+def _batch_predict(spect, frame_off, chunk_size, border_size, model, prec, checks):
+    """``batch_predict_aggregate`` at precision ``prec`` (_model_precision)."""
+    if prec != _lib.PREC_F32X3:
+        checks = None   # (no range flags: nothing to collect)
+    elif checks is None:
+        flags = []
+        out = _batch_predict(spect, frame_off, chunk_size, border_size, model, prec, flags)
+        if not model.engine().range_exceeded(flags):
             return out
-        if eng.range_exceeded(flags):
-            model.fp32_split_gemms = False
-            try:
-                return batch_predict_aggregate(spect, frame_off, chunk_size, border_size, model)
-            finally:
-                model.fp32_split_gemms = True
-        return out
-    if isinstance(model, _Unguarded):
-        model = model.model
+        prec = _lib.PREC_F32   # (the batch again, on the exact path)
     _lib.require_gpu(spect, "spectrogram")
     if spect.dim() != 2 or spect.shape[1] != 128:
         raise ValueError(f"expected a (frames, 128) spectrogram, got {tuple(spect.shape)}")
@@ -602,7 +610,7 @@ def batch_predict_aggregate(spect: torch.Tensor, frame_off, chunk_size: int, bor
         if n == 0:
             continue
         if n <= chunk_size - 2 * border_size:  # a single (n + 2 border)-frame chunk
-            r = split_predict_aggregate(spect[lo:hi], chunk_size, border_size, "keep_first", model)
+            r = _split_predict(spect[lo:hi], chunk_size, border_size, "keep_first", model, prec, checks)
             beat[lo:hi], down[lo:hi] = r["beat"], r["downbeat"]
             continue
         c0 = len(rows)
@@ -627,7 +635,7 @@ def batch_predict_aggregate(spect: torch.Tensor, frame_off, chunk_size: int, bor
     step = -(-B // n_slices)                 # (66 chunks -> 33 + 33, not 64 + 2)
     with torch.cuda.device(dev):
         main = torch.cuda.current_stream(dev)
-        side = _side_streams(dev, min(n_slices, CONCURRENT_STREAMS)) if n_slices > 1 and CONCURRENT_STREAMS > 1 else [main]
+        side = _side_streams(main, min(n_slices, CONCURRENT_STREAMS)) if n_slices > 1 and CONCURRENT_STREAMS > 1 else [main]
         if side[0] is not main:
             ready = torch.cuda.Event()
             ready.record(main)
@@ -641,7 +649,7 @@ def batch_predict_aggregate(spect: torch.Tensor, frame_off, chunk_size: int, bor
                 _lib.check(lib.bt_split_chunks_batch(_lib.stream_ptr(dev), spect.data_ptr(), d_rows[4 * i:].data_ptr(), nb,
                                                      chunk_size, chunks.data_ptr()))
                 if isinstance(model, BeatThis) and not _model_hooked(model):
-                    model._run(chunks, 0, 2, out=(cb[i: i + nb], cd[i: i + nb]))   # logits straight into their rows
+                    model._run(chunks, 0, 2, out=(cb[i: i + nb], cd[i: i + nb]), prec=prec, checks=checks)   # logits straight into their rows
                 else:
                     r = model(chunks)
                     cb[i: i + nb], cd[i: i + nb] = r["beat"], r["downbeat"]
@@ -654,13 +662,6 @@ def batch_predict_aggregate(spect: torch.Tensor, frame_off, chunk_size: int, bor
                                           len(pieces), max_frames, chunk_size, border_size, beat.data_ptr(),
                                           down.data_ptr()))
     return beat, down
-
-
-class _Unguarded:
-    """Marks a model whose range checks the caller has already taken over (batch_predict_aggregate's inner call)."""
-
-    def __init__(self, model):
-        self.model = model
 
 
 def resample_gpu(signal: torch.Tensor, in_rate: int, out_rate: int) -> torch.Tensor:

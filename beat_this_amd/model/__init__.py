@@ -255,9 +255,9 @@ class BeatThis(_TracksChildren, nn.Module):
             return _lib.PREC_HALF
         return _lib.PREC_F32X3 if self.fp32_split_gemms and not _lib.lib().bt_half_is_bf16() else _lib.PREC_F32
 
-    def _run(self, x: torch.Tensor, first: int, last: int, out=None):
-        """Stages first..last in the engine; precision follows autocast like the whole forward.  ``out``: see
-        Engine.forward_stages."""
+    def _run(self, x: torch.Tensor, first: int, last: int, out=None, prec=None, checks=None):
+        """Stages first..last in the engine at ``prec`` (BT_PREC_*; None: follows autocast like the whole forward).  ``out``
+        (the logits' tensors) and ``checks`` (where the range flag goes; None: looked at now): see Engine.forward_stages."""
         if x.dim() != 3:
             raise ValueError(f"expected a (batch, time, features) input, got {tuple(x.shape)}")
         _lib.require_gpu(x, "stage input")
@@ -265,7 +265,8 @@ class BeatThis(_TracksChildren, nn.Module):
             D = self.hparams["transformer_dim"]
             empty = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
             return (empty, empty.clone()) if last == 2 else torch.empty((x.shape[0], x.shape[1], D), dtype=torch.float32, device=x.device)
-        return self.engine().forward_stages(x, self._precision(), first, last, logits_out=out)
+        prec = self._precision() if prec is None else prec
+        return self.engine().forward_stages(x, prec, first, last, logits_out=out, checks=checks)
 
     def _run_unit(self, x: torch.Tensor, kind: str, index: int):
         """A sub-module call (see _Node): reference layouts in and out, fp32 results; precision follows autocast (the hi + lo

@@ -8,6 +8,7 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import math
+import threading
 
 import torch
 
@@ -230,14 +231,24 @@ class PackedModel:
         self._keep.append(t)
         return t.data_ptr()
 
-    def ensure_hl8(self) -> bool:
-        """Pack the hl8 (BT_OPT_X3_GEMM_FP8) forms of the main layers' GEMM weights if that has not happened yet; -> True when
-        bt_pair_weights fields changed (a bt_engine copies its description at creation: the caller re-creates the handle)."""
+    def ensure_hl8(self):
+        """Pack the hl8 (BT_OPT_X3_GEMM_FP8) forms of the main layers' GEMM weights if that has not happened yet.  -> None when
+        nothing changed, else a function that puts the description and the work list back: a bt_engine copies its description
+        at creation, so the caller re-creates the handle and calls it if that fails (Engine._rebuild_handle)."""
         todo, self._hl8_todo = self._hl8_todo, []
+        if not todo:
+            return None
+        old, n_keep = [(pw, field, getattr(pw, field)) for pw, field, _, _ in todo], len(self._keep)
         for pw, field, src, rows in todo:
             w = self._by_ptr[getattr(pw, src)[0]][:rows].cpu()
             setattr(pw, field, self._hl8(w))
-        return bool(todo)
+
+        def undo():
+            for pw, field, value in old:
+                setattr(pw, field, value)
+            del self._keep[n_keep:]
+            self._hl8_todo = todo
+        return undo
 
     def _pair(self, pw, sd, pa: str, pf: str, dim: int, x3: bool = False) -> None:
         heads = dim // 32
@@ -358,7 +369,12 @@ class Engine:
         # Footprint: ~66 MB (fp32) / ~45 MB (half) per chunk and stream; inference.py runs slices of <= 96 chunks
         # (MAX_CHUNKS_PER_LAUNCH) on the caller's stream + CONCURRENT_STREAMS side streams.
         self._ws = collections.OrderedDict()
-        self._deferred = None      # list collecting (pinned flag, event) pairs while deferred_range_checks() is active
+        self._graphs = collections.OrderedDict()   # (stream, B, T, prec) -> captured forward (graph_forward)
+        self._graph_ws = {}        # stream -> workspace of the captured forwards replayed on it
+        self._a2b_ws = {}          # stream -> (workspace, small requests in a row) of Audio2Beats' one-call path
+        self._graphs_ok = True     # False once a capture failed: plain launches from then on
+        self.profiling = False     # set while bt_profile_begin records (bench.py): no captured forwards meanwhile
+        self._lock = threading.Lock()
         self.last_fallbacks = 0    # BT_PREC_F32X3 forwards whose range flag fired (and were repeated in exact fp32)
 
     def __del__(self):
@@ -381,8 +397,10 @@ class Engine:
         for name in opts:
             if name not in self.OPTIONS:
                 raise ValueError(f"unknown engine option {name!r} (known: {sorted(self.OPTIONS)})")
-        if int(opts.get("x3_gemm_fp8", 0)) > 0 and self.packed.ensure_hl8():
-            self._recreate_handle()   # (the hl8 weights were packed just now: the handle's copy of the description is stale)
+        if int(opts.get("x3_gemm_fp8", 0)) > 0:
+            undo = self.packed.ensure_hl8()
+            if undo is not None:   # (the hl8 weights were packed just now: the handle's copy of the description is stale)
+                self._rebuild_handle(undo)
         for name, value in opts.items():
             _lib.check(_lib.lib().bt_engine_set_option(self._h, self.OPTIONS[name], int(value)))
         self._drop_graphs()
@@ -390,20 +408,27 @@ class Engine:
     def _drop_graphs(self) -> None:
         """Captured forwards replay the kernels / tables they were recorded with: dropped together with their per-stream
         workspaces (up to ~0.9 GB for 11 chunks), which nothing else refers to."""
-        self.__dict__.pop("_graphs", None)
-        self.__dict__.pop("_graph_ws", None)
+        self._graphs = collections.OrderedDict()
+        self._graph_ws = {}
 
-    def _recreate_handle(self) -> None:
-        """A new bt_engine from the (changed) description, options carried over; the old handle is released afterwards."""
-        if self._deferred is not None:
-            raise RuntimeError("the engine cannot be re-created while range checks of earlier forwards are pending")
-        torch.cuda.synchronize(self.device)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().bt_engine_create(C.byref(self.packed.desc), C.byref(h)))
-        for name in self.OPTIONS:
-            _lib.check(_lib.lib().bt_engine_set_option(h, self.OPTIONS[name], self.get_option(name)))
-        old_h, self._h = self._h, h
-        _lib.lib().bt_engine_destroy(old_h)
+    def _rebuild_handle(self, undo) -> None:
+        """A new bt_engine from the (changed) ``packed.desc``, options carried over, in place of the old one, which is released
+        afterwards together with the captured forwards (they hold the old tables' addresses).  If the new handle cannot be
+        made, ``undo()`` puts the old description back -- the old handle stays in effect -- and the error is raised.  Calls
+        on other threads must not overlap this."""
+        torch.cuda.synchronize(self.device)   # (nothing may still be reading what the old description points to)
+        lib, h = _lib.lib(), C.c_void_p()
+        try:
+            _lib.check(lib.bt_engine_create(C.byref(self.packed.desc), C.byref(h)))
+            for name, opt in self.OPTIONS.items():
+                _lib.check(lib.bt_engine_set_option(h, opt, self.get_option(name)))
+        except Exception:
+            if h.value:
+                lib.bt_engine_destroy(h)
+            undo()
+            raise
+        old, self._h = self._h, h   # swap first, then release: self._h never dangles
+        lib.bt_engine_destroy(old)  # (its profiling records, if a bench leg had some open, go with it)
         self._drop_graphs()
 
     def get_option(self, name: str) -> int:
@@ -416,22 +441,13 @@ class Engine:
         takes any length, beat_tracker.py:188-192): grow the table to the next multiple of 512 and re-create the handle."""
         if T <= self.packed.desc.rope_len:
             return
-        if self._deferred is not None:
-            raise RuntimeError("the rotary table cannot grow while range checks of earlier forwards are pending")
-        torch.cuda.synchronize(self.device)   # (nothing may still be reading the old table when it is released)
-        old_rope, old_len, old_t = self.packed.desc.rope, self.packed.desc.rope_len, self.packed._rope_t
-        self.packed.set_positions(-(-T // 512) * 512)
-        h = C.c_void_p()
-        try:
-            _lib.check(_lib.lib().bt_engine_create(C.byref(self.packed.desc), C.byref(h)))
-        except Exception:   # the old handle (and its table) stay valid
-            self.packed.desc.rope, self.packed.desc.rope_len, self.packed._rope_t = old_rope, old_len, old_t
-            raise
-        self._drop_graphs()   # (captured forwards hold the old table's address)
-        for name in self.OPTIONS:            # the new handle inherits the old one's options
-            _lib.check(_lib.lib().bt_engine_set_option(h, self.OPTIONS[name], self.get_option(name)))
-        old_h, self._h = self._h, h       # swap first, then release: self._h never dangles
-        _lib.lib().bt_engine_destroy(old_h)   # (its profiling records, if a bench leg had some open, go with it)
+        p = self.packed
+        old = p.desc.rope, p.desc.rope_len, p._rope_t   # (the old table stays alive until the old handle is gone)
+        p.set_positions(-(-T // 512) * 512)
+
+        def undo():
+            p.desc.rope, p.desc.rope_len, p._rope_t = old
+        self._rebuild_handle(undo)
 
     def _workspace(self, need: int) -> torch.Tensor:
         key = torch.cuda.current_stream(self.device)
@@ -458,10 +474,13 @@ class Engine:
         """spect: (B, T, 128) fp32 on the engine's device -> (beat, downbeat) fp32 (B, T)."""
         return self.forward_stages(spect, prec, 0, 2)
 
-    def forward_stages(self, spect: torch.Tensor, prec: int, first: int, last: int, logits_out=None):
+    def forward_stages(self, spect: torch.Tensor, prec: int, first: int, last: int, logits_out=None, checks=None):
         """Stages first..last of BeatThis.forward (0 frontend, 1 transformer_blocks, 2 task_heads; bt_forward_stages):
         (B, T, 128) or (B, T, D) fp32 in -> (B, T, D) fp32, or (beat, downbeat) when the head is included.
-        ``logits_out`` = (beat, downbeat): contiguous fp32 (B, T) tensors the logits are written into (last == 2 only)."""
+        ``logits_out`` = (beat, downbeat): contiguous fp32 (B, T) tensors the logits are written into (last == 2 only).
+        ``checks``: where the range flag of a BT_PREC_F32X3 forward goes -- None: looked at now, and a fired flag repeats
+        the call on the exact fp32 path; a list: a (pinned host copy, event) pair is appended without waiting, and the
+        caller decides with ``range_exceeded``."""
         _lib.require_gpu(spect, "stage input")
         B, T, M = spect.shape
         D = self.packed.desc.transformer_dim
@@ -491,16 +510,16 @@ class Engine:
                 # Range guard of the hi + lo split (include/beat_this_amd.h, BT_PREC_F32X3): the first word of the workspace is
                 # non-zero when an operand left the fp16 range of a hi part (the result then holds inf / NaN).  Default: look at
                 # it now (one stream synchronisation per forward) and repeat the batch on the exact fp32 MFMA path.  A caller
-                # that pipelines several forwards collects the flags instead (deferred_range_checks) and decides later.
+                # that pipelines several forwards collects the flags instead (``checks``) and decides later.
                 flag = ws[:4].view(torch.int32)
-                if self._deferred is not None:
+                if checks is not None:
                     host = torch.empty(1, dtype=torch.int32, pin_memory=True)
                     host.copy_(flag, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream(self.device))
-                    self._deferred.append((host, ev))
+                    checks.append((host, ev))
                 elif int(flag.item()) != 0:
-                    self.last_fallbacks += 1
+                    self._count_fallback()
                     return self.forward_stages(spect, _lib.PREC_F32, first, last, logits_out=logits_out)
         return (beat, down) if last == 2 else out
 
@@ -532,15 +551,14 @@ class Engine:
         """The whole forward of a (B, T, 128) batch as ONE hipGraph, for the single-file path (a 30 s file is 2 chunks = ~55
         launches whose host side is a sixth of the call): -> entry with ``.x`` (B, T, 128) to fill, ``.replay()`` and
         ``.beat`` / ``.down`` (B, T) holding the logits afterwards (valid until the next replay on the same stream), or None
-        where graphs are off / not applicable (T != GRAPH_T, too many chunks, pending range checks, profiling).  Entries are
-        per (stream, B, precision); a capture that fails -- or whose replay does not reproduce the plain launches -- switches
-        graphs off for this engine and the caller falls back to plain launches."""
-        if not getattr(self, "_graphs_ok", True) or T != self.GRAPH_T or B > self.GRAPH_MAX_CHUNKS or self._deferred is not None \
-                or self._h_prof_on():
+        where graphs are off / not applicable (T != GRAPH_T, too many chunks, profiling).  Entries are per (stream, B,
+        precision); a capture that fails -- or whose replay does not reproduce the plain launches -- switches graphs off for
+        this engine and the caller falls back to plain launches.  The caller reads the entry's range flag (``.flag``) itself."""
+        if not self._graphs_ok or T != self.GRAPH_T or B > self.GRAPH_MAX_CHUNKS or self.profiling:
             return None
         stream = torch.cuda.current_stream(self.device)
         key = (stream, B, T, prec)
-        e = self.__dict__.setdefault("_graphs", collections.OrderedDict()).pop(key, None)
+        e = self._graphs.pop(key, None)
         if e is None:
             try:
                 e = _GraphEntry(self, B, T, prec, stream)
@@ -549,7 +567,7 @@ class Engine:
                 self._graph_error = repr(err)
                 return None
         # (the dictionary again: constructing an entry may have grown the rotary table, which drops the captured forwards)
-        cache = self.__dict__.setdefault("_graphs", collections.OrderedDict())
+        cache = self._graphs
         cache[key] = e
         while len(cache) > self.GRAPH_MAX_ENTRIES:
             cache.popitem(last=False)
@@ -558,7 +576,7 @@ class Engine:
     def _graph_workspace(self, stream, need: int) -> torch.Tensor:
         """One workspace per stream for all captured forwards replayed on it (replays of one stream run in order, so they can
         share it); an entry that needs more gets a larger one, which later entries share (older graphs keep theirs alive)."""
-        pool = self.__dict__.setdefault("_graph_ws", {})
+        pool = self._graph_ws
         ws = pool.get(stream)
         if ws is None or ws.numel() < need:
             ws = pool[stream] = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -569,7 +587,7 @@ class Engine:
         graph the library captures is keyed by this allocation, so it stays put from call to call (a longer file than any
         before re-allocates -- and re-captures -- once)."""
         stream = torch.cuda.current_stream(self.device)
-        pool = self.__dict__.setdefault("_a2b_ws", {})
+        pool = self._a2b_ws
         ws, small = pool.get(stream, (None, 0))
         if ws is not None and ws.numel() > 4 * need:
             # far larger than this call needs (one very long file among short ones: ~80 MB per chunk): kept for a while, given
@@ -586,36 +604,20 @@ class Engine:
             pool.pop(next(iter(pool)))
         return ws
 
-    def _h_prof_on(self) -> bool:
-        return bool(getattr(self, "profiling", False))
-
-    # -- BT_PREC_F32X3 range guard, deferred form ------------------------------------------------------------------------
-    def deferred_range_checks(self):
-        """Context manager: BT_PREC_F32X3 forwards inside it do not synchronise; their range flags are copied to pinned host
-        memory asynchronously and collected in the list the context yields.  ``Engine.range_exceeded(list)`` (after the
-        work has been waited for, or waiting itself) tells whether any of them fired -- the caller then repeats that
-        work with the model's ``fp32_split_gemms`` off."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def ctx():
-            outer, mine = self._deferred, []
-            self._deferred = mine
-            try:
-                yield mine
-            finally:
-                self._deferred = outer
-                if outer is not None:
-                    outer.extend(mine)
-        return ctx()
+    # -- BT_PREC_F32X3 range guard ---------------------------------------------------------------------------------------
+    def _count_fallback(self) -> None:
+        """One more forward whose range flag fired and was repeated on the exact path (``last_fallbacks``; any thread)."""
+        with self._lock:
+            self.last_fallbacks += 1
 
     def range_exceeded(self, checks) -> bool:
+        """Whether any flag of ``checks`` (forward_stages' list) fired; waits for them, and counts one fallback if so."""
         bad = False
         for host, ev in checks:
             ev.synchronize()
             bad = bad or int(host[0]) != 0
         if bad:
-            self.last_fallbacks += 1
+            self._count_fallback()
         return bad
 
 

@@ -43,31 +43,27 @@ def deduplicate_peaks(peaks, width=1) -> np.ndarray:
 
 
 class PendingBeats:
-    """Handle of an enqueued ``Postprocessor.ragged_async`` call; ``result()`` -> [(beats, downbeats)] per track."""
+    """Handle of an enqueued post-processing call (``Postprocessor.ragged_async``); ``result()`` -> [(beats, downbeats)] per
+    track.  ``result()`` waits for ``done`` (the device-to-host copy into the pinned buffer ``host``), turns the buffer into
+    the result with ``decode``, gives the buffer back to ``owner``'s pool and keeps the result.  ``out``: a result known
+    already (an empty batch, a host-side post-processor); ``keep``: device buffers the copy reads from."""
 
-    def __init__(self, host, done, frame_off, total, fps, owner=None, keep=None):
-        self._host, self._done, self._frame_off, self._total, self._fps = host, done, frame_off, total, fps
-        self._owner, self._keep, self._out = owner, keep, None
+    def __init__(self, out=None, host=None, done=None, decode=None, owner=None, keep=None):
+        self._out, self._host, self._done, self._decode, self._owner, self._keep = out, host, done, decode, owner, keep
 
     def result(self):
-        if self._out is not None:
-            return self._out
-        n = len(self._frame_off) - 1
-        if self._host is None:
-            self._out = [(np.zeros(0), np.zeros(0)) for _ in range(n)]
-            return self._out
-        self._done.synchronize()
-        host, total = self._host.numpy(), self._total
-        cnt = host[2 * total:]
-        out = []
-        for k in range(n):
-            lo = int(self._frame_off[k])
-            out.append(_host_post(host[lo: lo + cnt[2 * k]], host[total + lo: total + lo + cnt[2 * k + 1]], self._fps))
-        if self._owner is not None:  # hand the pinned buffer back
-            self._owner.__dict__.setdefault("_pin_pool", []).append(self._host._base if self._host._base is not None else self._host)
-        self._host = self._keep = None
-        self._out = out
-        return out
+        if self._out is None:
+            self._done.synchronize()
+            try:
+                self._out = self._decode(self._host.numpy())
+            finally:
+                self._owner._return_pinned(self._host)
+                self._host = self._keep = None
+        return self._out
+
+
+def _no_tracks(n: int) -> PendingBeats:
+    return PendingBeats([(np.zeros(0), np.zeros(0)) for _ in range(n)])
 
 
 # DBNDownBeatTrackingProcessor(beats_per_bar=[3, 4], min_bpm=55.0, max_bpm=215.0, fps=fps, transition_lambda=100)
@@ -116,33 +112,6 @@ def _dbn_rows(rows: np.ndarray, fps: float) -> np.ndarray:
 def _split_rows(out: np.ndarray, fps: float):
     res = _dbn_rows(out, fps)
     return res[:, 0].copy(), res[res[:, 1] == 1][:, 0].copy()
-
-
-class PendingDBN:
-    """Handle of an enqueued DBN ``Postprocessor.ragged_async`` call; ``result()`` -> [(beats, downbeats)] per track."""
-
-    def __init__(self, host, done, frame_off, fps, owner=None, keep=None):
-        self._host, self._done, self._frame_off, self._fps = host, done, frame_off, fps
-        self._owner, self._keep, self._out = owner, keep, None
-
-    def result(self):
-        if self._out is not None:
-            return self._out
-        n = len(self._frame_off) - 1
-        if self._host is None:
-            self._out = [(np.zeros(0), np.zeros(0)) for _ in range(n)]
-            return self._out
-        self._done.synchronize()
-        host = self._host.numpy()
-        out = []
-        for k in range(n):
-            lo = n + 2 * int(self._frame_off[k])
-            out.append(_split_rows(host[lo: lo + 2 * int(host[k])].reshape(-1, 2), self._fps))
-        if self._owner is not None:
-            self._owner.__dict__.setdefault("_pin_pool", []).append(self._host._base if self._host._base is not None else self._host)
-        self._host = self._keep = None
-        self._out = out
-        return out
 
 
 _DBN_LOCK = threading.Lock()
@@ -228,7 +197,7 @@ class Postprocessor:
         n = len(frame_off) - 1
         total = int(frame_off[-1])
         if n == 0 or total == 0:
-            return PendingBeats(None, None, frame_off, 0, self.fps)
+            return _no_tracks(n)
         dev = beat.device
         b1, d1 = beat.reshape(-1), downbeat.reshape(-1)
         if (b1.dtype == d1.dtype == torch.float32 and b1.is_contiguous() and d1.is_contiguous() and b1.numel() == total
@@ -251,16 +220,26 @@ class Postprocessor:
             host[:size].copy_(buf, non_blocking=True)
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
-        return PendingBeats(host[:size], done, frame_off, total, self.fps, owner=self, keep=(buf, logits, d_spans))
+
+        def decode(h):   # [indices | counts]: the peak frames of track k start at its first frame
+            cnt = h[2 * total:]
+            return [_host_post(h[lo: lo + cnt[2 * k]], h[total + lo: total + lo + cnt[2 * k + 1]], self.fps)
+                    for k, lo in enumerate(map(int, frame_off[:-1]))]
+        return PendingBeats(host=host[:size], done=done, decode=decode, owner=self, keep=(buf, logits, d_spans))
 
     def _pinned(self, size: int) -> torch.Tensor:
         """A pinned host buffer of at least ``size`` int32 (pool of returned buffers: page-locking costs ~a millisecond)."""
-        pool = self.__dict__.setdefault("_pin_pool", [])
         with _PIN_LOCK:   # (one Postprocessor may serve several host threads)
+            pool = self.__dict__.setdefault("_pin_pool", [])
             for i, t in enumerate(pool):
                 if t.numel() >= size:
                     return pool.pop(i)
         return torch.empty((max(size, 1 << 16),), dtype=torch.int32, pin_memory=True)
+
+    def _return_pinned(self, t: torch.Tensor) -> None:
+        """Give a buffer of ``_pinned`` (or a view of one) back to the pool."""
+        with _PIN_LOCK:
+            self.__dict__.setdefault("_pin_pool", []).append(t if t._base is None else t._base)
 
     def postp_dbn(self, beat, downbeat, padding_mask=None):
         B = beat.shape[0]
@@ -299,7 +278,7 @@ class Postprocessor:
                 t = self._dbn_dev[dev] = torch.from_numpy(self._dbn_tables).to(dev)
             return t
 
-    def _dbn_ragged_async(self, beat, downbeat, frame_off) -> PendingDBN:
+    def _dbn_ragged_async(self, beat, downbeat, frame_off) -> PendingBeats:
         """DBN decode of the tracks ``frame_off[k]:frame_off[k+1]`` of the 1-D device tensors: one bt_dbn_decode (three
         launches) and one device-to-host copy of [row counts | rows]."""
         _lib.require_gpu(beat, "beat logits")
@@ -307,7 +286,7 @@ class Postprocessor:
         n = len(frame_off) - 1
         total = int(frame_off[-1])
         if n == 0 or total == 0:
-            return PendingDBN(None, None, frame_off, self.fps)
+            return _no_tracks(n)
         dev = beat.device
         b1, d1 = beat.reshape(-1), downbeat.reshape(-1)
         f64 = b1.dtype == torch.float64 or d1.dtype == torch.float64
@@ -337,4 +316,8 @@ class Postprocessor:
             host[:size].copy_(buf, non_blocking=True)
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
-        return PendingDBN(host[:size], done, frame_off, self.fps, owner=self, keep=(buf, logits, d_spans, ws))
+
+        def decode(h):   # [row counts | rows]: the (frame, beat number) rows of track k start at row frame_off[k]
+            return [_split_rows(h[n + 2 * lo: n + 2 * lo + 2 * int(h[k])].reshape(-1, 2), self.fps)
+                    for k, lo in enumerate(map(int, frame_off[:-1]))]
+        return PendingBeats(host=host[:size], done=done, decode=decode, owner=self, keep=(buf, logits, d_spans, ws))

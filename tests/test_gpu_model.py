@@ -929,3 +929,111 @@ def test_one_audio2beats_shared_by_host_threads():
         for j, (b, d) in out:
             assert np.array_equal(b, want[j][0]) and np.array_equal(d, want[j][1]), j
     report("shared_engine_threads", threads=n_threads, files=len(files))
+
+
+@pytest.mark.timeout(300)
+def test_range_checks_of_one_thread_do_not_reach_another_on_the_same_model():
+    """Precision and range checks belong to the call, not to the model: two threads drive one model, each on its own stream.
+    Thread A runs a batch whose range flag fires (repeated on the exact path); thread B runs an ordinary batch, ordinary
+    pieces and a short piece whose flag fires.  Both batches are long enough for the side streams of the forward slices.
+    Every result equals the same call's single-threaded one -- the exact path's where the flag fired, the default
+    precision's elsewhere (B never ran the exact path by A's doing, nor returned an unchecked overflow) -- and every
+    overflowing call counts one fallback."""
+    import threading
+
+    from beat_this_amd import inference as inf
+    from beat_this_amd import weights as W
+    from beat_this_amd.inference import Spect2Frames
+
+    K = 12
+    s2f = Spect2Frames(checkpoint_path=None, device=dev(), float16=False)
+    s2f.model = _model("small0", 5, "lively")
+    m, eng = s2f.model, s2f.model.engine()
+
+    def spect(n, seed, scale=1.0):
+        return torch.from_numpy(W.synthetic_spect(n, seed=seed)).to(dev()) * scale
+
+    off = [0, 16000, 32000, 48000]   # (3 x 11 chunks: slices on side streams, inf.CONCURRENT_SLICE_CHUNKS)
+    assert 3 * len(inf.chunk_starts(16000, 1500, 6)) >= inf.CONCURRENT_SLICE_CHUNKS
+    hot = torch.cat([spect(16000, 51 + i, 1.0e6) for i in range(3)])
+    cool = torch.cat([spect(16000, 61 + i) for i in range(3)])
+    pieces = [spect(3100, 53), spect(700, 54), spect(700, 55, 1.0e6)]   # (graph path, short piece, short piece that overflows)
+
+    def exact(fn):
+        m.fp32_split_gemms = False
+        try:
+            return fn()
+        finally:
+            m.fp32_split_gemms = True
+
+    def run_a():
+        return s2f.spect2frames_batch(hot, off)
+
+    def run_b():
+        return [s2f.spect2frames_batch(cool, off)] + [s2f.spect2frames(p) for p in pieces]
+
+    sa, sb = torch.cuda.Stream(device=dev()), torch.cuda.Stream(device=dev())
+    torch.cuda.synchronize(dev())
+    # both workloads once on this thread, on the streams the threads use (the captured forwards are made here)
+    before = eng.last_fallbacks
+    with torch.cuda.stream(sa):
+        want_a = run_a()
+        assert eng.last_fallbacks == before + 1, "the scaled batch does not raise the range flag"
+        exact_a = exact(run_a)
+    with torch.cuda.stream(sb):
+        want_b = run_b()
+        assert eng.last_fallbacks == before + 2, "only the scaled short piece raises the range flag"
+        exact_hot = exact(lambda: s2f.spect2frames(pieces[2]))
+    torch.cuda.synchronize(dev())
+    assert all(torch.isfinite(t).all() for t in exact_a + exact_hot)
+    assert torch.equal(want_a[0], exact_a[0]) and torch.equal(want_a[1], exact_a[1])
+    assert torch.equal(want_b[3][0], exact_hot[0]) and torch.equal(want_b[3][1], exact_hot[1])
+    assert len(eng._graphs) == 1
+    before = eng.last_fallbacks
+    got_a, got_b, errors = [], [], []
+
+    def work(stream, fn, out):
+        try:
+            with torch.cuda.stream(stream):
+                for _ in range(K):
+                    out.append(fn())
+                stream.synchronize()
+        except Exception as e:  # noqa: BLE001
+            errors.append(repr(e))
+
+    ths = [threading.Thread(target=work, args=(sa, run_a, got_a)), threading.Thread(target=work, args=(sb, run_b, got_b))]
+    for th in ths:
+        th.start()
+    for th in ths:
+        th.join()
+    assert not errors, errors
+    assert len(got_a) == len(got_b) == K
+    for b, d in got_a:
+        assert torch.equal(b, want_a[0]) and torch.equal(d, want_a[1])
+    for outs in got_b:
+        for (b, d), (wb, wd) in zip(outs, want_b):
+            assert torch.equal(b, wb) and torch.equal(d, wd)
+    assert eng.last_fallbacks == before + 2 * K
+    report("range_checks_per_call", calls=K, fallbacks=eng.last_fallbacks - before)
+
+
+def test_one_call_gives_its_pinned_buffer_back_when_the_library_call_fails(monkeypatch):
+    """Audio2Beats' one-call path takes a pinned result buffer from the post-processor's pool; a library call that fails
+    (here: a workspace one byte short of the plan, which bt_audio2beats_enqueue refuses before it launches anything) raises
+    and leaves that buffer in the pool."""
+    from beat_this_amd import weights as W
+    from beat_this_amd.inference import Audio2Beats
+
+    a2b = Audio2Beats(checkpoint_path=None, device=dev(), float16=False, dbn=False)
+    a2b.model = _model("small0", 4, "lively")
+    sig = W.synthetic_audio(20.0, seed=7)
+    assert a2b._one_call(sig, 22050) is not None   # (a successful call: its buffer is in the pool afterwards)
+    pool = a2b.frames2beats.__dict__["_pin_pool"]
+    assert len(pool) == 1
+    buf = pool[0]
+    eng = a2b.model.engine()
+    workspace = eng._a2b_workspace
+    monkeypatch.setattr(eng, "_a2b_workspace", lambda need: workspace(need)[: need - 1])
+    with pytest.raises(RuntimeError, match="workspace too small"):
+        a2b._one_call(sig, 22050)
+    assert len(pool) == 1 and pool[0] is buf
