@@ -798,23 +798,25 @@ DEVI void split8(const f32x16& p, int s, u32x4& whi, u32x4& wlo) {
 // Scores of one key block, S^T = K . Q^T (+ st.negm when INIT: the subtraction of the reference maximum rides on the
 // accumulator input like in the half kernel -- starting from zero and subtracting on the VALU costs 16 adds and 16
 // register clears per block and changed nothing measurable in the result), small terms first.
-template <bool INIT, int QB>
+// (NA: the query blocks of the wave that exist -- the first NA of its QB; the others are not touched.  NA < QB only in the wave
+// of attn_frag_x3q2_kernel whose second block lies beyond the sequence.)
+template <bool INIT, int QB, int NA = QB>
 DEVI void score_x(const KFragX& kf, const QStateX (&st)[QB], f32x16 (&sc)[QB]) {
 #pragma unroll
-  for (int j = 0; j < QB; ++j) {
+  for (int j = 0; j < NA; ++j) {
     if constexpr (INIT) sc[j] = st[j].negm; else zero16(sc[j]);
     sc[j] = MFMA32_H(kf.k0l, st[j].q0, sc[j]);
   }
 #pragma unroll
-  for (int j = 0; j < QB; ++j) sc[j] = MFMA32_H(kf.k1l, st[j].q1, sc[j]);
+  for (int j = 0; j < NA; ++j) sc[j] = MFMA32_H(kf.k1l, st[j].q1, sc[j]);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) sc[j] = MFMA32_H(kf.k0, st[j].q0l, sc[j]);
+  for (int j = 0; j < NA; ++j) sc[j] = MFMA32_H(kf.k0, st[j].q0l, sc[j]);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) sc[j] = MFMA32_H(kf.k1, st[j].q1l, sc[j]);
+  for (int j = 0; j < NA; ++j) sc[j] = MFMA32_H(kf.k1, st[j].q1l, sc[j]);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) sc[j] = MFMA32_H(kf.k0, st[j].q0, sc[j]);
+  for (int j = 0; j < NA; ++j) sc[j] = MFMA32_H(kf.k0, st[j].q0, sc[j]);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) sc[j] = MFMA32_H(kf.k1, st[j].q1, sc[j]);
+  for (int j = 0; j < NA; ++j) sc[j] = MFMA32_H(kf.k1, st[j].q1, sc[j]);
 }
 // scores -> probabilities -> row sums, split, O^T += V^T . P^T
 // (Measured and rejected: accumulating each LDS tile's products in a fresh accumulator and adding it to the running output
@@ -834,10 +836,10 @@ DEVI unsigned cvt_pk_rn(float a, float b) {   // (the instruction the hand-sched
   asm("s_nop 0\n\tv_cvt_pk_f16_f32 %0, %1, %2" : "=v"(w) : "v"(a), "v"(b));
   return w;
 }
-template <bool SAFE, bool MASK, int QB, bool PRESUB = (QB == 1), bool P16 = false>
+template <bool SAFE, bool MASK, int QB, bool PRESUB = (QB == 1), bool P16 = false, int NA = QB>
 DEVI void finish_x(f32x16 (&sc)[QB], const VFragX& vf, int g, QStateX (&st)[QB], int key0, int L) {
 #pragma unroll
-  for (int j = 0; j < QB; ++j) {
+  for (int j = 0; j < NA; ++j) {
     if constexpr (SAFE) {
       if constexpr (MASK) {
 #pragma unroll
@@ -875,7 +877,7 @@ DEVI void finish_x(f32x16 (&sc)[QB], const VFragX& vf, int g, QStateX (&st)[QB],
   if constexpr (P16) {
     u32x4 w0[QB], w1[QB];
 #pragma unroll
-    for (int j = 0; j < QB; ++j) {
+    for (int j = 0; j < NA; ++j) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         w0[j][i] = cvt_pk_rn(sc[j][2 * i], sc[j][2 * i + 1]);
@@ -888,34 +890,34 @@ DEVI void finish_x(f32x16 (&sc)[QB], const VFragX& vf, int g, QStateX (&st)[QB],
       rowsum8(st[j].l4, w1[j]);
     }
 #pragma unroll
-    for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v0l, __builtin_bit_cast(hfx8, w0[j]), st[j].acc);
+    for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v0l, __builtin_bit_cast(hfx8, w0[j]), st[j].acc);
 #pragma unroll
-    for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v1l, __builtin_bit_cast(hfx8, w1[j]), st[j].acc);
+    for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v1l, __builtin_bit_cast(hfx8, w1[j]), st[j].acc);
 #pragma unroll
-    for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v0, __builtin_bit_cast(hfx8, w0[j]), st[j].acc);
+    for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v0, __builtin_bit_cast(hfx8, w0[j]), st[j].acc);
 #pragma unroll
-    for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v1, __builtin_bit_cast(hfx8, w1[j]), st[j].acc);
+    for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v1, __builtin_bit_cast(hfx8, w1[j]), st[j].acc);
     return;
   }
   u32x4 h0[QB], l0[QB], h1[QB], l1[QB];
 #pragma unroll
-  for (int j = 0; j < QB; ++j) {
+  for (int j = 0; j < NA; ++j) {
     split8(sc[j], 0, h0[j], l0[j]);
     split8(sc[j], 1, h1[j], l1[j]);
   }
   // small terms first; consecutive MFMAs of different query blocks never share an accumulator
 #pragma unroll
-  for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v0l, __builtin_bit_cast(hfx8, h0[j]), st[j].acc);
+  for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v0l, __builtin_bit_cast(hfx8, h0[j]), st[j].acc);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v1l, __builtin_bit_cast(hfx8, h1[j]), st[j].acc);
+  for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v1l, __builtin_bit_cast(hfx8, h1[j]), st[j].acc);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v0, __builtin_bit_cast(hfx8, l0[j]), st[j].acc);
+  for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v0, __builtin_bit_cast(hfx8, l0[j]), st[j].acc);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v1, __builtin_bit_cast(hfx8, l1[j]), st[j].acc);
+  for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v1, __builtin_bit_cast(hfx8, l1[j]), st[j].acc);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v0, __builtin_bit_cast(hfx8, h0[j]), st[j].acc);
+  for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v0, __builtin_bit_cast(hfx8, h0[j]), st[j].acc);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) st[j].acc = MFMA32_H(vf.v1, __builtin_bit_cast(hfx8, h1[j]), st[j].acc);
+  for (int j = 0; j < NA; ++j) st[j].acc = MFMA32_H(vf.v1, __builtin_bit_cast(hfx8, h1[j]), st[j].acc);
 }
 
 template <int KBX>
@@ -978,15 +980,15 @@ DEVI void attn_tiles_x(rsrc_t rk, rsrc_t rv, char* smem, int tid, int wave, int 
 // overflowing query fell from 1.1 % to the figure in DESIGN.md section 5 (21 % on the outlier stress weights before).
 // (diag_max_x: that block's part, computed right behind the loads -- before any LDS-DMA is issued -- so that its fragments are
 // dead when the passes start; dmax[j] = this lane's maximum over its 16 keys of the block.)
-template <int QB>
+template <int QB, int NA = QB>
 DEVI void diag_max_x(const char* kseq, const int (&qblk)[QB], int g, int lr, const QStateX (&st)[QB], int L, float (&dmax)[QB]) {
   KFragX kd[QB];
 #pragma unroll
-  for (int j = 0; j < QB; ++j) kd[j] = ld_kx(kseq + (long)qblk[j] * BLKX_BYTES, g, lr);
+  for (int j = 0; j < NA; ++j) kd[j] = ld_kx(kseq + (long)qblk[j] * BLKX_BYTES, g, lr);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (VGPR-returning loads: landed before the first LDS-DMA is issued)
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int j = 0; j < QB; ++j) {
+  for (int j = 0; j < NA; ++j) {
     f32x16 sd;
     zero16(sd);
     sd = MFMA32_H(kd[j].k0l, st[j].q0, sd);
@@ -1001,23 +1003,23 @@ DEVI void diag_max_x(const char* kseq, const int (&qblk)[QB], int g, int lr, con
     dmax[j] = m;
   }
 }
-template <int QB>
+template <int QB, int NA = QB>
 DEVI void ref_max_x(const char* smem, int g, int lr, QStateX (&st)[QB], int L, int nblk, const float (&dmax)[QB]) {
   float bm[QB];
 #pragma unroll
-  for (int j = 0; j < QB; ++j) bm[j] = dmax[j];
+  for (int j = 0; j < NA; ++j) bm[j] = dmax[j];
   const int nref = min(2, nblk);
   for (int c = 0; c < nref; ++c) {
     const KFragX kf = ld_kx(smem + c * BLKX_BYTES, g, lr);
     f32x16 s0[QB];
-    score_x<false, QB>(kf, st, s0);
+    score_x<false, QB, NA>(kf, st, s0);
 #pragma unroll
-    for (int j = 0; j < QB; ++j)
+    for (int j = 0; j < NA; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) bm[j] = fmaxf(bm[j], (32 * c + crow(r, g) < L) ? s0[j][r] : -1e30f);
   }
 #pragma unroll
-  for (int j = 0; j < QB; ++j) {
+  for (int j = 0; j < NA; ++j) {
     const float m = ceilf(fmaxf(bm[j], __shfl_xor(bm[j], 32)));
 #pragma unroll
     for (int r = 0; r < 16; ++r) st[j].negm[r] = -m - P_SHIFT_X;
@@ -1252,12 +1254,26 @@ __global__ __launch_bounds__(256, 2) void attn_frag_x3q2_kernel(const AttnFragP 
   const char* vseq = reinterpret_cast<const char*>(p.v) + seq_off;
   QStateX st[QB];
   const int qb0 = (qt * 4 + wave) * QB;  // this wave's first query block
+  // `one` (wave-uniform): the wave's second block lies beyond the sequence (T = 1500: 47 blocks on 6 x 8 slots; also every wave
+  // behind the last block).  Such a wave stages its share of every K / V tile and meets every barrier like the others, but runs
+  // the one-block statement of the key loop and the plain code for block 0 alone: no Q fragments, reference maximum, scores or
+  // products of a second copy of the last block whose result nobody stores.  (Block 0 of a wave wholly behind the sequence
+  // still is such a copy: its wave has nothing else to do.)
+  // (-DBT_X3Q2_ONE=0 builds the kernel that computes the copy: A/B, tools/build_variant.py)
+#ifndef BT_X3Q2_ONE
+#define BT_X3Q2_ONE 1
+#endif
+  const bool one = BT_X3Q2_ONE && __builtin_amdgcn_readfirstlane((int)(qb0 + 1 >= nblk)) != 0;
   // (the Q fragments are loaded twice: the asm statement below takes 140 of the 256 registers for itself, and what is
   // only needed again behind it -- Q for the last, ragged tile -- is cheaper fetched again than kept)
   auto load_q = [&]() {
     const int ln = lane_id_fresh(), gg = ln >> 5, ll = ln & 31;
 #pragma unroll
     for (int j = 0; j < QB; ++j) {
+      if (j == 1 && one) {   // (defined values for the statement's operand list; never read)
+        st[j].q0 = st[j].q1 = st[j].q0l = st[j].q1l = hfx8{0, 0, 0, 0, 0, 0, 0, 0};
+        continue;
+      }
       const int qbc = min(qb0 + j, nblk - 1);
       const char* qblk = reinterpret_cast<const char*>(p.q) + seq_off + (long)qbc * BLKX_BYTES;
       st[j].q0 = *reinterpret_cast<const hfx8*>(qblk + ((2 * gg) * 32 + ll) * 16);
@@ -1272,7 +1288,12 @@ __global__ __launch_bounds__(256, 2) void attn_frag_x3q2_kernel(const AttnFragP 
   float dmax[QB];   // the queries' own key block in the reference maximum: before any LDS-DMA is in flight (diag_max_x)
   {
     const int qbi[QB] = {min(qb0, nblk - 1), min(qb0 + 1, nblk - 1)};
-    diag_max_x<QB>(kseq, qbi, g, lr, st, L, dmax);
+    if (one) {
+      diag_max_x<QB, 1>(kseq, qbi, g, lr, st, L, dmax);
+      dmax[1] = -1e30f;
+    } else {
+      diag_max_x<QB>(kseq, qbi, g, lr, st, L, dmax);
+    }
   }
   const unsigned seq_bytes = (unsigned)p.nbp * BLKX_BYTES;   // (tiles beyond it read as zeros: the ring is always refilled)
   const rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(kseq), 0, seq_bytes, 0x00020000);
@@ -1314,6 +1335,21 @@ __global__ __launch_bounds__(256, 2) void attn_frag_x3q2_kernel(const AttnFragP 
     const unsigned m0base = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + wave * 1024));
     const float m1 = -1.0f;
     int t = 0, soff = 3 * TILEX_BYTES;
+    // (the statement is chosen once per wave, here: nothing of the choice is inside the loop)
+    if (one) {
+    if constexpr (P16)
+      asm volatile(ATTN_X3Q2P_ONE_ASM
+                   : "+v"(st[0].acc), "+v"(st[1].acc), "+v"(st[0].l4), "+v"(st[1].l4), "+s"(t), "+s"(soff)
+                   : "v"(st[0].q0), "v"(st[0].q1), "v"(st[0].q0l), "v"(st[0].q1l), "v"(st[1].q0), "v"(st[1].q1), "v"(st[1].q0l), "v"(st[1].q1l),
+                     "v"(st[0].negm), "v"(st[1].negm), "v"(klane), "v"(vlane), "v"(dmaoff), "s"(dk), "s"(dv), "s"(m0base), "s"(m1), "s"(nfull)
+                   : ATTN_X3Q2P_CLOBBERS);
+    else
+      asm volatile(ATTN_X3Q2_ONE_ASM
+                   : "+v"(st[0].acc), "+v"(st[1].acc), "+v"(st[0].l), "+v"(st[1].l), "+s"(t), "+s"(soff)
+                   : "v"(st[0].q0), "v"(st[0].q1), "v"(st[0].q0l), "v"(st[0].q1l), "v"(st[1].q0), "v"(st[1].q1), "v"(st[1].q0l), "v"(st[1].q1l),
+                     "v"(st[0].negm), "v"(st[1].negm), "v"(klane), "v"(vlane), "v"(dmaoff), "s"(dk), "s"(dv), "s"(m0base), "s"(m1), "s"(nfull)
+                   : ATTN_X3Q2_CLOBBERS);
+    } else {
     if constexpr (P16)
       asm volatile(ATTN_X3Q2P_ASM
                    : "+v"(st[0].acc), "+v"(st[1].acc), "+v"(st[0].l4), "+v"(st[1].l4), "+s"(t), "+s"(soff)
@@ -1326,6 +1362,7 @@ __global__ __launch_bounds__(256, 2) void attn_frag_x3q2_kernel(const AttnFragP 
                    : "v"(st[0].q0), "v"(st[0].q1), "v"(st[0].q0l), "v"(st[0].q1l), "v"(st[1].q0), "v"(st[1].q1), "v"(st[1].q0l), "v"(st[1].q1l),
                      "v"(st[0].negm), "v"(st[1].negm), "v"(klane), "v"(vlane), "v"(dmaoff), "s"(dk), "s"(dv), "s"(m0base), "s"(m1), "s"(nfull)
                    : ATTN_X3Q2_CLOBBERS);
+    }
     }
     // every piece of the ring this wave asked for has landed, and so has everybody else's: the last tile (fewer than KBX
     // blocks and / or a masked last block) is read from its ring buffer by the plain code
@@ -1349,9 +1386,15 @@ __global__ __launch_bounds__(256, 2) void attn_frag_x3q2_kernel(const AttnFragP 
         const KFragX kf = ld_kx(kb + c * BLKX_BYTES, g2, lr2);
         const VFragX vf = ld_vx(vb + c * BLKX_BYTES, lane2);
         f32x16 sc[QB];
-        score_x<true, QB>(kf, st, sc);
-        if (partial && blk == nblk - 1) finish_x<false, true, QB, true, P16>(sc, vf, g2, st, blk * 32, L);
-        else finish_x<false, false, QB, true, P16>(sc, vf, g2, st, blk * 32, L);
+        if (one) {
+          score_x<true, QB, 1>(kf, st, sc);
+          if (partial && blk == nblk - 1) finish_x<false, true, QB, true, P16, 1>(sc, vf, g2, st, blk * 32, L);
+          else finish_x<false, false, QB, true, P16, 1>(sc, vf, g2, st, blk * 32, L);
+        } else {
+          score_x<true, QB>(kf, st, sc);
+          if (partial && blk == nblk - 1) finish_x<false, true, QB, true, P16>(sc, vf, g2, st, blk * 32, L);
+          else finish_x<false, false, QB, true, P16>(sc, vf, g2, st, blk * 32, L);
+        }
       }
       __syncthreads();
     }
@@ -1361,7 +1404,12 @@ __global__ __launch_bounds__(256, 2) void attn_frag_x3q2_kernel(const AttnFragP 
   stage_ring(2);
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // tile 0 (this wave's four pieces of it) has landed
   __syncthreads();
-  ref_max_x<QB>(smem, g, lr, st, L, nblk, dmax);
+  if (one) {
+    ref_max_x<QB, 1>(smem, g, lr, st, L, nblk, dmax);
+    zero16(st[1].negm);
+  } else {
+    ref_max_x<QB>(smem, g, lr, st, L, nblk, dmax);
+  }
   fast_pass();
   // (Lane-derived values are taken again from an operand hipcc cannot see through wherever they are needed: nothing but the
   // softmax state may stay live across an asm statement -- the three-term one leaves 18 registers -- and a value kept was a
@@ -1386,6 +1434,7 @@ __global__ __launch_bounds__(256, 2) void attn_frag_x3q2_kernel(const AttnFragP 
   float amax = 0.f;
 #pragma unroll
   for (int j = 0; j < QB; ++j) {
+    if (j == 1 && one) continue;   // (wave-uniform: the exchanges below are executed by all lanes or by none)
     const int qi = (qb0 + j) * 32 + lrE;
     const bool okq = qb0 + j < nblk && qi < L && !bad[j];
     const float gatev = okq ? p.gates[(long)sh * p.nbp * 32 + qi] : 0.f;

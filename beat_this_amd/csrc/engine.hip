@@ -213,6 +213,7 @@ struct FragLayer {
   bool ff8;    // FF1 / FF2 on hl8: the out-projection's shadow and FF1's hidden activation are hl8
   bool next8;  // FF2 leaves the shadow in hl8 for the next layer's QKV
   bool tail;   // half: out-projection + FF1 + FF2 in one tail.hip launch
+  bool shadow_dead;   // x3, last layer of a forward that runs through to the head: FF2 writes neither the shadow nor the statistics
 };
 
 enum { LAYERS_GENERIC, LAYERS_FRAG_HALF, LAYERS_FRAG_X3 };
@@ -224,7 +225,7 @@ struct Route {
   int x3_attn, x3_attn_front;   // AttnFragP.x3 of the main layers' / the frontend's attention (0 outside x3)
   bool half_shadow;             // the main residual stream has a half shadow in ws.xmb
   int layers;                   // LAYERS_*
-  struct Block { PairRoute freq, time; bool conv3; } blk[3];
+  struct Block { PairRoute freq, time; bool conv3; bool x_dead; } blk[3];   // x_dead: the time half leaves only the shadow of its x
   bool lin3, lin_f8;            // frontend.linear on gemm3; it leaves the shadow in hl8
   struct Layer { PairRoute pair; FragLayer frag; } layer[BT_MAX_LAYERS];
 };
@@ -246,11 +247,19 @@ struct Route {
 //   gemm3_supported.  It reads the shadow of x (half, or hl32 from the (hi, lo) kernel) that the time half's outff kernel
 //   writes into ws.hid, and that kernel writes it exactly when conv3 holds.  Else gemm.hip; the last block's output is
 //   half when lin3 (same rounding point as the fp32 -> half conversion of linear's A operand, half the bytes both ways).
+// Stores nobody reads (x3 only; BT_SKIP_DEAD_STORES):  x_dead: conv3 under frag x3 -- the conv reads the shadow in ws.hid, the
+//   next block works on the other ping-pong buffer, so the (hi, lo) out-projection + FF kernel does not write the block's fp32
+//   x (6.1 MB per chunk and block).  shadow_dead: the last main layer of a forward that ends at the head (last == 2): the head
+//   reads the fp32 ws.xm alone, FF2 leaves ws.xmb and ws.ssq[0] unwritten.  A forward that ends earlier (stage exits) and
+//   the unit entry points keep every store: their callers can look at the buffers.
 // frontend.linear:  lin3 (gemm3): frag half, or frag x3 with lin_w_x3 and the last conv on gemm3 (only that form writes
 //   the hl32 planes lin3 reads); gemm3_supported.  Else gemm.hip (+ the hl32 shadow pass under frag x3).
 // Attention (x3): 4 = launch_attn_frag picks the 64-key kernel or two query blocks per wave on the hand-scheduled key
 //   loop; + BT_X3_P16 in the main layers when BT_OPT_X3_ATTN_P16 is 1 or 2, in the frontend when it is >= 2.
-Route plan_route(const bt_engine& e, int B, int T, int prec, int first, const Workspace& ws) {
+#ifndef BT_SKIP_DEAD_STORES
+#define BT_SKIP_DEAD_STORES 1
+#endif
+Route plan_route(const bt_engine& e, int B, int T, int prec, int first, int last, const Workspace& ws) {
   const bt_model_desc& d = e.d;
   const int D = d.transformer_dim;
   Route r;
@@ -285,6 +294,7 @@ Route plan_route(const bt_engine& e, int B, int T, int prec, int first, const Wo
     const Gemm3P cg = conv3_params(d, ws, blk, B, T, frag_x3, blk == 2 && lin3_fits);
     rb.conv3 = d.partial_transformers && rb.time.outff && (frag_x3 ? rb.time.split : frag_half) && cg.N >= 128 && cg.W &&
                gemm3_supported(cg);
+    rb.x_dead = BT_SKIP_DEAD_STORES && rb.conv3 && frag_x3;   // (conv3 under frag x3 implies the time half's (hi, lo) kernel)
   }
   r.lin3 = lin3_fits && (!frag_x3 || r.blk[2].conv3);
   r.lin_f8 = r.lin3 && frag_x3 && e.x3_gemm_fp8 >= 2 && d.n_layers > 0 && d.layers[0].w_qkvg_f8;
@@ -298,6 +308,7 @@ Route plan_route(const bt_engine& e, int B, int T, int prec, int first, const Wo
     f.ff8 = frag_x3 && e.x3_gemm_fp8 >= 1 && w.w_ff1_f8 && w.w_ff2_f8;
     f.next8 = frag_x3 && e.x3_gemm_fp8 >= 2 && l + 1 < d.n_layers && d.layers[l + 1].w_qkvg_f8 && w.w_ff2_f8;
     f.tail = frag_half && w.w_tail_frag && layer_tail_supported(D, d.ff_mult * D);
+    f.shadow_dead = BT_SKIP_DEAD_STORES && frag_x3 && last == 2 && l == d.n_layers - 1;
   }
   return r;
 }
@@ -406,8 +417,9 @@ int freq_half(prof::State* pf, const bt_pair_weights& pw, const PairRoute& pr, c
 
 // time-direction half of a frontend block (sequences = (b, f), tokens = t).  shadow: where the out-projection + FF kernel
 // writes the half / hl32 shadow of the new x (the A operand of the block's conv on gemm3), or null
+// (shadow_only: Route::Block::x_dead)
 int time_half(prof::State* pf, const bt_pair_weights& pw, const PairRoute& pr, const Route& r, const float* rope, float* x,
-              const Workspace& ws, int B, int T, int F, void* shadow, hipStream_t s) {
+              const Workspace& ws, int B, int T, int F, void* shadow, bool shadow_only, hipStream_t s) {
   const long M = (long)B * T * F;
   if (int rc = check_rows(M)) return rc;
   if (pr.time_frag) {   // fragment-major QKV straight from the projection (x3: hi + lo blocks), flash attention on it
@@ -430,7 +442,7 @@ int time_half(prof::State* pf, const bt_pair_weights& pw, const PairRoute& pr, c
   if (pr.outff) {   // x += to_out(ws.ao); x += FF(x) in one launch
     FusedOutFFP f;
     f.x = x; f.M = M; f.C = pw.dim; f.ao = ws.ao; f.wfrag = pr.split ? pw.w_outff_frag_x3 : pw.w_outff_frag[r.fp];
-    f.b1 = pw.b_ff1; f.b2 = pw.b_ff2; f.xb = shadow; f.abl = 0;
+    f.b1 = pw.b_ff1; f.b2 = pw.b_ff2; f.xb = shadow; f.abl = 0; f.shadow_only = shadow && shadow_only && pr.split;
     LAUNCH_CAT(CAT_FF_FUSED, s, launch_outff_fused(f, pr.split ? BT_PREC_F32X3 : r.fp, s), "fused out-projection + feed-forward");
     return BT_OK;
   }
@@ -485,7 +497,7 @@ int frag_layer(prof::State* pf, const bt_pair_weights& pw, const FragLayer& f, c
   memset(&g, 0, sizeof g);
   g.A = ws.hid; g.lda = HID; g.M = M; g.K = HID; g.W = w(pw.w_ff2, pw.w_ff2_x3, pw.w_ff2_f8, f.ff8); g.N = D; g.epi = G3_RESID;
   g.x3 = r.x3 | (f.ff8 ? G3_X3_F8 : 0) | (f.next8 ? G3_X3_OUT_F8 : 0); g.status = status;
-  g.bias = pw.b_ff2; g.x = ws.xm; g.ldx = D; g.xb = ws.xmb; g.ssq_out = ws.ssq[0];
+  g.bias = pw.b_ff2; g.x = ws.xm; g.ldx = D; g.xb = f.shadow_dead ? nullptr : ws.xmb; g.ssq_out = f.shadow_dead ? nullptr : ws.ssq[0];
   LAUNCH_CAT(CAT_FF2, s, launch_gemm3(g, s), r.x3 ? "ff2 gemm (hi + lo)" : "ff2 gemm");
   return BT_OK;
 }
@@ -501,7 +513,7 @@ int frontend(prof::State* pf, const bt_model_desc& d, const Route& r, const floa
     float* x = front_x(ws, blk);
     if (d.partial_transformers) {
       if (int rc = freq_half(pf, d.front[blk][0], rb.freq, r, d.rope, x, B, T, 32 >> blk, s)) return rc;
-      if (int rc = time_half(pf, d.front[blk][1], rb.time, r, d.rope, x, ws, B, T, 32 >> blk, rb.conv3 ? ws.hid : nullptr, s))
+      if (int rc = time_half(pf, d.front[blk][1], rb.time, r, d.rope, x, ws, B, T, 32 >> blk, rb.conv3 ? ws.hid : nullptr, rb.x_dead, s))
         return rc;
     }
     if (rb.conv3) {
@@ -617,7 +629,7 @@ int bt_forward_stages(bt_engine* e, void* stream, int prec, int first, int last,
   const Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec, (size_t)e->ws_guard);
   if (ws.total > ws_bytes) return bt_set_error(BT_ERR_WORKSPACE, "workspace too small");
   if (prec == BT_PREC_F32X3 && BT_HALF_IS_BF16) return bt_set_error(BT_ERR_ARG, "BT_PREC_F32X3 needs an IEEE fp16 build");
-  const Route r = plan_route(*e, B, T, prec, first, ws);
+  const Route r = plan_route(*e, B, T, prec, first, last, ws);
   hipStream_t s = (hipStream_t)stream;
   // range flag of this forward (first word of the workspace): cleared here; bit 0 is ORed by the gemm3 / attention / QKV
   // kernels when a value beyond the fp16 range goes through a split, bit 1 by whatever ends the call (head, final norm,
@@ -680,7 +692,7 @@ int bt_forward_unit(bt_engine* e, void* stream, int prec, int unit, int index, c
   const Workspace ws = carve((char*)d_ws, B, T, D, d.ff_mult, prec, (size_t)e->ws_guard);
   if (ws.total > ws_bytes) return bt_set_error(BT_ERR_WORKSPACE, "workspace too small");
   // (the units run the route's pair forms on the generic kernels: no shadows, no fragment-major main layers)
-  const Route r = plan_route(*e, B, T, prec, 0, ws);
+  const Route r = plan_route(*e, B, T, prec, 0, 0, ws);
   hipStream_t s = (hipStream_t)stream;
   const bool block_unit = unit == BT_UNIT_PARTIAL || unit == BT_UNIT_CONV;
   const bool layer_unit = unit == BT_UNIT_ATTN || unit == BT_UNIT_FF;
@@ -704,7 +716,7 @@ int bt_forward_unit(bt_engine* e, void* stream, int prec, int unit, int index, c
       const Route::Block& rb = r.blk[index];
       if (int rc = copy_in((size_t)B * T * 1024 * 4)) return rc;
       if (int rc = freq_half(pf, d.front[index][0], rb.freq, r, d.rope, d_out, B, T, 32 >> index, s)) return rc;
-      return time_half(pf, d.front[index][1], rb.time, r, d.rope, d_out, ws, B, T, 32 >> index, nullptr, s);
+      return time_half(pf, d.front[index][1], rb.time, r, d.rope, d_out, ws, B, T, 32 >> index, nullptr, false, s);
     }
     case BT_UNIT_CONV: {
       const GemmP g = conv_params(d, index, r.wp, d_in, d_out, B, T, true);
@@ -1092,7 +1104,7 @@ int bt_outff_fused(void* stream, int prec, const bt_pair_weights* w, const void*
   if (!w || !d_ao || !d_x || M <= 0 || w->dim > 128 || !wf) return bt_set_error(BT_ERR_ARG, "bad argument to bt_outff_fused");
   FusedOutFFP f;
   f.x = d_x; f.M = M; f.C = w->dim; f.ao = d_ao; f.wfrag = wf; f.b1 = w->b_ff1; f.b2 = w->b_ff2;
-  f.xb = prec == BT_PREC_F32 ? nullptr : d_xb; f.abl = 0;
+  f.xb = prec == BT_PREC_F32 ? nullptr : d_xb; f.abl = 0; f.shadow_only = 0;
   LAUNCH(launch_outff_fused(f, prec, (hipStream_t)stream), "fused out-projection + feed-forward");
   return BT_OK;
 }

@@ -102,7 +102,8 @@ struct WRing {
 // FF tail: xn[kt][r] = updated x of this lane's token in C layout; `step0` = stream step of the first hidden
 // block.  b1s = first-layer bias in LDS (loaded once per workgroup; keeps ordinary global loads out of the ring's
 // vmcnt accounting).
-template <typename T, int C>
+// STORE_X = false: the fp32 row is not written (FusedOutFFP::shadow_only) -- an instantiation without the stores, not a predicate.
+template <typename T, int C, bool STORE_X = true>
 DEVI void ff_tail(WRing<T, C>& ws, int step0, float (&xn)[C / 32][16], const float* b1s, const float* b2,
                   float* xrow, hf* xbrow, bool ok, int lane, int g) {
   constexpr int KT = C / 32, HB = 4 * C / 32;
@@ -150,7 +151,9 @@ DEVI void ff_tail(WRing<T, C>& ws, int step0, float (&xn)[C / 32][16], const flo
       const f32x4 b = *reinterpret_cast<const f32x4*>(b2 + f0);
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[a][j] = fmaf(acc2[mt][4 * a + j], PW, b[j]);
-      if (ok) *reinterpret_cast<f32x4*>(xrow + f0) = v[a];
+      if constexpr (STORE_X) {
+        if (ok) *reinterpret_cast<f32x4*>(xrow + f0) = v[a];
+      }
     }
     if (xbrow) {  // half shadow: the two halves of the wave exchange 4-feature runs so that a lane stores 16 bytes
                   // (features 16 k + 8 g .. + 7); 8-byte row-strided stores cost 44 us per forward here.  Executed by all lanes.
@@ -189,7 +192,7 @@ DEVI void ff_tail(WRing<T, C>& ws, int step0, float (&xn)[C / 32][16], const flo
 }
 
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, int C>
+template <typename T, int C, bool STORE_X = true>
 __global__ __launch_bounds__(256) void outff_fused_kernel(const FusedOutFFP p) {
   constexpr int KT = C / 32, HB = 4 * C / 32;
   constexpr int TILE_B = WRing<T, C>::TILE_B, STEP_B = WRing<T, C>::STEP_B, NST = WRing<T, C>::NST;
@@ -239,7 +242,7 @@ __global__ __launch_bounds__(256) void outff_fused_kernel(const FusedOutFFP p) {
     for (int r = 0; r < 16; ++r) xn[mt][r] = fmaf(acc[r], OpScale<T>::PW, xn[mt][r]);
   }
   hf* xbrow = p.xb ? reinterpret_cast<hf*>(p.xb) + tok * C * (std::is_same<T, hl>::value ? 2 : 1) : nullptr;
-  ff_tail<T, C>(ws, KT, xn, b1s, p.b2, xrow, xbrow, ok_st, lane, g);
+  ff_tail<T, C, STORE_X>(ws, KT, xn, b1s, p.b2, xrow, xbrow, ok_st, lane, g);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -416,6 +419,19 @@ __global__ __launch_bounds__(256) void attnff_fused_kernel(const FusedAttnFFP p)
 template <typename T>
 int launch_outff_t(const FusedOutFFP& p, hipStream_t s) {
   dim3 grid((unsigned)((p.M + 127) / 128)), block(256);
+  if constexpr (std::is_same<T, hl>::value) {
+    if (p.shadow_only) {
+      if (!p.xb) return -2;
+      switch (p.C) {
+        case 64: hipLaunchKernelGGL((outff_fused_kernel<T, 64, false>), grid, block, 0, s, p); break;
+        case 128: hipLaunchKernelGGL((outff_fused_kernel<T, 128, false>), grid, block, 0, s, p); break;
+        default: return -2;
+      }
+      return (int)hipGetLastError();
+    }
+  } else if (p.shadow_only) {
+    return -2;
+  }
   switch (p.C) {
     case 32: hipLaunchKernelGGL((outff_fused_kernel<T, 32>), grid, block, 0, s, p); break;
     case 64: hipLaunchKernelGGL((outff_fused_kernel<T, 64>), grid, block, 0, s, p); break;

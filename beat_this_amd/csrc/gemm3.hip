@@ -168,6 +168,112 @@ DEVI void flag_range(int* status, float amax, float limit = 65504.f) {
   if (status && __any(!(amax <= limit)) && (threadIdx.x & 63) == 0) atomicOr(status, 1);
 }
 
+// The gate column tile of the hi + lo QKV projection (N = 3 inner + heads, heads <= 32: ONE 32-feature block of real columns in
+// a 128-column tile whose other 96 - 112 weight rows are padding).  The generic tile runs its full 2 x 2 MFMA blocks per wave
+// on it; here the four waves take one 32-token block of the A tile each against the ONE weight block that exists: 3 MFMAs per
+// k16 piece and wave instead of 12, a quarter of the weight-side LDS-DMA and fragment reads.  The A panel streams as in the
+// generic tile (same pieces, same LDS image), every output element sees the same operand pieces in the same k order and the
+// same three-term order: gates are bit-identical to the generic tile's (x3 & 15 = 3 forces that one; tests).
+// A shape known at compile time, chosen once per workgroup in front of the k-loop -- round 6 skipped the padding blocks with
+// run-time branches inside the loop and lost 1.4 %.  -DBT_QKV_GATE_TILE=0 builds without it (A/B: tools/build_variant.py).
+#ifndef BT_QKV_GATE_TILE
+#define BT_QKV_GATE_TILE 1
+#endif
+template <typename CFG>
+DEVI void qkv_gate_tile_x3(const Gemm3P& p, char* smem, int m0, int n0, int n_tiles, int lane, int wave) {
+  constexpr int BM = CFG::BM, BN = CFG::BN, ROWB = CFG::BK * 2, NST = CFG::NST, KR = CFG::BK / 2, EB = 4;
+  constexpr int NW = CFG::WGM * CFG::WGN, NT = 64 * NW;
+  constexpr int CPR = ROWB / 16, RPI = 64 / CPR;
+  constexpr int A_BYTES = BM * ROWB, ST_BYTES = A_BYTES + BN * ROWB;   // (the generic tile's stage: W uses its first 4 KB)
+  constexpr int APC = A_BYTES / (NT * 16), LPS = APC + 1;
+  static_assert(ROWB == 128 && NW * 32 == BM && 32 * ROWB == NT * 16 && APC <= 4, "one 32-token block per wave, one W piece per thread");
+  const int g = lane >> 5, lr = lane & 31;
+  const int nk = p.K / KR;
+  const int Lv = p.nblk * 32;
+  auto swz = [](int r) { return (r >> 1) & 7; };
+  const unsigned a_bytes = (unsigned)((long)p.M * p.lda * EB), w_bytes = (unsigned)((long)n_tiles * BN * p.K * EB);
+  unsigned voffA[4];
+#pragma unroll
+  for (int i = 0; i < APC; ++i) {
+    const int r = (i * NW + wave) * RPI + lane / CPR;
+    const int c = (lane % CPR) ^ swz(r);
+    const long row = (long)m0 + r;
+    const int seq = (int)(row / Lv), t = (int)(row - (long)seq * Lv);
+    voffA[i] = (seq < p.n_seq && t < p.L) ? (unsigned)(((long)seq * p.L + t) * p.lda * EB + c * 16) : OOB;
+  }
+  unsigned voffW;
+  {
+    const int r = wave * RPI + lane / CPR;   // weight rows n0 .. n0 + 31
+    voffW = (unsigned)((long)(n0 + r) * p.K * EB + ((lane % CPR) ^ swz(r)) * 16);
+  }
+  const rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.A)), 0, a_bytes, 0x00020000);
+  const rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, w_bytes, 0x00020000);
+  auto issue = [&](int kt, int stage) {
+    char* st_ = smem + stage * ST_BYTES + wave * 1024;
+    const int so_ = kt * ROWB;
+#pragma unroll
+    for (int i_ = 0; i_ < APC; ++i_)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lptr_t)(st_ + i_ * NW * 1024), 16, voffA[i_], so_, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lptr_t)(st_ + A_BYTES), 16, voffW, so_, 0, 0);
+  };
+  const int pofs = A_BYTES + lr * ROWB;                 // P = the weight block (accumulator rows = gate features)
+  const int qofs = (wave * 32 + lr) * ROWB;             // Q = this wave's token block (lanes = tokens)
+  const int sw = swz(lr);
+  int kc[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) kc[m] = ((2 * m + g) ^ sw) * 16;
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  // this wave's token block (wave-uniform sequence and block index), this lane's token
+  const int vb = m0 + wave * 32;
+  const int tseq = vb / Lv, tblk = (vb - tseq * Lv) >> 5;
+  const int t = tblk * 32 + lr;
+  const long trow = (tseq < p.n_seq && t < p.L) ? (long)tseq * p.L + t : -1;
+  float part[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) part[q] = (p.ssq_in && trow >= 0 && q < p.ssq_parts) ? p.ssq_in[(long)q * p.M + trow] : 0.f;
+#pragma unroll
+  for (int s0 = 0; s0 < NST - 1; ++s0)
+    if (s0 < nk) issue(s0, s0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (ordinary loads and LDS-DMA do not return in one order: see the generic tile)
+  __builtin_amdgcn_sched_barrier(0);
+  float rs = 1.f;
+  if (p.ssq_in) {   // the generic tile's sum, term by term
+    float sum = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) sum += part[q];
+    for (int q = 8; q < p.ssq_parts; ++q) sum += trow >= 0 ? p.ssq_in[(long)q * p.M + trow] : 0.f;
+    rs = trow >= 0 ? sqrtf((float)p.K) / fmaxf(sqrtf(sum), 1e-12f) : 0.f;
+  }
+  int stage = 0, stage2 = NST - 1;
+  for (int kt = 0; kt < nk; ++kt) {
+    if (NST > 2 && kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NST - 2) * LPS) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (kt + NST - 1 < nk) issue(kt + NST - 1, stage2);
+    const char* st = smem + stage * ST_BYTES;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {   // k16 piece m: hi at chunk pair m, lo at chunk pair m + 2; small terms first
+      const hfx8 ph = *reinterpret_cast<const hfx8*>(st + pofs + kc[m]);
+      const hfx8 pl = *reinterpret_cast<const hfx8*>(st + pofs + kc[m + 2]);
+      const hfx8 qh = *reinterpret_cast<const hfx8*>(st + qofs + kc[m]);
+      const hfx8 ql = *reinterpret_cast<const hfx8*>(st + qofs + kc[m + 2]);
+      acc = MFMA32_H(pl, qh, acc);
+      acc = MFMA32_H(ph, ql, acc);
+      acc = MFMA32_H(ph, qh, acc);
+    }
+    stage = stage == NST - 1 ? 0 : stage + 1;
+    stage2 = stage2 == NST - 1 ? 0 : stage2 + 1;
+  }
+  if (tseq >= p.n_seq) return;  // wave-uniform
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int h = n0 - 3 * p.inner + crow(r, g);
+    if (h < p.heads) p.gates[((long)tseq * p.heads + h) * p.nbp * 32 + t] = sigmoidf(fmaf(acc[r], rs, p.b_gates[h]));
+  }
+}
+
 // ABL (development, BT_G3_ABL = 8): per-wave timing dump (k-loop, waits, epilogue) read by tools/gemm3_probe.py;
 // bits 0 - 2 (no LDS-DMA after the prologue / no GELU / no MFMAs) are ablations that can be instantiated by hand
 // X3: 0 = half operands, 1 = hl32 operands (BT_PREC_F32X3), 2 = "hl8" operands (round 5, BASELINE config 5: the cross terms
@@ -233,6 +339,14 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
   int kind = 0;
   if constexpr (EPI == G3_QKV) kind = n0 < 3 * p.inner ? n0 / p.inner : 3;
   const bool normal = EPI == G3_QKV && kind == 2;
+  // the gate column on its own narrow tile (workgroup-uniform, in front of everything: nothing of it inside the k-loop below).
+  // hl32 operands on 128 x 128 x 32 tiles only: the half path and the opt-in hl8 form keep the generic tile.
+  if constexpr (BT_QKV_GATE_TILE && EPI == G3_QKV && X3 == 1 && ABL == 0 && BM == 128 && BN == 128 && ROWB == 128 && NW == 4) {
+    if (kind == 3 && p.heads <= 32 && (p.x3 & 15) != 3) {
+      qkv_gate_tile_x3<CFG>(p, smem, m0, n0, n_tiles, lane, wave);
+      return;
+    }
+  }
 
   // ---- staging: per-lane source offsets (bytes) of the two 4 KB pieces of each operand ---------------------
   const unsigned a_bytes = (unsigned)((long)p.M * p.lda * EB), w_bytes = (unsigned)((long)n_tiles * BN * p.K * EB);
@@ -660,10 +774,12 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
             if (xb) *reinterpret_cast<u32x2*>(xb + off) = u32x2{pk2(v[0], v[1]), pk2(v[2], v[3])};
           }
         }
-        float ssq = ok ? fmaf(v[0], v[0], fmaf(v[1], v[1], fmaf(v[2], v[2], v[3] * v[3]))) : 0.f;
+        if (p.ssq_out) {   // (uniform: a launch without statistics -- the last layer's FF2 in front of the head -- skips the sums too)
+          float ssq = ok ? fmaf(v[0], v[0], fmaf(v[1], v[1], fmaf(v[2], v[2], v[3] * v[3]))) : 0.f;
 #pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ssq += __shfl_xor(ssq, o);
-        if (p.ssq_out && ok && cp == 0) p.ssq_out[(unsigned)(n0 / 64 + wn) * (unsigned)p.M + (unsigned)(row0 + 32 * b + r)] = ssq;
+          for (int o = 8; o > 0; o >>= 1) ssq += __shfl_xor(ssq, o);
+          if (ok && cp == 0) p.ssq_out[(unsigned)(n0 / 64 + wn) * (unsigned)p.M + (unsigned)(row0 + 32 * b + r)] = ssq;
+        }
       }
     }
     }

@@ -163,6 +163,9 @@ struct FusedOutFFP {  // x += Wout . ao ; x += FF(x)      (time direction, after
   const float* b1; const float* b2;
   void* xb;                          // optional half shadow of the new x
   int abl;                           // development (BT_F2_ABL)
+  // BT_PREC_F32X3, C >= 64: only the shadow of the new x is written, x itself stays what it was (the frontend block's conv on
+  // gemm3 reads the shadow alone and nothing reads the block's x again: Route::Block::x_dead).  Needs xb.
+  int shadow_only;
 };
 int launch_outff_fused(const FusedOutFFP& p, int prec, hipStream_t s);
 struct FusedAttnFFP {  // x += AttnF(x) ; x += FF(x)      (frequency direction)

@@ -21,6 +21,15 @@ probabilities enter P.V as their fp16 hi parts only (P_hi . V_hi + P_hi . V_lo: 
 the row sums are taken from the SAME rounded values on v_mfma_f32_4x4x4_16b_f16 with an all-ones A operand (numerator and
 denominator of the softmax see identical probabilities, fp16 subnormals included, so the rounding largely cancels in O / l).
 Per step and query block: 10 big + 4 small MFMAs and 24 VALU instructions (16 exponentials, 8 conversions) against 12 and 56.
+
+One-block forms (ATTN_X3Q2_ONE_ASM, ATTN_X3Q2P_ONE_ASM): the same two statements with query block B switched off, for the wave
+whose second block does not exist (T = 1500: 47 query blocks on 48 slots -- the kernel used to run the loop on a second copy of
+block 46 and drop the result).  Ring protocol, LDS-DMA issue, barriers, waits, fragment reads, operand list and register
+assignment are those of the two-block statement (the wave still stages its share of every K / V tile for the other three);
+B's score, P.V and row-sum MFMAs and its softmax VALU instructions are left out.  A's instructions keep their order, so A's
+arithmetic is the two-block statement's instruction for instruction.  What B's work used to separate is kept apart by explicit
+wait states: behind a Y phase (A's last score MFMA -> A's first exponential) and behind an X phase (A's last conversion ->
+A's first P.V MFMA).
 """
 import os
 
@@ -112,6 +121,10 @@ def softmax_fillers(q):
     ]
 
 
+ONE = False                       # one-block forms: query block B switched off (see the module docstring)
+Y_GAP = ["s_nop 7", "s_nop 3"]      # one-block forms, behind a Y phase: 12 wait states between A's scores and their first VALU reader
+X_GAP = ["s_nop 3"]                 # ... behind an X phase: A's probability words are written before its P.V MFMAs read them
+
 ONES = 126                        # v[126:127]: packed fp16 (1, 1, 1, 1) -- the A operand of the row-sum MFMAs (P16)
 
 
@@ -141,6 +154,8 @@ def phase_p(sm, mm, pv_vbuf, sc_kbuf, reads, head=(), dma=None):
     s = lambda r: vr(S[sm] + r)      # noqa: E731
     E = [f"v_exp_f32_e32 {s(r)}, {s(r)}" for r in range(16)]
     C = [f"v_cvt_pk_f16_f32 {vr(H[sm] + j)}, {s(2 * j)}, {s(2 * j + 1)}" for j in range(8)]
+    if ONE and sm == "B":   # B has no softmax step: the fragment reads keep their slots
+        E, C = [None] * 16, [None] * 8
     g = [E[0:4] + [reads[0]],
          E[4:8] + [reads[1]] + E[8:12] + [reads[2]],
          E[12:16] + [reads[3]],
@@ -148,10 +163,13 @@ def phase_p(sm, mm, pv_vbuf, sc_kbuf, reads, head=(), dma=None):
          C[4:6],
          C[6:8],
          []]
+    g = [[x for x in grp if x is not None] for grp in g]
     if dma:   # refill of the ring (X(1) only): address arithmetic first, then one LDS-DMA instruction per filler group
         g[2] = g[2] + dma[0]
         for i in range(4):
             g[3 + i] = g[3 + i] + dma[1 + i]
+    if ONE and mm == "B":   # no MFMAs of B: A's softmax step, the reads and the refill in their order
+        return list(head) + [x for grp in g for x in grp] + X_GAP
     out = list(head)
     out += [pv[0]] + g[0] + [rs[0]]
     out += [sc[0], sc[1]] + g[1]
@@ -160,6 +178,8 @@ def phase_p(sm, mm, pv_vbuf, sc_kbuf, reads, head=(), dma=None):
     out += [pv[2]] + g[4] + [rs[2]]
     out += [sc[4], sc[5]] + g[5]
     out += [pv[3]] + g[6] + [rs[3]]
+    if ONE:
+        out += Y_GAP
     return out
 
 
@@ -201,7 +221,7 @@ def build_p():
           "s_cbranch_scc1 Lloop%="]
     # drain: P.V and row sums of B for the last block (V buffer 1); dependent MFMAs kept apart by explicit wait states
     pv, rs = pv_mfmas_p("B", 1), rowsum_mfmas("B")
-    for i in range(4):
+    for i in range(0 if ONE else 4):
         A += [pv[i], rs[i], "s_nop 7", "s_nop 3"]
     A += ["s_waitcnt lgkmcnt(0)", "s_nop 7", "s_nop 7"]
     return A
@@ -231,14 +251,16 @@ def phase(sm, mm, pv_vbuf, sc_kbuf, reads, head=(), tail_groups=None):
     if ABL & 4:
         out = [h for h in out if "barrier" not in h]
     for i in range(12):
-        if not ((ABL & 16) and i % 2 == 0) and not ((ABL & 8) and i % 2 == 1):
+        if not ((ABL & 16) and i % 2 == 0) and not ((ABL & 8) and i % 2 == 1) and not (ONE and mm == "B"):
             out.append(mf[i])
-        if not (ABL & 1):
+        if not (ABL & 1) and not (ONE and sm == "B"):
             out += fill[i]
         if i < 4 and not (ABL & 2):
             out.append(reads[i])
         if tail_groups and i in tail_groups and not (ABL & 4):
             out += tail_groups[i]
+    if ONE:
+        out += X_GAP if mm == "B" else Y_GAP
     return out
 
 
@@ -298,13 +320,14 @@ def build():
           f"s_cmp_lt_i32 {o('t')}, {o('nfull')}",
           f"s_cbranch_scc1 Lloop%="]
     # ---- drain: P.V of B for the last block (V buffer 1), then the MFMA results may be read by compiler code
-    A += pv_mfmas("B", 1)
+    if not ONE:
+        A += pv_mfmas("B", 1)
     A += ["s_waitcnt lgkmcnt(0)", "s_nop 7", "s_nop 7"]   # (the fragment reads of the next tile land in registers hipcc may reuse)
     return A
 
 
 def main():
-    global ABL
+    global ABL, ONE
     here = os.path.dirname(os.path.abspath(__file__))
     out = os.path.join(here, "..", "..", "beat_this_amd", "csrc", "attn_x3_loop.inc")
     lines = build()
@@ -328,6 +351,16 @@ def main():
         for x in lp:
             f.write(f'  "{x}\\n\\t" \\\n')
         f.write('  ""\n')
+        ONE = True
+        for macro, lo in (("ATTN_X3Q2_ONE_ASM", build()), ("ATTN_X3Q2P_ONE_ASM", build_p())):
+            f.write(f"// one-block form ({macro}: query block B switched off): {len(lo)} instructions, "
+                    f"{sum('v_mfma_f32_32x32' in x for x in lo)} big + {sum('v_mfma_f32_4x4x4' in x for x in lo)} small MFMAs; "
+                    "operands and clobbers of the two-block statement\n")
+            f.write(f"#define {macro} \\\n")
+            for x in lo:
+                f.write(f'  "{x}\\n\\t" \\\n')
+            f.write('  ""\n')
+        ONE = False
         f.write("#define ATTN_X3Q2_CLOBBERS " + ", ".join(f'"v{i}"' for i in CLOBBER_V) + ", " +
                 ", ".join(f'"s{i}"' for i in CLOBBER_S) + ', "scc", "memory"\n')
         # (P16 leaves the lo words, the row-sum tree's temporaries and v125 to the compiler: its row sums are four registers)
