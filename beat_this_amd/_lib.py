@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "engine.hip"]
+           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "engine.hip"]
 HEADERS = ["common.h", "chain.h", "kernels.h", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
@@ -105,6 +105,21 @@ class A2BPlan(C.Structure):   # bt_a2b_plan
                 ("off_forward", C.c_size_t), ("forward_bytes", C.c_size_t)]
 
 
+class TrainItem(C.Structure):   # bt_train_item
+    _fields_ = [("row", C.c_int64), ("ann_begin", C.c_int64), ("ann_end", C.c_int64), ("n", C.c_int32),
+                ("start_frame", C.c_int32), ("op_begin", C.c_int32), ("op_end", C.c_int32), ("has_downbeats", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class TrainOp(C.Structure):   # bt_train_op
+    _fields_ = [("start", C.c_int32), ("length", C.c_int32), ("kind", C.c_int32), ("part_begin", C.c_int32),
+                ("part_end", C.c_int32)]
+
+
+class TrainPart(C.Structure):   # bt_train_part
+    _fields_ = [("new_off", C.c_int32), ("old_off", C.c_int32)]
+
+
 G3_FF1, G3_RESID, G3_QKV = 0, 1, 2
 UNIT_STEM, UNIT_PARTIAL, UNIT_CONV, UNIT_LINEAR, UNIT_ATTN, UNIT_FF, UNIT_NORM, UNIT_FRONT_ATTN, UNIT_FRONT_FF = range(9)
 
@@ -183,6 +198,13 @@ EXPORTS = {
     "bt_bce_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int]),
     "bt_bce_loss_host": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bt_train_batch_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "bt_train_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bt_train_batch_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -198,7 +220,9 @@ FLAGS_BY_SOURCE = {"tail.hip": ["-Xclang", "-target-feature", "-Xclang", "-packe
                    # the metrics repeat numpy's fp64 operations one by one (interp midpoints, distances, ratios)
                    "metrics.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # the losses' fp32 terms must have the same bits on the host and the device (bt_bce_loss_host)
-                   "loss.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
+                   "loss.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
+                   # an annotation's frame is rint(time * fps) - start in fp64, the same on the host and the device
+                   "data.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
 # compile-time switches: BT_DEV_BUILD=1 in the environment of build() compiles the development instrumentation (per-wave timing
 # dumps, ablation variants read by tools/*_probe.py) into the kernels; release builds contain none of it
 EXTRA_DEFINES = (["-DBT_DEV"] if os.environ.get("BT_DEV_BUILD") == "1" else []) + os.environ.get("BT_DEFINES", "").split()

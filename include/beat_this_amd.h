@@ -407,6 +407,55 @@ int bt_bce_loss_host(int kind, int tolerance, float pos_weight, const void* logi
                      int target_dtype, const void* mask, int mask_dtype, const int64_t* offsets, int n_rows, double* row_sum,
                      int64_t* row_count, double* total, float* grad, float* terms);
 
+/* Training batches (the reference's beat_this/dataset: BeatTrackingDataset.__getitem__ + collate; csrc/data.hip, DESIGN.md
+ * section 12): excerpts of a resident spectrogram store with the mask augmentation applied as a gather, the framewise
+ * targets and the masks, ONE launch per batch, no memset, no atomics, no synchronisation, no allocation.
+ *
+ * Store: [store_rows][128] of store_dtype (BT_LOSS_F16 / BT_LOSS_F32).  Item b takes n <= L frames from store row `row`
+ * on; output frame t >= n is padding (zero spectrogram, zero targets, padding mask 0).  Its mask ops are ops[op_begin ..
+ * op_end) in the order the reference applies them in place; output frame t is resolved by walking them from the LAST to the
+ * first: outside [start, start + length) t stays; inside a BT_MASK_ZERO op the frame is zero; inside a BT_MASK_PERMUTE op
+ * t = start + old_off + (t - start - new_off) of the last part (parts[part_begin .. part_end), ascending new_off, new_off[0]
+ * = 0, no empty parts) whose new_off <= t - start.  Its annotations are time / value [ann_begin .. ann_end), times
+ * ascending; annotation i lies on frame rint(time[i] * fps) - start_frame (fp64, ties to even) and counts when
+ * 0 <= frame < n; it is a downbeat when value[i] == 1.  downbeat_mask[b] = has_downbeats != 0. */
+#define BT_MASK_ZERO 0
+#define BT_MASK_PERMUTE 1
+#define BT_TRAIN_FRAME_BLOCK 64   /* frames per workgroup */
+typedef struct {
+  int64_t row;                 /* first store row of the excerpt */
+  int64_t ann_begin, ann_end;  /* its range in the annotation arrays */
+  int32_t n;                   /* frames of the excerpt, 0 <= n <= L */
+  int32_t start_frame;         /* frame of the piece the excerpt starts at */
+  int32_t op_begin, op_end;    /* its range in the op table */
+  int32_t has_downbeats;
+  int32_t reserved;
+} bt_train_item;
+typedef struct {
+  int32_t start, length, kind; /* frames [start, start + length) of the excerpt, BT_MASK_* */
+  int32_t part_begin, part_end;/* its range in the parts table (permute only) */
+} bt_train_op;
+typedef struct {
+  int32_t new_off, old_off;    /* offset of the part in the permuted order and in the original one */
+} bt_train_part;
+/* sizeof of the three structs, then offsetof ann_begin, n, op_begin, has_downbeats (item), kind, part_begin (op), old_off
+ * (part): ten entries, the binding's self-check */
+void bt_train_batch_struct_sizes(int32_t* out);
+/* All pointers device memory; the tables may be NULL when their count is 0.  Outputs, each optional: d_spect [B][L][128] of
+ * spect_dtype (BT_LOSS_F32 / _F16; fp32 -> fp16 rounds to nearest even), d_truth_beat / d_truth_downbeat / d_padding_mask
+ * [B][L] uint8 (0 / 1), d_downbeat_mask [B] uint8.  Every byte of every output given is written.  A table entry that points
+ * outside its table or outside the store yields zeros, never an access outside; bt_train_batch_host refuses such tables. */
+int bt_train_batch(void* stream, const void* d_store, int store_dtype, int64_t store_rows, const bt_train_item* d_items, int B,
+                   int L, const bt_train_op* d_ops, int n_ops, const bt_train_part* d_parts, int n_parts,
+                   const double* d_ann_time, const int32_t* d_ann_value, int64_t n_ann, double fps, void* d_spect,
+                   int spect_dtype, uint8_t* d_truth_beat, uint8_t* d_truth_downbeat, uint8_t* d_padding_mask,
+                   uint8_t* d_downbeat_mask);
+/* HOST: the same from host memory, bit-identical outputs; tables are validated (BT_ERR_ARG names the first bad entry) */
+int bt_train_batch_host(const void* store, int store_dtype, int64_t store_rows, const bt_train_item* items, int B, int L,
+                        const bt_train_op* ops, int n_ops, const bt_train_part* parts, int n_parts, const double* ann_time,
+                        const int32_t* ann_value, int64_t n_ann, double fps, void* spect, int spect_dtype, uint8_t* truth_beat,
+                        uint8_t* truth_downbeat, uint8_t* padding_mask, uint8_t* downbeat_mask);
+
 /* HOST: deduplicate_peaks(peaks, width) on its own (postprocessor.py:176-197): groups of ascending frame indices not more than
  * `width` apart (measured from the running mean) are replaced by their mean; out must hold n doubles */
 int bt_deduplicate_peaks_host(const int32_t* idx, int n, double width, double* out, int32_t* n_out);
