@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "engine.hip"]
+           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "engine.hip"]
 HEADERS = ["common.h", "chain.h", "kernels.h", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
@@ -120,8 +120,20 @@ class TrainPart(C.Structure):   # bt_train_part
     _fields_ = [("new_off", C.c_int32), ("old_off", C.c_int32)]
 
 
+class TrainArgs(C.Structure):   # bt_train_args
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("dim", C.c_int32), ("hidden", C.c_int32), ("rope_len", C.c_int32),
+                ("residual", C.c_int32), ("sum_head", C.c_int32), ("reserved", C.c_int32), ("rope", C.c_void_p),
+                ("gamma", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
+                ("w3", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p), ("save_o", C.c_void_p),
+                ("save_lse", C.c_void_p), ("gy", C.c_void_p), ("gy2", C.c_void_p), ("gx", C.c_void_p), ("g_gamma", C.c_void_p),
+                ("g_w1", C.c_void_p), ("g_b1", C.c_void_p), ("g_w2", C.c_void_p), ("g_b2", C.c_void_p), ("g_w3", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 G3_FF1, G3_RESID, G3_QKV = 0, 1, 2
 UNIT_STEM, UNIT_PARTIAL, UNIT_CONV, UNIT_LINEAR, UNIT_ATTN, UNIT_FF, UNIT_NORM, UNIT_FRONT_ATTN, UNIT_FRONT_FF = range(9)
+TRAIN_UNIT_HEAD = 16                                        # BT_TRAIN_UNIT_HEAD
+TRAIN_DW_ROWS, TRAIN_CS_ROWS, TRAIN_ATTN_BLOCK = 1024, 64, 64   # BT_TRAIN_* tile edges (tests sit on both sides of them)
 
 EXPORTS = {
     "bt_last_error": (C.c_char_p, []),
@@ -205,6 +217,10 @@ EXPORTS = {
     "bt_train_batch_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bt_train_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "bt_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bt_train_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs)]),
+    "bt_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs)]),
 }
 
 

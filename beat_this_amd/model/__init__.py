@@ -9,6 +9,9 @@ follows the caller exactly like the reference: under ``torch.autocast`` (what
 ``Spect2Frames(float16=True)`` enters, inference.py:246) the half-precision (fp16 MFMA operand) path runs, otherwise
 an fp32-class path: exact fp32 MFMAs, or -- ``fp32_split_gemms``, what the inference classes select for
 ``float16=False`` -- three fp16 MFMAs per product on hi + lo operand halves.  There is no CPU implementation here.
+
+Fine-tuning: the main transformer layers, the final RMSNorm and the task heads are differentiable (``backward.py``); see the
+``BeatThis`` class docstring.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from . import backward as _bw
 from ..pack import Engine, PackedModel
 from ..weights import random_state_dict, resolve_hparams, state_dict_shapes
 
@@ -29,7 +33,7 @@ class _TracksChildren:
     """nn.Module mix-in: assigning, adding or deleting a sub-module bumps _TREE_EPOCH."""
 
     def __setattr__(self, name, value):
-        if isinstance(value, nn.Module):
+        if isinstance(value, (nn.Module, nn.Parameter)):   # (a replaced Parameter: the cached parameter lists are stale too)
             _TREE_EPOCH[0] += 1
         super().__setattr__(name, value)
 
@@ -107,6 +111,17 @@ class _Stage(_Node):
         return state
 
     def forward(self, x: torch.Tensor):
+        root = self._root()
+        if self._stage == 0:
+            root._refuse_trainable_frontend()
+        elif root._differentiable(x, self):
+            # the differentiable route (backward.py): the reference's container loop over the units / the head
+            if self._stage == 2:
+                return root._head_train(x)
+            for attn, ff in self.layers:
+                x = attn(x) + x
+                x = ff(x) + x
+            return self.norm(x)
         if self._stage < 2 and _hooked_below(self):
             # somebody hooked a sub-module of this stage: run it through the sub-modules, like the reference's containers
             # (beat_tracker.py:77-80, roformer.py:176-181), so that the hook fires
@@ -136,6 +151,16 @@ def _hooked_below(node: nn.Module) -> bool:
     return False
 
 
+def _params_of(node: nn.Module) -> tuple:
+    """The parameters below ``node``, collected once per tree epoch (asked on every call in grad mode)."""
+    epoch = _TREE_EPOCH[0]
+    cache = node.__dict__.get("_bt_params")
+    if cache is None or cache[0] != epoch:
+        cache = (epoch, tuple(node.parameters()))
+        node.__dict__["_bt_params"] = cache
+    return cache[1]
+
+
 def _attach(root: nn.Module, key: str, value: torch.Tensor) -> None:
     *path, leaf = key.split(".")
     node = root
@@ -150,6 +175,26 @@ def _attach(root: nn.Module, key: str, value: torch.Tensor) -> None:
 
 
 class BeatThis(_TracksChildren, nn.Module):
+    """The reference's ``BeatThis`` on the HIP kernels.  Inference is the default: parameters are created with
+    ``requires_grad=False``, the model is in ``eval()``, and nothing below changes what such a model runs.
+
+    Fine-tuning.  ``model.transformer_blocks.requires_grad_(True)`` and / or ``model.task_heads.requires_grad_(True)`` opt in.
+    When grad mode is on and one of those parameters requires grad -- or the tensor handed to ``transformer_blocks``,
+    ``task_heads``, ``layers[l][0]``, ``layers[l][1]`` or ``.norm`` does -- the differentiable route runs: ``forward`` computes
+    the frontend on the usual fast path under ``no_grad`` (at the model's own precision), then the six main layers, the final
+    RMSNorm and the heads go through ``torch.autograd.Function``s over the library's training kernels, composed like the
+    reference's containers.  Fixed semantics of that route:
+      * its arithmetic is fp32, whatever ``fp32_split_gemms`` says and also under ``torch.autocast``;
+      * dropout is taken as 0, in ``train()`` and ``eval()`` alike (the constructor still accepts ``dropout``);
+      * ``rotary_embed.freqs`` never receives a gradient, as in the reference;
+      * the frontend is frozen in this version: a frontend parameter that requires grad makes a grad-mode forward raise
+        ``NotImplementedError`` rather than silently leaving its ``.grad`` empty;
+      * parameters on the CPU raise the same ``RuntimeError`` as ever.
+    The route reads the parameters' storage at call time, so an optimizer step is seen at once.  The inference paths run on
+    packed copies: the ``_version`` of every parameter is recorded when they are packed, and a parameter that requires grad
+    and was changed in place since makes the next inference call pack again (checked only for parameters that require grad).
+    """
+
     def __init__(self, spect_dim: int = 128, transformer_dim: int = 512, ff_mult: int = 4, n_layers: int = 6,
                  head_dim: int = 32, stem_dim: int = 32, dropout: dict = {"frontend": 0.1, "transformer": 0.2},
                  sum_head: bool = True, partial_transformers: bool = True):
@@ -165,6 +210,7 @@ class BeatThis(_TracksChildren, nn.Module):
             _attach(self, key, init[key])
         self._bind_units()
         self._engine = None
+        self._packed_versions = ()   # (is frontend, parameter, its _version when the engine was packed)
         # outside autocast: True = every product of the forward on three half MFMAs over hi + lo operand halves
         # (BT_PREC_F32X3: fp32-class results -- 1e-5 at the logits, identical beats -- at 16/3 of the fp32 matrix rate; operands
         # beyond the fp16 range of a hi half are detected and the batch is repeated on the exact path, Engine.forward_stages);
@@ -177,6 +223,7 @@ class BeatThis(_TracksChildren, nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_engine"] = None   # (a handle of the HIP library: rebuilt on first use)
+        state["_packed_versions"] = ()
         return state
 
     def __setstate__(self, state):
@@ -214,17 +261,30 @@ class BeatThis(_TracksChildren, nn.Module):
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         state_dict = {k.replace("_orig_mod.", ""): v for k, v in state_dict.items()}
         self._engine = None
+        _TREE_EPOCH[0] += 1   # (assign=True replaces the Parameter objects)
         return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     def _apply(self, fn, *args, **kwargs):
         self._engine = None
+        _TREE_EPOCH[0] += 1
         return super()._apply(fn, *args, **kwargs)
 
     @property
     def device(self) -> torch.device:
         return self.task_heads.beat_downbeat_lin.weight.device
 
-    def engine(self) -> Engine:
+    def _stale(self, frontend_only: bool) -> bool:
+        """A parameter that requires grad was changed in place since the engine packed its copy (an optimizer step)."""
+        for front, p, version in self._packed_versions:
+            if p.requires_grad and p._version != version and (front or not frontend_only):
+                return True
+        return False
+
+    def engine(self, frontend_only: bool = False) -> Engine:
+        """The inference engine on packed copies of the parameters; packed again when a trainable parameter changed in place
+        (``frontend_only``: the caller runs the frontend alone, whose parameters are frozen)."""
+        if self._engine is not None and self._stale(frontend_only):
+            self._engine = None
         if self._engine is None:
             dev = self.device
             if dev.type != "cuda":
@@ -233,12 +293,73 @@ class BeatThis(_TracksChildren, nn.Module):
                     "move the model to a ROCm GPU: model.to('cuda')")
             _lib.lib()  # fail loudly if the HIP library is missing
             self._engine = Engine(PackedModel(self.state_dict(), self.hparams, dev))
+            self._packed_versions = tuple((name.startswith("frontend."), p, p._version) for name, p in self.named_parameters())
         return self._engine
+
+    # -- the differentiable route (backward.py) ------------------------------------------------------------------------------
+    def _differentiable(self, x, node: nn.Module) -> bool:
+        """Grad mode is on and ``x`` (if given) or a parameter below ``node`` requires grad."""
+        if not torch.is_grad_enabled():
+            return False
+        if x is not None and x.requires_grad:
+            return True
+        for p in _params_of(node):
+            if p.requires_grad:
+                return True
+        return False
+
+    def _refuse_trainable_frontend(self) -> None:
+        if torch.is_grad_enabled():
+            for p in _params_of(self.frontend):
+                if p.requires_grad:
+                    raise NotImplementedError(
+                        "the frontend is frozen in this version: only transformer_blocks and task_heads are differentiable; "
+                        "call model.frontend.requires_grad_(False) (or run under torch.no_grad())")
+
+    def _rope(self, T: int):
+        """The engine's rotary table for ``T`` frames (the table does not depend on anything that is trained)."""
+        eng = self._engine if self._engine is not None else self.engine()
+        eng.ensure_positions(T)
+        return eng.packed._rope_t, int(eng.packed.desc.rope_len)
+
+    def _unit_train(self, x: torch.Tensor, kind: str, node: nn.Module) -> torch.Tensor:
+        D = self.hparams["transformer_dim"]
+        _lib.require_gpu(x, "sub-module input")
+        if self.device.type != "cuda":
+            self.engine()   # (raises: no CPU implementation)
+        if x.dim() != 3 or x.shape[2] != D:
+            raise ValueError(f"expected a (batch, time, {D}) input, got {tuple(x.shape)}")
+        if x.shape[0] == 0 or x.shape[1] == 0:
+            return _bw.empty_with_graph(x.shape, x, _params_of(node))
+        x = x.to(torch.float32)
+        if kind == "attn":
+            return _bw.attention(node, x, *self._rope(x.shape[1]))
+        return _bw.feedforward(node, x) if kind == "ff" else _bw.final_norm(node, x)
+
+    def _head_train(self, x: torch.Tensor) -> dict:
+        D = self.hparams["transformer_dim"]
+        _lib.require_gpu(x, "stage input")
+        if self.device.type != "cuda":
+            self.engine()
+        if x.dim() != 3 or x.shape[2] != D:
+            raise ValueError(f"expected a (batch, time, {D}) input, got {tuple(x.shape)}")
+        if x.shape[0] == 0 or x.shape[1] == 0:
+            params = _params_of(self.task_heads)
+            return {"beat": _bw.empty_with_graph(x.shape[:2], x, params), "downbeat": _bw.empty_with_graph(x.shape[:2], x, params)}
+        beat, down = _bw.head(self.task_heads, x.to(torch.float32), self.hparams["sum_head"])
+        return {"beat": beat, "downbeat": down}
 
     def forward(self, x: torch.Tensor) -> dict:
         if x.dim() != 3:
             raise ValueError(f"expected (batch, time, {self.hparams['spect_dim']}) input, got {tuple(x.shape)}")
         _lib.require_gpu(x, "model input")
+        if torch.is_grad_enabled():
+            self._refuse_trainable_frontend()
+            if self._differentiable(None, self.transformer_blocks) or self._differentiable(None, self.task_heads):
+                # fine-tuning: the frozen frontend on the fast path, the trunk and the heads on the differentiable route
+                with torch.no_grad():
+                    h = self.frontend(x)
+                return self.task_heads(self.transformer_blocks(h))
         if x.shape[0] == 0 or x.shape[1] == 0:
             empty = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
             return {"beat": empty, "downbeat": empty.clone()}
@@ -266,12 +387,17 @@ class BeatThis(_TracksChildren, nn.Module):
             empty = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
             return (empty, empty.clone()) if last == 2 else torch.empty((x.shape[0], x.shape[1], D), dtype=torch.float32, device=x.device)
         prec = self._precision() if prec is None else prec
-        return self.engine().forward_stages(x, prec, first, last, logits_out=out, checks=checks)
+        return self.engine(frontend_only=last == 0).forward_stages(x, prec, first, last, logits_out=out, checks=checks)
 
     def _run_unit(self, x: torch.Tensor, kind: str, index: int):
         """A sub-module call (see _Node): reference layouts in and out, fp32 results; precision follows autocast (the hi + lo
         mode of ``fp32_split_gemms`` is the exact fp32 path here)."""
         _lib.require_gpu(x, "sub-module input")
+        if kind in ("attn", "ff", "norm"):
+            tb = self.transformer_blocks
+            node = tb.norm if kind == "norm" else tb.layers[index][0 if kind == "attn" else 1]
+            if self._differentiable(x, node):
+                return self._unit_train(x, kind, node)
         half = torch.is_autocast_enabled("cuda") if hasattr(torch, "is_autocast_enabled") else False
         prec = _lib.PREC_HALF if half else _lib.PREC_F32
         eng = self.engine()

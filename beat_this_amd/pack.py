@@ -645,7 +645,11 @@ class _GraphEntry:
             capture.wait_stream(torch.cuda.current_stream(dev))
             self.graph = torch.cuda.CUDAGraph()
             # (thread_local: other host threads keep launching on their own streams while this one records)
-            with torch.cuda.graph(self.graph, stream=capture, capture_error_mode="thread_local"):   # ... then recorded on a stream of the engine's device
+            # (inference_mode(False): the first live capture of a process makes torch allocate the CUDA generator's graph-state
+            # tensors, and every later capture fills them in place.  The inference classes get here inside inference_mode; state
+            # allocated there would be inference tensors, and a capture OUTSIDE inference mode -- a training step -- would then
+            # be refused for as long as this entry lives.)
+            with torch.inference_mode(False), torch.cuda.graph(self.graph, stream=capture, capture_error_mode="thread_local"):   # ... then recorded on a stream of the engine's device
                 self._launch()
             # a capture is only trusted once a replay has reproduced the plain launches bit for bit (same kernels, same input)
             self.beat.fill_(float("nan"))

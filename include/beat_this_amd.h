@@ -600,6 +600,47 @@ int bt_attnff_fused(void* stream, int prec, const bt_pair_weights* w, const floa
 int bt_layer_tail(void* stream, const bt_pair_weights* w, int hidden, const void* d_ao, float* d_x, int64_t M, void* d_xb,
                   float* d_ssq_out);
 
+/* ---- training: forward and backward of the trunk's units and of the heads (csrc/train.hip) ------------
+ * One call per unit, like bt_forward_unit: BT_UNIT_ATTN, BT_UNIT_FF, BT_UNIT_NORM (the trunk's final RMSNorm) and
+ * BT_TRAIN_UNIT_HEAD.  Everything is fp32 with fp32 accumulation.  The parameters are read in the REFERENCE's layout and values,
+ * straight from the nn.Parameter storage -- not the engine's packed copies:
+ *   attention:  gamma = norm.gamma [dim], w1 = to_qkv.weight [3 dim, dim], w2 / b2 = to_gates.weight [dim / 32, dim] / .bias,
+ *               w3 = to_out.0.weight [dim, dim], rope = the engine's [rope_len][16][2] cos / sin table
+ *   FF:         gamma = net.0.gamma, w1 / b1 = net.1.weight [hidden, dim] / .bias, w2 / b2 = net.4.weight [dim, hidden] / .bias
+ *   norm:       gamma = transformer_blocks.norm.gamma
+ *   head:       w1 / b1 = task_heads.beat_downbeat_lin.weight [2, dim] / .bias [2]; sum_head: beat = b + d (SumHead) or b (Head)
+ * Shapes: x, y, gy, gx [B T, dim] contiguous; dim a multiple of 32 from 32 to 1024 (heads of 32), hidden = ff_mult dim with
+ * ff_mult 1 .. 16, 1 <= T <= rope_len (0: 1536); anything else is BT_ERR_ARG.  residual != 0: the unit is x + f(x) (attention and FF).
+ * The forward writes y (head: y = beat, y2 = downbeat, each [B T]) and, for the attention, what the backward needs beside x:
+ * save_o [B T, dim] (the attention output before the gate) and save_lse [B T, dim / 32] (base-2 log-sum-exp of the scaled
+ * scores); everything else is recomputed.  The backward takes x, those two, the upstream gradient gy (head: gy = d beat, gy2 =
+ * d downbeat, either may be NULL = zero) and OVERWRITES the gradients whose pointer is not NULL: gx, g_gamma, g_w1, g_b1, g_w2,
+ * g_b2, g_w3 (shaped like the parameters).  Every byte of a gradient is written by one thread of one launch; there are no
+ * atomics, and the order of every sum depends on (B, T, dim, hidden) only: results are bitwise reproducible, and a
+ * sequence's gx is the same alone and inside a batch.  Weight gradients are summed over chunks of BT_TRAIN_DW_ROWS rows, bias
+ * and gamma gradients over chunks of BT_TRAIN_CS_ROWS rows (partials in the workspace, added in chunk order by a second
+ * launch); the attention works on blocks of BT_TRAIN_ATTN_BLOCK queries x keys.  No call synchronises, allocates or clears
+ * memory: ws / ws_bytes is the caller's workspace, at least bt_train_workspace_bytes (0: unsupported shape), contents
+ * undefined before and after; no launch reads workspace bytes that the same call has not written. */
+#define BT_TRAIN_UNIT_HEAD 16
+#define BT_TRAIN_DW_ROWS 1024
+#define BT_TRAIN_CS_ROWS 64
+#define BT_TRAIN_ATTN_BLOCK 64
+typedef struct {
+  int32_t B, T, dim, hidden, rope_len, residual, sum_head, reserved;
+  const float* rope;
+  const float* gamma; const float* w1; const float* b1; const float* w2; const float* b2; const float* w3;
+  const float* x; float* y; float* y2; float* save_o; float* save_lse;
+  const float* gy; const float* gy2;
+  float* gx; float* g_gamma; float* g_w1; float* g_b1; float* g_w2; float* g_b2; float* g_w3;
+  void* ws; size_t ws_bytes;
+} bt_train_args;
+/* sizeof, then offsetof rope, x, gy, gx, ws, ws_bytes: seven entries, the binding's self-check */
+void bt_train_struct_sizes(int32_t* out);
+size_t bt_train_workspace_bytes(int unit, int backward, int B, int T, int dim, int hidden);
+int bt_train_forward(void* stream, int unit, const bt_train_args* a);
+int bt_train_backward(void* stream, int unit, const bt_train_args* a);
+
 #ifdef __cplusplus
 }
 #endif
