@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "engine.hip"]
+           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "optim.hip", "engine.hip"]
 HEADERS = ["common.h", "chain.h", "kernels.h", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
@@ -130,10 +130,32 @@ class TrainArgs(C.Structure):   # bt_train_args
                 ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
+class OptimTensor(C.Structure):   # bt_optim_tensor
+    _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int64), ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimChunk(C.Structure):   # bt_optim_chunk
+    _fields_ = [("tensor", C.c_int32), ("chunk", C.c_int32)]
+
+
+class OptimGroup(C.Structure):   # bt_optim_group
+    _fields_ = [("decay", C.c_float), ("one_minus_beta1", C.c_float), ("beta2", C.c_float), ("one_minus_beta2", C.c_float),
+                ("step_size", C.c_float), ("bias2_sqrt", C.c_float), ("eps", C.c_float), ("reserved", C.c_float)]
+
+
+OPTIM_MAX_GROUPS = 8                                        # BT_OPTIM_MAX_GROUPS
+
+
+class OptimHyper(C.Structure):   # bt_optim_hyper
+    _fields_ = [("n_groups", C.c_int32), ("zero_grads", C.c_int32), ("grad_scale", C.c_float), ("reserved", C.c_int32),
+                ("g", OptimGroup * OPTIM_MAX_GROUPS)]
+
+
 G3_FF1, G3_RESID, G3_QKV = 0, 1, 2
 UNIT_STEM, UNIT_PARTIAL, UNIT_CONV, UNIT_LINEAR, UNIT_ATTN, UNIT_FF, UNIT_NORM, UNIT_FRONT_ATTN, UNIT_FRONT_FF = range(9)
 TRAIN_UNIT_HEAD = 16                                        # BT_TRAIN_UNIT_HEAD
 TRAIN_DW_ROWS, TRAIN_CS_ROWS, TRAIN_ATTN_BLOCK = 1024, 64, 64   # BT_TRAIN_* tile edges (tests sit on both sides of them)
+OPTIM_CHUNK, OPTIM_NORM_SLICE = 4096, 4096                 # BT_OPTIM_CHUNK / _NORM_SLICE: elements per workgroup (likewise)
 
 EXPORTS = {
     "bt_last_error": (C.c_char_p, []),
@@ -221,6 +243,16 @@ EXPORTS = {
     "bt_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bt_train_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs)]),
     "bt_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs)]),
+    "bt_optim_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "bt_optim_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
+                                C.c_int64, C.POINTER(C.c_int64)]),
+    "bt_grad_norm_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "bt_grad_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bt_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_int64, C.POINTER(OptimHyper), C.c_void_p]),
+    "bt_grad_norm_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]),
+    "bt_adamw_step_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.POINTER(OptimHyper), C.c_void_p]),
 }
 
 
@@ -238,7 +270,9 @@ FLAGS_BY_SOURCE = {"tail.hip": ["-Xclang", "-target-feature", "-Xclang", "-packe
                    # the losses' fp32 terms must have the same bits on the host and the device (bt_bce_loss_host)
                    "loss.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # an annotation's frame is rint(time * fps) - start in fp64, the same on the host and the device
-                   "data.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
+                   "data.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
+                   # the AdamW step and the gradient norm must have the same bits on the host and the device (the host twins)
+                   "optim.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
 # compile-time switches: BT_DEV_BUILD=1 in the environment of build() compiles the development instrumentation (per-wave timing
 # dumps, ablation variants read by tools/*_probe.py) into the kernels; release builds contain none of it
 EXTRA_DEFINES = (["-DBT_DEV"] if os.environ.get("BT_DEV_BUILD") == "1" else []) + os.environ.get("BT_DEFINES", "").split()

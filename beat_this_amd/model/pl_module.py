@@ -1,0 +1,160 @@
+"""``PLBeatThis`` -- the reference's training module (beat_this/model/pl_module.py:21-317) without Lightning: a plain
+``nn.Module`` that wraps a ``BeatThis`` model with its loss pair, post-processor, metrics and optimiser, and is driven by
+``beat_this_amd.train.fit``.  Same constructor arguments, same ``state_dict`` keys (``model.`` prefix) and the same
+``hyper_parameters``, so the checkpoints ``fit`` writes are read by ``load_model`` and ``losses_from_hparams`` like the
+reference's.  The schedule and the parameter grouping live in ``beat_this_amd.optim``.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+from torch import nn
+
+from .. import optim as _optim
+from ..loss import losses_from_hparams
+from ..metrics import Metrics
+from ..postprocessor import Postprocessor
+from . import BeatThis
+
+CosineWarmupScheduler = _optim.CosineWarmupScheduler   # (the reference defines it in this module)
+
+
+def _plain(value):
+    """hyper-parameters as plain Python values (what ``torch.load(..., weights_only=True)`` reads back)"""
+    if isinstance(value, dict):
+        return {str(k): _plain(v) for k, v in value.items()}
+    if isinstance(value, (list, tuple)):
+        return [_plain(v) for v in value]
+    if isinstance(value, (bool, np.bool_)):
+        return bool(value)
+    if isinstance(value, (int, np.integer)):
+        return int(value)
+    if isinstance(value, (float, np.floating)):
+        return float(value)
+    return value
+
+
+TARGETS = ("beat", "downbeat")
+_MODEL_KEYS = ("spect_dim", "transformer_dim", "ff_mult", "stem_dim", "n_layers", "head_dim", "dropout", "sum_head", "partial_transformers")
+
+
+class PLBeatThis(nn.Module):
+    """The model and everything a training run needs around it.
+
+    The frontend is frozen (``requires_grad_(False)``: its backward pass is not part of this package); the six main layers,
+    the final RMSNorm and the task heads are trainable.  ``dropout`` is accepted and stored in the hyper-parameters, but the
+    differentiable route runs with dropout 0 and in fp32 (see ``BeatThis``), so a run here is not the reference's
+    regularisation.  ``max_epochs`` is stored only; ``fit`` takes the number of epochs to run."""
+
+    def __init__(self, spect_dim=128, fps=50, transformer_dim=512, ff_mult=4, n_layers=6, stem_dim=32,
+                 dropout={"frontend": 0.1, "transformer": 0.2}, lr=0.0008, weight_decay=0.01,
+                 pos_weights={"beat": 1, "downbeat": 1}, head_dim=32, loss_type="shift_tolerant_weighted_bce",
+                 warmup_steps=1000, max_epochs=100, use_dbn=False, eval_trim_beats=5, sum_head=True, partial_transformers=True):
+        given = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
+        super().__init__()
+        hp = self.hyper_parameters = _plain(given)   # what a checkpoint carries: every constructor argument, as plain values
+        for key in ("lr", "weight_decay", "fps", "warmup_steps", "max_epochs", "pos_weights", "eval_trim_beats"):
+            setattr(self, key, hp[key])
+        self.model = BeatThis(**{k: hp[k] for k in _MODEL_KEYS})
+        # trainable: the trunk and the heads, without the rotary tables (fixed in the reference too); frozen: the frontend
+        for name, p in self.model.named_parameters():
+            p.requires_grad_(not name.startswith("frontend.") and not name.endswith("rotary_embed.freqs"))
+        self.beat_loss, self.downbeat_loss = losses_from_hparams(hp)
+        self.postprocessor = Postprocessor(("minimal", "dbn")[bool(use_dbn)], fps)
+        self.metrics = Metrics(eval_trim_beats)
+        self.lr_scheduler = None
+
+    # ---- losses and metrics ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _loss_masks(batch) -> dict:
+        """Which frames count, per target: everything that is not padding; for downbeats only in pieces whose dataset
+        annotates them (the reference multiplies the two masks, pl_module.py:100-105)."""
+        frames = batch["padding_mask"]
+        annotated = batch["downbeat_mask"].reshape(-1, 1)
+        return {"beat": frames, "downbeat": torch.logical_and(frames, annotated)}
+
+    def _compute_loss(self, batch, model_prediction) -> dict:
+        """-> {"beat", "downbeat", "total"}: each target's loss on its float targets and mask, and their sum"""
+        masks = self._loss_masks(batch)
+        fns = dict(zip(TARGETS, (self.beat_loss, self.downbeat_loss)))
+        out = {t: fns[t](model_prediction[t], batch["truth_" + t].float(), masks[t]) for t in TARGETS}
+        out["total"] = out["beat"] + out["downbeat"]
+        return out
+
+    def _compute_metrics(self, batch, postp_beat, postp_downbeat, step="val") -> dict:
+        """Batch means of ``Metrics`` per target, keyed "<metric>_<target>".  The truth is the annotations in seconds
+        (``truth_orig_*``: float64 bytes, one entry per piece), not the quantised frame targets; a tuple-valued metric (Cemgil)
+        is averaged over its entries too, as the reference's np.mean does (pl_module.py:156-160)."""
+        out = {}
+        for target, events in zip(TARGETS, (postp_beat, postp_downbeat)):
+            pieces = events if isinstance(events, tuple) else (events,)   # (an unbatched post-processor call gives one array)
+            truths = batch["truth_orig_" + target]
+            if len(truths) != len(pieces):
+                raise ValueError(f"{len(pieces)} predicted {target} sequences for {len(truths)} annotated pieces")
+            rows = [self.metrics(np.frombuffer(t, dtype=np.float64), e, step=step) for t, e in zip(truths, pieces)]
+            for name in rows[0]:
+                out[f"{name}_{target}"] = float(np.mean([r[name] for r in rows]))
+        return out
+
+    def _postprocess(self, prediction, padding_mask):
+        return self.postprocessor(*(prediction[t] for t in TARGETS), padding_mask)
+
+    # ---- the steps: what the reference's steps compute (pl_module.py:199-277), returned instead of logged ------------------------
+    def training_step(self, batch, batch_idx=0):
+        """-> the total loss (differentiable); the three losses of the batch stay in ``self.last_losses`` (detached)"""
+        losses = self._compute_loss(batch, self.model(batch["spect"]))
+        self.last_losses = {k: v.detach() for k, v in losses.items()}
+        return losses["total"]
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0):
+        """-> (losses, metrics): F-measure and Cemgil of beats and downbeats on the batch's excerpts"""
+        prediction = self.model(batch["spect"])
+        events = self._postprocess(prediction, batch["padding_mask"])
+        return self._compute_loss(batch, prediction), self._compute_metrics(batch, *events, step="val")
+
+    @torch.no_grad()
+    def test_step(self, batch, batch_idx=0):
+        """-> (losses, metrics) of one whole piece, through ``predict_step``"""
+        metrics, prediction = self.predict_step(batch, batch_idx)[:2]
+        return self._compute_loss(batch, prediction), metrics
+
+    @torch.no_grad()
+    def predict_step(self, batch, batch_idx=0, dataloader_idx=0, chunk_size=1500, overlap_mode="keep_first"):
+        """One whole piece (a batch of one, unpadded) in chunks of ``chunk_size`` frames -> (metrics, prediction, dataset,
+        spect_path); where chunks overlap, ``overlap_mode`` keeps the first ("keep_first") or the last one's frames.  The
+        frames the loss crops at a chunk's edges (twice its tolerance) are the chunks' borders."""
+        from ..inference import split_predict_aggregate
+
+        spect = batch["spect"]
+        if spect.dim() != 3 or spect.shape[0] != 1:
+            raise ValueError(f"predict_step takes one whole piece per call, got a batch of shape {tuple(spect.shape)}: "
+                             "use a loader with batch_size=1")
+        if not bool(batch["padding_mask"].all()):
+            raise ValueError("predict_step takes an unpadded piece: build the dataset with train_length=None")
+        border = 2 * getattr(self.beat_loss, "tolerance", 0)
+        logits = split_predict_aggregate(spect[0], chunk_size, border, overlap_mode, self.model)
+        prediction = {t: logits[t][None] for t in TARGETS}
+        metrics = self._compute_metrics(batch, *self._postprocess(prediction, None), step="test")
+        return metrics, prediction, batch["dataset"], batch["spect_path"]
+
+    def configure_optimizers(self, total_steps, max_grad_norm=None, accumulate=1):
+        """The reference's optimiser and schedule (pl_module.py:279-306) on this package's kernels: AdamW at ``lr`` with
+        ``weight_decay`` on the matrices only, and the cosine schedule with ``warmup_steps`` over ``total_steps`` optimiser
+        steps (what Lightning's ``estimated_stepping_batches`` is there), stepped once per optimiser step."""
+        optimizer = _optim.AdamW(_optim.param_groups_for(self, self.weight_decay), lr=self.lr, max_grad_norm=max_grad_norm,
+                                 accumulate=accumulate)
+        self.lr_scheduler = _optim.CosineWarmupScheduler(optimizer, self.warmup_steps, total_steps)
+        return {"optimizer": optimizer, "lr_scheduler": {"scheduler": self.lr_scheduler, "interval": "step"}}
+
+    # ---- state dict: the reference's keys ("model." prefix; torch.compile's "_orig_mod." never appears) ----------------------------
+    def state_dict(self, *args, **kwargs):
+        return {k.replace("_orig_mod.", ""): v for k, v in super().state_dict(*args, **kwargs).items()}
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        """Hands the "model." entries to ``BeatThis.load_state_dict`` (which drops its packed inference engine)"""
+        clean = {k.replace("_orig_mod.", ""): v for k, v in state_dict.items()}
+        inner = {k[len("model."):]: v for k, v in clean.items() if k.startswith("model.")}
+        if strict and len(inner) != len(clean):
+            raise RuntimeError(f"unexpected keys in the state dict: {sorted(k for k in clean if not k.startswith('model.'))[:5]}")
+        return self.model.load_state_dict(inner, strict=strict, assign=assign)

@@ -1,0 +1,240 @@
+#!/usr/bin/env python3
+"""Fine-tuning loop: ``fit`` drives a ``PLBeatThis`` over a ``BeatDataModule`` the way the reference's Lightning trainer is set
+up in launch_scripts/train.py:118-131 -- epochs over the training loader, gradient accumulation, one optimiser and scheduler
+step per accumulated batch group, validation with the package's own metrics every few epochs, one checkpoint per epoch -- and
+``python -m beat_this_amd.train`` is the command line around it.  Every step's arithmetic runs in the package's kernels: the
+differentiable route of ``BeatThis`` (fp32, dropout 0, frozen frontend), the losses, and the fused AdamW of
+``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
+and ``load_model`` read as it is.
+
+Not offered: the reference's wandb logger, ``--compile`` and ``--force-flash-attention`` (nothing here is compiled by torch or
+runs torch's attention), mixed precision, and the test run after training (``beat_this_amd.evaluate`` scores a checkpoint).
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+FPS = 50
+# the augmentation settings and the target widening of the class weights that the reference trains with
+# (launch_scripts/train.py:42-57, 75); the three --*-augmentation switches pick from the table
+AUGMENTATIONS = {
+    "tempo": {"min": -20, "max": 20, "stride": 4},
+    "pitch": {"min": -5, "max": 6},
+    "mask": {"kind": "permute", "min_count": 1, "max_count": 6, "min_len": 0.1, "max_len": 2, "min_parts": 5, "max_parts": 9},
+}
+POS_WEIGHT_WIDEN = 3
+CHECKPOINT_KEYS = ("state_dict", "hyper_parameters", "optimizer_states", "lr_schedulers", "epoch", "global_step", "rng")
+
+
+def _rng_state() -> dict:
+    """numpy's global generator (the data pipeline's only source of randomness) as tensors and plain numbers"""
+    kind, keys, pos, has_gauss, cached = np.random.get_state()
+    return {"kind": str(kind), "keys": torch.from_numpy(np.asarray(keys, dtype=np.int64)), "pos": int(pos),
+            "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}
+
+
+def _set_rng_state(state: dict) -> None:
+    np.random.set_state((state["kind"], state["keys"].numpy().astype(np.uint32), int(state["pos"]), int(state["has_gauss"]),
+                         float(state["cached_gaussian"])))
+
+
+def _to_cpu(obj):
+    if isinstance(obj, torch.Tensor):
+        return obj.detach().cpu()
+    if isinstance(obj, dict):
+        return {k: _to_cpu(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_cpu(v) for v in obj)
+    return obj
+
+
+def save_checkpoint(path, pl_module, optimizer, scheduler, epoch: int, global_step: int) -> None:
+    """One file with the reference's (Lightning's) top-level keys: ``state_dict`` (``model.`` prefix), ``hyper_parameters``,
+    ``optimizer_states`` and ``lr_schedulers`` (one entry each), ``epoch`` (the last finished one), ``global_step`` (optimiser
+    steps so far) and ``rng``.  Written next to ``path`` first and then moved over it."""
+    ckpt = {"state_dict": _to_cpu(dict(pl_module.state_dict())), "hyper_parameters": dict(pl_module.hyper_parameters),
+            "optimizer_states": [_to_cpu(optimizer.state_dict())], "lr_schedulers": [_to_cpu(scheduler.state_dict())],
+            "epoch": int(epoch), "global_step": int(global_step), "rng": _rng_state()}
+    path = os.fspath(path)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = path + ".part"
+    torch.save(ckpt, tmp)
+    os.replace(tmp, path)
+
+
+def validate(pl_module, datamodule) -> dict:
+    """The mean over the validation set (weighted by batch size) of the losses and of what the reference's ``step="val"``
+    reports: F-measure and Cemgil for beats and downbeats."""
+    sums, count = {}, 0
+    for i, batch in enumerate(datamodule.val_dataloader()):
+        losses, metrics = pl_module.validation_step(batch, i)
+        n = int(batch["spect"].shape[0])
+        values = {"val_loss": losses["total"], "val_loss_beat": losses["beat"], "val_loss_downbeat": losses["downbeat"]}
+        values.update({f"val_{k}": v for k, v in metrics.items()})
+        for k, v in values.items():
+            sums[k] = sums.get(k, 0.0) + n * float(v)
+        count += n
+    return {k: v / count for k, v in sums.items()} if count else {}
+
+
+def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
+        resume=None, log=print) -> dict:
+    """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
+
+    Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
+    with its own count) one ``optimizer.step()`` and ``scheduler.step()`` -- the 1 / count scaling and, with ``max_grad_norm``,
+    the clipping to that global gradient norm happen inside the optimiser's kernels.  The schedule spans all
+    ``max_epochs * ceil(batches / accumulate_grad_batches)`` steps.  The epoch's mean training loss is accumulated on the
+    device and read once per epoch.  After every ``val_frequency``-th epoch ``validate`` runs.  At each epoch's end a
+    checkpoint goes to ``checkpoint_path`` (if given).  ``resume``: such a checkpoint (path or loaded dict) -- weights,
+    optimiser, schedule, counters and numpy's generator are restored and the run continues with the next epoch, bit for bit
+    as if it had not stopped.
+
+    -> dict: ``train_loss`` (one mean per epoch run), ``val`` ([(epoch, metrics)]), ``epoch``, ``global_step``, ``optimizer``,
+    ``scheduler``."""
+    accumulate = int(accumulate_grad_batches)
+    if accumulate < 1 or int(max_epochs) < 0 or int(val_frequency) < 1:
+        raise ValueError("accumulate_grad_batches and val_frequency must be at least 1, max_epochs at least 0")
+    datamodule.setup("fit")   # (returns at once when the caller has set the data up already)
+    loader = datamodule.train_dataloader()
+    steps_per_epoch = math.ceil(len(loader) / accumulate)
+    conf = pl_module.configure_optimizers(max(1, steps_per_epoch * int(max_epochs)), max_grad_norm=max_grad_norm, accumulate=accumulate)
+    optimizer, scheduler = conf["optimizer"], conf["lr_scheduler"]["scheduler"]
+    device = optimizer.device
+    first_epoch, global_step = 0, 0
+    if resume is not None:
+        from .inference import load_checkpoint
+
+        ckpt = resume if isinstance(resume, dict) else load_checkpoint(resume, "cpu")
+        missing = [k for k in CHECKPOINT_KEYS if k not in ckpt]
+        if missing:
+            raise ValueError(f"cannot resume: the checkpoint has no {missing} (written by fit()?)")
+        pl_module.load_state_dict(ckpt["state_dict"])
+        optimizer.load_state_dict(ckpt["optimizer_states"][0])
+        scheduler.load_state_dict(ckpt["lr_schedulers"][0])
+        _set_rng_state(ckpt["rng"])
+        first_epoch, global_step = int(ckpt["epoch"]) + 1, int(ckpt["global_step"])
+        log(f"resumed after epoch {ckpt['epoch']} ({global_step} optimiser steps)")
+    history = {"train_loss": [], "val": [], "optimizer": optimizer, "scheduler": scheduler}
+    optimizer.zero_grad()
+    for epoch in range(first_epoch, int(max_epochs)):
+        loss_sum = torch.zeros((), dtype=torch.float32, device=device)
+        batches = pending = 0
+        for i, batch in enumerate(loader):
+            loss = pl_module.training_step(batch, i)
+            loss.backward()
+            loss_sum += loss.detach()
+            batches += 1
+            pending += 1
+            if pending == accumulate:
+                optimizer.step(accumulated=pending)
+                scheduler.step()
+                global_step += 1
+                pending = 0
+        if pending:   # the remainder of the epoch: stepped with its own count
+            optimizer.step(accumulated=pending)
+            scheduler.step()
+            global_step += 1
+        mean = float(loss_sum) / max(batches, 1)   # (the epoch's only read-back)
+        history["train_loss"].append(mean)
+        line = f"epoch {epoch}: train_loss {mean:.6f}, {global_step} steps, lr {scheduler.get_last_lr()[0]:.3e}"
+        if (epoch + 1) % int(val_frequency) == 0:
+            metrics = validate(pl_module, datamodule)
+            history["val"].append((epoch, metrics))
+            line += "".join(f", {k} {v:.4f}" for k, v in metrics.items())
+        if checkpoint_path is not None:
+            save_checkpoint(checkpoint_path, pl_module, optimizer, scheduler, epoch, global_step)
+        log(line)
+    history["epoch"], history["global_step"] = max(first_epoch, int(max_epochs)) - 1, global_step
+    return history
+
+
+# ---- command line (launch_scripts/train.py:135-291) ------------------------------------------------------------------------------
+def get_parser() -> argparse.ArgumentParser:
+    from .loss import LOSS_TYPES
+
+    p = argparse.ArgumentParser(description="Fine-tune Beat This! on the MI355X kernels (frozen frontend, fp32, dropout 0).")
+    toggle = argparse.BooleanOptionalAction
+    p.add_argument("--data-dir", type=str, required=True, help="data folder: annotations/ and the spectrogram bundles")
+    p.add_argument("--checkpoint", type=str, default=None,
+                   help="checkpoint (name, path or URL) to start from; default: a new model with the reference's initialisation")
+    p.add_argument("--output", type=str, required=True, help="where the checkpoint is written at each epoch's end")
+    p.add_argument("--gpu", type=int, default=0, help="index of the GPU to use (default: %(default)s)")
+    p.add_argument("--n-layers", type=int, default=6, help="main transformer layers of a new model (default: %(default)s)")
+    p.add_argument("--transformer-dim", type=int, default=512, help="width of a new model (default: %(default)s)")
+    p.add_argument("--lr", type=float, default=0.0008)
+    p.add_argument("--weight-decay", type=float, default=0.01)
+    p.add_argument("--loss", type=str, default="shift_tolerant_weighted_bce", choices=list(LOSS_TYPES), help="the loss to use")
+    p.add_argument("--warmup-steps", type=int, default=1000, help="warm-up steps of the schedule")
+    p.add_argument("--max-epochs", type=int, default=100)
+    p.add_argument("--batch-size", type=int, default=8)
+    p.add_argument("--accumulate-grad-batches", type=int, default=8)
+    p.add_argument("--train-length", type=int, default=1500, help="excerpt length in frames")
+    p.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm to this (default: no clipping)")
+    p.add_argument("--dbn", default=False, action=toggle, help="DBN post-processing in validation")
+    p.add_argument("--eval-trim-beats", metavar="SECONDS", type=float, default=5,
+                   help="skip the first seconds of each piece in the metrics (default: %(default)s)")
+    p.add_argument("--val-frequency", metavar="N", type=int, default=5, help="validate every N epochs (default: %(default)s)")
+    p.add_argument("--tempo-augmentation", default=True, action=toggle, help="use the precomputed tempo variants")
+    p.add_argument("--pitch-augmentation", default=True, action=toggle, help="use the precomputed pitch variants")
+    p.add_argument("--mask-augmentation", default=True, action=toggle, help="mask stretches of the excerpts")
+    p.add_argument("--length-based-oversampling-factor", type=float, default=0.65,
+                   help="oversampling of long pieces; 0 takes one excerpt per piece (default: %(default)s)")
+    p.add_argument("--val", default=True, action=toggle,
+                   help="--no-val trains on the validation data as well (the validation metrics then mean nothing)")
+    p.add_argument("--hung-data", default=False, action=toggle, help="train on the datasets of Hung et al. only")
+    p.add_argument("--fold", type=int, default=None, help="the cross-validation fold NOT to train on (0-based)")
+    p.add_argument("--seed", type=int, default=0, help="seed of the random number generators")
+    p.add_argument("--resume-checkpoint", type=str, default=None, help="continue the run that wrote this checkpoint")
+    return p
+
+
+def main(argv=None) -> int:
+    args = get_parser().parse_args(argv)
+    from .dataset import BeatDataModule
+    from .inference import load_checkpoint
+    from .model.pl_module import PLBeatThis
+
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    if not torch.cuda.is_available():
+        print("beat_this_amd.train needs a ROCm GPU: this package has no CPU path", file=sys.stderr)
+        return 2
+    device = torch.device(f"cuda:{args.gpu}")
+    print("Starting a run with:", vars(args))
+    enabled = {name: dict(settings) for name, settings in AUGMENTATIONS.items() if getattr(args, f"{name}_augmentation")}
+    datamodule = BeatDataModule(args.data_dir, batch_size=args.batch_size, train_length=args.train_length, spect_fps=FPS,
+                                test_dataset="gtzan", length_based_oversampling_factor=args.length_based_oversampling_factor,
+                                augmentations=enabled, hung_data=args.hung_data, no_val=not args.val, fold=args.fold,
+                                device=device)
+    datamodule.setup("fit")   # (the class weights below need the training set; fit()'s own setup call then returns at once)
+    pos_weights = datamodule.get_train_positive_weights(widen_target_mask=POS_WEIGHT_WIDEN)
+    print("Using positive weights:", pos_weights)
+    start = args.resume_checkpoint or args.checkpoint
+    ckpt = load_checkpoint(start, "cpu") if start else None
+    arch = dict(transformer_dim=args.transformer_dim, n_layers=args.n_layers)
+    if ckpt is not None:   # the architecture is the checkpoint's
+        keys = ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "stem_dim", "head_dim", "sum_head", "partial_transformers", "dropout")
+        arch = {k: ckpt["hyper_parameters"][k] for k in keys if k in ckpt["hyper_parameters"]}
+    pl_module = PLBeatThis(**arch, fps=FPS, lr=args.lr, weight_decay=args.weight_decay, pos_weights=pos_weights, loss_type=args.loss,
+                           warmup_steps=args.warmup_steps, max_epochs=args.max_epochs, use_dbn=args.dbn,
+                           eval_trim_beats=args.eval_trim_beats)
+    if ckpt is not None and not args.resume_checkpoint:   # (a resumed run's weights are restored by fit() with the rest)
+        pl_module.load_state_dict(ckpt["state_dict"])
+    pl_module.to(device)
+    with torch.cuda.device(device):
+        fit(pl_module, datamodule, args.max_epochs, accumulate_grad_batches=args.accumulate_grad_batches,
+            val_frequency=args.val_frequency, max_grad_norm=args.max_grad_norm, checkpoint_path=args.output,
+            resume=ckpt if args.resume_checkpoint else None)
+    print("wrote", args.output)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -641,6 +641,60 @@ size_t bt_train_workspace_bytes(int unit, int backward, int B, int T, int dim, i
 int bt_train_forward(void* stream, int unit, const bt_train_args* a);
 int bt_train_backward(void* stream, int unit, const bt_train_args* a);
 
+/* ---- training: the optimiser step (csrc/optim.hip) ------------------------------------------------------
+ * Multi-tensor AdamW with torch.optim.AdamW's default semantics (decoupled decay, no amsgrad, no maximize), all fp32.  With
+ * gs = grad_scale (times *d_coef when d_coef is given, multiplied in fp32) every element does, one operation at a time and
+ * without multiply-add contraction:
+ *     g = grad * gs;   p = p * decay;   m = m + (g - m) * one_minus_beta1;   v = v * beta2 + (g * g) * one_minus_beta2;
+ *     p = p - step_size * (m / (sqrt(v) / bias2_sqrt + eps))
+ * where the caller computes, per group and in fp64 before rounding to fp32: decay = 1 - lr wd, step_size = lr / (1 - beta1^t),
+ * bias2_sqrt = sqrt(1 - beta2^t).  Divide and square root are correctly rounded, denormals are kept: the device and the host
+ * twin agree bit for bit.
+ * Layout: gradients, m and v live in three flat fp32 buffers of `total` elements (16-byte aligned); tensor i occupies
+ * [offset, offset + numel) of each, offset a multiple of 4, the padding between tensors is zero and never written.  The
+ * parameters stay in their own storage (`param`, 4-byte aligned; 16-byte aligned ones are moved 16 bytes at a time).  One
+ * workgroup of 256 threads updates one chunk of BT_OPTIM_CHUNK elements of one tensor: the chunk table lists (tensor, chunk
+ * within the tensor) for every chunk.  bt_optim_plan, on the host, lays the tensors out and fills both tables: `tensors` must
+ * hold n_tensors records; `chunks` may be NULL (sizing call) or hold chunk_capacity records; *total and *n_chunks are always
+ * written.  zero_grads != 0: the pass stores 0 over every gradient it has consumed.
+ * Global gradient norm: bt_grad_norm writes one fp64 sum of squares per slice of BT_OPTIM_NORM_SLICE elements of the flat
+ * gradient buffer into the workspace (launch 1; 256 threads, each its elements in ascending order, then a 256-leaf tree) and
+ * adds them in index order (launch 2, one workgroup); record[0] = norm = sqrt(sum) |grad_scale| and record[1] = coef =
+ * min(1, max_norm / (norm + 1e-6)) as fp32 (torch.nn.utils.clip_grad_norm_; a non-finite norm propagates as in torch).
+ * No call synchronises, allocates, clears memory or uses atomics; the order of every sum depends on the layout alone. */
+#define BT_OPTIM_CHUNK 4096
+#define BT_OPTIM_NORM_SLICE 4096
+#define BT_OPTIM_MAX_GROUPS 8
+typedef struct {
+  float* param; int64_t offset, numel; int32_t group, reserved;
+} bt_optim_tensor;
+typedef struct {
+  int32_t tensor, chunk;
+} bt_optim_chunk;
+typedef struct {
+  float decay, one_minus_beta1, beta2, one_minus_beta2, step_size, bias2_sqrt, eps, reserved;
+} bt_optim_group;
+typedef struct {
+  int32_t n_groups, zero_grads; float grad_scale; int32_t reserved;
+  bt_optim_group g[BT_OPTIM_MAX_GROUPS];
+} bt_optim_hyper;
+/* sizeof of the four structs, offsetof offset and group (tensor record) and g (hyper), then BT_OPTIM_CHUNK, BT_OPTIM_NORM_SLICE
+ * and BT_OPTIM_MAX_GROUPS: ten entries, the binding's self-check */
+void bt_optim_struct_sizes(int32_t* out);
+/* HOST */
+int bt_optim_plan(int n_tensors, const void* const* params, const int64_t* numel, const int32_t* groups, int n_groups,
+                  bt_optim_tensor* tensors, int64_t* total, bt_optim_chunk* chunks, int64_t chunk_capacity, int64_t* n_chunks);
+size_t bt_grad_norm_workspace_bytes(int64_t total);
+int bt_grad_norm(void* stream, const float* d_grad, int64_t total, float grad_scale, float max_norm, void* d_ws, size_t ws_bytes,
+                 float* d_record);
+int bt_adamw_step(void* stream, const bt_optim_tensor* d_tensors, int n_tensors, const bt_optim_chunk* d_chunks, int64_t n_chunks,
+                  float* d_grad, float* d_m, float* d_v, int64_t total, const bt_optim_hyper* hyper, const float* d_coef);
+/* HOST: the same arithmetic in the same order on host arrays (`param` of the tensor records: host pointers); the tables are
+ * validated entry by entry */
+int bt_grad_norm_host(const float* grad, int64_t total, float grad_scale, float max_norm, float* record);
+int bt_adamw_step_host(const bt_optim_tensor* tensors, int n_tensors, const bt_optim_chunk* chunks, int64_t n_chunks, float* grad,
+                       float* m, float* v, int64_t total, const bt_optim_hyper* hyper, const float* coef);
+
 #ifdef __cplusplus
 }
 #endif
