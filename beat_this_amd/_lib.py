@@ -19,7 +19,7 @@ if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # develop
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
            "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "optim.hip", "engine.hip"]
-HEADERS = ["common.h", "chain.h", "kernels.h", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
+HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
 ABI_VERSION = 600   # BT_ABI_VERSION of include/beat_this_amd.h this binding was written against
@@ -130,6 +130,10 @@ class TrainArgs(C.Structure):   # bt_train_args
                 ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
+class TrainDropout(C.Structure):   # bt_train_dropout
+    _fields_ = [("p", C.c_float), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("stream", C.c_uint64)]
+
+
 class OptimTensor(C.Structure):   # bt_optim_tensor
     _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int64), ("group", C.c_int32), ("reserved", C.c_int32)]
 
@@ -155,6 +159,7 @@ G3_FF1, G3_RESID, G3_QKV = 0, 1, 2
 UNIT_STEM, UNIT_PARTIAL, UNIT_CONV, UNIT_LINEAR, UNIT_ATTN, UNIT_FF, UNIT_NORM, UNIT_FRONT_ATTN, UNIT_FRONT_FF = range(9)
 TRAIN_UNIT_HEAD = 16                                        # BT_TRAIN_UNIT_HEAD
 TRAIN_DW_ROWS, TRAIN_CS_ROWS, TRAIN_ATTN_BLOCK = 1024, 64, 64   # BT_TRAIN_* tile edges (tests sit on both sides of them)
+DROP_ATTN_P, DROP_ATTN_OUT, DROP_FF_HIDDEN, DROP_FF_OUT = range(4)   # BT_DROP_*: the four sites of the training route's dropout
 OPTIM_CHUNK, OPTIM_NORM_SLICE = 4096, 4096                 # BT_OPTIM_CHUNK / _NORM_SLICE: elements per workgroup (likewise)
 
 EXPORTS = {
@@ -243,6 +248,12 @@ EXPORTS = {
     "bt_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bt_train_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs)]),
     "bt_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs)]),
+    "bt_train_dropout_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "bt_train_workspace_bytes_dropout": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bt_train_forward_dropout": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs), C.POINTER(TrainDropout)]),
+    "bt_train_backward_dropout": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs), C.POINTER(TrainDropout)]),
+    "bt_philox4x32_10_host": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "bt_dropout_mask_host": (C.c_int, [C.POINTER(TrainDropout), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bt_optim_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "bt_optim_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
                                 C.c_int64, C.POINTER(C.c_int64)]),

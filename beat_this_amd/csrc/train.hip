@@ -20,6 +20,10 @@
 //
 // Saved by the training forward: the attention's pre-gate output O [B T, D] and the per-(row, head) base-2 log-sum-exp;
 // everything else (RMSNorm, projections, RoPE, gates, GELU) is recomputed in the backward from the unit's input x.
+//
+// Dropout: the kernels that meet one of the four sites have a second instantiation (template
+// parameter DROP) that evaluates the masks of dropout.h for the elements it touches; the masks are stored nowhere, and the
+// instantiations without dropout are the code and the launches they were before.  The order of every sum is the same.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +33,7 @@
 #include <string>
 
 #include "../../include/beat_this_amd.h"
+#include "dropout.h"
 
 int bt_set_error_external(int code, const char* msg);   // engine.hip (bt_last_error)
 
@@ -65,8 +70,28 @@ __device__ inline float gelu_grad_f(float v) {
   return 0.5f * (1.0f + erff(v * 0.70710678118654752f)) + v * 0.3989422804014327f * expf(-0.5f * v * v);
 }
 
-template <bool AT, bool BT>
-__global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
+// a[jj] of lane l of a quad of lanes (4 q .. 4 q + 3) becomes a[l mod 4] of lane 4 q + jj: a 4 x 4 transpose over three
+// exchanges.  Every lane of the quad has to be active.
+__device__ inline void quad_transpose(uint32_t (&a)[4], int lane) {
+  const int ql = lane & 3, qb = lane & ~3;
+  uint32_t b[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int give = (ql - s) & 3, from = (ql + s) & 3;
+    uint32_t v = give == 0 ? a[0] : give == 1 ? a[1] : give == 2 ? a[2] : a[3];
+    if (s) v = (uint32_t)__shfl((int)v, qb + from, 64);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[k] = from == k ? v : b[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) a[k] = b[k];
+}
+
+// DROP: the site `ds` over the [M][N] result (N a multiple of 4): drop_act == 0 masks the value before the residual is added
+// (C = resid + m c (acc + bias)), drop_act != 0 masks the second output (act = m c gelu(value)) and leaves C alone.  A lane
+// evaluates the groups of four of its sixteen rows and the quad exchanges the words, so every word of a call is used.
+template <bool AT, bool BT, bool DROP>
+__device__ inline void gemm_body(const GemmP& p, const DropSite& ds, int drop_act) {
   __shared__ float As[GK][GT + 4];
   __shared__ float Bs[GK][GT + 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -105,16 +130,42 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
   if (col >= p.N) return;
   float* C = p.C ? p.C + (long)blockIdx.z * p.cz : nullptr;
   const float b = p.bias ? p.bias[col] : 0.0f;
+  uint32_t words[16];
+  if constexpr (DROP) {   // (N is a multiple of 4: the four lanes of a quad are all here or all gone)
+#pragma unroll
+    for (int ri = 0; ri < 4; ++ri) {
+      const long row = m0 + wm * 32 + (lane & 3) + 8 * ri + 4 * g;
+      const PhiloxWords w = drop_words(ds, drop_row_group((uint64_t)row, (uint32_t)p.N, (uint32_t)col));
+      uint32_t q[4] = {w.w[0], w.w[1], w.w[2], w.w[3]};
+      quad_transpose(q, lane);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) words[4 * ri + jj] = q[jj];
+    }
+  }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const long row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;   // C/D map of the 32x32 MFMAs
     if (row >= p.M) continue;
     float v = acc[r] + b;
+    float keep = 1.0f;
+    if constexpr (DROP) {
+      keep = words[r] >= ds.thr ? ds.scale : 0.0f;
+      if (!drop_act) v *= keep;
+    }
     if (p.resid) v += p.resid[row * p.ldr + col];
     if (p.accum) v += C[row * p.ldc + col];
     if (C) C[row * p.ldc + col] = v;
-    if (p.act) p.act[row * p.ldact + col] = gelu_f(v);
+    if (p.act) p.act[row * p.ldact + col] = DROP && drop_act ? gelu_f(v) * keep : gelu_f(v);
   }
+}
+
+template <bool AT, bool BT>
+__global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
+  gemm_body<AT, BT, false>(p, DropSite{}, 0);
+}
+
+__global__ __launch_bounds__(256) void gemm_drop_kernel(const GemmP p, const DropSite ds, const int drop_act) {
+  gemm_body<false, false, true>(p, ds, drop_act);
 }
 
 template <bool AT, bool BT> void launch_gemm(GemmP p, int chunks, hipStream_t s) {
@@ -122,13 +173,18 @@ template <bool AT, bool BT> void launch_gemm(GemmP p, int chunks, hipStream_t s)
   hipLaunchKernelGGL((gemm_kernel<AT, BT>), grid, dim3(256), 0, s, p);
 }
 
-// Y[M, N] = A[M, K] W[N, K]^T (+ bias, + resid; act = gelu(Y))
+// Y[M, N] = A[M, K] W[N, K]^T (+ bias, + resid; act = gelu(Y)); ds: the dropout site over Y (drop_act == 0) or over act
 void linear_fwd(const float* A, const float* W, const float* bias, long M, int N, int K, float* Y, const float* resid, float* act,
-                hipStream_t s) {
+                hipStream_t s, const DropSite* ds = nullptr, int drop_act = 0) {
   GemmP p{};
   p.A = A; p.lda = K; p.B = W; p.ldb = K; p.M = (int)M; p.N = N; p.K = K; p.kchunk = K;
   p.C = Y; p.ldc = N; p.bias = bias; p.resid = resid; p.ldr = N; p.act = act; p.ldact = N;
-  launch_gemm<false, false>(p, 1, s);
+  if (!ds) {
+    launch_gemm<false, false>(p, 1, s);
+    return;
+  }
+  dim3 grid((unsigned)((p.N + GT - 1) / GT), (unsigned)((p.M + GT - 1) / GT), 1);
+  hipLaunchKernelGGL(gemm_drop_kernel, grid, dim3(256), 0, s, p, *ds, drop_act);
 }
 
 // dA[M, K] (+)= dY[M, N] W[N, K]
@@ -284,8 +340,11 @@ __device__ inline float dot32(const float* a, const float* b) {
   return s;
 }
 
-// O = softmax(q k^T / sqrt(32)) v (before the gate) and lse = base-2 log-sum-exp of the scaled scores
-__global__ __launch_bounds__(AB) void attn_fwd_kernel(const float* qkv, int T, int D, float* O, float* lse) {
+// O = softmax(q k^T / sqrt(32)) v (before the gate) and lse = base-2 log-sum-exp of the scaled scores.
+// DROP: the normaliser and the maximum see every key, the accumulator only the kept (query, key) pairs; O is the dropped
+// output, scaled by 1 / (1 - p).  A thread walks its query's keys four at a time: one call per group.
+template <bool DROP>
+__device__ inline void attn_fwd_body(const float* qkv, int T, int D, float* O, float* lse, const DropSite& ds) {
   __shared__ __attribute__((aligned(16))) float Ks[AB][32];
   __shared__ __attribute__((aligned(16))) float Vs[AB][32];
   const int lane = threadIdx.x, h = blockIdx.y, b = blockIdx.z, H = D / 32;
@@ -304,30 +363,63 @@ __global__ __launch_bounds__(AB) void attn_fwd_kernel(const float* qkv, int T, i
     stage_tile(base + 2 * D, ld, k0, T, Vs, lane);
     __syncthreads();
     const int nk = min(AB, T - k0);
-    for (int j = 0; j < nk; ++j) {
-      const float s = dot32(q, Ks[j]) * QK_SCALE_LOG2E;
-      if (s > mx) {
-        const float corr = exp2f(mx - s);
-        l *= corr;
+    if constexpr (!DROP) {
+      for (int j = 0; j < nk; ++j) {
+        const float s = dot32(q, Ks[j]) * QK_SCALE_LOG2E;
+        if (s > mx) {
+          const float corr = exp2f(mx - s);
+          l *= corr;
 #pragma unroll
-        for (int d = 0; d < 32; ++d) acc[d] *= corr;
-        mx = s;
+          for (int d = 0; d < 32; ++d) acc[d] *= corr;
+          mx = s;
+        }
+        const float p = exp2f(s - mx);
+        l += p;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) acc[d] = fmaf(p, Vs[j][d], acc[d]);
       }
-      const float p = exp2f(s - mx);
-      l += p;
+    } else {
+      for (int j0 = 0; j0 < nk; j0 += 4) {
+        const PhiloxWords w = drop_words(ds, drop_attn_group((uint64_t)b * H + h, (uint32_t)T, (uint32_t)t, (uint32_t)(k0 + j0)));
 #pragma unroll
-      for (int d = 0; d < 32; ++d) acc[d] = fmaf(p, Vs[j][d], acc[d]);
+        for (int jj = 0; jj < 4; ++jj) {
+          const int j = j0 + jj;
+          if (j < nk) {
+            const float s = dot32(q, Ks[j]) * QK_SCALE_LOG2E;
+            if (s > mx) {
+              const float corr = exp2f(mx - s);
+              l *= corr;
+#pragma unroll
+              for (int d = 0; d < 32; ++d) acc[d] *= corr;
+              mx = s;
+            }
+            const float p = exp2f(s - mx);
+            l += p;
+            const float pk = w.w[jj] >= ds.thr ? p : 0.0f;
+#pragma unroll
+            for (int d = 0; d < 32; ++d) acc[d] = fmaf(pk, Vs[j][d], acc[d]);
+          }
+        }
+      }
     }
   }
   if (!ok) return;
   const long m = (long)b * T + t;
-  store_row32(O + m * D + h * 32, acc, 1.0f / l);
+  store_row32(O + m * D + h * 32, acc, DROP ? ds.scale / l : 1.0f / l);
   lse[m * H + h] = mx + log2f(l);
 }
 
-// dq of a query: keys in ascending order
-__global__ __launch_bounds__(AB) void attn_dq_kernel(const float* qkv, const float* dO, const float* lse, const float* delta, int T,
-                                                     int D, float* dqkv) {
+__global__ __launch_bounds__(AB) void attn_fwd_kernel(const float* qkv, int T, int D, float* O, float* lse) {
+  attn_fwd_body<false>(qkv, T, D, O, lse, DropSite{});
+}
+__global__ __launch_bounds__(AB) void attn_fwd_drop_kernel(const float* qkv, int T, int D, float* O, float* lse, const DropSite ds) {
+  attn_fwd_body<true>(qkv, T, D, O, lse, ds);
+}
+
+// dq of a query: keys in ascending order.  DROP: dP = m c (dO . v), dS = P (dP - delta)
+template <bool DROP>
+__device__ inline void attn_dq_body(const float* qkv, const float* dO, const float* lse, const float* delta, int T, int D, float* dqkv,
+                                    const DropSite& ds) {
   __shared__ __attribute__((aligned(16))) float Ks[AB][32];
   __shared__ __attribute__((aligned(16))) float Vs[AB][32];
   const int lane = threadIdx.x, h = blockIdx.y, b = blockIdx.z, H = D / 32;
@@ -347,19 +439,47 @@ __global__ __launch_bounds__(AB) void attn_dq_kernel(const float* qkv, const flo
     stage_tile(base + 2 * D, ld, k0, T, Vs, lane);
     __syncthreads();
     const int nk = min(AB, T - k0);
-    for (int j = 0; j < nk; ++j) {
-      const float p = exp2f(dot32(q, Ks[j]) * QK_SCALE_LOG2E - ls);
-      const float ds = p * (dot32(go, Vs[j]) - dl);
+    if constexpr (!DROP) {
+      for (int j = 0; j < nk; ++j) {
+        const float p = exp2f(dot32(q, Ks[j]) * QK_SCALE_LOG2E - ls);
+        const float ds_ = p * (dot32(go, Vs[j]) - dl);
 #pragma unroll
-      for (int d = 0; d < 32; ++d) acc[d] = fmaf(ds, Ks[j][d], acc[d]);
+        for (int d = 0; d < 32; ++d) acc[d] = fmaf(ds_, Ks[j][d], acc[d]);
+      }
+    } else {
+      for (int j0 = 0; j0 < nk; j0 += 4) {
+        const PhiloxWords w = drop_words(ds, drop_attn_group((uint64_t)b * H + h, (uint32_t)T, (uint32_t)t, (uint32_t)(k0 + j0)));
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int j = j0 + jj;
+          if (j < nk) {
+            const float p = exp2f(dot32(q, Ks[j]) * QK_SCALE_LOG2E - ls);
+            const float dp = w.w[jj] >= ds.thr ? dot32(go, Vs[j]) * ds.scale : 0.0f;
+            const float ds_ = p * (dp - dl);
+#pragma unroll
+            for (int d = 0; d < 32; ++d) acc[d] = fmaf(ds_, Ks[j][d], acc[d]);
+          }
+        }
+      }
     }
   }
   if (ok) store_row32(dqkv + ((long)b * T + t) * ld + h * 32, acc, QK_SCALE);
 }
 
-// dk and dv of a key: queries in ascending order
-__global__ __launch_bounds__(AB) void attn_dkv_kernel(const float* qkv, const float* dO, const float* lse, const float* delta, int T,
-                                                      int D, float* dqkv) {
+__global__ __launch_bounds__(AB) void attn_dq_kernel(const float* qkv, const float* dO, const float* lse, const float* delta, int T,
+                                                     int D, float* dqkv) {
+  attn_dq_body<false>(qkv, dO, lse, delta, T, D, dqkv, DropSite{});
+}
+__global__ __launch_bounds__(AB) void attn_dq_drop_kernel(const float* qkv, const float* dO, const float* lse, const float* delta,
+                                                          int T, int D, float* dqkv, const DropSite ds) {
+  attn_dq_body<true>(qkv, dO, lse, delta, T, D, dqkv, ds);
+}
+
+// dk and dv of a key: queries in ascending order.  DROP: dV += (m c P)^T dO, and dS as in the dq sweep.  The four keys of a
+// quad of lanes are one group of every query: the lanes evaluate four queries' groups, one each, and exchange the words.
+template <bool DROP>
+__device__ inline void attn_dkv_body(const float* qkv, const float* dO, const float* lse, const float* delta, int T, int D,
+                                     float* dqkv, const DropSite& ds) {
   __shared__ __attribute__((aligned(16))) float Qs[AB][32];
   __shared__ __attribute__((aligned(16))) float Gs[AB][32];
   __shared__ float Ls[AB], Ds[AB];
@@ -386,13 +506,38 @@ __global__ __launch_bounds__(AB) void attn_dkv_kernel(const float* qkv, const fl
     }
     __syncthreads();
     const int nq = min(AB, T - q0);
-    for (int i = 0; i < nq; ++i) {
-      const float p = exp2f(dot32(Qs[i], k) * QK_SCALE_LOG2E - Ls[i]);
-      const float ds = p * (dot32(Gs[i], v) - Ds[i]);
+    if constexpr (!DROP) {
+      for (int i = 0; i < nq; ++i) {
+        const float p = exp2f(dot32(Qs[i], k) * QK_SCALE_LOG2E - Ls[i]);
+        const float ds_ = p * (dot32(Gs[i], v) - Ds[i]);
 #pragma unroll
-      for (int d = 0; d < 32; ++d) {
-        dv[d] = fmaf(p, Gs[i][d], dv[d]);
-        dk[d] = fmaf(ds, Qs[i][d], dk[d]);
+        for (int d = 0; d < 32; ++d) {
+          dv[d] = fmaf(p, Gs[i][d], dv[d]);
+          dk[d] = fmaf(ds_, Qs[i][d], dk[d]);
+        }
+      }
+    } else {
+      for (int i0 = 0; i0 < nq; i0 += 4) {   // (every lane of the wave takes part, also the ones behind key T - 1)
+        const PhiloxWords w =
+            drop_words(ds, drop_attn_group((uint64_t)b * H + h, (uint32_t)T, (uint32_t)(q0 + i0 + (lane & 3)), (uint32_t)t));
+        uint32_t mine[4] = {w.w[0], w.w[1], w.w[2], w.w[3]};
+        quad_transpose(mine, lane);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int i = i0 + jj;
+          if (i < nq) {
+            const bool kept = mine[jj] >= ds.thr;
+            const float p = exp2f(dot32(Qs[i], k) * QK_SCALE_LOG2E - Ls[i]);
+            const float pm = kept ? p * ds.scale : 0.0f;
+            const float dp = kept ? dot32(Gs[i], v) * ds.scale : 0.0f;
+            const float ds_ = p * (dp - Ds[i]);
+#pragma unroll
+            for (int d = 0; d < 32; ++d) {
+              dv[d] = fmaf(pm, Gs[i][d], dv[d]);
+              dk[d] = fmaf(ds_, Qs[i][d], dk[d]);
+            }
+          }
+        }
       }
     }
   }
@@ -400,6 +545,15 @@ __global__ __launch_bounds__(AB) void attn_dkv_kernel(const float* qkv, const fl
   float* out = dqkv + ((long)b * T + t) * ld + h * 32;
   store_row32(out + D, dk, QK_SCALE);
   store_row32(out + 2 * D, dv, 1.0f);
+}
+
+__global__ __launch_bounds__(AB) void attn_dkv_kernel(const float* qkv, const float* dO, const float* lse, const float* delta, int T,
+                                                      int D, float* dqkv) {
+  attn_dkv_body<false>(qkv, dO, lse, delta, T, D, dqkv, DropSite{});
+}
+__global__ __launch_bounds__(AB) void attn_dkv_drop_kernel(const float* qkv, const float* dO, const float* lse, const float* delta,
+                                                           int T, int D, float* dqkv, const DropSite ds) {
+  attn_dkv_body<true>(qkv, dO, lse, delta, T, D, dqkv, ds);
 }
 
 __device__ inline float sigmoid_f(float v) { return 1.0f / (1.0f + expf(-v)); }
@@ -436,6 +590,30 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* O, const flo
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(float* h, const float* da, long n) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) h[i] = da[i] * gelu_grad_f(h[i]);
+}
+
+// the same behind a dropped GELU: dh = da m c gelu'(h); a thread takes one group of four (n4 = n / 4 groups of a row site)
+__global__ __launch_bounds__(256) void gelu_bwd_drop_kernel(float* h, const float* da, long n4, const DropSite ds) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const PhiloxWords w = drop_words(ds, (uint64_t)i);
+  const f32x4 a = reinterpret_cast<const f32x4*>(da)[i], x = reinterpret_cast<const f32x4*>(h)[i];
+  f32x4 r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r[j] = a[j] * (w.w[j] >= ds.thr ? ds.scale : 0.0f) * gelu_grad_f(x[j]);
+  reinterpret_cast<f32x4*>(h)[i] = r;
+}
+
+// out = in m c over a row site (n4 = elements / 4): the masked upstream gradient behind to_out / the second FF linear
+__global__ __launch_bounds__(256) void mask_kernel(const float* in, long n4, const DropSite ds, float* out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const PhiloxWords w = drop_words(ds, (uint64_t)i);
+  const f32x4 a = reinterpret_cast<const f32x4*>(in)[i];
+  f32x4 r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r[j] = a[j] * (w.w[j] >= ds.thr ? ds.scale : 0.0f);
+  reinterpret_cast<f32x4*>(out)[i] = r;
 }
 
 // ---- head ------------------------------------------------------------------------------------------------------------------
@@ -478,10 +656,12 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* g_beat, cons
 size_t up64(size_t n) { return (n + 63) / 64 * 64; }
 
 struct Layout {
-  size_t xn, rinv, a, b, c, d, e, small0, small1, small2, part, total;   // offsets in floats
+  size_t xn, rinv, a, b, c, d, e, small0, small1, small2, part, gm, total;   // offsets in floats
 };
 
-Layout layout(int unit, int backward, long M, int D, int HID) {
+// drop: the backward of the attention and the feed-forward with dropout keeps the masked upstream gradient in one more
+// region, behind the others (whose offsets are the same with and without)
+Layout layout(int unit, int backward, long M, int D, int HID, bool drop = false) {
   Layout L{};
   size_t at = 0;
   auto take = [&](size_t n) { const size_t o = at; at += up64(n); return o; };
@@ -524,6 +704,7 @@ Layout layout(int unit, int backward, long M, int D, int HID) {
       }
       break;
   }
+  if (drop && backward && (unit == BT_UNIT_FF || unit == BT_UNIT_ATTN)) L.gm = take(MD);
   L.total = std::max<size_t>(at, 64);
   return L;
 }
@@ -579,14 +760,75 @@ size_t bt_train_workspace_bytes(int unit, int backward, int B, int T, int dim, i
   return layout(unit, backward != 0, (long)B * T, dim, hidden).total * sizeof(float);
 }
 
-int bt_train_forward(void* stream, int unit, const bt_train_args* ap) {
-  const char* fn = "bt_train_forward";
+// NULL or p == 0: no dropout; otherwise 0 < p < 1 on the attention or the feed-forward
+static const char* check_dropout(int unit, const bt_train_dropout* dp, bool* active) {
+  *active = false;
+  if (!dp) return nullptr;
+  if (!(dp->p >= 0.0f && dp->p < 1.0f)) return "dropout p must satisfy 0 <= p < 1";
+  if (dp->p == 0.0f) return nullptr;
+  if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return "dropout applies to BT_UNIT_ATTN and BT_UNIT_FF only";
+  *active = true;
+  return nullptr;
+}
+
+void bt_train_dropout_struct_sizes(int32_t* out) {
+  out[0] = (int32_t)sizeof(bt_train_dropout);
+  out[1] = (int32_t)offsetof(bt_train_dropout, p);
+  out[2] = (int32_t)offsetof(bt_train_dropout, seed);
+  out[3] = (int32_t)offsetof(bt_train_dropout, stream);
+}
+
+size_t bt_train_workspace_bytes_dropout(int unit, int backward, int B, int T, int dim, int hidden) {
+  if (check_shape(unit, B, T, dim, hidden, 1 << 30)) return 0;
+  return layout(unit, backward != 0, (long)B * T, dim, hidden, true).total * sizeof(float);
+}
+
+void bt_philox4x32_10_host(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
+  const PhiloxWords w = philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1]);
+  for (int i = 0; i < 4; ++i) out[i] = w.w[i];
+}
+
+int bt_dropout_mask_host(const bt_train_dropout* dp, int site, int B, int T, int dim, int hidden, uint8_t* out) {
+  const char* fn = "bt_dropout_mask_host";
+  if (!dp || !out) return fail(fn, "null argument");
+  if (!(dp->p >= 0.0f && dp->p < 1.0f)) return fail(fn, "dropout p must satisfy 0 <= p < 1");
+  if (site < BT_DROP_ATTN_P || site > BT_DROP_FF_OUT) return fail(fn, "site must be one of BT_DROP_*");
+  if (B < 1 || T < 1 || dim < 32 || dim % 32 || (site == BT_DROP_FF_HIDDEN && (hidden < 4 || hidden % 4)))
+    return fail(fn, "need B, T >= 1, dim a multiple of 32 and hidden a multiple of 4");
+  const DropSite ds = drop_site(dp->p, dp->seed, dp->stream, site);
+  if (site == BT_DROP_ATTN_P) {
+    const int H = dim / 32;
+    for (long bh = 0; bh < (long)B * H; ++bh)
+      for (int q = 0; q < T; ++q)
+        for (int k0 = 0; k0 < T; k0 += 4) {
+          const PhiloxWords w = drop_words(ds, drop_attn_group((uint64_t)bh, (uint32_t)T, (uint32_t)q, (uint32_t)k0));
+          for (int k = k0; k < std::min(T, k0 + 4); ++k) out[(bh * T + q) * T + k] = w.w[k - k0] >= ds.thr;
+        }
+    return BT_OK;
+  }
+  const int N = site == BT_DROP_FF_HIDDEN ? hidden : dim;
+  for (long row = 0; row < (long)B * T; ++row)
+    for (int c0 = 0; c0 < N; c0 += 4) {
+      const PhiloxWords w = drop_words(ds, drop_row_group((uint64_t)row, (uint32_t)N, (uint32_t)c0));
+      for (int j = 0; j < 4; ++j) out[row * N + c0 + j] = w.w[j] >= ds.thr;
+    }
+  return BT_OK;
+}
+
+int bt_train_forward(void* stream, int unit, const bt_train_args* ap) { return bt_train_forward_dropout(stream, unit, ap, nullptr); }
+
+int bt_train_backward(void* stream, int unit, const bt_train_args* ap) { return bt_train_backward_dropout(stream, unit, ap, nullptr); }
+
+int bt_train_forward_dropout(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
+  const char* fn = dp ? "bt_train_forward_dropout" : "bt_train_forward";
   if (!ap) return fail(fn, "null argument");
   const bt_train_args& a = *ap;
   if (const char* e = check_shape(unit, a.B, a.T, a.dim, a.hidden, a.rope_len)) return fail(fn, e);
+  bool drop = false;
+  if (const char* e = check_dropout(unit, dp, &drop)) return fail(fn, e);
   const long M = (long)a.B * a.T;
   const int D = a.dim, HID = a.hidden;
-  const Layout L = layout(unit, 0, M, D, HID);
+  const Layout L = layout(unit, 0, M, D, HID, drop);
   if (!a.x || !a.y || !a.ws) return fail(fn, "null x, y or workspace");
   if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
   hipStream_t s = (hipStream_t)stream;
@@ -600,42 +842,70 @@ int bt_train_forward(void* stream, int unit, const bt_train_args* ap) {
       if (!a.w1 || !a.b1 || !a.y2) return fail(fn, "null parameter or output");
       hipLaunchKernelGGL(head_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.w1, a.b1, M, D, a.sum_head, a.y, a.y2);
       break;
-    case BT_UNIT_FF:
+    case BT_UNIT_FF: {
       if (!a.gamma || !a.w1 || !a.b1 || !a.w2 || !a.b2) return fail(fn, "null parameter");
       hipLaunchKernelGGL(rms_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, M, D, ws + L.xn, ws + L.rinv);
-      linear_fwd(ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, s);
-      linear_fwd(ws + L.a, a.w2, a.b2, M, D, HID, a.y, a.residual ? a.x : nullptr, nullptr, s);
+      if (!drop) {
+        linear_fwd(ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, s);
+        linear_fwd(ws + L.a, a.w2, a.b2, M, D, HID, a.y, a.residual ? a.x : nullptr, nullptr, s);
+      } else {
+        const DropSite hid = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_FF_HIDDEN);
+        const DropSite out = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_FF_OUT);
+        linear_fwd(ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, s, &hid, 1);
+        linear_fwd(ws + L.a, a.w2, a.b2, M, D, HID, a.y, a.residual ? a.x : nullptr, nullptr, s, &out, 0);
+      }
       break;
+    }
     default: {   // attention
       if (!a.gamma || !a.w1 || !a.w2 || !a.b2 || !a.w3 || !a.rope || !a.save_o || !a.save_lse)
         return fail(fn, "null parameter, rotary table or saved-tensor pointer");
       attn_prologue(a, L, ws, M, s);
-      hipLaunchKernelGGL(attn_fwd_kernel, dim3(blocks_of(a.T, AB), D / 32, a.B), dim3(AB), 0, s, (const float*)(ws + L.a), a.T, D,
-                         a.save_o, a.save_lse);
+      if (!drop) {
+        hipLaunchKernelGGL(attn_fwd_kernel, dim3(blocks_of(a.T, AB), D / 32, a.B), dim3(AB), 0, s, (const float*)(ws + L.a), a.T, D,
+                           a.save_o, a.save_lse);
+      } else {
+        hipLaunchKernelGGL(attn_fwd_drop_kernel, dim3(blocks_of(a.T, AB), D / 32, a.B), dim3(AB), 0, s, (const float*)(ws + L.a), a.T,
+                           D, a.save_o, a.save_lse, drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P));
+      }
       hipLaunchKernelGGL(gate_fwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o,
                          (const float*)(ws + L.small0), M, D, ws + L.b);
-      linear_fwd(ws + L.b, a.w3, nullptr, M, D, D, a.y, a.residual ? a.x : nullptr, nullptr, s);
+      if (!drop) {
+        linear_fwd(ws + L.b, a.w3, nullptr, M, D, D, a.y, a.residual ? a.x : nullptr, nullptr, s);
+      } else {
+        const DropSite out = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_OUT);
+        linear_fwd(ws + L.b, a.w3, nullptr, M, D, D, a.y, a.residual ? a.x : nullptr, nullptr, s, &out, 0);
+      }
       break;
     }
   }
   return finish(fn);
 }
 
-int bt_train_backward(void* stream, int unit, const bt_train_args* ap) {
-  const char* fn = "bt_train_backward";
+int bt_train_backward_dropout(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
+  const char* fn = dp ? "bt_train_backward_dropout" : "bt_train_backward";
   if (!ap) return fail(fn, "null argument");
   const bt_train_args& a = *ap;
   if (const char* e = check_shape(unit, a.B, a.T, a.dim, a.hidden, a.rope_len)) return fail(fn, e);
+  bool drop = false;
+  if (const char* e = check_dropout(unit, dp, &drop)) return fail(fn, e);
   const long M = (long)a.B * a.T;
   const int D = a.dim, HID = a.hidden, H = D / 32;
-  const Layout L = layout(unit, 1, M, D, HID);
+  const Layout L = layout(unit, 1, M, D, HID, drop);
   if (!a.x || !a.ws) return fail(fn, "null x or workspace");
   if (unit != BT_TRAIN_UNIT_HEAD && !a.gy) return fail(fn, "null upstream gradient");
+  if (drop && (uintptr_t)a.gy % 16) return fail(fn, "with dropout the upstream gradient must be 16-byte aligned");
   if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)a.ws;
   float* part = ws + L.part;
   const float* resid = a.residual ? a.gy : nullptr;
+  // gy as the last linear layer of the unit sees it: behind the output site's mask with dropout (the residual takes a.gy)
+  const float* gy = drop ? ws + L.gm : a.gy;
+  auto mask_gy = [&](int site) {
+    if (drop)
+      hipLaunchKernelGGL(mask_kernel, dim3(blocks_of(M * D / 4, 256)), dim3(256), 0, s, a.gy, M * D / 4,
+                         drop_site(dp->p, dp->seed, dp->stream, site), ws + L.gm);
+  };
   switch (unit) {
     case BT_UNIT_NORM:
       if (!a.gamma) return fail(fn, "null parameter");
@@ -657,12 +927,18 @@ int bt_train_backward(void* stream, int unit, const bt_train_args* ap) {
       float* xn = ws + L.xn;
       float* h = ws + L.a;
       float* act = ws + L.b;
+      mask_gy(BT_DROP_FF_OUT);
       hipLaunchKernelGGL(rms_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, M, D, xn, ws + L.rinv);
-      linear_fwd(xn, a.w1, a.b1, M, HID, D, h, nullptr, act, s);
-      if (a.g_w2) linear_bwd_weight(a.gy, act, M, D, HID, part, a.g_w2, s);
-      if (a.g_b2) colsum(a.gy, D, nullptr, 0, nullptr, 0, M, D, part, a.g_b2, s);
-      linear_bwd_input(a.gy, a.w2, M, D, HID, act, false, s);                       // da over gelu(h)
-      hipLaunchKernelGGL(gelu_bwd_kernel, dim3(blocks_of(M * HID, 256)), dim3(256), 0, s, h, (const float*)act, M * HID);   // dh over h
+      const DropSite hid = drop ? drop_site(dp->p, dp->seed, dp->stream, BT_DROP_FF_HIDDEN) : DropSite{};
+      linear_fwd(xn, a.w1, a.b1, M, HID, D, h, nullptr, act, s, drop ? &hid : nullptr, 1);
+      if (a.g_w2) linear_bwd_weight(gy, act, M, D, HID, part, a.g_w2, s);
+      if (a.g_b2) colsum(gy, D, nullptr, 0, nullptr, 0, M, D, part, a.g_b2, s);
+      linear_bwd_input(gy, a.w2, M, D, HID, act, false, s);                         // da over gelu(h)
+      if (!drop)
+        hipLaunchKernelGGL(gelu_bwd_kernel, dim3(blocks_of(M * HID, 256)), dim3(256), 0, s, h, (const float*)act, M * HID);   // dh over h
+      else
+        hipLaunchKernelGGL(gelu_bwd_drop_kernel, dim3(blocks_of(M * HID / 4, 256)), dim3(256), 0, s, h, (const float*)act, M * HID / 4,
+                           hid);
       if (a.g_w1) linear_bwd_weight(h, xn, M, HID, D, part, a.g_w1, s);
       if (a.g_b1) colsum(h, HID, nullptr, 0, nullptr, 0, M, HID, part, a.g_b1, s);
       if (a.gx || a.g_gamma) {
@@ -684,20 +960,29 @@ int bt_train_backward(void* stream, int unit, const bt_train_args* ap) {
       float* dqkv = ws + L.d;
       float* delta = ws + L.small1;
       float* dgl = ws + L.small2;
+      mask_gy(BT_DROP_ATTN_OUT);
       attn_prologue(a, L, ws, M, s);
       if (a.g_w3) {
         hipLaunchKernelGGL(gate_fwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o, (const float*)gl, M, D,
                            og);
-        linear_bwd_weight(a.gy, og, M, D, D, part, a.g_w3, s);
+        linear_bwd_weight(gy, og, M, D, D, part, a.g_w3, s);
       }
-      linear_bwd_input(a.gy, a.w3, M, D, D, dO, false, s);                          // d og
+      linear_bwd_input(gy, a.w3, M, D, D, dO, false, s);                            // d og
       hipLaunchKernelGGL(gate_bwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o, (const float*)gl, dO, M,
                          D, delta, dgl);                                             // -> dO, delta, d gate logits
       const dim3 grid(blocks_of(a.T, AB), H, a.B);
-      hipLaunchKernelGGL(attn_dkv_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
-                         (const float*)delta, a.T, D, dqkv);
-      hipLaunchKernelGGL(attn_dq_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
-                         (const float*)delta, a.T, D, dqkv);
+      if (!drop) {
+        hipLaunchKernelGGL(attn_dkv_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
+                           (const float*)delta, a.T, D, dqkv);
+        hipLaunchKernelGGL(attn_dq_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
+                           (const float*)delta, a.T, D, dqkv);
+      } else {   // (delta = sum_d dO O holds with the dropped O: sum_k P dP = sum_k (m c P)(dO . v) = dO . O)
+        const DropSite pd = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P);
+        hipLaunchKernelGGL(attn_dkv_drop_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
+                           (const float*)delta, a.T, D, dqkv, pd);
+        hipLaunchKernelGGL(attn_dq_drop_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
+                           (const float*)delta, a.T, D, dqkv, pd);
+      }
       hipLaunchKernelGGL(rope_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, dqkv, a.rope, M, a.T, D, 1);
       if (a.g_w1) linear_bwd_weight(dqkv, xn, M, 3 * D, D, part, a.g_w1, s);
       if (a.g_w2) linear_bwd_weight(dgl, xn, M, H, D, part, a.g_w2, s);

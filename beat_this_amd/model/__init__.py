@@ -185,7 +185,14 @@ class BeatThis(_TracksChildren, nn.Module):
     RMSNorm and the heads go through ``torch.autograd.Function``s over the library's training kernels, composed like the
     reference's containers.  Fixed semantics of that route:
       * its arithmetic is fp32, whatever ``fp32_split_gemms`` says and also under ``torch.autocast``;
-      * dropout is taken as 0, in ``train()`` and ``eval()`` alike (the constructor still accepts ``dropout``);
+      * dropout is off unless ``enable_dropout(seed)`` was called: then, in ``train()`` mode and with ``dropout["transformer"]``
+        above 0, the main layers drop where the reference's do (the attention probabilities, after ``to_out``, after the GELU,
+        after the feed-forward's second linear) -- the reference's rule plus the opt-in; in ``eval()`` nothing is dropped.  The
+        masks are this package's own (Philox4x32-10 under ``seed``, include/beat_this_amd.h), not torch's generator: every
+        attention / feed-forward call that drops takes the next stream number from a counter (``dropout_state()``), which
+        ``set_dropout_state()`` rewinds to repeat a run bit for bit.  A graph capture with dropout active raises
+        ``RuntimeError`` (a replay would repeat its masks).  ``dropout["frontend"]`` is unused: the frozen frontend always
+        runs the inference path;
       * ``rotary_embed.freqs`` never receives a gradient, as in the reference;
       * the frontend is frozen in this version: a frontend parameter that requires grad makes a grad-mode forward raise
         ``NotImplementedError`` rather than silently leaving its ``.grad`` empty;
@@ -209,6 +216,8 @@ class BeatThis(_TracksChildren, nn.Module):
         for key in state_dict_shapes(self.hparams):
             _attach(self, key, init[key])
         self._bind_units()
+        self.dropout = dict(dropout)
+        self._dropout_rng = None     # enable_dropout(): {"seed", "calls"}
         self._engine = None
         self._packed_versions = ()   # (is frontend, parameter, its _version when the engine was packed)
         # outside autocast: True = every product of the forward on three half MFMAs over hi + lo operand halves
@@ -308,6 +317,46 @@ class BeatThis(_TracksChildren, nn.Module):
                 return True
         return False
 
+    # -- dropout on the differentiable route -------------------------------------------------------------
+    def enable_dropout(self, seed: int = 0) -> "BeatThis":
+        """Opt in: in ``train()`` mode the differentiable route drops at rate ``dropout["transformer"]``, with masks drawn
+        under ``seed``; the call counter starts at 0."""
+        p = float(self.dropout.get("transformer", 0.0))
+        if not 0.0 <= p < 1.0:   # (NaN fails both comparisons)
+            raise ValueError(f"dropout['transformer'] = {p}: the rate must satisfy 0 <= p < 1")
+        self.set_dropout_state({"seed": seed, "calls": 0})
+        return self
+
+    def disable_dropout(self) -> "BeatThis":
+        self._dropout_rng = None
+        return self
+
+    def dropout_state(self):
+        """{"seed", "calls"} -- the seed and how many attention / feed-forward calls have drawn masks so far -- or None when
+        dropout is not enabled"""
+        return None if getattr(self, "_dropout_rng", None) is None else dict(self._dropout_rng)
+
+    def set_dropout_state(self, state: dict) -> None:
+        """Enable dropout at ``state`` (what ``dropout_state()`` returned): the next call that drops takes stream ``calls``"""
+        seed, calls = int(state["seed"]), int(state["calls"])
+        if not (0 <= seed < 1 << 64 and 0 <= calls < 1 << 64):
+            raise ValueError(f"dropout seed and calls must fit 64 unsigned bits, got {seed} and {calls}")
+        self._dropout_rng = {"seed": seed, "calls": calls}
+
+    def _next_dropout(self):
+        """(p, seed, stream) for one attention / feed-forward call of the differentiable route, or None: dropout is active
+        iff it is enabled, the model is in ``train()`` mode and the rate is above 0"""
+        rng = getattr(self, "_dropout_rng", None)
+        p = float(self.dropout.get("transformer", 0.0)) if rng is not None and self.training else 0.0
+        if not p > 0.0:
+            return None
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dropout is active during a graph capture: seed and stream number travel by value, so every replay "
+                               "would repeat the masks of the captured step; capture in eval() or after disable_dropout()")
+        stream = rng["calls"]
+        rng["calls"] = stream + 1
+        return p, rng["seed"], stream
+
     def _refuse_trainable_frontend(self) -> None:
         if torch.is_grad_enabled():
             for p in _params_of(self.frontend):
@@ -333,8 +382,8 @@ class BeatThis(_TracksChildren, nn.Module):
             return _bw.empty_with_graph(x.shape, x, _params_of(node))
         x = x.to(torch.float32)
         if kind == "attn":
-            return _bw.attention(node, x, *self._rope(x.shape[1]))
-        return _bw.feedforward(node, x) if kind == "ff" else _bw.final_norm(node, x)
+            return _bw.attention(node, x, *self._rope(x.shape[1]), self._next_dropout())
+        return _bw.feedforward(node, x, self._next_dropout()) if kind == "ff" else _bw.final_norm(node, x)
 
     def _head_train(self, x: torch.Tensor) -> dict:
         D = self.hparams["transformer_dim"]

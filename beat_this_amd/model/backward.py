@@ -5,8 +5,13 @@ csrc/train.hip).  One Function per unit, each ``once_differentiable``; the refer
 
 The kernels read the parameters' own storage at call time (the reference's layout and values, not the engine's packed
 copies), so an optimizer step is seen by the next forward.  The arithmetic is fp32 whatever ``fp32_split_gemms`` says and
-also under ``torch.autocast``; dropout is taken as 0.  Gradients are overwritten by the library and handed to autograd,
-which accumulates into ``.grad``; they are bitwise reproducible (no atomics anywhere).
+also under ``torch.autocast``.  Gradients are overwritten by the library and handed to autograd, which accumulates into
+``.grad``; they are bitwise reproducible (no atomics anywhere).
+
+Dropout: the attention and the feed-forward take ``drop`` = None (the calls and launches of a model without dropout) or
+``(p, seed, stream)``, which goes to bt_train_forward_dropout and, from ``ctx``, unchanged to bt_train_backward_dropout: the
+kernels recompute the masks from those three numbers, nothing is stored.  ``BeatThis`` decides when dropout is active and
+hands out the streams.
 """
 from __future__ import annotations
 
@@ -32,8 +37,9 @@ def _on_device_of(x: torch.Tensor, *tensors) -> None:
                                "move the model and the input to the same ROCm GPU")
 
 
-def _workspace(unit: int, backward: bool, B: int, T: int, D: int, hidden: int, device) -> torch.Tensor:
-    need = _lib.lib().bt_train_workspace_bytes(unit, int(backward), B, T, D, hidden)
+def _workspace(unit: int, backward: bool, B: int, T: int, D: int, hidden: int, device, drop=None) -> torch.Tensor:
+    query = _lib.lib().bt_train_workspace_bytes if drop is None else _lib.lib().bt_train_workspace_bytes_dropout
+    need = query(unit, int(backward), B, T, D, hidden)
     if need == 0:
         raise ValueError(f"the differentiable route supports widths that are multiples of 32 from 32 to 1024 and ff_mult 1 .. 16, "
                          f"got batch {B}, {T} frames, width {D}, hidden width {hidden}")
@@ -57,6 +63,18 @@ def _call(fn, unit: int, a: _lib.TrainArgs, ws: torch.Tensor, device) -> None:
         _lib.check(fn(_lib.stream_ptr(device), unit, C.byref(a)))
 
 
+def _run(backward: bool, unit: int, a: _lib.TrainArgs, shape, hidden: int, device, drop) -> None:
+    """One attention / feed-forward call: the usual entry point, or with ``drop`` = (p, seed, stream) the dropout one"""
+    B, T, D = shape
+    ws = _workspace(unit, backward, B, T, D, hidden, device, drop)
+    lib = _lib.lib()
+    if drop is None:
+        return _call(lib.bt_train_backward if backward else lib.bt_train_forward, unit, a, ws, device)
+    d = _lib.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2])
+    fn = lib.bt_train_backward_dropout if backward else lib.bt_train_forward_dropout
+    _call(lambda stream, u, args: fn(stream, u, args, C.byref(d)), unit, a, ws, device)
+
+
 def _grad_like(p: torch.Tensor, wanted: bool):
     return torch.empty(p.shape, dtype=torch.float32, device=p.device) if wanted else None
 
@@ -65,7 +83,7 @@ class AttentionFn(torch.autograd.Function):
     """Attention.forward (roformer.py:114-132) on (B, T, D): the branch without the residual."""
 
     @staticmethod
-    def forward(ctx, x, gamma, w_qkv, w_gates, b_gates, w_out, rope, rope_len):
+    def forward(ctx, x, gamma, w_qkv, w_gates, b_gates, w_out, rope, rope_len, drop=None):
         xf = _f32(x)
         B, T, D = xf.shape
         ps = [_f32(p) for p in (gamma, w_qkv, w_gates, b_gates, w_out)]
@@ -76,9 +94,9 @@ class AttentionFn(torch.autograd.Function):
         a = _args(xf, rope=rope, rope_len=rope_len)
         a.gamma, a.w1, a.w2, a.b2, a.w3 = (p.data_ptr() for p in ps)
         a.y, a.save_o, a.save_lse = y.data_ptr(), o.data_ptr(), lse.data_ptr()
-        _call(_lib.lib().bt_train_forward, _lib.UNIT_ATTN, a, _workspace(_lib.UNIT_ATTN, False, B, T, D, 0, xf.device), xf.device)
+        _run(False, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, drop)
         ctx.save_for_backward(xf, o, lse, rope, *ps)
-        ctx.rope_len = rope_len
+        ctx.rope_len, ctx.drop = rope_len, drop
         return y
 
     @staticmethod
@@ -94,15 +112,15 @@ class AttentionFn(torch.autograd.Function):
         a.gamma, a.w1, a.w2, a.b2, a.w3 = (p.data_ptr() for p in (gamma, w_qkv, w_gates, b_gates, w_out))
         a.save_o, a.save_lse, a.gy = o.data_ptr(), lse.data_ptr(), gyf.data_ptr()
         a.gx, a.g_gamma, a.g_w1, a.g_w2, a.g_b2, a.g_w3 = (_lib.ptr(g) for g in (gx, g_gamma, g_qkv, g_wg, g_bg, g_out))
-        _call(_lib.lib().bt_train_backward, _lib.UNIT_ATTN, a, _workspace(_lib.UNIT_ATTN, True, B, T, D, 0, xf.device), xf.device)
-        return gx, g_gamma, g_qkv, g_wg, g_bg, g_out, None, None
+        _run(True, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, ctx.drop)
+        return gx, g_gamma, g_qkv, g_wg, g_bg, g_out, None, None, None
 
 
 class FeedForwardFn(torch.autograd.Function):
     """FeedForward.forward (roformer.py:38-61) on (B, T, D): the branch without the residual."""
 
     @staticmethod
-    def forward(ctx, x, gamma, w1, b1, w2, b2):
+    def forward(ctx, x, gamma, w1, b1, w2, b2, drop=None):
         xf = _f32(x)
         B, T, D = xf.shape
         ps = [_f32(p) for p in (gamma, w1, b1, w2, b2)]
@@ -112,8 +130,9 @@ class FeedForwardFn(torch.autograd.Function):
         a = _args(xf, hidden=hidden)
         a.gamma, a.w1, a.b1, a.w2, a.b2 = (p.data_ptr() for p in ps)
         a.y = y.data_ptr()
-        _call(_lib.lib().bt_train_forward, _lib.UNIT_FF, a, _workspace(_lib.UNIT_FF, False, B, T, D, hidden, xf.device), xf.device)
+        _run(False, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, drop)
         ctx.save_for_backward(xf, *ps)
+        ctx.drop = drop
         return y
 
     @staticmethod
@@ -128,8 +147,8 @@ class FeedForwardFn(torch.autograd.Function):
         a.gamma, a.w1, a.b1, a.w2, a.b2 = (p.data_ptr() for p in (gamma, w1, b1, w2, b2))
         a.gy = gyf.data_ptr()
         a.gx, a.g_gamma, a.g_w1, a.g_b1, a.g_w2, a.g_b2 = (_lib.ptr(g) for g in grads)
-        _call(_lib.lib().bt_train_backward, _lib.UNIT_FF, a, _workspace(_lib.UNIT_FF, True, B, T, D, hidden, xf.device), xf.device)
-        return tuple(grads)
+        _run(True, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, ctx.drop)
+        return (*grads, None)
 
 
 class NormFn(torch.autograd.Function):
@@ -207,16 +226,16 @@ def empty_with_graph(shape, x: torch.Tensor, params) -> torch.Tensor:
     return out
 
 
-def attention(node, x, rope, rope_len):
-    """``transformer_blocks.layers[l][0]`` of the differentiable route"""
+def attention(node, x, rope, rope_len, drop=None):
+    """``transformer_blocks.layers[l][0]`` of the differentiable route; ``drop``: None or (p, seed, stream)"""
     return AttentionFn.apply(x, node.norm.gamma, node.to_qkv.weight, node.to_gates.weight, node.to_gates.bias,
-                             node.to_out[0].weight, rope, rope_len)
+                             node.to_out[0].weight, rope, rope_len, drop)
 
 
-def feedforward(node, x):
+def feedforward(node, x, drop=None):
     """``transformer_blocks.layers[l][1]``"""
     net = node.net
-    return FeedForwardFn.apply(x, net[0].gamma, net[1].weight, net[1].bias, net._modules["4"].weight, net._modules["4"].bias)
+    return FeedForwardFn.apply(x, net[0].gamma, net[1].weight, net[1].bias, net._modules["4"].weight, net._modules["4"].bias, drop)
 
 
 def final_norm(node, x):

@@ -3,7 +3,7 @@
 up in launch_scripts/train.py:118-131 -- epochs over the training loader, gradient accumulation, one optimiser and scheduler
 step per accumulated batch group, validation with the package's own metrics every few epochs, one checkpoint per epoch -- and
 ``python -m beat_this_amd.train`` is the command line around it.  Every step's arithmetic runs in the package's kernels: the
-differentiable route of ``BeatThis`` (fp32, dropout 0, frozen frontend), the losses, and the fused AdamW of
+differentiable route of ``BeatThis`` (fp32, frozen frontend, dropout in the main layers when enabled), the losses, and the fused AdamW of
 ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
 and ``load_model`` read as it is.
 
@@ -57,10 +57,14 @@ def _to_cpu(obj):
 def save_checkpoint(path, pl_module, optimizer, scheduler, epoch: int, global_step: int) -> None:
     """One file with the reference's (Lightning's) top-level keys: ``state_dict`` (``model.`` prefix), ``hyper_parameters``,
     ``optimizer_states`` and ``lr_schedulers`` (one entry each), ``epoch`` (the last finished one), ``global_step`` (optimiser
-    steps so far) and ``rng``.  Written next to ``path`` first and then moved over it."""
+    steps so far) and ``rng`` (numpy's generator; with dropout enabled also ``rng["dropout"]`` = the model's
+    ``dropout_state()``).  Written next to ``path`` first and then moved over it."""
     ckpt = {"state_dict": _to_cpu(dict(pl_module.state_dict())), "hyper_parameters": dict(pl_module.hyper_parameters),
             "optimizer_states": [_to_cpu(optimizer.state_dict())], "lr_schedulers": [_to_cpu(scheduler.state_dict())],
             "epoch": int(epoch), "global_step": int(global_step), "rng": _rng_state()}
+    dropout = pl_module.model.dropout_state()
+    if dropout is not None:
+        ckpt["rng"]["dropout"] = dropout
     path = os.fspath(path)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = path + ".part"
@@ -94,7 +98,10 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     device and read once per epoch.  After every ``val_frequency``-th epoch ``validate`` runs.  At each epoch's end a
     checkpoint goes to ``checkpoint_path`` (if given).  ``resume``: such a checkpoint (path or loaded dict) -- weights,
     optimiser, schedule, counters and numpy's generator are restored and the run continues with the next epoch, bit for bit
-    as if it had not stopped.
+    as if it had not stopped (with dropout enabled also the model's seed and call counter, when the checkpoint has them).
+
+    A module whose model has dropout enabled is put into ``train()`` mode here and stays in it; validation runs under
+    ``no_grad`` on the inference path, which never drops.
 
     -> dict: ``train_loss`` (one mean per epoch run), ``val`` ([(epoch, metrics)]), ``epoch``, ``global_step``, ``optimizer``,
     ``scheduler``."""
@@ -119,8 +126,12 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
         optimizer.load_state_dict(ckpt["optimizer_states"][0])
         scheduler.load_state_dict(ckpt["lr_schedulers"][0])
         _set_rng_state(ckpt["rng"])
+        if "dropout" in ckpt["rng"] and pl_module.model.dropout_state() is not None:
+            pl_module.model.set_dropout_state(ckpt["rng"]["dropout"])
         first_epoch, global_step = int(ckpt["epoch"]) + 1, int(ckpt["global_step"])
         log(f"resumed after epoch {ckpt['epoch']} ({global_step} optimiser steps)")
+    if pl_module.model.dropout_state() is not None:
+        pl_module.train()
     history = {"train_loss": [], "val": [], "optimizer": optimizer, "scheduler": scheduler}
     optimizer.zero_grad()
     for epoch in range(first_epoch, int(max_epochs)):
@@ -159,7 +170,8 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
 def get_parser() -> argparse.ArgumentParser:
     from .loss import LOSS_TYPES
 
-    p = argparse.ArgumentParser(description="Fine-tune Beat This! on the MI355X kernels (frozen frontend, fp32, dropout 0).")
+    p = argparse.ArgumentParser(description="Fine-tune Beat This! on the MI355X kernels (frozen frontend, fp32, dropout in the "
+                                            "main transformer with --dropout).")
     toggle = argparse.BooleanOptionalAction
     p.add_argument("--data-dir", type=str, required=True, help="data folder: annotations/ and the spectrogram bundles")
     p.add_argument("--checkpoint", type=str, default=None,
@@ -177,6 +189,10 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--accumulate-grad-batches", type=int, default=8)
     p.add_argument("--train-length", type=int, default=1500, help="excerpt length in frames")
     p.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm to this (default: no clipping)")
+    p.add_argument("--dropout", default=False, action=toggle,
+                   help="train the main transformer layers with dropout, seeded by --seed (default: off)")
+    p.add_argument("--transformer-dropout", metavar="RATE", type=float, default=None,
+                   help="dropout rate of the main transformer layers, 0 <= RATE < 1 (default: the checkpoint's, or 0.2 for a new model)")
     p.add_argument("--dbn", default=False, action=toggle, help="DBN post-processing in validation")
     p.add_argument("--eval-trim-beats", metavar="SECONDS", type=float, default=5,
                    help="skip the first seconds of each piece in the metrics (default: %(default)s)")
@@ -222,7 +238,10 @@ def main(argv=None) -> int:
     if ckpt is not None:   # the architecture is the checkpoint's
         keys = ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "stem_dim", "head_dim", "sum_head", "partial_transformers", "dropout")
         arch = {k: ckpt["hyper_parameters"][k] for k in keys if k in ckpt["hyper_parameters"]}
-    pl_module = PLBeatThis(**arch, fps=FPS, lr=args.lr, weight_decay=args.weight_decay, pos_weights=pos_weights, loss_type=args.loss,
+    if args.transformer_dropout is not None:
+        arch["dropout"] = dict(arch.get("dropout", {"frontend": 0.1}), transformer=args.transformer_dropout)
+    pl_module = PLBeatThis(**arch, apply_dropout=args.dropout, dropout_seed=args.seed, fps=FPS, lr=args.lr,
+                           weight_decay=args.weight_decay, pos_weights=pos_weights, loss_type=args.loss,
                            warmup_steps=args.warmup_steps, max_epochs=args.max_epochs, use_dbn=args.dbn,
                            eval_trim_beats=args.eval_trim_beats)
     if ckpt is not None and not args.resume_checkpoint:   # (a resumed run's weights are restored by fit() with the rest)

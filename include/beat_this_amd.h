@@ -641,6 +641,46 @@ size_t bt_train_workspace_bytes(int unit, int backward, int B, int T, int dim, i
 int bt_train_forward(void* stream, int unit, const bt_train_args* a);
 int bt_train_backward(void* stream, int unit, const bt_train_args* a);
 
+/* ---- training: dropout in the attention and feed-forward units (csrc/dropout.h, csrc/train.hip) ---------
+ * The reference's transformer drops at four places per layer (roformer.py): the attention probabilities, the output of to_out,
+ * the GELU's output and the output of the feed-forward's second linear.  The *_dropout entry points take the unit calls'
+ * arguments plus a bt_train_dropout; NULL, or p == 0, launches exactly what bt_train_forward / bt_train_backward launch (which
+ * are these calls with NULL).  0 <= p < 1, anything else (NaN too) is BT_ERR_ARG; p > 0 with BT_UNIT_NORM or BT_TRAIN_UNIT_HEAD
+ * is BT_ERR_ARG.  Masks are never stored: every kernel evaluates Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, key
+ * increments 0x9E3779B9, 0xBB67AE85) for the elements it touches, and the backward must be given the p, seed and stream of
+ * its forward.  THE MASK CONTRACT.  An element belongs to group g (64-bit) and word w (0 .. 3) of its site:
+ *     counter = { g mod 2^32,  site << 24 | g >> 32,  stream mod 2^32,  stream >> 32 },  key = { seed mod 2^32, seed >> 32 }
+ *     kept iff word w of Philox4x32-10(counter, key) >= thr,  thr = floor(p 2^32) computed in double (p = 0 keeps everything);
+ *     a kept value is multiplied by 1 / (1 - p), computed and applied in fp32.
+ *   BT_DROP_ATTN_P    [B][H][T][T], query q by key k of head h = dim / 32 of sequence b:
+ *                     g = ((b H + h) T + q) ((T + 3) / 4) + k / 4,  w = k mod 4   (integer divisions; a group never leaves its
+ *                     query; the words behind key T - 1 of a query's last group are unused)
+ *   BT_DROP_ATTN_OUT  [B T][dim]:     g = row (dim / 4) + col / 4,     w = col mod 4   (to_out's result, before the residual)
+ *   BT_DROP_FF_HIDDEN [B T][hidden]:  g = row (hidden / 4) + col / 4,  w = col mod 4   (the GELU's result)
+ *   BT_DROP_FF_OUT    [B T][dim]:     g = row (dim / 4) + col / 4,     w = col mod 4   (net.4's result, before the residual)
+ * `stream` is the caller's: one value per unit call, so that two calls with one seed never share a counter (the two sites of a
+ * unit share the stream and differ in the site).  With dropout the attention keeps its normaliser over every key, adds p v for
+ * the kept (q, k) pairs only and stores save_o = the dropped output (before the gate); save_lse is unchanged.  The backward with
+ * p > 0 needs bt_train_workspace_bytes_dropout (one more [B T, dim] region: the masked upstream gradient); the forward's
+ * workspace is the same as without. */
+#define BT_DROP_ATTN_P 0
+#define BT_DROP_ATTN_OUT 1
+#define BT_DROP_FF_HIDDEN 2
+#define BT_DROP_FF_OUT 3
+typedef struct {
+  float p; uint32_t reserved; uint64_t seed; uint64_t stream;
+} bt_train_dropout;
+/* sizeof, then offsetof p, seed, stream: four entries, the binding's self-check */
+void bt_train_dropout_struct_sizes(int32_t* out);
+size_t bt_train_workspace_bytes_dropout(int unit, int backward, int B, int T, int dim, int hidden);
+int bt_train_forward_dropout(void* stream, int unit, const bt_train_args* a, const bt_train_dropout* dropout);
+int bt_train_backward_dropout(void* stream, int unit, const bt_train_args* a, const bt_train_dropout* dropout);
+/* HOST: out[0 .. 3] = Philox4x32-10 of ctr[0 .. 3] under key[0 .. 1] */
+void bt_philox4x32_10_host(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
+/* HOST: the mask of one site as bytes (1 = kept), one per element in the site's layout above; dim a multiple of 32, hidden a
+ * multiple of 4 (used by BT_DROP_FF_HIDDEN only), B, T >= 1 */
+int bt_dropout_mask_host(const bt_train_dropout* dropout, int site, int B, int T, int dim, int hidden, uint8_t* out);
+
 /* ---- training: the optimiser step (csrc/optim.hip) ------------------------------------------------------
  * Multi-tensor AdamW with torch.optim.AdamW's default semantics (decoupled decay, no amsgrad, no maximize), all fp32.  With
  * gs = grad_scale (times *d_coef when d_coef is given, multiplied in fp32) every element does, one operation at a time and
