@@ -13,9 +13,9 @@ import ctypes as C
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 import trunk_grad_util as U
+from finetune_reference import shift_tolerant_bce
 from gpu_util import POISONS, Guarded, assert_intact, dev, report
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
@@ -219,15 +219,6 @@ def test_gradients_are_bitwise_reproducible_and_batch_invariant():
 
 
 # ---- 5. through the public interface -----------------------------------------------------------------------------------------
-def shift_tolerant_bce(preds, targets, mask, pos_weight=1.0, tol=3):
-    """the shift-tolerant loss as DESIGN.md section 11 states it, in torch on the CPU (differentiable, any float dtype)"""
-    X = F.max_pool1d(preds[:, None], 1 + 2 * tol, 1)[:, 0][:, tol:preds.shape[1] - 3 * tol]
-    S = F.max_pool1d(targets[:, None], 1 + 4 * tol, 1)[:, 0]
-    y = targets[:, 2 * tol:targets.shape[1] - 2 * tol]
-    w = (y + (1 - S)) * mask[:, 2 * tol:mask.shape[1] - 2 * tol]
-    return F.binary_cross_entropy_with_logits(X, y, weight=w, pos_weight=torch.tensor(pos_weight, dtype=preds.dtype))
-
-
 def make_batch(B, T, seed):
     """the device entries of a ``ds.batch(...)`` result"""
     gen = torch.Generator().manual_seed(seed)

@@ -1,10 +1,11 @@
 """Dropout on the fine-tuning route (csrc/dropout.h, csrc/train.hip, BeatThis.enable_dropout, fit): the device against fp64
-torch on the CPU that applies the masks of the numpy restatement (dropout_reference.py), with the yardstick of
+torch on the CPU that applies the masks of the numpy restatement (dropout_reference.py, finetune_reference.py), with the yardstick of
 trunk_grad_util.py -- e_ref is the same computation in fp32, and the outputs and every gradient have to be within 10 e_ref.
 One wrong mask bit in the forward, the dQ or the dK / dV sweep moves an element by about 1 / T relative, decades over that.
 
 Sizes: T = 1, 63, 64, 65, 130, 257 sit on both sides of the 64-wide attention blocks and GEMM tiles, cover T % 4 != 0 (a
-query's last group of keys is ragged) and more than one block; D = 64 and 96 (two and three heads), ff_mult 2, B = 2."""
+query's last group of keys is ragged) and more than one block; D = 64 and 96 (two and three heads), ff_mult 2, B = 2; the units
+also at D = 128 (four heads), ff_mult 4 -- the shipped model's hidden = 4 D -- for T = 65 and 130."""
 import copy
 import ctypes as C
 import os
@@ -15,10 +16,9 @@ import sys
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-import dropout_reference as R
 import trunk_grad_util as U
+from finetune_reference import attention_drop, feedforward_drop, shift_tolerant_bce, unit_masks
 from conftest import ROOT
 from dataset_reference import build_data_folder
 from gpu_util import POISONS, Guarded, assert_intact, dev, report
@@ -55,41 +55,14 @@ def make_model(D, n_layers=2, seed=3):
     return _CACHE[(D, n_layers, seed)]
 
 
-def unit_state_dict(D):
-    """the ``lively`` weights of a 2-layer, ff_mult 2 trunk of width D (a state dict only: the engine's frontend cannot be built
-    at D = 96, ff_mult 2, and the unit calls need nothing of it but the rotary table, which does not depend on the width)"""
-    if ("sd", D) not in _CACHE:
-        _CACHE[("sd", D)] = W.random_state_dict(W.resolve_hparams(dict(transformer_dim=D, ff_mult=2, n_layers=2)), seed=3, style="lively")
-    return _CACHE[("sd", D)]
-
-
-# ---- the units with masks, in torch on the CPU (any float dtype) ------------------------------------------------------------------
-def attention_drop(x, sd, pfx, heads, mask_p, mask_out, c):
-    """oracle.attention with the softmax written out, the probabilities times mask_p c and to_out's result times mask_out c"""
-    b, n, dim = x.shape
-    xn = O.rmsnorm(x, sd[pfx + "norm.gamma"])
-    qkv = O._linear(xn, sd[pfx + "to_qkv.weight"]).view(b, n, 3, heads, 32).permute(2, 0, 3, 1, 4)
-    fr = sd[pfx + "rotary_embed.freqs"]
-    q, k, v = O.rope(qkv[0], fr), O.rope(qkv[1], fr), qkv[2]
-    att = torch.softmax((q @ k.transpose(-1, -2)) * (32 ** -0.5), dim=-1)
-    out = (att * mask_p * c) @ v
-    gates = O._linear(xn, sd[pfx + "to_gates.weight"], sd[pfx + "to_gates.bias"])
-    out = (out * torch.sigmoid(gates).permute(0, 2, 1)[..., None]).permute(0, 2, 1, 3).reshape(b, n, dim)
-    return O._linear(out, sd[pfx + "to_out.0.weight"]) * mask_out * c
-
-
-def feedforward_drop(x, sd, pfx, mask_hidden, mask_out, c):
-    h = O.rmsnorm(x, sd[pfx + "net.0.gamma"])
-    h = F.gelu(O._linear(h, sd[pfx + "net.1.weight"], sd[pfx + "net.1.bias"])) * mask_hidden * c
-    return O._linear(h, sd[pfx + "net.4.weight"], sd[pfx + "net.4.bias"]) * mask_out * c
-
-
-def unit_masks(kind, p, seed, stream, Bn, T, D, hidden):
-    """the two masks of one unit call as numpy arrays in the shapes the restatements multiply by"""
-    if kind == "attn":
-        return (R.mask(p, seed, stream, R.ATTN_P, Bn, T, D), R.mask(p, seed, stream, R.ATTN_OUT, Bn, T, D).reshape(Bn, T, D))
-    return (R.mask(p, seed, stream, R.FF_HIDDEN, Bn, T, D, hidden).reshape(Bn, T, hidden),
-            R.mask(p, seed, stream, R.FF_OUT, Bn, T, D).reshape(Bn, T, D))
+def unit_state_dict(D, ff_mult=2):
+    """the ``lively`` weights of a 2-layer trunk of width D and hidden width ff_mult D (a state dict only: the engine's frontend
+    cannot be built at D = 96, ff_mult 2, and the unit calls need nothing of it but the rotary table, which does not depend on the
+    width)"""
+    if ("sd", D, ff_mult) not in _CACHE:
+        _CACHE[("sd", D, ff_mult)] = W.random_state_dict(W.resolve_hparams(dict(transformer_dim=D, ff_mult=ff_mult, n_layers=2)), seed=3,
+                                                        style="lively")
+    return _CACHE[("sd", D, ff_mult)]
 
 
 def unit_truth(kind, sd, pfx, x, g, dtype, masks, p, residual):
@@ -122,15 +95,15 @@ class Unit:
     """The operands of one attention / feed-forward call (layer 1 of unit_state_dict), optionally in guarded buffers filled
     with ``poison``; ``run`` does the forward and the backward and returns the outputs by state-dict key"""
 
-    def __init__(self, kind, D, x, gy, residual, poison=None):
+    def __init__(self, kind, D, x, gy, residual, poison=None, ff_mult=2):
         from beat_this_amd import _lib as L
 
         self.L, self.kind, self.poison, self.keep = L, kind, poison, []
-        m, sd = make_model(64)[0], unit_state_dict(D)
+        m, sd = make_model(64)[0], unit_state_dict(D, ff_mult)
         self.sd, self.pfx = sd, f"transformer_blocks.layers.1.{0 if kind == 'attn' else 1}."
         self.unit = L.UNIT_ATTN if kind == "attn" else L.UNIT_FF
         Bn, T = x.shape[:2]
-        self.shape, self.hidden = (Bn, T, D), 2 * D
+        self.shape, self.hidden = (Bn, T, D), ff_mult * D
         eng = m.engine()
         eng.ensure_positions(T)
         self.rope = eng.packed._rope_t
@@ -196,19 +169,27 @@ def same_bits(a, b):
 
 
 # ---- 1. units against the truth ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D", [64, 96])
+# D -> (ff_mult, the T of TS, the rates): two and three heads at hidden = 2 D over every size; four heads at the shipped model's
+# ratio hidden = 4 D on both sides of a second 64-row block
+UNIT_CASES = {64: (2, TS, (0.2, 0.5)), 96: (2, TS, (0.2, 0.5)), 128: (4, (65, 130), (0.2,))}
+
+
+@pytest.mark.parametrize("D", [64, 96, 128])
 @pytest.mark.parametrize("kind", ["attn", "ff"])
 def test_unit_against_the_truth(kind, D):
-    sd = unit_state_dict(D)
+    ff_mult, sizes, rates = UNIT_CASES[D]
+    sd = unit_state_dict(D, ff_mult)
     worst = (0.0, None)
     for i, T in enumerate(TS):
+        if T not in sizes:
+            continue
         x, g = randn(B, T, D, seed=200 + 2 * i), randn(B, T, D, seed=201 + 2 * i)
-        for p in (0.2, 0.5):
+        for p in rates:
             for residual in (0, 1):
                 stream = 1000 * i + int(10 * p) + residual
-                u = Unit(kind, D, x, g, residual)
+                u = Unit(kind, D, x, g, residual, ff_mult=ff_mult)
                 got = u.run((p, SEED, stream))
-                masks = unit_masks(kind, p, SEED, stream, B, T, D, 2 * D)
+                masks = unit_masks(kind, p, SEED, stream, B, T, D, ff_mult * D)
                 g32, g64 = (unit_truth(kind, sd, u.pfx, x, g, dt, masks, p, residual) for dt in (torch.float32, torch.float64))
                 e_ref, ratio = U.check(f"dropout {kind} D={D} T={T} p={p} residual={residual}", got, g32, g64)
                 worst = max(worst, (ratio, (T, p, residual, e_ref)))
@@ -254,15 +235,6 @@ def test_determinism_guard_bands_and_poison(kind):
 
 
 # ---- 4. the model -------------------------------------------------------------------------------------------------------------------
-def shift_tolerant_bce(preds, targets, mask, tol=3):
-    """the shift-tolerant loss as DESIGN.md section 11 states it, in torch on the CPU (differentiable, any float dtype)"""
-    X = F.max_pool1d(preds[:, None], 1 + 2 * tol, 1)[:, 0][:, tol:preds.shape[1] - 3 * tol]
-    S = F.max_pool1d(targets[:, None], 1 + 4 * tol, 1)[:, 0]
-    y = targets[:, 2 * tol:targets.shape[1] - 2 * tol]
-    w = (y + (1 - S)) * mask[:, 2 * tol:mask.shape[1] - 2 * tol]
-    return F.binary_cross_entropy_with_logits(X, y, weight=w, pos_weight=torch.tensor(1.0, dtype=preds.dtype))
-
-
 def make_batch(Bn, T, seed):
     gen = torch.Generator().manual_seed(seed)
     spect = torch.log1p(torch.rand(Bn, T, 128, generator=gen) * 30)
