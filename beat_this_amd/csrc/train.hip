@@ -24,6 +24,10 @@
 // Dropout: the kernels that meet one of the four sites have a second instantiation (template
 // parameter DROP) that evaluates the masks of dropout.h for the elements it touches; the masks are stored nowhere, and the
 // instantiations without dropout are the code and the launches they were before.  The order of every sum is the same.
+//
+// 16-mixed: the *_mixed entry points run the same unit code with `mixed` set, which sends the GEMMs and
+// the three attention sweeps to the fp16 MFMA kernels of train_mixed.inc; every other launch, and every launch of the entry
+// points that existed before, is unchanged.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -168,19 +172,26 @@ __global__ __launch_bounds__(256) void gemm_drop_kernel(const GemmP p, const Dro
   gemm_body<false, false, true>(p, ds, drop_act);
 }
 
-template <bool AT, bool BT> void launch_gemm(GemmP p, int chunks, hipStream_t s) {
+#include "train_mixed.inc"   // the 16-mixed route's kernels: fp16 MFMA GEMM and attention sweeps
+
+template <bool AT, bool BT> void launch_gemm(GemmP p, int chunks, hipStream_t s, bool mixed = false) {
+  if (mixed) return launch_mx_gemm<AT, BT>(p, chunks, s);
   dim3 grid((unsigned)((p.N + GT - 1) / GT), (unsigned)((p.M + GT - 1) / GT), (unsigned)chunks);
   hipLaunchKernelGGL((gemm_kernel<AT, BT>), grid, dim3(256), 0, s, p);
 }
 
 // Y[M, N] = A[M, K] W[N, K]^T (+ bias, + resid; act = gelu(Y)); ds: the dropout site over Y (drop_act == 0) or over act
 void linear_fwd(const float* A, const float* W, const float* bias, long M, int N, int K, float* Y, const float* resid, float* act,
-                hipStream_t s, const DropSite* ds = nullptr, int drop_act = 0) {
+                hipStream_t s, const DropSite* ds = nullptr, int drop_act = 0, bool mixed = false) {
   GemmP p{};
   p.A = A; p.lda = K; p.B = W; p.ldb = K; p.M = (int)M; p.N = N; p.K = K; p.kchunk = K;
   p.C = Y; p.ldc = N; p.bias = bias; p.resid = resid; p.ldr = N; p.act = act; p.ldact = N;
   if (!ds) {
-    launch_gemm<false, false>(p, 1, s);
+    launch_gemm<false, false>(p, 1, s, mixed);
+    return;
+  }
+  if (mixed) {
+    hipLaunchKernelGGL(mx_gemm_drop_kernel, mx_grid(p, 1), dim3(256), 0, s, p, *ds, drop_act);
     return;
   }
   dim3 grid((unsigned)((p.N + GT - 1) / GT), (unsigned)((p.M + GT - 1) / GT), 1);
@@ -188,11 +199,11 @@ void linear_fwd(const float* A, const float* W, const float* bias, long M, int N
 }
 
 // dA[M, K] (+)= dY[M, N] W[N, K]
-void linear_bwd_input(const float* dY, const float* W, long M, int N, int K, float* dA, bool accum, hipStream_t s) {
+void linear_bwd_input(const float* dY, const float* W, long M, int N, int K, float* dA, bool accum, hipStream_t s, bool mixed = false) {
   GemmP p{};
   p.A = dY; p.lda = N; p.B = W; p.ldb = K; p.M = (int)M; p.N = K; p.K = N; p.kchunk = N;
   p.C = dA; p.ldc = K; p.accum = accum;
-  launch_gemm<false, true>(p, 1, s);
+  launch_gemm<false, true>(p, 1, s, mixed);
 }
 
 __global__ __launch_bounds__(256) void reduce_parts_kernel(const float* part, long n, int chunks, float* out) {
@@ -207,12 +218,13 @@ int dw_chunks(long M) { return (int)((M + DW_ROWS - 1) / DW_ROWS); }
 int cs_chunks(long M) { return (int)((M + CS_ROWS - 1) / CS_ROWS); }
 
 // dW[N, K] = dY[M, N]^T A[M, K]: partials over DW_ROWS-row chunks in `part`, then added in chunk order
-void linear_bwd_weight(const float* dY, const float* A, long M, int N, int K, float* part, float* dW, hipStream_t s) {
+void linear_bwd_weight(const float* dY, const float* A, long M, int N, int K, float* part, float* dW, hipStream_t s,
+                       bool mixed = false) {
   const int chunks = dw_chunks(M);
   GemmP p{};
   p.A = dY; p.lda = N; p.B = A; p.ldb = K; p.M = N; p.N = K; p.K = (int)M; p.kchunk = DW_ROWS;
   p.C = part; p.ldc = K; p.cz = (long)N * K;
-  launch_gemm<true, true>(p, chunks, s);
+  launch_gemm<true, true>(p, chunks, s, mixed);
   const long n = (long)N * K;
   hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)part, n, chunks, dW);
 }
@@ -733,12 +745,12 @@ int finish(const char* fn) {
 unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // the recomputed part shared by the attention's forward and backward: xn, rinv, rotated qkv, gate logits
-void attn_prologue(const bt_train_args& a, const Layout& L, float* ws, long M, hipStream_t s) {
+void attn_prologue(const bt_train_args& a, const Layout& L, float* ws, long M, hipStream_t s, bool mixed) {
   const int D = a.dim, H = D / 32;
   hipLaunchKernelGGL(rms_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, M, D, ws + L.xn, ws + L.rinv);
-  linear_fwd(ws + L.xn, a.w1, nullptr, M, 3 * D, D, ws + L.a, nullptr, nullptr, s);
+  linear_fwd(ws + L.xn, a.w1, nullptr, M, 3 * D, D, ws + L.a, nullptr, nullptr, s, nullptr, 0, mixed);
   hipLaunchKernelGGL(rope_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, ws + L.a, a.rope, M, a.T, D, 0);
-  linear_fwd(ws + L.xn, a.w2, a.b2, M, H, D, ws + L.small0, nullptr, nullptr, s);
+  linear_fwd(ws + L.xn, a.w2, a.b2, M, H, D, ws + L.small0, nullptr, nullptr, s, nullptr, 0, mixed);
 }
 
 }  // namespace
@@ -819,8 +831,8 @@ int bt_train_forward(void* stream, int unit, const bt_train_args* ap) { return b
 
 int bt_train_backward(void* stream, int unit, const bt_train_args* ap) { return bt_train_backward_dropout(stream, unit, ap, nullptr); }
 
-int bt_train_forward_dropout(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
-  const char* fn = dp ? "bt_train_forward_dropout" : "bt_train_forward";
+// mixed: the 16-mixed route (train_mixed.inc) -- the GEMMs and the attention sweeps on fp16 MFMAs, everything else as it is
+static int train_forward(const char* fn, void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp, bool mixed) {
   if (!ap) return fail(fn, "null argument");
   const bt_train_args& a = *ap;
   if (const char* e = check_shape(unit, a.B, a.T, a.dim, a.hidden, a.rope_len)) return fail(fn, e);
@@ -846,21 +858,28 @@ int bt_train_forward_dropout(void* stream, int unit, const bt_train_args* ap, co
       if (!a.gamma || !a.w1 || !a.b1 || !a.w2 || !a.b2) return fail(fn, "null parameter");
       hipLaunchKernelGGL(rms_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, M, D, ws + L.xn, ws + L.rinv);
       if (!drop) {
-        linear_fwd(ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, s);
-        linear_fwd(ws + L.a, a.w2, a.b2, M, D, HID, a.y, a.residual ? a.x : nullptr, nullptr, s);
+        linear_fwd(ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, s, nullptr, 0, mixed);
+        linear_fwd(ws + L.a, a.w2, a.b2, M, D, HID, a.y, a.residual ? a.x : nullptr, nullptr, s, nullptr, 0, mixed);
       } else {
         const DropSite hid = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_FF_HIDDEN);
         const DropSite out = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_FF_OUT);
-        linear_fwd(ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, s, &hid, 1);
-        linear_fwd(ws + L.a, a.w2, a.b2, M, D, HID, a.y, a.residual ? a.x : nullptr, nullptr, s, &out, 0);
+        linear_fwd(ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, s, &hid, 1, mixed);
+        linear_fwd(ws + L.a, a.w2, a.b2, M, D, HID, a.y, a.residual ? a.x : nullptr, nullptr, s, &out, 0, mixed);
       }
       break;
     }
     default: {   // attention
       if (!a.gamma || !a.w1 || !a.w2 || !a.b2 || !a.w3 || !a.rope || !a.save_o || !a.save_lse)
         return fail(fn, "null parameter, rotary table or saved-tensor pointer");
-      attn_prologue(a, L, ws, M, s);
-      if (!drop) {
+      attn_prologue(a, L, ws, M, s, mixed);
+      if (mixed) {
+        const dim3 grid(blocks_of(a.T, XB), D / 32, a.B);
+        if (!drop)
+          hipLaunchKernelGGL(mx_attn_fwd_kernel, grid, dim3(64), 0, s, (const float*)(ws + L.a), a.T, D, a.save_o, a.save_lse);
+        else
+          hipLaunchKernelGGL(mx_attn_fwd_drop_kernel, grid, dim3(64), 0, s, (const float*)(ws + L.a), a.T, D, a.save_o, a.save_lse,
+                             drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P));
+      } else if (!drop) {
         hipLaunchKernelGGL(attn_fwd_kernel, dim3(blocks_of(a.T, AB), D / 32, a.B), dim3(AB), 0, s, (const float*)(ws + L.a), a.T, D,
                            a.save_o, a.save_lse);
       } else {
@@ -870,10 +889,10 @@ int bt_train_forward_dropout(void* stream, int unit, const bt_train_args* ap, co
       hipLaunchKernelGGL(gate_fwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o,
                          (const float*)(ws + L.small0), M, D, ws + L.b);
       if (!drop) {
-        linear_fwd(ws + L.b, a.w3, nullptr, M, D, D, a.y, a.residual ? a.x : nullptr, nullptr, s);
+        linear_fwd(ws + L.b, a.w3, nullptr, M, D, D, a.y, a.residual ? a.x : nullptr, nullptr, s, nullptr, 0, mixed);
       } else {
         const DropSite out = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_OUT);
-        linear_fwd(ws + L.b, a.w3, nullptr, M, D, D, a.y, a.residual ? a.x : nullptr, nullptr, s, &out, 0);
+        linear_fwd(ws + L.b, a.w3, nullptr, M, D, D, a.y, a.residual ? a.x : nullptr, nullptr, s, &out, 0, mixed);
       }
       break;
     }
@@ -881,8 +900,11 @@ int bt_train_forward_dropout(void* stream, int unit, const bt_train_args* ap, co
   return finish(fn);
 }
 
-int bt_train_backward_dropout(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
-  const char* fn = dp ? "bt_train_backward_dropout" : "bt_train_backward";
+int bt_train_forward_dropout(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
+  return train_forward(dp ? "bt_train_forward_dropout" : "bt_train_forward", stream, unit, ap, dp, false);
+}
+
+static int train_backward(const char* fn, void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp, bool mixed) {
   if (!ap) return fail(fn, "null argument");
   const bt_train_args& a = *ap;
   if (const char* e = check_shape(unit, a.B, a.T, a.dim, a.hidden, a.rope_len)) return fail(fn, e);
@@ -930,19 +952,19 @@ int bt_train_backward_dropout(void* stream, int unit, const bt_train_args* ap, c
       mask_gy(BT_DROP_FF_OUT);
       hipLaunchKernelGGL(rms_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, M, D, xn, ws + L.rinv);
       const DropSite hid = drop ? drop_site(dp->p, dp->seed, dp->stream, BT_DROP_FF_HIDDEN) : DropSite{};
-      linear_fwd(xn, a.w1, a.b1, M, HID, D, h, nullptr, act, s, drop ? &hid : nullptr, 1);
-      if (a.g_w2) linear_bwd_weight(gy, act, M, D, HID, part, a.g_w2, s);
+      linear_fwd(xn, a.w1, a.b1, M, HID, D, h, nullptr, act, s, drop ? &hid : nullptr, 1, mixed);
+      if (a.g_w2) linear_bwd_weight(gy, act, M, D, HID, part, a.g_w2, s, mixed);
       if (a.g_b2) colsum(gy, D, nullptr, 0, nullptr, 0, M, D, part, a.g_b2, s);
-      linear_bwd_input(gy, a.w2, M, D, HID, act, false, s);                         // da over gelu(h)
+      linear_bwd_input(gy, a.w2, M, D, HID, act, false, s, mixed);                     // da over gelu(h)
       if (!drop)
         hipLaunchKernelGGL(gelu_bwd_kernel, dim3(blocks_of(M * HID, 256)), dim3(256), 0, s, h, (const float*)act, M * HID);   // dh over h
       else
         hipLaunchKernelGGL(gelu_bwd_drop_kernel, dim3(blocks_of(M * HID / 4, 256)), dim3(256), 0, s, h, (const float*)act, M * HID / 4,
                            hid);
-      if (a.g_w1) linear_bwd_weight(h, xn, M, HID, D, part, a.g_w1, s);
+      if (a.g_w1) linear_bwd_weight(h, xn, M, HID, D, part, a.g_w1, s, mixed);
       if (a.g_b1) colsum(h, HID, nullptr, 0, nullptr, 0, M, HID, part, a.g_b1, s);
       if (a.gx || a.g_gamma) {
-        linear_bwd_input(h, a.w1, M, HID, D, xn, false, s);                         // d xn over xn
+        linear_bwd_input(h, a.w1, M, HID, D, xn, false, s, mixed);                     // d xn over xn
         hipLaunchKernelGGL(rms_bwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, (const float*)xn, resid, M, D, a.gx,
                            ws + L.rinv);
         if (a.g_gamma) colsum(xn, D, a.x, D, ws + L.rinv, 1, M, D, part, a.g_gamma, s);
@@ -961,17 +983,31 @@ int bt_train_backward_dropout(void* stream, int unit, const bt_train_args* ap, c
       float* delta = ws + L.small1;
       float* dgl = ws + L.small2;
       mask_gy(BT_DROP_ATTN_OUT);
-      attn_prologue(a, L, ws, M, s);
+      attn_prologue(a, L, ws, M, s, mixed);
       if (a.g_w3) {
         hipLaunchKernelGGL(gate_fwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o, (const float*)gl, M, D,
                            og);
-        linear_bwd_weight(gy, og, M, D, D, part, a.g_w3, s);
+        linear_bwd_weight(gy, og, M, D, D, part, a.g_w3, s, mixed);
       }
-      linear_bwd_input(gy, a.w3, M, D, D, dO, false, s);                            // d og
+      linear_bwd_input(gy, a.w3, M, D, D, dO, false, s, mixed);                        // d og
       hipLaunchKernelGGL(gate_bwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o, (const float*)gl, dO, M,
                          D, delta, dgl);                                             // -> dO, delta, d gate logits
       const dim3 grid(blocks_of(a.T, AB), H, a.B);
-      if (!drop) {
+      if (mixed) {
+        const dim3 xgrid(blocks_of(a.T, XB), H, a.B);
+        if (!drop) {
+          hipLaunchKernelGGL(mx_attn_dkv_kernel, xgrid, dim3(64), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
+                             (const float*)delta, a.T, D, dqkv);
+          hipLaunchKernelGGL(mx_attn_dq_kernel, xgrid, dim3(64), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
+                             (const float*)delta, a.T, D, dqkv);
+        } else {
+          const DropSite pd = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P);
+          hipLaunchKernelGGL(mx_attn_dkv_drop_kernel, xgrid, dim3(64), 0, s, (const float*)qkv, (const float*)dO,
+                             (const float*)a.save_lse, (const float*)delta, a.T, D, dqkv, pd);
+          hipLaunchKernelGGL(mx_attn_dq_drop_kernel, xgrid, dim3(64), 0, s, (const float*)qkv, (const float*)dO,
+                             (const float*)a.save_lse, (const float*)delta, a.T, D, dqkv, pd);
+        }
+      } else if (!drop) {
         hipLaunchKernelGGL(attn_dkv_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
                            (const float*)delta, a.T, D, dqkv);
         hipLaunchKernelGGL(attn_dq_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
@@ -984,18 +1020,63 @@ int bt_train_backward_dropout(void* stream, int unit, const bt_train_args* ap, c
                            (const float*)delta, a.T, D, dqkv, pd);
       }
       hipLaunchKernelGGL(rope_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, dqkv, a.rope, M, a.T, D, 1);
-      if (a.g_w1) linear_bwd_weight(dqkv, xn, M, 3 * D, D, part, a.g_w1, s);
-      if (a.g_w2) linear_bwd_weight(dgl, xn, M, H, D, part, a.g_w2, s);
+      if (a.g_w1) linear_bwd_weight(dqkv, xn, M, 3 * D, D, part, a.g_w1, s, mixed);
+      if (a.g_w2) linear_bwd_weight(dgl, xn, M, H, D, part, a.g_w2, s, mixed);
       if (a.g_b2) colsum(dgl, H, nullptr, 0, nullptr, 0, M, H, part, a.g_b2, s);
       if (a.gx || a.g_gamma) {
         float* dxn = og;   // (the gated output is no longer needed)
-        linear_bwd_input(dqkv, a.w1, M, 3 * D, D, dxn, false, s);
-        linear_bwd_input(dgl, a.w2, M, H, D, dxn, true, s);
+        linear_bwd_input(dqkv, a.w1, M, 3 * D, D, dxn, false, s, mixed);
+        linear_bwd_input(dgl, a.w2, M, H, D, dxn, true, s, mixed);
         hipLaunchKernelGGL(rms_bwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, (const float*)dxn, resid, M, D, a.gx,
                            ws + L.rinv);
         if (a.g_gamma) colsum(dxn, D, a.x, D, ws + L.rinv, 1, M, D, part, a.g_gamma, s);
       }
       break;
+    }
+  }
+  return finish(fn);
+}
+
+int bt_train_backward_dropout(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
+  return train_backward(dp ? "bt_train_backward_dropout" : "bt_train_backward", stream, unit, ap, dp, false);
+}
+
+// ---- the 16-mixed route: the attention and the feed-forward only ---------------------------------------
+size_t bt_train_workspace_bytes_mixed(int unit, int backward, int B, int T, int dim, int hidden, int with_dropout) {
+  if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return 0;
+  if (check_shape(unit, B, T, dim, hidden, 1 << 30)) return 0;
+  return layout(unit, backward != 0, (long)B * T, dim, hidden, with_dropout != 0).total * sizeof(float);
+}
+
+int bt_train_forward_mixed(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
+  if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return fail("bt_train_forward_mixed", "unit must be BT_UNIT_ATTN or BT_UNIT_FF");
+  return train_forward("bt_train_forward_mixed", stream, unit, ap, dp, true);
+}
+
+int bt_train_backward_mixed(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
+  if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return fail("bt_train_backward_mixed", "unit must be BT_UNIT_ATTN or BT_UNIT_FF");
+  return train_backward("bt_train_backward_mixed", stream, unit, ap, dp, true);
+}
+
+int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B, int M, int N, int K, float* C) {
+  const char* fn = "bt_train_matmul_mixed";
+  if (!A || !B || !C) return fail(fn, "null argument");
+  if (form < 0 || form > 2) return fail(fn, "form must be 0 (A W^T), 1 (dY W) or 2 (dY^T A)");
+  if (M < 1 || N < 1 || K < 1 || M > (1 << 22) || N > (1 << 22) || K > (1 << 22)) return fail(fn, "need 1 <= M, N, K <= 2^22");
+  hipStream_t s = (hipStream_t)stream;
+  GemmP p{};
+  p.M = M; p.N = N; p.C = C; p.ldc = N;
+  if (form == 0) {          // A [M, K], B [N, K]
+    p.A = A; p.lda = K; p.B = B; p.ldb = K; p.K = K; p.kchunk = K;
+    launch_mx_gemm<false, false>(p, 1, s);
+  } else if (form == 1) {   // A [M, K], B [K, N]
+    p.A = A; p.lda = K; p.B = B; p.ldb = N; p.K = K; p.kchunk = K;
+    launch_mx_gemm<false, true>(p, 1, s);
+  } else {                  // A [K, M], B [K, N]: the chunks of BT_TRAIN_DW_ROWS summed rows, added in chunk order
+    for (long k0 = 0; k0 < K; k0 += DW_ROWS) {
+      p.A = A + k0 * M; p.lda = M; p.B = B + k0 * N; p.ldb = N;
+      p.K = (int)std::min<long>(DW_ROWS, K - k0); p.kchunk = p.K; p.accum = k0 > 0;
+      launch_mx_gemm<true, true>(p, 1, s);
     }
   }
   return finish(fn);

@@ -185,6 +185,11 @@ class BeatThis(_TracksChildren, nn.Module):
     RMSNorm and the heads go through ``torch.autograd.Function``s over the library's training kernels, composed like the
     reference's containers.  Fixed semantics of that route:
       * its arithmetic is fp32, whatever ``fp32_split_gemms`` says and also under ``torch.autocast``;
+      * ``set_train_precision("16-mixed")`` opts in to the reference's training precision on that route alone: the attention and
+        the feed-forward round both operands of every matrix product to fp16 and accumulate in fp32 (DESIGN.md section 16;
+        parameters, saved tensors, gradients and everything that is no matrix product stay fp32).  Use it with a loss scale
+        (``beat_this_amd.optim.LossScaler``; ``fit(precision="16-mixed")`` does).  ``"32-true"`` is the default and is what the
+        route was before; ``torch.autocast`` selects neither;
       * dropout is off unless ``enable_dropout(seed)`` was called: then, in ``train()`` mode and with ``dropout["transformer"]``
         above 0, the main layers drop where the reference's do (the attention probabilities, after ``to_out``, after the GELU,
         after the feed-forward's second linear) -- the reference's rule plus the opt-in; in ``eval()`` nothing is dropped.  The
@@ -218,6 +223,7 @@ class BeatThis(_TracksChildren, nn.Module):
         self._bind_units()
         self.dropout = dict(dropout)
         self._dropout_rng = None     # enable_dropout(): {"seed", "calls"}
+        self._train_precision = "32-true"
         self._engine = None
         self._packed_versions = ()   # (is frontend, parameter, its _version when the engine was packed)
         # outside autocast: True = every product of the forward on three half MFMAs over hi + lo operand halves
@@ -317,6 +323,20 @@ class BeatThis(_TracksChildren, nn.Module):
                 return True
         return False
 
+    # -- 16-mixed on the differentiable route --------------------------------------------------------------
+    def set_train_precision(self, precision: str) -> "BeatThis":
+        """"16-mixed": the attention and the feed-forward of the differentiable route run their matrix products on fp16
+        operands with fp32 accumulation; "32-true" (the default): fp32.  Inference, ``no_grad`` and ``eval()`` validation
+        never look at it."""
+        if precision not in ("16-mixed", "32-true"):
+            raise ValueError(f"train precision must be '16-mixed' or '32-true', got {precision!r}")
+        self._train_precision = precision
+        return self
+
+    @property
+    def train_precision(self) -> str:
+        return getattr(self, "_train_precision", "32-true")
+
     # -- dropout on the differentiable route (DESIGN.md section 15) -------------------------------------------------------------
     def enable_dropout(self, seed: int = 0) -> "BeatThis":
         """Opt in: in ``train()`` mode the differentiable route drops at rate ``dropout["transformer"]``, with masks drawn
@@ -381,9 +401,10 @@ class BeatThis(_TracksChildren, nn.Module):
         if x.shape[0] == 0 or x.shape[1] == 0:
             return _bw.empty_with_graph(x.shape, x, _params_of(node))
         x = x.to(torch.float32)
+        mixed = self.train_precision == "16-mixed"
         if kind == "attn":
-            return _bw.attention(node, x, *self._rope(x.shape[1]), self._next_dropout())
-        return _bw.feedforward(node, x, self._next_dropout()) if kind == "ff" else _bw.final_norm(node, x)
+            return _bw.attention(node, x, *self._rope(x.shape[1]), self._next_dropout(), mixed)
+        return _bw.feedforward(node, x, self._next_dropout(), mixed) if kind == "ff" else _bw.final_norm(node, x)
 
     def _head_train(self, x: torch.Tensor) -> dict:
         D = self.hparams["transformer_dim"]

@@ -12,6 +12,11 @@ Dropout: the attention and the feed-forward take ``drop`` = None (the calls and 
 ``(p, seed, stream)``, which goes to bt_train_forward_dropout and, from ``ctx``, unchanged to bt_train_backward_dropout: the
 kernels recompute the masks from those three numbers, nothing is stored.  ``BeatThis`` decides when dropout is active and
 hands out the streams.
+
+16-mixed: the attention and the feed-forward take ``mixed``; True sends the same arguments to
+bt_train_forward_mixed / bt_train_backward_mixed (both operands of every matrix product rounded to fp16, fp32 accumulation,
+everything else fp32), False -- the default -- makes the calls above.  ``BeatThis.set_train_precision`` decides it;
+``torch.autocast`` does not.
 """
 from __future__ import annotations
 
@@ -37,9 +42,12 @@ def _on_device_of(x: torch.Tensor, *tensors) -> None:
                                "move the model and the input to the same ROCm GPU")
 
 
-def _workspace(unit: int, backward: bool, B: int, T: int, D: int, hidden: int, device, drop=None) -> torch.Tensor:
-    query = _lib.lib().bt_train_workspace_bytes if drop is None else _lib.lib().bt_train_workspace_bytes_dropout
-    need = query(unit, int(backward), B, T, D, hidden)
+def _workspace(unit: int, backward: bool, B: int, T: int, D: int, hidden: int, device, drop=None, mixed=False) -> torch.Tensor:
+    if mixed:
+        need = _lib.lib().bt_train_workspace_bytes_mixed(unit, int(backward), B, T, D, hidden, int(drop is not None))
+    else:
+        query = _lib.lib().bt_train_workspace_bytes if drop is None else _lib.lib().bt_train_workspace_bytes_dropout
+        need = query(unit, int(backward), B, T, D, hidden)
     if need == 0:
         raise ValueError(f"the differentiable route supports widths that are multiples of 32 from 32 to 1024 and ff_mult 1 .. 16, "
                          f"got batch {B}, {T} frames, width {D}, hidden width {hidden}")
@@ -63,11 +71,16 @@ def _call(fn, unit: int, a: _lib.TrainArgs, ws: torch.Tensor, device) -> None:
         _lib.check(fn(_lib.stream_ptr(device), unit, C.byref(a)))
 
 
-def _run(backward: bool, unit: int, a: _lib.TrainArgs, shape, hidden: int, device, drop) -> None:
-    """One attention / feed-forward call: the usual entry point, or with ``drop`` = (p, seed, stream) the dropout one"""
+def _run(backward: bool, unit: int, a: _lib.TrainArgs, shape, hidden: int, device, drop, mixed=False) -> None:
+    """One attention / feed-forward call: the usual entry point, or with ``drop`` = (p, seed, stream) the dropout one;
+    ``mixed``: the 16-mixed entry point, which takes the dropout or NULL"""
     B, T, D = shape
-    ws = _workspace(unit, backward, B, T, D, hidden, device, drop)
+    ws = _workspace(unit, backward, B, T, D, hidden, device, drop, mixed)
     lib = _lib.lib()
+    if mixed:
+        fn = lib.bt_train_backward_mixed if backward else lib.bt_train_forward_mixed
+        d = None if drop is None else C.byref(_lib.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2]))
+        return _call(lambda stream, u, args: fn(stream, u, args, d), unit, a, ws, device)
     if drop is None:
         return _call(lib.bt_train_backward if backward else lib.bt_train_forward, unit, a, ws, device)
     d = _lib.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2])
@@ -83,7 +96,7 @@ class AttentionFn(torch.autograd.Function):
     """Attention.forward (roformer.py:114-132) on (B, T, D): the branch without the residual."""
 
     @staticmethod
-    def forward(ctx, x, gamma, w_qkv, w_gates, b_gates, w_out, rope, rope_len, drop=None):
+    def forward(ctx, x, gamma, w_qkv, w_gates, b_gates, w_out, rope, rope_len, drop=None, mixed=False):
         xf = _f32(x)
         B, T, D = xf.shape
         ps = [_f32(p) for p in (gamma, w_qkv, w_gates, b_gates, w_out)]
@@ -94,9 +107,9 @@ class AttentionFn(torch.autograd.Function):
         a = _args(xf, rope=rope, rope_len=rope_len)
         a.gamma, a.w1, a.w2, a.b2, a.w3 = (p.data_ptr() for p in ps)
         a.y, a.save_o, a.save_lse = y.data_ptr(), o.data_ptr(), lse.data_ptr()
-        _run(False, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, drop)
+        _run(False, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, drop, mixed)
         ctx.save_for_backward(xf, o, lse, rope, *ps)
-        ctx.rope_len, ctx.drop = rope_len, drop
+        ctx.rope_len, ctx.drop, ctx.mixed = rope_len, drop, bool(mixed)
         return y
 
     @staticmethod
@@ -112,15 +125,15 @@ class AttentionFn(torch.autograd.Function):
         a.gamma, a.w1, a.w2, a.b2, a.w3 = (p.data_ptr() for p in (gamma, w_qkv, w_gates, b_gates, w_out))
         a.save_o, a.save_lse, a.gy = o.data_ptr(), lse.data_ptr(), gyf.data_ptr()
         a.gx, a.g_gamma, a.g_w1, a.g_w2, a.g_b2, a.g_w3 = (_lib.ptr(g) for g in (gx, g_gamma, g_qkv, g_wg, g_bg, g_out))
-        _run(True, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, ctx.drop)
-        return gx, g_gamma, g_qkv, g_wg, g_bg, g_out, None, None, None
+        _run(True, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, ctx.drop, ctx.mixed)
+        return gx, g_gamma, g_qkv, g_wg, g_bg, g_out, None, None, None, None
 
 
 class FeedForwardFn(torch.autograd.Function):
     """FeedForward.forward (roformer.py:38-61) on (B, T, D): the branch without the residual."""
 
     @staticmethod
-    def forward(ctx, x, gamma, w1, b1, w2, b2, drop=None):
+    def forward(ctx, x, gamma, w1, b1, w2, b2, drop=None, mixed=False):
         xf = _f32(x)
         B, T, D = xf.shape
         ps = [_f32(p) for p in (gamma, w1, b1, w2, b2)]
@@ -130,9 +143,9 @@ class FeedForwardFn(torch.autograd.Function):
         a = _args(xf, hidden=hidden)
         a.gamma, a.w1, a.b1, a.w2, a.b2 = (p.data_ptr() for p in ps)
         a.y = y.data_ptr()
-        _run(False, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, drop)
+        _run(False, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, drop, mixed)
         ctx.save_for_backward(xf, *ps)
-        ctx.drop = drop
+        ctx.drop, ctx.mixed = drop, bool(mixed)
         return y
 
     @staticmethod
@@ -147,8 +160,8 @@ class FeedForwardFn(torch.autograd.Function):
         a.gamma, a.w1, a.b1, a.w2, a.b2 = (p.data_ptr() for p in (gamma, w1, b1, w2, b2))
         a.gy = gyf.data_ptr()
         a.gx, a.g_gamma, a.g_w1, a.g_b1, a.g_w2, a.g_b2 = (_lib.ptr(g) for g in grads)
-        _run(True, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, ctx.drop)
-        return (*grads, None)
+        _run(True, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, ctx.drop, ctx.mixed)
+        return (*grads, None, None)
 
 
 class NormFn(torch.autograd.Function):
@@ -226,16 +239,17 @@ def empty_with_graph(shape, x: torch.Tensor, params) -> torch.Tensor:
     return out
 
 
-def attention(node, x, rope, rope_len, drop=None):
-    """``transformer_blocks.layers[l][0]`` of the differentiable route; ``drop``: None or (p, seed, stream)"""
+def attention(node, x, rope, rope_len, drop=None, mixed=False):
+    """``transformer_blocks.layers[l][0]`` of the differentiable route; ``drop``: None or (p, seed, stream); ``mixed``: 16-mixed"""
     return AttentionFn.apply(x, node.norm.gamma, node.to_qkv.weight, node.to_gates.weight, node.to_gates.bias,
-                             node.to_out[0].weight, rope, rope_len, drop)
+                             node.to_out[0].weight, rope, rope_len, drop, mixed)
 
 
-def feedforward(node, x, drop=None):
+def feedforward(node, x, drop=None, mixed=False):
     """``transformer_blocks.layers[l][1]``"""
     net = node.net
-    return FeedForwardFn.apply(x, net[0].gamma, net[1].weight, net[1].bias, net._modules["4"].weight, net._modules["4"].bias, drop)
+    return FeedForwardFn.apply(x, net[0].gamma, net[1].weight, net[1].bias, net._modules["4"].weight, net._modules["4"].bias, drop,
+                               mixed)
 
 
 def final_norm(node, x):

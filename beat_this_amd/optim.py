@@ -2,6 +2,8 @@
 tensors, the global gradient norm and its clip coefficient in two more, nothing read back), ``CosineWarmupScheduler`` (the
 reference's schedule, pl_module.py:342-369) and ``param_groups_for`` (its grouping, pl_module.py:283-296).  DESIGN.md section 14.
 ``adamw_step_host`` / ``grad_norm_host`` / ``plan`` expose the library's host twins and its planner on numpy arrays.
+``LossScaler`` is the dynamic loss scale of 16-mixed training with ``torch.amp.GradScaler``'s rule,
+``scale_update`` that rule as a pure function.
 """
 from __future__ import annotations
 
@@ -70,6 +72,58 @@ def adamw_step_host(tensors, n_tensors, chunks, n_chunks, grad, m, v, h: _lib.Op
                                              grad.size, C.byref(h), None if c is None else c.ctypes.data))
 
 
+# ---- the loss scale of 16-mixed training ------------------------------------------------------------------------------------------
+def scale_update(scale: float, growth_tracker: int, found_inf: bool, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000):
+    """``torch.amp.GradScaler.update``'s rule on plain numbers -> (scale, growth_tracker).  A step with a non-finite gradient
+    multiplies the scale by ``backoff_factor`` and clears the tracker; the ``growth_interval``-th finite step in a row
+    multiplies it by ``growth_factor`` (unless that leaves fp32's range) and clears the tracker.  The scale is an fp32 number,
+    as torch's is."""
+    scale = np.float32(scale)
+    if found_inf:
+        return float(scale * np.float32(backoff_factor)), 0
+    streak = int(growth_tracker) + 1
+    if streak == int(growth_interval):
+        with np.errstate(over="ignore"):
+            grown = scale * np.float32(growth_factor)
+        return float(grown if np.isfinite(grown) else scale), 0
+    return float(scale), streak
+
+
+class LossScaler:
+    """The dynamic loss scale of 16-mixed training, ``torch.amp.GradScaler``'s semantics and defaults: multiply the loss by
+    ``scale`` before ``backward()`` and hand the scaler to ``AdamW.step(loss_scaler=...)``, which divides the gradients by it
+    inside its kernel, skips the step when a gradient is not finite, and calls ``update``.  With the default factors the
+    scale stays a power of two, so scaling and unscaling are exact."""
+
+    def __init__(self, init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000):
+        if not (init_scale > 0 and growth_factor > 1.0 and 0.0 < backoff_factor < 1.0 and int(growth_interval) >= 1):
+            raise ValueError("LossScaler needs init_scale > 0, growth_factor > 1, 0 < backoff_factor < 1 and growth_interval >= 1")
+        self.scale = float(np.float32(init_scale))
+        self.growth_factor, self.backoff_factor = float(growth_factor), float(backoff_factor)
+        self.growth_interval, self.growth_tracker = int(growth_interval), 0
+        self.skipped_steps = 0
+
+    def get_scale(self) -> float:
+        return self.scale
+
+    def update(self, found_inf: bool) -> None:
+        self.skipped_steps += int(bool(found_inf))
+        self.scale, self.growth_tracker = scale_update(self.scale, self.growth_tracker, bool(found_inf), self.growth_factor,
+                                                       self.backoff_factor, self.growth_interval)
+
+    def state_dict(self) -> dict:
+        """``torch.amp.GradScaler.state_dict``'s keys"""
+        return {"scale": self.scale, "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": self.growth_tracker}
+
+    def load_state_dict(self, state: dict) -> None:
+        self.scale = float(np.float32(state["scale"]))
+        self.growth_factor, self.backoff_factor = float(state["growth_factor"]), float(state["backoff_factor"])
+        self.growth_interval, self.growth_tracker = int(state["growth_interval"]), int(state["_growth_tracker"])
+
+
 # ---- the optimiser ------------------------------------------------------------------------------------------------------------
 class AdamW(torch.optim.Optimizer):
     """``torch.optim.AdamW`` at its defaults (decoupled decay, no amsgrad, no maximize) for fp32 parameters on a ROCm GPU, on
@@ -82,7 +136,14 @@ class AdamW(torch.optim.Optimizer):
     clipped to that global L2 norm as ``torch.nn.utils.clip_grad_norm_`` does, by two more launches that leave the coefficient
     on the device.  ``accumulate``: the gradients are the sum over that many backward passes and are scaled by its inverse
     inside the kernel (``step(accumulated=k)`` overrides it for one step, e.g. the remainder of an epoch).  Nothing in
-    ``step()`` waits for the GPU; ``last_grad_norm()`` is the only call that does.
+    ``step()`` waits for the GPU; ``last_grad_norm()`` is the only call that does -- unless a ``LossScaler`` is given.
+
+    ``step(loss_scaler=s)`` (16-mixed training): the gradients were computed from ``s.scale`` times the loss.  The step always
+    measures the gradient norm, with the kernel's gradient scale set to 1 / (count * scale), and THE HOST READS that 4-byte
+    norm: the one wait per optimiser step, the wait ``torch.amp.GradScaler.step`` has too.  A norm that is not finite means
+    some gradient was not: the step is skipped entirely -- parameters, moments and the step count stay as they are, the
+    gradients are cleared -- and ``last_step_skipped`` is True; either way ``s.update`` then backs the scale off or counts
+    towards its growth.
 
     Unlike torch, which skips a parameter whose ``grad`` is None, every parameter handed to this optimiser is updated on every
     step: a ``None`` gradient counts as zero (decay and the decaying momentum still move the parameter, as torch does for a
@@ -179,7 +240,7 @@ class AdamW(torch.optim.Optimizer):
             p.grad = view
 
     @torch.no_grad()
-    def step(self, closure=None, *, accumulated=None):
+    def step(self, closure=None, *, accumulated=None, loss_scaler=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -188,16 +249,27 @@ class AdamW(torch.optim.Optimizer):
         count = self.accumulate if accumulated is None else int(accumulated)
         if count < 1:
             raise ValueError(f"accumulated must be a positive number of backward passes, got {accumulated}")
-        self._t += 1
-        h = hyper(self.param_groups, self._t, grad_scale=1.0 / count, zero_grads=True)
+        grad_scale = 1.0 / count if loss_scaler is None else 1.0 / (count * loss_scaler.scale)
+        h = hyper(self.param_groups, self._t + 1, grad_scale=grad_scale, zero_grads=True)
         L = _lib.lib()
+        self.last_step_skipped = False
         with torch.cuda.device(self.device):
             stream = _lib.stream_ptr(self.device)
             coef = None
-            if self.max_grad_norm is not None:
-                _lib.check(L.bt_grad_norm(stream, self._grad.data_ptr(), self._total, h.grad_scale, self.max_grad_norm,
+            if self.max_grad_norm is not None or loss_scaler is not None:
+                max_norm = math.inf if self.max_grad_norm is None else self.max_grad_norm   # (inf: the coefficient is 1)
+                _lib.check(L.bt_grad_norm(stream, self._grad.data_ptr(), self._total, h.grad_scale, max_norm,
                                           self._norm_ws.data_ptr(), self._norm_ws.numel(), self._record.data_ptr()))
-                coef = self._record.data_ptr() + 4
+                if self.max_grad_norm is not None:
+                    coef = self._record.data_ptr() + 4
+            if loss_scaler is not None:
+                finite = math.isfinite(float(self._record[0]))   # (the step's one wait for the GPU)
+                loss_scaler.update(not finite)
+                if not finite:
+                    self._grad.zero_()
+                    self.last_step_skipped = True
+                    return loss
+            self._t += 1
             _lib.check(L.bt_adamw_step(stream, self._tables[0].data_ptr(), len(self._params), self._tables[1].data_ptr(),
                                        self._n_chunks, self._grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), self._total,
                                        C.byref(h), coef))

@@ -3,12 +3,12 @@
 up in launch_scripts/train.py:118-131 -- epochs over the training loader, gradient accumulation, one optimiser and scheduler
 step per accumulated batch group, validation with the package's own metrics every few epochs, one checkpoint per epoch -- and
 ``python -m beat_this_amd.train`` is the command line around it.  Every step's arithmetic runs in the package's kernels: the
-differentiable route of ``BeatThis`` (fp32, frozen frontend, dropout in the main layers when enabled), the losses, and the fused AdamW of
-``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
+differentiable route of ``BeatThis`` (fp32 or, with ``precision="16-mixed"``, fp16 matrix products under a dynamic loss scale;
+frozen frontend, dropout in the main layers when enabled), the losses, and the fused AdamW of ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
 and ``load_model`` read as it is.
 
 Not offered: the reference's wandb logger, ``--compile`` and ``--force-flash-attention`` (nothing here is compiled by torch or
-runs torch's attention), mixed precision, and the test run after training (``beat_this_amd.evaluate`` scores a checkpoint).
+runs torch's attention), bf16 mixed precision, and the test run after training (``beat_this_amd.evaluate`` scores a checkpoint).
 """
 from __future__ import annotations
 
@@ -54,17 +54,20 @@ def _to_cpu(obj):
     return obj
 
 
-def save_checkpoint(path, pl_module, optimizer, scheduler, epoch: int, global_step: int) -> None:
+def save_checkpoint(path, pl_module, optimizer, scheduler, epoch: int, global_step: int, loss_scaler=None) -> None:
     """One file with the reference's (Lightning's) top-level keys: ``state_dict`` (``model.`` prefix), ``hyper_parameters``,
     ``optimizer_states`` and ``lr_schedulers`` (one entry each), ``epoch`` (the last finished one), ``global_step`` (optimiser
     steps so far) and ``rng`` (numpy's generator; with dropout enabled also ``rng["dropout"]`` = the model's
-    ``dropout_state()``).  Written next to ``path`` first and then moved over it."""
+    ``dropout_state()``); a 16-mixed run adds ``loss_scaler`` (the ``LossScaler``'s state).  Written next to ``path`` first and
+    then moved over it."""
     ckpt = {"state_dict": _to_cpu(dict(pl_module.state_dict())), "hyper_parameters": dict(pl_module.hyper_parameters),
             "optimizer_states": [_to_cpu(optimizer.state_dict())], "lr_schedulers": [_to_cpu(scheduler.state_dict())],
             "epoch": int(epoch), "global_step": int(global_step), "rng": _rng_state()}
     dropout = pl_module.model.dropout_state()
     if dropout is not None:
         ckpt["rng"]["dropout"] = dropout
+    if loss_scaler is not None:
+        ckpt["loss_scaler"] = loss_scaler.state_dict()
     path = os.fspath(path)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = path + ".part"
@@ -88,7 +91,7 @@ def validate(pl_module, datamodule) -> dict:
 
 
 def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
-        resume=None, log=print) -> dict:
+        resume=None, log=print, precision=None) -> dict:
     """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
 
     Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
@@ -100,11 +103,23 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     optimiser, schedule, counters and numpy's generator are restored and the run continues with the next epoch, bit for bit
     as if it had not stopped (with dropout enabled also the model's seed and call counter, when the checkpoint has them).
 
+    ``precision``: "16-mixed" or "32-true" sets the model's ``set_train_precision`` first (None leaves it as it is).  A 16-mixed
+    run multiplies the loss by a ``LossScaler``'s scale before ``backward()`` and hands the scaler to every optimiser step, which
+    unscales, skips a step whose gradients are not finite and moves the scale (one 4-byte read per step, ``AdamW.step``); the
+    schedule steps with every optimiser call, skipped or not, as the reference's trainer does.  The losses reported are
+    unscaled; the scaler's state goes into the checkpoint under ``loss_scaler`` and comes back with ``resume``.  Without
+    16-mixed the calls are the ones of an fp32 run.
+
     A module whose model has dropout enabled is put into ``train()`` mode here and stays in it; validation runs under
     ``no_grad`` on the inference path, which never drops.
 
     -> dict: ``train_loss`` (one mean per epoch run), ``val`` ([(epoch, metrics)]), ``epoch``, ``global_step``, ``optimizer``,
-    ``scheduler``."""
+    ``scheduler``, ``loss_scaler`` (None in an fp32 run)."""
+    from .optim import LossScaler
+
+    if precision is not None:
+        pl_module.model.set_train_precision(precision)
+    scaler = LossScaler() if pl_module.model.train_precision == "16-mixed" else None
     accumulate = int(accumulate_grad_batches)
     if accumulate < 1 or int(max_epochs) < 0 or int(val_frequency) < 1:
         raise ValueError("accumulate_grad_batches and val_frequency must be at least 1, max_epochs at least 0")
@@ -128,28 +143,34 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
         _set_rng_state(ckpt["rng"])
         if "dropout" in ckpt["rng"] and pl_module.model.dropout_state() is not None:
             pl_module.model.set_dropout_state(ckpt["rng"]["dropout"])
+        if scaler is not None and "loss_scaler" in ckpt:
+            scaler.load_state_dict(ckpt["loss_scaler"])
         first_epoch, global_step = int(ckpt["epoch"]) + 1, int(ckpt["global_step"])
         log(f"resumed after epoch {ckpt['epoch']} ({global_step} optimiser steps)")
     if pl_module.model.dropout_state() is not None:
         pl_module.train()
-    history = {"train_loss": [], "val": [], "optimizer": optimizer, "scheduler": scheduler}
+    history = {"train_loss": [], "val": [], "optimizer": optimizer, "scheduler": scheduler, "loss_scaler": scaler}
+    step = optimizer.step if scaler is None else (lambda accumulated: optimizer.step(accumulated=accumulated, loss_scaler=scaler))
     optimizer.zero_grad()
     for epoch in range(first_epoch, int(max_epochs)):
         loss_sum = torch.zeros((), dtype=torch.float32, device=device)
         batches = pending = 0
         for i, batch in enumerate(loader):
             loss = pl_module.training_step(batch, i)
-            loss.backward()
+            if scaler is None:
+                loss.backward()
+            else:
+                (loss * scaler.scale).backward()
             loss_sum += loss.detach()
             batches += 1
             pending += 1
             if pending == accumulate:
-                optimizer.step(accumulated=pending)
+                step(accumulated=pending)
                 scheduler.step()
                 global_step += 1
                 pending = 0
         if pending:   # the remainder of the epoch: stepped with its own count
-            optimizer.step(accumulated=pending)
+            step(accumulated=pending)
             scheduler.step()
             global_step += 1
         mean = float(loss_sum) / max(batches, 1)   # (the epoch's only read-back)
@@ -160,7 +181,7 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
             history["val"].append((epoch, metrics))
             line += "".join(f", {k} {v:.4f}" for k, v in metrics.items())
         if checkpoint_path is not None:
-            save_checkpoint(checkpoint_path, pl_module, optimizer, scheduler, epoch, global_step)
+            save_checkpoint(checkpoint_path, pl_module, optimizer, scheduler, epoch, global_step, scaler)
         log(line)
     history["epoch"], history["global_step"] = max(first_epoch, int(max_epochs)) - 1, global_step
     return history
@@ -170,8 +191,8 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
 def get_parser() -> argparse.ArgumentParser:
     from .loss import LOSS_TYPES
 
-    p = argparse.ArgumentParser(description="Fine-tune Beat This! on the MI355X kernels (frozen frontend, fp32, dropout in the "
-                                            "main transformer with --dropout).")
+    p = argparse.ArgumentParser(description="Fine-tune Beat This! on the MI355X kernels (frozen frontend, fp32 or --precision "
+                                            "16-mixed, dropout in the main transformer with --dropout).")
     toggle = argparse.BooleanOptionalAction
     p.add_argument("--data-dir", type=str, required=True, help="data folder: annotations/ and the spectrogram bundles")
     p.add_argument("--checkpoint", type=str, default=None,
@@ -193,6 +214,9 @@ def get_parser() -> argparse.ArgumentParser:
                    help="train the main transformer layers with dropout, seeded by --seed (default: off)")
     p.add_argument("--transformer-dropout", metavar="RATE", type=float, default=None,
                    help="dropout rate of the main transformer layers, 0 <= RATE < 1 (default: the checkpoint's, or 0.2 for a new model)")
+    p.add_argument("--precision", type=str, default="32-true", choices=["32-true", "16-mixed"],
+                   help="16-mixed: the reference's training precision -- fp16 matrix products in the main layers, fp32 master "
+                        "weights, a dynamic loss scale (default: %(default)s)")
     p.add_argument("--dbn", default=False, action=toggle, help="DBN post-processing in validation")
     p.add_argument("--eval-trim-beats", metavar="SECONDS", type=float, default=5,
                    help="skip the first seconds of each piece in the metrics (default: %(default)s)")
@@ -243,7 +267,7 @@ def main(argv=None) -> int:
     pl_module = PLBeatThis(**arch, apply_dropout=args.dropout, dropout_seed=args.seed, fps=FPS, lr=args.lr,
                            weight_decay=args.weight_decay, pos_weights=pos_weights, loss_type=args.loss,
                            warmup_steps=args.warmup_steps, max_epochs=args.max_epochs, use_dbn=args.dbn,
-                           eval_trim_beats=args.eval_trim_beats)
+                           eval_trim_beats=args.eval_trim_beats, precision=args.precision)
     if ckpt is not None and not args.resume_checkpoint:   # (a resumed run's weights are restored by fit() with the rest)
         pl_module.load_state_dict(ckpt["state_dict"])
     pl_module.to(device)

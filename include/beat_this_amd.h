@@ -681,6 +681,37 @@ void bt_philox4x32_10_host(const uint32_t* ctr, const uint32_t* key, uint32_t* o
  * multiple of 4 (used by BT_DROP_FF_HIDDEN only), B, T >= 1 */
 int bt_dropout_mask_host(const bt_train_dropout* dropout, int site, int B, int T, int dim, int hidden, uint8_t* out);
 
+/* ---- training: the 16-mixed route of the attention and the feed-forward (csrc/train_mixed.inc) -----------
+ * The reference trains with precision="16-mixed": fp16 matrix products, fp32 master weights, a dynamic loss scale.  The *_mixed
+ * entry points are the unit calls above (same bt_train_args, same bt_train_dropout or NULL, same shape limits, same saved
+ * tensors x / save_o / save_lse in fp32, same recomputation, fp32 parameters read from the nn.Parameter storage, fp32 x, y, gy,
+ * gx and gradients) with ONE difference.  THE ARITHMETIC CONTRACT: both operands of every matrix product are rounded to IEEE
+ * fp16, round to nearest even, as they are staged, and the product accumulates in fp32 on the gfx950 fp16 MFMAs
+ * (v_mfma_f32_32x32x16_f16).  The products are Y = A W^T, dA = dY W and dW = dY^T A of to_qkv, to_gates, to_out, net.1 and
+ * net.4, and the attention's S = Q K^T, O = P V, dP = dO V^T, dV = P^T dO, dQ = dS K and dK = dS^T Q.  Q and K are rounded after
+ * RoPE; P is rounded after the dropout mask and its 1 / (1 - p) have been applied in fp32 (in the forward P is the probability
+ * relative to the running maximum of the keys seen so far, exp2(s - max), the flash form; the backward rounds exp2(s - lse)).
+ * Everything else is fp32 and is the code of the fp32 route: RMSNorm and its backward, biases and residuals, the softmax
+ * statistics, lse and delta, dS = P (dP - delta), the gates, the GELU and its derivative, RoPE, the column sums and the chunked
+ * dW reduction (BT_TRAIN_DW_ROWS, BT_TRAIN_CS_ROWS).  A value beyond fp16's range becomes inf and propagates; nothing clamps
+ * it -- the caller scales the loss and looks at the gradient norm (beat_this_amd.optim.LossScaler).
+ * Kept from the fp32 route: no atomics; every gradient byte is written by one thread of one launch; every order of summation
+ * depends on the shapes alone (a GEMM element sums k ascending in steps of 16, dQ its key tiles of 32 in ascending order, dK / dV
+ * their query tiles of 32 in ascending order), so two runs are bit-identical; a sequence's gx is the same alone and inside a
+ * batch; no launch reads workspace bytes that its own call has not written; no call synchronises, allocates or clears memory.
+ * The dropout mask contract is unchanged.  Units other than BT_UNIT_ATTN and BT_UNIT_FF are BT_ERR_ARG (workspace query: 0):
+ * the final norm and the head have no matrix product worth an MFMA and stay on the fp32 entries.  The workspace is that of the
+ * fp32 route (with_dropout != 0: that of the dropout entries). */
+size_t bt_train_workspace_bytes_mixed(int unit, int backward, int B, int T, int dim, int hidden, int with_dropout);
+int bt_train_forward_mixed(void* stream, int unit, const bt_train_args* a, const bt_train_dropout* dropout_or_null);
+int bt_train_backward_mixed(void* stream, int unit, const bt_train_args* a, const bt_train_dropout* dropout_or_null);
+/* DIAGNOSTIC: the raw GEMM of the mixed route, fp32 in and out, C [M, N] contiguous, 1 <= M, N, K <= 2^22:
+ *   form 0: C = A B^T, A [M, K], B [N, K]   (Y = A W^T)
+ *   form 1: C = A B,   A [M, K], B [K, N]   (dA = dY W)
+ *   form 2: C = A^T B, A [K, M], B [K, N]   (dW = dY^T A; K = the summed rows, taken BT_TRAIN_DW_ROWS at a time and the chunks
+ *                                            added into C in chunk order, one launch per chunk) */
+int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B, int M, int N, int K, float* C);
+
 /* ---- training: the optimiser step (csrc/optim.hip) ------------------------------------------------------
  * Multi-tensor AdamW with torch.optim.AdamW's default semantics (decoupled decay, no amsgrad, no maximize), all fp32.  With
  * gs = grad_scale (times *d_coef when d_coef is given, multiplied in fp32) every element does, one operation at a time and
