@@ -258,6 +258,12 @@ EXPORTS = {
     "bt_train_forward_mixed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs), C.POINTER(TrainDropout)]),
     "bt_train_backward_mixed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TrainArgs), C.POINTER(TrainDropout)]),
     "bt_train_matmul_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "bt_train_matmul_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bt_train_matmul": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrainDropout), C.c_int, C.c_int,
+                                  C.c_void_p, C.c_size_t]),
+    "bt_train_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(TrainDropout),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bt_optim_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "bt_optim_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
                                 C.c_int64, C.POINTER(C.c_int64)]),

@@ -180,12 +180,12 @@ template <bool AT, bool BT> void launch_gemm(GemmP p, int chunks, hipStream_t s,
   hipLaunchKernelGGL((gemm_kernel<AT, BT>), grid, dim3(256), 0, s, p);
 }
 
-// Y[M, N] = A[M, K] W[N, K]^T (+ bias, + resid; act = gelu(Y)); ds: the dropout site over Y (drop_act == 0) or over act
+// Y[M, N] (+)= A[M, K] W[N, K]^T (+ bias, + resid; act = gelu(Y)); ds: the dropout site over Y (drop_act == 0) or over act
 void linear_fwd(const float* A, const float* W, const float* bias, long M, int N, int K, float* Y, const float* resid, float* act,
-                hipStream_t s, const DropSite* ds = nullptr, int drop_act = 0, bool mixed = false) {
+                hipStream_t s, const DropSite* ds = nullptr, int drop_act = 0, bool mixed = false, bool accum = false) {
   GemmP p{};
   p.A = A; p.lda = K; p.B = W; p.ldb = K; p.M = (int)M; p.N = N; p.K = K; p.kchunk = K;
-  p.C = Y; p.ldc = N; p.bias = bias; p.resid = resid; p.ldr = N; p.act = act; p.ldact = N;
+  p.C = Y; p.ldc = N; p.bias = bias; p.resid = resid; p.ldr = N; p.accum = accum; p.act = act; p.ldact = N;
   if (!ds) {
     launch_gemm<false, false>(p, 1, s, mixed);
     return;
@@ -744,6 +744,47 @@ int finish(const char* fn) {
 
 unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
+// the attention's forward sweep over qkv [B T, 3 D] (after RoPE) -> O, lse; pd: the BT_DROP_ATTN_P site or null
+void attn_fwd_sweep(const float* qkv, int B, int T, int D, float* O, float* lse, const DropSite* pd, hipStream_t s, bool mixed) {
+  if (mixed) {
+    const dim3 grid(blocks_of(T, XB), D / 32, B);
+    if (!pd)
+      hipLaunchKernelGGL(mx_attn_fwd_kernel, grid, dim3(64), 0, s, qkv, T, D, O, lse);
+    else
+      hipLaunchKernelGGL(mx_attn_fwd_drop_kernel, grid, dim3(64), 0, s, qkv, T, D, O, lse, *pd);
+  } else if (!pd) {
+    hipLaunchKernelGGL(attn_fwd_kernel, dim3(blocks_of(T, AB), D / 32, B), dim3(AB), 0, s, qkv, T, D, O, lse);
+  } else {
+    hipLaunchKernelGGL(attn_fwd_drop_kernel, dim3(blocks_of(T, AB), D / 32, B), dim3(AB), 0, s, qkv, T, D, O, lse, *pd);
+  }
+}
+
+// the attention's two backward sweeps (dK / dV, then dQ) -> dqkv [B T, 3 D], before the backward RoPE
+// (delta = sum_d dO O holds with the dropped O: sum_k P dP = sum_k (m c P)(dO . v) = dO . O)
+void attn_bwd_sweeps(const float* qkv, const float* dO, const float* lse, const float* delta, int B, int T, int D, float* dqkv,
+                     const DropSite* pd, hipStream_t s, bool mixed) {
+  const int H = D / 32;
+  if (mixed) {
+    const dim3 xgrid(blocks_of(T, XB), H, B);
+    if (!pd) {
+      hipLaunchKernelGGL(mx_attn_dkv_kernel, xgrid, dim3(64), 0, s, qkv, dO, lse, delta, T, D, dqkv);
+      hipLaunchKernelGGL(mx_attn_dq_kernel, xgrid, dim3(64), 0, s, qkv, dO, lse, delta, T, D, dqkv);
+    } else {
+      hipLaunchKernelGGL(mx_attn_dkv_drop_kernel, xgrid, dim3(64), 0, s, qkv, dO, lse, delta, T, D, dqkv, *pd);
+      hipLaunchKernelGGL(mx_attn_dq_drop_kernel, xgrid, dim3(64), 0, s, qkv, dO, lse, delta, T, D, dqkv, *pd);
+    }
+    return;
+  }
+  const dim3 grid(blocks_of(T, AB), H, B);
+  if (!pd) {
+    hipLaunchKernelGGL(attn_dkv_kernel, grid, dim3(AB), 0, s, qkv, dO, lse, delta, T, D, dqkv);
+    hipLaunchKernelGGL(attn_dq_kernel, grid, dim3(AB), 0, s, qkv, dO, lse, delta, T, D, dqkv);
+  } else {
+    hipLaunchKernelGGL(attn_dkv_drop_kernel, grid, dim3(AB), 0, s, qkv, dO, lse, delta, T, D, dqkv, *pd);
+    hipLaunchKernelGGL(attn_dq_drop_kernel, grid, dim3(AB), 0, s, qkv, dO, lse, delta, T, D, dqkv, *pd);
+  }
+}
+
 // the recomputed part shared by the attention's forward and backward: xn, rinv, rotated qkv, gate logits
 void attn_prologue(const bt_train_args& a, const Layout& L, float* ws, long M, hipStream_t s, bool mixed) {
   const int D = a.dim, H = D / 32;
@@ -872,19 +913,9 @@ static int train_forward(const char* fn, void* stream, int unit, const bt_train_
       if (!a.gamma || !a.w1 || !a.w2 || !a.b2 || !a.w3 || !a.rope || !a.save_o || !a.save_lse)
         return fail(fn, "null parameter, rotary table or saved-tensor pointer");
       attn_prologue(a, L, ws, M, s, mixed);
-      if (mixed) {
-        const dim3 grid(blocks_of(a.T, XB), D / 32, a.B);
-        if (!drop)
-          hipLaunchKernelGGL(mx_attn_fwd_kernel, grid, dim3(64), 0, s, (const float*)(ws + L.a), a.T, D, a.save_o, a.save_lse);
-        else
-          hipLaunchKernelGGL(mx_attn_fwd_drop_kernel, grid, dim3(64), 0, s, (const float*)(ws + L.a), a.T, D, a.save_o, a.save_lse,
-                             drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P));
-      } else if (!drop) {
-        hipLaunchKernelGGL(attn_fwd_kernel, dim3(blocks_of(a.T, AB), D / 32, a.B), dim3(AB), 0, s, (const float*)(ws + L.a), a.T, D,
-                           a.save_o, a.save_lse);
-      } else {
-        hipLaunchKernelGGL(attn_fwd_drop_kernel, dim3(blocks_of(a.T, AB), D / 32, a.B), dim3(AB), 0, s, (const float*)(ws + L.a), a.T,
-                           D, a.save_o, a.save_lse, drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P));
+      {
+        const DropSite pd = drop ? drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P) : DropSite{};
+        attn_fwd_sweep(ws + L.a, a.B, a.T, D, a.save_o, a.save_lse, drop ? &pd : nullptr, s, mixed);
       }
       hipLaunchKernelGGL(gate_fwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o,
                          (const float*)(ws + L.small0), M, D, ws + L.b);
@@ -992,32 +1023,9 @@ static int train_backward(const char* fn, void* stream, int unit, const bt_train
       linear_bwd_input(gy, a.w3, M, D, D, dO, false, s, mixed);                        // d og
       hipLaunchKernelGGL(gate_bwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o, (const float*)gl, dO, M,
                          D, delta, dgl);                                             // -> dO, delta, d gate logits
-      const dim3 grid(blocks_of(a.T, AB), H, a.B);
-      if (mixed) {
-        const dim3 xgrid(blocks_of(a.T, XB), H, a.B);
-        if (!drop) {
-          hipLaunchKernelGGL(mx_attn_dkv_kernel, xgrid, dim3(64), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
-                             (const float*)delta, a.T, D, dqkv);
-          hipLaunchKernelGGL(mx_attn_dq_kernel, xgrid, dim3(64), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
-                             (const float*)delta, a.T, D, dqkv);
-        } else {
-          const DropSite pd = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P);
-          hipLaunchKernelGGL(mx_attn_dkv_drop_kernel, xgrid, dim3(64), 0, s, (const float*)qkv, (const float*)dO,
-                             (const float*)a.save_lse, (const float*)delta, a.T, D, dqkv, pd);
-          hipLaunchKernelGGL(mx_attn_dq_drop_kernel, xgrid, dim3(64), 0, s, (const float*)qkv, (const float*)dO,
-                             (const float*)a.save_lse, (const float*)delta, a.T, D, dqkv, pd);
-        }
-      } else if (!drop) {
-        hipLaunchKernelGGL(attn_dkv_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
-                           (const float*)delta, a.T, D, dqkv);
-        hipLaunchKernelGGL(attn_dq_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
-                           (const float*)delta, a.T, D, dqkv);
-      } else {   // (delta = sum_d dO O holds with the dropped O: sum_k P dP = sum_k (m c P)(dO . v) = dO . O)
-        const DropSite pd = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P);
-        hipLaunchKernelGGL(attn_dkv_drop_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
-                           (const float*)delta, a.T, D, dqkv, pd);
-        hipLaunchKernelGGL(attn_dq_drop_kernel, grid, dim3(AB), 0, s, (const float*)qkv, (const float*)dO, (const float*)a.save_lse,
-                           (const float*)delta, a.T, D, dqkv, pd);
+      {
+        const DropSite pd = drop ? drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P) : DropSite{};
+        attn_bwd_sweeps(qkv, dO, a.save_lse, delta, a.B, a.T, D, dqkv, drop ? &pd : nullptr, s, mixed);
       }
       hipLaunchKernelGGL(rope_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, dqkv, a.rope, M, a.T, D, 1);
       if (a.g_w1) linear_bwd_weight(dqkv, xn, M, 3 * D, D, part, a.g_w1, s, mixed);
@@ -1079,6 +1087,65 @@ int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B
       launch_mx_gemm<true, true>(p, 1, s);
     }
   }
+  return finish(fn);
+}
+
+size_t bt_train_matmul_workspace_bytes(int form, int M, int N, int K) {
+  if (form != 2 || M < 1 || N < 1 || K < 1 || M > (1 << 22) || N > (1 << 22) || K > (1 << 22)) return 0;
+  return (size_t)dw_chunks(K) * (size_t)M * (size_t)N * sizeof(float);
+}
+
+int bt_train_matmul(void* stream, int mixed, int form, const float* A, const float* B, int M, int N, int K, float* C,
+                    const float* bias, const float* resid, int accum, float* act, const bt_train_dropout* dp, int site,
+                    int drop_act, void* ws, size_t ws_bytes) {
+  const char* fn = "bt_train_matmul";
+  if (!A || !B || !C) return fail(fn, "null argument");
+  if (form < 0 || form > 2) return fail(fn, "form must be 0 (A W^T), 1 (dY W) or 2 (dY^T A)");
+  if (M < 1 || N < 1 || K < 1 || M > (1 << 22) || N > (1 << 22) || K > (1 << 22)) return fail(fn, "need 1 <= M, N, K <= 2^22");
+  if (form != 0 && (bias || resid || act || dp)) return fail(fn, "bias, resid, act and dropout belong to form 0");
+  if (form == 2 && accum) return fail(fn, "form 2 overwrites C");
+  bool drop = false;
+  if (dp) {
+    if (!(dp->p >= 0.0f && dp->p < 1.0f)) return fail(fn, "dropout p must satisfy 0 <= p < 1");
+    drop = dp->p > 0.0f;
+  }
+  if (drop && (site < BT_DROP_ATTN_OUT || site > BT_DROP_FF_OUT)) return fail(fn, "site must be one of the row sites of BT_DROP_*");
+  if (drop && N % 4) return fail(fn, "with dropout N must be a multiple of 4");
+  if (drop && drop_act && !act) return fail(fn, "drop_act masks act, which is null");
+  hipStream_t s = (hipStream_t)stream;
+  const bool mx = mixed != 0;
+  if (form == 0) {          // A [M, K], B [N, K]
+    const DropSite ds = drop ? drop_site(dp->p, dp->seed, dp->stream, site) : DropSite{};
+    linear_fwd(A, B, bias, M, N, K, C, resid, act, s, drop ? &ds : nullptr, drop_act, mx, accum != 0);
+  } else if (form == 1) {   // A [M, K], B [K, N]
+    linear_bwd_input(A, B, M, K, N, C, accum != 0, s, mx);
+  } else {                  // A [K, M], B [K, N]: partials of BT_TRAIN_DW_ROWS summed rows in ws, then added in chunk order
+    if (!ws) return fail(fn, "form 2 needs a workspace");
+    if (ws_bytes < bt_train_matmul_workspace_bytes(2, M, N, K)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
+    linear_bwd_weight(A, B, K, M, N, (float*)ws, C, s, mx);
+  }
+  return finish(fn);
+}
+
+int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int dim, const float* qkv,
+                       const bt_train_dropout* dp, float* O, float* lse, const float* dO, const float* delta, float* dqkv) {
+  const char* fn = "bt_train_attention";
+  if (dim < 32 || dim > 1024 || dim % 32) return fail(fn, "unsupported width (a multiple of 32 from 32 to 1024)");
+  if (B < 1 || B > 65535 || T < 1 || (long)B * T > (1L << 22)) return fail(fn, "need 1 <= B <= 65535, T >= 1 and B T <= 2^22");
+  if (!qkv || !lse || (backward ? !dO || !delta || !dqkv : !O)) return fail(fn, "null argument");
+  if ((uintptr_t)qkv % 16 || (backward ? (uintptr_t)dO % 16 || (uintptr_t)dqkv % 16 : (uintptr_t)O % 16))
+    return fail(fn, "qkv, O, dO and dqkv must be 16-byte aligned");
+  bool drop = false;
+  if (dp) {
+    if (!(dp->p >= 0.0f && dp->p < 1.0f)) return fail(fn, "dropout p must satisfy 0 <= p < 1");
+    drop = dp->p > 0.0f;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const DropSite pd = drop ? drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P) : DropSite{};
+  if (!backward)
+    attn_fwd_sweep(qkv, B, T, dim, O, lse, drop ? &pd : nullptr, s, mixed != 0);
+  else
+    attn_bwd_sweeps(qkv, dO, lse, delta, B, T, dim, dqkv, drop ? &pd : nullptr, s, mixed != 0);
   return finish(fn);
 }
 

@@ -711,6 +711,33 @@ int bt_train_backward_mixed(void* stream, int unit, const bt_train_args* a, cons
  *   form 2: C = A^T B, A [K, M], B [K, N]   (dW = dY^T A; K = the summed rows, taken BT_TRAIN_DW_ROWS at a time and the chunks
  *                                            added into C in chunk order, one launch per chunk) */
 int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B, int M, int N, int K, float* C);
+/* DIAGNOSTIC: the GEMM of either training route (mixed = 0: the fp32 MFMA kernels, 1: the fp16 ones) through the host helpers
+ * the unit calls launch it with, forms as above, C [M, N] contiguous, 1 <= M, N, K <= 2^22.  The caller supplies every buffer;
+ * nothing is allocated, cleared or synchronised.
+ *   form 0: C = [resid +] m c (A B^T + bias) [+ the old C when accum != 0]; act (or NULL) = gelu(C).  bias [N], resid and act
+ *           [M, N] or NULL.  dropout (or NULL, or p == 0: none) puts the row site `site` (BT_DROP_ATTN_OUT, _FF_HIDDEN or _FF_OUT)
+ *           over the [M, N] result, N a multiple of 4: drop_act == 0 masks the value before the residual as written above,
+ *           drop_act != 0 leaves C alone and masks act = m c gelu(C) (act must be given)
+ *   form 1: C (+)= A B; accum as above, the other optional arguments must be NULL
+ *   form 2: C = A^T B over K summed rows the way a weight gradient is taken: one launch writes the partials of the
+ *           BT_TRAIN_DW_ROWS-row chunks into ws ([chunks][M][N] floats, bt_train_matmul_workspace_bytes), a second adds them
+ *           in chunk order; every optional argument must be NULL / 0
+ * ws / ws_bytes: form 2 only (too small: BT_ERR_WORKSPACE); bt_train_matmul_workspace_bytes is 0 for the other forms. */
+size_t bt_train_matmul_workspace_bytes(int form, int M, int N, int K);
+int bt_train_matmul(void* stream, int mixed, int form, const float* A, const float* B, int M, int N, int K, float* C,
+                    const float* bias, const float* resid, int accum, float* act, const bt_train_dropout* dropout_or_null,
+                    int site, int drop_act, void* ws, size_t ws_bytes);
+/* DIAGNOSTIC: the attention sweeps of either route on their own, launched as the unit calls launch them (blocks of
+ * BT_TRAIN_ATTN_BLOCK queries on the fp32 route, of 32 on the mixed one).  qkv [B T, 3 dim] is what the sweeps read after RoPE:
+ * q | k | v, head h in columns 32 h of each section; dim a multiple of 32 from 32 to 1024, B <= 65535, B T <= 2^22; qkv, O, dO
+ * and dqkv 16-byte aligned.  dropout (or NULL, or p == 0: none) is the BT_DROP_ATTN_P site.
+ *   backward == 0: writes O [B T, dim] (before the gate; the dropped output with dropout) and lse [B T, dim / 32]
+ *   backward != 0: reads dO [B T, dim], lse and delta [B T, dim / 32] (= sum_d dO O per row and head), runs the dK / dV sweep and
+ *                  the dQ sweep and writes every element of dqkv [B T, 3 dim], the gradient before the backward RoPE
+ * The arguments of the other direction may be NULL. */
+int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int dim, const float* qkv,
+                       const bt_train_dropout* dropout_or_null, float* O, float* lse, const float* dO, const float* delta,
+                       float* dqkv);
 
 /* ---- training: the optimiser step (csrc/optim.hip) ------------------------------------------------------
  * Multi-tensor AdamW with torch.optim.AdamW's default semantics (decoupled decay, no amsgrad, no maximize), all fp32.  With

@@ -157,7 +157,8 @@ def grad_keys(d):
 
 # ---- the cases of tests/test_gpu_mixed.py ------------------------------------------------------------------------------------------
 UNIT_DIMS = {64: 2, 192: 4}                                             # width -> ff_mult
-UNIT_SIZES = ((1, 1), (1, 63), (1, 64), (1, 65), (3, 33), (1, 130), (1, 1025))   # (B, T)
+# (B, T); (3, 700): 2100 rows, three BT_TRAIN_DW_ROWS chunks of the weight gradients, the last of 52 rows
+UNIT_SIZES = ((1, 1), (1, 63), (1, 64), (1, 65), (3, 33), (1, 130), (1, 1025), (3, 700))
 DROP_SIZES = ((1, 65), (1, 130))
 DROP_P, DROP_SEED = 0.2, 0x5EED_0000_0000_0016
 TRUNK = dict(D=128, L=6, B=2, T=333, ff_mult=4)

@@ -6,6 +6,7 @@ Tile edges of the kernels, each with a T on both sides (B = 1, so T is the numbe
   * attention key block = query block = 64 (BT_TRAIN_ATTN_BLOCK):            T = 63, 64, 65
   * GEMM row tile = 64 and the column sums' row chunk = 64 (BT_TRAIN_CS_ROWS): T = 63, 64, 65
   * the weight gradients' row chunk = 1024 (BT_TRAIN_DW_ROWS):                 T = 1023, 1024, 1025
+and a batch-sized row count, (B, T) = (3, 700): 2100 rows, three chunks of the weight gradients, the last of 52 rows.
 """
 import copy
 import ctypes as C
@@ -25,6 +26,7 @@ pytestmark = pytest.mark.gpu
 SIZES = [(B, T) for T in (1, 31, 32, 33, 65, 100) for B in (1, 3)]
 EDGES_64 = [(1, 63), (1, 64)]                   # (65 is in SIZES)
 EDGES_1024 = [(1, 1023), (1, 1024), (1, 1025)]
+BATCH = [(3, 700)]                              # more than two BT_TRAIN_DW_ROWS chunks
 MODELS = {64: dict(transformer_dim=64, ff_mult=2), 192: dict(transformer_dim=192), 256: dict(transformer_dim=256)}
 _CACHE = {}
 
@@ -99,7 +101,7 @@ def unit_case(m, sd, kind, B, T, seed, sum_head=True):
 def test_unit_against_the_yardstick(kind, D, style):
     sum_head = kind != "head_plain"
     m, sd = make_model(D, style=style, sum_head=sum_head)
-    sizes = SIZES + EDGES_64 + (EDGES_1024 if D == 64 else [])
+    sizes = SIZES + EDGES_64 + (EDGES_1024 + BATCH if D == 64 else [])
     worst = (0.0, None)
     for i, (B, T) in enumerate(sizes):
         got, g32, g64 = unit_case(m, sd, kind.split("_")[0], B, T, seed=100 + 3 * i, sum_head=sum_head)
