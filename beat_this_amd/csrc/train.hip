@@ -37,14 +37,12 @@
 #include <string>
 
 #include "../../include/beat_this_amd.h"
-#include "dropout.h"
+#include "train_common.h"    // GemmP, gemm_epilogue, the vector types and constants shared with the 16-mixed kernels
+#include "train_mixed.inc"   // the 16-mixed route's kernels: fp16 MFMA GEMM and attention sweeps
 
 int bt_set_error_external(int code, const char* msg);   // engine.hip (bt_last_error)
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int DW_ROWS = BT_TRAIN_DW_ROWS;   // rows per partial of a weight gradient
 constexpr int CS_ROWS = BT_TRAIN_CS_ROWS;   // rows per partial of a column sum
@@ -53,47 +51,8 @@ constexpr int GT = 64;                      // GEMM tile: GT x GT outputs, GK de
 constexpr int GK = 16;
 static_assert(AB == 64, "the attention kernels stage with one 64-lane wave");
 constexpr float RMS_EPS = 1e-12f;
-constexpr float QK_SCALE = 0.17677669529663687f;            // 32^-0.5
-constexpr float QK_SCALE_LOG2E = 0.2550348616841918f;       // 32^-0.5 * log2(e)
 
-// ---- GEMM: C[m][n] (+)= sum_k A(m, k) B(n, k) over k in [z kchunk, (z + 1) kchunk) --------------------------------------
-// A(m, k) = AT ? A[k lda + m] : A[m lda + k];  B(n, k) = BT ? B[k ldb + n] : B[n ldb + k]
-struct GemmP {
-  const float* A; long lda;
-  const float* B; long ldb;
-  int M, N, K, kchunk;
-  float* C; long ldc; long cz;      // C of chunk z starts at C + z cz (C may be null when only act is wanted)
-  const float* bias;                // + bias[n]
-  const float* resid; long ldr;     // + resid[m][n]
-  int accum;                        // + the old C[m][n]
-  float* act; long ldact;           // act[m][n] = gelu(value)
-};
-
-__device__ inline float gelu_f(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
-__device__ inline float gelu_grad_f(float v) {
-  return 0.5f * (1.0f + erff(v * 0.70710678118654752f)) + v * 0.3989422804014327f * expf(-0.5f * v * v);
-}
-
-// a[jj] of lane l of a quad of lanes (4 q .. 4 q + 3) becomes a[l mod 4] of lane 4 q + jj: a 4 x 4 transpose over three
-// exchanges.  Every lane of the quad has to be active.
-__device__ inline void quad_transpose(uint32_t (&a)[4], int lane) {
-  const int ql = lane & 3, qb = lane & ~3;
-  uint32_t b[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int give = (ql - s) & 3, from = (ql + s) & 3;
-    uint32_t v = give == 0 ? a[0] : give == 1 ? a[1] : give == 2 ? a[2] : a[3];
-    if (s) v = (uint32_t)__shfl((int)v, qb + from, 64);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) b[k] = from == k ? v : b[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) a[k] = b[k];
-}
-
-// DROP: the site `ds` over the [M][N] result (N a multiple of 4): drop_act == 0 masks the value before the residual is added
-// (C = resid + m c (acc + bias)), drop_act != 0 masks the second output (act = m c gelu(value)) and leaves C alone.  A lane
-// evaluates the groups of four of its sixteen rows and the quad exchanges the words, so every word of a call is used.
+// ---- GEMM (GemmP and the epilogue: train_common.h), one 32 x 32 MFMA tile per wave -----------------------------------------
 template <bool AT, bool BT, bool DROP>
 __device__ inline void gemm_body(const GemmP& p, const DropSite& ds, int drop_act) {
   __shared__ float As[GK][GT + 4];
@@ -130,37 +89,8 @@ __device__ inline void gemm_body(const GemmP& p, const DropSite& ds, int drop_ac
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + g][wm * 32 + lr], Bs[kk + g][wn * 32 + lr], acc, 0, 0, 0);
     __syncthreads();
   }
-  const long col = n0 + wn * 32 + lr;
-  if (col >= p.N) return;
   float* C = p.C ? p.C + (long)blockIdx.z * p.cz : nullptr;
-  const float b = p.bias ? p.bias[col] : 0.0f;
-  uint32_t words[16];
-  if constexpr (DROP) {   // (N is a multiple of 4: the four lanes of a quad are all here or all gone)
-#pragma unroll
-    for (int ri = 0; ri < 4; ++ri) {
-      const long row = m0 + wm * 32 + (lane & 3) + 8 * ri + 4 * g;
-      const PhiloxWords w = drop_words(ds, drop_row_group((uint64_t)row, (uint32_t)p.N, (uint32_t)col));
-      uint32_t q[4] = {w.w[0], w.w[1], w.w[2], w.w[3]};
-      quad_transpose(q, lane);
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) words[4 * ri + jj] = q[jj];
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const long row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;   // C/D map of the 32x32 MFMAs
-    if (row >= p.M) continue;
-    float v = acc[r] + b;
-    float keep = 1.0f;
-    if constexpr (DROP) {
-      keep = words[r] >= ds.thr ? ds.scale : 0.0f;
-      if (!drop_act) v *= keep;
-    }
-    if (p.resid) v += p.resid[row * p.ldr + col];
-    if (p.accum) v += C[row * p.ldc + col];
-    if (C) C[row * p.ldc + col] = v;
-    if (p.act) p.act[row * p.ldact + col] = DROP && drop_act ? gelu_f(v) * keep : gelu_f(v);
-  }
+  gemm_epilogue<DROP>(p, ds, drop_act, C, acc, m0 + wm * 32, n0 + wn * 32 + lr, lane);
 }
 
 template <bool AT, bool BT>
@@ -172,38 +102,47 @@ __global__ __launch_bounds__(256) void gemm_drop_kernel(const GemmP p, const Dro
   gemm_body<false, false, true>(p, ds, drop_act);
 }
 
-#include "train_mixed.inc"   // the 16-mixed route's kernels: fp16 MFMA GEMM and attention sweeps
+unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
-template <bool AT, bool BT> void launch_gemm(GemmP p, int chunks, hipStream_t s, bool mixed = false) {
-  if (mixed) return launch_mx_gemm<AT, BT>(p, chunks, s);
-  dim3 grid((unsigned)((p.N + GT - 1) / GT), (unsigned)((p.M + GT - 1) / GT), (unsigned)chunks);
-  hipLaunchKernelGGL((gemm_kernel<AT, BT>), grid, dim3(256), 0, s, p);
+// What every launch helper below needs to know of the call it serves: the stream, the route (mixed: the fp16 MFMA kernels of
+// train_mixed.inc), and the dropout of the call (null: none, otherwise p > 0).
+struct Launch {
+  hipStream_t s;
+  bool mixed;
+  const bt_train_dropout* dp;
+  bool drop() const { return dp != nullptr; }
+  DropSite site(int id) const { return drop_site(dp->p, dp->seed, dp->stream, id); }
+};
+constexpr int NO_SITE = -1;   // linear_fwd: a result that no dropout site covers
+
+dim3 gemm_grid(const Launch& lc, const GemmP& p, int chunks) {
+  const int t = lc.mixed ? MT : GT;
+  return dim3(blocks_of(p.N, t), blocks_of(p.M, t), (unsigned)chunks);
 }
 
-// Y[M, N] (+)= A[M, K] W[N, K]^T (+ bias, + resid; act = gelu(Y)); ds: the dropout site over Y (drop_act == 0) or over act
-void linear_fwd(const float* A, const float* W, const float* bias, long M, int N, int K, float* Y, const float* resid, float* act,
-                hipStream_t s, const DropSite* ds = nullptr, int drop_act = 0, bool mixed = false, bool accum = false) {
+template <bool AT, bool BT> void launch_gemm(const Launch& lc, const GemmP& p, int chunks) {
+  const auto kernel = lc.mixed ? mx_gemm_kernel<AT, BT> : gemm_kernel<AT, BT>;
+  hipLaunchKernelGGL(kernel, gemm_grid(lc, p, chunks), dim3(256), 0, lc.s, p);
+}
+
+// Y[M, N] (+)= A[M, K] W[N, K]^T (+ bias, + resid; act = gelu(Y)); site: with dropout, the BT_DROP_* row site over Y
+// (drop_act == 0) or over act, or NO_SITE
+void linear_fwd(const Launch& lc, const float* A, const float* W, const float* bias, long M, int N, int K, float* Y, const float* resid,
+                float* act, int site = NO_SITE, int drop_act = 0, bool accum = false) {
   GemmP p{};
   p.A = A; p.lda = K; p.B = W; p.ldb = K; p.M = (int)M; p.N = N; p.K = K; p.kchunk = K;
   p.C = Y; p.ldc = N; p.bias = bias; p.resid = resid; p.ldr = N; p.accum = accum; p.act = act; p.ldact = N;
-  if (!ds) {
-    launch_gemm<false, false>(p, 1, s, mixed);
-    return;
-  }
-  if (mixed) {
-    hipLaunchKernelGGL(mx_gemm_drop_kernel, mx_grid(p, 1), dim3(256), 0, s, p, *ds, drop_act);
-    return;
-  }
-  dim3 grid((unsigned)((p.N + GT - 1) / GT), (unsigned)((p.M + GT - 1) / GT), 1);
-  hipLaunchKernelGGL(gemm_drop_kernel, grid, dim3(256), 0, s, p, *ds, drop_act);
+  if (!lc.drop() || site == NO_SITE) return launch_gemm<false, false>(lc, p, 1);
+  const auto kernel = lc.mixed ? mx_gemm_drop_kernel : gemm_drop_kernel;
+  hipLaunchKernelGGL(kernel, gemm_grid(lc, p, 1), dim3(256), 0, lc.s, p, lc.site(site), drop_act);
 }
 
 // dA[M, K] (+)= dY[M, N] W[N, K]
-void linear_bwd_input(const float* dY, const float* W, long M, int N, int K, float* dA, bool accum, hipStream_t s, bool mixed = false) {
+void linear_bwd_input(const Launch& lc, const float* dY, const float* W, long M, int N, int K, float* dA, bool accum = false) {
   GemmP p{};
   p.A = dY; p.lda = N; p.B = W; p.ldb = K; p.M = (int)M; p.N = K; p.K = N; p.kchunk = N;
   p.C = dA; p.ldc = K; p.accum = accum;
-  launch_gemm<false, true>(p, 1, s, mixed);
+  launch_gemm<false, true>(lc, p, 1);
 }
 
 __global__ __launch_bounds__(256) void reduce_parts_kernel(const float* part, long n, int chunks, float* out) {
@@ -218,15 +157,14 @@ int dw_chunks(long M) { return (int)((M + DW_ROWS - 1) / DW_ROWS); }
 int cs_chunks(long M) { return (int)((M + CS_ROWS - 1) / CS_ROWS); }
 
 // dW[N, K] = dY[M, N]^T A[M, K]: partials over DW_ROWS-row chunks in `part`, then added in chunk order
-void linear_bwd_weight(const float* dY, const float* A, long M, int N, int K, float* part, float* dW, hipStream_t s,
-                       bool mixed = false) {
+void linear_bwd_weight(const Launch& lc, const float* dY, const float* A, long M, int N, int K, float* part, float* dW) {
   const int chunks = dw_chunks(M);
   GemmP p{};
   p.A = dY; p.lda = N; p.B = A; p.ldb = K; p.M = N; p.N = K; p.K = (int)M; p.kchunk = DW_ROWS;
   p.C = part; p.ldc = K; p.cz = (long)N * K;
-  launch_gemm<true, true>(p, chunks, s, mixed);
+  launch_gemm<true, true>(lc, p, chunks);
   const long n = (long)N * K;
-  hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)part, n, chunks, dW);
+  hipLaunchKernelGGL(reduce_parts_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, lc.s, (const float*)part, n, chunks, dW);
 }
 
 // out[j] = sum_m a[m][j] (* b[m][j]) (* r[m rs]), j < N: partials over CS_ROWS-row chunks, then added in chunk order
@@ -245,12 +183,11 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* a, long lda, c
   part[(long)blockIdx.y * N + j] = acc;
 }
 
-void colsum(const float* a, long lda, const float* b, long ldb, const float* r, long rs, long M, int N, float* part, float* out,
-            hipStream_t s) {
+void colsum(const Launch& lc, const float* a, long lda, const float* b, long ldb, const float* r, long rs, long M, int N, float* part,
+            float* out) {
   const int chunks = cs_chunks(M);
-  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)chunks), dim3(256), 0, s, a, lda, b, ldb, r, rs, M, N,
-                     part);
-  hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const float*)part, (long)N, chunks, out);
+  hipLaunchKernelGGL(colsum_kernel, dim3(blocks_of(N, 256), (unsigned)chunks), dim3(256), 0, lc.s, a, lda, b, ldb, r, rs, M, N, part);
+  hipLaunchKernelGGL(reduce_parts_kernel, dim3(blocks_of(N, 256)), dim3(256), 0, lc.s, (const float*)part, (long)N, chunks, out);
 }
 
 // ---- RMSNorm (roformer.py:22-32): y = x / max(|x|, 1e-12) sqrt(D) gamma; one wave per row ---------------------------------
@@ -375,43 +312,29 @@ __device__ inline void attn_fwd_body(const float* qkv, int T, int D, float* O, f
     stage_tile(base + 2 * D, ld, k0, T, Vs, lane);
     __syncthreads();
     const int nk = min(AB, T - k0);
-    if constexpr (!DROP) {
-      for (int j = 0; j < nk; ++j) {
-        const float s = dot32(q, Ks[j]) * QK_SCALE_LOG2E;
-        if (s > mx) {
-          const float corr = exp2f(mx - s);
-          l *= corr;
+    auto step = [&](int j, bool kept) {   // key j of the tile
+      const float s = dot32(q, Ks[j]) * QK_SCALE_LOG2E;
+      if (s > mx) {
+        const float corr = exp2f(mx - s);
+        l *= corr;
 #pragma unroll
-          for (int d = 0; d < 32; ++d) acc[d] *= corr;
-          mx = s;
-        }
-        const float p = exp2f(s - mx);
-        l += p;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) acc[d] = fmaf(p, Vs[j][d], acc[d]);
+        for (int d = 0; d < 32; ++d) acc[d] *= corr;
+        mx = s;
       }
+      const float p = exp2f(s - mx);
+      l += p;
+      const float pk = kept ? p : 0.0f;
+#pragma unroll
+      for (int d = 0; d < 32; ++d) acc[d] = fmaf(pk, Vs[j][d], acc[d]);
+    };
+    if constexpr (!DROP) {
+      for (int j = 0; j < nk; ++j) step(j, true);
     } else {
       for (int j0 = 0; j0 < nk; j0 += 4) {
         const PhiloxWords w = drop_words(ds, drop_attn_group((uint64_t)b * H + h, (uint32_t)T, (uint32_t)t, (uint32_t)(k0 + j0)));
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          const int j = j0 + jj;
-          if (j < nk) {
-            const float s = dot32(q, Ks[j]) * QK_SCALE_LOG2E;
-            if (s > mx) {
-              const float corr = exp2f(mx - s);
-              l *= corr;
-#pragma unroll
-              for (int d = 0; d < 32; ++d) acc[d] *= corr;
-              mx = s;
-            }
-            const float p = exp2f(s - mx);
-            l += p;
-            const float pk = w.w[jj] >= ds.thr ? p : 0.0f;
-#pragma unroll
-            for (int d = 0; d < 32; ++d) acc[d] = fmaf(pk, Vs[j][d], acc[d]);
-          }
-        }
+        for (int jj = 0; jj < 4; ++jj)
+          if (j0 + jj < nk) step(j0 + jj, w.w[jj] >= ds.thr);
       }
     }
   }
@@ -451,27 +374,22 @@ __device__ inline void attn_dq_body(const float* qkv, const float* dO, const flo
     stage_tile(base + 2 * D, ld, k0, T, Vs, lane);
     __syncthreads();
     const int nk = min(AB, T - k0);
-    if constexpr (!DROP) {
-      for (int j = 0; j < nk; ++j) {
-        const float p = exp2f(dot32(q, Ks[j]) * QK_SCALE_LOG2E - ls);
-        const float ds_ = p * (dot32(go, Vs[j]) - dl);
+    auto step = [&](int j, bool kept) {   // key j of the tile
+      const float p = exp2f(dot32(q, Ks[j]) * QK_SCALE_LOG2E - ls);
+      float dp = dot32(go, Vs[j]);
+      if constexpr (DROP) dp = kept ? dp * ds.scale : 0.0f;
+      const float ds_ = p * (dp - dl);
 #pragma unroll
-        for (int d = 0; d < 32; ++d) acc[d] = fmaf(ds_, Ks[j][d], acc[d]);
-      }
+      for (int d = 0; d < 32; ++d) acc[d] = fmaf(ds_, Ks[j][d], acc[d]);
+    };
+    if constexpr (!DROP) {
+      for (int j = 0; j < nk; ++j) step(j, true);
     } else {
       for (int j0 = 0; j0 < nk; j0 += 4) {
         const PhiloxWords w = drop_words(ds, drop_attn_group((uint64_t)b * H + h, (uint32_t)T, (uint32_t)t, (uint32_t)(k0 + j0)));
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          const int j = j0 + jj;
-          if (j < nk) {
-            const float p = exp2f(dot32(q, Ks[j]) * QK_SCALE_LOG2E - ls);
-            const float dp = w.w[jj] >= ds.thr ? dot32(go, Vs[j]) * ds.scale : 0.0f;
-            const float ds_ = p * (dp - dl);
-#pragma unroll
-            for (int d = 0; d < 32; ++d) acc[d] = fmaf(ds_, Ks[j][d], acc[d]);
-          }
-        }
+        for (int jj = 0; jj < 4; ++jj)
+          if (j0 + jj < nk) step(j0 + jj, w.w[jj] >= ds.thr);
       }
     }
   }
@@ -518,16 +436,22 @@ __device__ inline void attn_dkv_body(const float* qkv, const float* dO, const fl
     }
     __syncthreads();
     const int nq = min(AB, T - q0);
-    if constexpr (!DROP) {
-      for (int i = 0; i < nq; ++i) {
-        const float p = exp2f(dot32(Qs[i], k) * QK_SCALE_LOG2E - Ls[i]);
-        const float ds_ = p * (dot32(Gs[i], v) - Ds[i]);
-#pragma unroll
-        for (int d = 0; d < 32; ++d) {
-          dv[d] = fmaf(p, Gs[i][d], dv[d]);
-          dk[d] = fmaf(ds_, Qs[i][d], dk[d]);
-        }
+    auto step = [&](int i, bool kept) {   // query i of the tile
+      const float p = exp2f(dot32(Qs[i], k) * QK_SCALE_LOG2E - Ls[i]);
+      float pm = p, dp = dot32(Gs[i], v);
+      if constexpr (DROP) {
+        pm = kept ? p * ds.scale : 0.0f;
+        dp = kept ? dp * ds.scale : 0.0f;
       }
+      const float ds_ = p * (dp - Ds[i]);
+#pragma unroll
+      for (int d = 0; d < 32; ++d) {
+        dv[d] = fmaf(pm, Gs[i][d], dv[d]);
+        dk[d] = fmaf(ds_, Qs[i][d], dk[d]);
+      }
+    };
+    if constexpr (!DROP) {
+      for (int i = 0; i < nq; ++i) step(i, true);
     } else {
       for (int i0 = 0; i0 < nq; i0 += 4) {   // (every lane of the wave takes part, also the ones behind key T - 1)
         const PhiloxWords w =
@@ -535,21 +459,8 @@ __device__ inline void attn_dkv_body(const float* qkv, const float* dO, const fl
         uint32_t mine[4] = {w.w[0], w.w[1], w.w[2], w.w[3]};
         quad_transpose(mine, lane);
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          const int i = i0 + jj;
-          if (i < nq) {
-            const bool kept = mine[jj] >= ds.thr;
-            const float p = exp2f(dot32(Qs[i], k) * QK_SCALE_LOG2E - Ls[i]);
-            const float pm = kept ? p * ds.scale : 0.0f;
-            const float dp = kept ? dot32(Gs[i], v) * ds.scale : 0.0f;
-            const float ds_ = p * (dp - Ds[i]);
-#pragma unroll
-            for (int d = 0; d < 32; ++d) {
-              dv[d] = fmaf(pm, Gs[i][d], dv[d]);
-              dk[d] = fmaf(ds_, Qs[i][d], dk[d]);
-            }
-          }
-        }
+        for (int jj = 0; jj < 4; ++jj)
+          if (i0 + jj < nq) step(i0 + jj, mine[jj] >= ds.thr);
       }
     }
   }
@@ -721,14 +632,37 @@ Layout layout(int unit, int backward, long M, int D, int HID, bool drop = false)
   return L;
 }
 
+const char* check_width(int D) {
+  return D < 32 || D > 1024 || D % 32 ? "unsupported width (a multiple of 32 from 32 to 1024)" : nullptr;
+}
+
 const char* check_shape(int unit, int B, int T, int D, int HID, int rope_len) {
   if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF && unit != BT_UNIT_NORM && unit != BT_TRAIN_UNIT_HEAD)
     return "unit must be BT_UNIT_ATTN, BT_UNIT_FF, BT_UNIT_NORM or BT_TRAIN_UNIT_HEAD";
-  if (D < 32 || D > 1024 || D % 32) return "unsupported width (a multiple of 32 from 32 to 1024)";
+  if (const char* e = check_width(D)) return e;
   if (unit == BT_UNIT_FF && (HID < D || HID > 16 * D || HID % D)) return "unsupported hidden width (ff_mult 1 .. 16 times the width)";
   const int max_T = rope_len > 0 ? rope_len : 1536;
   if (B < 1 || T < 1 || T > max_T) return "need B >= 1 and 1 <= T <= rope_len (rows of the rotary table)";
   if ((long)B * T > (1L << 22)) return "more than 2^22 rows";
+  return nullptr;
+}
+
+const char* check_mnk(int M, int N, int K) {
+  return M < 1 || N < 1 || K < 1 || M > (1 << 22) || N > (1 << 22) || K > (1 << 22) ? "need 1 <= M, N, K <= 2^22" : nullptr;
+}
+
+// 0 <= p < 1 (NaN fails); *active: dropout is on (dp may be null: off)
+const char* check_p(const bt_train_dropout* dp, bool* active) {
+  *active = false;
+  if (dp && !(dp->p >= 0.0f && dp->p < 1.0f)) return "dropout p must satisfy 0 <= p < 1";
+  *active = dp && dp->p > 0.0f;
+  return nullptr;
+}
+
+// the same for a unit call: p > 0 on the attention or the feed-forward only
+const char* check_dropout(int unit, const bt_train_dropout* dp, bool* active) {
+  if (const char* e = check_p(dp, active)) return e;
+  if (*active && unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return "dropout applies to BT_UNIT_ATTN and BT_UNIT_FF only";
   return nullptr;
 }
 
@@ -742,56 +676,39 @@ int finish(const char* fn) {
   return BT_OK;
 }
 
-unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
-
-// the attention's forward sweep over qkv [B T, 3 D] (after RoPE) -> O, lse; pd: the BT_DROP_ATTN_P site or null
-void attn_fwd_sweep(const float* qkv, int B, int T, int D, float* O, float* lse, const DropSite* pd, hipStream_t s, bool mixed) {
-  if (mixed) {
-    const dim3 grid(blocks_of(T, XB), D / 32, B);
-    if (!pd)
-      hipLaunchKernelGGL(mx_attn_fwd_kernel, grid, dim3(64), 0, s, qkv, T, D, O, lse);
-    else
-      hipLaunchKernelGGL(mx_attn_fwd_drop_kernel, grid, dim3(64), 0, s, qkv, T, D, O, lse, *pd);
-  } else if (!pd) {
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(blocks_of(T, AB), D / 32, B), dim3(AB), 0, s, qkv, T, D, O, lse);
+// the attention's forward sweep over qkv [B T, 3 D] (after RoPE) -> O, lse; with dropout, the BT_DROP_ATTN_P site
+void attn_fwd_sweep(const Launch& lc, const float* qkv, int B, int T, int D, float* O, float* lse) {
+  const dim3 grid(blocks_of(T, lc.mixed ? XB : AB), D / 32, B), block(lc.mixed ? 64 : AB);
+  if (!lc.drop()) {
+    hipLaunchKernelGGL(lc.mixed ? mx_attn_fwd_kernel : attn_fwd_kernel, grid, block, 0, lc.s, qkv, T, D, O, lse);
   } else {
-    hipLaunchKernelGGL(attn_fwd_drop_kernel, dim3(blocks_of(T, AB), D / 32, B), dim3(AB), 0, s, qkv, T, D, O, lse, *pd);
+    const auto kernel = lc.mixed ? mx_attn_fwd_drop_kernel : attn_fwd_drop_kernel;
+    hipLaunchKernelGGL(kernel, grid, block, 0, lc.s, qkv, T, D, O, lse, lc.site(BT_DROP_ATTN_P));
   }
 }
 
 // the attention's two backward sweeps (dK / dV, then dQ) -> dqkv [B T, 3 D], before the backward RoPE
 // (delta = sum_d dO O holds with the dropped O: sum_k P dP = sum_k (m c P)(dO . v) = dO . O)
-void attn_bwd_sweeps(const float* qkv, const float* dO, const float* lse, const float* delta, int B, int T, int D, float* dqkv,
-                     const DropSite* pd, hipStream_t s, bool mixed) {
-  const int H = D / 32;
-  if (mixed) {
-    const dim3 xgrid(blocks_of(T, XB), H, B);
-    if (!pd) {
-      hipLaunchKernelGGL(mx_attn_dkv_kernel, xgrid, dim3(64), 0, s, qkv, dO, lse, delta, T, D, dqkv);
-      hipLaunchKernelGGL(mx_attn_dq_kernel, xgrid, dim3(64), 0, s, qkv, dO, lse, delta, T, D, dqkv);
-    } else {
-      hipLaunchKernelGGL(mx_attn_dkv_drop_kernel, xgrid, dim3(64), 0, s, qkv, dO, lse, delta, T, D, dqkv, *pd);
-      hipLaunchKernelGGL(mx_attn_dq_drop_kernel, xgrid, dim3(64), 0, s, qkv, dO, lse, delta, T, D, dqkv, *pd);
-    }
-    return;
-  }
-  const dim3 grid(blocks_of(T, AB), H, B);
-  if (!pd) {
-    hipLaunchKernelGGL(attn_dkv_kernel, grid, dim3(AB), 0, s, qkv, dO, lse, delta, T, D, dqkv);
-    hipLaunchKernelGGL(attn_dq_kernel, grid, dim3(AB), 0, s, qkv, dO, lse, delta, T, D, dqkv);
+void attn_bwd_sweeps(const Launch& lc, const float* qkv, const float* dO, const float* lse, const float* delta, int B, int T, int D,
+                     float* dqkv) {
+  const dim3 grid(blocks_of(T, lc.mixed ? XB : AB), D / 32, B), block(lc.mixed ? 64 : AB);
+  if (!lc.drop()) {
+    hipLaunchKernelGGL(lc.mixed ? mx_attn_dkv_kernel : attn_dkv_kernel, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv);
+    hipLaunchKernelGGL(lc.mixed ? mx_attn_dq_kernel : attn_dq_kernel, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv);
   } else {
-    hipLaunchKernelGGL(attn_dkv_drop_kernel, grid, dim3(AB), 0, s, qkv, dO, lse, delta, T, D, dqkv, *pd);
-    hipLaunchKernelGGL(attn_dq_drop_kernel, grid, dim3(AB), 0, s, qkv, dO, lse, delta, T, D, dqkv, *pd);
+    const DropSite pd = lc.site(BT_DROP_ATTN_P);
+    hipLaunchKernelGGL(lc.mixed ? mx_attn_dkv_drop_kernel : attn_dkv_drop_kernel, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv, pd);
+    hipLaunchKernelGGL(lc.mixed ? mx_attn_dq_drop_kernel : attn_dq_drop_kernel, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv, pd);
   }
 }
 
 // the recomputed part shared by the attention's forward and backward: xn, rinv, rotated qkv, gate logits
-void attn_prologue(const bt_train_args& a, const Layout& L, float* ws, long M, hipStream_t s, bool mixed) {
+void attn_prologue(const Launch& lc, const bt_train_args& a, const Layout& L, float* ws, long M) {
   const int D = a.dim, H = D / 32;
-  hipLaunchKernelGGL(rms_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, M, D, ws + L.xn, ws + L.rinv);
-  linear_fwd(ws + L.xn, a.w1, nullptr, M, 3 * D, D, ws + L.a, nullptr, nullptr, s, nullptr, 0, mixed);
-  hipLaunchKernelGGL(rope_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, ws + L.a, a.rope, M, a.T, D, 0);
-  linear_fwd(ws + L.xn, a.w2, a.b2, M, H, D, ws + L.small0, nullptr, nullptr, s, nullptr, 0, mixed);
+  hipLaunchKernelGGL(rms_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, lc.s, a.x, a.gamma, M, D, ws + L.xn, ws + L.rinv);
+  linear_fwd(lc, ws + L.xn, a.w1, nullptr, M, 3 * D, D, ws + L.a, nullptr, nullptr);
+  hipLaunchKernelGGL(rope_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, lc.s, ws + L.a, a.rope, M, a.T, D, 0);
+  linear_fwd(lc, ws + L.xn, a.w2, a.b2, M, H, D, ws + L.small0, nullptr, nullptr);
 }
 
 }  // namespace
@@ -811,17 +728,6 @@ void bt_train_struct_sizes(int32_t* out) {
 size_t bt_train_workspace_bytes(int unit, int backward, int B, int T, int dim, int hidden) {
   if (check_shape(unit, B, T, dim, hidden, 1 << 30)) return 0;
   return layout(unit, backward != 0, (long)B * T, dim, hidden).total * sizeof(float);
-}
-
-// NULL or p == 0: no dropout; otherwise 0 < p < 1 on the attention or the feed-forward
-static const char* check_dropout(int unit, const bt_train_dropout* dp, bool* active) {
-  *active = false;
-  if (!dp) return nullptr;
-  if (!(dp->p >= 0.0f && dp->p < 1.0f)) return "dropout p must satisfy 0 <= p < 1";
-  if (dp->p == 0.0f) return nullptr;
-  if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return "dropout applies to BT_UNIT_ATTN and BT_UNIT_FF only";
-  *active = true;
-  return nullptr;
 }
 
 void bt_train_dropout_struct_sizes(int32_t* out) {
@@ -844,7 +750,8 @@ void bt_philox4x32_10_host(const uint32_t* ctr, const uint32_t* key, uint32_t* o
 int bt_dropout_mask_host(const bt_train_dropout* dp, int site, int B, int T, int dim, int hidden, uint8_t* out) {
   const char* fn = "bt_dropout_mask_host";
   if (!dp || !out) return fail(fn, "null argument");
-  if (!(dp->p >= 0.0f && dp->p < 1.0f)) return fail(fn, "dropout p must satisfy 0 <= p < 1");
+  bool drop = false;   // (p == 0 is served like any other p: every element kept)
+  if (const char* e = check_p(dp, &drop)) return fail(fn, e);
   if (site < BT_DROP_ATTN_P || site > BT_DROP_FF_OUT) return fail(fn, "site must be one of BT_DROP_*");
   if (B < 1 || T < 1 || dim < 32 || dim % 32 || (site == BT_DROP_FF_HIDDEN && (hidden < 4 || hidden % 4)))
     return fail(fn, "need B, T >= 1, dim a multiple of 32 and hidden a multiple of 4");
@@ -884,8 +791,10 @@ static int train_forward(const char* fn, void* stream, int unit, const bt_train_
   const Layout L = layout(unit, 0, M, D, HID, drop);
   if (!a.x || !a.y || !a.ws) return fail(fn, "null x, y or workspace");
   if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
-  hipStream_t s = (hipStream_t)stream;
+  const Launch lc{(hipStream_t)stream, mixed, drop ? dp : nullptr};
+  hipStream_t s = lc.s;
   float* ws = (float*)a.ws;
+  const float* resid = a.residual ? a.x : nullptr;
   switch (unit) {
     case BT_UNIT_NORM:
       if (!a.gamma) return fail(fn, "null parameter");
@@ -895,38 +804,21 @@ static int train_forward(const char* fn, void* stream, int unit, const bt_train_
       if (!a.w1 || !a.b1 || !a.y2) return fail(fn, "null parameter or output");
       hipLaunchKernelGGL(head_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.w1, a.b1, M, D, a.sum_head, a.y, a.y2);
       break;
-    case BT_UNIT_FF: {
+    case BT_UNIT_FF:
       if (!a.gamma || !a.w1 || !a.b1 || !a.w2 || !a.b2) return fail(fn, "null parameter");
       hipLaunchKernelGGL(rms_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, M, D, ws + L.xn, ws + L.rinv);
-      if (!drop) {
-        linear_fwd(ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, s, nullptr, 0, mixed);
-        linear_fwd(ws + L.a, a.w2, a.b2, M, D, HID, a.y, a.residual ? a.x : nullptr, nullptr, s, nullptr, 0, mixed);
-      } else {
-        const DropSite hid = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_FF_HIDDEN);
-        const DropSite out = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_FF_OUT);
-        linear_fwd(ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, s, &hid, 1, mixed);
-        linear_fwd(ws + L.a, a.w2, a.b2, M, D, HID, a.y, a.residual ? a.x : nullptr, nullptr, s, &out, 0, mixed);
-      }
+      linear_fwd(lc, ws + L.xn, a.w1, a.b1, M, HID, D, nullptr, nullptr, ws + L.a, BT_DROP_FF_HIDDEN, 1);
+      linear_fwd(lc, ws + L.a, a.w2, a.b2, M, D, HID, a.y, resid, nullptr, BT_DROP_FF_OUT);
       break;
-    }
-    default: {   // attention
+    default:   // attention
       if (!a.gamma || !a.w1 || !a.w2 || !a.b2 || !a.w3 || !a.rope || !a.save_o || !a.save_lse)
         return fail(fn, "null parameter, rotary table or saved-tensor pointer");
-      attn_prologue(a, L, ws, M, s, mixed);
-      {
-        const DropSite pd = drop ? drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P) : DropSite{};
-        attn_fwd_sweep(ws + L.a, a.B, a.T, D, a.save_o, a.save_lse, drop ? &pd : nullptr, s, mixed);
-      }
+      attn_prologue(lc, a, L, ws, M);
+      attn_fwd_sweep(lc, ws + L.a, a.B, a.T, D, a.save_o, a.save_lse);
       hipLaunchKernelGGL(gate_fwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o,
                          (const float*)(ws + L.small0), M, D, ws + L.b);
-      if (!drop) {
-        linear_fwd(ws + L.b, a.w3, nullptr, M, D, D, a.y, a.residual ? a.x : nullptr, nullptr, s, nullptr, 0, mixed);
-      } else {
-        const DropSite out = drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_OUT);
-        linear_fwd(ws + L.b, a.w3, nullptr, M, D, D, a.y, a.residual ? a.x : nullptr, nullptr, s, &out, 0, mixed);
-      }
+      linear_fwd(lc, ws + L.b, a.w3, nullptr, M, D, D, a.y, resid, nullptr, BT_DROP_ATTN_OUT);
       break;
-    }
   }
   return finish(fn);
 }
@@ -948,7 +840,8 @@ static int train_backward(const char* fn, void* stream, int unit, const bt_train
   if (unit != BT_TRAIN_UNIT_HEAD && !a.gy) return fail(fn, "null upstream gradient");
   if (drop && (uintptr_t)a.gy % 16) return fail(fn, "with dropout the upstream gradient must be 16-byte aligned");
   if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
-  hipStream_t s = (hipStream_t)stream;
+  const Launch lc{(hipStream_t)stream, mixed, drop ? dp : nullptr};
+  hipStream_t s = lc.s;
   float* ws = (float*)a.ws;
   float* part = ws + L.part;
   const float* resid = a.residual ? a.gy : nullptr;
@@ -956,23 +849,22 @@ static int train_backward(const char* fn, void* stream, int unit, const bt_train
   const float* gy = drop ? ws + L.gm : a.gy;
   auto mask_gy = [&](int site) {
     if (drop)
-      hipLaunchKernelGGL(mask_kernel, dim3(blocks_of(M * D / 4, 256)), dim3(256), 0, s, a.gy, M * D / 4,
-                         drop_site(dp->p, dp->seed, dp->stream, site), ws + L.gm);
+      hipLaunchKernelGGL(mask_kernel, dim3(blocks_of(M * D / 4, 256)), dim3(256), 0, s, a.gy, M * D / 4, lc.site(site), ws + L.gm);
   };
   switch (unit) {
     case BT_UNIT_NORM:
       if (!a.gamma) return fail(fn, "null parameter");
       hipLaunchKernelGGL(rms_bwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, a.gy, (const float*)nullptr, M, D, a.gx,
                          ws + L.rinv);
-      if (a.g_gamma) colsum(a.gy, D, a.x, D, ws + L.rinv, 1, M, D, part, a.g_gamma, s);
+      if (a.g_gamma) colsum(lc, a.gy, D, a.x, D, ws + L.rinv, 1, M, D, part, a.g_gamma);
       break;
     case BT_TRAIN_UNIT_HEAD: {
       if (!a.w1) return fail(fn, "null parameter");
       float* gbd = ws + L.small0;
       hipLaunchKernelGGL(head_bwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, a.gy, a.gy2, a.w1, M, D, a.sum_head, gbd, a.gx);
       if (a.g_w1)
-        for (int c = 0; c < 2; ++c) colsum(a.x, D, nullptr, 0, gbd + c, 2, M, D, part, a.g_w1 + (long)c * D, s);
-      if (a.g_b1) colsum(gbd, 2, nullptr, 0, nullptr, 0, M, 2, part, a.g_b1, s);
+        for (int c = 0; c < 2; ++c) colsum(lc, a.x, D, nullptr, 0, gbd + c, 2, M, D, part, a.g_w1 + (long)c * D);
+      if (a.g_b1) colsum(lc, gbd, 2, nullptr, 0, nullptr, 0, M, 2, part, a.g_b1);
       break;
     }
     case BT_UNIT_FF: {
@@ -982,23 +874,22 @@ static int train_backward(const char* fn, void* stream, int unit, const bt_train
       float* act = ws + L.b;
       mask_gy(BT_DROP_FF_OUT);
       hipLaunchKernelGGL(rms_fwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, M, D, xn, ws + L.rinv);
-      const DropSite hid = drop ? drop_site(dp->p, dp->seed, dp->stream, BT_DROP_FF_HIDDEN) : DropSite{};
-      linear_fwd(xn, a.w1, a.b1, M, HID, D, h, nullptr, act, s, drop ? &hid : nullptr, 1, mixed);
-      if (a.g_w2) linear_bwd_weight(gy, act, M, D, HID, part, a.g_w2, s, mixed);
-      if (a.g_b2) colsum(gy, D, nullptr, 0, nullptr, 0, M, D, part, a.g_b2, s);
-      linear_bwd_input(gy, a.w2, M, D, HID, act, false, s, mixed);                     // da over gelu(h)
+      linear_fwd(lc, xn, a.w1, a.b1, M, HID, D, h, nullptr, act, BT_DROP_FF_HIDDEN, 1);
+      if (a.g_w2) linear_bwd_weight(lc, gy, act, M, D, HID, part, a.g_w2);
+      if (a.g_b2) colsum(lc, gy, D, nullptr, 0, nullptr, 0, M, D, part, a.g_b2);
+      linear_bwd_input(lc, gy, a.w2, M, D, HID, act);                                    // da over gelu(h)
       if (!drop)
         hipLaunchKernelGGL(gelu_bwd_kernel, dim3(blocks_of(M * HID, 256)), dim3(256), 0, s, h, (const float*)act, M * HID);   // dh over h
       else
         hipLaunchKernelGGL(gelu_bwd_drop_kernel, dim3(blocks_of(M * HID / 4, 256)), dim3(256), 0, s, h, (const float*)act, M * HID / 4,
-                           hid);
-      if (a.g_w1) linear_bwd_weight(h, xn, M, HID, D, part, a.g_w1, s, mixed);
-      if (a.g_b1) colsum(h, HID, nullptr, 0, nullptr, 0, M, HID, part, a.g_b1, s);
+                           lc.site(BT_DROP_FF_HIDDEN));
+      if (a.g_w1) linear_bwd_weight(lc, h, xn, M, HID, D, part, a.g_w1);
+      if (a.g_b1) colsum(lc, h, HID, nullptr, 0, nullptr, 0, M, HID, part, a.g_b1);
       if (a.gx || a.g_gamma) {
-        linear_bwd_input(h, a.w1, M, HID, D, xn, false, s, mixed);                     // d xn over xn
+        linear_bwd_input(lc, h, a.w1, M, HID, D, xn);                                    // d xn over xn
         hipLaunchKernelGGL(rms_bwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, (const float*)xn, resid, M, D, a.gx,
                            ws + L.rinv);
-        if (a.g_gamma) colsum(xn, D, a.x, D, ws + L.rinv, 1, M, D, part, a.g_gamma, s);
+        if (a.g_gamma) colsum(lc, xn, D, a.x, D, ws + L.rinv, 1, M, D, part, a.g_gamma);
       }
       break;
     }
@@ -1014,30 +905,27 @@ static int train_backward(const char* fn, void* stream, int unit, const bt_train
       float* delta = ws + L.small1;
       float* dgl = ws + L.small2;
       mask_gy(BT_DROP_ATTN_OUT);
-      attn_prologue(a, L, ws, M, s, mixed);
+      attn_prologue(lc, a, L, ws, M);
       if (a.g_w3) {
         hipLaunchKernelGGL(gate_fwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o, (const float*)gl, M, D,
                            og);
-        linear_bwd_weight(gy, og, M, D, D, part, a.g_w3, s, mixed);
+        linear_bwd_weight(lc, gy, og, M, D, D, part, a.g_w3);
       }
-      linear_bwd_input(gy, a.w3, M, D, D, dO, false, s, mixed);                        // d og
+      linear_bwd_input(lc, gy, a.w3, M, D, D, dO);                                       // d og
       hipLaunchKernelGGL(gate_bwd_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, (const float*)a.save_o, (const float*)gl, dO, M,
                          D, delta, dgl);                                             // -> dO, delta, d gate logits
-      {
-        const DropSite pd = drop ? drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P) : DropSite{};
-        attn_bwd_sweeps(qkv, dO, a.save_lse, delta, a.B, a.T, D, dqkv, drop ? &pd : nullptr, s, mixed);
-      }
+      attn_bwd_sweeps(lc, qkv, dO, a.save_lse, delta, a.B, a.T, D, dqkv);
       hipLaunchKernelGGL(rope_kernel, dim3(blocks_of(M * D, 256)), dim3(256), 0, s, dqkv, a.rope, M, a.T, D, 1);
-      if (a.g_w1) linear_bwd_weight(dqkv, xn, M, 3 * D, D, part, a.g_w1, s, mixed);
-      if (a.g_w2) linear_bwd_weight(dgl, xn, M, H, D, part, a.g_w2, s, mixed);
-      if (a.g_b2) colsum(dgl, H, nullptr, 0, nullptr, 0, M, H, part, a.g_b2, s);
+      if (a.g_w1) linear_bwd_weight(lc, dqkv, xn, M, 3 * D, D, part, a.g_w1);
+      if (a.g_w2) linear_bwd_weight(lc, dgl, xn, M, H, D, part, a.g_w2);
+      if (a.g_b2) colsum(lc, dgl, H, nullptr, 0, nullptr, 0, M, H, part, a.g_b2);
       if (a.gx || a.g_gamma) {
         float* dxn = og;   // (the gated output is no longer needed)
-        linear_bwd_input(dqkv, a.w1, M, 3 * D, D, dxn, false, s, mixed);
-        linear_bwd_input(dgl, a.w2, M, H, D, dxn, true, s, mixed);
+        linear_bwd_input(lc, dqkv, a.w1, M, 3 * D, D, dxn);
+        linear_bwd_input(lc, dgl, a.w2, M, H, D, dxn, true);
         hipLaunchKernelGGL(rms_bwd_kernel, dim3(blocks_of(M, 4)), dim3(256), 0, s, a.x, a.gamma, (const float*)dxn, resid, M, D, a.gx,
                            ws + L.rinv);
-        if (a.g_gamma) colsum(dxn, D, a.x, D, ws + L.rinv, 1, M, D, part, a.g_gamma, s);
+        if (a.g_gamma) colsum(lc, dxn, D, a.x, D, ws + L.rinv, 1, M, D, part, a.g_gamma);
       }
       break;
     }
@@ -1070,28 +958,26 @@ int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B
   const char* fn = "bt_train_matmul_mixed";
   if (!A || !B || !C) return fail(fn, "null argument");
   if (form < 0 || form > 2) return fail(fn, "form must be 0 (A W^T), 1 (dY W) or 2 (dY^T A)");
-  if (M < 1 || N < 1 || K < 1 || M > (1 << 22) || N > (1 << 22) || K > (1 << 22)) return fail(fn, "need 1 <= M, N, K <= 2^22");
-  hipStream_t s = (hipStream_t)stream;
-  GemmP p{};
-  p.M = M; p.N = N; p.C = C; p.ldc = N;
+  if (const char* e = check_mnk(M, N, K)) return fail(fn, e);
+  const Launch lc{(hipStream_t)stream, true, nullptr};
   if (form == 0) {          // A [M, K], B [N, K]
-    p.A = A; p.lda = K; p.B = B; p.ldb = K; p.K = K; p.kchunk = K;
-    launch_mx_gemm<false, false>(p, 1, s);
+    linear_fwd(lc, A, B, nullptr, M, N, K, C, nullptr, nullptr);
   } else if (form == 1) {   // A [M, K], B [K, N]
-    p.A = A; p.lda = K; p.B = B; p.ldb = N; p.K = K; p.kchunk = K;
-    launch_mx_gemm<false, true>(p, 1, s);
-  } else {                  // A [K, M], B [K, N]: the chunks of BT_TRAIN_DW_ROWS summed rows, added in chunk order
+    linear_bwd_input(lc, A, B, M, K, N, C);
+  } else {                  // A [K, M], B [K, N]: the chunks of BT_TRAIN_DW_ROWS summed rows, added in place in chunk order
+    GemmP p{};
+    p.M = M; p.N = N; p.C = C; p.ldc = N;
     for (long k0 = 0; k0 < K; k0 += DW_ROWS) {
       p.A = A + k0 * M; p.lda = M; p.B = B + k0 * N; p.ldb = N;
       p.K = (int)std::min<long>(DW_ROWS, K - k0); p.kchunk = p.K; p.accum = k0 > 0;
-      launch_mx_gemm<true, true>(p, 1, s);
+      launch_gemm<true, true>(lc, p, 1);
     }
   }
   return finish(fn);
 }
 
 size_t bt_train_matmul_workspace_bytes(int form, int M, int N, int K) {
-  if (form != 2 || M < 1 || N < 1 || K < 1 || M > (1 << 22) || N > (1 << 22) || K > (1 << 22)) return 0;
+  if (form != 2 || check_mnk(M, N, K)) return 0;
   return (size_t)dw_chunks(K) * (size_t)M * (size_t)N * sizeof(float);
 }
 
@@ -1101,28 +987,23 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
   const char* fn = "bt_train_matmul";
   if (!A || !B || !C) return fail(fn, "null argument");
   if (form < 0 || form > 2) return fail(fn, "form must be 0 (A W^T), 1 (dY W) or 2 (dY^T A)");
-  if (M < 1 || N < 1 || K < 1 || M > (1 << 22) || N > (1 << 22) || K > (1 << 22)) return fail(fn, "need 1 <= M, N, K <= 2^22");
+  if (const char* e = check_mnk(M, N, K)) return fail(fn, e);
   if (form != 0 && (bias || resid || act || dp)) return fail(fn, "bias, resid, act and dropout belong to form 0");
   if (form == 2 && accum) return fail(fn, "form 2 overwrites C");
   bool drop = false;
-  if (dp) {
-    if (!(dp->p >= 0.0f && dp->p < 1.0f)) return fail(fn, "dropout p must satisfy 0 <= p < 1");
-    drop = dp->p > 0.0f;
-  }
+  if (const char* e = check_p(dp, &drop)) return fail(fn, e);
   if (drop && (site < BT_DROP_ATTN_OUT || site > BT_DROP_FF_OUT)) return fail(fn, "site must be one of the row sites of BT_DROP_*");
   if (drop && N % 4) return fail(fn, "with dropout N must be a multiple of 4");
   if (drop && drop_act && !act) return fail(fn, "drop_act masks act, which is null");
-  hipStream_t s = (hipStream_t)stream;
-  const bool mx = mixed != 0;
+  const Launch lc{(hipStream_t)stream, mixed != 0, drop ? dp : nullptr};
   if (form == 0) {          // A [M, K], B [N, K]
-    const DropSite ds = drop ? drop_site(dp->p, dp->seed, dp->stream, site) : DropSite{};
-    linear_fwd(A, B, bias, M, N, K, C, resid, act, s, drop ? &ds : nullptr, drop_act, mx, accum != 0);
+    linear_fwd(lc, A, B, bias, M, N, K, C, resid, act, site, drop_act, accum != 0);
   } else if (form == 1) {   // A [M, K], B [K, N]
-    linear_bwd_input(A, B, M, K, N, C, accum != 0, s, mx);
+    linear_bwd_input(lc, A, B, M, K, N, C, accum != 0);
   } else {                  // A [K, M], B [K, N]: partials of BT_TRAIN_DW_ROWS summed rows in ws, then added in chunk order
     if (!ws) return fail(fn, "form 2 needs a workspace");
     if (ws_bytes < bt_train_matmul_workspace_bytes(2, M, N, K)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
-    linear_bwd_weight(A, B, K, M, N, (float*)ws, C, s, mx);
+    linear_bwd_weight(lc, A, B, K, M, N, (float*)ws, C);
   }
   return finish(fn);
 }
@@ -1130,22 +1011,18 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
 int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int dim, const float* qkv,
                        const bt_train_dropout* dp, float* O, float* lse, const float* dO, const float* delta, float* dqkv) {
   const char* fn = "bt_train_attention";
-  if (dim < 32 || dim > 1024 || dim % 32) return fail(fn, "unsupported width (a multiple of 32 from 32 to 1024)");
+  if (const char* e = check_width(dim)) return fail(fn, e);
   if (B < 1 || B > 65535 || T < 1 || (long)B * T > (1L << 22)) return fail(fn, "need 1 <= B <= 65535, T >= 1 and B T <= 2^22");
   if (!qkv || !lse || (backward ? !dO || !delta || !dqkv : !O)) return fail(fn, "null argument");
   if ((uintptr_t)qkv % 16 || (backward ? (uintptr_t)dO % 16 || (uintptr_t)dqkv % 16 : (uintptr_t)O % 16))
     return fail(fn, "qkv, O, dO and dqkv must be 16-byte aligned");
   bool drop = false;
-  if (dp) {
-    if (!(dp->p >= 0.0f && dp->p < 1.0f)) return fail(fn, "dropout p must satisfy 0 <= p < 1");
-    drop = dp->p > 0.0f;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const DropSite pd = drop ? drop_site(dp->p, dp->seed, dp->stream, BT_DROP_ATTN_P) : DropSite{};
+  if (const char* e = check_p(dp, &drop)) return fail(fn, e);
+  const Launch lc{(hipStream_t)stream, mixed != 0, drop ? dp : nullptr};
   if (!backward)
-    attn_fwd_sweep(qkv, B, T, dim, O, lse, drop ? &pd : nullptr, s, mixed != 0);
+    attn_fwd_sweep(lc, qkv, B, T, dim, O, lse);
   else
-    attn_bwd_sweeps(qkv, dO, lse, delta, B, T, dim, dqkv, drop ? &pd : nullptr, s, mixed != 0);
+    attn_bwd_sweeps(lc, qkv, dO, lse, delta, B, T, dim, dqkv);
   return finish(fn);
 }
 

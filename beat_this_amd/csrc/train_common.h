@@ -1,0 +1,96 @@
+// What the fp32 kernels of train.hip and the 16-mixed kernels of train_mixed.inc share: the GEMM's parameter block and its
+// epilogue, the vector types, the attention's scale constants, GELU and the quad exchange of mask words.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+#include "dropout.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+constexpr float QK_SCALE = 0.17677669529663687f;            // 32^-0.5
+constexpr float QK_SCALE_LOG2E = 0.2550348616841918f;       // 32^-0.5 * log2(e)
+
+// ---- GEMM: C[m][n] (+)= sum_k A(m, k) B(n, k) over k in [z kchunk, (z + 1) kchunk) --------------------------------------
+// A(m, k) = AT ? A[k lda + m] : A[m lda + k];  B(n, k) = BT ? B[k ldb + n] : B[n ldb + k]
+struct GemmP {
+  const float* A; long lda;
+  const float* B; long ldb;
+  int M, N, K, kchunk;
+  float* C; long ldc; long cz;      // C of chunk z starts at C + z cz (C may be null when only act is wanted)
+  const float* bias;                // + bias[n]
+  const float* resid; long ldr;     // + resid[m][n]
+  int accum;                        // + the old C[m][n]
+  float* act; long ldact;           // act[m][n] = gelu(value)
+};
+
+__device__ inline float gelu_f(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+__device__ inline float gelu_grad_f(float v) {
+  return 0.5f * (1.0f + erff(v * 0.70710678118654752f)) + v * 0.3989422804014327f * expf(-0.5f * v * v);
+}
+
+// a[jj] of lane l of a quad of lanes (4 q .. 4 q + 3) becomes a[l mod 4] of lane 4 q + jj: a 4 x 4 transpose over three
+// exchanges.  Every lane of the quad has to be active.
+__device__ inline void quad_transpose(uint32_t (&a)[4], int lane) {
+  const int ql = lane & 3, qb = lane & ~3;
+  uint32_t b[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int give = (ql - s) & 3, from = (ql + s) & 3;
+    uint32_t v = give == 0 ? a[0] : give == 1 ? a[1] : give == 2 ? a[2] : a[3];
+    if (s) v = (uint32_t)__shfl((int)v, qb + from, 64);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[k] = from == k ? v : b[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) a[k] = b[k];
+}
+
+// The GEMMs' epilogue for one 32 x 32 MFMA tile (C / D map of the 32x32 MFMAs: register r of lane l is row
+// (r & 3) + 8 (r >> 2) + 4 (l >> 5)): rows rb .., this lane's column col, C the chunk's output or null.
+// DROP: the site `ds` over the [M][N] result (N a multiple of 4): drop_act == 0 masks the value before the residual is added
+// (C = resid + m c (acc + bias)), drop_act != 0 masks the second output (act = m c gelu(value)) and leaves C alone.  A lane
+// evaluates the groups of four of its sixteen rows and the quad exchanges the words, so every word of a call is used.
+template <bool DROP>
+__device__ inline void gemm_epilogue(const GemmP& p, const DropSite& ds, int drop_act, float* C, const f32x16& acc, long rb, long col,
+                                     int lane) {
+  if (col >= p.N) return;   // (DROP: N is a multiple of 4, the four lanes of a quad are all here or all gone)
+  const int g = lane >> 5;
+  const float b = p.bias ? p.bias[col] : 0.0f;
+  uint32_t words[16];
+  if constexpr (DROP) {
+#pragma unroll
+    for (int ri = 0; ri < 4; ++ri) {
+      const long row = rb + (lane & 3) + 8 * ri + 4 * g;
+      const PhiloxWords w = drop_words(ds, drop_row_group((uint64_t)row, (uint32_t)p.N, (uint32_t)col));
+      uint32_t q[4] = {w.w[0], w.w[1], w.w[2], w.w[3]};
+      quad_transpose(q, lane);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) words[4 * ri + jj] = q[jj];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const long row = rb + (r & 3) + 8 * (r >> 2) + 4 * g;
+    if (row < p.M) {
+      float v = acc[r] + b;
+      float keep = 1.0f;
+      if constexpr (DROP) {
+        keep = words[r] >= ds.thr ? ds.scale : 0.0f;
+        if (!drop_act) v *= keep;
+      }
+      if (p.resid) v += p.resid[row * p.ldr + col];
+      if (p.accum) v += C[row * p.ldc + col];
+      if (C) C[row * p.ldc + col] = v;
+      if (p.act) p.act[row * p.ldact + col] = DROP && drop_act ? gelu_f(v) * keep : gelu_f(v);
+    }
+  }
+}
+
+}  // namespace

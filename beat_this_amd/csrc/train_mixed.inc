@@ -1,4 +1,5 @@
-// The 16-mixed kernels of the training route (DESIGN.md section 16), included by train.hip inside its unnamed namespace.
+// The 16-mixed kernels of the training route (DESIGN.md section 16), included by train.hip; what they share with its fp32
+// kernels (GemmP, the GEMM epilogue, the vector types, the scale constants) is train_common.h.
 // THE CONTRACT: both operands of every matrix product are rounded to IEEE fp16 (round to nearest even) as they are staged, and
 // the product accumulates in fp32 on v_mfma_f32_32x32x16_f16.  Everything else of the route is the fp32 code of train.hip.  A
 // value beyond fp16's range becomes inf and propagates: nothing clamps, the loss scaler sees it in the gradient norm.
@@ -12,6 +13,10 @@
 // Reproducibility is that of train.hip: no atomics, one thread of one launch per output byte, every order of summation a
 // function of the shapes alone (a GEMM element: k ascending in MFMA steps of 16; dQ: key tiles of 32 ascending; dK / dV: query
 // tiles of 32 ascending), and a row's results do not depend on the other sequences of the batch.
+
+#include "train_common.h"
+
+namespace {
 
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
@@ -67,43 +72,6 @@ __device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k
 
 __device__ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// gemm_body's epilogue for one 32 x 32 MFMA tile: rows rb .., this lane's column col
-template <bool DROP>
-__device__ inline void mx_epilogue(const GemmP& p, const DropSite& ds, int drop_act, float* C, const f32x16& acc, long rb, long col,
-                                   int lane) {
-  if (col >= p.N) return;   // (DROP: N is a multiple of 4, the four lanes of a quad are all here or all gone)
-  const int g = lane >> 5;
-  const float b = p.bias ? p.bias[col] : 0.0f;
-  uint32_t words[16];
-  if constexpr (DROP) {
-#pragma unroll
-    for (int ri = 0; ri < 4; ++ri) {
-      const long row = rb + (lane & 3) + 8 * ri + 4 * g;
-      const PhiloxWords w = drop_words(ds, drop_row_group((uint64_t)row, (uint32_t)p.N, (uint32_t)col));
-      uint32_t q[4] = {w.w[0], w.w[1], w.w[2], w.w[3]};
-      quad_transpose(q, lane);
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) words[4 * ri + jj] = q[jj];
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const long row = rb + (r & 3) + 8 * (r >> 2) + 4 * g;
-    if (row < p.M) {
-      float v = acc[r] + b;
-      float keep = 1.0f;
-      if constexpr (DROP) {
-        keep = words[r] >= ds.thr ? ds.scale : 0.0f;
-        if (!drop_act) v *= keep;
-      }
-      if (p.resid) v += p.resid[row * p.ldr + col];
-      if (p.accum) v += C[row * p.ldc + col];
-      if (C) C[row * p.ldc + col] = v;
-      if (p.act) p.act[row * p.ldact + col] = DROP && drop_act ? gelu_f(v) * keep : gelu_f(v);
-    }
-  }
-}
-
 // gemm_body with fp16 operands: the same GemmP, the same epilogue (bias, residual, +=, GELU into a second output, dropout)
 template <bool AT, bool BT, bool DROP>
 __device__ inline void mx_gemm_body(const GemmP& p, const DropSite& ds, int drop_act) {
@@ -142,10 +110,10 @@ __device__ inline void mx_gemm_body(const GemmP& p, const DropSite& ds, int drop
     __syncthreads();
   }
   float* C = p.C ? p.C + (long)blockIdx.z * p.cz : nullptr;
-  mx_epilogue<DROP>(p, ds, drop_act, C, acc[0][0], m0 + wm * 64, n0 + wn * 64 + lr, lane);
-  mx_epilogue<DROP>(p, ds, drop_act, C, acc[0][1], m0 + wm * 64, n0 + wn * 64 + 32 + lr, lane);
-  mx_epilogue<DROP>(p, ds, drop_act, C, acc[1][0], m0 + wm * 64 + 32, n0 + wn * 64 + lr, lane);
-  mx_epilogue<DROP>(p, ds, drop_act, C, acc[1][1], m0 + wm * 64 + 32, n0 + wn * 64 + 32 + lr, lane);
+  gemm_epilogue<DROP>(p, ds, drop_act, C, acc[0][0], m0 + wm * 64, n0 + wn * 64 + lr, lane);
+  gemm_epilogue<DROP>(p, ds, drop_act, C, acc[0][1], m0 + wm * 64, n0 + wn * 64 + 32 + lr, lane);
+  gemm_epilogue<DROP>(p, ds, drop_act, C, acc[1][0], m0 + wm * 64 + 32, n0 + wn * 64 + lr, lane);
+  gemm_epilogue<DROP>(p, ds, drop_act, C, acc[1][1], m0 + wm * 64 + 32, n0 + wn * 64 + 32 + lr, lane);
 }
 
 template <bool AT, bool BT>
@@ -155,14 +123,6 @@ __global__ __launch_bounds__(256) void mx_gemm_kernel(const GemmP p) {
 
 __global__ __launch_bounds__(256) void mx_gemm_drop_kernel(const GemmP p, const DropSite ds, const int drop_act) {
   mx_gemm_body<false, false, true>(p, ds, drop_act);
-}
-
-dim3 mx_grid(const GemmP& p, int chunks) {
-  return dim3((unsigned)((p.N + MT - 1) / MT), (unsigned)((p.M + MT - 1) / MT), (unsigned)chunks);
-}
-
-template <bool AT, bool BT> void launch_mx_gemm(const GemmP& p, int chunks, hipStream_t s) {
-  hipLaunchKernelGGL((mx_gemm_kernel<AT, BT>), mx_grid(p, chunks), dim3(256), 0, s, p);
 }
 
 // ---- attention, head dim 32, one wave per workgroup: XB own rows against tiles of XB rows of the other side -------------------
@@ -417,3 +377,5 @@ __global__ __launch_bounds__(64) void mx_attn_dkv_drop_kernel(const float* qkv, 
                                                               int T, int D, float* dqkv, const DropSite ds) {
   mx_attn_dkv_body<true>(qkv, dO, lse, delta, T, D, dqkv, ds);
 }
+
+}  // namespace

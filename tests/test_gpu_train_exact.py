@@ -1,6 +1,7 @@
 """The training route's GEMMs and attention sweeps element by element, on the fp32 route and the 16-mixed one (csrc/train.hip,
 csrc/train_mixed.inc), through the raw diagnostic entries bt_train_matmul and bt_train_attention -- which launch through the
-host helpers the unit calls use (linear_fwd, linear_bwd_input, linear_bwd_weight, attn_fwd_sweep, attn_bwd_sweeps).
+host helpers the unit calls use (linear_fwd, linear_bwd_input, linear_bwd_weight, attn_fwd_sweep, attn_bwd_sweeps, each with the
+call's Launch context), and whose GEMMs share one epilogue (gemm_epilogue of csrc/train_common.h).
 
 1. Products of integers in [-8, 8]: every partial sum is an integer below 2^24, so C has to be the int64 product bit for bit
    whatever the order, on the fp32 MFMA as on the fp16 one -- the three forms at the edges of the 64-wide, 128-wide and 32-wide
