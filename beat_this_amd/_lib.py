@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "optim.hip", "engine.hip"]
+           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "engine.hip"]
 HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
@@ -134,6 +134,16 @@ class TrainDropout(C.Structure):   # bt_train_dropout
     _fields_ = [("p", C.c_float), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("stream", C.c_uint64)]
 
 
+class FrontArgs(C.Structure):   # bt_front_args
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("dim", C.c_int32),
+                ("reserved0", C.c_int32), ("reserved1", C.c_int32), ("reserved2", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p),
+                ("bn_w", C.c_void_p), ("bn_b", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p), ("bn1_w", C.c_void_p),
+                ("bn1_b", C.c_void_p), ("bn1_mean", C.c_void_p), ("bn1_var", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
+                ("save_pre", C.c_void_p), ("gy", C.c_void_p), ("gx", C.c_void_p), ("g_w", C.c_void_p), ("g_b", C.c_void_p),
+                ("g_bn_w", C.c_void_p), ("g_bn_b", C.c_void_p), ("g_bn1_w", C.c_void_p), ("g_bn1_b", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 class OptimTensor(C.Structure):   # bt_optim_tensor
     _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int64), ("group", C.c_int32), ("reserved", C.c_int32)]
 
@@ -158,6 +168,8 @@ class OptimHyper(C.Structure):   # bt_optim_hyper
 G3_FF1, G3_RESID, G3_QKV = 0, 1, 2
 UNIT_STEM, UNIT_PARTIAL, UNIT_CONV, UNIT_LINEAR, UNIT_ATTN, UNIT_FF, UNIT_NORM, UNIT_FRONT_ATTN, UNIT_FRONT_FF = range(9)
 TRAIN_UNIT_HEAD = 16                                        # BT_TRAIN_UNIT_HEAD
+FRONT_STEM, FRONT_CONV, FRONT_LINEAR, FRONT_SWAP = range(4)   # BT_FRONT_*: the frontend's own training units
+FRONT_MAX_FRAMES, FRONT_MAX_ROWS = 65535, 1 << 22           # limits of the frontend's training route: B T, B T 32
 TRAIN_DW_ROWS, TRAIN_CS_ROWS, TRAIN_ATTN_BLOCK = 1024, 64, 64   # BT_TRAIN_* tile edges (tests sit on both sides of them)
 DROP_ATTN_P, DROP_ATTN_OUT, DROP_FF_HIDDEN, DROP_FF_OUT = range(4)   # BT_DROP_*: the four sites of the training route's dropout
 OPTIM_CHUNK, OPTIM_NORM_SLICE = 4096, 4096                 # BT_OPTIM_CHUNK / _NORM_SLICE: elements per workgroup (likewise)
@@ -264,6 +276,10 @@ EXPORTS = {
                                   C.c_void_p, C.c_size_t]),
     "bt_train_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(TrainDropout),
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bt_front_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "bt_front_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bt_front_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontArgs)]),
+    "bt_front_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontArgs)]),
     "bt_optim_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "bt_optim_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
                                 C.c_int64, C.POINTER(C.c_int64)]),

@@ -1,0 +1,542 @@
+// Training forward and backward of the frontend's own units: everything of BeatThis.frontend that is
+// no attention / feed-forward leaf (those run on the unit code of train.hip):
+//   stem         y = gelu(bn2d(conv(4, 3)/(4, 1) of bn1d(x)))                    (beat_tracker.py:108-126)
+//   conv unit    y = gelu(norm(conv(2, 3)/(2, 1) of x)), three instances          (beat_tracker.py:155-166)
+//   swap         (b, t, f, c) <-> (b, f, t, c), the layout change between the two directions of a partial transformer
+//   projection   y = frontend.linear of "b c f t -> b t (c f)"                    (beat_tracker.py:71-76)
+// Activations are the library's (b, t, f, c), channels last, fp32; the parameters are read in the reference's layout straight
+// from the nn.Parameter storage and the gradients are written in that layout.  BatchNorm runs on its running statistics
+// (eval-mode arithmetic): s = weight / sqrt(var + 1e-5), sh = bias - mean s, evaluated in fp64 and rounded once, by a small
+// launch at the head of every call (into the call's workspace).
+//
+// The conv unit's three matrix products are implicit GEMMs on v_mfma_f32_32x32x2_f32: the operand tiles are staged into LDS
+// straight from the activation (a row of the implicit A matrix is three runs of 2 Cin floats at t - 1, t, t + 1, zeros
+// outside the sequence), no im2col buffer exists.  With rows m = (b, t, f') over the F' = F / 2 output bins:
+//   forward          pre [M, Cout]     = A [M, 6 Cin] W^T                  k = dt 2 Cin + df Cin + ci
+//   backward-data    gx  [M, 2 Cin]    = G [M, 3 Cout] W                   k = dt Cout + co; the 2 Cin columns of a row are the
+//                                                                           bins 2 f', 2 f' + 1 of gx (b, t, f, ci): the products
+//                                                                           of the M = B T F, N = Cin form, two rows at a time
+//   backward-weight  gW  [Cout, 6 Cin] = sum over rows of G^T A            partials per DW_ROWS rows, added in chunk order
+// The forward saves `pre` (the backward needs it for gelu' and for the gain's gradient and would otherwise repeat the GEMM);
+// the stem (K = 12, vector unit) recomputes it.
+//
+// Reproducibility, as in train.hip: no atomics; every output element is written by one thread of one launch; a GEMM element
+// sums k ascending; weight gradients over chunks of DW_ROWS rows and column sums over chunks of CS_ROWS rows, partials added in
+// chunk order by a second launch; a row's results depend on its own sequence only.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "../../include/beat_this_amd.h"
+#include "train_common.h"   // f32x16, gelu_f, gelu_grad_f
+
+int bt_set_error_external(int code, const char* msg);   // engine.hip (bt_last_error)
+
+namespace {
+
+constexpr int DW_ROWS = BT_TRAIN_DW_ROWS;
+constexpr int CS_ROWS = BT_TRAIN_CS_ROWS;
+constexpr int GT = 64;   // GEMM tile: GT x GT outputs, GK deep; four waves, one 32 x 32 MFMA tile each
+constexpr int GK = 16;
+constexpr int MEL = 128, STEM_C = 32, STEM_F = 32, STEM_TAPS = 12;
+
+unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
+int dw_chunks(long M) { return (int)((M + DW_ROWS - 1) / DW_ROWS); }
+int cs_chunks(long M) { return (int)((M + CS_ROWS - 1) / CS_ROWS); }
+
+// fold [4][C]: s, sh, 1 / sqrt(var + eps), mean
+__global__ __launch_bounds__(256) void bn_fold_kernel(const float* w, const float* b, const float* mean, const float* var, int C,
+                                                      float* fold) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const double rstd = 1.0 / sqrt((double)var[c] + 1e-5);
+  const double s = (double)w[c] * rstd;
+  fold[c] = (float)s;
+  fold[C + c] = (float)((double)b[c] - (double)mean[c] * s);
+  fold[2 * C + c] = (float)rstd;
+  fold[3 * C + c] = mean[c];
+}
+
+// part[chunk][j] = sum over the chunk's CS_ROWS rows of a[m][j], rows ascending
+__global__ __launch_bounds__(256) void front_colsum_kernel(const float* a, long M, int N, float* part) {
+  const int j = blockIdx.y * 256 + threadIdx.x;
+  if (j >= N) return;
+  const long mb = (long)blockIdx.x * CS_ROWS, me = std::min<long>(M, mb + CS_ROWS);
+  float acc = 0.0f;
+  for (long m = mb; m < me; ++m) acc += a[m * N + j];
+  part[(long)blockIdx.x * N + j] = acc;
+}
+
+__global__ __launch_bounds__(256) void front_reduce_kernel(const float* part, long n, int chunks, float* out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float acc = part[i];
+  for (int c = 1; c < chunks; ++c) acc += part[(long)c * n + i];
+  out[i] = acc;
+}
+
+void colsum(hipStream_t s, const float* a, long M, int N, float* part, float* out) {
+  const int chunks = cs_chunks(M);
+  hipLaunchKernelGGL(front_colsum_kernel, dim3((unsigned)chunks, blocks_of(N, 256)), dim3(256), 0, s, a, M, N, part);
+  hipLaunchKernelGGL(front_reduce_kernel, dim3(blocks_of(N, 256)), dim3(256), 0, s, (const float*)part, (long)N, chunks, out);
+}
+
+// ---- conv unit -------------------------------------------------------------------------------------------------------------
+struct ConvP {
+  const float* x;      // [B, T, F, Cin] = [M, 2 Cin]
+  const float* w;      // [Cout][Cin][2][3]
+  const float* g;      // g_pre [M, Cout]
+  const float* fold;   // [4][Cout]
+  float* out;
+  float* out2;
+  int T, Fo, Cin, Cout;
+  long M;              // B T Fo
+};
+
+// implicit A of the forward: row m = (b, t, fo), column k = dt 2 Cin + (df Cin + ci); zeros at t + dt - 1 outside [0, T)
+__device__ inline float conv_a(const ConvP& p, long m, int k) {
+  const int C2 = 2 * p.Cin, dt = k / C2, j = k - dt * C2;
+  const int t = (int)((m / p.Fo) % p.T) + dt - 1;
+  return t >= 0 && t < p.T ? p.x[(m + (long)(dt - 1) * p.Fo) * C2 + j] : 0.0f;
+}
+// implicit A of the backward-data: g_conv = g_pre s of row (b, t - (dt - 1), fo), column k = dt Cout + co
+__device__ inline float conv_g(const ConvP& p, long m, int k) {
+  const int dt = k / p.Cout, co = k - dt * p.Cout;
+  const int t = (int)((m / p.Fo) % p.T) - (dt - 1);
+  return t >= 0 && t < p.T ? p.g[(m - (long)(dt - 1) * p.Fo) * p.Cout + co] * p.fold[co] : 0.0f;
+}
+// W[co][ci][df][dt] for j = df Cin + ci
+__device__ inline float conv_w(const ConvP& p, int co, int j, int dt) {
+  const int df = j / p.Cin, ci = j - df * p.Cin;
+  return p.w[((long)co * p.Cin + ci) * 6 + df * 3 + dt];
+}
+
+// MODE 0: forward, 1: backward-data, 2: backward-weight (blockIdx.z = chunk of DW_ROWS rows)
+template <int MODE>
+__global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvP p) {
+  __shared__ float As[GK][GT + 4];
+  __shared__ float Bs[GK][GT + 4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 5, lr = lane & 31, wm = wave >> 1, wn = wave & 1;
+  const int C2 = 2 * p.Cin;
+  const long GM = MODE == 2 ? (long)p.Cout : p.M;
+  const int GN = MODE == 0 ? p.Cout : MODE == 1 ? C2 : 3 * C2;
+  const long kb = MODE == 2 ? (long)blockIdx.z * DW_ROWS : 0;
+  const long ke = MODE == 0 ? 3L * C2 : MODE == 1 ? 3L * p.Cout : std::min<long>(p.M, kb + DW_ROWS);
+  const long m0 = (long)blockIdx.y * GT;
+  const int n0 = blockIdx.x * GT;
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  for (long k0 = kb; k0 < ke; k0 += GK) {
+#pragma unroll
+    for (int i = 0; i < GT * GK / 256; ++i) {
+      const int e = tid + i * 256;
+      // MODE 0 / 1: the k index runs fastest (a row of A is contiguous in k); MODE 2: the tile's row / column does
+      const int kk = MODE == 2 ? e / GT : e % GK, mn = MODE == 2 ? e % GT : e / GK;
+      const long gk = k0 + kk, gm = m0 + mn;
+      const int gn = n0 + mn;
+      float a = 0.0f, b = 0.0f;
+      if (gk < ke) {
+        if (gm < GM) {
+          if (MODE == 0) a = conv_a(p, gm, (int)gk);
+          if (MODE == 1) a = conv_g(p, gm, (int)gk);
+          if (MODE == 2) a = p.g[gk * p.Cout + gm] * p.fold[gm];
+        }
+        if (gn < GN) {
+          if (MODE == 0) b = conv_w(p, gn, (int)gk % C2, (int)gk / C2);
+          if (MODE == 1) b = conv_w(p, (int)gk % p.Cout, gn, (int)gk / p.Cout);
+          if (MODE == 2) b = conv_a(p, gk, gn);
+        }
+      }
+      As[kk][mn] = a;
+      Bs[kk][mn] = b;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < GK; kk += 2)
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + g][wm * 32 + lr], Bs[kk + g][wn * 32 + lr], acc, 0, 0, 0);
+    __syncthreads();
+  }
+  const int col = n0 + wn * 32 + lr;
+  if (col >= GN) return;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {   // (C / D map of the 32x32 MFMAs: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5))
+    const long row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+    if (row >= GM) continue;
+    if (MODE == 0) {
+      p.out[row * p.Cout + col] = acc[r];
+      p.out2[row * p.Cout + col] = gelu_f(p.fold[col] * acc[r] + p.fold[p.Cout + col]);
+    } else if (MODE == 1) {
+      p.out[row * C2 + col] = acc[r];
+    } else {
+      p.out[((long)blockIdx.z * p.Cout + row) * (3 * C2) + col] = acc[r];
+    }
+  }
+}
+
+// gw [Cout][Cin][2][3] = the partials [chunk][Cout][dt 2 Cin + df Cin + ci] added in chunk order
+__global__ __launch_bounds__(256) void conv_dw_reduce_kernel(const float* part, int Cout, int Cin, int chunks, float* gw) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Cout * Cin * 6) return;
+  const int dt = i % 3, df = (i / 3) % 2, ci = (i / 6) % Cin, co = i / (6 * Cin);
+  const int k = dt * 2 * Cin + df * Cin + ci;
+  const long n = (long)Cout * 6 * Cin;
+  float acc = part[(long)co * 6 * Cin + k];
+  for (int c = 1; c < chunks; ++c) acc += part[c * n + (long)co * 6 * Cin + k];
+  gw[i] = acc;
+}
+
+// gp = gy gelu'(s pre + sh), gh = gp (pre - mean) / sqrt(var + eps)
+__global__ __launch_bounds__(256) void conv_gpre_kernel(const float* pre, const float* gy, const float* fold, long n, int C, float* gp,
+                                                        float* gh) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = (int)(i % C);
+  const float v = pre[i];
+  const float gv = gy[i] * gelu_grad_f(fold[c] * v + fold[C + c]);
+  gp[i] = gv;
+  gh[i] = gv * ((v - fold[3 * C + c]) * fold[2 * C + c]);
+}
+
+// ---- stem: bn1d, conv 1 -> 32 channels (4, 3) / (4, 1), bn2d, GELU; K = 12, on the vector unit --------------------------------
+__device__ inline float stem_xn(const float* x, const float* f1, long bt, int f) { return x[bt * MEL + f] * f1[f] + f1[MEL + f]; }
+
+// pre of (row bt = b T + t, fo, co): taps dt ascending, df ascending inside
+__device__ inline float stem_pre(const float* x, const float* w, const float* f1, int T, long bt, int fo, int co) {
+  const int t = (int)(bt % T);
+  float acc = 0.0f;
+#pragma unroll
+  for (int dt = 0; dt < 3; ++dt) {
+    const int tt = t + dt - 1;
+    if (tt < 0 || tt >= T) continue;
+#pragma unroll
+    for (int df = 0; df < 4; ++df) acc = fmaf(w[co * STEM_TAPS + df * 3 + dt], stem_xn(x, f1, bt + dt - 1, 4 * fo + df), acc);
+  }
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void stem_fwd_kernel(const float* x, const float* w, const float* f1, const float* f2, long BT, int T,
+                                                       float* y) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= BT * STEM_F * STEM_C) return;
+  const int co = (int)(i % STEM_C), fo = (int)((i / STEM_C) % STEM_F);
+  const float pre = stem_pre(x, w, f1, T, i / (STEM_F * STEM_C), fo, co);
+  y[i] = gelu_f(f2[co] * pre + f2[STEM_C + co]);
+}
+
+__global__ __launch_bounds__(256) void stem_gpre_kernel(const float* x, const float* w, const float* f1, const float* f2,
+                                                        const float* gy, long BT, int T, float* gp, float* gh) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= BT * STEM_F * STEM_C) return;
+  const int co = (int)(i % STEM_C), fo = (int)((i / STEM_C) % STEM_F);
+  const float pre = stem_pre(x, w, f1, T, i / (STEM_F * STEM_C), fo, co);
+  const float gv = gy[i] * gelu_grad_f(f2[co] * pre + f2[STEM_C + co]);
+  gp[i] = gv;
+  gh[i] = gv * ((pre - f2[3 * STEM_C + co]) * f2[2 * STEM_C + co]);
+}
+
+// part[chunk][co][df][dt] = sum over the chunk's DW_ROWS rows (b, t, fo) of g_conv[row][co] xn(b, t + dt - 1, 4 fo + df)
+__global__ __launch_bounds__(STEM_C * STEM_TAPS) void stem_dw_kernel(const float* x, const float* f1, const float* f2, const float* gp,
+                                                                     long M, int T, float* part) {
+  const int co = threadIdx.x % STEM_C, tap = threadIdx.x / STEM_C, df = tap / 3, dt = tap % 3;
+  const long mb = (long)blockIdx.x * DW_ROWS, me = std::min<long>(M, mb + DW_ROWS);
+  const float s = f2[co];
+  float acc = 0.0f;
+  for (long m = mb; m < me; ++m) {
+    const long bt = m / STEM_F;
+    const int fo = (int)(m % STEM_F), tt = (int)(bt % T) + dt - 1;
+    const float xn = tt >= 0 && tt < T ? stem_xn(x, f1, bt + dt - 1, 4 * fo + df) : 0.0f;
+    acc = fmaf(gp[m * STEM_C + co] * s, xn, acc);
+  }
+  part[((long)blockIdx.x * STEM_C + co) * STEM_TAPS + tap] = acc;
+}
+
+// gradient of the bn1d output, per (b, t, f): gxn; ghn = gxn (x - mean) / sqrt(var + eps); gx = gxn s (gx may be null)
+__global__ __launch_bounds__(256) void stem_dx_kernel(const float* x, const float* w, const float* f1, const float* f2, const float* gp,
+                                                      long BT, int T, float* gxn, float* ghn, float* gx) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= BT * MEL) return;
+  const int f = (int)(i % MEL), fo = f >> 2, df = f & 3;
+  const long bt = i / MEL;
+  const int t = (int)(bt % T);
+  float acc = 0.0f;
+#pragma unroll
+  for (int dt = 0; dt < 3; ++dt) {
+    const int tt = t - (dt - 1);
+    if (tt < 0 || tt >= T) continue;
+    const float* gr = gp + ((bt - (dt - 1)) * STEM_F + fo) * STEM_C;
+    for (int co = 0; co < STEM_C; ++co) acc = fmaf(w[co * STEM_TAPS + df * 3 + dt] * f2[co], gr[co], acc);
+  }
+  gxn[i] = acc;
+  ghn[i] = acc * ((x[i] - f1[3 * MEL + f]) * f1[2 * MEL + f]);
+  if (gx) gx[i] = acc * f1[f];
+}
+
+// ---- layout: y[b][q][p][c] = x[b][p][q][c] ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void swap_kernel(const float* x, long n, int P, int Q, int C, float* y) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;   // index into y
+  if (i >= n) return;
+  const int c = (int)(i % C);
+  const long r = i / C;
+  const int p = (int)(r % P), q = (int)((r / P) % Q);
+  const long b = r / ((long)P * Q);
+  y[i] = x[((b * P + p) * Q + q) * C + c];
+}
+
+void swap(hipStream_t s, const float* x, long B, int P, int Q, int C, float* y) {
+  const long n = B * P * Q * C;
+  hipLaunchKernelGGL(swap_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, x, n, P, Q, C, y);
+}
+
+// ---- workspace layouts (floats; every region a multiple of 64 floats) ---------------------------------------------------------
+size_t up64(size_t n) { return (n + 63) / 64 * 64; }
+
+struct Layout {
+  size_t fold, fold1, a, b, c, d, part, total;
+};
+
+Layout layout(int unit, int backward, long BT, int F, int C, int dim) {
+  Layout L{};
+  size_t at = 0;
+  auto take = [&](size_t n) { const size_t o = at; at += up64(n); return o; };
+  switch (unit) {
+    case BT_FRONT_STEM: {
+      const size_t M = (size_t)BT * STEM_F;
+      L.fold1 = take(4 * MEL);
+      L.fold = take(4 * STEM_C);
+      if (backward) {
+        L.a = take(M * STEM_C);          // g_pre
+        L.b = take(M * STEM_C);          // g_pre xhat
+        L.c = take((size_t)BT * MEL);    // gradient of the bn1d output
+        L.d = take((size_t)BT * MEL);    // the same times xhat
+        L.part = take(std::max({(size_t)dw_chunks(M) * STEM_C * STEM_TAPS, (size_t)cs_chunks(M) * STEM_C, (size_t)cs_chunks(BT) * MEL}));
+      }
+      break;
+    }
+    case BT_FRONT_CONV: {
+      const size_t M = (size_t)BT * (F / 2), Cout = 2 * (size_t)C;
+      L.fold = take(4 * Cout);
+      if (backward) {
+        L.a = take(M * Cout);            // g_pre
+        L.b = take(M * Cout);            // g_pre xhat
+        L.part = take(std::max((size_t)dw_chunks(M) * Cout * 6 * C, (size_t)cs_chunks(M) * Cout));
+      }
+      break;
+    }
+    case BT_FRONT_LINEAR: {
+      const size_t K = (size_t)F * C;
+      L.a = take((size_t)BT * K);        // the input in the weight's column order (c f)
+      if (backward) {
+        L.b = take((size_t)BT * K);      // its gradient
+        L.part = take(std::max(bt_train_matmul_workspace_bytes(2, dim, (int)K, (int)BT) / sizeof(float), (size_t)cs_chunks(BT) * dim));
+      }
+      break;
+    }
+    default:
+      break;
+  }
+  L.total = std::max<size_t>(at, 64);
+  return L;
+}
+
+const char* check_shape(int unit, int B, int T, int F, int C, int dim) {
+  if (unit < BT_FRONT_STEM || unit > BT_FRONT_SWAP) return "unit must be BT_FRONT_STEM, _CONV, _LINEAR or _SWAP";
+  if (B < 1 || T < 1) return "need B >= 1 and T >= 1";
+  if (unit == BT_FRONT_SWAP)   // (serves both directions: T and F are the two swapped extents, whichever is the time)
+    return F < 1 || F > (1 << 22) || C < 1 || C > 1024 || (long)B * T > (1L << 22) || (long)B * T * F > (1L << 22)
+               ? "the swap needs F >= 1, 1 <= C <= 1024 and B T F <= 2^22 rows"
+               : nullptr;
+  if ((long)B * T > 65535) return "more than 65535 frames (B T): the frequency direction runs one sequence per frame";
+  if ((long)B * T * 32 > (1L << 22)) return "more than 2^22 rows (B T 32)";
+  switch (unit) {
+    case BT_FRONT_STEM:
+      if (F != MEL || C != STEM_C) return "the stem takes F = 128 mel bins and writes C = 32 channels";
+      break;
+    case BT_FRONT_CONV:
+      if (F < 2 || F > 32 || F % 2 || C < 32 || C > 512 || C % 32) return "the conv unit needs an even F <= 32 and C a multiple of 32 up to 512";
+      break;
+    case BT_FRONT_LINEAR:
+      if (F < 1 || F > 32 || C < 32 || C > 1024 || C % 32 || dim < 32 || dim > 1024 || dim % 32)
+        return "the projection needs 1 <= F <= 32 and C, dim multiples of 32 up to 1024";
+      break;
+    default:
+      break;
+  }
+  return nullptr;
+}
+
+int fail(const char* fn, const char* msg, int code = BT_ERR_ARG) {
+  return bt_set_error_external(code, (std::string(fn) + ": " + msg).c_str());
+}
+
+int finish(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(fn, hipGetErrorString(e), BT_ERR_HIP);
+  return BT_OK;
+}
+
+void fold(hipStream_t s, const float* w, const float* b, const float* mean, const float* var, int C, float* out) {
+  hipLaunchKernelGGL(bn_fold_kernel, dim3(blocks_of(C, 256)), dim3(256), 0, s, w, b, mean, var, C, out);
+}
+
+dim3 conv_grid(long GM, int GN, int chunks) { return dim3(blocks_of(GN, GT), blocks_of(GM, GT), (unsigned)chunks); }
+
+}  // namespace
+
+extern "C" {
+
+void bt_front_struct_sizes(int32_t* out) {
+  out[0] = (int32_t)sizeof(bt_front_args);
+  out[1] = (int32_t)offsetof(bt_front_args, w);
+  out[2] = (int32_t)offsetof(bt_front_args, x);
+  out[3] = (int32_t)offsetof(bt_front_args, gy);
+  out[4] = (int32_t)offsetof(bt_front_args, gx);
+  out[5] = (int32_t)offsetof(bt_front_args, ws);
+  out[6] = (int32_t)offsetof(bt_front_args, ws_bytes);
+}
+
+size_t bt_front_workspace_bytes(int unit, int backward, int B, int T, int F, int C, int dim) {
+  if (check_shape(unit, B, T, F, C, dim)) return 0;
+  return layout(unit, backward != 0, (long)B * T, F, C, dim).total * sizeof(float);
+}
+
+int bt_front_forward(void* stream, int unit, const bt_front_args* ap) {
+  const char* fn = "bt_front_forward";
+  if (!ap) return fail(fn, "null argument");
+  const bt_front_args& a = *ap;
+  if (const char* e = check_shape(unit, a.B, a.T, a.F, a.C, a.dim)) return fail(fn, e);
+  const long BT = (long)a.B * a.T;
+  const Layout L = layout(unit, 0, BT, a.F, a.C, a.dim);
+  if (!a.x || !a.y || !a.ws) return fail(fn, "null x, y or workspace");
+  if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)a.ws;
+  switch (unit) {
+    case BT_FRONT_STEM: {
+      if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.bn1_w || !a.bn1_b || !a.bn1_mean || !a.bn1_var)
+        return fail(fn, "null parameter");
+      fold(s, a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, MEL, ws + L.fold1);
+      fold(s, a.bn_w, a.bn_b, a.bn_mean, a.bn_var, STEM_C, ws + L.fold);
+      hipLaunchKernelGGL(stem_fwd_kernel, dim3(blocks_of(BT * STEM_F * STEM_C, 256)), dim3(256), 0, s, a.x, a.w,
+                         (const float*)(ws + L.fold1), (const float*)(ws + L.fold), BT, a.T, a.y);
+      break;
+    }
+    case BT_FRONT_CONV: {
+      if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.save_pre) return fail(fn, "null parameter or saved-tensor pointer");
+      const int Cout = 2 * a.C;
+      fold(s, a.bn_w, a.bn_b, a.bn_mean, a.bn_var, Cout, ws + L.fold);
+      ConvP p{a.x, a.w, nullptr, ws + L.fold, a.save_pre, a.y, a.T, a.F / 2, a.C, Cout, BT * (a.F / 2)};
+      hipLaunchKernelGGL(conv_gemm_kernel<0>, conv_grid(p.M, Cout, 1), dim3(256), 0, s, p);
+      break;
+    }
+    case BT_FRONT_LINEAR: {
+      if (!a.w || !a.b) return fail(fn, "null parameter");
+      const int K = a.F * a.C;
+      swap(s, a.x, BT, a.F, a.C, 1, ws + L.a);   // (f c) -> (c f)
+      if (int rc = bt_train_matmul(stream, 0, 0, ws + L.a, a.w, (int)BT, a.dim, K, a.y, a.b, nullptr, 0, nullptr, nullptr, 0, 0,
+                                   nullptr, 0))
+        return rc;
+      break;
+    }
+    default:
+      swap(s, a.x, a.B, a.T, a.F, a.C, a.y);
+      break;
+  }
+  return finish(fn);
+}
+
+int bt_front_backward(void* stream, int unit, const bt_front_args* ap) {
+  const char* fn = "bt_front_backward";
+  if (!ap) return fail(fn, "null argument");
+  const bt_front_args& a = *ap;
+  if (const char* e = check_shape(unit, a.B, a.T, a.F, a.C, a.dim)) return fail(fn, e);
+  const long BT = (long)a.B * a.T;
+  const Layout L = layout(unit, 1, BT, a.F, a.C, a.dim);
+  if (!a.gy || !a.ws) return fail(fn, "null upstream gradient or workspace");
+  if (unit != BT_FRONT_SWAP && !a.x) return fail(fn, "null x");
+  if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)a.ws;
+  switch (unit) {
+    case BT_FRONT_STEM: {
+      if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.bn1_w || !a.bn1_b || !a.bn1_mean || !a.bn1_var)
+        return fail(fn, "null parameter");
+      const long M = BT * STEM_F;
+      const float* f1 = ws + L.fold1;
+      const float* f2 = ws + L.fold;
+      fold(s, a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, MEL, ws + L.fold1);
+      fold(s, a.bn_w, a.bn_b, a.bn_mean, a.bn_var, STEM_C, ws + L.fold);
+      hipLaunchKernelGGL(stem_gpre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, a.gy, BT, a.T,
+                         ws + L.a, ws + L.b);
+      if (a.g_bn_b) colsum(s, ws + L.a, M, STEM_C, ws + L.part, a.g_bn_b);
+      if (a.g_bn_w) colsum(s, ws + L.b, M, STEM_C, ws + L.part, a.g_bn_w);
+      if (a.g_w) {
+        const int chunks = dw_chunks(M);
+        hipLaunchKernelGGL(stem_dw_kernel, dim3((unsigned)chunks), dim3(STEM_C * STEM_TAPS), 0, s, a.x, f1, f2,
+                           (const float*)(ws + L.a), M, a.T, ws + L.part);
+        hipLaunchKernelGGL(front_reduce_kernel, dim3(blocks_of(STEM_C * STEM_TAPS, 256)), dim3(256), 0, s, (const float*)(ws + L.part),
+                           (long)STEM_C * STEM_TAPS, chunks, a.g_w);
+      }
+      if (a.gx || a.g_bn1_w || a.g_bn1_b) {
+        hipLaunchKernelGGL(stem_dx_kernel, dim3(blocks_of(BT * MEL, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, (const float*)(ws + L.a),
+                           BT, a.T, ws + L.c, ws + L.d, a.gx);
+        if (a.g_bn1_b) colsum(s, ws + L.c, BT, MEL, ws + L.part, a.g_bn1_b);
+        if (a.g_bn1_w) colsum(s, ws + L.d, BT, MEL, ws + L.part, a.g_bn1_w);
+      }
+      break;
+    }
+    case BT_FRONT_CONV: {
+      if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.save_pre) return fail(fn, "null parameter or saved-tensor pointer");
+      const int Cout = 2 * a.C, Fo = a.F / 2;
+      const long M = BT * Fo;
+      fold(s, a.bn_w, a.bn_b, a.bn_mean, a.bn_var, Cout, ws + L.fold);
+      hipLaunchKernelGGL(conv_gpre_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, (const float*)a.save_pre, a.gy,
+                         (const float*)(ws + L.fold), M * Cout, Cout, ws + L.a, ws + L.b);
+      if (a.g_bn_b) colsum(s, ws + L.a, M, Cout, ws + L.part, a.g_bn_b);
+      if (a.g_bn_w) colsum(s, ws + L.b, M, Cout, ws + L.part, a.g_bn_w);
+      ConvP p{a.x, a.w, ws + L.a, ws + L.fold, nullptr, nullptr, a.T, Fo, a.C, Cout, M};
+      if (a.gx) {
+        p.out = a.gx;
+        hipLaunchKernelGGL(conv_gemm_kernel<1>, conv_grid(M, 2 * a.C, 1), dim3(256), 0, s, p);
+      }
+      if (a.g_w) {
+        const int chunks = dw_chunks(M);
+        p.out = ws + L.part;
+        hipLaunchKernelGGL(conv_gemm_kernel<2>, conv_grid(Cout, 6 * a.C, chunks), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3(blocks_of((long)Cout * 6 * a.C, 256)), dim3(256), 0, s,
+                           (const float*)(ws + L.part), Cout, a.C, chunks, a.g_w);
+      }
+      break;
+    }
+    case BT_FRONT_LINEAR: {
+      if (!a.w) return fail(fn, "null parameter");
+      const int K = a.F * a.C;
+      if (a.g_b) colsum(s, a.gy, BT, a.dim, ws + L.part, a.g_b);
+      if (a.g_w) {
+        swap(s, a.x, BT, a.F, a.C, 1, ws + L.a);
+        if (int rc = bt_train_matmul(stream, 0, 2, a.gy, ws + L.a, a.dim, K, (int)BT, a.g_w, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
+                                     ws + L.part, (L.total - L.part) * sizeof(float)))
+          return rc;
+      }
+      if (a.gx) {
+        if (int rc = bt_train_matmul(stream, 0, 1, a.gy, a.w, (int)BT, K, a.dim, ws + L.b, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
+                                     nullptr, 0))
+          return rc;
+        swap(s, ws + L.b, BT, a.C, a.F, 1, a.gx);   // (c f) -> (f c)
+      }
+      break;
+    }
+    default:   // y = swap(x) over (T, F): gx = the swap over (F, T) of gy
+      if (!a.gx) return fail(fn, "null gx");
+      swap(s, a.gy, a.B, a.F, a.T, a.C, a.gx);
+      break;
+  }
+  return finish(fn);
+}
+
+}  // extern "C"

@@ -10,8 +10,8 @@ follows the caller exactly like the reference: under ``torch.autocast`` (what
 an fp32-class path: exact fp32 MFMAs, or -- ``fp32_split_gemms``, what the inference classes select for
 ``float16=False`` -- three fp16 MFMAs per product on hi + lo operand halves.  There is no CPU implementation here.
 
-Fine-tuning: the main transformer layers, the final RMSNorm and the task heads are differentiable (``backward.py``); see the
-``BeatThis`` class docstring.
+Fine-tuning: the main transformer layers, the final RMSNorm and the task heads are differentiable (``backward.py``), and with
+``set_frontend_trainable()`` the frontend is too; see the ``BeatThis`` class docstring.
 """
 from __future__ import annotations
 
@@ -113,6 +113,8 @@ class _Stage(_Node):
     def forward(self, x: torch.Tensor):
         root = self._root()
         if self._stage == 0:
+            if root._frontend_route():
+                return root._frontend_train(x)
             root._refuse_trainable_frontend()
         elif root._differentiable(x, self):
             # the differentiable route (backward.py): the reference's container loop over the units / the head
@@ -197,10 +199,23 @@ class BeatThis(_TracksChildren, nn.Module):
         attention / feed-forward call that drops takes the next stream number from a counter (``dropout_state()``), which
         ``set_dropout_state()`` rewinds to repeat a run bit for bit.  A graph capture with dropout active raises
         ``RuntimeError`` (a replay would repeat its masks).  ``dropout["frontend"]`` is unused: the frozen frontend always
-        runs the inference path;
+        runs the inference path and the differentiable one runs without dropout;
       * ``rotary_embed.freqs`` never receives a gradient, as in the reference;
-      * the frontend is frozen in this version: a frontend parameter that requires grad makes a grad-mode forward raise
-        ``NotImplementedError`` rather than silently leaving its ``.grad`` empty;
+      * the frontend is frozen unless ``set_frontend_trainable()`` was called: without that opt-in a frontend parameter that
+        requires grad makes a grad-mode forward raise ``NotImplementedError`` rather than silently leaving its ``.grad`` empty
+        (the opt-in is never inferred from ``requires_grad``);
+      * ``set_frontend_trainable()`` -- whole-model fine-tuning: it sets ``requires_grad`` on the frontend's
+        weights and, in grad mode, ``model(x)`` and ``model.frontend(x)`` run the frontend on the differentiable route too (the
+        stem, the three conv units, the projection and the twelve attention / feed-forward leaves of the partial transformers);
+        gradients also reach ``x`` when it requires grad.  That part of the route is fp32 under ``"32-true"`` and ``"16-mixed"``
+        alike (only the trunk's units go mixed); it runs WITHOUT dropout even after ``enable_dropout`` (``dropout["frontend"]``
+        stays unused); and its BatchNorm statistics are frozen: every BatchNorm uses ``running_mean`` / ``running_var``, in
+        ``train()`` as in ``eval()``, and those buffers and ``num_batches_tracked`` never receive a gradient and are never
+        updated.  The callable nodes below ``frontend`` (``stem``, ``blocks[i]``, ``.partial``, ``.linear`` ...) stay
+        inference-only, and the route does not pass through them: forward hooks registered BELOW ``frontend`` do not fire on a
+        grad-mode call with the flag set (hooks on ``frontend`` itself and on the trunk's nodes do; under ``no_grad`` all fire as
+        ever).  ``set_frontend_trainable(False)`` restores the frozen state and drops the engine's packed copies, so the frozen
+        frontend runs on the weights as trained;
       * parameters on the CPU raise the same ``RuntimeError`` as ever.
     The route reads the parameters' storage at call time, so an optimizer step is seen at once.  The inference paths run on
     packed copies: the ``_version`` of every parameter is recorded when they are packed, and a parameter that requires grad
@@ -224,6 +239,7 @@ class BeatThis(_TracksChildren, nn.Module):
         self.dropout = dict(dropout)
         self._dropout_rng = None     # enable_dropout(): {"seed", "calls"}
         self._train_precision = "32-true"
+        self._frontend_trainable = False   # set_frontend_trainable()
         self._engine = None
         self._packed_versions = ()   # (is frontend, parameter, its _version when the engine was packed)
         # outside autocast: True = every product of the forward on three half MFMAs over hi + lo operand halves
@@ -322,6 +338,39 @@ class BeatThis(_TracksChildren, nn.Module):
             if p.requires_grad:
                 return True
         return False
+
+    # -- whole-model fine-tuning: the differentiable frontend -----------------------------------------------
+    def set_frontend_trainable(self, flag: bool = True) -> "BeatThis":
+        """The opt-in to the differentiable frontend: ``requires_grad`` of the frontend's weights (not of the rotary tables;
+        ``running_mean``, ``running_var`` and ``num_batches_tracked`` are buffers and stay what they are) becomes ``flag``,
+        and with ``flag`` set a grad-mode ``model(x)`` / ``model.frontend(x)`` runs the frontend on the differentiable route.
+        ``False`` restores the frozen state."""
+        flag = bool(flag)
+        for name, p in self.frontend.named_parameters():
+            p.requires_grad_(flag and not name.endswith("rotary_embed.freqs"))
+        self._frontend_trainable = flag
+        # the re-pack check looks at parameters that require grad only: frontend weights trained under the flag and frozen again
+        # would stay on the engine's old packed copies, so the engine is packed anew on its next use
+        self._engine = None
+        return self
+
+    @property
+    def frontend_trainable(self) -> bool:
+        return getattr(self, "_frontend_trainable", False)
+
+    def _frontend_route(self) -> bool:
+        return self.frontend_trainable and torch.is_grad_enabled()
+
+    def _frontend_train(self, x: torch.Tensor) -> torch.Tensor:
+        D = self.hparams["transformer_dim"]
+        _lib.require_gpu(x, "stage input")
+        if self.device.type != "cuda":
+            self.engine()   # (raises: no CPU implementation)
+        if x.dim() != 3 or x.shape[2] != self.hparams["spect_dim"]:
+            raise ValueError(f"expected a (batch, time, {self.hparams['spect_dim']}) input, got {tuple(x.shape)}")
+        if x.shape[0] == 0 or x.shape[1] == 0:
+            return _bw.empty_with_graph((x.shape[0], x.shape[1], D), x, _params_of(self.frontend))
+        return _bw.frontend_train(self, x.to(torch.float32))
 
     # -- 16-mixed on the differentiable route (DESIGN.md section 16) --------------------------------------------------------------
     def set_train_precision(self, precision: str) -> "BeatThis":
@@ -423,6 +472,9 @@ class BeatThis(_TracksChildren, nn.Module):
         if x.dim() != 3:
             raise ValueError(f"expected (batch, time, {self.hparams['spect_dim']}) input, got {tuple(x.shape)}")
         _lib.require_gpu(x, "model input")
+        if self._frontend_route():
+            # whole-model fine-tuning: the frontend, the trunk and the heads on the differentiable route
+            return self.task_heads(self.transformer_blocks(self.frontend(x)))
         if torch.is_grad_enabled():
             self._refuse_trainable_frontend()
             if self._differentiable(None, self.transformer_blocks) or self._differentiable(None, self.task_heads):
@@ -468,6 +520,10 @@ class BeatThis(_TracksChildren, nn.Module):
             node = tb.norm if kind == "norm" else tb.layers[index][0 if kind == "attn" else 1]
             if self._differentiable(x, node):
                 return self._unit_train(x, kind, node)
+        elif self._frontend_route():
+            raise NotImplementedError(
+                "the sub-modules below frontend are inference-only: with set_frontend_trainable() the differentiable route is "
+                "model(x) / model.frontend(x); call this node under torch.no_grad()")
         half = torch.is_autocast_enabled("cuda") if hasattr(torch, "is_autocast_enabled") else False
         prec = _lib.PREC_HALF if half else _lib.PREC_F32
         eng = self.engine()

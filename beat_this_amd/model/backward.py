@@ -13,6 +13,11 @@ Dropout: the attention and the feed-forward take ``drop`` = None (the calls and 
 kernels recompute the masks from those three numbers, nothing is stored.  ``BeatThis`` decides when dropout is active and
 hands out the streams.
 
+The frontend (the lower part of this file): ``StemFn``, ``ConvUnitFn``, ``SwapFn`` and ``ProjectionFn`` over
+bt_front_forward / bt_front_backward (csrc/train_front.hip), composed by ``frontend_train`` with ``AttentionFn`` /
+``FeedForwardFn`` for the twelve leaves of the partial transformers; fp32, BatchNorm on its running statistics, no dropout.
+``BeatThis.set_frontend_trainable`` decides whether it runs.
+
 16-mixed: the attention and the feed-forward take ``mixed``; True sends the same arguments to
 bt_train_forward_mixed / bt_train_backward_mixed (both operands of every matrix product rounded to fp16, fp32 accumulation,
 everything else fp32), False -- the default -- makes the calls above.  ``BeatThis.set_train_precision`` decides it;
@@ -93,10 +98,11 @@ def _grad_like(p: torch.Tensor, wanted: bool):
 
 
 class AttentionFn(torch.autograd.Function):
-    """Attention.forward (roformer.py:114-132) on (B, T, D): the branch without the residual."""
+    """Attention.forward (roformer.py:114-132) on (B, T, D): the branch without the residual, or with ``residual`` the unit's
+    own x + f(x) (the frontend's leaves)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, w_qkv, w_gates, b_gates, w_out, rope, rope_len, drop=None, mixed=False):
+    def forward(ctx, x, gamma, w_qkv, w_gates, b_gates, w_out, rope, rope_len, drop=None, mixed=False, residual=False):
         xf = _f32(x)
         B, T, D = xf.shape
         ps = [_f32(p) for p in (gamma, w_qkv, w_gates, b_gates, w_out)]
@@ -105,11 +111,12 @@ class AttentionFn(torch.autograd.Function):
         o = torch.empty_like(xf)
         lse = torch.empty((B, T, D // 32), dtype=torch.float32, device=xf.device)
         a = _args(xf, rope=rope, rope_len=rope_len)
+        a.residual = int(bool(residual))
         a.gamma, a.w1, a.w2, a.b2, a.w3 = (p.data_ptr() for p in ps)
         a.y, a.save_o, a.save_lse = y.data_ptr(), o.data_ptr(), lse.data_ptr()
         _run(False, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, drop, mixed)
         ctx.save_for_backward(xf, o, lse, rope, *ps)
-        ctx.rope_len, ctx.drop, ctx.mixed = rope_len, drop, bool(mixed)
+        ctx.rope_len, ctx.drop, ctx.mixed, ctx.residual = rope_len, drop, bool(mixed), int(bool(residual))
         return y
 
     @staticmethod
@@ -122,18 +129,19 @@ class AttentionFn(torch.autograd.Function):
         gx, g_gamma, g_qkv, g_wg, g_bg, g_out = (_grad_like(t, need[i]) for i, t in
                                                  enumerate((xf, gamma, w_qkv, w_gates, b_gates, w_out)))
         a = _args(xf, rope=rope, rope_len=ctx.rope_len)
+        a.residual = ctx.residual
         a.gamma, a.w1, a.w2, a.b2, a.w3 = (p.data_ptr() for p in (gamma, w_qkv, w_gates, b_gates, w_out))
         a.save_o, a.save_lse, a.gy = o.data_ptr(), lse.data_ptr(), gyf.data_ptr()
         a.gx, a.g_gamma, a.g_w1, a.g_w2, a.g_b2, a.g_w3 = (_lib.ptr(g) for g in (gx, g_gamma, g_qkv, g_wg, g_bg, g_out))
         _run(True, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, ctx.drop, ctx.mixed)
-        return gx, g_gamma, g_qkv, g_wg, g_bg, g_out, None, None, None, None
+        return gx, g_gamma, g_qkv, g_wg, g_bg, g_out, None, None, None, None, None
 
 
 class FeedForwardFn(torch.autograd.Function):
-    """FeedForward.forward (roformer.py:38-61) on (B, T, D): the branch without the residual."""
+    """FeedForward.forward (roformer.py:38-61) on (B, T, D): the branch without the residual, or with ``residual`` x + f(x)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, w1, b1, w2, b2, drop=None, mixed=False):
+    def forward(ctx, x, gamma, w1, b1, w2, b2, drop=None, mixed=False, residual=False):
         xf = _f32(x)
         B, T, D = xf.shape
         ps = [_f32(p) for p in (gamma, w1, b1, w2, b2)]
@@ -141,11 +149,12 @@ class FeedForwardFn(torch.autograd.Function):
         hidden = int(ps[1].shape[0])
         y = torch.empty_like(xf)
         a = _args(xf, hidden=hidden)
+        a.residual = int(bool(residual))
         a.gamma, a.w1, a.b1, a.w2, a.b2 = (p.data_ptr() for p in ps)
         a.y = y.data_ptr()
         _run(False, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, drop, mixed)
         ctx.save_for_backward(xf, *ps)
-        ctx.drop, ctx.mixed = drop, bool(mixed)
+        ctx.drop, ctx.mixed, ctx.residual = drop, bool(mixed), int(bool(residual))
         return y
 
     @staticmethod
@@ -157,11 +166,12 @@ class FeedForwardFn(torch.autograd.Function):
         gyf = _f32(gy)
         grads = [_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, gamma, w1, b1, w2, b2))]
         a = _args(xf, hidden=hidden)
+        a.residual = ctx.residual
         a.gamma, a.w1, a.b1, a.w2, a.b2 = (p.data_ptr() for p in (gamma, w1, b1, w2, b2))
         a.gy = gyf.data_ptr()
         a.gx, a.g_gamma, a.g_w1, a.g_b1, a.g_w2, a.g_b2 = (_lib.ptr(g) for g in grads)
         _run(True, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, ctx.drop, ctx.mixed)
-        return (*grads, None, None)
+        return (*grads, None, None, None)
 
 
 class NormFn(torch.autograd.Function):
@@ -239,17 +249,18 @@ def empty_with_graph(shape, x: torch.Tensor, params) -> torch.Tensor:
     return out
 
 
-def attention(node, x, rope, rope_len, drop=None, mixed=False):
-    """``transformer_blocks.layers[l][0]`` of the differentiable route; ``drop``: None or (p, seed, stream); ``mixed``: 16-mixed"""
+def attention(node, x, rope, rope_len, drop=None, mixed=False, residual=False):
+    """``transformer_blocks.layers[l][0]`` of the differentiable route; ``drop``: None or (p, seed, stream); ``mixed``: 16-mixed;
+    ``residual``: x + f(x) in the unit's own kernels (``residual = 1`` of bt_train_args)"""
     return AttentionFn.apply(x, node.norm.gamma, node.to_qkv.weight, node.to_gates.weight, node.to_gates.bias,
-                             node.to_out[0].weight, rope, rope_len, drop, mixed)
+                             node.to_out[0].weight, rope, rope_len, drop, mixed, residual)
 
 
-def feedforward(node, x, drop=None, mixed=False):
+def feedforward(node, x, drop=None, mixed=False, residual=False):
     """``transformer_blocks.layers[l][1]``"""
     net = node.net
     return FeedForwardFn.apply(x, net[0].gamma, net[1].weight, net[1].bias, net._modules["4"].weight, net._modules["4"].bias, drop,
-                               mixed)
+                               mixed, residual)
 
 
 def final_norm(node, x):
@@ -259,3 +270,203 @@ def final_norm(node, x):
 def head(node, x, sum_head: bool):
     lin = node.beat_downbeat_lin
     return HeadFn.apply(x, lin.weight, lin.bias, sum_head)
+
+
+# ---- the differentiable frontend (csrc/train_front.hip) -----------------------------------------------------
+# Activations are the library's (b, t, f, c), channels last, fp32.  BatchNorm runs on its running statistics, there is no
+# dropout, and the arithmetic is fp32 whatever the train precision says.
+def check_front_limits(B: int, T: int) -> None:
+    """Raised before any launch: the frequency direction runs B T sequences, every unit B T 32 rows at the most."""
+    if B * T > _lib.FRONT_MAX_FRAMES or B * T * 32 > _lib.FRONT_MAX_ROWS:
+        raise ValueError(f"the differentiable frontend takes at most {_lib.FRONT_MAX_FRAMES} frames per call (batch x time, "
+                         f"{_lib.FRONT_MAX_ROWS} rows of 32 frequency tokens), got batch {B} x {T} frames: split the batch")
+
+
+def _front_args(B, T, F, Cc, dim=0) -> _lib.FrontArgs:
+    a = _lib.FrontArgs()
+    a.B, a.T, a.F, a.C, a.dim = int(B), int(T), int(F), int(Cc), int(dim)
+    return a
+
+
+def _front_call(backward: bool, unit: int, a: _lib.FrontArgs, device) -> None:
+    need = _lib.lib().bt_front_workspace_bytes(unit, int(backward), a.B, a.T, a.F, a.C, a.dim)
+    if need == 0:
+        check_front_limits(a.B, a.T)
+        raise ValueError(f"the differentiable frontend does not support batch {a.B}, {a.T} frames, {a.F} frequency bins, "
+                         f"{a.C} channels, width {a.dim} (unit {unit})")
+    ws = torch.empty(need, dtype=torch.uint8, device=device)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
+    fn = _lib.lib().bt_front_backward if backward else _lib.lib().bt_front_forward
+    with torch.cuda.device(device):
+        _lib.check(fn(_lib.stream_ptr(device), unit, C.byref(a)))
+
+
+class StemFn(torch.autograd.Function):
+    """make_stem (beat_tracker.py:108-126): (B, T, 128) -> (B, T, 32, 32) = (b, t, f, c).  Inputs: x, conv weight, bn1d weight,
+    bias, running_mean, running_var, bn2d weight, bias, running_mean, running_var."""
+
+    @staticmethod
+    def forward(ctx, x, w, w1, b1, m1, v1, w2, b2, m2, v2):
+        xf = _f32(x)
+        ps = [_f32(p) for p in (w, w1, b1, m1, v1, w2, b2, m2, v2)]
+        _on_device_of(xf, *ps)
+        B, T, F = xf.shape
+        y = torch.empty((B, T, 32, 32), dtype=torch.float32, device=xf.device)
+        a = _front_args(B, T, F, int(ps[0].shape[0]))
+        a.x, a.y, a.w = xf.data_ptr(), y.data_ptr(), ps[0].data_ptr()
+        a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
+        _front_call(False, _lib.FRONT_STEM, a, xf.device)
+        ctx.save_for_backward(xf, *ps)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xf, *ps = ctx.saved_tensors
+        B, T, F = xf.shape
+        need = ctx.needs_input_grad
+        gyf = _f32(gy)
+        gx, g_w, g_w1, g_b1, g_w2, g_b2 = (_grad_like(t, need[i]) for i, t in
+                                           ((0, xf), (1, ps[0]), (2, ps[1]), (3, ps[2]), (6, ps[5]), (7, ps[6])))
+        a = _front_args(B, T, F, int(ps[0].shape[0]))
+        a.x, a.gy, a.w = xf.data_ptr(), gyf.data_ptr(), ps[0].data_ptr()
+        a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
+        a.gx, a.g_w, a.g_bn1_w, a.g_bn1_b, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in (gx, g_w, g_w1, g_b1, g_w2, g_b2))
+        _front_call(True, _lib.FRONT_STEM, a, xf.device)
+        return gx, g_w, g_w1, g_b1, None, None, g_w2, g_b2, None, None
+
+
+class ConvUnitFn(torch.autograd.Function):
+    """blocks.i.conv2d + .norm + GELU (beat_tracker.py:155-166): (B, T, F, C) -> (B, T, F / 2, 2 C).  Saves its input and the
+    convolution's result ``pre``.  Inputs: x, conv weight, norm weight, bias, running_mean, running_var."""
+
+    @staticmethod
+    def forward(ctx, x, w, nw, nb, nm, nv):
+        xf = _f32(x)
+        ps = [_f32(p) for p in (w, nw, nb, nm, nv)]
+        _on_device_of(xf, *ps)
+        B, T, F, Cc = xf.shape
+        if tuple(ps[0].shape) != (2 * Cc, Cc, 2, 3) or F % 2:
+            raise ValueError(f"conv unit: input {tuple(xf.shape)} against a weight of shape {tuple(ps[0].shape)}")
+        y = torch.empty((B, T, F // 2, 2 * Cc), dtype=torch.float32, device=xf.device)
+        pre = torch.empty_like(y)
+        a = _front_args(B, T, F, Cc)
+        a.x, a.y, a.save_pre, a.w = xf.data_ptr(), y.data_ptr(), pre.data_ptr(), ps[0].data_ptr()
+        a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
+        _front_call(False, _lib.FRONT_CONV, a, xf.device)
+        ctx.save_for_backward(xf, pre, *ps)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xf, pre, *ps = ctx.saved_tensors
+        B, T, F, Cc = xf.shape
+        need = ctx.needs_input_grad
+        gyf = _f32(gy)
+        gx, g_w, g_nw, g_nb = (_grad_like(t, need[i]) for i, t in enumerate((xf, ps[0], ps[1], ps[2])))
+        a = _front_args(B, T, F, Cc)
+        a.x, a.save_pre, a.gy, a.w = xf.data_ptr(), pre.data_ptr(), gyf.data_ptr(), ps[0].data_ptr()
+        a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
+        a.gx, a.g_w, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in (gx, g_w, g_nw, g_nb))
+        _front_call(True, _lib.FRONT_CONV, a, xf.device)
+        return gx, g_w, g_nw, g_nb, None, None
+
+
+class SwapFn(torch.autograd.Function):
+    """(B, P, Q, C) -> (B, Q, P, C): between the frequency and the time direction of a partial transformer"""
+
+    @staticmethod
+    def forward(ctx, x):
+        xf = _f32(x)
+        _on_device_of(xf)
+        B, P, Q, Cc = xf.shape
+        y = torch.empty((B, Q, P, Cc), dtype=torch.float32, device=xf.device)
+        a = _front_args(B, P, Q, Cc)
+        a.x, a.y = xf.data_ptr(), y.data_ptr()
+        _front_call(False, _lib.FRONT_SWAP, a, xf.device)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        gyf = _f32(gy)
+        B, Q, P, Cc = gyf.shape
+        gx = torch.empty((B, P, Q, Cc), dtype=torch.float32, device=gyf.device)
+        a = _front_args(B, P, Q, Cc)
+        a.gy, a.gx = gyf.data_ptr(), gx.data_ptr()
+        _front_call(True, _lib.FRONT_SWAP, a, gyf.device)
+        return gx
+
+
+class ProjectionFn(torch.autograd.Function):
+    """concat + frontend.linear (beat_tracker.py:71-76): (B, T, F, C) -> (B, T, D); the weight's columns are c F + f"""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        xf, wf, bf = _f32(x), _f32(w), _f32(b)
+        _on_device_of(xf, wf, bf)
+        B, T, F, Cc = xf.shape
+        D = int(wf.shape[0])
+        if int(wf.shape[1]) != F * Cc:
+            raise ValueError(f"projection: input {tuple(xf.shape)} against a weight of shape {tuple(wf.shape)}")
+        y = torch.empty((B, T, D), dtype=torch.float32, device=xf.device)
+        a = _front_args(B, T, F, Cc, D)
+        a.x, a.y, a.w, a.b = xf.data_ptr(), y.data_ptr(), wf.data_ptr(), bf.data_ptr()
+        _front_call(False, _lib.FRONT_LINEAR, a, xf.device)
+        ctx.save_for_backward(xf, wf, bf)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xf, wf, bf = ctx.saved_tensors
+        B, T, F, Cc = xf.shape
+        gyf = _f32(gy)
+        gx, g_w, g_b = (_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, wf, bf)))
+        a = _front_args(B, T, F, Cc, int(wf.shape[0]))
+        a.x, a.gy, a.w, a.b = xf.data_ptr(), gyf.data_ptr(), wf.data_ptr(), bf.data_ptr()
+        a.gx, a.g_w, a.g_b = (_lib.ptr(g) for g in (gx, g_w, g_b))
+        _front_call(True, _lib.FRONT_LINEAR, a, xf.device)
+        return gx, g_w, g_b
+
+
+def _bn(node):
+    return node.weight, node.bias, node.running_mean, node.running_var
+
+
+def stem(node, x):
+    """``frontend.stem``: (B, T, 128) -> (b, t, f, c)"""
+    return StemFn.apply(x, node.conv2d.weight, *_bn(node.bn1d), *_bn(node.bn2d))
+
+
+def conv_unit(block, x):
+    """``frontend.blocks[i]`` behind its partial transformer: conv2d, norm, GELU on (b, t, f, c)"""
+    return ConvUnitFn.apply(x, block.conv2d.weight, *_bn(block.norm))
+
+
+def partial_ft(node, x, rope_for):
+    """PartialFTTransformer.forward (beat_tracker.py:290-301) on (b, t, f, c): attention and feed-forward over the frequency
+    tokens of every frame, then over the time tokens of every bin -- the trunk's unit code with its residual on (B T, F, C) and
+    (B F, T, C), fp32, no dropout.  ``rope_for(n)``: the rotary table for n tokens."""
+    B, T, F, Cc = x.shape
+    y = x.reshape(B * T, F, Cc)
+    y = attention(node.attnF, y, *rope_for(F), residual=True)
+    y = feedforward(node.ffF, y, residual=True)
+    y = SwapFn.apply(y.reshape(B, T, F, Cc)).reshape(B * F, T, Cc)
+    y = attention(node.attnT, y, *rope_for(T), residual=True)
+    y = feedforward(node.ffT, y, residual=True)
+    return SwapFn.apply(y.reshape(B, F, T, Cc))
+
+
+def frontend_train(model, x):
+    """``BeatThis.frontend`` on the differentiable route, in the reference's order (beat_tracker.py:54-80, 290-301): stem, three
+    times (partial transformer, conv unit), projection.  (B, T, 128) -> (B, T, D)."""
+    fr = model.frontend
+    check_front_limits(int(x.shape[0]), int(x.shape[1]))
+    h = stem(fr.stem, x)
+    for blk in fr.blocks:
+        if "partial" in blk._modules:
+            h = partial_ft(blk.partial, h, model._rope)
+        h = conv_unit(blk, h)
+    return ProjectionFn.apply(h, fr.linear.weight, fr.linear.bias)

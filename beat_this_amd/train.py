@@ -4,7 +4,7 @@ up in launch_scripts/train.py:118-131 -- epochs over the training loader, gradie
 step per accumulated batch group, validation with the package's own metrics every few epochs, one checkpoint per epoch -- and
 ``python -m beat_this_amd.train`` is the command line around it.  Every step's arithmetic runs in the package's kernels: the
 differentiable route of ``BeatThis`` (fp32 or, with ``precision="16-mixed"``, fp16 matrix products under a dynamic loss scale;
-frozen frontend, dropout in the main layers when enabled), the losses, and the fused AdamW of ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
+frozen frontend or, with ``train_frontend``, the whole model; dropout in the main layers when enabled), the losses, and the fused AdamW of ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
 and ``load_model`` read as it is.
 
 Not offered: the reference's wandb logger, ``--compile`` and ``--force-flash-attention`` (nothing here is compiled by torch or
@@ -91,7 +91,7 @@ def validate(pl_module, datamodule) -> dict:
 
 
 def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
-        resume=None, log=print, precision=None) -> dict:
+        resume=None, log=print, precision=None, train_frontend=None) -> dict:
     """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
 
     Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
@@ -110,6 +110,10 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     unscaled; the scaler's state goes into the checkpoint under ``loss_scaler`` and comes back with ``resume``.  Without
     16-mixed the calls are the ones of an fp32 run.
 
+    ``train_frontend``: True / False calls the model's ``set_frontend_trainable`` first, before the optimiser is built, so
+    that its state covers the frontend's weights (None leaves the model as it is): whole-model fine-tuning with frozen
+    BatchNorm statistics.  A checkpoint then carries the larger optimiser state, and ``resume`` needs the same setting.
+
     A module whose model has dropout enabled is put into ``train()`` mode here and stays in it; validation runs under
     ``no_grad`` on the inference path, which never drops.
 
@@ -119,6 +123,8 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
 
     if precision is not None:
         pl_module.model.set_train_precision(precision)
+    if train_frontend is not None:
+        pl_module.model.set_frontend_trainable(train_frontend)
     scaler = LossScaler() if pl_module.model.train_precision == "16-mixed" else None
     accumulate = int(accumulate_grad_batches)
     if accumulate < 1 or int(max_epochs) < 0 or int(val_frequency) < 1:
@@ -191,7 +197,7 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
 def get_parser() -> argparse.ArgumentParser:
     from .loss import LOSS_TYPES
 
-    p = argparse.ArgumentParser(description="Fine-tune Beat This! on the MI355X kernels (frozen frontend, fp32 or --precision "
+    p = argparse.ArgumentParser(description="Fine-tune Beat This! on the MI355X kernels (frozen frontend unless --train-frontend, fp32 or --precision "
                                             "16-mixed, dropout in the main transformer with --dropout).")
     toggle = argparse.BooleanOptionalAction
     p.add_argument("--data-dir", type=str, required=True, help="data folder: annotations/ and the spectrogram bundles")
@@ -217,6 +223,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", type=str, default="32-true", choices=["32-true", "16-mixed"],
                    help="16-mixed: the reference's training precision -- fp16 matrix products in the main layers, fp32 master "
                         "weights, a dynamic loss scale (default: %(default)s)")
+    p.add_argument("--train-frontend", default=False, action=toggle,
+                   help="whole-model fine-tuning: also train the frontend (frozen BatchNorm statistics, no frontend dropout, "
+                        "fp32 frontend under either precision; default: the frontend stays frozen)")
     p.add_argument("--dbn", default=False, action=toggle, help="DBN post-processing in validation")
     p.add_argument("--eval-trim-beats", metavar="SECONDS", type=float, default=5,
                    help="skip the first seconds of each piece in the metrics (default: %(default)s)")
@@ -267,7 +276,7 @@ def main(argv=None) -> int:
     pl_module = PLBeatThis(**arch, apply_dropout=args.dropout, dropout_seed=args.seed, fps=FPS, lr=args.lr,
                            weight_decay=args.weight_decay, pos_weights=pos_weights, loss_type=args.loss,
                            warmup_steps=args.warmup_steps, max_epochs=args.max_epochs, use_dbn=args.dbn,
-                           eval_trim_beats=args.eval_trim_beats, precision=args.precision)
+                           eval_trim_beats=args.eval_trim_beats, precision=args.precision, train_frontend=args.train_frontend)
     if ckpt is not None and not args.resume_checkpoint:   # (a resumed run's weights are restored by fit() with the rest)
         pl_module.load_state_dict(ckpt["state_dict"])
     pl_module.to(device)

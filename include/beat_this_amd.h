@@ -711,8 +711,11 @@ int bt_train_backward_mixed(void* stream, int unit, const bt_train_args* a, cons
  *   form 2: C = A^T B, A [K, M], B [K, N]   (dW = dY^T A; K = the summed rows, taken BT_TRAIN_DW_ROWS at a time and the chunks
  *                                            added into C in chunk order, one launch per chunk) */
 int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B, int M, int N, int K, float* C);
-/* DIAGNOSTIC: the GEMM of either training route (mixed = 0: the fp32 MFMA kernels, 1: the fp16 ones) through the host helpers
- * the unit calls launch it with, forms as above, C [M, N] contiguous, 1 <= M, N, K <= 2^22.  The caller supplies every buffer;
+/* The GEMM of either training route (mixed = 0: the fp32 MFMA kernels, 1: the fp16 ones) through the host helpers
+ * the unit calls launch it with.  A diagnostic for the trunk's units, and PRODUCTION for the frontend's projection:
+ * bt_front_forward / bt_front_backward (BT_FRONT_LINEAR) call forms 0, 1 and 2 with mixed = 0 and size their workspace with
+ * bt_train_matmul_workspace_bytes, so what this entry computes, and in which order it sums, is part of section 17's contract.
+ * Forms as above, forms as above, C [M, N] contiguous, 1 <= M, N, K <= 2^22.  The caller supplies every buffer;
  * nothing is allocated, cleared or synchronised.
  *   form 0: C = [resid +] m c (A B^T + bias) [+ the old C when accum != 0]; act (or NULL) = gelu(C).  bias [N], resid and act
  *           [M, N] or NULL.  dropout (or NULL, or p == 0: none) puts the row site `site` (BT_DROP_ATTN_OUT, _FF_HIDDEN or _FF_OUT)
@@ -738,6 +741,53 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
 int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int dim, const float* qkv,
                        const bt_train_dropout* dropout_or_null, float* O, float* lse, const float* dO, const float* delta,
                        float* dqkv);
+
+/* ---- training: the frontend's own units (csrc/train_front.hip) ------------------------------------------
+ * What BeatThis.frontend holds beside its twelve attention / feed-forward leaves (those are BT_UNIT_ATTN / BT_UNIT_FF calls of
+ * bt_train_forward / bt_train_backward on (B', T') = (B T, F) and (B F, T) rows).  Activations are this library's (b, t, f, c),
+ * channels last, fp32 and contiguous; parameters are read in the REFERENCE's layout straight from the nn.Parameter storage and
+ * gradients are written in that layout.  BatchNorm uses its RUNNING statistics (s = weight / sqrt(running_var + 1e-5), sh =
+ * bias - running_mean s, evaluated in fp64 and rounded once); the statistics are never written and get no gradient.
+ *   BT_FRONT_STEM    x [B, T, 128] -> y [B, T, 32, 32] = gelu(bn2d(conv(bn1d(x)))), F = 128, C = 32: w = stem.conv2d.weight
+ *                    [32][1][4][3] (kernel (4, 3), stride (4, 1), padding (0, 1) over (f, t)), bn_* = stem.bn2d, bn1_* = stem.bn1d
+ *   BT_FRONT_CONV    x [B, T, F, C] -> y [B, T, F / 2, 2 C] = gelu(s pre + sh), w = blocks.i.conv2d.weight [2 C][C][2][3]
+ *                    (kernel (2, 3), stride (2, 1), padding (0, 1), no bias), bn_* = blocks.i.norm [2 C];
+ *                    pre[b, t, f', co] = sum_{dt < 3, df < 2, ci} w[co][ci][df][dt] x[b, t + dt - 1, 2 f' + df, ci];
+ *                    the forward also writes save_pre [B, T, F / 2, 2 C] = pre, which the backward reads.  F even, <= 32; C a
+ *                    multiple of 32, <= 512.  The three matrix products run on v_mfma_f32_32x32x2_f32 as implicit GEMMs.
+ *   BT_FRONT_LINEAR  x [B, T, F, C] -> y [B, T, dim] = frontend.linear of the reference's "b t (c f)" rows: w [dim][C F] with
+ *                    column c F + f, b [dim]
+ *   BT_FRONT_SWAP    x [B, T, F, C] -> y [B, F, T, C]; the backward takes gy [B, F, T, C] and writes gx [B, T, F, C].  T and F are
+ *                    the two swapped extents, whichever holds the time: the way back is the same call with them exchanged; its
+ *                    limits are B T F <= 2^22 rows and C <= 1024
+ * The backward takes x (not BT_FRONT_SWAP), save_pre (BT_FRONT_CONV), the upstream gradient gy (shaped like y) and OVERWRITES the
+ * gradients whose pointer is not NULL: gx (the stem's: the gradient of the spectrogram), g_w, g_b (projection), g_bn_w / g_bn_b
+ * (bn2d, blocks.i.norm: sum of g_pre (pre - mean) / sqrt(var + eps) and of g_pre, g_pre = gy gelu'(s pre + sh)), g_bn1_w / g_bn1_b
+ * (bn1d).  The contract is section 13's: no atomics; every gradient byte is written by one thread of one launch; the order of
+ * every sum depends on the shapes alone (a GEMM element sums k ascending; weight gradients over chunks of BT_TRAIN_DW_ROWS rows,
+ * column sums over chunks of BT_TRAIN_CS_ROWS rows, partials in the workspace added in chunk order by a second launch), so two
+ * runs are bit-identical, and a sequence's gx is the same alone and inside a batch.  No call synchronises, allocates or clears
+ * memory; no launch reads workspace bytes that the same call has not written.  Limits: B T <= 65535 (the frequency direction
+ * runs one sequence per frame) and B T 32 <= 2^22 rows (BT_FRONT_SWAP: see above); anything else is BT_ERR_ARG and the workspace query returns 0. */
+#define BT_FRONT_STEM 0
+#define BT_FRONT_CONV 1
+#define BT_FRONT_LINEAR 2
+#define BT_FRONT_SWAP 3
+typedef struct {
+  int32_t B, T, F, C, dim, reserved0, reserved1, reserved2;
+  const float* w; const float* b;
+  const float* bn_w; const float* bn_b; const float* bn_mean; const float* bn_var;
+  const float* bn1_w; const float* bn1_b; const float* bn1_mean; const float* bn1_var;
+  const float* x; float* y; float* save_pre;
+  const float* gy;
+  float* gx; float* g_w; float* g_b; float* g_bn_w; float* g_bn_b; float* g_bn1_w; float* g_bn1_b;
+  void* ws; size_t ws_bytes;
+} bt_front_args;
+/* sizeof, then offsetof w, x, gy, gx, ws, ws_bytes: seven entries, the binding's self-check */
+void bt_front_struct_sizes(int32_t* out);
+size_t bt_front_workspace_bytes(int unit, int backward, int B, int T, int F, int C, int dim);
+int bt_front_forward(void* stream, int unit, const bt_front_args* a);
+int bt_front_backward(void* stream, int unit, const bt_front_args* a);
 
 /* ---- training: the optimiser step (csrc/optim.hip) ------------------------------------------------------
  * Multi-tensor AdamW with torch.optim.AdamW's default semantics (decoupled decay, no amsgrad, no maximize), all fp32.  With
