@@ -310,9 +310,8 @@ FLAGS_BY_SOURCE = {"tail.hip": ["-Xclang", "-target-feature", "-Xclang", "-packe
                    "data.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # the AdamW step and the gradient norm must have the same bits on the host and the device (the host twins)
                    "optim.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
-# compile-time switches: BT_DEV_BUILD=1 in the environment of build() compiles the development instrumentation (per-wave timing
-# dumps, ablation variants read by tools/*_probe.py) into the kernels; release builds contain none of it
-EXTRA_DEFINES = (["-DBT_DEV"] if os.environ.get("BT_DEV_BUILD") == "1" else []) + os.environ.get("BT_DEFINES", "").split()
+# compile-time switches: BT_DEFINES in the environment of build() (e.g. "-DBT_HALF_BF16"); every one of them builds a correct library
+EXTRA_DEFINES = os.environ.get("BT_DEFINES", "").split()
 
 
 def build(force: bool = False, verbose: bool = False, lib_path: str | None = None, obj_dir: str | None = None,

@@ -22,7 +22,6 @@
 //     fp32/half (common factor 2^-m cancels in O / l) unless exp2 overflows.  Overflow or a sum
 //     >= 1e30 is detected on l at the end and the whole workgroup then re-runs the classic
 //     online-softmax loop (SAFE pass), so the result is always the exact softmax.
-#include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
@@ -122,12 +121,6 @@ DEVI void rowsum16_valu(f32x4& l, const f32x16& p) {
 // error of 2^-10 in the row sum only if ALL 1500 keys sit there).  The common factor cancels in O / l.  bfloat16 has
 // the fp32 exponent range and needs no shift.
 constexpr float P_SHIFT = BT_HALF_IS_BF16 ? 0.f : 4.f;
-// BT_ATTN_EXPT (development, variant builds only -- results are WRONG): what the key loop of the fast pass spends where.
-//   1 = no exponentials, 2 = no packing either (VALU-free), 4 = no row-sum MFMAs, 8 = no fragment reads from LDS in the loop,
-//   16 = no LDS-DMA / barriers after the prologue, 32 = one score MFMA per block instead of two, 64 = one P.V MFMA instead of two
-#ifndef BT_ATTN_EXPT
-#define BT_ATTN_EXPT 0
-#endif
 
 // Per-query-block softmax state of a wave (QB query blocks of 32 queries share every K / V fragment read).
 struct QState {
@@ -310,45 +303,30 @@ DEVI void score_fast(const KFrag& kf, const QState (&st)[QB], f32x16 (&sc)[QB]) 
 #pragma unroll
   for (int j = 0; j < QB; ++j) {
     sc[j] = MFMA32_H(kf.k0, st[j].q0, st[j].negm);
-#if !(BT_ATTN_EXPT & 32)
     sc[j] = MFMA32_H(kf.k1, st[j].q1, sc[j]);
-#endif
   }
 }
 template <int QB>
 DEVI void finish_fast(f32x16 (&sc)[QB], const VFrag& vf, QState (&st)[QB]) {
 #pragma unroll
   for (int j = 0; j < QB; ++j) {
-#if !(BT_ATTN_EXPT & 3)
 #pragma unroll
     for (int r = 0; r < 16; ++r) sc[j][r] = __builtin_amdgcn_exp2f(sc[j][r]);
-#endif
-#if BT_ATTN_EXPT & 2
-    const u32x4 w0 = {__builtin_bit_cast(unsigned, sc[j][0]), __builtin_bit_cast(unsigned, sc[j][1]), __builtin_bit_cast(unsigned, sc[j][2]), __builtin_bit_cast(unsigned, sc[j][3])};
-    const u32x4 w1 = {__builtin_bit_cast(unsigned, sc[j][8]), __builtin_bit_cast(unsigned, sc[j][9]), __builtin_bit_cast(unsigned, sc[j][10]), __builtin_bit_cast(unsigned, sc[j][11])};
-#else
     const u32x4 w0 = pack8(sc[j], 0), w1 = pack8(sc[j], 1);
-#endif
-#if BT_ATTN_EXPT & 4
-    st[j].l[0] += __builtin_bit_cast(float, w0[0]);
-#elif BT_ATTN_ROWSUM == 1
+#if BT_ATTN_ROWSUM == 1
     rowsum16_valu(st[j].l, sc[j]);
 #else
     rowsum8(st[j].l, w0);
     rowsum8(st[j].l, w1);
 #endif
-#if BT_ATTN_EXPT & 64
-    st[j].acc = MFMA32_H(vf.v0, __builtin_bit_cast(hfx8, w0 ^ w1), st[j].acc);
-#else
     st[j].acc = MFMA32_H(vf.v0, __builtin_bit_cast(hfx8, w0), st[j].acc);
     st[j].acc = MFMA32_H(vf.v1, __builtin_bit_cast(hfx8, w1), st[j].acc);
-#endif
   }
 }
 
 template <int QB>
 DEVI void attn_pass_pipe(rsrc_t rk, rsrc_t rv, char* smem, int tid, int wave, int lane, int g, int lr,
-                         QState (&st)[QB], int L, int nblk, long long* t_loop = nullptr) {
+                         QState (&st)[QB], int L, int nblk) {
   const int ntiles = (nblk + KB - 1) / KB;
   const bool partial = (L & 31) != 0;
   int nfull = nblk / KB;  // tiles of KB unmasked blocks
@@ -379,20 +357,11 @@ DEVI void attn_pass_pipe(rsrc_t rk, rsrc_t rv, char* smem, int tid, int wave, in
       for (int r = 0; r < 16; ++r) st[j].negm[r] = -bm - P_SHIFT;
     }
   }
-  if (t_loop) *t_loop = wall_clock64();
   if (nfull > 0) {
     f32x16 sc[QB];
     KFrag kn = ld_k(smem, g, lr);
     score_fast<QB>(kn, st, sc);
     kn = ld_k(smem + BLK_BYTES, g, lr);
-#if BT_ATTN_EXPT & 8
-    const VFrag vf0 = ld_v(smem + TILE_BYTES, lane);
-#define LD_V(addr, lane) vf0
-#define LD_K(addr, g, lr) kn
-#else
-#define LD_V(addr, lane) ld_v(addr, lane)
-#define LD_K(addr, g, lr) ld_k(addr, g, lr)
-#endif
     // (Reading the V fragments one block ahead as well -- a second V register set, 127 VGPRs -- was measured and dropped:
     // main-layer shape 104.8 / 103.2 vs 108.9 / 105.0 us, frontend shape 237 / 235 vs 228 / 231 us, the x3 kernel 2 % slower:
     // the fragment reads cost LDS issue slots and energy, not exposed latency.)
@@ -402,25 +371,23 @@ DEVI void attn_pass_pipe(rsrc_t rk, rsrc_t rv, char* smem, int tid, int wave, in
       const char* kb_next = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
 #pragma unroll
       for (int c = 0; c < KB; ++c) {
-        const VFrag vf = LD_V(vb + c * BLK_BYTES, lane);
+        const VFrag vf = ld_v(vb + c * BLK_BYTES, lane);
         if (c + 1 < KB) {
           f32x16 sn[QB];
           score_fast<QB>(kn, st, sn);
-          if (c + 2 < KB) kn = LD_K(kb + (c + 2) * BLK_BYTES, g, lr);
+          if (c + 2 < KB) kn = ld_k(kb + (c + 2) * BLK_BYTES, g, lr);
           __builtin_amdgcn_sched_barrier(0);
           finish_fast<QB>(sc, vf, st);
 #pragma unroll
           for (int j = 0; j < QB; ++j) sc[j] = sn[j];
         } else {
-#if !(BT_ATTN_EXPT & 16)
           __syncthreads();  // tile t+1 has landed; nobody reads tile t any more (every fragment read of it has arrived)
           if (t + 2 < ntiles) stage_tile(rk, rv, t + 2, smem, t & 1, tid, wave);
-#endif
           const bool more = t + 1 < nfull;  // (uniform)
           KFrag k0n = kn;
           if (more) {
-            k0n = LD_K(kb_next, g, lr);
-            kn = LD_K(kb_next + BLK_BYTES, g, lr);
+            k0n = ld_k(kb_next, g, lr);
+            kn = ld_k(kb_next + BLK_BYTES, g, lr);
           }
           __builtin_amdgcn_sched_barrier(0);
           finish_fast<QB>(sc, vf, st);
@@ -447,15 +414,15 @@ DEVI void attn_pass_pipe(rsrc_t rk, rsrc_t rv, char* smem, int tid, int wave, in
   __syncthreads();
 }
 
-#undef LD_V
-#undef LD_K
-
-template <int ABL, int QB>
+template <int QB>
 __global__ __launch_bounds__(256, (QB == 1 ? 4 : 2)) void attn_frag_kernel(const AttnFragP p, int nqt, int sh_total) {
   __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES];
   // XCD-aware order: the q-tiles of one (sequence, head) run on one XCD (block b -> XCD b % 8), so its
   // K/V stream is fetched into one L2
-  const long long t_entry = wall_clock64();
+  // (The three clock reads of this kernel are what is left of a timing dump that is gone.  Nothing uses their values, but the
+  // compiler does not drop them, and without them it allocates and schedules the whole kernel differently: they stay until
+  // somebody measures the kernel without them.)
+  (void)wall_clock64();
   const int bid = blockIdx.x;
   const int idx = bid >> 3;
   const int sh = (idx / nqt) * 8 + (bid & 7);
@@ -483,20 +450,10 @@ __global__ __launch_bounds__(256, (QB == 1 ? 4 : 2)) void attn_frag_kernel(const
   const unsigned seq_bytes = (unsigned)p.nbp * BLK_BYTES;
   const rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(kseq), 0, seq_bytes, 0x00020000);
   const rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(vseq), 0, seq_bytes, 0x00020000);
-  const long long tc0 = clock64(), tw0 = wall_clock64();
-  long long t_loop = tw0;
-  attn_pass_pipe<QB>(rk, rv, smem, tid0, wave, lane0, g0, lr0, st, L, nblk, (ABL & 128) ? &t_loop : nullptr);
+  (void)clock64(), (void)wall_clock64();
+  attn_pass_pipe<QB>(rk, rv, smem, tid0, wave, lane0, g0, lr0, st, L, nblk);
   // (lane-derived values again: nothing but the softmax state stays live across the key loop)
   const int lane = lane_id_fresh(), tid = wave * 64 + lane, g = lane >> 5, lr = lane & 31;
-  if constexpr ((ABL & 128) != 0) {  // development: shader-clock ticks vs 100 MHz wall ticks of the pass
-    if (lane == 0) {
-      long long* dbg = reinterpret_cast<long long*>(const_cast<float*>(p.gates));
-      dbg[((long)bid * 4 + wave) * 4] = clock64() - tc0;
-      dbg[((long)bid * 4 + wave) * 4 + 1] = wall_clock64() - tw0;
-      dbg[((long)bid * 4 + wave) * 4 + 2] = tw0 - t_entry;   // kernel entry -> pass start (descriptor setup, Q loads issued)
-      dbg[((long)bid * 4 + wave) * 4 + 3] = t_loop - tw0;    // pass start -> key loop start (tile 0 landed, reference maximum)
-    }
-  }
   float l_tot[QB];
   bool bad = false;
 #pragma unroll
@@ -558,7 +515,7 @@ __global__ __launch_bounds__(256, (QB == 1 ? 4 : 2)) void attn_frag_kernel(const
 // fragment read feeding both blocks), the design of attn_frag_x3q2_kernel without the lo terms.  256 queries per workgroup, a
 // ring of four 8 KB [K tile | V tile] buffers of 64 keys, two workgroups per CU.
 //
-// SAME BITS AS attn_frag_kernel<0, 1> for every query (the forward picks the kernel by launch size; a chunk must not depend on
+// SAME BITS AS attn_frag_kernel<1> for every query (the forward picks the kernel by launch size; a chunk must not depend on
 // its batch): same reference point (the query's maximum over key block 0, minus P_SHIFT, on the score MFMA's accumulator input),
 // same order of the products, the packing, the row-sum MFMAs and the P.V MFMAs, the ragged last tile on the same plain code --
 // and the same REPEAT UNITS: a fast pass that overflowed re-runs the 128 queries that are one workgroup of attn_frag_kernel
@@ -1206,9 +1163,6 @@ __global__ __launch_bounds__(256, MINW) void attn_frag_x3_kernel(const AttnFragP
     const unsigned long long bw = __ballot(bad[j]);
     if (lane == 0 && qb0 + j < nblk) p.fix_mask[(long)sh * p.nbp + qb0 + j] = (int)(unsigned)bw;
   }
-#ifdef BT_DEV   // development: workgroups of the launch (word 2 of the status block; attn_fix_x3_kernel counts words 1 and 3)
-  if (p.status && tid == 0) atomicAdd(p.status + 2, 1);
-#endif
 
   float amax = 0.f;
 #pragma unroll
@@ -1426,9 +1380,6 @@ __global__ __launch_bounds__(256, 2) void attn_frag_x3q2_kernel(const AttnFragP 
     const unsigned long long bw = __ballot(bad[j]);
     if (laneE == 0 && qb0 + j < nblk) p.fix_mask[(long)sh * p.nbp + qb0 + j] = (int)(unsigned)bw;
   }
-#ifdef BT_DEV
-  if (p.status && tid == 0) atomicAdd(p.status + 2, 1);
-#endif
 
   const int seq = sh / p.heads, head = sh - seq * p.heads;
   float amax = 0.f;
@@ -1543,9 +1494,6 @@ __global__ __launch_bounds__(64 * FIX_NW, 2) void attn_fix_x3_kernel(const AttnF
       if (total == 0) continue;
       const int sh = first + FIX_GRID * w2;
       const int* mw = p.fix_mask + (long)sh * p.nbp;
-#ifdef BT_DEV   // development: queries recomputed here / pairs with any (words 1, 3 of the status block)
-      if (p.status && tid == 0) { atomicAdd(p.status + 1, total); atomicAdd(p.status + 3, 1); }
-#endif
       const long seq_off = (long)sh * p.nbp * BLKX_BYTES;
       const char* kseq = reinterpret_cast<const char*>(p.k) + seq_off;
       const char* vseq = reinterpret_cast<const char*>(p.v) + seq_off;
@@ -1672,13 +1620,13 @@ __global__ __launch_bounds__(64 * FIX_NW, 2) void attn_fix_x3_kernel(const AttnF
 
 int attn_frag_blocks(int L) { return ((L + 31) / 32 + KB - 1) / KB * KB; }
 
-template <int ABL, int QB>
+template <int QB>
 static void launch_v(const AttnFragP& p, hipStream_t s) {
   const int nblk = (p.L + 31) / 32;
   const int nqt = (nblk + 4 * QB - 1) / (4 * QB);
   const long sh = (long)p.n_seq * p.heads;
   const long grid = (sh + 7) / 8 * 8 * nqt;
-  hipLaunchKernelGGL((attn_frag_kernel<ABL, QB>), dim3((unsigned)grid), dim3(256), 0, s, p, nqt, (int)sh);
+  hipLaunchKernelGGL((attn_frag_kernel<QB>), dim3((unsigned)grid), dim3(256), 0, s, p, nqt, (int)sh);
 }
 
 template <int QB, int OUT, int KBX, int MINW, bool P16>
@@ -1752,13 +1700,6 @@ int launch_attn_frag(const AttnFragP& p, hipStream_t s) {
     return (int)hipGetLastError();
   }
   // (Two query blocks per wave -- QB = 2, half the fragment reads per MFMA at half the occupancy -- measured equal.)
-#ifdef BT_DEV
-  // development builds only: BT_ATTN_ABL=128 dumps per-wave phase timings over the gates buffer (tools/attn_probe.py)
-  static const int abl = getenv("BT_ATTN_ABL") ? atoi(getenv("BT_ATTN_ABL")) : 0;
-  if (abl == 128) { launch_v<128, 1>(p, s); return (int)hipGetLastError(); }
-  static const int qb = getenv("BT_ATTN_QB") ? atoi(getenv("BT_ATTN_QB")) : 1;   // two query blocks per wave (A/B only)
-  if (qb == 2) { launch_v<0, 2>(p, s); return (int)hipGetLastError(); }
-#endif
 #if !BT_HALF_IS_BF16
   {
     // Round 6: two query blocks per wave on the hand-scheduled loop (attn_frag_hq2_kernel), bit-identical to the one-block kernel
@@ -1781,6 +1722,6 @@ int launch_attn_frag(const AttnFragP& p, hipStream_t s) {
     }
   }
 #endif
-  launch_v<0, 1>(p, s);
+  launch_v<1>(p, s);
   return (int)hipGetLastError();
 }

@@ -442,7 +442,7 @@ int time_half(prof::State* pf, const bt_pair_weights& pw, const PairRoute& pr, c
   if (pr.outff) {   // x += to_out(ws.ao); x += FF(x) in one launch
     FusedOutFFP f;
     f.x = x; f.M = M; f.C = pw.dim; f.ao = ws.ao; f.wfrag = pr.split ? pw.w_outff_frag_x3 : pw.w_outff_frag[r.fp];
-    f.b1 = pw.b_ff1; f.b2 = pw.b_ff2; f.xb = shadow; f.abl = 0; f.shadow_only = shadow && shadow_only && pr.split;
+    f.b1 = pw.b_ff1; f.b2 = pw.b_ff2; f.xb = shadow; f.shadow_only = shadow && shadow_only && pr.split;
     LAUNCH_CAT(CAT_FF_FUSED, s, launch_outff_fused(f, pr.split ? BT_PREC_F32X3 : r.fp, s), "fused out-projection + feed-forward");
     return BT_OK;
   }
@@ -1104,7 +1104,7 @@ int bt_outff_fused(void* stream, int prec, const bt_pair_weights* w, const void*
   if (!w || !d_ao || !d_x || M <= 0 || w->dim > 128 || !wf) return bt_set_error(BT_ERR_ARG, "bad argument to bt_outff_fused");
   FusedOutFFP f;
   f.x = d_x; f.M = M; f.C = w->dim; f.ao = d_ao; f.wfrag = wf; f.b1 = w->b_ff1; f.b2 = w->b_ff2;
-  f.xb = prec == BT_PREC_F32 ? nullptr : d_xb; f.abl = 0; f.shadow_only = 0;
+  f.xb = prec == BT_PREC_F32 ? nullptr : d_xb; f.shadow_only = 0;
   LAUNCH(launch_outff_fused(f, prec, (hipStream_t)stream), "fused out-projection + feed-forward");
   return BT_OK;
 }

@@ -13,16 +13,12 @@
 // a 4-stage LDS ring (LDS-DMA), fragment-major, one step per barrier, shared by the 4 waves of a workgroup:
 //   [out-proj: KT steps of KT tiles (rows mt*32.., k-tile kt) + KT zero tiles]  (outff only)
 //   [FF: 4C/32 steps of KT tiles of W1p (rows hb*32..) + KT tiles of W2p (rows mt*32.., cols hb*32..)]
-#include <cstdlib>
 #include <type_traits>
 
 #include "chain.h"
 #include "kernels.h"
 
 namespace {
-
-// Development instrumentation (per-wave phase timing, load / store ablations) is compiled in with -DBT_DEV only
-// (BT_DEV_BUILD=1 for beat_this_amd._lib.build): release builds read no environment variables and carry no debug hooks.
 
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -35,16 +31,6 @@ DEVI unsigned pk2_hf(float a, float b) {
 // (buffer_load ... lds, no staging registers) into a ring of NST stages; step s + NST - 1 is issued while
 // step s is consumed, so three steps of L2 latency are covered instead of none (the register-staged
 // version waited for every step's load inside the step: ~2 k cycles x 25 steps per workgroup).
-#ifdef BT_DEV
-// development: per-wave phase timing of attnff_fused_kernel (bt_debug_fused2_buffer; null = off)
-__device__ long long* g_f2_dbg = nullptr;
-#define F2_DBG g_f2_dbg
-#define F2_ABL(p) ((p).abl)
-#else
-#define F2_DBG ((long long*)nullptr)
-#define F2_ABL(p) 0
-#endif
-
 template <typename T, int C>
 struct WRing {
   static constexpr int KT = C / 32;
@@ -65,8 +51,6 @@ struct WRing {
   rsrc_t rs;
   char* lds;
   int tid, wave, total;
-  long long t_wait = 0, t_bar = 0;  // (timing dump only)
-  bool timing = false;
   DEVI void issue(int s) {
     if (s >= total) return;
     char* dst = lds + (s % NST) * STEP_B + wave * 1024;
@@ -81,8 +65,6 @@ struct WRing {
   // make step s readable by every wave (all older LDS-DMA done in every wave), then refill the stage freed by step s-1
   DEVI const char* acquire(int s) {
     const int ahead = min(NST - 2, total - 1 - s);  // younger steps that may stay in flight
-    long long q0 = 0, q1 = 0;
-    if (timing) q0 = clock64();
     // lgkmcnt(0): every LDS read this wave issued has RETURNED before the barrier.  The stage refilled right after the
     // barrier is the one step s - 1 was read from, and hipcc sinks the MFMAs of a step's last tiles (with their still
     // outstanding ds_reads) below this wait: a fast wave's LDS-DMA then raced a slow wave's queued read (WAR; a few
@@ -91,9 +73,7 @@ struct WRing {
     if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * CH) : "memory");
     else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(CH) : "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (timing) q1 = clock64();
     __builtin_amdgcn_s_barrier();
-    if (timing) { const long long q2 = clock64(); t_wait += q1 - q0; t_bar += q2 - q1; }
     issue(s + NST - 1);
     return lds + (s % NST) * STEP_B;
   }
@@ -201,9 +181,8 @@ __global__ __launch_bounds__(256) void outff_fused_kernel(const FusedOutFFP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave index in an SGPR: uniform index math stays scalar)
   const int g = lane >> 5, lr = lane & 31;
   const long tok = ((long)blockIdx.x * 4 + wave) * 32 + lr;
-  const bool ok_st = tok < p.M && !(F2_ABL(p) & 2);
-  const bool ok = tok < p.M && !(F2_ABL(p) & 1);
-  float* xrow = p.x + (tok < p.M ? tok : 0) * C;
+  const bool ok = tok < p.M;
+  float* xrow = p.x + (ok ? tok : 0) * C;
   for (int i = tid; i < 4 * C; i += 256) b1s[i] = p.b1[i];
 
   // attention output row of this token as B-operand fragments (natural k order)
@@ -242,7 +221,7 @@ __global__ __launch_bounds__(256) void outff_fused_kernel(const FusedOutFFP p) {
     for (int r = 0; r < 16; ++r) xn[mt][r] = fmaf(acc[r], OpScale<T>::PW, xn[mt][r]);
   }
   hf* xbrow = p.xb ? reinterpret_cast<hf*>(p.xb) + tok * C * (std::is_same<T, hl>::value ? 2 : 1) : nullptr;
-  ff_tail<T, C, STORE_X>(ws, KT, xn, b1s, p.b2, xrow, xbrow, ok_st, lane, g);
+  ff_tail<T, C, STORE_X>(ws, KT, xn, b1s, p.b2, xrow, xbrow, ok, lane, g);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -264,8 +243,6 @@ __global__ __launch_bounds__(256) void attnff_fused_kernel(const FusedAttnFFP p)
   const long tok = ((long)blockIdx.x * 4 + wave) * 32 + lr;
   const bool ok = tok < p.M;
   float* xrow = p.x + (ok ? tok : 0) * C;
-  long long* dbg = F2_DBG;
-  const long long t_in = dbg ? clock64() : 0;
   for (int i = tid; i < 4 * C; i += 256) b1s[i] = p.b1[i];
 
   float ss = 0.f;
@@ -298,8 +275,6 @@ __global__ __launch_bounds__(256) void attnff_fused_kernel(const FusedAttnFFP p)
   // vmcnt values that assume in-order return, and LDS-DMA returns are not ordered against VGPR returns (observed:
   // RoPE factors consumed before they arrived, a few wrong rows per launch at C = 32).
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  ws.timing = dbg != nullptr;
-  const long long t_ring = dbg ? clock64() : 0;
   ws.prologue();
 
   // ---- step 0: gates of all heads; gate hd sits in register hd of the g = 0 half ----------------------------
@@ -408,12 +383,7 @@ __global__ __launch_bounds__(256) void attnff_fused_kernel(const FusedAttnFFP p)
     for (int a = 0; a < 4; ++a)
 #pragma unroll
       for (int j = 0; j < 4; ++j) xn[mt][4 * a + j] = fmaf(acco[mt][4 * a + j], PW, xv[mt][a][j]);
-  const long long t_ff = dbg ? clock64() : 0;
   ff_tail<T, C>(ws, 1 + 2 * H, xn, b1s, p.b2, xrow, nullptr, ok, lane, g);
-  if (dbg && lane == 0) {
-    long long* d = dbg + ((long)blockIdx.x * 4 + wave) * 6;
-    d[0] = t_ring - t_in; d[1] = t_ff - t_ring; d[2] = clock64() - t_ff; d[3] = ws.t_wait; d[4] = ws.t_bar; d[5] = 0;
-  }
 }
 
 template <typename T>
@@ -454,20 +424,8 @@ int launch_attnff_t(const FusedAttnFFP& p, hipStream_t s) {
 
 }  // namespace
 
-#ifdef BT_DEV
-extern "C" int bt_debug_fused2_buffer(void* buf) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_f2_dbg), &buf, sizeof buf);
-}
-#endif
-
-int launch_outff_fused(const FusedOutFFP& p0, int prec, hipStream_t s) {
-  if (p0.M <= 0) return -2;
-  FusedOutFFP p = p0;
-  p.abl = 0;
-#ifdef BT_DEV
-  static const int abl = getenv("BT_F2_ABL") ? atoi(getenv("BT_F2_ABL")) : 0;
-  p.abl = abl;
-#endif
+int launch_outff_fused(const FusedOutFFP& p, int prec, hipStream_t s) {
+  if (p.M <= 0) return -2;
   if (prec == BT_PREC_F32X3) return BT_HALF_IS_BF16 ? -2 : launch_outff_t<hl>(p, s);
   return prec == BT_PREC_F32 ? launch_outff_t<float>(p, s) : launch_outff_t<hf>(p, s);
 }

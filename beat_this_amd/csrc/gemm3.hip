@@ -27,7 +27,6 @@
 //   * RMSNorm: the producer of the residual stream (EPI_RESID here, gemm2's fp32 epilogues for
 //     frontend.linear) writes per-row partial sums of squares per 64 columns; the consumers (QKV, FF1)
 //     add the partials -- no pass over A for the statistics (LDS-DMA data never visits registers).
-#include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
@@ -274,8 +273,6 @@ DEVI void qkv_gate_tile_x3(const Gemm3P& p, char* smem, int m0, int n0, int n_ti
   }
 }
 
-// ABL (development, BT_G3_ABL = 8): per-wave timing dump (k-loop, waits, epilogue) read by tools/gemm3_probe.py;
-// bits 0 - 2 (no LDS-DMA after the prologue / no GELU / no MFMAs) are ablations that can be instantiated by hand
 // X3: 0 = half operands, 1 = hl32 operands (BT_PREC_F32X3), 2 = "hl8" operands (round 5, BASELINE config 5: the cross terms
 // of the hi + lo product on ONE block-scaled fp8 MFMA per 32-k step).  An hl8 group of 32 columns is 128 B like an hl32 one:
 // [32 hi halves | 32 hi bytes = e4m3(v) | 32 lo bytes = e4m3(2^11 (v - hi))] for a weight, 2^-3 of that in the byte sections of an
@@ -285,7 +282,7 @@ DEVI void qkv_gate_tile_x3(const Gemm3P& p, char* smem, int m0, int n0, int n_ti
 //   acc += hi(P) . hi(Q)                                                        two v_mfma_f32_32x32x16_f16
 // i.e. 64 + 64 matrix-pipe cycles where the three-term form spends 192 (the scaled fp8 MFMA runs at 2.3 x the fp16 rate:
 // tools/ubench/mfma_f8_cross.hip), on the same ring, swizzle, fragment-read count and operand registers.
-template <int EPI, typename CFG, int X3 = 0, int ABL = 0>
+template <int EPI, typename CFG, int X3 = 0>
 __global__ __launch_bounds__(64 * CFG::WGM * CFG::WGN, (CFG::OCC * CFG::WGM * CFG::WGN + 3) / 4)
 void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int nsplit) {
   constexpr int BM = CFG::BM, BN = CFG::BN, BK = CFG::BK, NST = CFG::NST;
@@ -341,7 +338,7 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
   const bool normal = EPI == G3_QKV && kind == 2;
   // the gate column on its own narrow tile (workgroup-uniform, in front of everything: nothing of it inside the k-loop below).
   // hl32 operands on 128 x 128 x 32 tiles only: the half path and the opt-in hl8 form keep the generic tile.
-  if constexpr (BT_QKV_GATE_TILE && EPI == G3_QKV && X3 == 1 && ABL == 0 && BM == 128 && BN == 128 && ROWB == 128 && NW == 4) {
+  if constexpr (BT_QKV_GATE_TILE && EPI == G3_QKV && X3 == 1 && BM == 128 && BN == 128 && ROWB == 128 && NW == 4) {
     if (kind == 3 && p.heads <= 32 && (p.x3 & 15) != 3) {
       qkv_gate_tile_x3<CFG>(p, smem, m0, n0, n_tiles, lane, wave);
       return;
@@ -367,9 +364,6 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
       ok = seq < p.n_seq && t < p.L;
       row = (long)seq * p.L + t;
     }
-#ifdef BT_ABL_HID_WRAP   // development ablation (tools/build_variant.py): see the FF1 store below
-    if (EPI == G3_RESID && X3 && p.K >= 1024 && p.conv_C2 == 0) row &= BT_ABL_HID_WRAP - 1;
-#endif
     // (HL16: LDS chunks 0, 1 = the hi halves of the step's 16 k values, 2, 3 = their lo halves, 64 B further in the group)
     voffA[i] = ok ? (unsigned)(row * p.lda * EB + (HL16 ? (c >> 1) * 64 + (c & 1) * 16 : c * 16)) : OOB;
     if constexpr (EPI == G3_RESID) {  // conv: which of the three time taps exist for this row
@@ -500,20 +494,17 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
     }
   }
   int stage = 0, stage2 = NST - 1;
-  long long t_wait = 0, t_bar = 0, t_loop0 = 0;
-  if constexpr ((ABL & 8) != 0) t_loop0 = clock64();
   for (int kt = 0; kt < nk; ++kt) {
+    // (tq0, tq1: left over from a timing dump that is gone, and unused.  Without this declaration hipcc numbers two scalar
+    // registers of the two hl8 FF1 kernels differently -- same instructions, same order; it stays until those are measured.)
     long long tq0 = 0, tq1 = 0;
-    if constexpr ((ABL & 8) != 0) tq0 = clock64();
     // tile kt has landed in every wave; NST - 2 younger tiles may stay in flight across the barrier
     // lgkmcnt(0): the fragment reads of tile kt - 1 have returned in THIS wave before the barrier -- the stage they came
     // from is refilled right after it (WAR: see WRing::acquire in fused2.hip)
-    if (NST > 2 && kt + 1 < nk && !(ABL & 1)) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NST - 2) * LPS) : "memory");
+    if (NST > 2 && kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NST - 2) * LPS) : "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if constexpr ((ABL & 8) != 0) tq1 = clock64();
     __builtin_amdgcn_s_barrier();
-    if constexpr ((ABL & 8) != 0) { const long long tq2 = clock64(); t_wait += tq1 - tq0; t_bar += tq2 - tq1; }
-    if (kt + NST - 1 < nk && !(ABL & 1)) G3_ISSUE(kt + NST - 1, stage2);
+    if (kt + NST - 1 < nk) G3_ISSUE(kt + NST - 1, stage2);
     const char* st = smem + stage * ST_BYTES;
     if constexpr (X3 == 2) {
       // chunks of a 128-byte row: 0 .. 3 the hi halves (k16 piece m = chunks 2 m, 2 m + 1), 4, 5 the hi bytes, 6, 7 the lo
@@ -555,7 +546,7 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
       }
     } else if constexpr (!X3) {
 #pragma unroll
-      for (int m = 0; m < ((ABL & 4) ? 0 : MS); ++m) {
+      for (int m = 0; m < MS; ++m) {
         hfx8 fp[NP], fq[NQ];
 #pragma unroll
         for (int a = 0; a < NP; ++a) fp[a] = *reinterpret_cast<const hfx8*>(st + pofs + a * 32 * ROWB + kc[m]);
@@ -568,7 +559,7 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
       }
     } else {
 #pragma unroll
-      for (int m = 0; m < ((ABL & 4) ? 0 : MS / 2); ++m) {  // k16 piece m: hi at chunk pair m, lo at chunk pair m + MS / 2
+      for (int m = 0; m < MS / 2; ++m) {  // k16 piece m: hi at chunk pair m, lo at chunk pair m + MS / 2
         hfx8 ph[NP], pl[NP], qh[NQ], ql[NQ];
 #pragma unroll
         for (int a = 0; a < NP; ++a) {
@@ -600,8 +591,6 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
   }
 
 #undef G3_ISSUE
-  long long t_loop1 = 0;
-  if constexpr ((ABL & 8) != 0) t_loop1 = clock64();
   // ---- epilogue ---------------------------------------------------------------------------------------------
   // FF1 / RESID results leave through LDS (free after the k-loop), one private 8 KB area per wave, one 32-token
   // block at a time: lanes write their token's pieces with the 16-byte chunk index XORed by the row (conflict free),
@@ -650,15 +639,7 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
         const int r = ps * 4 + r4;
         const u32x4 w = *reinterpret_cast<const u32x4*>(wst + r * 256 + (cp << 4));
         const long row = (long)row0 + 32 * b + r;
-#ifdef BT_ABL_HID_WRAP
-        // Development ablation, results are garbage by construction: the hidden activation of row r lives at row r mod
-        // BT_ABL_HID_WRAP (a power of two; 2048 rows = 16.8 MB of hl32: resident in L2 / MALL), FF2 reads it from there -- the
-        // forward then runs every MFMA, LDS-DMA and epilogue instruction of the real one but the hidden activation's HBM round
-        // trip: an UPPER BOUND on what a fused layer tail that never writes it could save.
-        if (row < p.M) *reinterpret_cast<u32x4*>(out8 + ((row & (BT_ABL_HID_WRAP - 1)) * p.ldo + nb0) * 4 + ((cp ^ (r & 15)) << 4)) = w;
-#else
         if (row < p.M) ST_STREAM(reinterpret_cast<u32x4*>(out8 + (row * p.ldo + nb0) * 4 + ((cp ^ (r & 15)) << 4)), w);
-#endif
       }
     }
   } else if constexpr (EPI == G3_FF1) {
@@ -670,10 +651,7 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
       for (int a = 0; a < FB; ++a) {
         float v[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float u = fmaf(acc[a][b][r], rs[b], bqv[a][r >> 2][r & 3]);
-          v[r] = (ABL & 2) ? u : gelu_tanh(u);
-        }
+        for (int r = 0; r < 16; ++r) v[r] = gelu_tanh(fmaf(acc[a][b][r], rs[b], bqv[a][r >> 2][r & 3]));
         u32x4 piece[2];
         pack_row_hf(v, piece);
 #pragma unroll
@@ -857,18 +835,9 @@ void gemm3_kernel(const Gemm3P p, int n_tiles, int total_tiles, int per_xcd, int
     }
   }
   if constexpr (X3) flag_range(p.status, amax, (p.x3 & G3_X3_OUT_F8) ? HL8_ACT_MAX : 65504.f);   // (hl8 activations end earlier: common.h)
-  if constexpr ((ABL & 8) != 0) {  // development timing dump over the head of the (already written) output
-    const long long t_end = clock64();
-    __syncthreads();
-    if (lane == 0) {
-      long long* dbg = reinterpret_cast<long long*>(EPI == G3_RESID ? p.out : (void*)const_cast<float*>(p.ssq_in));
-      long long* d = dbg + ((long)blockIdx.x * NW + wave) * 4;
-      d[0] = t_loop1 - t_loop0; d[1] = t_wait; d[2] = t_bar; d[3] = t_end - t_loop1;
-    }
-  }
 }
 
-template <int EPI, typename CFG, int X3 = 0, int ABL = 0>
+template <int EPI, typename CFG, int X3 = 0>
 void launch_cfg(const Gemm3P& p, hipStream_t s) {
   const int n_tiles = (p.N + CFG::BN - 1) / CFG::BN;
   const long rows = p.epi == G3_QKV ? (long)p.n_seq * p.nblk * 32 : (long)p.M;
@@ -889,7 +858,7 @@ void launch_cfg(const Gemm3P& p, hipStream_t s) {
     per = (m_tiles + per_m - 1) / per_m * (n_tiles / nsplit);
   }
   dim3 grid((unsigned)(per * 8)), block(64 * CFG::WGM * CFG::WGN);
-  hipLaunchKernelGGL((gemm3_kernel<EPI, CFG, X3, ABL>), grid, block, 0, s, p, n_tiles, (int)total, (int)per, nsplit);
+  hipLaunchKernelGGL((gemm3_kernel<EPI, CFG, X3>), grid, block, 0, s, p, n_tiles, (int)total, (int)per, nsplit);
 }
 
 }  // namespace
@@ -921,20 +890,13 @@ bool gemm3_supported(const Gemm3P& p) {
 
 int launch_gemm3(const Gemm3P& p, hipStream_t s) {
   if (!gemm3_supported(p)) return -2;
-#ifdef BT_DEV
-  // development builds only: BT_G3_ABL (timing dump), BT_G3_BIG = 0 / 1 forces the tile configuration
-  static const int abl = getenv("BT_G3_ABL") ? atoi(getenv("BT_G3_ABL")) : 0;
-  static const int force_big = getenv("BT_G3_BIG") ? atoi(getenv("BT_G3_BIG")) : -1;
-#else
-  constexpr int abl = 0, force_big = -1;
-#endif
   // Measured on the final0 shapes (M = 24000): for K = 512 the 256^2 configuration is no faster in isolation (FF1 85 vs
   // 86 us) and slower inside the forward (one workgroup per CU cannot hide its epilogue behind another workgroup's
   // k-loop); for the long-K residual GEMM (FF2, K = 4 D: half the operand traffic per flop, epilogue amortised over 32
   // k-steps) it wins inside the forward as well, 0.452 vs 0.487 ms per step.
   const bool big_ok = p.epi != G3_QKV && p.N % 256 == 0;
   // (x3 = 2 / 3 through the single-operator entry bt_gemm3 forces the 256-row / the 128-row configuration: tools/x3_probe.py)
-  const int force = (p.x3 & 15) == 2 ? 1 : (p.x3 & 15) == 3 ? 0 : force_big;
+  const int force = (p.x3 & 15) == 2 ? 1 : (p.x3 & 15) == 3 ? 0 : -1;
   // (x3 = 4 / 5 force the 256 x 128 k16 / the 64 x 128 tiles further down)
   const bool forced_small = (p.x3 & 15) == 4 || (p.x3 & 15) == 5;
   // BT_PREC_F32X3, round 6: the 256-column tiles only when they fill the chip (>= 160 tiles of 192 rows: M >= 15 k rows at N = 512).  A
@@ -962,21 +924,8 @@ int launch_gemm3(const Gemm3P& p, hipStream_t s) {
   // (round 6, on their three-stage ring: also the short-K residual GEMMs -- the out-projection -- of every forward below 20 k rows:
   // 19.5 / 20.5 / 30.1 / 34.0 / 47.1 us against 22.7 / 23.4 / 32.6 / 35.5 / 51.1 us on the 128 x 128 tiles at M = 4.5 / 6 / 9 / 12 / 16.5 k)
   const bool hx = p.x3 && p.epi == G3_RESID && !big && !rows192 && !mx &&
-                  ((p.x3 & 15) == 5 || ((p.x3 & 15) <= 1 && force_big < 0 && (sx_tiles < 256 || (p.K < 1024 && p.M < 20000))));
+                  ((p.x3 & 15) == 5 || ((p.x3 & 15) <= 1 && (sx_tiles < 256 || (p.K < 1024 && p.M < 20000))));
   if (p.x3) {
-#ifdef BT_DEV
-    // development: ablations of the x3 kernel (results are garbage): BT_G3_ABL = 1 no LDS-DMA after the prologue, 4 no MFMAs
-    if (abl == 8 && p.epi == G3_FF1) { launch_cfg<G3_FF1, G3CfgSX, true, 8>(p, s); return (int)hipGetLastError(); }
-    if (abl == 1 || abl == 4) {
-      const bool b = big || rows192;
-      if (p.epi == G3_FF1) { if (abl == 1) { if (b) launch_cfg<G3_FF1, G3CfgBX, true, 1>(p, s); else launch_cfg<G3_FF1, G3CfgSX, true, 1>(p, s); }
-                             else { if (b) launch_cfg<G3_FF1, G3CfgBX, true, 4>(p, s); else launch_cfg<G3_FF1, G3CfgSX, true, 4>(p, s); } }
-      else if (p.epi == G3_RESID) { if (abl == 1) { if (b) launch_cfg<G3_RESID, G3CfgBX, true, 1>(p, s); else launch_cfg<G3_RESID, G3CfgSX, true, 1>(p, s); }
-                                    else { if (b) launch_cfg<G3_RESID, G3CfgBX, true, 4>(p, s); else launch_cfg<G3_RESID, G3CfgSX, true, 4>(p, s); } }
-      else { if (abl == 1) launch_cfg<G3_QKV, G3CfgSX, true, 1>(p, s); else launch_cfg<G3_QKV, G3CfgSX, true, 4>(p, s); }
-      return (int)hipGetLastError();
-    }
-#endif
     if (f8) {
       if (p.epi == G3_QKV) launch_cfg<G3_QKV, G3CfgSX, 2>(p, s);
       else if (p.epi == G3_FF1) { if (big) launch_cfg<G3_FF1, G3CfgBX, 2>(p, s); else launch_cfg<G3_FF1, G3CfgSX, 2>(p, s); }
@@ -1006,16 +955,9 @@ int launch_gemm3(const Gemm3P& p, hipStream_t s) {
   switch (p.epi) {
     case G3_FF1:
       if (big) launch_cfg<G3_FF1, CfgB>(p, s);
-#ifdef BT_DEV
-      else if (abl == 8) launch_cfg<G3_FF1, CfgS, false, 8>(p, s);
-#endif
       else launch_cfg<G3_FF1, CfgS>(p, s);
       break;
     case G3_RESID:
-#ifdef BT_DEV
-      if (big && abl == 8) { launch_cfg<G3_RESID, CfgB, false, 8>(p, s); break; }
-      if (!big && abl == 8) { launch_cfg<G3_RESID, CfgS, false, 8>(p, s); break; }
-#endif
       if (rows192) launch_cfg<G3_RESID, G3CfgT>(p, s);
       else if (big) launch_cfg<G3_RESID, CfgB>(p, s);
       else launch_cfg<G3_RESID, CfgS>(p, s);

@@ -162,7 +162,6 @@ struct FusedOutFFP {  // x += Wout . ao ; x += FF(x)      (time direction, after
   const void* wfrag;                 // bt_pair_weights.w_outff_frag
   const float* b1; const float* b2;
   void* xb;                          // optional half shadow of the new x
-  int abl;                           // development (BT_F2_ABL)
   // BT_PREC_F32X3, C >= 64: only the shadow of the new x is written, x itself stays what it was (the frontend block's conv on
   // gemm3 reads the shadow alone and nothing reads the block's x again: Route::Block::x_dead).  Needs xb.
   int shadow_only;

@@ -2,7 +2,7 @@
 """Generator of the hand-scheduled key loop of attn_frag_hq2_kernel (csrc/attn2.hip), the fp16 path's attention on two query
 blocks per wave (round 6): writes csrc/attn_hq2_loop.inc.
 
-    python tools/gen/attn_hq2_loop.py           (the .inc is committed; re-run after editing the schedule)
+    python tools/gen/attn_hq2_loop.py [-o PATH] (the .inc is committed; re-run after editing the schedule)
 
 Same design as tools/gen/attn_x3_loop.py's P16 statement with the lo terms gone -- ONE inline-assembly statement, two 32-query
 blocks A and B per wave half a step apart, a ring of four [K tile | V tile] buffers of 64 keys:
@@ -17,6 +17,7 @@ ARITHMETIC IS THAT OF attn_frag_kernel, BIT FOR BIT (the forward picks the kerne
 k0 . q0 + k1 . q1 in that order on the accumulator input, exp2 in place, round-to-nearest packing, row sums H[0:2], H[2:4],
 H[4:6], H[6:8] in that order, P.V = v0 . H[0:4] then v1 . H[4:8].
 """
+import argparse
 import os
 
 KBX = 2                      # 32-key blocks per LDS tile
@@ -160,7 +161,9 @@ def build():
 
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(here, "..", "..", "beat_this_amd", "csrc", "attn_hq2_loop.inc")
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("-o", "--output", metavar="PATH", help="file to write (default: the committed csrc/attn_hq2_loop.inc)")
+    out = ap.parse_args().output or os.path.join(here, "..", "..", "beat_this_amd", "csrc", "attn_hq2_loop.inc")
     lines = build()
     with open(out, "w") as f:
         f.write("// GENERATED by tools/gen/attn_hq2_loop.py -- do not edit; the schedule is described there.\n")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Generator of the hand-scheduled key loop of attn_frag_x3q2_kernel (csrc/attn2.hip): writes csrc/attn_x3_loop.inc.
 
-    python tools/gen/attn_x3_loop.py            (the .inc is committed; re-run after editing the schedule)
+    python tools/gen/attn_x3_loop.py [-o PATH]  (the .inc is committed; re-run after editing the schedule)
 
 The loop is ONE inline-assembly statement: hipcc allocates the operands that are used as whole vectors (Q fragments, the
 reference-maximum splats, the output accumulators), everything that is touched element by element lives in physical
@@ -31,6 +31,7 @@ arithmetic is the two-block statement's instruction for instruction.  What B's w
 wait states: behind a Y phase (A's last score MFMA -> A's first exponential) and behind an X phase (A's last conversion ->
 A's first P.V MFMA).
 """
+import argparse
 import os
 
 KBX = 2                      # 32-key blocks per LDS tile
@@ -274,8 +275,7 @@ def dma_group(piece, s_dst, s_off):
             f"buffer_load_dwordx4 {o('dmaoff')}, {rs}, s{ST + 2} offen lds"]
 
 
-ABL = 0   # development ablations (results are garbage): 1 no softmax VALU, 2 no fragment reads in the loop, 4 no refill / barrier,
-          # 8 no P.V MFMAs, 16 no score MFMAs
+ABL = 0   # --abl N: a throwaway listing with parts of the three-term loop left out (bits: see main); never built
 
 
 def build():
@@ -326,40 +326,50 @@ def build():
     return A
 
 
+def write_macro(f, macro, lines):
+    f.write(f"#define {macro} \\\n")
+    for x in lines:
+        f.write(f'  "{x}\\n\\t" \\\n')
+    f.write('  ""\n')
+
+
 def main():
     global ABL, ONE
     here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(here, "..", "..", "beat_this_amd", "csrc", "attn_x3_loop.inc")
+    csrc = os.path.realpath(os.path.join(here, "..", "..", "beat_this_amd", "csrc"))
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("-o", "--output", metavar="PATH", help="file to write (default: the committed csrc/attn_x3_loop.inc)")
+    ap.add_argument("--abl", type=int, default=0, metavar="N",
+                    help="a throwaway listing of the three-term statement with parts left out, for studying what the loop spends "
+                         "where (its results are garbage): 1 no softmax VALU, 2 no fragment reads in the loop, 4 no refill / "
+                         "barrier, 8 no P.V MFMAs, 16 no score MFMAs.  Needs -o, outside the sources")
+    args = ap.parse_args()
+    out = args.output or os.path.join(csrc, "attn_x3_loop.inc")
+    if args.abl:
+        if not args.output or os.path.commonpath([csrc, os.path.realpath(out)]) == csrc:
+            ap.error("--abl writes a listing that must never be built: give -o PATH outside beat_this_amd/csrc")
+        ABL = args.abl
+        with open(out, "w") as f:
+            f.write(f"// ablated listing (--abl {ABL}) of tools/gen/attn_x3_loop.py: NOT a source, its results are garbage\n")
+            write_macro(f, "ATTN_X3Q2_ASM", build())
+        print(f"wrote {os.path.normpath(out)}")
+        return
     lines = build()
     n_mfma = sum("v_mfma" in x for x in lines)
     with open(out, "w") as f:
         f.write("// GENERATED by tools/gen/attn_x3_loop.py -- do not edit; the schedule is described there and in DESIGN.md.\n")
         f.write(f"// {len(lines)} instructions, {n_mfma} MFMAs; operands: " + ", ".join(f"%{i} {n}" for i, n in enumerate(OPS)) + "\n")
-        f.write("// (-DBT_X3Q2_ABL=n, development builds: ablated forms of the loop whose results are garbage -- what the loop spends where)\n")
-        f.write("#ifndef BT_X3Q2_ABL\n#define BT_X3Q2_ABL 0\n#endif\n")
-        for abl in (0, 1, 2, 3, 4, 7, 8, 16, 9, 17):
-            ABL = abl
-            f.write(f"#if BT_X3Q2_ABL == {abl}\n#define ATTN_X3Q2_ASM \\\n")
-            for x in build():
-                f.write(f'  "{x}\\n\\t" \\\n')
-            f.write('  ""\n#endif\n')
-        ABL = 0
+        write_macro(f, "ATTN_X3Q2_ASM", lines)
         lp = build_p()
         f.write(f"// P16 statement: {len(lp)} instructions, {sum('v_mfma_f32_32x32' in x for x in lp)} big + "
                 f"{sum('v_mfma_f32_4x4x4' in x for x in lp)} small MFMAs; operands as above with lA / lB four registers each\n")
-        f.write("#define ATTN_X3Q2P_ASM \\\n")
-        for x in lp:
-            f.write(f'  "{x}\\n\\t" \\\n')
-        f.write('  ""\n')
+        write_macro(f, "ATTN_X3Q2P_ASM", lp)
         ONE = True
         for macro, lo in (("ATTN_X3Q2_ONE_ASM", build()), ("ATTN_X3Q2P_ONE_ASM", build_p())):
             f.write(f"// one-block form ({macro}: query block B switched off): {len(lo)} instructions, "
                     f"{sum('v_mfma_f32_32x32' in x for x in lo)} big + {sum('v_mfma_f32_4x4x4' in x for x in lo)} small MFMAs; "
                     "operands and clobbers of the two-block statement\n")
-            f.write(f"#define {macro} \\\n")
-            for x in lo:
-                f.write(f'  "{x}\\n\\t" \\\n')
-            f.write('  ""\n')
+            write_macro(f, macro, lo)
         ONE = False
         f.write("#define ATTN_X3Q2_CLOBBERS " + ", ".join(f'"v{i}"' for i in CLOBBER_V) + ", " +
                 ", ".join(f'"s{i}"' for i in CLOBBER_S) + ', "scc", "memory"\n')
