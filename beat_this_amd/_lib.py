@@ -144,6 +144,18 @@ class FrontArgs(C.Structure):   # bt_front_args
                 ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
+class FrontBnArgs(C.Structure):   # bt_front_bn_args
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("reserved0", C.c_int32),
+                ("reserved1", C.c_int32), ("reserved2", C.c_int32), ("reserved3", C.c_int32), ("w", C.c_void_p),
+                ("bn_w", C.c_void_p), ("bn_b", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p),
+                ("bn_tracked", C.c_void_p), ("bn1_w", C.c_void_p), ("bn1_b", C.c_void_p), ("bn1_mean", C.c_void_p),
+                ("bn1_var", C.c_void_p), ("bn1_tracked", C.c_void_p), ("save_mean", C.c_void_p), ("save_rstd", C.c_void_p),
+                ("save1_mean", C.c_void_p), ("save1_rstd", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
+                ("save_pre", C.c_void_p), ("gy", C.c_void_p), ("gx", C.c_void_p), ("g_w", C.c_void_p), ("g_bn_w", C.c_void_p),
+                ("g_bn_b", C.c_void_p), ("g_bn1_w", C.c_void_p), ("g_bn1_b", C.c_void_p), ("ws", C.c_void_p),
+                ("ws_bytes", C.c_size_t)]
+
+
 class OptimTensor(C.Structure):   # bt_optim_tensor
     _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int64), ("group", C.c_int32), ("reserved", C.c_int32)]
 
@@ -280,6 +292,10 @@ EXPORTS = {
     "bt_front_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bt_front_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontArgs)]),
     "bt_front_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontArgs)]),
+    "bt_front_bn_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "bt_front_bn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bt_front_bn_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontBnArgs)]),
+    "bt_front_bn_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontBnArgs)]),
     "bt_optim_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "bt_optim_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
                                 C.c_int64, C.POINTER(C.c_int64)]),

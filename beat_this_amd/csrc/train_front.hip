@@ -7,7 +7,10 @@
 // Activations are the library's (b, t, f, c), channels last, fp32; the parameters are read in the reference's layout straight
 // from the nn.Parameter storage and the gradients are written in that layout.  BatchNorm runs on its running statistics
 // (eval-mode arithmetic): s = weight / sqrt(var + 1e-5), sh = bias - mean s, evaluated in fp64 and rounded once, by a small
-// launch at the head of every call (into the call's workspace).
+// launch at the head of every call (into the call's workspace).  The bt_front_bn_* entry points run the
+// stem and the conv unit on the statistics of the call's own batch instead -- torch's training-mode BatchNorm: the same
+// kernels, the fold table written by the launch that finishes the statistics and moves the running buffers, one elementwise
+// launch for the GELU, and one that centres the gradient at each BatchNorm's input.
 //
 // The conv unit's three matrix products are implicit GEMMs on v_mfma_f32_32x32x2_f32: the operand tiles are staged into LDS
 // straight from the activation (a row of the implicit A matrix is three runs of 2 Cin floats at t - 1, t, t + 1, zeros
@@ -83,6 +86,131 @@ void colsum(hipStream_t s, const float* a, long M, int N, float* part, float* ou
   const int chunks = cs_chunks(M);
   hipLaunchKernelGGL(front_colsum_kernel, dim3((unsigned)chunks, blocks_of(N, 256)), dim3(256), 0, s, a, M, N, part);
   hipLaunchKernelGGL(front_reduce_kernel, dim3(blocks_of(N, 256)), dim3(256), 0, s, (const float*)part, (long)N, chunks, out);
+}
+
+// ---- batch-statistics BatchNorm ----------------------------------------------------------------------------
+// part[chunk][0][j] = the mean of column j over the chunk's CS_ROWS rows, part[chunk][1][j] = the sum of squared deviations from
+// that mean: rows ascending, fp64 (centred per chunk, so nothing cancels whatever the column's offset is)
+__global__ __launch_bounds__(256) void bn_moments_kernel(const float* a, long M, int N, double* part) {
+  const int j = blockIdx.y * 256 + threadIdx.x;
+  if (j >= N) return;
+  const long mb = (long)blockIdx.x * CS_ROWS, me = std::min<long>(M, mb + CS_ROWS);
+  const float* col = a + mb * N + j;
+  double sum = 0.0, mean, m2 = 0.0;
+  if (me - mb == CS_ROWS) {   // a whole chunk: its column in registers, all loads in flight at once, the tensor read once
+    float v[CS_ROWS];
+#pragma unroll
+    for (int r = 0; r < CS_ROWS; ++r) v[r] = col[(long)r * N];
+#pragma unroll
+    for (int r = 0; r < CS_ROWS; ++r) sum += (double)v[r];
+    mean = sum / (double)CS_ROWS;
+#pragma unroll
+    for (int r = 0; r < CS_ROWS; ++r) {
+      const double d = (double)v[r] - mean;
+      m2 += d * d;
+    }
+  } else {                    // the ragged last chunk: the same sums in the same order
+    const int rows = (int)(me - mb);
+    for (int r = 0; r < rows; ++r) sum += (double)col[(long)r * N];
+    mean = sum / (double)rows;
+    for (int r = 0; r < rows; ++r) {
+      const double d = (double)col[(long)r * N] - mean;
+      m2 += d * d;
+    }
+  }
+  part[((long)blockIdx.x * 2) * N + j] = mean;
+  part[((long)blockIdx.x * 2 + 1) * N + j] = m2;
+}
+
+// count, mean and sum of squared deviations of a run of rows; `a` then `b`, the run on the left first (Chan et al.)
+struct Moments {
+  double n, mean, m2;
+};
+__device__ inline Moments merge(const Moments& a, const Moments& b) {
+  if (b.n == 0.0) return a;
+  if (a.n == 0.0) return b;
+  const double tot = a.n + b.n, d = b.mean - a.mean;
+  return Moments{tot, a.mean + d * (b.n / tot), a.m2 + b.m2 + d * d * (a.n * b.n / tot)};
+}
+
+// One workgroup per channel merges the chunks' moments in chunk order, fp64: thread t its run of ceil(chunks / 256) consecutive
+// chunks one by one, then the 256 runs pairwise, the left neighbour first (a fixed tree over the shapes alone; one thread
+// walking 6000 chunks took 1.5 ms).  Thread 0 rounds once: the batch's mean and 1 / sqrt(var_b + eps) go to save_mean /
+// save_rstd, the fold table is built from those ROUNDED values (the backward rebuilds the same table from them, bit for bit), and
+// the running statistics move: running_mean = 0.9 running_mean + 0.1 mean_b, running_var = 0.9 running_var + 0.1 var_b n /
+// (n - 1); channel 0 counts the batch.
+__global__ __launch_bounds__(256) void bn_finish_kernel(const double* part, long M, int C, int chunks, const float* w, const float* b,
+                                                        float* fold, float* save_mean, float* save_rstd, float* run_mean,
+                                                        float* run_var, int64_t* tracked) {
+  __shared__ Moments runs[256];
+  const int c = blockIdx.x, t = threadIdx.x;
+  const int per = (chunks + 255) / 256, k1 = std::min(chunks, (t + 1) * per);
+  Moments m{0.0, 0.0, 0.0};
+  for (int k = t * per; k < k1; ++k) {
+    const double rows = (double)(std::min<long>(M, (long)(k + 1) * CS_ROWS) - (long)k * CS_ROWS);
+    m = merge(m, Moments{rows, part[((long)k * 2) * C + c], part[((long)k * 2 + 1) * C + c]});
+  }
+  runs[t] = m;
+  __syncthreads();
+  for (int step = 1; step < 256; step <<= 1) {
+    if (t % (2 * step) == 0) runs[t] = merge(runs[t], runs[t + step]);
+    __syncthreads();
+  }
+  if (t != 0) return;
+  if (c == 0 && tracked) *tracked += 1;
+  const double n = runs[0].n, mean = runs[0].mean, var = runs[0].m2 / n;
+  const float mean_f = (float)mean, rstd_f = (float)(1.0 / sqrt(var + 1e-5));
+  const double s = (double)w[c] * (double)rstd_f;
+  fold[c] = (float)s;
+  fold[C + c] = (float)((double)b[c] - (double)mean_f * s);
+  fold[2 * C + c] = rstd_f;
+  fold[3 * C + c] = mean_f;
+  save_mean[c] = mean_f;
+  save_rstd[c] = rstd_f;
+  run_mean[c] = (float)(0.9 * (double)run_mean[c] + 0.1 * mean);
+  run_var[c] = (float)(0.9 * (double)run_var[c] + 0.1 * (var * (n / (n - 1.0))));
+}
+
+// the backward's fold table, from the forward's saved batch statistics
+__global__ __launch_bounds__(256) void bn_fold_saved_kernel(const float* w, const float* b, const float* mean, const float* rstd, int C,
+                                                            float* fold) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const double s = (double)w[c] * (double)rstd[c];
+  fold[c] = (float)s;
+  fold[C + c] = (float)((double)b[c] - (double)mean[c] * s);
+  fold[2 * C + c] = rstd[c];
+  fold[3 * C + c] = mean[c];
+}
+
+// y = gelu(s pre + sh), the expression of conv_gemm<0>'s epilogue
+__global__ __launch_bounds__(256) void bn_gelu_kernel(const float* pre, const float* fold, long n, int C, float* y) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = (int)(i % C);
+  y[i] = gelu_f(fold[c] * pre[i] + fold[C + c]);
+}
+
+// The statistics are functions of the batch: g [rows, C], the gradient at the BatchNorm's output (times gelu'), becomes
+// g - g_bias / n - xhat g_weight / n in place; v is the BatchNorm's input, gb / gw the two column sums.  With gx: gx = s (that)
+// and g stays as it is (bn1d, whose output gradient nothing reads afterwards).
+__global__ __launch_bounds__(256) void bn_centre_kernel(float* g, const float* v, const float* fold, const float* gb, const float* gw,
+                                                        long n, int C, float rows, float* gx) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = (int)(i % C);
+  const float xhat = (v[i] - fold[3 * C + c]) * fold[2 * C + c];
+  const float r = g[i] - gb[c] / rows - xhat * (gw[c] / rows);
+  if (gx) gx[i] = r * fold[c];
+  else g[i] = r;
+}
+
+void batch_stats(hipStream_t s, const float* a, long M, int C, double* part, const float* w, const float* b, float* fold,
+                 float* save_mean, float* save_rstd, float* run_mean, float* run_var, int64_t* tracked) {
+  const int chunks = cs_chunks(M);
+  hipLaunchKernelGGL(bn_moments_kernel, dim3((unsigned)chunks, blocks_of(C, 256)), dim3(256), 0, s, a, M, C, part);
+  hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)C), dim3(256), 0, s, (const double*)part, M, C, chunks, w, b, fold,
+                     save_mean, save_rstd, run_mean, run_var, tracked);
 }
 
 // ---- conv unit -------------------------------------------------------------------------------------------------------------
@@ -170,7 +298,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvP p) {
     if (row >= GM) continue;
     if (MODE == 0) {
       p.out[row * p.Cout + col] = acc[r];
-      p.out2[row * p.Cout + col] = gelu_f(p.fold[col] * acc[r] + p.fold[p.Cout + col]);
+      if (p.out2) p.out2[row * p.Cout + col] = gelu_f(p.fold[col] * acc[r] + p.fold[p.Cout + col]);   // (null: batch statistics)
     } else if (MODE == 1) {
       p.out[row * C2 + col] = acc[r];
     } else {
@@ -238,6 +366,24 @@ __global__ __launch_bounds__(256) void stem_gpre_kernel(const float* x, const fl
   const float gv = gy[i] * gelu_grad_f(f2[co] * pre + f2[STEM_C + co]);
   gp[i] = gv;
   gh[i] = gv * ((pre - f2[3 * STEM_C + co]) * f2[2 * STEM_C + co]);
+}
+
+// batch statistics: pre alone, staged in the workspace for its statistics and the GELU pass
+__global__ __launch_bounds__(256) void stem_pre_kernel(const float* x, const float* w, const float* f1, long BT, int T, float* pre) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= BT * STEM_F * STEM_C) return;
+  pre[i] = stem_pre(x, w, f1, T, i / (STEM_F * STEM_C), (int)((i / STEM_C) % STEM_F), (int)(i % STEM_C));
+}
+
+// bn_centre_kernel for bn2d, whose input is recomputed
+__global__ __launch_bounds__(256) void stem_centre_kernel(const float* x, const float* w, const float* f1, const float* f2, float* g,
+                                                          const float* gb, const float* gw, long BT, int T, float rows) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= BT * STEM_F * STEM_C) return;
+  const int co = (int)(i % STEM_C), fo = (int)((i / STEM_C) % STEM_F);
+  const float pre = stem_pre(x, w, f1, T, i / (STEM_F * STEM_C), fo, co);
+  const float xhat = (pre - f2[3 * STEM_C + co]) * f2[2 * STEM_C + co];
+  g[i] = g[i] - gb[co] / rows - xhat * (gw[co] / rows);
 }
 
 // part[chunk][co][df][dt] = sum over the chunk's DW_ROWS rows (b, t, fo) of g_conv[row][co] xn(b, t + dt - 1, 4 fo + df)
@@ -386,6 +532,78 @@ void fold(hipStream_t s, const float* w, const float* b, const float* mean, cons
 
 dim3 conv_grid(long GM, int GN, int chunks) { return dim3(blocks_of(GN, GT), blocks_of(GM, GT), (unsigned)chunks); }
 
+// the conv unit's backward-data and backward-weight GEMMs on p.g = g_pre (they multiply by s = p.fold while staging)
+void conv_backward_gemms(hipStream_t s, ConvP p, float* part, float* gx, float* g_w) {
+  if (gx) {
+    p.out = gx;
+    hipLaunchKernelGGL(conv_gemm_kernel<1>, conv_grid(p.M, 2 * p.Cin, 1), dim3(256), 0, s, p);
+  }
+  if (g_w) {
+    const int chunks = dw_chunks(p.M);
+    p.out = part;
+    hipLaunchKernelGGL(conv_gemm_kernel<2>, conv_grid(p.Cout, 6 * p.Cin, chunks), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3(blocks_of((long)p.Cout * 6 * p.Cin, 256)), dim3(256), 0, s, (const float*)part,
+                       p.Cout, p.Cin, chunks, g_w);
+  }
+}
+
+// the stem's weight gradient from gp = g_pre
+void stem_dw(hipStream_t s, const float* x, const float* f1, const float* f2, const float* gp, long M, int T, float* part, float* g_w) {
+  const int chunks = dw_chunks(M);
+  hipLaunchKernelGGL(stem_dw_kernel, dim3((unsigned)chunks), dim3(STEM_C * STEM_TAPS), 0, s, x, f1, f2, gp, M, T, part);
+  hipLaunchKernelGGL(front_reduce_kernel, dim3(blocks_of(STEM_C * STEM_TAPS, 256)), dim3(256), 0, s, (const float*)part,
+                     (long)STEM_C * STEM_TAPS, chunks, g_w);
+}
+
+// ---- batch statistics: workspace and argument checks ---------------------------------------------------------------------------
+struct BnLayout {
+  size_t fold, fold1, pre, a, b, c, d, sums, sums1, part, total;
+};
+
+// a chunk's moments are two doubles per column: four floats of the workspace
+BnLayout bn_layout(int unit, int backward, long BT, int F, int C) {
+  BnLayout L{};
+  size_t at = 0;
+  auto take = [&](size_t n) { const size_t o = at; at += up64(n); return o; };
+  if (unit == BT_FRONT_STEM) {
+    const size_t M = (size_t)BT * STEM_F;
+    L.fold1 = take(4 * MEL);
+    L.fold = take(4 * STEM_C);
+    if (backward) {
+      L.a = take(M * STEM_C);          // g_pre
+      L.b = take(M * STEM_C);          // g_pre xhat
+      L.c = take((size_t)BT * MEL);    // gradient of the bn1d output
+      L.d = take((size_t)BT * MEL);    // the same times xhat
+      L.sums = take(2 * STEM_C);       // g_bias, g_weight of bn2d when the caller wants none
+      L.sums1 = take(2 * MEL);         // the same of bn1d
+      L.part = take(std::max({(size_t)dw_chunks(M) * STEM_C * STEM_TAPS, (size_t)cs_chunks(M) * STEM_C, (size_t)cs_chunks(BT) * MEL}));
+    } else {
+      L.pre = take(M * STEM_C);
+      L.part = take(4 * std::max((size_t)cs_chunks(M) * STEM_C, (size_t)cs_chunks(BT) * MEL));
+    }
+  } else {
+    const size_t M = (size_t)BT * (F / 2), Cout = 2 * (size_t)C;
+    L.fold = take(4 * Cout);
+    if (backward) {
+      L.a = take(M * Cout);
+      L.b = take(M * Cout);
+      L.sums = take(2 * Cout);
+      L.part = take(std::max((size_t)dw_chunks(M) * Cout * 6 * C, (size_t)cs_chunks(M) * Cout));
+    } else {
+      L.part = take(4 * (size_t)cs_chunks(M) * Cout);
+    }
+  }
+  L.total = at;
+  return L;
+}
+
+const char* bn_check_shape(int unit, int B, int T, int F, int C) {
+  if (unit != BT_FRONT_STEM && unit != BT_FRONT_CONV) return "batch statistics: unit must be BT_FRONT_STEM or BT_FRONT_CONV";
+  if (const char* e = check_shape(unit, B, T, F, C, 0)) return e;
+  if ((long)B * T * (unit == BT_FRONT_STEM ? 1 : F / 2) < 2) return "Expected more than 1 value per channel when training";
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -475,13 +693,7 @@ int bt_front_backward(void* stream, int unit, const bt_front_args* ap) {
                          ws + L.a, ws + L.b);
       if (a.g_bn_b) colsum(s, ws + L.a, M, STEM_C, ws + L.part, a.g_bn_b);
       if (a.g_bn_w) colsum(s, ws + L.b, M, STEM_C, ws + L.part, a.g_bn_w);
-      if (a.g_w) {
-        const int chunks = dw_chunks(M);
-        hipLaunchKernelGGL(stem_dw_kernel, dim3((unsigned)chunks), dim3(STEM_C * STEM_TAPS), 0, s, a.x, f1, f2,
-                           (const float*)(ws + L.a), M, a.T, ws + L.part);
-        hipLaunchKernelGGL(front_reduce_kernel, dim3(blocks_of(STEM_C * STEM_TAPS, 256)), dim3(256), 0, s, (const float*)(ws + L.part),
-                           (long)STEM_C * STEM_TAPS, chunks, a.g_w);
-      }
+      if (a.g_w) stem_dw(s, a.x, f1, f2, ws + L.a, M, a.T, ws + L.part, a.g_w);
       if (a.gx || a.g_bn1_w || a.g_bn1_b) {
         hipLaunchKernelGGL(stem_dx_kernel, dim3(blocks_of(BT * MEL, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, (const float*)(ws + L.a),
                            BT, a.T, ws + L.c, ws + L.d, a.gx);
@@ -499,18 +711,7 @@ int bt_front_backward(void* stream, int unit, const bt_front_args* ap) {
                          (const float*)(ws + L.fold), M * Cout, Cout, ws + L.a, ws + L.b);
       if (a.g_bn_b) colsum(s, ws + L.a, M, Cout, ws + L.part, a.g_bn_b);
       if (a.g_bn_w) colsum(s, ws + L.b, M, Cout, ws + L.part, a.g_bn_w);
-      ConvP p{a.x, a.w, ws + L.a, ws + L.fold, nullptr, nullptr, a.T, Fo, a.C, Cout, M};
-      if (a.gx) {
-        p.out = a.gx;
-        hipLaunchKernelGGL(conv_gemm_kernel<1>, conv_grid(M, 2 * a.C, 1), dim3(256), 0, s, p);
-      }
-      if (a.g_w) {
-        const int chunks = dw_chunks(M);
-        p.out = ws + L.part;
-        hipLaunchKernelGGL(conv_gemm_kernel<2>, conv_grid(Cout, 6 * a.C, chunks), dim3(256), 0, s, p);
-        hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3(blocks_of((long)Cout * 6 * a.C, 256)), dim3(256), 0, s,
-                           (const float*)(ws + L.part), Cout, a.C, chunks, a.g_w);
-      }
+      conv_backward_gemms(s, ConvP{a.x, a.w, ws + L.a, ws + L.fold, nullptr, nullptr, a.T, Fo, a.C, Cout, M}, ws + L.part, a.gx, a.g_w);
       break;
     }
     case BT_FRONT_LINEAR: {
@@ -535,6 +736,122 @@ int bt_front_backward(void* stream, int unit, const bt_front_args* ap) {
       if (!a.gx) return fail(fn, "null gx");
       swap(s, a.gy, a.B, a.F, a.T, a.C, a.gx);
       break;
+  }
+  return finish(fn);
+}
+
+// ---- batch-statistics BatchNorm: the same kernels, the statistics from the call's own batch -------------
+void bt_front_bn_struct_sizes(int32_t* out) {
+  out[0] = (int32_t)sizeof(bt_front_bn_args);
+  out[1] = (int32_t)offsetof(bt_front_bn_args, w);
+  out[2] = (int32_t)offsetof(bt_front_bn_args, bn_tracked);
+  out[3] = (int32_t)offsetof(bt_front_bn_args, save_mean);
+  out[4] = (int32_t)offsetof(bt_front_bn_args, x);
+  out[5] = (int32_t)offsetof(bt_front_bn_args, gy);
+  out[6] = (int32_t)offsetof(bt_front_bn_args, gx);
+  out[7] = (int32_t)offsetof(bt_front_bn_args, ws);
+  out[8] = (int32_t)offsetof(bt_front_bn_args, ws_bytes);
+}
+
+size_t bt_front_bn_workspace_bytes(int unit, int backward, int B, int T, int F, int C) {
+  if (bn_check_shape(unit, B, T, F, C)) return 0;
+  return bn_layout(unit, backward != 0, (long)B * T, F, C).total * sizeof(float);
+}
+
+int bt_front_bn_forward(void* stream, int unit, const bt_front_bn_args* ap) {
+  const char* fn = "bt_front_bn_forward";
+  if (!ap) return fail(fn, "null argument");
+  const bt_front_bn_args& a = *ap;
+  if (const char* e = bn_check_shape(unit, a.B, a.T, a.F, a.C)) return fail(fn, e);
+  const long BT = (long)a.B * a.T;
+  const BnLayout L = bn_layout(unit, 0, BT, a.F, a.C);
+  if (!a.x || !a.y || !a.ws) return fail(fn, "null x, y or workspace");
+  if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.save_mean || !a.save_rstd)
+    return fail(fn, "null parameter, running buffer or saved-statistics pointer");
+  if ((uintptr_t)a.ws % 8) return fail(fn, "the workspace must be 8-byte aligned");
+  if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)a.ws;
+  double* part = (double*)(ws + L.part);
+  if (unit == BT_FRONT_STEM) {
+    if (!a.bn1_w || !a.bn1_b || !a.bn1_mean || !a.bn1_var || !a.save1_mean || !a.save1_rstd)
+      return fail(fn, "null bn1d parameter, running buffer or saved-statistics pointer");
+    const long M = BT * STEM_F;
+    batch_stats(s, a.x, BT, MEL, part, a.bn1_w, a.bn1_b, ws + L.fold1, a.save1_mean, a.save1_rstd, a.bn1_mean, a.bn1_var, a.bn1_tracked);
+    hipLaunchKernelGGL(stem_pre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, a.x, a.w, (const float*)(ws + L.fold1), BT,
+                       a.T, ws + L.pre);
+    batch_stats(s, ws + L.pre, M, STEM_C, part, a.bn_w, a.bn_b, ws + L.fold, a.save_mean, a.save_rstd, a.bn_mean, a.bn_var, a.bn_tracked);
+    hipLaunchKernelGGL(bn_gelu_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, (const float*)(ws + L.pre),
+                       (const float*)(ws + L.fold), M * STEM_C, STEM_C, a.y);
+  } else {
+    if (!a.save_pre) return fail(fn, "null saved-tensor pointer");
+    const int Cout = 2 * a.C;
+    const long M = BT * (a.F / 2);
+    ConvP p{a.x, a.w, nullptr, nullptr, a.save_pre, nullptr, a.T, a.F / 2, a.C, Cout, M};   // (pre alone: no fold, no GELU output)
+    hipLaunchKernelGGL(conv_gemm_kernel<0>, conv_grid(M, Cout, 1), dim3(256), 0, s, p);
+    batch_stats(s, a.save_pre, M, Cout, part, a.bn_w, a.bn_b, ws + L.fold, a.save_mean, a.save_rstd, a.bn_mean, a.bn_var, a.bn_tracked);
+    hipLaunchKernelGGL(bn_gelu_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, (const float*)a.save_pre,
+                       (const float*)(ws + L.fold), M * Cout, Cout, a.y);
+  }
+  return finish(fn);
+}
+
+int bt_front_bn_backward(void* stream, int unit, const bt_front_bn_args* ap) {
+  const char* fn = "bt_front_bn_backward";
+  if (!ap) return fail(fn, "null argument");
+  const bt_front_bn_args& a = *ap;
+  if (const char* e = bn_check_shape(unit, a.B, a.T, a.F, a.C)) return fail(fn, e);
+  const long BT = (long)a.B * a.T;
+  const BnLayout L = bn_layout(unit, 1, BT, a.F, a.C);
+  if (!a.x || !a.gy || !a.ws) return fail(fn, "null x, upstream gradient or workspace");
+  if (!a.w || !a.bn_w || !a.bn_b || !a.save_mean || !a.save_rstd) return fail(fn, "null parameter or saved-statistics pointer");
+  if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)a.ws;
+  const float* f2 = ws + L.fold;
+  if (unit == BT_FRONT_STEM) {
+    if (!a.bn1_w || !a.bn1_b || !a.save1_mean || !a.save1_rstd) return fail(fn, "null bn1d parameter or saved-statistics pointer");
+    const long M = BT * STEM_F;
+    const float* f1 = ws + L.fold1;
+    float* gb = a.g_bn_b ? a.g_bn_b : ws + L.sums;
+    float* gw = a.g_bn_w ? a.g_bn_w : ws + L.sums + STEM_C;
+    hipLaunchKernelGGL(bn_fold_saved_kernel, dim3(1), dim3(256), 0, s, a.bn1_w, a.bn1_b, (const float*)a.save1_mean,
+                       (const float*)a.save1_rstd, MEL, ws + L.fold1);
+    hipLaunchKernelGGL(bn_fold_saved_kernel, dim3(1), dim3(256), 0, s, a.bn_w, a.bn_b, (const float*)a.save_mean,
+                       (const float*)a.save_rstd, STEM_C, ws + L.fold);
+    hipLaunchKernelGGL(stem_gpre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, a.gy, BT, a.T, ws + L.a,
+                       ws + L.b);
+    colsum(s, ws + L.a, M, STEM_C, ws + L.part, gb);
+    colsum(s, ws + L.b, M, STEM_C, ws + L.part, gw);
+    hipLaunchKernelGGL(stem_centre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, ws + L.a,
+                       (const float*)gb, (const float*)gw, BT, a.T, (float)M);
+    if (a.g_w) stem_dw(s, a.x, f1, f2, ws + L.a, M, a.T, ws + L.part, a.g_w);
+    if (a.gx || a.g_bn1_w || a.g_bn1_b) {
+      float* gb1 = a.g_bn1_b ? a.g_bn1_b : ws + L.sums1;
+      float* gw1 = a.g_bn1_w ? a.g_bn1_w : ws + L.sums1 + MEL;
+      hipLaunchKernelGGL(stem_dx_kernel, dim3(blocks_of(BT * MEL, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, (const float*)(ws + L.a), BT,
+                         a.T, ws + L.c, ws + L.d, (float*)nullptr);
+      colsum(s, ws + L.c, BT, MEL, ws + L.part, gb1);
+      colsum(s, ws + L.d, BT, MEL, ws + L.part, gw1);
+      if (a.gx)
+        hipLaunchKernelGGL(bn_centre_kernel, dim3(blocks_of(BT * MEL, 256)), dim3(256), 0, s, ws + L.c, a.x, f1, (const float*)gb1,
+                           (const float*)gw1, BT * MEL, MEL, (float)BT, a.gx);
+    }
+  } else {
+    if (!a.save_pre) return fail(fn, "null saved-tensor pointer");
+    const int Cout = 2 * a.C, Fo = a.F / 2;
+    const long M = BT * Fo;
+    float* gb = a.g_bn_b ? a.g_bn_b : ws + L.sums;
+    float* gw = a.g_bn_w ? a.g_bn_w : ws + L.sums + Cout;
+    hipLaunchKernelGGL(bn_fold_saved_kernel, dim3(blocks_of(Cout, 256)), dim3(256), 0, s, a.bn_w, a.bn_b, (const float*)a.save_mean,
+                       (const float*)a.save_rstd, Cout, ws + L.fold);
+    hipLaunchKernelGGL(conv_gpre_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, (const float*)a.save_pre, a.gy, f2, M * Cout,
+                       Cout, ws + L.a, ws + L.b);
+    colsum(s, ws + L.a, M, Cout, ws + L.part, gb);
+    colsum(s, ws + L.b, M, Cout, ws + L.part, gw);
+    hipLaunchKernelGGL(bn_centre_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, ws + L.a, (const float*)a.save_pre, f2,
+                       (const float*)gb, (const float*)gw, M * Cout, Cout, (float)M, (float*)nullptr);
+    conv_backward_gemms(s, ConvP{a.x, a.w, ws + L.a, f2, nullptr, nullptr, a.T, Fo, a.C, Cout, M}, ws + L.part, a.gx, a.g_w);
   }
   return finish(fn);
 }

@@ -209,17 +209,27 @@ class BeatThis(_TracksChildren, nn.Module):
         stem, the three conv units, the projection and the twelve attention / feed-forward leaves of the partial transformers);
         gradients also reach ``x`` when it requires grad.  That part of the route is fp32 under ``"32-true"`` and ``"16-mixed"``
         alike (only the trunk's units go mixed); it runs WITHOUT dropout even after ``enable_dropout`` (``dropout["frontend"]``
-        stays unused); and its BatchNorm statistics are frozen: every BatchNorm uses ``running_mean`` / ``running_var``, in
-        ``train()`` as in ``eval()``, and those buffers and ``num_batches_tracked`` never receive a gradient and are never
-        updated.  The callable nodes below ``frontend`` (``stem``, ``blocks[i]``, ``.partial``, ``.linear`` ...) stay
+        stays unused); and its BatchNorm statistics are frozen unless ``set_batch_statistics()`` was called: every BatchNorm
+        uses ``running_mean`` / ``running_var``, in ``train()`` as in ``eval()``, and those buffers and
+        ``num_batches_tracked`` never receive a gradient and are never updated.  The callable nodes below ``frontend`` (``stem``, ``blocks[i]``, ``.partial``, ``.linear`` ...) stay
         inference-only, and the route does not pass through them: forward hooks registered BELOW ``frontend`` do not fire on a
         grad-mode call with the flag set (hooks on ``frontend`` itself and on the trunk's nodes do; under ``no_grad`` all fire as
         ever).  ``set_frontend_trainable(False)`` restores the frozen state and drops the engine's packed copies, so the frozen
         frontend runs on the weights as trained;
+      * ``set_batch_statistics()`` -- training from scratch, a second opt-in on top of
+        ``set_frontend_trainable()`` and never inferred from ``train()``: in ``train()`` mode and grad mode the frontend's five
+        BatchNorms (``stem.bn1d``, ``stem.bn2d``, ``blocks[i].norm``) are torch's training-mode ones (eps 1e-5, momentum 0.1):
+        they normalise with the mean and biased variance of the call's own batch, the backward differentiates through those
+        statistics, and every forward call moves ``running_mean`` / ``running_var`` (unbiased variance) and adds 1 to
+        ``num_batches_tracked`` -- once per call, each micro-batch of an accumulated step on its own.  So the call WRITES to
+        the model's buffers, and a sequence's input gradient is no longer the same alone and inside a batch.  A batch with
+        batch x time = 1 raises torch's ``ValueError`` before any launch.  In ``eval()``, under ``no_grad`` and on the inference
+        paths the running statistics are used as ever (those calls see the moved buffers: the engine packs again);
       * parameters on the CPU raise the same ``RuntimeError`` as ever.
     The route reads the parameters' storage at call time, so an optimizer step is seen at once.  The inference paths run on
     packed copies: the ``_version`` of every parameter is recorded when they are packed, and a parameter that requires grad
-    and was changed in place since makes the next inference call pack again (checked only for parameters that require grad).
+    and was changed in place since makes the next inference call pack again (checked only for parameters that require grad);
+    so does a batch-statistics forward, which leaves a note that the running buffers moved.
     """
 
     def __init__(self, spect_dim: int = 128, transformer_dim: int = 512, ff_mult: int = 4, n_layers: int = 6,
@@ -240,6 +250,8 @@ class BeatThis(_TracksChildren, nn.Module):
         self._dropout_rng = None     # enable_dropout(): {"seed", "calls"}
         self._train_precision = "32-true"
         self._frontend_trainable = False   # set_frontend_trainable()
+        self._batch_statistics = False     # set_batch_statistics()
+        self._stats_moved = False          # a batch-statistics forward wrote the running buffers since the engine was packed
         self._engine = None
         self._packed_versions = ()   # (is frontend, parameter, its _version when the engine was packed)
         # outside autocast: True = every product of the forward on three half MFMAs over hi + lo operand halves
@@ -305,7 +317,11 @@ class BeatThis(_TracksChildren, nn.Module):
         return self.task_heads.beat_downbeat_lin.weight.device
 
     def _stale(self, frontend_only: bool) -> bool:
-        """A parameter that requires grad was changed in place since the engine packed its copy (an optimizer step)."""
+        """A parameter that requires grad was changed in place since the engine packed its copy (an optimizer step), or a
+        batch-statistics forward moved the running buffers (the kernels write them through raw pointers: no ``_version``
+        tells, the route leaves a note instead)."""
+        if getattr(self, "_stats_moved", False):
+            return True
         for front, p, version in self._packed_versions:
             if p.requires_grad and p._version != version and (front or not frontend_only):
                 return True
@@ -325,6 +341,7 @@ class BeatThis(_TracksChildren, nn.Module):
             _lib.lib()  # fail loudly if the HIP library is missing
             self._engine = Engine(PackedModel(self.state_dict(), self.hparams, dev))
             self._packed_versions = tuple((name.startswith("frontend."), p, p._version) for name, p in self.named_parameters())
+            self._stats_moved = False
         return self._engine
 
     # -- the differentiable route (backward.py) ------------------------------------------------------------------------------
@@ -349,6 +366,8 @@ class BeatThis(_TracksChildren, nn.Module):
         for name, p in self.frontend.named_parameters():
             p.requires_grad_(flag and not name.endswith("rotary_embed.freqs"))
         self._frontend_trainable = flag
+        if not flag:
+            self._batch_statistics = False
         # the re-pack check looks at parameters that require grad only: frontend weights trained under the flag and frozen again
         # would stay on the engine's old packed copies, so the engine is packed anew on its next use
         self._engine = None
@@ -361,6 +380,27 @@ class BeatThis(_TracksChildren, nn.Module):
     def _frontend_route(self) -> bool:
         return self.frontend_trainable and torch.is_grad_enabled()
 
+    # -- batch-statistics BatchNorm on the differentiable frontend ------------------------------------------
+    def set_batch_statistics(self, flag: bool = True) -> "BeatThis":
+        """The opt-in to training-mode BatchNorm (never inferred from ``train()``): with it, a grad-mode call in ``train()``
+        mode normalises the frontend's five BatchNorms with the statistics of its own batch and moves ``running_mean``,
+        ``running_var`` and ``num_batches_tracked`` (momentum 0.1).  Needs ``set_frontend_trainable()`` first;
+        ``set_frontend_trainable(False)`` clears it."""
+        flag = bool(flag)
+        if flag and not self.frontend_trainable:
+            raise RuntimeError("batch statistics belong to the differentiable frontend: call set_frontend_trainable() first")
+        self._batch_statistics = flag
+        return self
+
+    @property
+    def batch_statistics(self) -> bool:
+        return getattr(self, "_batch_statistics", False)
+
+    def _batch_route(self) -> bool:
+        """Batch statistics are used iff the opt-in is set, the frontend is trainable, grad mode is on and the model is in
+        ``train()`` mode."""
+        return self.batch_statistics and self._frontend_route() and self.training
+
     def _frontend_train(self, x: torch.Tensor) -> torch.Tensor:
         D = self.hparams["transformer_dim"]
         _lib.require_gpu(x, "stage input")
@@ -370,7 +410,13 @@ class BeatThis(_TracksChildren, nn.Module):
             raise ValueError(f"expected a (batch, time, {self.hparams['spect_dim']}) input, got {tuple(x.shape)}")
         if x.shape[0] == 0 or x.shape[1] == 0:
             return _bw.empty_with_graph((x.shape[0], x.shape[1], D), x, _params_of(self.frontend))
-        return _bw.frontend_train(self, x.to(torch.float32))
+        batch = self._batch_route()
+        if batch:
+            _bw.check_batch_statistics(int(x.shape[0]), int(x.shape[1]))
+        h = _bw.frontend_train(self, x.to(torch.float32), batch)
+        if batch:   # noted AFTER the call: an engine that ``_rope`` packed half way through it is stale as well
+            self._stats_moved = True
+        return h
 
     # -- 16-mixed on the differentiable route --------------------------------------------------------------
     def set_train_precision(self, precision: str) -> "BeatThis":

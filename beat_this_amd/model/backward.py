@@ -16,7 +16,9 @@ hands out the streams.
 The frontend (the lower part of this file): ``StemFn``, ``ConvUnitFn``, ``SwapFn`` and ``ProjectionFn`` over
 bt_front_forward / bt_front_backward (csrc/train_front.hip), composed by ``frontend_train`` with ``AttentionFn`` /
 ``FeedForwardFn`` for the twelve leaves of the partial transformers; fp32, BatchNorm on its running statistics, no dropout.
-``BeatThis.set_frontend_trainable`` decides whether it runs.
+``BeatThis.set_frontend_trainable`` decides whether it runs.  ``StemBatchFn`` / ``ConvUnitBatchFn`` (section 18, bt_front_bn_*)
+are the same two units on the statistics of the call's batch; their forward moves the running buffers in place
+(``BeatThis.set_batch_statistics``).
 
 16-mixed: the attention and the feed-forward take ``mixed``; True sends the same arguments to
 bt_train_forward_mixed / bt_train_backward_mixed (both operands of every matrix product rounded to fp16, fp32 accumulation,
@@ -373,6 +375,117 @@ class ConvUnitFn(torch.autograd.Function):
         return gx, g_w, g_nw, g_nb, None, None
 
 
+# ---- batch-statistics BatchNorm: the stem and the conv unit over bt_front_bn_forward / _backward -----------
+def check_batch_statistics(B: int, T: int) -> None:
+    """torch's own refusal, raised before any launch: a BatchNorm in training mode needs two values per channel, and
+    ``stem.bn1d`` has B T of them"""
+    if B * T < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {(B, 128, T)}: batch statistics "
+                         "need batch x time >= 2")
+
+
+def _front_bn_call(backward: bool, unit: int, a: _lib.FrontBnArgs, device) -> None:
+    need = _lib.lib().bt_front_bn_workspace_bytes(unit, int(backward), a.B, a.T, a.F, a.C)
+    if need == 0:
+        check_front_limits(a.B, a.T)
+        check_batch_statistics(a.B, a.T * (1 if unit == _lib.FRONT_STEM else a.F // 2))
+        raise ValueError(f"the differentiable frontend does not support batch {a.B}, {a.T} frames, {a.F} frequency bins, "
+                         f"{a.C} channels (unit {unit}, batch statistics)")
+    ws = torch.empty(need, dtype=torch.uint8, device=device)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
+    fn = _lib.lib().bt_front_bn_backward if backward else _lib.lib().bt_front_bn_forward
+    with torch.cuda.device(device):
+        _lib.check(fn(_lib.stream_ptr(device), unit, C.byref(a)))
+
+
+def _running(mean, var, tracked, C_):
+    """The three buffers of a BatchNorm as the kernels update them: in place, in their own storage."""
+    for t, dtype in ((mean, torch.float32), (var, torch.float32), (tracked, torch.int64)):
+        if t.dtype != dtype or not t.is_contiguous() or t.numel() != (1 if t is tracked else C_):
+            raise ValueError(f"batch statistics update the running buffers in place: expected contiguous {dtype} buffers of "
+                             f"{C_} channels, got {t.dtype} {tuple(t.shape)}")
+    return mean.data_ptr(), var.data_ptr(), tracked.data_ptr()
+
+
+class StemBatchFn(torch.autograd.Function):
+    """``StemFn`` with bn1d and bn2d on the statistics of the call's batch.  Inputs: x, conv weight, bn1d weight, bias, bn2d
+    weight, bias, then the six buffers (bn1d running_mean, running_var, num_batches_tracked, bn2d likewise), which the forward
+    updates in place, once, and which take no part in the graph.  Saves the batch's mean and 1 / sqrt(var + eps) of both."""
+
+    @staticmethod
+    def forward(ctx, x, w, w1, b1, w2, b2, m1, v1, n1, m2, v2, n2):
+        xf = _f32(x)
+        ps = [_f32(p) for p in (w, w1, b1, w2, b2)]
+        _on_device_of(xf, *ps, m1, v1, n1, m2, v2, n2)
+        B, T, F = xf.shape
+        y = torch.empty((B, T, 32, 32), dtype=torch.float32, device=xf.device)
+        stats = [torch.empty(n, dtype=torch.float32, device=xf.device) for n in (F, F, 32, 32)]
+        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=int(ps[0].shape[0]))
+        a.x, a.y = xf.data_ptr(), y.data_ptr()
+        a.w, a.bn1_w, a.bn1_b, a.bn_w, a.bn_b = (p.data_ptr() for p in ps)
+        a.bn1_mean, a.bn1_var, a.bn1_tracked = _running(m1, v1, n1, F)
+        a.bn_mean, a.bn_var, a.bn_tracked = _running(m2, v2, n2, 32)
+        a.save1_mean, a.save1_rstd, a.save_mean, a.save_rstd = (t.data_ptr() for t in stats)
+        _front_bn_call(False, _lib.FRONT_STEM, a, xf.device)
+        ctx.save_for_backward(xf, *ps, *stats)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xf, w, w1, b1, w2, b2, *stats = ctx.saved_tensors
+        B, T, F = xf.shape
+        gyf = _f32(gy)
+        grads = [_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, w, w1, b1, w2, b2))]
+        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=int(w.shape[0]))
+        a.x, a.gy = xf.data_ptr(), gyf.data_ptr()
+        a.w, a.bn1_w, a.bn1_b, a.bn_w, a.bn_b = (p.data_ptr() for p in (w, w1, b1, w2, b2))
+        a.save1_mean, a.save1_rstd, a.save_mean, a.save_rstd = (t.data_ptr() for t in stats)
+        a.gx, a.g_w, a.g_bn1_w, a.g_bn1_b, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in grads)
+        _front_bn_call(True, _lib.FRONT_STEM, a, xf.device)
+        return (*grads, None, None, None, None, None, None)
+
+
+class ConvUnitBatchFn(torch.autograd.Function):
+    """``ConvUnitFn`` with the norm on the statistics of the call's batch.  Inputs: x, conv weight, norm weight, bias, then
+    running_mean, running_var, num_batches_tracked (updated in place by the forward, outside the graph)."""
+
+    @staticmethod
+    def forward(ctx, x, w, nw, nb, nm, nv, nn_):
+        xf = _f32(x)
+        ps = [_f32(p) for p in (w, nw, nb)]
+        _on_device_of(xf, *ps, nm, nv, nn_)
+        B, T, F, Cc = xf.shape
+        if tuple(ps[0].shape) != (2 * Cc, Cc, 2, 3) or F % 2:
+            raise ValueError(f"conv unit: input {tuple(xf.shape)} against a weight of shape {tuple(ps[0].shape)}")
+        y = torch.empty((B, T, F // 2, 2 * Cc), dtype=torch.float32, device=xf.device)
+        pre = torch.empty_like(y)
+        stats = [torch.empty(2 * Cc, dtype=torch.float32, device=xf.device) for _ in range(2)]
+        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=Cc)
+        a.x, a.y, a.save_pre = xf.data_ptr(), y.data_ptr(), pre.data_ptr()
+        a.w, a.bn_w, a.bn_b = (p.data_ptr() for p in ps)
+        a.bn_mean, a.bn_var, a.bn_tracked = _running(nm, nv, nn_, 2 * Cc)
+        a.save_mean, a.save_rstd = (t.data_ptr() for t in stats)
+        _front_bn_call(False, _lib.FRONT_CONV, a, xf.device)
+        ctx.save_for_backward(xf, pre, *ps, *stats)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xf, pre, w, nw, nb, mean, rstd = ctx.saved_tensors
+        B, T, F, Cc = xf.shape
+        gyf = _f32(gy)
+        grads = [_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, w, nw, nb))]
+        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=Cc)
+        a.x, a.save_pre, a.gy = xf.data_ptr(), pre.data_ptr(), gyf.data_ptr()
+        a.w, a.bn_w, a.bn_b = (p.data_ptr() for p in (w, nw, nb))
+        a.save_mean, a.save_rstd = mean.data_ptr(), rstd.data_ptr()
+        a.gx, a.g_w, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in grads)
+        _front_bn_call(True, _lib.FRONT_CONV, a, xf.device)
+        return (*grads, None, None, None)
+
+
 class SwapFn(torch.autograd.Function):
     """(B, P, Q, C) -> (B, Q, P, C): between the frequency and the time direction of a partial transformer"""
 
@@ -435,13 +548,22 @@ def _bn(node):
     return node.weight, node.bias, node.running_mean, node.running_var
 
 
-def stem(node, x):
+def _stats(node):
+    return node.running_mean, node.running_var, node.num_batches_tracked
+
+
+def stem(node, x, batch_statistics=False):
     """``frontend.stem``: (B, T, 128) -> (b, t, f, c)"""
+    if batch_statistics:
+        return StemBatchFn.apply(x, node.conv2d.weight, node.bn1d.weight, node.bn1d.bias, node.bn2d.weight, node.bn2d.bias,
+                                 *_stats(node.bn1d), *_stats(node.bn2d))
     return StemFn.apply(x, node.conv2d.weight, *_bn(node.bn1d), *_bn(node.bn2d))
 
 
-def conv_unit(block, x):
+def conv_unit(block, x, batch_statistics=False):
     """``frontend.blocks[i]`` behind its partial transformer: conv2d, norm, GELU on (b, t, f, c)"""
+    if batch_statistics:
+        return ConvUnitBatchFn.apply(x, block.conv2d.weight, block.norm.weight, block.norm.bias, *_stats(block.norm))
     return ConvUnitFn.apply(x, block.conv2d.weight, *_bn(block.norm))
 
 
@@ -459,14 +581,17 @@ def partial_ft(node, x, rope_for):
     return SwapFn.apply(y.reshape(B, F, T, Cc))
 
 
-def frontend_train(model, x):
+def frontend_train(model, x, batch_statistics=False):
     """``BeatThis.frontend`` on the differentiable route, in the reference's order (beat_tracker.py:54-80, 290-301): stem, three
-    times (partial transformer, conv unit), projection.  (B, T, 128) -> (B, T, D)."""
+    times (partial transformer, conv unit), projection.  (B, T, 128) -> (B, T, D).  ``batch_statistics``: the five BatchNorms
+    normalise with this call's batch and move their running buffers (section 18)."""
     fr = model.frontend
     check_front_limits(int(x.shape[0]), int(x.shape[1]))
-    h = stem(fr.stem, x)
+    if batch_statistics:
+        check_batch_statistics(int(x.shape[0]), int(x.shape[1]))
+    h = stem(fr.stem, x, batch_statistics)
     for blk in fr.blocks:
         if "partial" in blk._modules:
             h = partial_ft(blk.partial, h, model._rope)
-        h = conv_unit(blk, h)
+        h = conv_unit(blk, h, batch_statistics)
     return ProjectionFn.apply(h, fr.linear.weight, fr.linear.bias)

@@ -42,7 +42,9 @@ class PLBeatThis(nn.Module):
     """The model and everything a training run needs around it.
 
     The frontend is frozen unless ``train_frontend=True`` (``BeatThis.set_frontend_trainable``: whole-model fine-tuning with
-    frozen BatchNorm statistics, no frontend dropout, fp32 frontend arithmetic); the six main layers, the final RMSNorm and the
+    frozen BatchNorm statistics, no frontend dropout, fp32 frontend arithmetic; ``batch_statistics=True`` on top of it makes the
+    frontend's BatchNorms torch's training-mode ones, ``BeatThis.set_batch_statistics``, and ``fit`` then trains in ``train()``
+    mode: what training from scratch needs; no hyper-parameter either); the six main layers, the final RMSNorm and the
     task heads are trainable.  ``dropout`` is stored in the hyper-parameters and handed to the model;
     ``apply_dropout=True`` enables it there under ``dropout_seed`` (``BeatThis.enable_dropout``), and ``fit`` then trains in
     ``train()`` mode: the main layers drop at ``dropout["transformer"]`` like the reference's, with this package's own masks;
@@ -55,9 +57,11 @@ class PLBeatThis(nn.Module):
                  dropout={"frontend": 0.1, "transformer": 0.2}, lr=0.0008, weight_decay=0.01,
                  pos_weights={"beat": 1, "downbeat": 1}, head_dim=32, loss_type="shift_tolerant_weighted_bce",
                  warmup_steps=1000, max_epochs=100, use_dbn=False, eval_trim_beats=5, sum_head=True, partial_transformers=True,
-                 apply_dropout=False, dropout_seed=0, precision="32-true", train_frontend=False):
+                 apply_dropout=False, dropout_seed=0, precision="32-true", train_frontend=False,
+                 batch_statistics=False):
         given = {k: v for k, v in locals().items()
-                 if k not in ("self", "__class__", "apply_dropout", "dropout_seed", "precision", "train_frontend")}
+                 if k not in ("self", "__class__", "apply_dropout", "dropout_seed", "precision", "train_frontend",
+                              "batch_statistics")}
         super().__init__()
         hp = self.hyper_parameters = _plain(given)   # what a checkpoint carries: every constructor argument, as plain values
         for key in ("lr", "weight_decay", "fps", "warmup_steps", "max_epochs", "pos_weights", "eval_trim_beats"):
@@ -71,6 +75,8 @@ class PLBeatThis(nn.Module):
             p.requires_grad_(not name.startswith("frontend.") and not name.endswith("rotary_embed.freqs"))
         if train_frontend:   # whole-model fine-tuning (BeatThis.set_frontend_trainable; no hyper-parameter, like apply_dropout)
             self.model.set_frontend_trainable(True)
+        if batch_statistics:   # training-mode BatchNorm in the frontend (BeatThis.set_batch_statistics; raises without train_frontend)
+            self.model.set_batch_statistics(True)
         self.beat_loss, self.downbeat_loss = losses_from_hparams(hp)
         self.postprocessor = Postprocessor(("minimal", "dbn")[bool(use_dbn)], fps)
         self.metrics = Metrics(eval_trim_beats)

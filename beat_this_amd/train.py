@@ -91,7 +91,7 @@ def validate(pl_module, datamodule) -> dict:
 
 
 def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
-        resume=None, log=print, precision=None, train_frontend=None) -> dict:
+        resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None) -> dict:
     """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
 
     Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
@@ -114,7 +114,12 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     that its state covers the frontend's weights (None leaves the model as it is): whole-model fine-tuning with frozen
     BatchNorm statistics.  A checkpoint then carries the larger optimiser state, and ``resume`` needs the same setting.
 
-    A module whose model has dropout enabled is put into ``train()`` mode here and stays in it; validation runs under
+    ``batch_statistics``: True / False calls the model's ``set_batch_statistics`` next (None leaves it as it is; True needs a
+    trainable frontend): the frontend's BatchNorms then normalise with each batch's own statistics and move their running
+    buffers, every micro-batch on its own -- training from scratch.  The buffers travel in the ``state_dict``, so a checkpoint
+    and ``resume`` need nothing new; ``resume`` needs the same setting.
+
+    A module whose model has dropout enabled or uses batch statistics is put into ``train()`` mode here and stays in it; validation runs under
     ``no_grad`` on the inference path, which never drops.
 
     -> dict: ``train_loss`` (one mean per epoch run), ``val`` ([(epoch, metrics)]), ``epoch``, ``global_step``, ``optimizer``,
@@ -125,6 +130,8 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
         pl_module.model.set_train_precision(precision)
     if train_frontend is not None:
         pl_module.model.set_frontend_trainable(train_frontend)
+    if batch_statistics is not None:
+        pl_module.model.set_batch_statistics(batch_statistics)
     scaler = LossScaler() if pl_module.model.train_precision == "16-mixed" else None
     accumulate = int(accumulate_grad_batches)
     if accumulate < 1 or int(max_epochs) < 0 or int(val_frequency) < 1:
@@ -153,7 +160,7 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
             scaler.load_state_dict(ckpt["loss_scaler"])
         first_epoch, global_step = int(ckpt["epoch"]) + 1, int(ckpt["global_step"])
         log(f"resumed after epoch {ckpt['epoch']} ({global_step} optimiser steps)")
-    if pl_module.model.dropout_state() is not None:
+    if pl_module.model.dropout_state() is not None or pl_module.model.batch_statistics:
         pl_module.train()
     history = {"train_loss": [], "val": [], "optimizer": optimizer, "scheduler": scheduler, "loss_scaler": scaler}
     step = optimizer.step if scaler is None else (lambda accumulated: optimizer.step(accumulated=accumulated, loss_scaler=scaler))
@@ -226,6 +233,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--train-frontend", default=False, action=toggle,
                    help="whole-model fine-tuning: also train the frontend (frozen BatchNorm statistics, no frontend dropout, "
                         "fp32 frontend under either precision; default: the frontend stays frozen)")
+    p.add_argument("--batch-statistics", default=False, action=toggle,
+                   help="with --train-frontend: the frontend's BatchNorms use each batch's statistics and update their running "
+                        "ones, as training from scratch needs (default: frozen running statistics)")
     p.add_argument("--dbn", default=False, action=toggle, help="DBN post-processing in validation")
     p.add_argument("--eval-trim-beats", metavar="SECONDS", type=float, default=5,
                    help="skip the first seconds of each piece in the metrics (default: %(default)s)")
@@ -245,7 +255,10 @@ def get_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None) -> int:
-    args = get_parser().parse_args(argv)
+    parser = get_parser()
+    args = parser.parse_args(argv)
+    if args.batch_statistics and not args.train_frontend:
+        parser.error("--batch-statistics needs --train-frontend: batch statistics belong to the differentiable frontend")
     from .dataset import BeatDataModule
     from .inference import load_checkpoint
     from .model.pl_module import PLBeatThis
@@ -276,7 +289,8 @@ def main(argv=None) -> int:
     pl_module = PLBeatThis(**arch, apply_dropout=args.dropout, dropout_seed=args.seed, fps=FPS, lr=args.lr,
                            weight_decay=args.weight_decay, pos_weights=pos_weights, loss_type=args.loss,
                            warmup_steps=args.warmup_steps, max_epochs=args.max_epochs, use_dbn=args.dbn,
-                           eval_trim_beats=args.eval_trim_beats, precision=args.precision, train_frontend=args.train_frontend)
+                           eval_trim_beats=args.eval_trim_beats, precision=args.precision, train_frontend=args.train_frontend,
+                           batch_statistics=args.batch_statistics)
     if ckpt is not None and not args.resume_checkpoint:   # (a resumed run's weights are restored by fit() with the rest)
         pl_module.load_state_dict(ckpt["state_dict"])
     pl_module.to(device)

@@ -789,6 +789,45 @@ size_t bt_front_workspace_bytes(int unit, int backward, int B, int T, int F, int
 int bt_front_forward(void* stream, int unit, const bt_front_args* a);
 int bt_front_backward(void* stream, int unit, const bt_front_args* a);
 
+/* ---- training: the frontend's BatchNorm on BATCH statistics (csrc/train_front.hip) --------------------------
+ * BT_FRONT_STEM and BT_FRONT_CONV as above, with torch's training-mode nn.BatchNorm1d / 2d (eps 1e-5, momentum 0.1, affine,
+ * tracking) in place of the running statistics.  Over the n values of a channel (n = B T for bn1d, B T F' for bn2d and
+ * blocks.i.norm, F' the output bins):
+ *   forward   mean_b and the biased var_b of this call's batch: per chunk of BT_TRAIN_CS_ROWS rows the mean and the sum of
+ *             squared deviations from it (fp64, rows ascending), merged in chunk order by a second launch (Chan's formula, fp64:
+ *             one workgroup per channel, 256 runs of consecutive chunks and then the runs pairwise, left neighbour first -- a
+ *             fixed tree over the shapes alone) and rounded once; y uses s = weight rstd_b, sh = bias - mean_b s with rstd_b = 1 / sqrt(var_b + 1e-5).  The same
+ *             launch writes save_mean / save_rstd (save1_*: bn1d) and moves the running buffers IN PLACE, once per call:
+ *             running_mean = 0.9 running_mean + 0.1 mean_b, running_var = 0.9 running_var + 0.1 var_b n / (n - 1) (fp64, rounded
+ *             once), *tracked += 1 by one thread (a NULL tracked pointer: no count).  The stem takes the statistics of x first,
+ *             stages pre = conv(bn1d(x)) in the workspace and takes bn2d's from it; the time padding stays zero AFTER bn1d.
+ *             The conv unit writes save_pre as above.
+ *   backward  reads x, w, the gains and biases, save_mean / save_rstd (and save_pre) -- never the running buffers, which it
+ *             leaves alone.  With g the gradient at a BatchNorm's output and xhat = (v - mean_b) rstd_b: g_bias = sum g,
+ *             g_weight = sum g xhat (always computed; into the workspace when the pointer is NULL), and the gradient at the
+ *             BatchNorm's input is weight rstd_b (g - g_bias / n - xhat g_weight / n): the statistics are differentiated through.
+ * So a sequence's gx is NOT the same alone and inside a batch, and the forward WRITES to the buffers it is handed.  The rest
+ * of the contract is the one above: no atomics, one writer per output byte, summation orders from the shapes alone (two runs
+ * from the same buffers are bit-identical), no synchronisation, allocation or clearing, no read of unwritten workspace.
+ * n = 1 (torch: "Expected more than 1 value per channel when training") is BT_ERR_ARG before any launch, like every shape the
+ * calls above refuse and every NULL among the required pointers; the workspace query then returns 0. */
+typedef struct {
+  int32_t B, T, F, C, reserved0, reserved1, reserved2, reserved3;
+  const float* w;
+  const float* bn_w; const float* bn_b; float* bn_mean; float* bn_var; int64_t* bn_tracked;
+  const float* bn1_w; const float* bn1_b; float* bn1_mean; float* bn1_var; int64_t* bn1_tracked;
+  float* save_mean; float* save_rstd; float* save1_mean; float* save1_rstd;
+  const float* x; float* y; float* save_pre;
+  const float* gy;
+  float* gx; float* g_w; float* g_bn_w; float* g_bn_b; float* g_bn1_w; float* g_bn1_b;
+  void* ws; size_t ws_bytes;
+} bt_front_bn_args;
+/* sizeof, then offsetof w, bn_tracked, save_mean, x, gy, gx, ws, ws_bytes: nine entries, the binding's self-check */
+void bt_front_bn_struct_sizes(int32_t* out);
+size_t bt_front_bn_workspace_bytes(int unit, int backward, int B, int T, int F, int C);
+int bt_front_bn_forward(void* stream, int unit, const bt_front_bn_args* a);
+int bt_front_bn_backward(void* stream, int unit, const bt_front_bn_args* a);
+
 /* ---- training: the optimiser step (csrc/optim.hip) ------------------------------------------------------
  * Multi-tensor AdamW with torch.optim.AdamW's default semantics (decoupled decay, no amsgrad, no maximize), all fp32.  With
  * gs = grad_scale (times *d_coef when d_coef is given, multiplied in fp32) every element does, one operation at a time and
