@@ -19,7 +19,7 @@ if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # develop
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
            "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "engine.hip"]
-HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
+HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "train_front_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
 ABI_VERSION = 600   # BT_ABI_VERSION of include/beat_this_amd.h this binding was written against
@@ -136,7 +136,7 @@ class TrainDropout(C.Structure):   # bt_train_dropout
 
 class FrontArgs(C.Structure):   # bt_front_args
     _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("dim", C.c_int32),
-                ("reserved0", C.c_int32), ("reserved1", C.c_int32), ("reserved2", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p),
+                ("mixed", C.c_int32), ("reserved1", C.c_int32), ("reserved2", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p),
                 ("bn_w", C.c_void_p), ("bn_b", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p), ("bn1_w", C.c_void_p),
                 ("bn1_b", C.c_void_p), ("bn1_mean", C.c_void_p), ("bn1_var", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
                 ("save_pre", C.c_void_p), ("gy", C.c_void_p), ("gx", C.c_void_p), ("g_w", C.c_void_p), ("g_b", C.c_void_p),
@@ -145,7 +145,7 @@ class FrontArgs(C.Structure):   # bt_front_args
 
 
 class FrontBnArgs(C.Structure):   # bt_front_bn_args
-    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("reserved0", C.c_int32),
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("mixed", C.c_int32),
                 ("reserved1", C.c_int32), ("reserved2", C.c_int32), ("reserved3", C.c_int32), ("w", C.c_void_p),
                 ("bn_w", C.c_void_p), ("bn_b", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p),
                 ("bn_tracked", C.c_void_p), ("bn1_w", C.c_void_p), ("bn1_b", C.c_void_p), ("bn1_mean", C.c_void_p),
@@ -290,10 +290,12 @@ EXPORTS = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bt_front_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "bt_front_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bt_front_workspace_bytes_mixed": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bt_front_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontArgs)]),
     "bt_front_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontArgs)]),
     "bt_front_bn_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "bt_front_bn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bt_front_bn_workspace_bytes_mixed": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bt_front_bn_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontBnArgs)]),
     "bt_front_bn_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontBnArgs)]),
     "bt_optim_struct_sizes": (None, [C.POINTER(C.c_int32)]),

@@ -22,6 +22,9 @@
 //   backward-weight  gW  [Cout, 6 Cin] = sum over rows of G^T A            partials per DW_ROWS rows, added in chunk order
 // The forward saves `pre` (the backward needs it for gelu' and for the gain's gradient and would otherwise repeat the GEMM);
 // the stem (K = 12, vector unit) recomputes it.
+// With `mixed = 1` in the argument struct the same three products run on v_mfma_f32_32x32x16_f16 with both
+// operands rounded to fp16 as they are staged (train_front_mixed.inc) and the projection's GEMMs take bt_train_matmul's mixed
+// route; everything around the products is the code below either way.
 //
 // Reproducibility, as in train.hip: no atomics; every output element is written by one thread of one launch; a GEMM element
 // sums k ascending; weight gradients over chunks of DW_ROWS rows and column sums over chunks of CS_ROWS rows, partials added in
@@ -223,6 +226,7 @@ struct ConvP {
   float* out2;
   int T, Fo, Cin, Cout;
   long M;              // B T Fo
+  const _Float16* wh;  // 16-mixed: the packed fp16 weight of the launch's MODE (train_front_mixed.inc)
 };
 
 // implicit A of the forward: row m = (b, t, fo), column k = dt 2 Cin + (df Cin + ci); zeros at t + dt - 1 outside [0, T)
@@ -306,6 +310,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvP p) {
     }
   }
 }
+
+#include "train_front_mixed.inc"   // conv_pack_kernel, conv_gemm_mixed_kernel<MODE>: the same three products on fp16 MFMAs
 
 // gw [Cout][Cin][2][3] = the partials [chunk][Cout][dt 2 Cin + df Cin + ci] added in chunk order
 __global__ __launch_bounds__(256) void conv_dw_reduce_kernel(const float* part, int Cout, int Cin, int chunks, float* gw) {
@@ -443,10 +449,11 @@ void swap(hipStream_t s, const float* x, long B, int P, int Q, int C, float* y) 
 size_t up64(size_t n) { return (n + 63) / 64 * 64; }
 
 struct Layout {
-  size_t fold, fold1, a, b, c, d, part, total;
+  size_t fold, fold1, a, b, c, d, part, wimg, total;
 };
 
-Layout layout(int unit, int backward, long BT, int F, int C, int dim) {
+// mixed: the conv unit's fp16 weight image (Cout 6 Cin halves; the forward's, or the backward-data's transposed one)
+Layout layout(int unit, int backward, long BT, int F, int C, int dim, bool mixed = false) {
   Layout L{};
   size_t at = 0;
   auto take = [&](size_t n) { const size_t o = at; at += up64(n); return o; };
@@ -472,6 +479,7 @@ Layout layout(int unit, int backward, long BT, int F, int C, int dim) {
         L.b = take(M * Cout);            // g_pre xhat
         L.part = take(std::max((size_t)dw_chunks(M) * Cout * 6 * C, (size_t)cs_chunks(M) * Cout));
       }
+      if (mixed) L.wimg = take(Cout * 3 * C);
       break;
     }
     case BT_FRONT_LINEAR: {
@@ -532,16 +540,49 @@ void fold(hipStream_t s, const float* w, const float* b, const float* mean, cons
 
 dim3 conv_grid(long GM, int GN, int chunks) { return dim3(blocks_of(GN, GT), blocks_of(GM, GT), (unsigned)chunks); }
 
+// 16-mixed: the argument check shared by the four entry points, and the weight image of one MODE
+const char* check_mixed(int unit, int mixed, bool linear_too) {
+  if (mixed != 0 && mixed != 1) return "mixed must be 0 or 1";
+  if (mixed && unit != BT_FRONT_CONV && !(linear_too && unit == BT_FRONT_LINEAR))
+    return "mixed = 1 belongs to BT_FRONT_CONV and (bt_front_args) BT_FRONT_LINEAR: the other units have no product worth an MFMA";
+  return nullptr;
+}
+
+void conv_pack(hipStream_t s, const float* w, int Cout, int Cin, int transposed, float* img) {
+  hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_of((long)Cout * 6 * Cin, 256)), dim3(256), 0, s, w, Cout, Cin, transposed,
+                     (_Float16*)img);
+}
+
+// the forward GEMM (p.out = pre, p.out2 = y or null); wimg: the workspace of the fp16 weight image, null = the fp32 kernel
+void conv_forward_gemm(hipStream_t s, ConvP p, float* wimg) {
+  if (wimg) {
+    conv_pack(s, p.w, p.Cout, p.Cin, 0, wimg);
+    p.wh = (const _Float16*)wimg;
+    hipLaunchKernelGGL(conv_gemm_mixed_kernel<0>, conv_grid(p.M, p.Cout, 1), dim3(256), 0, s, p);
+  } else {
+    hipLaunchKernelGGL(conv_gemm_kernel<0>, conv_grid(p.M, p.Cout, 1), dim3(256), 0, s, p);
+  }
+}
+
 // the conv unit's backward-data and backward-weight GEMMs on p.g = g_pre (they multiply by s = p.fold while staging)
-void conv_backward_gemms(hipStream_t s, ConvP p, float* part, float* gx, float* g_w) {
+void conv_backward_gemms(hipStream_t s, ConvP p, float* part, float* gx, float* g_w, float* wimg) {
   if (gx) {
     p.out = gx;
-    hipLaunchKernelGGL(conv_gemm_kernel<1>, conv_grid(p.M, 2 * p.Cin, 1), dim3(256), 0, s, p);
+    if (wimg) {
+      conv_pack(s, p.w, p.Cout, p.Cin, 1, wimg);
+      p.wh = (const _Float16*)wimg;
+      hipLaunchKernelGGL(conv_gemm_mixed_kernel<1>, conv_grid(p.M, 2 * p.Cin, 1), dim3(256), 0, s, p);
+    } else {
+      hipLaunchKernelGGL(conv_gemm_kernel<1>, conv_grid(p.M, 2 * p.Cin, 1), dim3(256), 0, s, p);
+    }
   }
   if (g_w) {
     const int chunks = dw_chunks(p.M);
     p.out = part;
-    hipLaunchKernelGGL(conv_gemm_kernel<2>, conv_grid(p.Cout, 6 * p.Cin, chunks), dim3(256), 0, s, p);
+    if (wimg)
+      hipLaunchKernelGGL(conv_gemm_mixed_kernel<2>, conv_grid(p.Cout, 6 * p.Cin, chunks), dim3(256), 0, s, p);
+    else
+      hipLaunchKernelGGL(conv_gemm_kernel<2>, conv_grid(p.Cout, 6 * p.Cin, chunks), dim3(256), 0, s, p);
     hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3(blocks_of((long)p.Cout * 6 * p.Cin, 256)), dim3(256), 0, s, (const float*)part,
                        p.Cout, p.Cin, chunks, g_w);
   }
@@ -557,11 +598,11 @@ void stem_dw(hipStream_t s, const float* x, const float* f1, const float* f2, co
 
 // ---- batch statistics: workspace and argument checks ---------------------------------------------------------------------------
 struct BnLayout {
-  size_t fold, fold1, pre, a, b, c, d, sums, sums1, part, total;
+  size_t fold, fold1, pre, a, b, c, d, sums, sums1, part, wimg, total;
 };
 
 // a chunk's moments are two doubles per column: four floats of the workspace
-BnLayout bn_layout(int unit, int backward, long BT, int F, int C) {
+BnLayout bn_layout(int unit, int backward, long BT, int F, int C, bool mixed = false) {
   BnLayout L{};
   size_t at = 0;
   auto take = [&](size_t n) { const size_t o = at; at += up64(n); return o; };
@@ -592,6 +633,7 @@ BnLayout bn_layout(int unit, int backward, long BT, int F, int C) {
     } else {
       L.part = take(4 * (size_t)cs_chunks(M) * Cout);
     }
+    if (mixed) L.wimg = take(Cout * 3 * C);   // the fp16 weight image, as layout()
   }
   L.total = at;
   return L;
@@ -623,14 +665,21 @@ size_t bt_front_workspace_bytes(int unit, int backward, int B, int T, int F, int
   return layout(unit, backward != 0, (long)B * T, F, C, dim).total * sizeof(float);
 }
 
+size_t bt_front_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C, int dim) {
+  if (check_shape(unit, B, T, F, C, dim) || check_mixed(unit, 1, true)) return 0;
+  return layout(unit, backward != 0, (long)B * T, F, C, dim, true).total * sizeof(float);
+}
+
 int bt_front_forward(void* stream, int unit, const bt_front_args* ap) {
   const char* fn = "bt_front_forward";
   if (!ap) return fail(fn, "null argument");
   const bt_front_args& a = *ap;
   if (const char* e = check_shape(unit, a.B, a.T, a.F, a.C, a.dim)) return fail(fn, e);
+  if (const char* e = check_mixed(unit, a.mixed, true)) return fail(fn, e);
   const long BT = (long)a.B * a.T;
-  const Layout L = layout(unit, 0, BT, a.F, a.C, a.dim);
+  const Layout L = layout(unit, 0, BT, a.F, a.C, a.dim, a.mixed != 0);
   if (!a.x || !a.y || !a.ws) return fail(fn, "null x, y or workspace");
+  if (a.mixed && (uintptr_t)a.ws % 16) return fail(fn, "mixed = 1: the workspace must be 16-byte aligned");
   if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)a.ws;
@@ -648,15 +697,15 @@ int bt_front_forward(void* stream, int unit, const bt_front_args* ap) {
       if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.save_pre) return fail(fn, "null parameter or saved-tensor pointer");
       const int Cout = 2 * a.C;
       fold(s, a.bn_w, a.bn_b, a.bn_mean, a.bn_var, Cout, ws + L.fold);
-      ConvP p{a.x, a.w, nullptr, ws + L.fold, a.save_pre, a.y, a.T, a.F / 2, a.C, Cout, BT * (a.F / 2)};
-      hipLaunchKernelGGL(conv_gemm_kernel<0>, conv_grid(p.M, Cout, 1), dim3(256), 0, s, p);
+      conv_forward_gemm(s, ConvP{a.x, a.w, nullptr, ws + L.fold, a.save_pre, a.y, a.T, a.F / 2, a.C, Cout, BT * (a.F / 2)},
+                        a.mixed ? ws + L.wimg : nullptr);
       break;
     }
     case BT_FRONT_LINEAR: {
       if (!a.w || !a.b) return fail(fn, "null parameter");
       const int K = a.F * a.C;
       swap(s, a.x, BT, a.F, a.C, 1, ws + L.a);   // (f c) -> (c f)
-      if (int rc = bt_train_matmul(stream, 0, 0, ws + L.a, a.w, (int)BT, a.dim, K, a.y, a.b, nullptr, 0, nullptr, nullptr, 0, 0,
+      if (int rc = bt_train_matmul(stream, a.mixed, 0, ws + L.a, a.w, (int)BT, a.dim, K, a.y, a.b, nullptr, 0, nullptr, nullptr, 0, 0,
                                    nullptr, 0))
         return rc;
       break;
@@ -673,10 +722,12 @@ int bt_front_backward(void* stream, int unit, const bt_front_args* ap) {
   if (!ap) return fail(fn, "null argument");
   const bt_front_args& a = *ap;
   if (const char* e = check_shape(unit, a.B, a.T, a.F, a.C, a.dim)) return fail(fn, e);
+  if (const char* e = check_mixed(unit, a.mixed, true)) return fail(fn, e);
   const long BT = (long)a.B * a.T;
-  const Layout L = layout(unit, 1, BT, a.F, a.C, a.dim);
+  const Layout L = layout(unit, 1, BT, a.F, a.C, a.dim, a.mixed != 0);
   if (!a.gy || !a.ws) return fail(fn, "null upstream gradient or workspace");
   if (unit != BT_FRONT_SWAP && !a.x) return fail(fn, "null x");
+  if (a.mixed && (uintptr_t)a.ws % 16) return fail(fn, "mixed = 1: the workspace must be 16-byte aligned");
   if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)a.ws;
@@ -711,7 +762,8 @@ int bt_front_backward(void* stream, int unit, const bt_front_args* ap) {
                          (const float*)(ws + L.fold), M * Cout, Cout, ws + L.a, ws + L.b);
       if (a.g_bn_b) colsum(s, ws + L.a, M, Cout, ws + L.part, a.g_bn_b);
       if (a.g_bn_w) colsum(s, ws + L.b, M, Cout, ws + L.part, a.g_bn_w);
-      conv_backward_gemms(s, ConvP{a.x, a.w, ws + L.a, ws + L.fold, nullptr, nullptr, a.T, Fo, a.C, Cout, M}, ws + L.part, a.gx, a.g_w);
+      conv_backward_gemms(s, ConvP{a.x, a.w, ws + L.a, ws + L.fold, nullptr, nullptr, a.T, Fo, a.C, Cout, M}, ws + L.part, a.gx, a.g_w,
+                          a.mixed ? ws + L.wimg : nullptr);
       break;
     }
     case BT_FRONT_LINEAR: {
@@ -720,12 +772,12 @@ int bt_front_backward(void* stream, int unit, const bt_front_args* ap) {
       if (a.g_b) colsum(s, a.gy, BT, a.dim, ws + L.part, a.g_b);
       if (a.g_w) {
         swap(s, a.x, BT, a.F, a.C, 1, ws + L.a);
-        if (int rc = bt_train_matmul(stream, 0, 2, a.gy, ws + L.a, a.dim, K, (int)BT, a.g_w, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
+        if (int rc = bt_train_matmul(stream, a.mixed, 2, a.gy, ws + L.a, a.dim, K, (int)BT, a.g_w, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
                                      ws + L.part, (L.total - L.part) * sizeof(float)))
           return rc;
       }
       if (a.gx) {
-        if (int rc = bt_train_matmul(stream, 0, 1, a.gy, a.w, (int)BT, K, a.dim, ws + L.b, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
+        if (int rc = bt_train_matmul(stream, a.mixed, 1, a.gy, a.w, (int)BT, K, a.dim, ws + L.b, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
                                      nullptr, 0))
           return rc;
         swap(s, ws + L.b, BT, a.C, a.F, 1, a.gx);   // (c f) -> (f c)
@@ -758,17 +810,24 @@ size_t bt_front_bn_workspace_bytes(int unit, int backward, int B, int T, int F, 
   return bn_layout(unit, backward != 0, (long)B * T, F, C).total * sizeof(float);
 }
 
+size_t bt_front_bn_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C) {
+  if (bn_check_shape(unit, B, T, F, C) || check_mixed(unit, 1, false)) return 0;
+  return bn_layout(unit, backward != 0, (long)B * T, F, C, true).total * sizeof(float);
+}
+
 int bt_front_bn_forward(void* stream, int unit, const bt_front_bn_args* ap) {
   const char* fn = "bt_front_bn_forward";
   if (!ap) return fail(fn, "null argument");
   const bt_front_bn_args& a = *ap;
   if (const char* e = bn_check_shape(unit, a.B, a.T, a.F, a.C)) return fail(fn, e);
+  if (const char* e = check_mixed(unit, a.mixed, false)) return fail(fn, e);
   const long BT = (long)a.B * a.T;
-  const BnLayout L = bn_layout(unit, 0, BT, a.F, a.C);
+  const BnLayout L = bn_layout(unit, 0, BT, a.F, a.C, a.mixed != 0);
   if (!a.x || !a.y || !a.ws) return fail(fn, "null x, y or workspace");
   if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.save_mean || !a.save_rstd)
     return fail(fn, "null parameter, running buffer or saved-statistics pointer");
   if ((uintptr_t)a.ws % 8) return fail(fn, "the workspace must be 8-byte aligned");
+  if (a.mixed && (uintptr_t)a.ws % 16) return fail(fn, "mixed = 1: the workspace must be 16-byte aligned");
   if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)a.ws;
@@ -787,8 +846,8 @@ int bt_front_bn_forward(void* stream, int unit, const bt_front_bn_args* ap) {
     if (!a.save_pre) return fail(fn, "null saved-tensor pointer");
     const int Cout = 2 * a.C;
     const long M = BT * (a.F / 2);
-    ConvP p{a.x, a.w, nullptr, nullptr, a.save_pre, nullptr, a.T, a.F / 2, a.C, Cout, M};   // (pre alone: no fold, no GELU output)
-    hipLaunchKernelGGL(conv_gemm_kernel<0>, conv_grid(M, Cout, 1), dim3(256), 0, s, p);
+    // (pre alone: no fold, no GELU output)
+    conv_forward_gemm(s, ConvP{a.x, a.w, nullptr, nullptr, a.save_pre, nullptr, a.T, a.F / 2, a.C, Cout, M}, a.mixed ? ws + L.wimg : nullptr);
     batch_stats(s, a.save_pre, M, Cout, part, a.bn_w, a.bn_b, ws + L.fold, a.save_mean, a.save_rstd, a.bn_mean, a.bn_var, a.bn_tracked);
     hipLaunchKernelGGL(bn_gelu_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, (const float*)a.save_pre,
                        (const float*)(ws + L.fold), M * Cout, Cout, a.y);
@@ -801,9 +860,11 @@ int bt_front_bn_backward(void* stream, int unit, const bt_front_bn_args* ap) {
   if (!ap) return fail(fn, "null argument");
   const bt_front_bn_args& a = *ap;
   if (const char* e = bn_check_shape(unit, a.B, a.T, a.F, a.C)) return fail(fn, e);
+  if (const char* e = check_mixed(unit, a.mixed, false)) return fail(fn, e);
   const long BT = (long)a.B * a.T;
-  const BnLayout L = bn_layout(unit, 1, BT, a.F, a.C);
+  const BnLayout L = bn_layout(unit, 1, BT, a.F, a.C, a.mixed != 0);
   if (!a.x || !a.gy || !a.ws) return fail(fn, "null x, upstream gradient or workspace");
+  if (a.mixed && (uintptr_t)a.ws % 16) return fail(fn, "mixed = 1: the workspace must be 16-byte aligned");
   if (!a.w || !a.bn_w || !a.bn_b || !a.save_mean || !a.save_rstd) return fail(fn, "null parameter or saved-statistics pointer");
   if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
   hipStream_t s = (hipStream_t)stream;
@@ -851,7 +912,8 @@ int bt_front_bn_backward(void* stream, int unit, const bt_front_bn_args* ap) {
     colsum(s, ws + L.b, M, Cout, ws + L.part, gw);
     hipLaunchKernelGGL(bn_centre_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, ws + L.a, (const float*)a.save_pre, f2,
                        (const float*)gb, (const float*)gw, M * Cout, Cout, (float)M, (float*)nullptr);
-    conv_backward_gemms(s, ConvP{a.x, a.w, ws + L.a, f2, nullptr, nullptr, a.T, Fo, a.C, Cout, M}, ws + L.part, a.gx, a.g_w);
+    conv_backward_gemms(s, ConvP{a.x, a.w, ws + L.a, f2, nullptr, nullptr, a.T, Fo, a.C, Cout, M}, ws + L.part, a.gx, a.g_w,
+                        a.mixed ? ws + L.wimg : nullptr);
   }
   return finish(fn);
 }

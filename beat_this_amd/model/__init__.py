@@ -207,8 +207,10 @@ class BeatThis(_TracksChildren, nn.Module):
       * ``set_frontend_trainable()`` -- whole-model fine-tuning: it sets ``requires_grad`` on the frontend's
         weights and, in grad mode, ``model(x)`` and ``model.frontend(x)`` run the frontend on the differentiable route too (the
         stem, the three conv units, the projection and the twelve attention / feed-forward leaves of the partial transformers);
-        gradients also reach ``x`` when it requires grad.  That part of the route is fp32 under ``"32-true"`` and ``"16-mixed"``
-        alike (only the trunk's units go mixed); it runs WITHOUT dropout even after ``enable_dropout`` (``dropout["frontend"]``
+        gradients also reach ``x`` when it requires grad.  That part of the route is fp32 whatever ``set_train_precision`` says
+        (it covers the trunk's units alone) unless ``set_frontend_precision("16-mixed")`` was called: then the conv units, the
+        leaves and the projection round both operands of their matrix products to fp16 and accumulate in fp32 (DESIGN.md section
+        19; the stem and everything that is no matrix product stay fp32); it runs WITHOUT dropout even after ``enable_dropout`` (``dropout["frontend"]``
         stays unused); and its BatchNorm statistics are frozen unless ``set_batch_statistics()`` was called: every BatchNorm
         uses ``running_mean`` / ``running_var``, in ``train()`` as in ``eval()``, and those buffers and
         ``num_batches_tracked`` never receive a gradient and are never updated.  The callable nodes below ``frontend`` (``stem``, ``blocks[i]``, ``.partial``, ``.linear`` ...) stay
@@ -249,6 +251,7 @@ class BeatThis(_TracksChildren, nn.Module):
         self.dropout = dict(dropout)
         self._dropout_rng = None     # enable_dropout(): {"seed", "calls"}
         self._train_precision = "32-true"
+        self._frontend_precision = "32-true"   # set_frontend_precision()
         self._frontend_trainable = False   # set_frontend_trainable()
         self._batch_statistics = False     # set_batch_statistics()
         self._stats_moved = False          # a batch-statistics forward wrote the running buffers since the engine was packed
@@ -413,7 +416,7 @@ class BeatThis(_TracksChildren, nn.Module):
         batch = self._batch_route()
         if batch:
             _bw.check_batch_statistics(int(x.shape[0]), int(x.shape[1]))
-        h = _bw.frontend_train(self, x.to(torch.float32), batch)
+        h = _bw.frontend_train(self, x.to(torch.float32), batch, self.frontend_precision == "16-mixed")
         if batch:   # noted AFTER the call: an engine that ``_rope`` packed half way through it is stale as well
             self._stats_moved = True
         return h
@@ -431,6 +434,22 @@ class BeatThis(_TracksChildren, nn.Module):
     @property
     def train_precision(self) -> str:
         return getattr(self, "_train_precision", "32-true")
+
+    # -- 16-mixed in the differentiable frontend -------------------------------------------------------------
+    def set_frontend_precision(self, precision: str) -> "BeatThis":
+        """"16-mixed": the matrix products of the differentiable frontend -- the three conv units, the twelve leaves of the
+        partial transformers and the projection -- run on fp16 operands with fp32 accumulation (the stem, BatchNorm, GELU,
+        parameters, saved tensors and gradients stay fp32); "32-true" (the default): fp32.  Independent of
+        ``set_train_precision``, which covers the trunk alone.  Read only where the differentiable frontend runs (the frontend
+        trainable and grad mode on): inference, ``no_grad`` and validation never look at it."""
+        if precision not in ("16-mixed", "32-true"):
+            raise ValueError(f"frontend precision must be '16-mixed' or '32-true', got {precision!r}")
+        self._frontend_precision = precision
+        return self
+
+    @property
+    def frontend_precision(self) -> str:
+        return getattr(self, "_frontend_precision", "32-true")
 
     # -- dropout on the differentiable route (DESIGN.md section 15) -------------------------------------------------------------
     def enable_dropout(self, seed: int = 0) -> "BeatThis":

@@ -15,7 +15,8 @@ hands out the streams.
 
 The frontend (the lower part of this file): ``StemFn``, ``ConvUnitFn``, ``SwapFn`` and ``ProjectionFn`` over
 bt_front_forward / bt_front_backward (csrc/train_front.hip), composed by ``frontend_train`` with ``AttentionFn`` /
-``FeedForwardFn`` for the twelve leaves of the partial transformers; fp32, BatchNorm on its running statistics, no dropout.
+``FeedForwardFn`` for the twelve leaves of the partial transformers; BatchNorm on its running statistics, no dropout; fp32, or
+with ``BeatThis.set_frontend_precision("16-mixed")`` the conv units, the leaves and the projection take ``mixed`` (section 19).
 ``BeatThis.set_frontend_trainable`` decides whether it runs.  ``StemBatchFn`` / ``ConvUnitBatchFn`` (section 18, bt_front_bn_*)
 are the same two units on the statistics of the call's batch; their forward moves the running buffers in place
 (``BeatThis.set_batch_statistics``).
@@ -276,7 +277,8 @@ def head(node, x, sum_head: bool):
 
 # ---- the differentiable frontend (csrc/train_front.hip) -----------------------------------------------------
 # Activations are the library's (b, t, f, c), channels last, fp32.  BatchNorm runs on its running statistics, there is no
-# dropout, and the arithmetic is fp32 whatever the train precision says.
+# dropout, and the arithmetic is fp32 whatever the train precision says; ``mixed`` (BeatThis.set_frontend_precision) puts the conv
+# units', the leaves' and the projection's matrix products on fp16 operands.
 def check_front_limits(B: int, T: int) -> None:
     """Raised before any launch: the frequency direction runs B T sequences, every unit B T 32 rows at the most."""
     if B * T > _lib.FRONT_MAX_FRAMES or B * T * 32 > _lib.FRONT_MAX_ROWS:
@@ -284,14 +286,15 @@ def check_front_limits(B: int, T: int) -> None:
                          f"{_lib.FRONT_MAX_ROWS} rows of 32 frequency tokens), got batch {B} x {T} frames: split the batch")
 
 
-def _front_args(B, T, F, Cc, dim=0) -> _lib.FrontArgs:
+def _front_args(B, T, F, Cc, dim=0, mixed=False) -> _lib.FrontArgs:
     a = _lib.FrontArgs()
-    a.B, a.T, a.F, a.C, a.dim = int(B), int(T), int(F), int(Cc), int(dim)
+    a.B, a.T, a.F, a.C, a.dim, a.mixed = int(B), int(T), int(F), int(Cc), int(dim), int(bool(mixed))
     return a
 
 
 def _front_call(backward: bool, unit: int, a: _lib.FrontArgs, device) -> None:
-    need = _lib.lib().bt_front_workspace_bytes(unit, int(backward), a.B, a.T, a.F, a.C, a.dim)
+    query = _lib.lib().bt_front_workspace_bytes_mixed if a.mixed else _lib.lib().bt_front_workspace_bytes
+    need = query(unit, int(backward), a.B, a.T, a.F, a.C, a.dim)
     if need == 0:
         check_front_limits(a.B, a.T)
         raise ValueError(f"the differentiable frontend does not support batch {a.B}, {a.T} frames, {a.F} frequency bins, "
@@ -340,10 +343,11 @@ class StemFn(torch.autograd.Function):
 
 class ConvUnitFn(torch.autograd.Function):
     """blocks.i.conv2d + .norm + GELU (beat_tracker.py:155-166): (B, T, F, C) -> (B, T, F / 2, 2 C).  Saves its input and the
-    convolution's result ``pre``.  Inputs: x, conv weight, norm weight, bias, running_mean, running_var."""
+    convolution's result ``pre``.  Inputs: x, conv weight, norm weight, bias, running_mean, running_var; ``mixed``: the three
+    products on fp16 operands (section 19), in the forward and, remembered, in the backward."""
 
     @staticmethod
-    def forward(ctx, x, w, nw, nb, nm, nv):
+    def forward(ctx, x, w, nw, nb, nm, nv, mixed=False):
         xf = _f32(x)
         ps = [_f32(p) for p in (w, nw, nb, nm, nv)]
         _on_device_of(xf, *ps)
@@ -352,11 +356,12 @@ class ConvUnitFn(torch.autograd.Function):
             raise ValueError(f"conv unit: input {tuple(xf.shape)} against a weight of shape {tuple(ps[0].shape)}")
         y = torch.empty((B, T, F // 2, 2 * Cc), dtype=torch.float32, device=xf.device)
         pre = torch.empty_like(y)
-        a = _front_args(B, T, F, Cc)
+        a = _front_args(B, T, F, Cc, mixed=mixed)
         a.x, a.y, a.save_pre, a.w = xf.data_ptr(), y.data_ptr(), pre.data_ptr(), ps[0].data_ptr()
         a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
         _front_call(False, _lib.FRONT_CONV, a, xf.device)
         ctx.save_for_backward(xf, pre, *ps)
+        ctx.mixed = bool(mixed)
         return y
 
     @staticmethod
@@ -367,12 +372,12 @@ class ConvUnitFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         gyf = _f32(gy)
         gx, g_w, g_nw, g_nb = (_grad_like(t, need[i]) for i, t in enumerate((xf, ps[0], ps[1], ps[2])))
-        a = _front_args(B, T, F, Cc)
+        a = _front_args(B, T, F, Cc, mixed=ctx.mixed)
         a.x, a.save_pre, a.gy, a.w = xf.data_ptr(), pre.data_ptr(), gyf.data_ptr(), ps[0].data_ptr()
         a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
         a.gx, a.g_w, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in (gx, g_w, g_nw, g_nb))
         _front_call(True, _lib.FRONT_CONV, a, xf.device)
-        return gx, g_w, g_nw, g_nb, None, None
+        return gx, g_w, g_nw, g_nb, None, None, None
 
 
 # ---- batch-statistics BatchNorm: the stem and the conv unit over bt_front_bn_forward / _backward -----------
@@ -385,7 +390,8 @@ def check_batch_statistics(B: int, T: int) -> None:
 
 
 def _front_bn_call(backward: bool, unit: int, a: _lib.FrontBnArgs, device) -> None:
-    need = _lib.lib().bt_front_bn_workspace_bytes(unit, int(backward), a.B, a.T, a.F, a.C)
+    query = _lib.lib().bt_front_bn_workspace_bytes_mixed if a.mixed else _lib.lib().bt_front_bn_workspace_bytes
+    need = query(unit, int(backward), a.B, a.T, a.F, a.C)
     if need == 0:
         check_front_limits(a.B, a.T)
         check_batch_statistics(a.B, a.T * (1 if unit == _lib.FRONT_STEM else a.F // 2))
@@ -448,10 +454,11 @@ class StemBatchFn(torch.autograd.Function):
 
 class ConvUnitBatchFn(torch.autograd.Function):
     """``ConvUnitFn`` with the norm on the statistics of the call's batch.  Inputs: x, conv weight, norm weight, bias, then
-    running_mean, running_var, num_batches_tracked (updated in place by the forward, outside the graph)."""
+    running_mean, running_var, num_batches_tracked (updated in place by the forward, outside the graph); ``mixed`` as
+    ``ConvUnitFn``'s (the moments are those of the fp16-product ``pre``)."""
 
     @staticmethod
-    def forward(ctx, x, w, nw, nb, nm, nv, nn_):
+    def forward(ctx, x, w, nw, nb, nm, nv, nn_, mixed=False):
         xf = _f32(x)
         ps = [_f32(p) for p in (w, nw, nb)]
         _on_device_of(xf, *ps, nm, nv, nn_)
@@ -461,13 +468,14 @@ class ConvUnitBatchFn(torch.autograd.Function):
         y = torch.empty((B, T, F // 2, 2 * Cc), dtype=torch.float32, device=xf.device)
         pre = torch.empty_like(y)
         stats = [torch.empty(2 * Cc, dtype=torch.float32, device=xf.device) for _ in range(2)]
-        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=Cc)
+        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=Cc, mixed=int(bool(mixed)))
         a.x, a.y, a.save_pre = xf.data_ptr(), y.data_ptr(), pre.data_ptr()
         a.w, a.bn_w, a.bn_b = (p.data_ptr() for p in ps)
         a.bn_mean, a.bn_var, a.bn_tracked = _running(nm, nv, nn_, 2 * Cc)
         a.save_mean, a.save_rstd = (t.data_ptr() for t in stats)
         _front_bn_call(False, _lib.FRONT_CONV, a, xf.device)
         ctx.save_for_backward(xf, pre, *ps, *stats)
+        ctx.mixed = bool(mixed)
         return y
 
     @staticmethod
@@ -477,13 +485,13 @@ class ConvUnitBatchFn(torch.autograd.Function):
         B, T, F, Cc = xf.shape
         gyf = _f32(gy)
         grads = [_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, w, nw, nb))]
-        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=Cc)
+        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=Cc, mixed=int(ctx.mixed))
         a.x, a.save_pre, a.gy = xf.data_ptr(), pre.data_ptr(), gyf.data_ptr()
         a.w, a.bn_w, a.bn_b = (p.data_ptr() for p in (w, nw, nb))
         a.save_mean, a.save_rstd = mean.data_ptr(), rstd.data_ptr()
         a.gx, a.g_w, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in grads)
         _front_bn_call(True, _lib.FRONT_CONV, a, xf.device)
-        return (*grads, None, None, None)
+        return (*grads, None, None, None, None)
 
 
 class SwapFn(torch.autograd.Function):
@@ -513,10 +521,11 @@ class SwapFn(torch.autograd.Function):
 
 
 class ProjectionFn(torch.autograd.Function):
-    """concat + frontend.linear (beat_tracker.py:71-76): (B, T, F, C) -> (B, T, D); the weight's columns are c F + f"""
+    """concat + frontend.linear (beat_tracker.py:71-76): (B, T, F, C) -> (B, T, D); the weight's columns are c F + f;
+    ``mixed``: the three GEMMs of the forward and the backward on fp16 operands (section 19)"""
 
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, mixed=False):
         xf, wf, bf = _f32(x), _f32(w), _f32(b)
         _on_device_of(xf, wf, bf)
         B, T, F, Cc = xf.shape
@@ -524,10 +533,11 @@ class ProjectionFn(torch.autograd.Function):
         if int(wf.shape[1]) != F * Cc:
             raise ValueError(f"projection: input {tuple(xf.shape)} against a weight of shape {tuple(wf.shape)}")
         y = torch.empty((B, T, D), dtype=torch.float32, device=xf.device)
-        a = _front_args(B, T, F, Cc, D)
+        a = _front_args(B, T, F, Cc, D, mixed)
         a.x, a.y, a.w, a.b = xf.data_ptr(), y.data_ptr(), wf.data_ptr(), bf.data_ptr()
         _front_call(False, _lib.FRONT_LINEAR, a, xf.device)
         ctx.save_for_backward(xf, wf, bf)
+        ctx.mixed = bool(mixed)
         return y
 
     @staticmethod
@@ -537,11 +547,11 @@ class ProjectionFn(torch.autograd.Function):
         B, T, F, Cc = xf.shape
         gyf = _f32(gy)
         gx, g_w, g_b = (_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, wf, bf)))
-        a = _front_args(B, T, F, Cc, int(wf.shape[0]))
+        a = _front_args(B, T, F, Cc, int(wf.shape[0]), ctx.mixed)
         a.x, a.gy, a.w, a.b = xf.data_ptr(), gyf.data_ptr(), wf.data_ptr(), bf.data_ptr()
         a.gx, a.g_w, a.g_b = (_lib.ptr(g) for g in (gx, g_w, g_b))
         _front_call(True, _lib.FRONT_LINEAR, a, xf.device)
-        return gx, g_w, g_b
+        return gx, g_w, g_b, None
 
 
 def _bn(node):
@@ -560,31 +570,34 @@ def stem(node, x, batch_statistics=False):
     return StemFn.apply(x, node.conv2d.weight, *_bn(node.bn1d), *_bn(node.bn2d))
 
 
-def conv_unit(block, x, batch_statistics=False):
+def conv_unit(block, x, batch_statistics=False, mixed=False):
     """``frontend.blocks[i]`` behind its partial transformer: conv2d, norm, GELU on (b, t, f, c)"""
     if batch_statistics:
-        return ConvUnitBatchFn.apply(x, block.conv2d.weight, block.norm.weight, block.norm.bias, *_stats(block.norm))
-    return ConvUnitFn.apply(x, block.conv2d.weight, *_bn(block.norm))
+        return ConvUnitBatchFn.apply(x, block.conv2d.weight, block.norm.weight, block.norm.bias, *_stats(block.norm), mixed)
+    return ConvUnitFn.apply(x, block.conv2d.weight, *_bn(block.norm), mixed)
 
 
-def partial_ft(node, x, rope_for):
+def partial_ft(node, x, rope_for, mixed=False):
     """PartialFTTransformer.forward (beat_tracker.py:290-301) on (b, t, f, c): attention and feed-forward over the frequency
     tokens of every frame, then over the time tokens of every bin -- the trunk's unit code with its residual on (B T, F, C) and
-    (B F, T, C), fp32, no dropout.  ``rope_for(n)``: the rotary table for n tokens."""
+    (B F, T, C), no dropout; fp32, or with ``mixed`` the 16-mixed unit calls.  ``rope_for(n)``: the rotary table for n tokens."""
     B, T, F, Cc = x.shape
     y = x.reshape(B * T, F, Cc)
-    y = attention(node.attnF, y, *rope_for(F), residual=True)
-    y = feedforward(node.ffF, y, residual=True)
+    y = attention(node.attnF, y, *rope_for(F), mixed=mixed, residual=True)
+    y = feedforward(node.ffF, y, mixed=mixed, residual=True)
     y = SwapFn.apply(y.reshape(B, T, F, Cc)).reshape(B * F, T, Cc)
-    y = attention(node.attnT, y, *rope_for(T), residual=True)
-    y = feedforward(node.ffT, y, residual=True)
+    y = attention(node.attnT, y, *rope_for(T), mixed=mixed, residual=True)
+    y = feedforward(node.ffT, y, mixed=mixed, residual=True)
     return SwapFn.apply(y.reshape(B, F, T, Cc))
 
 
-def frontend_train(model, x, batch_statistics=False):
+def frontend_train(model, x, batch_statistics=False, mixed=None):
     """``BeatThis.frontend`` on the differentiable route, in the reference's order (beat_tracker.py:54-80, 290-301): stem, three
     times (partial transformer, conv unit), projection.  (B, T, 128) -> (B, T, D).  ``batch_statistics``: the five BatchNorms
-    normalise with this call's batch and move their running buffers (section 18)."""
+    normalise with this call's batch and move their running buffers (section 18).  ``mixed``: the conv units, the leaves and the
+    projection on fp16 operands (section 19); None reads ``model.frontend_precision``.  The stem is fp32 either way."""
+    if mixed is None:
+        mixed = model.frontend_precision == "16-mixed"
     fr = model.frontend
     check_front_limits(int(x.shape[0]), int(x.shape[1]))
     if batch_statistics:
@@ -592,6 +605,6 @@ def frontend_train(model, x, batch_statistics=False):
     h = stem(fr.stem, x, batch_statistics)
     for blk in fr.blocks:
         if "partial" in blk._modules:
-            h = partial_ft(blk.partial, h, model._rope)
-        h = conv_unit(blk, h, batch_statistics)
-    return ProjectionFn.apply(h, fr.linear.weight, fr.linear.bias)
+            h = partial_ft(blk.partial, h, model._rope, mixed)
+        h = conv_unit(blk, h, batch_statistics, mixed)
+    return ProjectionFn.apply(h, fr.linear.weight, fr.linear.bias, mixed)

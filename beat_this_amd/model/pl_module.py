@@ -51,17 +51,19 @@ class PLBeatThis(nn.Module):
     ``dropout["frontend"]`` stays unused (frozen frontend) and the route is fp32.  The two switches are not hyper-parameters:
     a checkpoint carries the reference's keys only.  ``precision`` ("32-true", the default, or "16-mixed": the reference's
     trainer setting, ``BeatThis.set_train_precision``) is no hyper-parameter either; with "16-mixed" ``fit`` scales the loss
-    (``beat_this_amd.optim.LossScaler``).  ``max_epochs`` is stored only; ``fit`` takes the number of epochs to run."""
+    (``beat_this_amd.optim.LossScaler``).  ``frontend_precision`` ("16-mixed" or "32-true"; None leaves the model's default,
+    "32-true") is ``BeatThis.set_frontend_precision``: fp16 matrix products in the differentiable frontend, independent of
+    ``precision`` and no hyper-parameter either.  ``max_epochs`` is stored only; ``fit`` takes the number of epochs to run."""
 
     def __init__(self, spect_dim=128, fps=50, transformer_dim=512, ff_mult=4, n_layers=6, stem_dim=32,
                  dropout={"frontend": 0.1, "transformer": 0.2}, lr=0.0008, weight_decay=0.01,
                  pos_weights={"beat": 1, "downbeat": 1}, head_dim=32, loss_type="shift_tolerant_weighted_bce",
                  warmup_steps=1000, max_epochs=100, use_dbn=False, eval_trim_beats=5, sum_head=True, partial_transformers=True,
                  apply_dropout=False, dropout_seed=0, precision="32-true", train_frontend=False,
-                 batch_statistics=False):
+                 batch_statistics=False, frontend_precision=None):
         given = {k: v for k, v in locals().items()
                  if k not in ("self", "__class__", "apply_dropout", "dropout_seed", "precision", "train_frontend",
-                              "batch_statistics")}
+                              "batch_statistics", "frontend_precision")}
         super().__init__()
         hp = self.hyper_parameters = _plain(given)   # what a checkpoint carries: every constructor argument, as plain values
         for key in ("lr", "weight_decay", "fps", "warmup_steps", "max_epochs", "pos_weights", "eval_trim_beats"):
@@ -70,6 +72,8 @@ class PLBeatThis(nn.Module):
         if apply_dropout:
             self.model.enable_dropout(seed=dropout_seed)
         self.model.set_train_precision(precision)
+        if frontend_precision is not None:   # BeatThis.set_frontend_precision; no hyper-parameter, like precision
+            self.model.set_frontend_precision(frontend_precision)
         # trainable: the trunk and the heads, without the rotary tables (fixed in the reference too); frozen: the frontend
         for name, p in self.model.named_parameters():
             p.requires_grad_(not name.startswith("frontend.") and not name.endswith("rotary_embed.freqs"))

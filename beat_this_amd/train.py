@@ -4,7 +4,8 @@ up in launch_scripts/train.py:118-131 -- epochs over the training loader, gradie
 step per accumulated batch group, validation with the package's own metrics every few epochs, one checkpoint per epoch -- and
 ``python -m beat_this_amd.train`` is the command line around it.  Every step's arithmetic runs in the package's kernels: the
 differentiable route of ``BeatThis`` (fp32 or, with ``precision="16-mixed"``, fp16 matrix products under a dynamic loss scale;
-frozen frontend or, with ``train_frontend``, the whole model; dropout in the main layers when enabled), the losses, and the fused AdamW of ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
+frozen frontend or, with ``train_frontend``, the whole model, its frontend in fp32 or with ``frontend_precision="16-mixed"`` on
+fp16 products too; dropout in the main layers when enabled), the losses, and the fused AdamW of ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
 and ``load_model`` read as it is.
 
 Not offered: the reference's wandb logger, ``--compile`` and ``--force-flash-attention`` (nothing here is compiled by torch or
@@ -91,7 +92,7 @@ def validate(pl_module, datamodule) -> dict:
 
 
 def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
-        resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None) -> dict:
+        resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None, frontend_precision=None) -> dict:
     """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
 
     Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
@@ -109,6 +110,10 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     schedule steps with every optimiser call, skipped or not, as the reference's trainer does.  The losses reported are
     unscaled; the scaler's state goes into the checkpoint under ``loss_scaler`` and comes back with ``resume``.  Without
     16-mixed the calls are the ones of an fp32 run.
+
+    ``frontend_precision``: "16-mixed" or "32-true" sets the model's ``set_frontend_precision`` (None leaves it as it is), before
+    the optimiser is built: fp16 matrix products in the differentiable frontend, independent of ``precision``.  The loss scaler
+    exists when either precision is "16-mixed".
 
     ``train_frontend``: True / False calls the model's ``set_frontend_trainable`` first, before the optimiser is built, so
     that its state covers the frontend's weights (None leaves the model as it is): whole-model fine-tuning with frozen
@@ -132,7 +137,9 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
         pl_module.model.set_frontend_trainable(train_frontend)
     if batch_statistics is not None:
         pl_module.model.set_batch_statistics(batch_statistics)
-    scaler = LossScaler() if pl_module.model.train_precision == "16-mixed" else None
+    if frontend_precision is not None:
+        pl_module.model.set_frontend_precision(frontend_precision)
+    scaler = LossScaler() if "16-mixed" in (pl_module.model.train_precision, pl_module.model.frontend_precision) else None
     accumulate = int(accumulate_grad_batches)
     if accumulate < 1 or int(max_epochs) < 0 or int(val_frequency) < 1:
         raise ValueError("accumulate_grad_batches and val_frequency must be at least 1, max_epochs at least 0")
@@ -232,7 +239,10 @@ def get_parser() -> argparse.ArgumentParser:
                         "weights, a dynamic loss scale (default: %(default)s)")
     p.add_argument("--train-frontend", default=False, action=toggle,
                    help="whole-model fine-tuning: also train the frontend (frozen BatchNorm statistics, no frontend dropout, "
-                        "fp32 frontend under either precision; default: the frontend stays frozen)")
+                        "fp32 frontend unless --frontend-precision 16-mixed; default: the frontend stays frozen)")
+    p.add_argument("--frontend-precision", type=str, default="32-true", choices=["32-true", "16-mixed"],
+                   help="with --train-frontend: 16-mixed runs the matrix products of the frontend's conv units, partial "
+                        "transformers and projection on fp16 operands too, under the same loss scale (default: %(default)s)")
     p.add_argument("--batch-statistics", default=False, action=toggle,
                    help="with --train-frontend: the frontend's BatchNorms use each batch's statistics and update their running "
                         "ones, as training from scratch needs (default: frozen running statistics)")
@@ -259,6 +269,8 @@ def main(argv=None) -> int:
     args = parser.parse_args(argv)
     if args.batch_statistics and not args.train_frontend:
         parser.error("--batch-statistics needs --train-frontend: batch statistics belong to the differentiable frontend")
+    if args.frontend_precision != "32-true" and not args.train_frontend:
+        parser.error("--frontend-precision needs --train-frontend: it belongs to the differentiable frontend")
     from .dataset import BeatDataModule
     from .inference import load_checkpoint
     from .model.pl_module import PLBeatThis
@@ -290,7 +302,7 @@ def main(argv=None) -> int:
                            weight_decay=args.weight_decay, pos_weights=pos_weights, loss_type=args.loss,
                            warmup_steps=args.warmup_steps, max_epochs=args.max_epochs, use_dbn=args.dbn,
                            eval_trim_beats=args.eval_trim_beats, precision=args.precision, train_frontend=args.train_frontend,
-                           batch_statistics=args.batch_statistics)
+                           batch_statistics=args.batch_statistics, frontend_precision=args.frontend_precision)
     if ckpt is not None and not args.resume_checkpoint:   # (a resumed run's weights are restored by fit() with the rest)
         pl_module.load_state_dict(ckpt["state_dict"])
     pl_module.to(device)

@@ -713,7 +713,7 @@ int bt_train_backward_mixed(void* stream, int unit, const bt_train_args* a, cons
 int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B, int M, int N, int K, float* C);
 /* The GEMM of either training route (mixed = 0: the fp32 MFMA kernels, 1: the fp16 ones) through the host helpers
  * the unit calls launch it with.  A diagnostic for the trunk's units, and PRODUCTION for the frontend's projection:
- * bt_front_forward / bt_front_backward (BT_FRONT_LINEAR) call forms 0, 1 and 2 with mixed = 0 and size their workspace with
+ * bt_front_forward / bt_front_backward (BT_FRONT_LINEAR) call forms 0, 1 and 2 with their own `mixed` and size their workspace with
  * bt_train_matmul_workspace_bytes, so what this entry computes, and in which order it sums, is part of section 17's contract.
  * Forms as above, forms as above, C [M, N] contiguous, 1 <= M, N, K <= 2^22.  The caller supplies every buffer;
  * nothing is allocated, cleared or synchronised.
@@ -774,7 +774,7 @@ int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int 
 #define BT_FRONT_LINEAR 2
 #define BT_FRONT_SWAP 3
 typedef struct {
-  int32_t B, T, F, C, dim, reserved0, reserved1, reserved2;
+  int32_t B, T, F, C, dim, mixed, reserved1, reserved2;
   const float* w; const float* b;
   const float* bn_w; const float* bn_b; const float* bn_mean; const float* bn_var;
   const float* bn1_w; const float* bn1_b; const float* bn1_mean; const float* bn1_var;
@@ -812,7 +812,7 @@ int bt_front_backward(void* stream, int unit, const bt_front_args* a);
  * n = 1 (torch: "Expected more than 1 value per channel when training") is BT_ERR_ARG before any launch, like every shape the
  * calls above refuse and every NULL among the required pointers; the workspace query then returns 0. */
 typedef struct {
-  int32_t B, T, F, C, reserved0, reserved1, reserved2, reserved3;
+  int32_t B, T, F, C, mixed, reserved1, reserved2, reserved3;
   const float* w;
   const float* bn_w; const float* bn_b; float* bn_mean; float* bn_var; int64_t* bn_tracked;
   const float* bn1_w; const float* bn1_b; float* bn1_mean; float* bn1_var; int64_t* bn1_tracked;
@@ -827,6 +827,34 @@ void bt_front_bn_struct_sizes(int32_t* out);
 size_t bt_front_bn_workspace_bytes(int unit, int backward, int B, int T, int F, int C);
 int bt_front_bn_forward(void* stream, int unit, const bt_front_bn_args* a);
 int bt_front_bn_backward(void* stream, int unit, const bt_front_bn_args* a);
+
+/* ---- training: 16-mixed in the frontend (csrc/train_front_mixed.inc) -------------------------------------
+ * The `mixed` field of both argument structs above is their first reserved int32; the layouts and the self-checks are
+ * unchanged.  0 selects the launches described above, bit for bit.  1 extends the 16-mixed contract of bt_train_forward_mixed
+ * to the frontend's own products: BOTH operands of every matrix product are rounded to IEEE fp16 (to nearest even; beyond
+ * fp16's range: inf) as they are staged, and the products accumulate in fp32 on v_mfma_f32_32x32x16_f16.
+ *   BT_FRONT_CONV    pre = A W^T, g_x = G W and g_W = G^T A.  A is the implicit im2col of x: rows (b, t, f'), columns
+ *                    dt 2 C + df C + ci, zero where frame t + dt - 1 lies outside the row's own sequence; G = g_pre s is multiplied
+ *                    in fp32 and then rounded.  A small launch at the head of the call packs the weight once into an fp16 image
+ *                    in the workspace ([co][dt][df C + ci] for the forward, its transpose for g_x): the same values, rounded
+ *                    the same way.  The epilogues are the fp32 kernels': pre and gelu(s pre + sh), per-chunk partials of g_W.
+ *   BT_FRONT_LINEAR  (bt_front_args only) forms 0, 1 and 2 of bt_train_matmul with mixed = 1.
+ * With bt_front_bn_forward / _backward (BT_FRONT_CONV) the forward takes the moments of the fp16-product pre and the backward's
+ * two GEMMs run mixed on the centred g_pre.  The frontend's twelve leaves are bt_train_forward_mixed / bt_train_backward_mixed
+ * calls with residual = 1.  Everything else stays fp32 and stays the code above: the stem (K = 12: no product worth an MFMA),
+ * BatchNorm folding, statistics and centring, GELU and its derivative, save_pre, the swaps, the column sums and the chunked g_W
+ * reduction, parameters, saved tensors and gradients.  Nothing clamps: a loss scaler sees an overflow in the gradient norm.
+ * Kept from section 13: no atomics; one writer per output byte; every order of summation depends on the shapes alone -- a
+ * forward or backward-data element sums k ascending in MFMA steps of 16, g_W sums the rows ascending in steps of 16 inside each
+ * chunk of BT_TRAIN_DW_ROWS rows and the chunks are added in order by the unchanged reduction -- so two runs are bit-identical;
+ * on running statistics a sequence's g_x is the same alone and inside a batch; no call synchronises, allocates or clears
+ * memory; no launch reads workspace bytes its own call has not written.
+ * mixed = 1 with BT_FRONT_STEM or BT_FRONT_SWAP (or BT_FRONT_LINEAR in bt_front_bn_args), and any value other than 0 and 1, is
+ * BT_ERR_ARG before any launch.  mixed = 1 needs a 16-byte aligned workspace of the size the two queries below return (the
+ * fp32 size plus the weight image); they take the parameters of the fp32 queries, whose values are unchanged, and return 0 for
+ * unsupported shapes and for units that have no mixed form. */
+size_t bt_front_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C, int dim);
+size_t bt_front_bn_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C);
 
 /* ---- training: the optimiser step (csrc/optim.hip) ------------------------------------------------------
  * Multi-tensor AdamW with torch.optim.AdamW's default semantics (decoupled decay, no amsgrad, no maximize), all fp32.  With
