@@ -11,6 +11,9 @@
 // stem and the conv unit on the statistics of the call's own batch instead -- torch's training-mode BatchNorm: the same
 // kernels, the fold table written by the launch that finishes the statistics and moves the running buffers, one elementwise
 // launch for the GELU, and one that centres the gradient at each BatchNorm's input.
+// Both families of entry points fill one description of the call (Call) and run one preamble and one launch sequence per unit and
+// direction, which branches on `batch` at exactly those three points.  Every refusal comes before any launch, checked in this
+// order: null struct, shape, mixed, required pointers, workspace alignment, workspace size.
 //
 // The conv unit's three matrix products are implicit GEMMs on v_mfma_f32_32x32x2_f32: the operand tiles are staged into LDS
 // straight from the activation (a row of the implicit A matrix is three runs of 2 Cin floats at t - 1, t, t + 1, zeros
@@ -54,17 +57,22 @@ unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
 int dw_chunks(long M) { return (int)((M + DW_ROWS - 1) / DW_ROWS); }
 int cs_chunks(long M) { return (int)((M + CS_ROWS - 1) / CS_ROWS); }
 
-// fold [4][C]: s, sh, 1 / sqrt(var + eps), mean
-__global__ __launch_bounds__(256) void bn_fold_kernel(const float* w, const float* b, const float* mean, const float* var, int C,
-                                                      float* fold) {
+// fold [4][C]: s, sh, 1 / sqrt(var + eps), mean.  The one writer of a channel's four entries: s = w rstd in fp64, rounded once.
+__device__ inline void write_fold(float* fold, int C, int c, float w, float b, float mean, double rstd) {
+  const double s = (double)w * rstd;
+  fold[c] = (float)s;
+  fold[C + c] = (float)((double)b - (double)mean * s);
+  fold[2 * C + c] = (float)rstd;
+  fold[3 * C + c] = mean;
+}
+
+// saved == 0: stat = the running variance, rstd stays unrounded fp64 inside s; saved != 0: stat = the forward's saved batch
+// rstd, the ROUNDED value bn_finish_kernel built its table from (the backward rebuilds that table bit for bit)
+__global__ __launch_bounds__(256) void bn_fold_kernel(const float* w, const float* b, const float* mean, const float* stat, int saved,
+                                                      int C, float* fold) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
-  const double rstd = 1.0 / sqrt((double)var[c] + 1e-5);
-  const double s = (double)w[c] * rstd;
-  fold[c] = (float)s;
-  fold[C + c] = (float)((double)b[c] - (double)mean[c] * s);
-  fold[2 * C + c] = (float)rstd;
-  fold[3 * C + c] = mean[c];
+  write_fold(fold, C, c, w[c], b[c], mean[c], saved ? (double)stat[c] : 1.0 / sqrt((double)stat[c] + 1e-5));
 }
 
 // part[chunk][j] = sum over the chunk's CS_ROWS rows of a[m][j], rows ascending
@@ -163,27 +171,11 @@ __global__ __launch_bounds__(256) void bn_finish_kernel(const double* part, long
   if (c == 0 && tracked) *tracked += 1;
   const double n = runs[0].n, mean = runs[0].mean, var = runs[0].m2 / n;
   const float mean_f = (float)mean, rstd_f = (float)(1.0 / sqrt(var + 1e-5));
-  const double s = (double)w[c] * (double)rstd_f;
-  fold[c] = (float)s;
-  fold[C + c] = (float)((double)b[c] - (double)mean_f * s);
-  fold[2 * C + c] = rstd_f;
-  fold[3 * C + c] = mean_f;
+  write_fold(fold, C, c, w[c], b[c], mean_f, (double)rstd_f);
   save_mean[c] = mean_f;
   save_rstd[c] = rstd_f;
   run_mean[c] = (float)(0.9 * (double)run_mean[c] + 0.1 * mean);
   run_var[c] = (float)(0.9 * (double)run_var[c] + 0.1 * (var * (n / (n - 1.0))));
-}
-
-// the backward's fold table, from the forward's saved batch statistics
-__global__ __launch_bounds__(256) void bn_fold_saved_kernel(const float* w, const float* b, const float* mean, const float* rstd, int C,
-                                                            float* fold) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  const double s = (double)w[c] * (double)rstd[c];
-  fold[c] = (float)s;
-  fold[C + c] = (float)((double)b[c] - (double)mean[c] * s);
-  fold[2 * C + c] = rstd[c];
-  fold[3 * C + c] = mean[c];
 }
 
 // y = gelu(s pre + sh), the expression of conv_gemm<0>'s epilogue
@@ -206,14 +198,6 @@ __global__ __launch_bounds__(256) void bn_centre_kernel(float* g, const float* v
   const float r = g[i] - gb[c] / rows - xhat * (gw[c] / rows);
   if (gx) gx[i] = r * fold[c];
   else g[i] = r;
-}
-
-void batch_stats(hipStream_t s, const float* a, long M, int C, double* part, const float* w, const float* b, float* fold,
-                 float* save_mean, float* save_rstd, float* run_mean, float* run_var, int64_t* tracked) {
-  const int chunks = cs_chunks(M);
-  hipLaunchKernelGGL(bn_moments_kernel, dim3((unsigned)chunks, blocks_of(C, 256)), dim3(256), 0, s, a, M, C, part);
-  hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)C), dim3(256), 0, s, (const double*)part, M, C, chunks, w, b, fold,
-                     save_mean, save_rstd, run_mean, run_var, tracked);
 }
 
 // ---- conv unit -------------------------------------------------------------------------------------------------------------
@@ -247,40 +231,76 @@ __device__ inline float conv_w(const ConvP& p, int co, int j, int dt) {
   return p.w[((long)co * p.Cin + ci) * 6 + df * 3 + dt];
 }
 
-// MODE 0: forward, 1: backward-data, 2: backward-weight (blockIdx.z = chunk of DW_ROWS rows)
+// The frame of a conv GEMM, the fp32 kernel's below and the fp16 one's in train_front_mixed.inc: what differs between the two is
+// how the operand tiles are staged and multiplied, nothing else.
+// MODE 0: forward, 1: backward-data, 2: backward-weight (blockIdx.z = chunk of DW_ROWS rows).  The product is GM x GN; a workgroup
+// owns the GT x GT tile at (m0, n0) and sums k over [kb, ke).
+template <int MODE>
+struct ConvTile {
+  int C2;
+  long GM;
+  int GN;
+  long kb, ke, m0;
+  int n0;
+  __device__ explicit ConvTile(const ConvP& p)
+      : C2(2 * p.Cin),
+        GM(MODE == 2 ? (long)p.Cout : p.M),
+        GN(MODE == 0 ? p.Cout : MODE == 1 ? C2 : 3 * C2),
+        kb(MODE == 2 ? (long)blockIdx.z * DW_ROWS : 0),
+        ke(MODE == 0 ? 3L * C2 : MODE == 1 ? 3L * p.Cout : std::min<long>(p.M, kb + DW_ROWS)),
+        m0((long)blockIdx.y * GT),
+        n0(blockIdx.x * GT) {}
+};
+
+// The epilogue of wave (wm, wn), lane (g, lr): the 32 x 32 accumulator tile to p.out (MODE 0: pre, and y = gelu(s pre + sh) to
+// p.out2 unless that is null; MODE 1: g_x; MODE 2: the chunk's partial of g_W).  C / D map of the 32x32 MFMAs, fp32 and fp16
+// alike: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
+template <int MODE>
+__device__ inline void conv_store(const ConvP& p, const ConvTile<MODE> t, const f32x16& acc, int wm, int wn, int lr, int g) {
+  const int col = t.n0 + wn * 32 + lr;
+  if (col >= t.GN) return;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const long row = t.m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+    if (row >= t.GM) continue;
+    if (MODE == 0) {
+      p.out[row * p.Cout + col] = acc[r];
+      if (p.out2) p.out2[row * p.Cout + col] = gelu_f(p.fold[col] * acc[r] + p.fold[p.Cout + col]);   // (null: batch statistics)
+    } else if (MODE == 1) {
+      p.out[row * t.C2 + col] = acc[r];
+    } else {
+      p.out[((long)blockIdx.z * p.Cout + row) * (3 * t.C2) + col] = acc[r];
+    }
+  }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvP p) {
   __shared__ float As[GK][GT + 4];
   __shared__ float Bs[GK][GT + 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 5, lr = lane & 31, wm = wave >> 1, wn = wave & 1;
-  const int C2 = 2 * p.Cin;
-  const long GM = MODE == 2 ? (long)p.Cout : p.M;
-  const int GN = MODE == 0 ? p.Cout : MODE == 1 ? C2 : 3 * C2;
-  const long kb = MODE == 2 ? (long)blockIdx.z * DW_ROWS : 0;
-  const long ke = MODE == 0 ? 3L * C2 : MODE == 1 ? 3L * p.Cout : std::min<long>(p.M, kb + DW_ROWS);
-  const long m0 = (long)blockIdx.y * GT;
-  const int n0 = blockIdx.x * GT;
+  const ConvTile<MODE> tile(p);
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-  for (long k0 = kb; k0 < ke; k0 += GK) {
+  for (long k0 = tile.kb; k0 < tile.ke; k0 += GK) {
 #pragma unroll
     for (int i = 0; i < GT * GK / 256; ++i) {
       const int e = tid + i * 256;
       // MODE 0 / 1: the k index runs fastest (a row of A is contiguous in k); MODE 2: the tile's row / column does
       const int kk = MODE == 2 ? e / GT : e % GK, mn = MODE == 2 ? e % GT : e / GK;
-      const long gk = k0 + kk, gm = m0 + mn;
-      const int gn = n0 + mn;
+      const long gk = k0 + kk, gm = tile.m0 + mn;
+      const int gn = tile.n0 + mn;
       float a = 0.0f, b = 0.0f;
-      if (gk < ke) {
-        if (gm < GM) {
+      if (gk < tile.ke) {
+        if (gm < tile.GM) {
           if (MODE == 0) a = conv_a(p, gm, (int)gk);
           if (MODE == 1) a = conv_g(p, gm, (int)gk);
           if (MODE == 2) a = p.g[gk * p.Cout + gm] * p.fold[gm];
         }
-        if (gn < GN) {
-          if (MODE == 0) b = conv_w(p, gn, (int)gk % C2, (int)gk / C2);
+        if (gn < tile.GN) {
+          if (MODE == 0) b = conv_w(p, gn, (int)gk % tile.C2, (int)gk / tile.C2);
           if (MODE == 1) b = conv_w(p, (int)gk % p.Cout, gn, (int)gk / p.Cout);
           if (MODE == 2) b = conv_a(p, gk, gn);
         }
@@ -294,21 +314,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvP p) {
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + g][wm * 32 + lr], Bs[kk + g][wn * 32 + lr], acc, 0, 0, 0);
     __syncthreads();
   }
-  const int col = n0 + wn * 32 + lr;
-  if (col >= GN) return;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {   // (C / D map of the 32x32 MFMAs: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5))
-    const long row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-    if (row >= GM) continue;
-    if (MODE == 0) {
-      p.out[row * p.Cout + col] = acc[r];
-      if (p.out2) p.out2[row * p.Cout + col] = gelu_f(p.fold[col] * acc[r] + p.fold[p.Cout + col]);   // (null: batch statistics)
-    } else if (MODE == 1) {
-      p.out[row * C2 + col] = acc[r];
-    } else {
-      p.out[((long)blockIdx.z * p.Cout + row) * (3 * C2) + col] = acc[r];
-    }
-  }
+  conv_store<MODE>(p, tile, acc, wm, wn, lr, g);
 }
 
 #include "train_front_mixed.inc"   // conv_pack_kernel, conv_gemm_mixed_kernel<MODE>: the same three products on fp16 MFMAs
@@ -354,42 +360,49 @@ __device__ inline float stem_pre(const float* x, const float* w, const float* f1
   return acc;
 }
 
+// The head of the stem's four elementwise kernels: this thread's flat element i = (bt, fo, co) of the [BT, 32, 32] output, its
+// channel and its recomputed pre; `in` is false past the end
+struct StemElement {
+  long i;
+  int co;
+  float pre;
+  bool in;
+};
+__device__ inline StemElement stem_element(const float* x, const float* w, const float* f1, long BT, int T) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= BT * STEM_F * STEM_C) return StemElement{i, 0, 0.0f, false};
+  const int co = (int)(i % STEM_C), fo = (int)((i / STEM_C) % STEM_F);
+  return StemElement{i, co, stem_pre(x, w, f1, T, i / (STEM_F * STEM_C), fo, co), true};
+}
+
 __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* x, const float* w, const float* f1, const float* f2, long BT, int T,
                                                        float* y) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= BT * STEM_F * STEM_C) return;
-  const int co = (int)(i % STEM_C), fo = (int)((i / STEM_C) % STEM_F);
-  const float pre = stem_pre(x, w, f1, T, i / (STEM_F * STEM_C), fo, co);
-  y[i] = gelu_f(f2[co] * pre + f2[STEM_C + co]);
+  const StemElement e = stem_element(x, w, f1, BT, T);
+  if (e.in) y[e.i] = gelu_f(f2[e.co] * e.pre + f2[STEM_C + e.co]);
 }
 
 __global__ __launch_bounds__(256) void stem_gpre_kernel(const float* x, const float* w, const float* f1, const float* f2,
                                                         const float* gy, long BT, int T, float* gp, float* gh) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= BT * STEM_F * STEM_C) return;
-  const int co = (int)(i % STEM_C), fo = (int)((i / STEM_C) % STEM_F);
-  const float pre = stem_pre(x, w, f1, T, i / (STEM_F * STEM_C), fo, co);
-  const float gv = gy[i] * gelu_grad_f(f2[co] * pre + f2[STEM_C + co]);
-  gp[i] = gv;
-  gh[i] = gv * ((pre - f2[3 * STEM_C + co]) * f2[2 * STEM_C + co]);
+  const StemElement e = stem_element(x, w, f1, BT, T);
+  if (!e.in) return;
+  const float gv = gy[e.i] * gelu_grad_f(f2[e.co] * e.pre + f2[STEM_C + e.co]);
+  gp[e.i] = gv;
+  gh[e.i] = gv * ((e.pre - f2[3 * STEM_C + e.co]) * f2[2 * STEM_C + e.co]);
 }
 
 // batch statistics: pre alone, staged in the workspace for its statistics and the GELU pass
 __global__ __launch_bounds__(256) void stem_pre_kernel(const float* x, const float* w, const float* f1, long BT, int T, float* pre) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= BT * STEM_F * STEM_C) return;
-  pre[i] = stem_pre(x, w, f1, T, i / (STEM_F * STEM_C), (int)((i / STEM_C) % STEM_F), (int)(i % STEM_C));
+  const StemElement e = stem_element(x, w, f1, BT, T);
+  if (e.in) pre[e.i] = e.pre;
 }
 
 // bn_centre_kernel for bn2d, whose input is recomputed
 __global__ __launch_bounds__(256) void stem_centre_kernel(const float* x, const float* w, const float* f1, const float* f2, float* g,
                                                           const float* gb, const float* gw, long BT, int T, float rows) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= BT * STEM_F * STEM_C) return;
-  const int co = (int)(i % STEM_C), fo = (int)((i / STEM_C) % STEM_F);
-  const float pre = stem_pre(x, w, f1, T, i / (STEM_F * STEM_C), fo, co);
-  const float xhat = (pre - f2[3 * STEM_C + co]) * f2[2 * STEM_C + co];
-  g[i] = g[i] - gb[co] / rows - xhat * (gw[co] / rows);
+  const StemElement e = stem_element(x, w, f1, BT, T);
+  if (!e.in) return;
+  const float xhat = (e.pre - f2[3 * STEM_C + e.co]) * f2[2 * STEM_C + e.co];
+  g[e.i] = g[e.i] - gb[e.co] / rows - xhat * (gw[e.co] / rows);
 }
 
 // part[chunk][co][df][dt] = sum over the chunk's DW_ROWS rows (b, t, fo) of g_conv[row][co] xn(b, t + dt - 1, 4 fo + df)
@@ -445,15 +458,18 @@ void swap(hipStream_t s, const float* x, long B, int P, int Q, int C, float* y) 
   hipLaunchKernelGGL(swap_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, x, n, P, Q, C, y);
 }
 
-// ---- workspace layouts (floats; every region a multiple of 64 floats) ---------------------------------------------------------
+// ---- workspace layout (floats; every region a multiple of 64 floats) -----------------------------------------------------------
 size_t up64(size_t n) { return (n + 63) / 64 * 64; }
 
 struct Layout {
-  size_t fold, fold1, a, b, c, d, part, wimg, total;
+  size_t fold, fold1, pre, a, b, c, d, sums, sums1, part, wimg, total;
 };
 
-// mixed: the conv unit's fp16 weight image (Cout 6 Cin halves; the forward's, or the backward-data's transposed one)
-Layout layout(int unit, int backward, long BT, int F, int C, int dim, bool mixed = false) {
+// The one layout of every route.  batch (section 18) adds the column sums of the backward (its centring needs them whether the
+// caller wants them or not) and, to the forward, the stem's staged pre and the chunks' moments (two doubles per column: four floats
+// of the workspace); mixed (section 19) adds the conv unit's fp16 weight image (Cout 6 Cin halves; the forward's, or the
+// backward-data's transposed one).
+Layout layout(int unit, bool backward, bool batch, bool mixed, long BT, int F, int C, int dim) {
   Layout L{};
   size_t at = 0;
   auto take = [&](size_t n) { const size_t o = at; at += up64(n); return o; };
@@ -467,7 +483,14 @@ Layout layout(int unit, int backward, long BT, int F, int C, int dim, bool mixed
         L.b = take(M * STEM_C);          // g_pre xhat
         L.c = take((size_t)BT * MEL);    // gradient of the bn1d output
         L.d = take((size_t)BT * MEL);    // the same times xhat
+        if (batch) {
+          L.sums = take(2 * STEM_C);     // g_bias, g_weight of bn2d when the caller wants none
+          L.sums1 = take(2 * MEL);       // the same of bn1d
+        }
         L.part = take(std::max({(size_t)dw_chunks(M) * STEM_C * STEM_TAPS, (size_t)cs_chunks(M) * STEM_C, (size_t)cs_chunks(BT) * MEL}));
+      } else if (batch) {
+        L.pre = take(M * STEM_C);
+        L.part = take(4 * std::max((size_t)cs_chunks(M) * STEM_C, (size_t)cs_chunks(BT) * MEL));
       }
       break;
     }
@@ -477,7 +500,10 @@ Layout layout(int unit, int backward, long BT, int F, int C, int dim, bool mixed
       if (backward) {
         L.a = take(M * Cout);            // g_pre
         L.b = take(M * Cout);            // g_pre xhat
+        if (batch) L.sums = take(2 * Cout);
         L.part = take(std::max((size_t)dw_chunks(M) * Cout * 6 * C, (size_t)cs_chunks(M) * Cout));
+      } else if (batch) {
+        L.part = take(4 * (size_t)cs_chunks(M) * Cout);
       }
       if (mixed) L.wimg = take(Cout * 3 * C);
       break;
@@ -524,6 +550,21 @@ const char* check_shape(int unit, int B, int T, int F, int C, int dim) {
   return nullptr;
 }
 
+const char* bn_check_shape(int unit, int B, int T, int F, int C) {
+  if (unit != BT_FRONT_STEM && unit != BT_FRONT_CONV) return "batch statistics: unit must be BT_FRONT_STEM or BT_FRONT_CONV";
+  if (const char* e = check_shape(unit, B, T, F, C, 0)) return e;
+  if ((long)B * T * (unit == BT_FRONT_STEM ? 1 : F / 2) < 2) return "Expected more than 1 value per channel when training";
+  return nullptr;
+}
+
+// 16-mixed: the units that have a mixed form (the projection's is bt_train_matmul's, which bt_front_bn_args does not reach)
+const char* check_mixed(int unit, int mixed, bool linear_too) {
+  if (mixed != 0 && mixed != 1) return "mixed must be 0 or 1";
+  if (mixed && unit != BT_FRONT_CONV && !(linear_too && unit == BT_FRONT_LINEAR))
+    return "mixed = 1 belongs to BT_FRONT_CONV and (bt_front_args) BT_FRONT_LINEAR: the other units have no product worth an MFMA";
+  return nullptr;
+}
+
 int fail(const char* fn, const char* msg, int code = BT_ERR_ARG) {
   return bt_set_error_external(code, (std::string(fn) + ": " + msg).c_str());
 }
@@ -534,116 +575,277 @@ int finish(const char* fn) {
   return BT_OK;
 }
 
-void fold(hipStream_t s, const float* w, const float* b, const float* mean, const float* var, int C, float* out) {
-  hipLaunchKernelGGL(bn_fold_kernel, dim3(blocks_of(C, 256)), dim3(256), 0, s, w, b, mean, var, C, out);
+// ---- one description of a call, whichever argument struct it came in ------------------------------------------------------------
+// One BatchNorm: gain and bias; the running buffers (read on running statistics, moved by the batch forward, left alone by the
+// batch backward); the batch route's counter and saved statistics; the two gradients.
+struct Bn {
+  const float *w, *b;
+  float *mean, *var;
+  int64_t* tracked;
+  float *save_mean, *save_rstd;
+  float *g_w, *g_b;
+};
+
+struct Call {
+  int B, T, F, C, dim;
+  int mixed;   // as the caller gave it: check_mixed refuses everything but 0 and 1
+  bool batch, backward;
+  Bn bn, bn1;  // bn2d or blocks.i.norm; the stem's bn1d
+  const float *w, *b, *x, *gy;
+  float *y, *save_pre, *gx, *g_w, *g_b;
+  void* ws;
+  size_t ws_bytes;
+};
+
+Call describe(const bt_front_args& a, bool backward) {
+  Call c{a.B, a.T, a.F, a.C, a.dim, a.mixed, false, backward};
+  // (running statistics: the two buffers are only read)
+  c.bn = Bn{a.bn_w, a.bn_b, const_cast<float*>(a.bn_mean), const_cast<float*>(a.bn_var), nullptr, nullptr, nullptr, a.g_bn_w, a.g_bn_b};
+  c.bn1 = Bn{a.bn1_w, a.bn1_b, const_cast<float*>(a.bn1_mean), const_cast<float*>(a.bn1_var), nullptr, nullptr, nullptr, a.g_bn1_w, a.g_bn1_b};
+  c.w = a.w, c.b = a.b, c.x = a.x, c.gy = a.gy;
+  c.y = a.y, c.save_pre = a.save_pre, c.gx = a.gx, c.g_w = a.g_w, c.g_b = a.g_b;
+  c.ws = a.ws, c.ws_bytes = a.ws_bytes;
+  return c;
+}
+
+Call describe(const bt_front_bn_args& a, bool backward) {
+  Call c{a.B, a.T, a.F, a.C, 0, a.mixed, true, backward};
+  c.bn = Bn{a.bn_w, a.bn_b, a.bn_mean, a.bn_var, a.bn_tracked, a.save_mean, a.save_rstd, a.g_bn_w, a.g_bn_b};
+  c.bn1 = Bn{a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, a.bn1_tracked, a.save1_mean, a.save1_rstd, a.g_bn1_w, a.g_bn1_b};
+  c.w = a.w, c.x = a.x, c.gy = a.gy;
+  c.y = a.y, c.save_pre = a.save_pre, c.gx = a.gx, c.g_w = a.g_w;
+  c.ws = a.ws, c.ws_bytes = a.ws_bytes;
+  return c;
+}
+
+// what the call needs of one BatchNorm
+bool bn_complete(const Call& c, const Bn& n) {
+  return n.w && n.b && ((c.batch && c.backward) || (n.mean && n.var)) && (!c.batch || (n.save_mean && n.save_rstd));
+}
+
+// the required pointers; the texts name the groups as each entry point's documentation does
+const char* check_pointers(int unit, const Call& c) {
+  const bool stem = unit == BT_FRONT_STEM, conv = unit == BT_FRONT_CONV;
+  if (c.batch) {
+    if (!c.backward && (!c.x || !c.y || !c.ws)) return "null x, y or workspace";
+    if (c.backward && (!c.x || !c.gy || !c.ws)) return "null x, upstream gradient or workspace";
+    if (!c.w || !bn_complete(c, c.bn))
+      return c.backward ? "null parameter or saved-statistics pointer" : "null parameter, running buffer or saved-statistics pointer";
+    if (stem && !bn_complete(c, c.bn1))
+      return c.backward ? "null bn1d parameter or saved-statistics pointer"
+                        : "null bn1d parameter, running buffer or saved-statistics pointer";
+    if (conv && !c.save_pre) return "null saved-tensor pointer";
+    return nullptr;
+  }
+  if (!c.backward && (!c.x || !c.y || !c.ws)) return "null x, y or workspace";
+  if (c.backward && (!c.gy || !c.ws)) return "null upstream gradient or workspace";
+  if (c.backward && unit != BT_FRONT_SWAP && !c.x) return "null x";
+  if (stem && (!c.w || !bn_complete(c, c.bn) || !bn_complete(c, c.bn1))) return "null parameter";
+  if (conv && (!c.w || !bn_complete(c, c.bn) || !c.save_pre)) return "null parameter or saved-tensor pointer";
+  if (unit == BT_FRONT_LINEAR && (!c.w || (!c.backward && !c.b))) return "null parameter";
+  if (unit == BT_FRONT_SWAP && c.backward && !c.gx) return "null gx";
+  return nullptr;
+}
+
+// The preamble of the four entry points, before any launch.  The order: shape, mixed, required pointers, alignment, workspace size.
+int prepare(const char* fn, int unit, const Call& c, Layout& L) {
+  const char* e = c.batch ? bn_check_shape(unit, c.B, c.T, c.F, c.C) : check_shape(unit, c.B, c.T, c.F, c.C, c.dim);
+  if (!e) e = check_mixed(unit, c.mixed, !c.batch);
+  if (!e) e = check_pointers(unit, c);
+  if (!e && c.batch && !c.backward && (uintptr_t)c.ws % 8) e = "the workspace must be 8-byte aligned";   // (the moments are doubles)
+  if (!e && c.mixed && (uintptr_t)c.ws % 16) e = "mixed = 1: the workspace must be 16-byte aligned";
+  if (e) return fail(fn, e);
+  L = layout(unit, c.backward, c.batch, c.mixed != 0, (long)c.B * c.T, c.F, c.C, c.dim);
+  if (c.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
+  return BT_OK;
+}
+
+// ---- launch sequences: one per unit and direction.  They branch on c.batch where section 18 says the routes differ: where the
+// fold table comes from (fold_table), one centring launch per BatchNorm in the backward, the GELU as a launch of its own in the
+// forward -----------------------------------------------------------------------------------------------------------------------
+// On running statistics the table is folded from the running buffers; the batch forward takes the moments of v [rows, C] (and
+// writes the saved statistics and moves the running buffers in the same launch); the batch backward folds the saved statistics.
+void fold_table(hipStream_t s, const Call& c, const Bn& n, int C, const float* v, long rows, const Layout& L, float* out) {
+  if (c.batch && !c.backward) {
+    const int chunks = cs_chunks(rows);
+    double* part = (double*)((float*)c.ws + L.part);
+    hipLaunchKernelGGL(bn_moments_kernel, dim3((unsigned)chunks, blocks_of(C, 256)), dim3(256), 0, s, v, rows, C, part);
+    hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)C), dim3(256), 0, s, (const double*)part, rows, C, chunks, n.w, n.b, out,
+                       n.save_mean, n.save_rstd, n.mean, n.var, n.tracked);
+  } else {
+    hipLaunchKernelGGL(bn_fold_kernel, dim3(blocks_of(C, 256)), dim3(256), 0, s, n.w, n.b, (const float*)(c.batch ? n.save_mean : n.mean),
+                       (const float*)(c.batch ? n.save_rstd : n.var), (int)c.batch, C, out);
+  }
+}
+
+// g_bias = the column sums of g, g_weight = those of gh = g xhat, into the caller's pointers; on batch statistics, whose centring
+// reads both, into `spare` [2][C] of the workspace where the caller gave none.  Returns where they are.
+struct BnSums {
+  const float *b, *w;
+};
+BnSums bn_sums(hipStream_t s, const Call& c, const Bn& n, const float* g, const float* gh, long M, int C, float* part, float* spare) {
+  float* gb = n.g_b ? n.g_b : c.batch ? spare : nullptr;
+  float* gw = n.g_w ? n.g_w : c.batch ? spare + C : nullptr;
+  if (gb) colsum(s, g, M, C, part, gb);
+  if (gw) colsum(s, gh, M, C, part, gw);
+  return BnSums{gb, gw};
+}
+
+void stem_forward(hipStream_t s, const Call& c, const Layout& L) {
+  float* ws = (float*)c.ws;
+  const long BT = (long)c.B * c.T, M = BT * STEM_F;
+  const float *f1 = ws + L.fold1, *f2 = ws + L.fold, *pre = ws + L.pre;
+  const dim3 grid(blocks_of(M * STEM_C, 256));
+  fold_table(s, c, c.bn1, MEL, c.x, BT, L, ws + L.fold1);
+  if (c.batch)   // bn2d's statistics are those of pre: staged, then its table, then the GELU
+    hipLaunchKernelGGL(stem_pre_kernel, grid, dim3(256), 0, s, c.x, c.w, f1, BT, c.T, ws + L.pre);
+  fold_table(s, c, c.bn, STEM_C, pre, M, L, ws + L.fold);
+  if (c.batch)
+    hipLaunchKernelGGL(bn_gelu_kernel, grid, dim3(256), 0, s, pre, f2, M * STEM_C, STEM_C, c.y);
+  else
+    hipLaunchKernelGGL(stem_fwd_kernel, grid, dim3(256), 0, s, c.x, c.w, f1, f2, BT, c.T, c.y);
+}
+
+void stem_backward(hipStream_t s, const Call& c, const Layout& L) {
+  float* ws = (float*)c.ws;
+  const long BT = (long)c.B * c.T, M = BT * STEM_F;
+  const float *f1 = ws + L.fold1, *f2 = ws + L.fold, *gp = ws + L.a;
+  float* part = ws + L.part;
+  fold_table(s, c, c.bn1, MEL, nullptr, 0, L, ws + L.fold1);
+  fold_table(s, c, c.bn, STEM_C, nullptr, 0, L, ws + L.fold);
+  hipLaunchKernelGGL(stem_gpre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, c.x, c.w, f1, f2, c.gy, BT, c.T, ws + L.a,
+                     ws + L.b);
+  const BnSums g = bn_sums(s, c, c.bn, gp, ws + L.b, M, STEM_C, part, ws + L.sums);
+  if (c.batch)
+    hipLaunchKernelGGL(stem_centre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, c.x, c.w, f1, f2, ws + L.a, g.b, g.w, BT,
+                       c.T, (float)M);
+  if (c.g_w) {   // the weight gradient from gp = g_pre
+    const int chunks = dw_chunks(M);
+    hipLaunchKernelGGL(stem_dw_kernel, dim3((unsigned)chunks), dim3(STEM_C * STEM_TAPS), 0, s, c.x, f1, f2, gp, M, c.T, part);
+    hipLaunchKernelGGL(front_reduce_kernel, dim3(blocks_of(STEM_C * STEM_TAPS, 256)), dim3(256), 0, s, (const float*)part,
+                       (long)STEM_C * STEM_TAPS, chunks, c.g_w);
+  }
+  if (c.gx || c.bn1.g_w || c.bn1.g_b) {
+    // running statistics: stem_dx writes gx = gxn s itself; batch statistics: gx is the centred gxn, times s
+    hipLaunchKernelGGL(stem_dx_kernel, dim3(blocks_of(BT * MEL, 256)), dim3(256), 0, s, c.x, c.w, f1, f2, gp, BT, c.T, ws + L.c,
+                       ws + L.d, c.batch ? nullptr : c.gx);
+    const BnSums g1 = bn_sums(s, c, c.bn1, ws + L.c, ws + L.d, BT, MEL, part, ws + L.sums1);
+    if (c.batch && c.gx)
+      hipLaunchKernelGGL(bn_centre_kernel, dim3(blocks_of(BT * MEL, 256)), dim3(256), 0, s, ws + L.c, c.x, f1, g1.b, g1.w, BT * MEL, MEL,
+                         (float)BT, c.gx);
+  }
 }
 
 dim3 conv_grid(long GM, int GN, int chunks) { return dim3(blocks_of(GN, GT), blocks_of(GM, GT), (unsigned)chunks); }
 
-// 16-mixed: the argument check shared by the four entry points, and the weight image of one MODE
-const char* check_mixed(int unit, int mixed, bool linear_too) {
-  if (mixed != 0 && mixed != 1) return "mixed must be 0 or 1";
-  if (mixed && unit != BT_FRONT_CONV && !(linear_too && unit == BT_FRONT_LINEAR))
-    return "mixed = 1 belongs to BT_FRONT_CONV and (bt_front_args) BT_FRONT_LINEAR: the other units have no product worth an MFMA";
-  return nullptr;
-}
-
-void conv_pack(hipStream_t s, const float* w, int Cout, int Cin, int transposed, float* img) {
-  hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_of((long)Cout * 6 * Cin, 256)), dim3(256), 0, s, w, Cout, Cin, transposed,
-                     (_Float16*)img);
-}
-
-// the forward GEMM (p.out = pre, p.out2 = y or null); wimg: the workspace of the fp16 weight image, null = the fp32 kernel
-void conv_forward_gemm(hipStream_t s, ConvP p, float* wimg) {
-  if (wimg) {
-    conv_pack(s, p.w, p.Cout, p.Cin, 0, wimg);
+// One conv GEMM.  wimg: the workspace of the fp16 weight image (16-mixed), null = the fp32 kernel.  MODE 0 and 1 read the weight
+// from the image, which a launch ahead of the GEMM packs ([co][k] for MODE 0, transposed for MODE 1); MODE 2 has no weight operand.
+template <int MODE>
+void launch_conv(hipStream_t s, ConvP p, float* wimg, dim3 grid) {
+  if (wimg && MODE != 2) {
+    hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_of((long)p.Cout * 6 * p.Cin, 256)), dim3(256), 0, s, p.w, p.Cout, p.Cin, MODE,
+                       (_Float16*)wimg);
     p.wh = (const _Float16*)wimg;
-    hipLaunchKernelGGL(conv_gemm_mixed_kernel<0>, conv_grid(p.M, p.Cout, 1), dim3(256), 0, s, p);
-  } else {
-    hipLaunchKernelGGL(conv_gemm_kernel<0>, conv_grid(p.M, p.Cout, 1), dim3(256), 0, s, p);
+  }
+  hipLaunchKernelGGL(wimg ? conv_gemm_mixed_kernel<MODE> : conv_gemm_kernel<MODE>, grid, dim3(256), 0, s, p);
+}
+
+void conv_forward(hipStream_t s, const Call& c, const Layout& L) {
+  float* ws = (float*)c.ws;
+  const int Cout = 2 * c.C, Fo = c.F / 2;
+  const long M = (long)c.B * c.T * Fo;
+  const float* f2 = ws + L.fold;
+  // batch statistics: the GEMM writes pre alone (no GELU output), the table comes from pre's moments, then the GELU
+  if (!c.batch) fold_table(s, c, c.bn, Cout, nullptr, 0, L, ws + L.fold);
+  launch_conv<0>(s, ConvP{c.x, c.w, nullptr, f2, c.save_pre, c.batch ? nullptr : c.y, c.T, Fo, c.C, Cout, M},
+                 c.mixed ? ws + L.wimg : nullptr, conv_grid(M, Cout, 1));
+  if (c.batch) {
+    fold_table(s, c, c.bn, Cout, c.save_pre, M, L, ws + L.fold);
+    hipLaunchKernelGGL(bn_gelu_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, (const float*)c.save_pre, f2, M * Cout, Cout, c.y);
   }
 }
 
-// the conv unit's backward-data and backward-weight GEMMs on p.g = g_pre (they multiply by s = p.fold while staging)
-void conv_backward_gemms(hipStream_t s, ConvP p, float* part, float* gx, float* g_w, float* wimg) {
-  if (gx) {
-    p.out = gx;
-    if (wimg) {
-      conv_pack(s, p.w, p.Cout, p.Cin, 1, wimg);
-      p.wh = (const _Float16*)wimg;
-      hipLaunchKernelGGL(conv_gemm_mixed_kernel<1>, conv_grid(p.M, 2 * p.Cin, 1), dim3(256), 0, s, p);
-    } else {
-      hipLaunchKernelGGL(conv_gemm_kernel<1>, conv_grid(p.M, 2 * p.Cin, 1), dim3(256), 0, s, p);
-    }
+void conv_backward(hipStream_t s, const Call& c, const Layout& L) {
+  float* ws = (float*)c.ws;
+  const int Cout = 2 * c.C, Fo = c.F / 2;
+  const long M = (long)c.B * c.T * Fo;
+  const float *f2 = ws + L.fold, *pre = c.save_pre;
+  float *part = ws + L.part, *wimg = c.mixed ? ws + L.wimg : nullptr;
+  fold_table(s, c, c.bn, Cout, nullptr, 0, L, ws + L.fold);
+  hipLaunchKernelGGL(conv_gpre_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, pre, c.gy, f2, M * Cout, Cout, ws + L.a, ws + L.b);
+  const BnSums g = bn_sums(s, c, c.bn, ws + L.a, ws + L.b, M, Cout, part, ws + L.sums);
+  if (c.batch)
+    hipLaunchKernelGGL(bn_centre_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, ws + L.a, pre, f2, g.b, g.w, M * Cout, Cout,
+                       (float)M, (float*)nullptr);
+  // backward-data and backward-weight on p.g = g_pre (they multiply by s = p.fold while staging)
+  ConvP p{c.x, c.w, ws + L.a, f2, nullptr, nullptr, c.T, Fo, c.C, Cout, M};
+  if (c.gx) {
+    p.out = c.gx;
+    launch_conv<1>(s, p, wimg, conv_grid(M, 2 * c.C, 1));
   }
-  if (g_w) {
-    const int chunks = dw_chunks(p.M);
+  if (c.g_w) {
+    const int chunks = dw_chunks(M);
     p.out = part;
-    if (wimg)
-      hipLaunchKernelGGL(conv_gemm_mixed_kernel<2>, conv_grid(p.Cout, 6 * p.Cin, chunks), dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL(conv_gemm_kernel<2>, conv_grid(p.Cout, 6 * p.Cin, chunks), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3(blocks_of((long)p.Cout * 6 * p.Cin, 256)), dim3(256), 0, s, (const float*)part,
-                       p.Cout, p.Cin, chunks, g_w);
+    launch_conv<2>(s, p, wimg, conv_grid(Cout, 6 * c.C, chunks));
+    hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3(blocks_of((long)Cout * 6 * c.C, 256)), dim3(256), 0, s, (const float*)part, Cout, c.C,
+                       chunks, c.g_w);
   }
 }
 
-// the stem's weight gradient from gp = g_pre
-void stem_dw(hipStream_t s, const float* x, const float* f1, const float* f2, const float* gp, long M, int T, float* part, float* g_w) {
-  const int chunks = dw_chunks(M);
-  hipLaunchKernelGGL(stem_dw_kernel, dim3((unsigned)chunks), dim3(STEM_C * STEM_TAPS), 0, s, x, f1, f2, gp, M, T, part);
-  hipLaunchKernelGGL(front_reduce_kernel, dim3(blocks_of(STEM_C * STEM_TAPS, 256)), dim3(256), 0, s, (const float*)part,
-                     (long)STEM_C * STEM_TAPS, chunks, g_w);
+int linear_forward(void* stream, const Call& c, const Layout& L) {
+  float* ws = (float*)c.ws;
+  const long BT = (long)c.B * c.T;
+  swap((hipStream_t)stream, c.x, BT, c.F, c.C, 1, ws + L.a);   // (f c) -> (c f)
+  return bt_train_matmul(stream, c.mixed, 0, ws + L.a, c.w, (int)BT, c.dim, c.F * c.C, c.y, c.b, nullptr, 0, nullptr, nullptr, 0, 0,
+                         nullptr, 0);
 }
 
-// ---- batch statistics: workspace and argument checks ---------------------------------------------------------------------------
-struct BnLayout {
-  size_t fold, fold1, pre, a, b, c, d, sums, sums1, part, wimg, total;
-};
-
-// a chunk's moments are two doubles per column: four floats of the workspace
-BnLayout bn_layout(int unit, int backward, long BT, int F, int C, bool mixed = false) {
-  BnLayout L{};
-  size_t at = 0;
-  auto take = [&](size_t n) { const size_t o = at; at += up64(n); return o; };
-  if (unit == BT_FRONT_STEM) {
-    const size_t M = (size_t)BT * STEM_F;
-    L.fold1 = take(4 * MEL);
-    L.fold = take(4 * STEM_C);
-    if (backward) {
-      L.a = take(M * STEM_C);          // g_pre
-      L.b = take(M * STEM_C);          // g_pre xhat
-      L.c = take((size_t)BT * MEL);    // gradient of the bn1d output
-      L.d = take((size_t)BT * MEL);    // the same times xhat
-      L.sums = take(2 * STEM_C);       // g_bias, g_weight of bn2d when the caller wants none
-      L.sums1 = take(2 * MEL);         // the same of bn1d
-      L.part = take(std::max({(size_t)dw_chunks(M) * STEM_C * STEM_TAPS, (size_t)cs_chunks(M) * STEM_C, (size_t)cs_chunks(BT) * MEL}));
-    } else {
-      L.pre = take(M * STEM_C);
-      L.part = take(4 * std::max((size_t)cs_chunks(M) * STEM_C, (size_t)cs_chunks(BT) * MEL));
-    }
-  } else {
-    const size_t M = (size_t)BT * (F / 2), Cout = 2 * (size_t)C;
-    L.fold = take(4 * Cout);
-    if (backward) {
-      L.a = take(M * Cout);
-      L.b = take(M * Cout);
-      L.sums = take(2 * Cout);
-      L.part = take(std::max((size_t)dw_chunks(M) * Cout * 6 * C, (size_t)cs_chunks(M) * Cout));
-    } else {
-      L.part = take(4 * (size_t)cs_chunks(M) * Cout);
-    }
-    if (mixed) L.wimg = take(Cout * 3 * C);   // the fp16 weight image, as layout()
+int linear_backward(void* stream, const Call& c, const Layout& L) {
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)c.ws;
+  const long BT = (long)c.B * c.T;
+  const int K = c.F * c.C;
+  if (c.g_b) colsum(s, c.gy, BT, c.dim, ws + L.part, c.g_b);
+  if (c.g_w) {
+    swap(s, c.x, BT, c.F, c.C, 1, ws + L.a);
+    if (int rc = bt_train_matmul(stream, c.mixed, 2, c.gy, ws + L.a, c.dim, K, (int)BT, c.g_w, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
+                                 ws + L.part, (L.total - L.part) * sizeof(float)))
+      return rc;
   }
-  L.total = at;
-  return L;
+  if (c.gx) {
+    if (int rc = bt_train_matmul(stream, c.mixed, 1, c.gy, c.w, (int)BT, K, c.dim, ws + L.b, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
+                                 nullptr, 0))
+      return rc;
+    swap(s, ws + L.b, BT, c.C, c.F, 1, c.gx);   // (c f) -> (f c)
+  }
+  return BT_OK;
 }
 
-const char* bn_check_shape(int unit, int B, int T, int F, int C) {
-  if (unit != BT_FRONT_STEM && unit != BT_FRONT_CONV) return "batch statistics: unit must be BT_FRONT_STEM or BT_FRONT_CONV";
-  if (const char* e = check_shape(unit, B, T, F, C, 0)) return e;
-  if ((long)B * T * (unit == BT_FRONT_STEM ? 1 : F / 2) < 2) return "Expected more than 1 value per channel when training";
-  return nullptr;
+int run(const char* fn, void* stream, int unit, const Call& c) {
+  Layout L;
+  if (int rc = prepare(fn, unit, c, L)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  switch (unit) {
+    case BT_FRONT_STEM:
+      c.backward ? stem_backward(s, c, L) : stem_forward(s, c, L);
+      break;
+    case BT_FRONT_CONV:
+      c.backward ? conv_backward(s, c, L) : conv_forward(s, c, L);
+      break;
+    case BT_FRONT_LINEAR:
+      if (int rc = c.backward ? linear_backward(stream, c, L) : linear_forward(stream, c, L)) return rc;
+      break;
+    default:   // y = swap(x) over (T, F): gx = the swap over (F, T) of gy
+      c.backward ? swap(s, c.gy, c.B, c.F, c.T, c.C, c.gx) : swap(s, c.x, c.B, c.T, c.F, c.C, c.y);
+      break;
+  }
+  return finish(fn);
+}
+
+size_t workspace_bytes(int unit, int backward, bool batch, bool mixed, int B, int T, int F, int C, int dim) {
+  if (batch ? bn_check_shape(unit, B, T, F, C) : check_shape(unit, B, T, F, C, dim)) return 0;
+  if (mixed && check_mixed(unit, 1, !batch)) return 0;
+  return layout(unit, backward != 0, batch, mixed, (long)B * T, F, C, dim).total * sizeof(float);
 }
 
 }  // namespace
@@ -660,139 +862,6 @@ void bt_front_struct_sizes(int32_t* out) {
   out[6] = (int32_t)offsetof(bt_front_args, ws_bytes);
 }
 
-size_t bt_front_workspace_bytes(int unit, int backward, int B, int T, int F, int C, int dim) {
-  if (check_shape(unit, B, T, F, C, dim)) return 0;
-  return layout(unit, backward != 0, (long)B * T, F, C, dim).total * sizeof(float);
-}
-
-size_t bt_front_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C, int dim) {
-  if (check_shape(unit, B, T, F, C, dim) || check_mixed(unit, 1, true)) return 0;
-  return layout(unit, backward != 0, (long)B * T, F, C, dim, true).total * sizeof(float);
-}
-
-int bt_front_forward(void* stream, int unit, const bt_front_args* ap) {
-  const char* fn = "bt_front_forward";
-  if (!ap) return fail(fn, "null argument");
-  const bt_front_args& a = *ap;
-  if (const char* e = check_shape(unit, a.B, a.T, a.F, a.C, a.dim)) return fail(fn, e);
-  if (const char* e = check_mixed(unit, a.mixed, true)) return fail(fn, e);
-  const long BT = (long)a.B * a.T;
-  const Layout L = layout(unit, 0, BT, a.F, a.C, a.dim, a.mixed != 0);
-  if (!a.x || !a.y || !a.ws) return fail(fn, "null x, y or workspace");
-  if (a.mixed && (uintptr_t)a.ws % 16) return fail(fn, "mixed = 1: the workspace must be 16-byte aligned");
-  if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
-  hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)a.ws;
-  switch (unit) {
-    case BT_FRONT_STEM: {
-      if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.bn1_w || !a.bn1_b || !a.bn1_mean || !a.bn1_var)
-        return fail(fn, "null parameter");
-      fold(s, a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, MEL, ws + L.fold1);
-      fold(s, a.bn_w, a.bn_b, a.bn_mean, a.bn_var, STEM_C, ws + L.fold);
-      hipLaunchKernelGGL(stem_fwd_kernel, dim3(blocks_of(BT * STEM_F * STEM_C, 256)), dim3(256), 0, s, a.x, a.w,
-                         (const float*)(ws + L.fold1), (const float*)(ws + L.fold), BT, a.T, a.y);
-      break;
-    }
-    case BT_FRONT_CONV: {
-      if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.save_pre) return fail(fn, "null parameter or saved-tensor pointer");
-      const int Cout = 2 * a.C;
-      fold(s, a.bn_w, a.bn_b, a.bn_mean, a.bn_var, Cout, ws + L.fold);
-      conv_forward_gemm(s, ConvP{a.x, a.w, nullptr, ws + L.fold, a.save_pre, a.y, a.T, a.F / 2, a.C, Cout, BT * (a.F / 2)},
-                        a.mixed ? ws + L.wimg : nullptr);
-      break;
-    }
-    case BT_FRONT_LINEAR: {
-      if (!a.w || !a.b) return fail(fn, "null parameter");
-      const int K = a.F * a.C;
-      swap(s, a.x, BT, a.F, a.C, 1, ws + L.a);   // (f c) -> (c f)
-      if (int rc = bt_train_matmul(stream, a.mixed, 0, ws + L.a, a.w, (int)BT, a.dim, K, a.y, a.b, nullptr, 0, nullptr, nullptr, 0, 0,
-                                   nullptr, 0))
-        return rc;
-      break;
-    }
-    default:
-      swap(s, a.x, a.B, a.T, a.F, a.C, a.y);
-      break;
-  }
-  return finish(fn);
-}
-
-int bt_front_backward(void* stream, int unit, const bt_front_args* ap) {
-  const char* fn = "bt_front_backward";
-  if (!ap) return fail(fn, "null argument");
-  const bt_front_args& a = *ap;
-  if (const char* e = check_shape(unit, a.B, a.T, a.F, a.C, a.dim)) return fail(fn, e);
-  if (const char* e = check_mixed(unit, a.mixed, true)) return fail(fn, e);
-  const long BT = (long)a.B * a.T;
-  const Layout L = layout(unit, 1, BT, a.F, a.C, a.dim, a.mixed != 0);
-  if (!a.gy || !a.ws) return fail(fn, "null upstream gradient or workspace");
-  if (unit != BT_FRONT_SWAP && !a.x) return fail(fn, "null x");
-  if (a.mixed && (uintptr_t)a.ws % 16) return fail(fn, "mixed = 1: the workspace must be 16-byte aligned");
-  if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
-  hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)a.ws;
-  switch (unit) {
-    case BT_FRONT_STEM: {
-      if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.bn1_w || !a.bn1_b || !a.bn1_mean || !a.bn1_var)
-        return fail(fn, "null parameter");
-      const long M = BT * STEM_F;
-      const float* f1 = ws + L.fold1;
-      const float* f2 = ws + L.fold;
-      fold(s, a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, MEL, ws + L.fold1);
-      fold(s, a.bn_w, a.bn_b, a.bn_mean, a.bn_var, STEM_C, ws + L.fold);
-      hipLaunchKernelGGL(stem_gpre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, a.gy, BT, a.T,
-                         ws + L.a, ws + L.b);
-      if (a.g_bn_b) colsum(s, ws + L.a, M, STEM_C, ws + L.part, a.g_bn_b);
-      if (a.g_bn_w) colsum(s, ws + L.b, M, STEM_C, ws + L.part, a.g_bn_w);
-      if (a.g_w) stem_dw(s, a.x, f1, f2, ws + L.a, M, a.T, ws + L.part, a.g_w);
-      if (a.gx || a.g_bn1_w || a.g_bn1_b) {
-        hipLaunchKernelGGL(stem_dx_kernel, dim3(blocks_of(BT * MEL, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, (const float*)(ws + L.a),
-                           BT, a.T, ws + L.c, ws + L.d, a.gx);
-        if (a.g_bn1_b) colsum(s, ws + L.c, BT, MEL, ws + L.part, a.g_bn1_b);
-        if (a.g_bn1_w) colsum(s, ws + L.d, BT, MEL, ws + L.part, a.g_bn1_w);
-      }
-      break;
-    }
-    case BT_FRONT_CONV: {
-      if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.save_pre) return fail(fn, "null parameter or saved-tensor pointer");
-      const int Cout = 2 * a.C, Fo = a.F / 2;
-      const long M = BT * Fo;
-      fold(s, a.bn_w, a.bn_b, a.bn_mean, a.bn_var, Cout, ws + L.fold);
-      hipLaunchKernelGGL(conv_gpre_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, (const float*)a.save_pre, a.gy,
-                         (const float*)(ws + L.fold), M * Cout, Cout, ws + L.a, ws + L.b);
-      if (a.g_bn_b) colsum(s, ws + L.a, M, Cout, ws + L.part, a.g_bn_b);
-      if (a.g_bn_w) colsum(s, ws + L.b, M, Cout, ws + L.part, a.g_bn_w);
-      conv_backward_gemms(s, ConvP{a.x, a.w, ws + L.a, ws + L.fold, nullptr, nullptr, a.T, Fo, a.C, Cout, M}, ws + L.part, a.gx, a.g_w,
-                          a.mixed ? ws + L.wimg : nullptr);
-      break;
-    }
-    case BT_FRONT_LINEAR: {
-      if (!a.w) return fail(fn, "null parameter");
-      const int K = a.F * a.C;
-      if (a.g_b) colsum(s, a.gy, BT, a.dim, ws + L.part, a.g_b);
-      if (a.g_w) {
-        swap(s, a.x, BT, a.F, a.C, 1, ws + L.a);
-        if (int rc = bt_train_matmul(stream, a.mixed, 2, a.gy, ws + L.a, a.dim, K, (int)BT, a.g_w, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
-                                     ws + L.part, (L.total - L.part) * sizeof(float)))
-          return rc;
-      }
-      if (a.gx) {
-        if (int rc = bt_train_matmul(stream, a.mixed, 1, a.gy, a.w, (int)BT, K, a.dim, ws + L.b, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
-                                     nullptr, 0))
-          return rc;
-        swap(s, ws + L.b, BT, a.C, a.F, 1, a.gx);   // (c f) -> (f c)
-      }
-      break;
-    }
-    default:   // y = swap(x) over (T, F): gx = the swap over (F, T) of gy
-      if (!a.gx) return fail(fn, "null gx");
-      swap(s, a.gy, a.B, a.F, a.T, a.C, a.gx);
-      break;
-  }
-  return finish(fn);
-}
-
-// ---- batch-statistics BatchNorm: the same kernels, the statistics from the call's own batch -------------
 void bt_front_bn_struct_sizes(int32_t* out) {
   out[0] = (int32_t)sizeof(bt_front_bn_args);
   out[1] = (int32_t)offsetof(bt_front_bn_args, w);
@@ -805,117 +874,35 @@ void bt_front_bn_struct_sizes(int32_t* out) {
   out[8] = (int32_t)offsetof(bt_front_bn_args, ws_bytes);
 }
 
+size_t bt_front_workspace_bytes(int unit, int backward, int B, int T, int F, int C, int dim) {
+  return workspace_bytes(unit, backward, false, false, B, T, F, C, dim);
+}
+size_t bt_front_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C, int dim) {
+  return workspace_bytes(unit, backward, false, true, B, T, F, C, dim);
+}
 size_t bt_front_bn_workspace_bytes(int unit, int backward, int B, int T, int F, int C) {
-  if (bn_check_shape(unit, B, T, F, C)) return 0;
-  return bn_layout(unit, backward != 0, (long)B * T, F, C).total * sizeof(float);
+  return workspace_bytes(unit, backward, true, false, B, T, F, C, 0);
 }
-
 size_t bt_front_bn_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C) {
-  if (bn_check_shape(unit, B, T, F, C) || check_mixed(unit, 1, false)) return 0;
-  return bn_layout(unit, backward != 0, (long)B * T, F, C, true).total * sizeof(float);
+  return workspace_bytes(unit, backward, true, true, B, T, F, C, 0);
 }
 
-int bt_front_bn_forward(void* stream, int unit, const bt_front_bn_args* ap) {
+// running statistics and batch statistics (section 18): adapter, shared preamble, dispatch
+int bt_front_forward(void* stream, int unit, const bt_front_args* a) {
+  const char* fn = "bt_front_forward";
+  return a ? run(fn, stream, unit, describe(*a, false)) : fail(fn, "null argument");
+}
+int bt_front_backward(void* stream, int unit, const bt_front_args* a) {
+  const char* fn = "bt_front_backward";
+  return a ? run(fn, stream, unit, describe(*a, true)) : fail(fn, "null argument");
+}
+int bt_front_bn_forward(void* stream, int unit, const bt_front_bn_args* a) {
   const char* fn = "bt_front_bn_forward";
-  if (!ap) return fail(fn, "null argument");
-  const bt_front_bn_args& a = *ap;
-  if (const char* e = bn_check_shape(unit, a.B, a.T, a.F, a.C)) return fail(fn, e);
-  if (const char* e = check_mixed(unit, a.mixed, false)) return fail(fn, e);
-  const long BT = (long)a.B * a.T;
-  const BnLayout L = bn_layout(unit, 0, BT, a.F, a.C, a.mixed != 0);
-  if (!a.x || !a.y || !a.ws) return fail(fn, "null x, y or workspace");
-  if (!a.w || !a.bn_w || !a.bn_b || !a.bn_mean || !a.bn_var || !a.save_mean || !a.save_rstd)
-    return fail(fn, "null parameter, running buffer or saved-statistics pointer");
-  if ((uintptr_t)a.ws % 8) return fail(fn, "the workspace must be 8-byte aligned");
-  if (a.mixed && (uintptr_t)a.ws % 16) return fail(fn, "mixed = 1: the workspace must be 16-byte aligned");
-  if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
-  hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)a.ws;
-  double* part = (double*)(ws + L.part);
-  if (unit == BT_FRONT_STEM) {
-    if (!a.bn1_w || !a.bn1_b || !a.bn1_mean || !a.bn1_var || !a.save1_mean || !a.save1_rstd)
-      return fail(fn, "null bn1d parameter, running buffer or saved-statistics pointer");
-    const long M = BT * STEM_F;
-    batch_stats(s, a.x, BT, MEL, part, a.bn1_w, a.bn1_b, ws + L.fold1, a.save1_mean, a.save1_rstd, a.bn1_mean, a.bn1_var, a.bn1_tracked);
-    hipLaunchKernelGGL(stem_pre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, a.x, a.w, (const float*)(ws + L.fold1), BT,
-                       a.T, ws + L.pre);
-    batch_stats(s, ws + L.pre, M, STEM_C, part, a.bn_w, a.bn_b, ws + L.fold, a.save_mean, a.save_rstd, a.bn_mean, a.bn_var, a.bn_tracked);
-    hipLaunchKernelGGL(bn_gelu_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, (const float*)(ws + L.pre),
-                       (const float*)(ws + L.fold), M * STEM_C, STEM_C, a.y);
-  } else {
-    if (!a.save_pre) return fail(fn, "null saved-tensor pointer");
-    const int Cout = 2 * a.C;
-    const long M = BT * (a.F / 2);
-    // (pre alone: no fold, no GELU output)
-    conv_forward_gemm(s, ConvP{a.x, a.w, nullptr, nullptr, a.save_pre, nullptr, a.T, a.F / 2, a.C, Cout, M}, a.mixed ? ws + L.wimg : nullptr);
-    batch_stats(s, a.save_pre, M, Cout, part, a.bn_w, a.bn_b, ws + L.fold, a.save_mean, a.save_rstd, a.bn_mean, a.bn_var, a.bn_tracked);
-    hipLaunchKernelGGL(bn_gelu_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, (const float*)a.save_pre,
-                       (const float*)(ws + L.fold), M * Cout, Cout, a.y);
-  }
-  return finish(fn);
+  return a ? run(fn, stream, unit, describe(*a, false)) : fail(fn, "null argument");
 }
-
-int bt_front_bn_backward(void* stream, int unit, const bt_front_bn_args* ap) {
+int bt_front_bn_backward(void* stream, int unit, const bt_front_bn_args* a) {
   const char* fn = "bt_front_bn_backward";
-  if (!ap) return fail(fn, "null argument");
-  const bt_front_bn_args& a = *ap;
-  if (const char* e = bn_check_shape(unit, a.B, a.T, a.F, a.C)) return fail(fn, e);
-  if (const char* e = check_mixed(unit, a.mixed, false)) return fail(fn, e);
-  const long BT = (long)a.B * a.T;
-  const BnLayout L = bn_layout(unit, 1, BT, a.F, a.C, a.mixed != 0);
-  if (!a.x || !a.gy || !a.ws) return fail(fn, "null x, upstream gradient or workspace");
-  if (a.mixed && (uintptr_t)a.ws % 16) return fail(fn, "mixed = 1: the workspace must be 16-byte aligned");
-  if (!a.w || !a.bn_w || !a.bn_b || !a.save_mean || !a.save_rstd) return fail(fn, "null parameter or saved-statistics pointer");
-  if (a.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
-  hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)a.ws;
-  const float* f2 = ws + L.fold;
-  if (unit == BT_FRONT_STEM) {
-    if (!a.bn1_w || !a.bn1_b || !a.save1_mean || !a.save1_rstd) return fail(fn, "null bn1d parameter or saved-statistics pointer");
-    const long M = BT * STEM_F;
-    const float* f1 = ws + L.fold1;
-    float* gb = a.g_bn_b ? a.g_bn_b : ws + L.sums;
-    float* gw = a.g_bn_w ? a.g_bn_w : ws + L.sums + STEM_C;
-    hipLaunchKernelGGL(bn_fold_saved_kernel, dim3(1), dim3(256), 0, s, a.bn1_w, a.bn1_b, (const float*)a.save1_mean,
-                       (const float*)a.save1_rstd, MEL, ws + L.fold1);
-    hipLaunchKernelGGL(bn_fold_saved_kernel, dim3(1), dim3(256), 0, s, a.bn_w, a.bn_b, (const float*)a.save_mean,
-                       (const float*)a.save_rstd, STEM_C, ws + L.fold);
-    hipLaunchKernelGGL(stem_gpre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, a.gy, BT, a.T, ws + L.a,
-                       ws + L.b);
-    colsum(s, ws + L.a, M, STEM_C, ws + L.part, gb);
-    colsum(s, ws + L.b, M, STEM_C, ws + L.part, gw);
-    hipLaunchKernelGGL(stem_centre_kernel, dim3(blocks_of(M * STEM_C, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, ws + L.a,
-                       (const float*)gb, (const float*)gw, BT, a.T, (float)M);
-    if (a.g_w) stem_dw(s, a.x, f1, f2, ws + L.a, M, a.T, ws + L.part, a.g_w);
-    if (a.gx || a.g_bn1_w || a.g_bn1_b) {
-      float* gb1 = a.g_bn1_b ? a.g_bn1_b : ws + L.sums1;
-      float* gw1 = a.g_bn1_w ? a.g_bn1_w : ws + L.sums1 + MEL;
-      hipLaunchKernelGGL(stem_dx_kernel, dim3(blocks_of(BT * MEL, 256)), dim3(256), 0, s, a.x, a.w, f1, f2, (const float*)(ws + L.a), BT,
-                         a.T, ws + L.c, ws + L.d, (float*)nullptr);
-      colsum(s, ws + L.c, BT, MEL, ws + L.part, gb1);
-      colsum(s, ws + L.d, BT, MEL, ws + L.part, gw1);
-      if (a.gx)
-        hipLaunchKernelGGL(bn_centre_kernel, dim3(blocks_of(BT * MEL, 256)), dim3(256), 0, s, ws + L.c, a.x, f1, (const float*)gb1,
-                           (const float*)gw1, BT * MEL, MEL, (float)BT, a.gx);
-    }
-  } else {
-    if (!a.save_pre) return fail(fn, "null saved-tensor pointer");
-    const int Cout = 2 * a.C, Fo = a.F / 2;
-    const long M = BT * Fo;
-    float* gb = a.g_bn_b ? a.g_bn_b : ws + L.sums;
-    float* gw = a.g_bn_w ? a.g_bn_w : ws + L.sums + Cout;
-    hipLaunchKernelGGL(bn_fold_saved_kernel, dim3(blocks_of(Cout, 256)), dim3(256), 0, s, a.bn_w, a.bn_b, (const float*)a.save_mean,
-                       (const float*)a.save_rstd, Cout, ws + L.fold);
-    hipLaunchKernelGGL(conv_gpre_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, (const float*)a.save_pre, a.gy, f2, M * Cout,
-                       Cout, ws + L.a, ws + L.b);
-    colsum(s, ws + L.a, M, Cout, ws + L.part, gb);
-    colsum(s, ws + L.b, M, Cout, ws + L.part, gw);
-    hipLaunchKernelGGL(bn_centre_kernel, dim3(blocks_of(M * Cout, 256)), dim3(256), 0, s, ws + L.a, (const float*)a.save_pre, f2,
-                       (const float*)gb, (const float*)gw, M * Cout, Cout, (float)M, (float*)nullptr);
-    conv_backward_gemms(s, ConvP{a.x, a.w, ws + L.a, f2, nullptr, nullptr, a.T, Fo, a.C, Cout, M}, ws + L.part, a.gx, a.g_w,
-                        a.mixed ? ws + L.wimg : nullptr);
-  }
-  return finish(fn);
+  return a ? run(fn, stream, unit, describe(*a, true)) : fail(fn, "null argument");
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // The 16-mixed conv unit of the differentiable frontend (DESIGN.md section 19), included by train_front.hip inside its
-// namespace, behind ConvP and the fp32 conv_gemm_kernel whose three products and epilogues these kernels repeat.
+// namespace, behind ConvP, ConvTile<MODE> and conv_store<MODE>: the three products of the fp32 conv_gemm_kernel in its frame and
+// with its epilogue; the staging and the MFMA loop are this file's own.
 // THE CONTRACT is section 16's: both operands of pre = A W^T, g_x = G W and g_W = G^T A are rounded to IEEE fp16 (to nearest
 // even, beyond its range: inf) as they are staged, G = g_pre s being multiplied in fp32 first, and the products accumulate in
 // fp32 on v_mfma_f32_32x32x16_f16.  Nothing clamps.  Everything around the products is the fp32 code of train_front.hip.
@@ -54,22 +55,16 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, int Cout
   img[i] = (_Float16)w[((long)co * Cin + ci) * 6 + df * 3 + dt];
 }
 
-// conv_gemm_kernel<MODE> with fp16 operands: the same grid, the same epilogue.  p.wh: the packed weight (MODE 0 and 1).
+// conv_gemm_kernel<MODE> with fp16 operands: the same grid, tile and epilogue.  p.wh: the packed weight (MODE 0 and 1).
 template <int MODE>
 __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
   __shared__ __attribute__((aligned(16))) _Float16 As[GT][MLD];
   __shared__ __attribute__((aligned(16))) _Float16 Bs[GT][MLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 5, lr = lane & 31, wm = wave >> 1, wn = wave & 1;
-  const int C2 = 2 * p.Cin;
-  const long GM = MODE == 2 ? (long)p.Cout : p.M;
-  const int GN = MODE == 0 ? p.Cout : MODE == 1 ? C2 : 3 * C2;
-  const long kb = MODE == 2 ? (long)blockIdx.z * DW_ROWS : 0;
-  const long ke = MODE == 0 ? 3L * C2 : MODE == 1 ? 3L * p.Cout : std::min<long>(p.M, kb + DW_ROWS);
-  const long m0 = (long)blockIdx.y * GT;
-  const int n0 = blockIdx.x * GT;
+  const ConvTile<MODE> tile(p);
   const bool vx = aligned16(p.x), vg = aligned16(p.g);
-  const int run = MODE == 1 ? p.Cout : C2;   // floats per frame of a row of the staged activation
+  const int run = MODE == 1 ? p.Cout : tile.C2;   // floats per frame of a row of the staged activation
   const int KW = 3 * run;                    // MODE 0 / 1: halves per row of the weight image
 
   // MODE 0 / 1: this thread stages four k of rows (tid >> 3) and 32 + (tid >> 3) of A and eight k of row tid >> 2 of the image
@@ -78,11 +73,11 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
   if (MODE != 2) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const long gm = m0 + i * 32 + (tid >> 3);
-      if (gm < GM) row_t[i] = (int)((gm / p.Fo) % p.T);
+      const long gm = tile.m0 + i * 32 + (tid >> 3);
+      if (gm < tile.GM) row_t[i] = (int)((gm / p.Fo) % p.T);
     }
   }
-  const int dt2 = n0 / C2, j2 = n0 - dt2 * C2;   // MODE 2: the run and the first column of this tile of the implicit A
+  const int dt2 = tile.n0 / tile.C2, j2 = tile.n0 - dt2 * tile.C2;   // MODE 2: the run and the first column of this tile of the implicit A
 
   h16x4 ra[2], rb[2];
   h16x8 rw;
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
       const int kk = (tid & 7) * 4;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const long gm = m0 + i * 32 + (tid >> 3);
+        const long gm = tile.m0 + i * 32 + (tid >> 3);
         const int t = row_t[i] + sh;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (row_t[i] >= 0 && t >= 0 && t < p.T) {
@@ -105,23 +100,23 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
         }
         ra[i] = to_h4(v);
       }
-      const int gn = n0 + (tid >> 2);
+      const int gn = tile.n0 + (tid >> 2);
       rw = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (gn < GN) rw = *reinterpret_cast<const h16x8*>(p.wh + (long)gn * KW + k0 + (tid & 3) * 8);
+      if (gn < tile.GN) rw = *reinterpret_cast<const h16x8*>(p.wh + (long)gn * KW + k0 + (tid & 3) * 8);
     } else {
       const int c4 = (tid & 15) * 4;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const long gk = k0 + i * 16 + (tid >> 4);
         f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-        if (gk < ke) {
-          if (m0 + c4 < GM) {
-            a = load4(p.g + gk * p.Cout + m0 + c4, vg);
+        if (gk < tile.ke) {
+          if (tile.m0 + c4 < tile.GM) {
+            a = load4(p.g + gk * p.Cout + tile.m0 + c4, vg);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) a[c] *= p.fold[m0 + c4 + c];
+            for (int c = 0; c < 4; ++c) a[c] *= p.fold[tile.m0 + c4 + c];
           }
           const int t = (int)((gk / p.Fo) % p.T) + dt2 - 1;
-          if (n0 + c4 < GN && t >= 0 && t < p.T) b = load4(p.x + (gk + (long)(dt2 - 1) * p.Fo) * C2 + j2 + c4, vx);
+          if (tile.n0 + c4 < tile.GN && t >= 0 && t < p.T) b = load4(p.x + (gk + (long)(dt2 - 1) * p.Fo) * tile.C2 + j2 + c4, vx);
         }
         ra[i] = to_h4(a);
         rb[i] = to_h4(b);
@@ -150,30 +145,16 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-  fetch(kb);
-  for (long k0 = kb; k0 < ke; k0 += MK) {
+  fetch(tile.kb);
+  for (long k0 = tile.kb; k0 < tile.ke; k0 += MK) {
     commit();
     __syncthreads();
-    if (k0 + MK < ke) fetch(k0 + MK);
+    if (k0 + MK < tile.ke) fetch(k0 + MK);
 #pragma unroll
     for (int s = 0; s < MK / 16; ++s)
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h16x8*>(&As[wm * 32 + lr][16 * s + 8 * g]),
                                                    *reinterpret_cast<const h16x8*>(&Bs[wn * 32 + lr][16 * s + 8 * g]), acc, 0, 0, 0);
     __syncthreads();
   }
-  const int col = n0 + wn * 32 + lr;
-  if (col >= GN) return;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const long row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-    if (row >= GM) continue;
-    if (MODE == 0) {
-      p.out[row * p.Cout + col] = acc[r];
-      if (p.out2) p.out2[row * p.Cout + col] = gelu_f(p.fold[col] * acc[r] + p.fold[p.Cout + col]);   // (null: batch statistics)
-    } else if (MODE == 1) {
-      p.out[row * C2 + col] = acc[r];
-    } else {
-      p.out[((long)blockIdx.z * p.Cout + row) * (3 * C2) + col] = acc[r];
-    }
-  }
+  conv_store<MODE>(p, tile, acc, wm, wn, lr, g);
 }

@@ -286,101 +286,6 @@ def check_front_limits(B: int, T: int) -> None:
                          f"{_lib.FRONT_MAX_ROWS} rows of 32 frequency tokens), got batch {B} x {T} frames: split the batch")
 
 
-def _front_args(B, T, F, Cc, dim=0, mixed=False) -> _lib.FrontArgs:
-    a = _lib.FrontArgs()
-    a.B, a.T, a.F, a.C, a.dim, a.mixed = int(B), int(T), int(F), int(Cc), int(dim), int(bool(mixed))
-    return a
-
-
-def _front_call(backward: bool, unit: int, a: _lib.FrontArgs, device) -> None:
-    query = _lib.lib().bt_front_workspace_bytes_mixed if a.mixed else _lib.lib().bt_front_workspace_bytes
-    need = query(unit, int(backward), a.B, a.T, a.F, a.C, a.dim)
-    if need == 0:
-        check_front_limits(a.B, a.T)
-        raise ValueError(f"the differentiable frontend does not support batch {a.B}, {a.T} frames, {a.F} frequency bins, "
-                         f"{a.C} channels, width {a.dim} (unit {unit})")
-    ws = torch.empty(need, dtype=torch.uint8, device=device)
-    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
-    fn = _lib.lib().bt_front_backward if backward else _lib.lib().bt_front_forward
-    with torch.cuda.device(device):
-        _lib.check(fn(_lib.stream_ptr(device), unit, C.byref(a)))
-
-
-class StemFn(torch.autograd.Function):
-    """make_stem (beat_tracker.py:108-126): (B, T, 128) -> (B, T, 32, 32) = (b, t, f, c).  Inputs: x, conv weight, bn1d weight,
-    bias, running_mean, running_var, bn2d weight, bias, running_mean, running_var."""
-
-    @staticmethod
-    def forward(ctx, x, w, w1, b1, m1, v1, w2, b2, m2, v2):
-        xf = _f32(x)
-        ps = [_f32(p) for p in (w, w1, b1, m1, v1, w2, b2, m2, v2)]
-        _on_device_of(xf, *ps)
-        B, T, F = xf.shape
-        y = torch.empty((B, T, 32, 32), dtype=torch.float32, device=xf.device)
-        a = _front_args(B, T, F, int(ps[0].shape[0]))
-        a.x, a.y, a.w = xf.data_ptr(), y.data_ptr(), ps[0].data_ptr()
-        a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
-        _front_call(False, _lib.FRONT_STEM, a, xf.device)
-        ctx.save_for_backward(xf, *ps)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        xf, *ps = ctx.saved_tensors
-        B, T, F = xf.shape
-        need = ctx.needs_input_grad
-        gyf = _f32(gy)
-        gx, g_w, g_w1, g_b1, g_w2, g_b2 = (_grad_like(t, need[i]) for i, t in
-                                           ((0, xf), (1, ps[0]), (2, ps[1]), (3, ps[2]), (6, ps[5]), (7, ps[6])))
-        a = _front_args(B, T, F, int(ps[0].shape[0]))
-        a.x, a.gy, a.w = xf.data_ptr(), gyf.data_ptr(), ps[0].data_ptr()
-        a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
-        a.gx, a.g_w, a.g_bn1_w, a.g_bn1_b, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in (gx, g_w, g_w1, g_b1, g_w2, g_b2))
-        _front_call(True, _lib.FRONT_STEM, a, xf.device)
-        return gx, g_w, g_w1, g_b1, None, None, g_w2, g_b2, None, None
-
-
-class ConvUnitFn(torch.autograd.Function):
-    """blocks.i.conv2d + .norm + GELU (beat_tracker.py:155-166): (B, T, F, C) -> (B, T, F / 2, 2 C).  Saves its input and the
-    convolution's result ``pre``.  Inputs: x, conv weight, norm weight, bias, running_mean, running_var; ``mixed``: the three
-    products on fp16 operands (section 19), in the forward and, remembered, in the backward."""
-
-    @staticmethod
-    def forward(ctx, x, w, nw, nb, nm, nv, mixed=False):
-        xf = _f32(x)
-        ps = [_f32(p) for p in (w, nw, nb, nm, nv)]
-        _on_device_of(xf, *ps)
-        B, T, F, Cc = xf.shape
-        if tuple(ps[0].shape) != (2 * Cc, Cc, 2, 3) or F % 2:
-            raise ValueError(f"conv unit: input {tuple(xf.shape)} against a weight of shape {tuple(ps[0].shape)}")
-        y = torch.empty((B, T, F // 2, 2 * Cc), dtype=torch.float32, device=xf.device)
-        pre = torch.empty_like(y)
-        a = _front_args(B, T, F, Cc, mixed=mixed)
-        a.x, a.y, a.save_pre, a.w = xf.data_ptr(), y.data_ptr(), pre.data_ptr(), ps[0].data_ptr()
-        a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
-        _front_call(False, _lib.FRONT_CONV, a, xf.device)
-        ctx.save_for_backward(xf, pre, *ps)
-        ctx.mixed = bool(mixed)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        xf, pre, *ps = ctx.saved_tensors
-        B, T, F, Cc = xf.shape
-        need = ctx.needs_input_grad
-        gyf = _f32(gy)
-        gx, g_w, g_nw, g_nb = (_grad_like(t, need[i]) for i, t in enumerate((xf, ps[0], ps[1], ps[2])))
-        a = _front_args(B, T, F, Cc, mixed=ctx.mixed)
-        a.x, a.save_pre, a.gy, a.w = xf.data_ptr(), pre.data_ptr(), gyf.data_ptr(), ps[0].data_ptr()
-        a.bn_w, a.bn_b, a.bn_mean, a.bn_var = (p.data_ptr() for p in ps[1:])
-        a.gx, a.g_w, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in (gx, g_w, g_nw, g_nb))
-        _front_call(True, _lib.FRONT_CONV, a, xf.device)
-        return gx, g_w, g_nw, g_nb, None, None, None
-
-
-# ---- batch-statistics BatchNorm (DESIGN.md section 18): the stem and the conv unit over bt_front_bn_forward / _backward -----------
 def check_batch_statistics(B: int, T: int) -> None:
     """torch's own refusal, raised before any launch: a BatchNorm in training mode needs two values per channel, and
     ``stem.bn1d`` has B T of them"""
@@ -389,17 +294,29 @@ def check_batch_statistics(B: int, T: int) -> None:
                          "need batch x time >= 2")
 
 
-def _front_bn_call(backward: bool, unit: int, a: _lib.FrontBnArgs, device) -> None:
-    query = _lib.lib().bt_front_bn_workspace_bytes_mixed if a.mixed else _lib.lib().bt_front_bn_workspace_bytes
-    need = query(unit, int(backward), a.B, a.T, a.F, a.C)
+def _front_args(B, T, F, Cc, dim=0, mixed=False, batch=False):
+    """The argument struct of bt_front_forward / _backward or, with ``batch`` (the stem and the conv unit on
+    the statistics of the call's batch), of bt_front_bn_forward / _backward, which has no ``dim``"""
+    if batch:
+        return _lib.FrontBnArgs(B=int(B), T=int(T), F=int(F), C=int(Cc), mixed=int(bool(mixed)))
+    return _lib.FrontArgs(B=int(B), T=int(T), F=int(F), C=int(Cc), dim=int(dim), mixed=int(bool(mixed)))
+
+
+def _front_call(backward: bool, unit: int, a, device) -> None:
+    """One call of the frontend's own units: the struct's type picks the family of entry points, its ``mixed`` the workspace query"""
+    batch = isinstance(a, _lib.FrontBnArgs)
+    family = "bt_front_bn" if batch else "bt_front"
+    shape = (a.B, a.T, a.F, a.C) if batch else (a.B, a.T, a.F, a.C, a.dim)
+    need = getattr(_lib.lib(), f"{family}_workspace_bytes_mixed" if a.mixed else f"{family}_workspace_bytes")(unit, int(backward), *shape)
     if need == 0:
         check_front_limits(a.B, a.T)
-        check_batch_statistics(a.B, a.T * (1 if unit == _lib.FRONT_STEM else a.F // 2))
-        raise ValueError(f"the differentiable frontend does not support batch {a.B}, {a.T} frames, {a.F} frequency bins, "
-                         f"{a.C} channels (unit {unit}, batch statistics)")
+        if batch:
+            check_batch_statistics(a.B, a.T * (1 if unit == _lib.FRONT_STEM else a.F // 2))
+        raise ValueError(f"the differentiable frontend does not support batch {a.B}, {a.T} frames, {a.F} frequency bins, {a.C} channels"
+                         + (f" (unit {unit}, batch statistics)" if batch else f", width {a.dim} (unit {unit})"))
     ws = torch.empty(need, dtype=torch.uint8, device=device)
     a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
-    fn = _lib.lib().bt_front_bn_backward if backward else _lib.lib().bt_front_bn_forward
+    fn = getattr(_lib.lib(), f"{family}_backward" if backward else f"{family}_forward")
     with torch.cuda.device(device):
         _lib.check(fn(_lib.stream_ptr(device), unit, C.byref(a)))
 
@@ -413,26 +330,140 @@ def _running(mean, var, tracked, C_):
     return mean.data_ptr(), var.data_ptr(), tracked.data_ptr()
 
 
+# What the two Functions of a unit share, running and batch statistics alike: the struct with the unit's input, conv weight,
+# gains and biases; the forward's outputs; the gradients of a backward.
+def _stem_args(xf, w, w1, b1, w2, b2, batch):
+    B, T, F = xf.shape
+    a = _front_args(B, T, F, int(w.shape[0]), batch=batch)
+    a.x, a.w, a.bn1_w, a.bn1_b, a.bn_w, a.bn_b = (t.data_ptr() for t in (xf, w, w1, b1, w2, b2))
+    return a
+
+
+def _stem_forward(a, xf):
+    y = torch.empty((xf.shape[0], xf.shape[1], 32, 32), dtype=torch.float32, device=xf.device)
+    a.y = y.data_ptr()
+    _front_call(False, _lib.FRONT_STEM, a, xf.device)
+    return y
+
+
+def _stem_backward(a, gy, grads, device):
+    """``grads``: gx, g_w, then gain and bias gradient of bn1d and of bn2d (None: not wanted)"""
+    gyf = _f32(gy)
+    a.gy = gyf.data_ptr()
+    a.gx, a.g_w, a.g_bn1_w, a.g_bn1_b, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in grads)
+    _front_call(True, _lib.FRONT_STEM, a, device)
+
+
+def _conv_args(xf, w, nw, nb, mixed, batch):
+    B, T, F, Cc = xf.shape
+    a = _front_args(B, T, F, Cc, mixed=mixed, batch=batch)
+    a.x, a.w, a.bn_w, a.bn_b = (t.data_ptr() for t in (xf, w, nw, nb))
+    return a
+
+
+def _conv_forward(a, xf, w):
+    """Returns y and the convolution's result ``pre``, which the backward takes"""
+    B, T, F, Cc = xf.shape
+    if tuple(w.shape) != (2 * Cc, Cc, 2, 3) or F % 2:
+        raise ValueError(f"conv unit: input {tuple(xf.shape)} against a weight of shape {tuple(w.shape)}")
+    y = torch.empty((B, T, F // 2, 2 * Cc), dtype=torch.float32, device=xf.device)
+    pre = torch.empty_like(y)
+    a.y, a.save_pre = y.data_ptr(), pre.data_ptr()
+    _front_call(False, _lib.FRONT_CONV, a, xf.device)
+    return y, pre
+
+
+def _conv_backward(a, pre, gy, grads, device):
+    """``grads``: gx, g_w, the norm's gain and bias gradient (None: not wanted)"""
+    gyf = _f32(gy)
+    a.save_pre, a.gy = pre.data_ptr(), gyf.data_ptr()
+    a.gx, a.g_w, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in grads)
+    _front_call(True, _lib.FRONT_CONV, a, device)
+
+
+class StemFn(torch.autograd.Function):
+    """make_stem (beat_tracker.py:108-126): (B, T, 128) -> (B, T, 32, 32) = (b, t, f, c).  Inputs: x, conv weight, bn1d weight,
+    bias, running_mean, running_var, bn2d weight, bias, running_mean, running_var."""
+
+    @staticmethod
+    def _args(xf, w, w1, b1, m1, v1, w2, b2, m2, v2):
+        a = _stem_args(xf, w, w1, b1, w2, b2, batch=False)
+        a.bn1_mean, a.bn1_var, a.bn_mean, a.bn_var = (t.data_ptr() for t in (m1, v1, m2, v2))
+        return a
+
+    @staticmethod
+    def forward(ctx, x, w, w1, b1, m1, v1, w2, b2, m2, v2):
+        xf = _f32(x)
+        ps = [_f32(p) for p in (w, w1, b1, m1, v1, w2, b2, m2, v2)]
+        _on_device_of(xf, *ps)
+        y = _stem_forward(StemFn._args(xf, *ps), xf)
+        ctx.save_for_backward(xf, *ps)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xf, *ps = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gx, g_w, g_w1, g_b1, g_w2, g_b2 = grads = [_grad_like(t, need[i]) for i, t in
+                                                   ((0, xf), (1, ps[0]), (2, ps[1]), (3, ps[2]), (6, ps[5]), (7, ps[6]))]
+        _stem_backward(StemFn._args(xf, *ps), gy, grads, xf.device)
+        return gx, g_w, g_w1, g_b1, None, None, g_w2, g_b2, None, None
+
+
+class ConvUnitFn(torch.autograd.Function):
+    """blocks.i.conv2d + .norm + GELU (beat_tracker.py:155-166): (B, T, F, C) -> (B, T, F / 2, 2 C).  Saves its input and the
+    convolution's result ``pre``.  Inputs: x, conv weight, norm weight, bias, running_mean, running_var; ``mixed``: the three
+    products on fp16 operands (section 19), in the forward and, remembered, in the backward."""
+
+    @staticmethod
+    def _args(xf, w, nw, nb, nm, nv, mixed):
+        a = _conv_args(xf, w, nw, nb, mixed, batch=False)
+        a.bn_mean, a.bn_var = nm.data_ptr(), nv.data_ptr()
+        return a
+
+    @staticmethod
+    def forward(ctx, x, w, nw, nb, nm, nv, mixed=False):
+        xf = _f32(x)
+        ps = [_f32(p) for p in (w, nw, nb, nm, nv)]
+        _on_device_of(xf, *ps)
+        y, pre = _conv_forward(ConvUnitFn._args(xf, *ps, mixed), xf, ps[0])
+        ctx.save_for_backward(xf, pre, *ps)
+        ctx.mixed = bool(mixed)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xf, pre, *ps = ctx.saved_tensors
+        grads = [_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, ps[0], ps[1], ps[2]))]
+        _conv_backward(ConvUnitFn._args(xf, *ps, ctx.mixed), pre, gy, grads, xf.device)
+        return (*grads, None, None, None)
+
+
+# ---- batch-statistics BatchNorm (DESIGN.md section 18): the same two units over bt_front_bn_forward / _backward --------------------
 class StemBatchFn(torch.autograd.Function):
     """``StemFn`` with bn1d and bn2d on the statistics of the call's batch.  Inputs: x, conv weight, bn1d weight, bias, bn2d
     weight, bias, then the six buffers (bn1d running_mean, running_var, num_batches_tracked, bn2d likewise), which the forward
     updates in place, once, and which take no part in the graph.  Saves the batch's mean and 1 / sqrt(var + eps) of both."""
 
     @staticmethod
+    def _args(xf, ps, stats):
+        a = _stem_args(xf, *ps, batch=True)
+        a.save1_mean, a.save1_rstd, a.save_mean, a.save_rstd = (t.data_ptr() for t in stats)
+        return a
+
+    @staticmethod
     def forward(ctx, x, w, w1, b1, w2, b2, m1, v1, n1, m2, v2, n2):
         xf = _f32(x)
         ps = [_f32(p) for p in (w, w1, b1, w2, b2)]
         _on_device_of(xf, *ps, m1, v1, n1, m2, v2, n2)
-        B, T, F = xf.shape
-        y = torch.empty((B, T, 32, 32), dtype=torch.float32, device=xf.device)
+        F = xf.shape[2]
         stats = [torch.empty(n, dtype=torch.float32, device=xf.device) for n in (F, F, 32, 32)]
-        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=int(ps[0].shape[0]))
-        a.x, a.y = xf.data_ptr(), y.data_ptr()
-        a.w, a.bn1_w, a.bn1_b, a.bn_w, a.bn_b = (p.data_ptr() for p in ps)
+        a = StemBatchFn._args(xf, ps, stats)
         a.bn1_mean, a.bn1_var, a.bn1_tracked = _running(m1, v1, n1, F)
         a.bn_mean, a.bn_var, a.bn_tracked = _running(m2, v2, n2, 32)
-        a.save1_mean, a.save1_rstd, a.save_mean, a.save_rstd = (t.data_ptr() for t in stats)
-        _front_bn_call(False, _lib.FRONT_STEM, a, xf.device)
+        y = _stem_forward(a, xf)
         ctx.save_for_backward(xf, *ps, *stats)
         return y
 
@@ -440,15 +471,8 @@ class StemBatchFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         xf, w, w1, b1, w2, b2, *stats = ctx.saved_tensors
-        B, T, F = xf.shape
-        gyf = _f32(gy)
         grads = [_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, w, w1, b1, w2, b2))]
-        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=int(w.shape[0]))
-        a.x, a.gy = xf.data_ptr(), gyf.data_ptr()
-        a.w, a.bn1_w, a.bn1_b, a.bn_w, a.bn_b = (p.data_ptr() for p in (w, w1, b1, w2, b2))
-        a.save1_mean, a.save1_rstd, a.save_mean, a.save_rstd = (t.data_ptr() for t in stats)
-        a.gx, a.g_w, a.g_bn1_w, a.g_bn1_b, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in grads)
-        _front_bn_call(True, _lib.FRONT_STEM, a, xf.device)
+        _stem_backward(StemBatchFn._args(xf, (w, w1, b1, w2, b2), stats), gy, grads, xf.device)
         return (*grads, None, None, None, None, None, None)
 
 
@@ -458,22 +482,21 @@ class ConvUnitBatchFn(torch.autograd.Function):
     ``ConvUnitFn``'s (the moments are those of the fp16-product ``pre``)."""
 
     @staticmethod
+    def _args(xf, ps, stats, mixed):
+        a = _conv_args(xf, *ps, mixed, batch=True)
+        a.save_mean, a.save_rstd = (t.data_ptr() for t in stats)
+        return a
+
+    @staticmethod
     def forward(ctx, x, w, nw, nb, nm, nv, nn_, mixed=False):
         xf = _f32(x)
         ps = [_f32(p) for p in (w, nw, nb)]
         _on_device_of(xf, *ps, nm, nv, nn_)
-        B, T, F, Cc = xf.shape
-        if tuple(ps[0].shape) != (2 * Cc, Cc, 2, 3) or F % 2:
-            raise ValueError(f"conv unit: input {tuple(xf.shape)} against a weight of shape {tuple(ps[0].shape)}")
-        y = torch.empty((B, T, F // 2, 2 * Cc), dtype=torch.float32, device=xf.device)
-        pre = torch.empty_like(y)
-        stats = [torch.empty(2 * Cc, dtype=torch.float32, device=xf.device) for _ in range(2)]
-        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=Cc, mixed=int(bool(mixed)))
-        a.x, a.y, a.save_pre = xf.data_ptr(), y.data_ptr(), pre.data_ptr()
-        a.w, a.bn_w, a.bn_b = (p.data_ptr() for p in ps)
-        a.bn_mean, a.bn_var, a.bn_tracked = _running(nm, nv, nn_, 2 * Cc)
-        a.save_mean, a.save_rstd = (t.data_ptr() for t in stats)
-        _front_bn_call(False, _lib.FRONT_CONV, a, xf.device)
+        Cout = 2 * xf.shape[3]
+        stats = [torch.empty(Cout, dtype=torch.float32, device=xf.device) for _ in range(2)]
+        a = ConvUnitBatchFn._args(xf, ps, stats, mixed)
+        a.bn_mean, a.bn_var, a.bn_tracked = _running(nm, nv, nn_, Cout)
+        y, pre = _conv_forward(a, xf, ps[0])
         ctx.save_for_backward(xf, pre, *ps, *stats)
         ctx.mixed = bool(mixed)
         return y
@@ -481,16 +504,9 @@ class ConvUnitBatchFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        xf, pre, w, nw, nb, mean, rstd = ctx.saved_tensors
-        B, T, F, Cc = xf.shape
-        gyf = _f32(gy)
+        xf, pre, w, nw, nb, *stats = ctx.saved_tensors
         grads = [_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, w, nw, nb))]
-        a = _lib.FrontBnArgs(B=B, T=T, F=F, C=Cc, mixed=int(ctx.mixed))
-        a.x, a.save_pre, a.gy = xf.data_ptr(), pre.data_ptr(), gyf.data_ptr()
-        a.w, a.bn_w, a.bn_b = (p.data_ptr() for p in (w, nw, nb))
-        a.save_mean, a.save_rstd = mean.data_ptr(), rstd.data_ptr()
-        a.gx, a.g_w, a.g_bn_w, a.g_bn_b = (_lib.ptr(g) for g in grads)
-        _front_bn_call(True, _lib.FRONT_CONV, a, xf.device)
+        _conv_backward(ConvUnitBatchFn._args(xf, (w, nw, nb), stats, ctx.mixed), pre, gy, grads, xf.device)
         return (*grads, None, None, None, None)
 
 

@@ -768,7 +768,9 @@ int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int 
  * column sums over chunks of BT_TRAIN_CS_ROWS rows, partials in the workspace added in chunk order by a second launch), so two
  * runs are bit-identical, and a sequence's gx is the same alone and inside a batch.  No call synchronises, allocates or clears
  * memory; no launch reads workspace bytes that the same call has not written.  Limits: B T <= 65535 (the frequency direction
- * runs one sequence per frame) and B T 32 <= 2^22 rows (BT_FRONT_SWAP: see above); anything else is BT_ERR_ARG and the workspace query returns 0. */
+ * runs one sequence per frame) and B T 32 <= 2^22 rows (BT_FRONT_SWAP: see above); anything else is BT_ERR_ARG and the workspace query returns 0.
+ * These two entry points and the two bt_front_bn_* ones below check, before any launch and in this order, the struct pointer, the
+ * shape, `mixed`, the required pointers, the workspace's alignment and its size; a call with several faults reports the first. */
 #define BT_FRONT_STEM 0
 #define BT_FRONT_CONV 1
 #define BT_FRONT_LINEAR 2

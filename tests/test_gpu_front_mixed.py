@@ -87,7 +87,8 @@ def abi_front(sd, unit, dims, B, T, x, gy, poison, mixed):
 
 
 def abi_conv_bn(sd, i, B, T, x, gy, poison, mixed):
-    """the same of conv unit i through bt_front_bn_* -> ({"y", "x", <key>: gradient}, {<key>: running buffer after the forward})"""
+    """the same of conv unit i through bt_front_bn_* -> ({"y", "save_pre", "x", <key>: gradient}, {<key>: running buffer after the
+    forward})"""
     from beat_this_amd import _lib as L
 
     p, F_, C_ = conv_spec(i)
@@ -102,10 +103,10 @@ def abi_conv_bn(sd, i, B, T, x, gy, poison, mixed):
     wkey = p + "conv2d.weight"
     a = L.FrontBnArgs(B=B, T=T, F=F_, C=C_, mixed=int(mixed))
     a.x, a.gy, a.w = guarded(xs, x).ptr(), guarded(ys, gy).ptr(), guarded(sd[wkey].shape, sd[wkey]).ptr()
-    outs = {"y": guarded(ys), "x": guarded(xs), wkey: guarded(sd[wkey].shape), p + "norm.weight": guarded(n_ch),
+    outs = {"y": guarded(ys), "save_pre": guarded(ys), "x": guarded(xs), wkey: guarded(sd[wkey].shape), p + "norm.weight": guarded(n_ch),
             p + "norm.bias": guarded(n_ch)}
     a.y, a.gx, a.g_w, a.g_bn_w, a.g_bn_b = (outs[k].ptr() for k in ("y", "x", wkey, p + "norm.weight", p + "norm.bias"))
-    a.save_pre, a.save_mean, a.save_rstd = guarded(ys).ptr(), guarded(n_ch).ptr(), guarded(n_ch).ptr()
+    a.save_pre, a.save_mean, a.save_rstd = outs["save_pre"].ptr(), guarded(n_ch).ptr(), guarded(n_ch).ptr()
     a.bn_w, a.bn_b = guarded(n_ch, sd[p + "norm.weight"]).ptr(), guarded(n_ch, sd[p + "norm.bias"]).ptr()
     stats = {p + "norm.running_mean": guarded(n_ch, sd[p + "norm.running_mean"]),
              p + "norm.running_var": guarded(n_ch, sd[p + "norm.running_var"]),
@@ -370,6 +371,20 @@ def test_a_sequence_alone_gives_the_same_input_gradient(i):
     assert same_bits(alone["x"][0], both["x"][0]) and same_bits(alone["y"][0], both["y"][0])
 
 
+@pytest.mark.parametrize("mixed", [False, True])
+@pytest.mark.parametrize("B,T", [(2, 3), (1, 65)])
+@pytest.mark.parametrize("i", [0, 2])
+def test_save_pre_has_the_same_bits_on_both_statistics(i, B, T, mixed):
+    """bt_front_bn_forward runs the conv GEMM of bt_front_forward with its GELU output suppressed: the saved ``pre`` of the same x
+    and weight has the same bits on running and on batch statistics, fp32 and mixed.  Unit 0 has 96 and 1040 rows: across the
+    64-row tile, no multiple of it, and across 1024."""
+    x, g = M.conv_inputs(i, B, T)
+    sd = M.state_dict()
+    running = abi_front(sd, "conv", conv_spec(i), B, T, x, g, POISONS[0], mixed)
+    batch, _ = abi_conv_bn(sd, i, B, T, x, g, POISONS[1], mixed)
+    assert torch.isfinite(running["save_pre"]).all() and same_bits(batch["save_pre"], running["save_pre"])
+
+
 def test_the_autograd_functions_pass_the_flag_on():
     """ConvUnitFn, ConvUnitBatchFn and ProjectionFn with mixed=True make the calls the C-ABI tests above make: the same bits"""
     from beat_this_amd.model import BeatThis
@@ -419,6 +434,9 @@ def test_refused_arguments():
         F_, C_, _ = shapes[unit]
         n16 = lib.bt_front_bn_workspace_bytes_mixed(unit, 0, 2, 3, F_, C_)
         assert lib.bt_front_bn_workspace_bytes(unit, 0, 2, 3, F_, C_) > 0 and (n16 == 0) == (unit == L.FRONT_STEM)
+    for backward in (0, 1):                               # the same weight image on batch statistics: 24 C^2 bytes
+        n32, n16 = (q(L.FRONT_CONV, backward, 2, 3, 32, 32) for q in (lib.bt_front_bn_workspace_bytes, lib.bt_front_bn_workspace_bytes_mixed))
+        assert n32 > 0 and n16 == n32 + 24 * 32 * 32
     assert lib.bt_front_workspace_bytes_mixed(L.FRONT_CONV, 0, 2, 3, 32, 48, 0) == 0      # an unsupported width
     assert lib.bt_front_bn_workspace_bytes_mixed(L.FRONT_CONV, 0, 1, 1, 2, 32) == 0       # one value per channel
     # refused before any launch: the pointers below are null, so a launch would be seen
