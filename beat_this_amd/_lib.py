@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "engine.hip"]
+           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "stretch.hip", "engine.hip"]
 HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "train_front_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
@@ -185,6 +185,8 @@ FRONT_MAX_FRAMES, FRONT_MAX_ROWS = 65535, 1 << 22           # limits of the fron
 TRAIN_DW_ROWS, TRAIN_CS_ROWS, TRAIN_ATTN_BLOCK = 1024, 64, 64   # BT_TRAIN_* tile edges (tests sit on both sides of them)
 DROP_ATTN_P, DROP_ATTN_OUT, DROP_FF_HIDDEN, DROP_FF_OUT = range(4)   # BT_DROP_*: the four sites of the training route's dropout
 OPTIM_CHUNK, OPTIM_NORM_SLICE = 4096, 4096                 # BT_OPTIM_CHUNK / _NORM_SLICE: elements per workgroup (likewise)
+STRETCH_MAX_SAMPLES, STRETCH_SCAN_BLOCK, STRETCH_TABLE_DOUBLES = 1 << 26, 64, 6146   # BT_STRETCH_* (csrc/stretch.hip)
+RESAMPLE_RATIO_TAPS, RESAMPLE_RATIO_CROSSINGS = 4096, 116   # BT_RESAMPLE_RATIO_*: the layout of tables.resample_ratio_table
 
 EXPORTS = {
     "bt_last_error": (C.c_char_p, []),
@@ -308,6 +310,11 @@ EXPORTS = {
     "bt_grad_norm_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]),
     "bt_adamw_step_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.POINTER(OptimHyper), C.c_void_p]),
+    "bt_stretch_out_len": (C.c_int64, [C.c_int64, C.c_double]),
+    "bt_stretch_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_double]),
+    "bt_stretch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p,
+                             C.c_size_t]),
+    "bt_resample_ratio": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_int64]),
 }
 
 
@@ -327,7 +334,9 @@ FLAGS_BY_SOURCE = {"tail.hip": ["-Xclang", "-target-feature", "-Xclang", "-packe
                    # an annotation's frame is rint(time * fps) - start in fp64, the same on the host and the device
                    "data.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # the AdamW step and the gradient norm must have the same bits on the host and the device (the host twins)
-                   "optim.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
+                   "optim.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
+                   # frame positions, output lengths and filter arguments are fp64 expressions that numpy evaluates too
+                   "stretch.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
 # compile-time switches: BT_DEFINES in the environment of build() (e.g. "-DBT_HALF_BF16"); every one of them builds a correct library
 EXTRA_DEFINES = os.environ.get("BT_DEFINES", "").split()
 

@@ -86,3 +86,72 @@ class LogMelSpect(torch.nn.Module):
             _lib.check(_lib.lib().bt_logmel(_lib.stream_ptr(x.device), C.byref(self._get_tables()), x.data_ptr(), n,
                                             out.data_ptr()))
         return out
+
+
+# ---- tempo and pitch variants (csrc/stretch.hip; the algorithm is defined in include/beat_this_amd.h) ------------------
+_STRETCH_TABLES: dict = {}
+
+
+def _stretch_tables(device):
+    """(window + twiddles as float64, the resampler's filter table as float32) on ``device``, uploaded once"""
+    key = torch.device(device)
+    if key not in _STRETCH_TABLES:
+        _STRETCH_TABLES[key] = (torch.from_numpy(tables.stretch_tables()).to(key),
+                                torch.from_numpy(tables.resample_ratio_table()).to(key))
+    return _STRETCH_TABLES[key]
+
+
+def _waveform(x, what):
+    if not isinstance(x, torch.Tensor) or x.dim() != 1:
+        raise ValueError(f"{what}: expected a 1-D tensor")
+    _lib.require_gpu(x, "waveform")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{what}: expected float32, got {x.dtype}")
+    return x.contiguous()
+
+
+def stretch_length(x: torch.Tensor, length_factor: float) -> torch.Tensor:
+    """``x`` (N,) -> (floor(N L + 0.5),) with the pitch unchanged: the phase vocoder of bt_stretch, 0.5 <= L <= 2."""
+    x = _waveform(x, "stretch_length")
+    L, n = float(length_factor), x.shape[0]
+    lib = _lib.lib()
+    m = lib.bt_stretch_out_len(n, L)
+    ws_bytes = lib.bt_stretch_workspace_bytes(n, L)
+    if m <= 0 or ws_bytes == 0:
+        raise ValueError(f"time stretch: unsupported length factor {L} (0.5 .. 2) or length {n} "
+                         f"(1 .. {_lib.STRETCH_MAX_SAMPLES} samples in and out)")
+    tab, _ = _stretch_tables(x.device)
+    y = torch.empty(m, dtype=torch.float32, device=x.device)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.bt_stretch(_lib.stream_ptr(x.device), tab.data_ptr(), x.data_ptr(), n, L, y.data_ptr(), m, ws.data_ptr(),
+                                  ws_bytes))
+    return y
+
+
+def time_stretch(x: torch.Tensor, stretch_factor: float) -> torch.Tensor:
+    """pedalboard's meaning of the factor: > 1 is faster and shorter (length factor 1 / stretch_factor)"""
+    return stretch_length(x, 1.0 / float(stretch_factor))
+
+
+def resample_ratio(x: torch.Tensor, step: float, n_out=None) -> torch.Tensor:
+    """y[m] = x at position m * step (band-limited to the lower of the two rates); n_out defaults to ceil(N / step)"""
+    x = _waveform(x, "resample_ratio")
+    step, n = float(step), x.shape[0]
+    if not (0.25 <= step <= 4.0):
+        raise ValueError(f"resample_ratio: step {step} outside 0.25 .. 4")
+    if n_out is None:
+        n_out = int(np.ceil(n / step))
+    _, tab = _stretch_tables(x.device)
+    y = torch.empty(int(n_out), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().bt_resample_ratio(_lib.stream_ptr(x.device), x.data_ptr(), n, step, tab.data_ptr(), y.data_ptr(),
+                                                int(n_out)))
+    return y
+
+
+def pitch_shift(x: torch.Tensor, semitones: float) -> torch.Tensor:
+    """same length, pitch moved by ``semitones``: stretch by r = 2^(s / 12), then read the result at step r"""
+    x = _waveform(x, "pitch_shift")
+    r = 2.0 ** (float(semitones) / 12.0)
+    return resample_ratio(stretch_length(x, r), r, x.shape[0])

@@ -90,3 +90,37 @@ def resample_filter(up: int, down: int):
     h = 2.0 * fc * np.sinc(2.0 * fc * n) * np.kaiser(2 * half + 1, beta)
     h /= h.sum()
     return h * up, half
+
+
+# ---- time stretch / pitch shift (csrc/stretch.hip) ---------------------------------------------
+STRETCH_N_FFT, STRETCH_HOP = 2048, 512
+
+
+def stretch_tables() -> np.ndarray:
+    """float64 [6146] for bt_stretch: the periodic Hann window w[2048], then (cos, -sin) of 2 pi t / 1024 for t = 0 .. 1023
+    (the twiddles of the 1024-point complex FFT), then (cos, -sin) of 2 pi k / 2048 for k = 0 .. 1024 (the real-FFT split)."""
+    n = STRETCH_N_FFT
+    win = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)
+    t = 2.0 * np.pi * np.arange(n // 2) / (n // 2)
+    k = 2.0 * np.pi * np.arange(n // 2 + 1) / n
+    return np.concatenate([win, np.stack([np.cos(t), -np.sin(t)], 1).ravel(), np.stack([np.cos(k), -np.sin(k)], 1).ravel()])
+
+
+# Arbitrary-ratio resampler: the same specification as resample_filter (flat to 91.3 % of the lower Nyquist frequency, nothing
+# from 100 % of it), designed for 150 dB so that the error of reading the table by linear interpolation (about
+# (pi^2 / 8) / taps^2 = -143 dB at 4096 taps per unit) still leaves it above the rational path's 125 dB.
+RATIO_TAPS_PER_CROSSING = 4096        # BT_RESAMPLE_RATIO_TAPS: table entries per unit of the filter's argument
+RATIO_CROSSINGS = 116                 # BT_RESAMPLE_RATIO_CROSSINGS: the filter's half width in samples of the lower rate
+RATIO_ATTENUATION_DB = 150.0
+
+
+def resample_ratio_table() -> np.ndarray:
+    """float32 [4096 * 116 + 1]: h(i / 4096), i >= 0, of h(t) = 2 fc sinc(2 fc t) kaiser(t / 116), fc = 0.47825 (the -6 dB
+    point in the middle of [0.913, 1] x Nyquist), scaled to unit DC gain."""
+    P, Z = RATIO_TAPS_PER_CROSSING, RATIO_CROSSINGS
+    beta = 0.1102 * (RATIO_ATTENUATION_DB - 8.7)
+    fc = 0.5 * (1.0 + RESAMPLE_PASSBAND_END) * 0.5
+    t = np.arange(P * Z + 1, dtype=np.float64) / P
+    h = 2.0 * fc * np.sinc(2.0 * fc * t) * np.i0(beta * np.sqrt(np.maximum(0.0, 1.0 - (t / Z) ** 2))) / np.i0(beta)
+    h /= (2.0 * h[P::P].sum() + h[0])          # unit gain at DC for integer-spaced taps
+    return h.astype(np.float32)

@@ -912,6 +912,60 @@ int bt_grad_norm_host(const float* grad, int64_t total, float grad_scale, float 
 int bt_adamw_step_host(const bt_optim_tensor* tensors, int n_tensors, const bt_optim_chunk* chunks, int64_t n_chunks, float* grad,
                        float* m, float* v, int64_t total, const bt_optim_hyper* hyper, const float* coef);
 
+/* ---- building bundles from audio: time stretch, pitch shift, arbitrary-ratio resampling (csrc/stretch.hip, DESIGN.md
+ * section 20) -------------------------------------------------------------------------------------------------------------------
+ * The reference's launch_scripts/preprocess_audio.py makes its tempo and pitch variants with pedalboard (Rubber Band).  That
+ * algorithm cannot be restated; the one below is this library's own and THIS TEXT is its definition (tests/stretch_reference.py
+ * is a numpy restatement of it).  What is kept of the reference is the meaning of its parameters: a tempo change of +p percent
+ * shortens the audio to 1 / (1 + p / 100) of its length, a pitch shift of s semitones keeps the length.
+ *
+ * TIME STRETCH  x[0 .. N) fp32 (zero outside), length factor L, 0.5 <= L <= 2  ->  y[0 .. M), M = floor(N L + 0.5) (fp64).
+ * Phase vocoder with identity phase locking (Laroche & Dolson 1999, the basic form).  n_fft = 2048, periodic Hann window
+ * w[i] = 0.5 - 0.5 cos(2 pi i / 2048) for analysis and synthesis, synthesis hop Hs = 512, real FFT, bins k = 0 .. 1024.  A frame
+ * "centred at c" is x[c - 1024 + i] w[i], i = 0 .. 2047, and X[k] = sum_i of it times exp(-2 pi i k i / 2048).
+ *   Frames: n = 0 .. ceil(M / Hs), frame n centred at OUTPUT sample n Hs.  It takes two analysis frames: X1_n centred at
+ *     a_n = floor(n Hs / L + 0.5) (fp64) and X0_n centred at a_n - Hs.
+ *   Phases are 32-bit fixed-point turns: q(z) = round(atan2(im, re) / (2 pi) * 2^32) mod 2^32, round to nearest, q(0) = 0.  The two
+ *     analysis frames are one synthesis hop apart, so the unwrapped phase advance of the classical vocoder is congruent to
+ *     d[n,k] = q(X1_n[k]) - q(X0_n[k]) (uint32; d[0,k] = q(X1_0[k])) and the accumulated phase is the integer prefix sum
+ *     S[n,k] = sum_{m = 0 .. n} d[m,k] (uint32): exact, independent of the order of summation.
+ *   Locking, per frame on mag = |X1_n|: bin k is a PEAK iff mag[k] > 0, mag[k] > mag[j] for the existing j of {k - 2, k - 1} and
+ *     mag[k] >= mag[j] for the existing j of {k + 1, k + 2}.  A bin b between consecutive peaks p < p' belongs to p iff
+ *     b <= (p + p') / 2 (integer division), bins below the first peak to the first, bins above the last to the last; in a
+ *     frame without a peak every bin belongs to itself.  With p(k) the owner of k:
+ *     phi[n,k] = S[n,p(k)] + q(X1_n[k]) - q(X1_n[p(k)])  (uint32).
+ *   Synthesis: Y_n[k] = mag[k] exp(2 pi i phi[n,k] / 2^32), imaginary parts of bins 0 and 1024 dropped; y_n = inverse real FFT
+ *     (1 / 2048 normalised) times w.  Output sample m = sum over its at most four frames (those with 0 <= m - n Hs + 1024 < 2048),
+ *     in ascending n, of y_n[m - n Hs + 1024], divided by the sum of w^2 at the same indices over the same frames.
+ *   At L = 1, X0_n = X1_{n-1}: the sum telescopes, phi = q(X1_n) whatever the peaks are, and y = x up to rounding.
+ * Arithmetic: the analysis (FFT, magnitude, atan2) is fp64 -- which bin is a peak is decided as the definition decides it, not by
+ * fp32 rounding -- and the synthesis fp32.  No atomics: two calls give the same bits.
+ * Limits: 1 <= N, M <= BT_STRETCH_MAX_SAMPLES (25 minutes at 44.1 kHz).  The workspace is the caller's, 16-byte aligned,
+ * bt_stretch_workspace_bytes (N, L) bytes (0: unsupported N or L; about 20.6 KB per 512 output samples); no launch reads a byte
+ * of it that this call has not written.  bt_stretch_out_len (N, L) = M (0: unsupported); n_out must equal it.
+ * d_tables: BT_STRETCH_TABLE_DOUBLES doubles -- w[2048], then (cos, -sin)(2 pi t / 1024) for t = 0 .. 1023, then
+ * (cos, -sin)(2 pi k / 2048) for k = 0 .. 1024 (beat_this_amd/tables.py: stretch_tables).
+ * The prefix sum runs in blocks of BT_STRETCH_SCAN_BLOCK frames (tests sit on both sides of the boundary).
+ *
+ * RESAMPLING BY AN ARBITRARY RATIO  y[m] = c sum_j x[j] h(c (m step - j)), m = 0 .. n_out - 1, c = min(1, 1 / step), x zero outside
+ * [0, n_in); 0.25 <= step <= 4, 1 <= n_in, n_out <= 4 BT_STRETCH_MAX_SAMPLES.  h(t) = 2 fc sinc(2 fc t) kaiser(t / Z), fc = 0.47825, |t| < Z = BT_RESAMPLE_RATIO_CROSSINGS, is read
+ * from d_table = h(i / P), i = 0 .. P Z, P = BT_RESAMPLE_RATIO_TAPS (fp32, tables.py: resample_ratio_table) by linear
+ * interpolation: u = |c (m step - j)| P in fp64, i = floor(u), h = tab[i] + (u - i)(tab[i+1] - tab[i]) in fp32.  The position
+ * m step and u are fp64 (fp32 positions are wrong after a few seconds of audio); products and the sum are fp32, taps in ascending j
+ * from ceil(m step - Z / c), floor(2 Z / c) + 1 of them.
+ * PITCH SHIFT by s semitones = bt_stretch with L = r = 2^(s / 12), then bt_resample_ratio with step = r to exactly N samples. */
+#define BT_STRETCH_MAX_SAMPLES (1 << 26)
+#define BT_STRETCH_SCAN_BLOCK 64
+#define BT_STRETCH_TABLE_DOUBLES 6146
+#define BT_RESAMPLE_RATIO_TAPS 4096
+#define BT_RESAMPLE_RATIO_CROSSINGS 116
+int64_t bt_stretch_out_len(int64_t n_in, double L);
+size_t bt_stretch_workspace_bytes(int64_t n_in, double L);
+int bt_stretch(void* stream, const double* d_tables, const float* d_in, int64_t n_in, double L, float* d_out, int64_t n_out,
+               void* d_ws, size_t ws_bytes);
+int bt_resample_ratio(void* stream, const float* d_in, int64_t n_in, double step, const float* d_table, float* d_out,
+                      int64_t n_out);
+
 #ifdef __cplusplus
 }
 #endif
