@@ -198,8 +198,9 @@ class BeatThis(_TracksChildren, nn.Module):
         masks are this package's own (Philox4x32-10 under ``seed``, include/beat_this_amd.h), not torch's generator: every
         attention / feed-forward call that drops takes the next stream number from a counter (``dropout_state()``), which
         ``set_dropout_state()`` rewinds to repeat a run bit for bit.  A graph capture with dropout active raises
-        ``RuntimeError`` (a replay would repeat its masks).  ``dropout["frontend"]`` is unused: the frozen frontend always
-        runs the inference path and the differentiable one runs without dropout;
+        ``RuntimeError`` (a replay would repeat its masks).  ``dropout["frontend"]`` is read only after the second opt-in
+        ``enable_dropout(seed, frontend=True)`` and only where the differentiable frontend runs (below): the frozen frontend
+        always runs the inference path, which never drops;
       * ``rotary_embed.freqs`` never receives a gradient, as in the reference;
       * the frontend is frozen unless ``set_frontend_trainable()`` was called: without that opt-in a frontend parameter that
         requires grad makes a grad-mode forward raise ``NotImplementedError`` rather than silently leaving its ``.grad`` empty
@@ -210,8 +211,13 @@ class BeatThis(_TracksChildren, nn.Module):
         gradients also reach ``x`` when it requires grad.  That part of the route is fp32 whatever ``set_train_precision`` says
         (it covers the trunk's units alone) unless ``set_frontend_precision("16-mixed")`` was called: then the conv units, the
         leaves and the projection round both operands of their matrix products to fp16 and accumulate in fp32 (DESIGN.md section
-        19; the stem and everything that is no matrix product stay fp32); it runs WITHOUT dropout even after ``enable_dropout`` (``dropout["frontend"]``
-        stays unused); and its BatchNorm statistics are frozen unless ``set_batch_statistics()`` was called: every BatchNorm
+        19; the stem and everything that is no matrix product stay fp32); it runs without dropout after ``enable_dropout(seed)``
+        and drops only after ``enable_dropout(seed, frontend=True)``: then, in ``train()`` mode and with
+        ``dropout["frontend"]`` above 0, the twelve leaves drop at that rate at the trunk's four places -- the stem, the conv units
+        and the projection never drop, as in the reference -- and every leaf call takes the next stream number from the same
+        counter, in forward order (block 0 ``attnF``, ``ffF``, ``attnT``, ``ffT``, then blocks 1 and 2, then the trunk's units):
+        a whole-model forward advances ``calls`` by 12 + 2 ``n_layers``;
+        and its BatchNorm statistics are frozen unless ``set_batch_statistics()`` was called: every BatchNorm
         uses ``running_mean`` / ``running_var``, in ``train()`` as in ``eval()``, and those buffers and
         ``num_batches_tracked`` never receive a gradient and are never updated.  The callable nodes below ``frontend`` (``stem``, ``blocks[i]``, ``.partial``, ``.linear`` ...) stay
         inference-only, and the route does not pass through them: forward hooks registered BELOW ``frontend`` do not fire on a
@@ -241,7 +247,7 @@ class BeatThis(_TracksChildren, nn.Module):
         self.hparams = resolve_hparams(dict(
             spect_dim=spect_dim, transformer_dim=transformer_dim, ff_mult=ff_mult, n_layers=n_layers,
             head_dim=head_dim, stem_dim=stem_dim, sum_head=sum_head, partial_transformers=partial_transformers))
-        # reference init statistics (beat_tracker.py:170-186); inference-only, so plain tensors
+        # reference init statistics (beat_tracker.py:170-186); inference-only, so plain tensors (``init_weights`` draws others)
         init = random_state_dict(self.hparams, seed=0, style="init0")
         for i, name in enumerate(("frontend", "transformer_blocks", "task_heads")):
             self.add_module(name, _Stage(self, i))
@@ -250,6 +256,7 @@ class BeatThis(_TracksChildren, nn.Module):
         self._bind_units()
         self.dropout = dict(dropout)
         self._dropout_rng = None     # enable_dropout(): {"seed", "calls"}
+        self._frontend_dropout = False   # enable_dropout(frontend=True): the leaves of the partial transformers drop too
         self._train_precision = "32-true"
         self._frontend_precision = "32-true"   # set_frontend_precision()
         self._frontend_trainable = False   # set_frontend_trainable()
@@ -302,6 +309,18 @@ class BeatThis(_TracksChildren, nn.Module):
             bind(layer[0], "attn", l)
             bind(layer[1], "ff", l)
         bind(self.transformer_blocks.norm, "norm")
+
+    def init_weights(self, init_seed: int = 0) -> "BeatThis":
+        """The reference's initial state (beat_tracker.py:170-186) drawn under ``init_seed``, written in place: the matrices and
+        the convolutions follow the seed; BatchNorm, gains and biases are ones and zeros and ``num_batches_tracked`` 0 whatever
+        it is.  Seed 0 is the state a new ``BeatThis`` holds.  (A method, not a constructor argument: the constructor's
+        arguments are the architecture, which a checkpoint's hyper-parameters carry one for one; this is none.)"""
+        init = random_state_dict(self.hparams, seed=int(init_seed), style="init0")
+        with torch.no_grad():
+            for key, t in self.state_dict().items():
+                t.copy_(init[key])
+        self._engine = None
+        return self
 
     # -- state dict plumbing (beat_tracker.py:194-203: strip torch.compile's "_orig_mod.") ----
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
@@ -416,7 +435,9 @@ class BeatThis(_TracksChildren, nn.Module):
         batch = self._batch_route()
         if batch:
             _bw.check_batch_statistics(int(x.shape[0]), int(x.shape[1]))
-        h = _bw.frontend_train(self, x.to(torch.float32), batch, self.frontend_precision == "16-mixed")
+        # the leaves' dropout: asked once per leaf call, in forward order (None where nothing drops)
+        drops = (lambda: self._next_dropout("frontend")) if self.frontend_dropout and self.training else None
+        h = _bw.frontend_train(self, x.to(torch.float32), batch, self.frontend_precision == "16-mixed", drops)
         if batch:   # noted AFTER the call: an engine that ``_rope`` packed half way through it is stale as well
             self._stats_moved = True
         return h
@@ -452,36 +473,59 @@ class BeatThis(_TracksChildren, nn.Module):
         return getattr(self, "_frontend_precision", "32-true")
 
     # -- dropout on the differentiable route -------------------------------------------------------------
-    def enable_dropout(self, seed: int = 0) -> "BeatThis":
+    def enable_dropout(self, seed: int = 0, frontend: bool = False) -> "BeatThis":
         """Opt in: in ``train()`` mode the differentiable route drops at rate ``dropout["transformer"]``, with masks drawn
-        under ``seed``; the call counter starts at 0."""
-        p = float(self.dropout.get("transformer", 0.0))
-        if not 0.0 <= p < 1.0:   # (NaN fails both comparisons)
-            raise ValueError(f"dropout['transformer'] = {p}: the rate must satisfy 0 <= p < 1")
-        self.set_dropout_state({"seed": seed, "calls": 0})
+        under ``seed``; the call counter starts at 0.  ``frontend=True`` is a second opt-in on top of it, never inferred: the
+        twelve leaves of the partial transformers drop at ``dropout["frontend"]`` where the differentiable frontend runs
+        (``set_frontend_trainable()`` and grad mode).  Without it the call means what it always did."""
+        for part in ("transformer", "frontend") if frontend else ("transformer",):
+            p = float(self.dropout.get(part, 0.0))
+            if not 0.0 <= p < 1.0:   # (NaN fails both comparisons)
+                raise ValueError(f"dropout[{part!r}] = {p}: the rate must satisfy 0 <= p < 1")
+        self.set_dropout_state({"seed": seed, "calls": 0, "frontend": bool(frontend)})
         return self
 
     def disable_dropout(self) -> "BeatThis":
         self._dropout_rng = None
+        self._frontend_dropout = False
         return self
+
+    @property
+    def frontend_dropout(self) -> bool:
+        """The frontend's leaves are opted in to dropout (``enable_dropout(frontend=True)``)"""
+        return getattr(self, "_dropout_rng", None) is not None and getattr(self, "_frontend_dropout", False)
 
     def dropout_state(self):
         """{"seed", "calls"} -- the seed and how many attention / feed-forward calls have drawn masks so far -- or None when
-        dropout is not enabled"""
-        return None if getattr(self, "_dropout_rng", None) is None else dict(self._dropout_rng)
+        dropout is not enabled; with the frontend's opt-in also ``"frontend": True``"""
+        if getattr(self, "_dropout_rng", None) is None:
+            return None
+        state = dict(self._dropout_rng)
+        if self.frontend_dropout:
+            state["frontend"] = True
+        return state
 
     def set_dropout_state(self, state: dict) -> None:
-        """Enable dropout at ``state`` (what ``dropout_state()`` returned): the next call that drops takes stream ``calls``"""
+        """Enable dropout at ``state`` (what ``dropout_state()`` returned): the next call that drops takes stream ``calls``.
+        ``state["frontend"]``, when present, sets the frontend's opt-in; absent, the opt-in stays what it is."""
         seed, calls = int(state["seed"]), int(state["calls"])
         if not (0 <= seed < 1 << 64 and 0 <= calls < 1 << 64):
             raise ValueError(f"dropout seed and calls must fit 64 unsigned bits, got {seed} and {calls}")
+        if "frontend" in state:
+            if state["frontend"]:
+                p = float(self.dropout.get("frontend", 0.0))
+                if not 0.0 <= p < 1.0:
+                    raise ValueError(f"dropout['frontend'] = {p}: the rate must satisfy 0 <= p < 1")
+            self._frontend_dropout = bool(state["frontend"])
         self._dropout_rng = {"seed": seed, "calls": calls}
 
-    def _next_dropout(self):
+    def _next_dropout(self, part: str = "transformer"):
         """(p, seed, stream) for one attention / feed-forward call of the differentiable route, or None: dropout is active
-        iff it is enabled, the model is in ``train()`` mode and the rate is above 0"""
+        iff it is enabled, the model is in ``train()`` mode and the rate ``dropout[part]`` is above 0; ``part`` "frontend" (a
+        leaf of a partial transformer) needs the frontend's opt-in as well.  A call that does not drop takes no number."""
         rng = getattr(self, "_dropout_rng", None)
-        p = float(self.dropout.get("transformer", 0.0)) if rng is not None and self.training else 0.0
+        on = rng is not None and self.training and (part != "frontend" or getattr(self, "_frontend_dropout", False))
+        p = float(self.dropout.get(part, 0.0)) if on else 0.0
         if not p > 0.0:
             return None
         if torch.cuda.is_current_stream_capturing():

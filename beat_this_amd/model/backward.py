@@ -15,7 +15,8 @@ hands out the streams.
 
 The frontend (the lower part of this file): ``StemFn``, ``ConvUnitFn``, ``SwapFn`` and ``ProjectionFn`` over
 bt_front_forward / bt_front_backward (csrc/train_front.hip), composed by ``frontend_train`` with ``AttentionFn`` /
-``FeedForwardFn`` for the twelve leaves of the partial transformers; BatchNorm on its running statistics, no dropout; fp32, or
+``FeedForwardFn`` for the twelve leaves of the partial transformers; BatchNorm on its running statistics; dropout in the leaves
+alone and only when ``BeatThis.enable_dropout(frontend=True)`` opted in (section 21: ``partial_ft`` takes the ``drop`` values); fp32, or
 with ``BeatThis.set_frontend_precision("16-mixed")`` the conv units, the leaves and the projection take ``mixed`` (section 19).
 ``BeatThis.set_frontend_trainable`` decides whether it runs.  ``StemBatchFn`` / ``ConvUnitBatchFn`` (section 18, bt_front_bn_*)
 are the same two units on the statistics of the call's batch; their forward moves the running buffers in place
@@ -276,8 +277,8 @@ def head(node, x, sum_head: bool):
 
 
 # ---- the differentiable frontend (csrc/train_front.hip) -----------------------------------------------------
-# Activations are the library's (b, t, f, c), channels last, fp32.  BatchNorm runs on its running statistics, there is no
-# dropout, and the arithmetic is fp32 whatever the train precision says; ``mixed`` (BeatThis.set_frontend_precision) puts the conv
+# Activations are the library's (b, t, f, c), channels last, fp32.  BatchNorm runs on its running statistics, only the leaves
+# of the partial transformers can drop (section 21), and the arithmetic is fp32 whatever the train precision says; ``mixed`` (BeatThis.set_frontend_precision) puts the conv
 # units', the leaves' and the projection's matrix products on fp16 operands.
 def check_front_limits(B: int, T: int) -> None:
     """Raised before any launch: the frequency direction runs B T sequences, every unit B T 32 rows at the most."""
@@ -593,25 +594,39 @@ def conv_unit(block, x, batch_statistics=False, mixed=False):
     return ConvUnitFn.apply(x, block.conv2d.weight, *_bn(block.norm), mixed)
 
 
-def partial_ft(node, x, rope_for, mixed=False):
+def partial_ft(node, x, rope_for, mixed=False, drops=None):
     """PartialFTTransformer.forward (beat_tracker.py:290-301) on (b, t, f, c): attention and feed-forward over the frequency
     tokens of every frame, then over the time tokens of every bin -- the trunk's unit code with its residual on (B T, F, C) and
-    (B F, T, C), no dropout; fp32, or with ``mixed`` the 16-mixed unit calls.  ``rope_for(n)``: the rotary table for n tokens."""
+    (B F, T, C); fp32, or with ``mixed`` the 16-mixed unit calls.  ``rope_for(n)``: the rotary table for n tokens.  ``drops``:
+    None (no dropout: the calls and launches as ever), four ``drop`` values -- None or (p, seed, stream) -- for attnF, ffF,
+    attnT, ffT, or a callable that yields the next one (asked once per leaf, in that order).  A frequency-direction leaf's mask
+    rows are (b T + t) F + f, a time-direction leaf's (b F + f) T + t (include/beat_this_amd.h)."""
+    if drops is None:
+        nxt = lambda: None
+    elif callable(drops):
+        nxt = drops
+    else:
+        four = list(drops)
+        if len(four) != 4:
+            raise ValueError(f"a partial transformer has four leaves (attnF, ffF, attnT, ffT), got {len(four)} drop values")
+        nxt = iter(four).__next__
     B, T, F, Cc = x.shape
     y = x.reshape(B * T, F, Cc)
-    y = attention(node.attnF, y, *rope_for(F), mixed=mixed, residual=True)
-    y = feedforward(node.ffF, y, mixed=mixed, residual=True)
+    y = attention(node.attnF, y, *rope_for(F), drop=nxt(), mixed=mixed, residual=True)
+    y = feedforward(node.ffF, y, drop=nxt(), mixed=mixed, residual=True)
     y = SwapFn.apply(y.reshape(B, T, F, Cc)).reshape(B * F, T, Cc)
-    y = attention(node.attnT, y, *rope_for(T), mixed=mixed, residual=True)
-    y = feedforward(node.ffT, y, mixed=mixed, residual=True)
+    y = attention(node.attnT, y, *rope_for(T), drop=nxt(), mixed=mixed, residual=True)
+    y = feedforward(node.ffT, y, drop=nxt(), mixed=mixed, residual=True)
     return SwapFn.apply(y.reshape(B, F, T, Cc))
 
 
-def frontend_train(model, x, batch_statistics=False, mixed=None):
+def frontend_train(model, x, batch_statistics=False, mixed=None, drops=None):
     """``BeatThis.frontend`` on the differentiable route, in the reference's order (beat_tracker.py:54-80, 290-301): stem, three
     times (partial transformer, conv unit), projection.  (B, T, 128) -> (B, T, D).  ``batch_statistics``: the five BatchNorms
     normalise with this call's batch and move their running buffers (section 18).  ``mixed``: the conv units, the leaves and the
-    projection on fp16 operands (section 19); None reads ``model.frontend_precision``.  The stem is fp32 either way."""
+    projection on fp16 operands (section 19); None reads ``model.frontend_precision``.  The stem is fp32 either way.  ``drops``:
+    None, or a callable that yields the ``drop`` of the next leaf call (section 21: ``BeatThis`` hands out the streams in forward
+    order); the stem, the conv units and the projection never drop."""
     if mixed is None:
         mixed = model.frontend_precision == "16-mixed"
     fr = model.frontend
@@ -621,6 +636,6 @@ def frontend_train(model, x, batch_statistics=False, mixed=None):
     h = stem(fr.stem, x, batch_statistics)
     for blk in fr.blocks:
         if "partial" in blk._modules:
-            h = partial_ft(blk.partial, h, model._rope, mixed)
+            h = partial_ft(blk.partial, h, model._rope, mixed, drops)
         h = conv_unit(blk, h, batch_statistics, mixed)
     return ProjectionFn.apply(h, fr.linear.weight, fr.linear.bias, mixed)

@@ -42,14 +42,17 @@ class PLBeatThis(nn.Module):
     """The model and everything a training run needs around it.
 
     The frontend is frozen unless ``train_frontend=True`` (``BeatThis.set_frontend_trainable``: whole-model fine-tuning with
-    frozen BatchNorm statistics, no frontend dropout, fp32 frontend arithmetic; ``batch_statistics=True`` on top of it makes the
+    frozen BatchNorm statistics, no frontend dropout unless ``apply_frontend_dropout``, fp32 frontend arithmetic; ``batch_statistics=True`` on top of it makes the
     frontend's BatchNorms torch's training-mode ones, ``BeatThis.set_batch_statistics``, and ``fit`` then trains in ``train()``
     mode: what training from scratch needs; no hyper-parameter either); the six main layers, the final RMSNorm and the
     task heads are trainable.  ``dropout`` is stored in the hyper-parameters and handed to the model;
     ``apply_dropout=True`` enables it there under ``dropout_seed`` (``BeatThis.enable_dropout``), and ``fit`` then trains in
     ``train()`` mode: the main layers drop at ``dropout["transformer"]`` like the reference's, with this package's own masks;
-    ``dropout["frontend"]`` stays unused (frozen frontend) and the route is fp32.  The two switches are not hyper-parameters:
-    a checkpoint carries the reference's keys only.  ``precision`` ("32-true", the default, or "16-mixed": the reference's
+    ``apply_frontend_dropout=True`` on top of ``apply_dropout`` and ``train_frontend`` (``ValueError`` without either) is
+    ``BeatThis.enable_dropout(frontend=True)``: the twelve leaves of the frontend's partial transformers drop at
+    ``dropout["frontend"]`` too, the reference's full recipe; without it ``dropout["frontend"]`` stays unused.  ``init_seed``
+    seeds the initial weights of the new model (``BeatThis.init_weights``; 0 is what it always was).  These switches are not
+    hyper-parameters: a checkpoint carries the reference's keys only.  ``precision`` ("32-true", the default, or "16-mixed": the reference's
     trainer setting, ``BeatThis.set_train_precision``) is no hyper-parameter either; with "16-mixed" ``fit`` scales the loss
     (``beat_this_amd.optim.LossScaler``).  ``frontend_precision`` ("16-mixed" or "32-true"; None leaves the model's default,
     "32-true") is ``BeatThis.set_frontend_precision``: fp16 matrix products in the differentiable frontend, independent of
@@ -60,17 +63,23 @@ class PLBeatThis(nn.Module):
                  pos_weights={"beat": 1, "downbeat": 1}, head_dim=32, loss_type="shift_tolerant_weighted_bce",
                  warmup_steps=1000, max_epochs=100, use_dbn=False, eval_trim_beats=5, sum_head=True, partial_transformers=True,
                  apply_dropout=False, dropout_seed=0, precision="32-true", train_frontend=False,
-                 batch_statistics=False, frontend_precision=None):
+                 batch_statistics=False, frontend_precision=None, apply_frontend_dropout=False, init_seed=0):
         given = {k: v for k, v in locals().items()
                  if k not in ("self", "__class__", "apply_dropout", "dropout_seed", "precision", "train_frontend",
-                              "batch_statistics", "frontend_precision")}
+                              "batch_statistics", "frontend_precision", "apply_frontend_dropout", "init_seed")}
+        if apply_frontend_dropout and not apply_dropout:
+            raise ValueError("apply_frontend_dropout needs apply_dropout=True: the frontend's dropout is a second opt-in on top of it")
+        if apply_frontend_dropout and not train_frontend:
+            raise ValueError("apply_frontend_dropout needs train_frontend=True: only the differentiable frontend drops")
         super().__init__()
         hp = self.hyper_parameters = _plain(given)   # what a checkpoint carries: every constructor argument, as plain values
         for key in ("lr", "weight_decay", "fps", "warmup_steps", "max_epochs", "pos_weights", "eval_trim_beats"):
             setattr(self, key, hp[key])
         self.model = BeatThis(**{k: hp[k] for k in _MODEL_KEYS})
+        if int(init_seed) != 0:   # (0: the state a new BeatThis holds, to the bit)
+            self.model.init_weights(init_seed)
         if apply_dropout:
-            self.model.enable_dropout(seed=dropout_seed)
+            self.model.enable_dropout(seed=dropout_seed, frontend=bool(apply_frontend_dropout))
         self.model.set_train_precision(precision)
         if frontend_precision is not None:   # BeatThis.set_frontend_precision; no hyper-parameter, like precision
             self.model.set_frontend_precision(frontend_precision)

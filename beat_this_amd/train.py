@@ -5,7 +5,8 @@ step per accumulated batch group, validation with the package's own metrics ever
 ``python -m beat_this_amd.train`` is the command line around it.  Every step's arithmetic runs in the package's kernels: the
 differentiable route of ``BeatThis`` (fp32 or, with ``precision="16-mixed"``, fp16 matrix products under a dynamic loss scale;
 frozen frontend or, with ``train_frontend``, the whole model, its frontend in fp32 or with ``frontend_precision="16-mixed"`` on
-fp16 products too; dropout in the main layers when enabled), the losses, and the fused AdamW of ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
+fp16 products too; dropout in the main layers when enabled and, with ``frontend_dropout``, in the leaves of the frontend's
+partial transformers as well), the losses, and the fused AdamW of ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
 and ``load_model`` read as it is.
 
 Not offered: the reference's wandb logger, ``--compile`` and ``--force-flash-attention`` (nothing here is compiled by torch or
@@ -59,7 +60,7 @@ def save_checkpoint(path, pl_module, optimizer, scheduler, epoch: int, global_st
     """One file with the reference's (Lightning's) top-level keys: ``state_dict`` (``model.`` prefix), ``hyper_parameters``,
     ``optimizer_states`` and ``lr_schedulers`` (one entry each), ``epoch`` (the last finished one), ``global_step`` (optimiser
     steps so far) and ``rng`` (numpy's generator; with dropout enabled also ``rng["dropout"]`` = the model's
-    ``dropout_state()``); a 16-mixed run adds ``loss_scaler`` (the ``LossScaler``'s state).  Written next to ``path`` first and
+    ``dropout_state()``, which carries the frontend's opt-in when it is set); a 16-mixed run adds ``loss_scaler`` (the ``LossScaler``'s state).  Written next to ``path`` first and
     then moved over it."""
     ckpt = {"state_dict": _to_cpu(dict(pl_module.state_dict())), "hyper_parameters": dict(pl_module.hyper_parameters),
             "optimizer_states": [_to_cpu(optimizer.state_dict())], "lr_schedulers": [_to_cpu(scheduler.state_dict())],
@@ -92,7 +93,8 @@ def validate(pl_module, datamodule) -> dict:
 
 
 def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
-        resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None, frontend_precision=None) -> dict:
+        resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None, frontend_precision=None,
+        frontend_dropout=None) -> dict:
     """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
 
     Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
@@ -124,6 +126,11 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     buffers, every micro-batch on its own -- training from scratch.  The buffers travel in the ``state_dict``, so a checkpoint
     and ``resume`` need nothing new; ``resume`` needs the same setting.
 
+    ``frontend_dropout``: True / False sets the frontend's dropout opt-in of a model whose dropout is enabled
+    (``BeatThis.enable_dropout(frontend=True)``; None leaves it as it is), before the optimiser is built; the seed and the call
+    counter stay what they are.  True needs dropout enabled and a trainable frontend (``ValueError`` otherwise).  The opt-in
+    travels in ``rng["dropout"]`` of the checkpoint, and ``resume`` restores it with the counter.
+
     A module whose model has dropout enabled or uses batch statistics is put into ``train()`` mode here and stays in it; validation runs under
     ``no_grad`` on the inference path, which never drops.
 
@@ -139,6 +146,14 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
         pl_module.model.set_batch_statistics(batch_statistics)
     if frontend_precision is not None:
         pl_module.model.set_frontend_precision(frontend_precision)
+    if frontend_dropout is not None:
+        state = pl_module.model.dropout_state()
+        if frontend_dropout and state is None:
+            raise ValueError("frontend_dropout=True needs dropout enabled: PLBeatThis(apply_dropout=True) or model.enable_dropout()")
+        if frontend_dropout and not pl_module.model.frontend_trainable:
+            raise ValueError("frontend_dropout=True needs a trainable frontend: train_frontend=True")
+        if state is not None:
+            pl_module.model.set_dropout_state(dict(state, frontend=bool(frontend_dropout)))
     scaler = LossScaler() if "16-mixed" in (pl_module.model.train_precision, pl_module.model.frontend_precision) else None
     accumulate = int(accumulate_grad_batches)
     if accumulate < 1 or int(max_epochs) < 0 or int(val_frequency) < 1:
@@ -212,7 +227,8 @@ def get_parser() -> argparse.ArgumentParser:
     from .loss import LOSS_TYPES
 
     p = argparse.ArgumentParser(description="Fine-tune Beat This! on the MI355X kernels (frozen frontend unless --train-frontend, fp32 or --precision "
-                                            "16-mixed, dropout in the main transformer with --dropout).")
+                                            "16-mixed, dropout in the main transformer with --dropout, in the frontend too with "
+                                            "--apply-frontend-dropout).")
     toggle = argparse.BooleanOptionalAction
     p.add_argument("--data-dir", type=str, required=True, help="data folder: annotations/ and the spectrogram bundles")
     p.add_argument("--checkpoint", type=str, default=None,
@@ -234,12 +250,18 @@ def get_parser() -> argparse.ArgumentParser:
                    help="train the main transformer layers with dropout, seeded by --seed (default: off)")
     p.add_argument("--transformer-dropout", metavar="RATE", type=float, default=None,
                    help="dropout rate of the main transformer layers, 0 <= RATE < 1 (default: the checkpoint's, or 0.2 for a new model)")
+    p.add_argument("--frontend-dropout", metavar="RATE", type=float, default=None,
+                   help="dropout rate of the frontend's partial transformers, 0 <= RATE < 1; used with --apply-frontend-dropout "
+                        "(default: the checkpoint's, or 0.1 for a new model)")
+    p.add_argument("--apply-frontend-dropout", default=False, action=toggle,
+                   help="with --dropout and --train-frontend: the attention / feed-forward leaves of the frontend's partial "
+                        "transformers drop too, at --frontend-dropout (default: off)")
     p.add_argument("--precision", type=str, default="32-true", choices=["32-true", "16-mixed"],
                    help="16-mixed: the reference's training precision -- fp16 matrix products in the main layers, fp32 master "
                         "weights, a dynamic loss scale (default: %(default)s)")
     p.add_argument("--train-frontend", default=False, action=toggle,
-                   help="whole-model fine-tuning: also train the frontend (frozen BatchNorm statistics, no frontend dropout, "
-                        "fp32 frontend unless --frontend-precision 16-mixed; default: the frontend stays frozen)")
+                   help="whole-model fine-tuning: also train the frontend (frozen BatchNorm statistics unless --batch-statistics, "
+                        "no frontend dropout unless --apply-frontend-dropout, fp32 frontend unless --frontend-precision 16-mixed; default: the frontend stays frozen)")
     p.add_argument("--frontend-precision", type=str, default="32-true", choices=["32-true", "16-mixed"],
                    help="with --train-frontend: 16-mixed runs the matrix products of the frontend's conv units, partial "
                         "transformers and projection on fp16 operands too, under the same loss scale (default: %(default)s)")
@@ -260,6 +282,8 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--hung-data", default=False, action=toggle, help="train on the datasets of Hung et al. only")
     p.add_argument("--fold", type=int, default=None, help="the cross-validation fold NOT to train on (0-based)")
     p.add_argument("--seed", type=int, default=0, help="seed of the random number generators")
+    p.add_argument("--init-seed", metavar="N", type=int, default=0,
+                   help="seed of a new model's initial weights; unused with --checkpoint or --resume-checkpoint (default: %(default)s)")
     p.add_argument("--resume-checkpoint", type=str, default=None, help="continue the run that wrote this checkpoint")
     return p
 
@@ -271,6 +295,10 @@ def main(argv=None) -> int:
         parser.error("--batch-statistics needs --train-frontend: batch statistics belong to the differentiable frontend")
     if args.frontend_precision != "32-true" and not args.train_frontend:
         parser.error("--frontend-precision needs --train-frontend: it belongs to the differentiable frontend")
+    if args.apply_frontend_dropout and not args.dropout:
+        parser.error("--apply-frontend-dropout needs --dropout: the frontend's dropout is a second opt-in on top of it")
+    if args.apply_frontend_dropout and not args.train_frontend:
+        parser.error("--apply-frontend-dropout needs --train-frontend: only the differentiable frontend drops")
     from .dataset import BeatDataModule
     from .inference import load_checkpoint
     from .model.pl_module import PLBeatThis
@@ -298,11 +326,14 @@ def main(argv=None) -> int:
         arch = {k: ckpt["hyper_parameters"][k] for k in keys if k in ckpt["hyper_parameters"]}
     if args.transformer_dropout is not None:
         arch["dropout"] = dict(arch.get("dropout", {"frontend": 0.1}), transformer=args.transformer_dropout)
+    if args.frontend_dropout is not None:
+        arch["dropout"] = dict(arch.get("dropout", {"transformer": 0.2}), frontend=args.frontend_dropout)
     pl_module = PLBeatThis(**arch, apply_dropout=args.dropout, dropout_seed=args.seed, fps=FPS, lr=args.lr,
                            weight_decay=args.weight_decay, pos_weights=pos_weights, loss_type=args.loss,
                            warmup_steps=args.warmup_steps, max_epochs=args.max_epochs, use_dbn=args.dbn,
                            eval_trim_beats=args.eval_trim_beats, precision=args.precision, train_frontend=args.train_frontend,
-                           batch_statistics=args.batch_statistics, frontend_precision=args.frontend_precision)
+                           batch_statistics=args.batch_statistics, frontend_precision=args.frontend_precision,
+                           apply_frontend_dropout=args.apply_frontend_dropout, init_seed=0 if ckpt is not None else args.init_seed)
     if ckpt is not None and not args.resume_checkpoint:   # (a resumed run's weights are restored by fit() with the rest)
         pl_module.load_state_dict(ckpt["state_dict"])
     pl_module.to(device)

@@ -662,7 +662,22 @@ int bt_train_backward(void* stream, int unit, const bt_train_args* a);
  * unit share the stream and differ in the site).  With dropout the attention keeps its normaliser over every key, adds p v for
  * the kept (q, k) pairs only and stores save_o = the dropped output (before the gate); save_lse is unchanged.  The backward with
  * p > 0 needs bt_train_workspace_bytes_dropout (one more [B T, dim] region: the masked upstream gradient); the forward's
- * workspace is the same as without. */
+ * workspace is the same as without.
+ * THE LEAVES OF THE FRONTEND.  The twelve attention / feed-forward leaves of the three partial
+ * transformers are these unit calls with residual != 0 on the rows of the (b, t, f, c) activation, B sequences of T frames, F
+ * frequency bins, C channels ((F, C) = (32, 32), (16, 64), (8, 128) in blocks 0, 1, 2), and their (B, T) above mean:
+ *   a frequency-direction leaf (attnF, ffF):  B' = B T, T' = F;  the row of token f of frame t of sequence b is (b T + t) F + f,
+ *                                             sequence b' = b T + t, query / key index f
+ *   a time-direction leaf (attnT, ffT):       B' = B F, T' = T;  the row of frame t of bin f of sequence b is (b F + f) T + t,
+ *                                             sequence b' = b F + f, query / key index t
+ * Sites, groups and words are exactly the ones above over (B', T', dim = C, hidden = ff_mult C, H = C / 32), so
+ * bt_dropout_mask_host(dropout, site, B', T', C, hidden, out) gives a leaf's masks.  The streams of a whole-model forward that
+ * drops in both parts, from the caller's counter n: block 0's attnF, ffF, attnT, ffT take n .. n + 3, block 1's n + 4 .. n + 7,
+ * block 2's n + 8 .. n + 11, then the trunk's layer l takes n + 12 + 2 l (attention) and n + 13 + 2 l (feed-forward); a part
+ * whose rate is 0, or that is not opted in, takes no number (a model without partial transformers has no leaves).  The rate
+ * of the leaves is the caller's own (BeatThis: dropout["frontend"]) and may differ from the trunk's.  Dropout adds no limit:
+ * every group index is 64-bit and the launches are the ones without dropout, so B' is bounded as ever by the 65535 sequences
+ * of a grid (the frontend's route refuses B T > 65535 before any launch) and B' T' by 2^22 rows. */
 #define BT_DROP_ATTN_P 0
 #define BT_DROP_ATTN_OUT 1
 #define BT_DROP_FF_HIDDEN 2
