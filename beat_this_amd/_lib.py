@@ -310,6 +310,11 @@ EXPORTS = {
     "bt_grad_norm_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]),
     "bt_adamw_step_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.POINTER(OptimHyper), C.c_void_p]),
+    "bt_adamw_ema_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int64, C.POINTER(OptimHyper), C.c_void_p, C.c_float, C.c_int]),
+    "bt_ema_exchange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "bt_adamw_ema_step_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.POINTER(OptimHyper), C.c_void_p, C.c_float, C.c_int]),
     "bt_stretch_out_len": (C.c_int64, [C.c_int64, C.c_double]),
     "bt_stretch_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_double]),
     "bt_stretch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p,

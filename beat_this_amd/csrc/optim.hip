@@ -14,9 +14,12 @@
 // (thread p adds the squares of its float4s k * 256 + p, k ascending, x y z w in turn; then a 256-leaf tree); launch 2, one
 // workgroup, adds the slices in index order and writes {norm, coef}.  No atomics, no memsets, no allocation; every sum's order
 // depends on the layout alone, so a step is bitwise reproducible.
-// Host: bt_adamw_step_host / bt_grad_norm_host repeat the same operations in the same order.  The file is compiled with
-// -ffp-contract=off, with hipcc's correctly rounded fp32 divide and square root and without flushing denormals, so the device
-// and the host agree bit for bit.
+// Weight averaging: bt_adamw_ema_step is the same pass with a fourth flat buffer.  The thread that has
+// computed an element's new p also moves that element's average, e = p on a copying step and e = e + (p - e) * w otherwise;
+// bt_ema_exchange swaps p and e over the same chunk table.  adamw_kernel<false> is the plain step, its body as before.
+// Host: bt_adamw_step_host / bt_adamw_ema_step_host / bt_grad_norm_host repeat the same operations in the same order.  The
+// file is compiled with -ffp-contract=off, with hipcc's correctly rounded fp32 divide and square root and without flushing
+// denormals, so the device and the host agree bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -47,6 +50,9 @@ __host__ __device__ inline void adamw_one(float& p, float& m, float& v, float gr
   p = p - h.step_size * (m / denom);
 }
 
+// the running average of an element, after adamw_one has made its new p (torch's get_ema_multi_avg_fn: lerp(e, p, 1 - decay))
+__host__ __device__ inline void ema_one(float& e, float p, float w) { e = e + (p - e) * w; }
+
 __host__ __device__ inline void square_into(double& acc, float x) {
   const double d = (double)x;
   acc += d * d;
@@ -66,10 +72,13 @@ __host__ __device__ inline bool tensor_ok(const bt_optim_tensor& t, int n_groups
 }
 
 // ---- device ------------------------------------------------------------------------------------------------------------------
+// EMA: the pass also keeps the average of every element it updates (ema, ema_weight, ema_copy); without it they are unused
+template <bool EMA>
 __global__ __launch_bounds__(THREADS) void adamw_kernel(const bt_optim_tensor* __restrict__ tensors, int n_tensors,
                                                         const bt_optim_chunk* __restrict__ chunks, float* __restrict__ grad,
                                                         float* __restrict__ m, float* __restrict__ v, int64_t total,
-                                                        bt_optim_hyper h, const float* __restrict__ coef) {
+                                                        bt_optim_hyper h, const float* __restrict__ coef,
+                                                        float* __restrict__ ema, float ema_weight, int ema_copy) {
   const bt_optim_chunk c = chunks[blockIdx.x];
   if (c.tensor < 0 || c.tensor >= n_tensors || c.chunk < 0) return;   // (a damaged table updates nothing, never outside)
   const bt_optim_tensor t = tensors[c.tensor];
@@ -83,6 +92,8 @@ __global__ __launch_bounds__(THREADS) void adamw_kernel(const bt_optim_tensor* _
   float* G = grad + f;
   float* M = m + f;
   float* V = v + f;
+  float* E = EMA ? ema + f : nullptr;
+  const bool copy = ema_copy != 0;   // (the first averaged step: e = p, the old e is not read)
   const bool zero = h.zero_grads != 0;
   const int p = threadIdx.x;
   const bool wide = ((uintptr_t)t.param & 15) == 0;   // (begin is a multiple of 4: the chunk is aligned like the tensor)
@@ -95,6 +106,8 @@ __global__ __launch_bounds__(THREADS) void adamw_kernel(const bt_optim_tensor* _
         float4 pp = ((const float4*)P)[i];
         const float4 gg = ((const float4*)G)[i];
         float4 mm = ((const float4*)M)[i], vv = ((const float4*)V)[i];
+        float4 ee;
+        if (EMA && !copy) ee = ((const float4*)E)[i];
         adamw_one(pp.x, mm.x, vv.x, gg.x, gs, hg);
         adamw_one(pp.y, mm.y, vv.y, gg.y, gs, hg);
         adamw_one(pp.z, mm.z, vv.z, gg.z, gs, hg);
@@ -103,6 +116,17 @@ __global__ __launch_bounds__(THREADS) void adamw_kernel(const bt_optim_tensor* _
         ((float4*)M)[i] = mm;
         ((float4*)V)[i] = vv;
         if (zero) ((float4*)G)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (EMA) {
+          if (copy) {
+            ee = pp;
+          } else {
+            ema_one(ee.x, pp.x, ema_weight);
+            ema_one(ee.y, pp.y, ema_weight);
+            ema_one(ee.z, pp.z, ema_weight);
+            ema_one(ee.w, pp.w, ema_weight);
+          }
+          ((float4*)E)[i] = ee;
+        }
       }
     }
   }
@@ -113,6 +137,48 @@ __global__ __launch_bounds__(THREADS) void adamw_kernel(const bt_optim_tensor* _
     M[i] = mm;
     V[i] = vv;
     if (zero) G[i] = 0.0f;
+    if (EMA) {
+      float ee = pp;
+      if (!copy) {
+        ee = E[i];
+        ema_one(ee, pp, ema_weight);
+      }
+      E[i] = ee;
+    }
+  }
+}
+
+// p <-> e over the chunk table of the step: a pure move, the same three access paths.  The group of a tensor plays no part
+// here, so its index is only held to the ABI's range (BT_OPTIM_MAX_GROUPS), not to a step's n_groups.
+__global__ __launch_bounds__(THREADS) void ema_exchange_kernel(const bt_optim_tensor* __restrict__ tensors, int n_tensors,
+                                                               const bt_optim_chunk* __restrict__ chunks, float* __restrict__ ema,
+                                                               int64_t total) {
+  const bt_optim_chunk c = chunks[blockIdx.x];
+  if (c.tensor < 0 || c.tensor >= n_tensors || c.chunk < 0) return;
+  const bt_optim_tensor t = tensors[c.tensor];
+  const int64_t begin = (int64_t)c.chunk * CHUNK;
+  if (!tensor_ok(t, BT_OPTIM_MAX_GROUPS, total) || begin >= t.numel) return;
+  const int n = (int)(t.numel - begin < CHUNK ? t.numel - begin : CHUNK);
+  float* P = t.param + begin;
+  float* E = ema + t.offset + begin;
+  const int p = threadIdx.x;
+  const bool wide = ((uintptr_t)t.param & 15) == 0;
+  const int n4 = n >> 2;
+  if (wide) {
+#pragma unroll
+    for (int k = 0; k < CHUNK / (4 * THREADS); ++k) {
+      const int i = k * THREADS + p;
+      if (i < n4) {
+        const float4 pp = ((const float4*)P)[i], ee = ((const float4*)E)[i];
+        ((float4*)P)[i] = ee;
+        ((float4*)E)[i] = pp;
+      }
+    }
+  }
+  for (int i = (wide ? 4 * n4 : 0) + p; i < n; i += THREADS) {
+    const float pp = P[i], ee = E[i];
+    P[i] = ee;
+    E[i] = pp;
   }
 }
 
@@ -187,6 +253,72 @@ double slice_sum_host(const float* grad, int64_t base, int64_t total) {
   for (int s = THREADS / 2; s > 0; s >>= 1)
     for (int p = 0; p < s; ++p) red[p] += red[p + s];
   return red[0];
+}
+
+const char* WEIGHT_ERROR = "ema_weight = 1 - decay must be a number in (0, 1]";
+bool weight_ok(float w) { return w > 0.0f && w <= 1.0f; }   // (a NaN fails both comparisons)
+
+// bt_adamw_step and bt_adamw_ema_step: the refusals, then one launch
+int adamw_launch(const char* fn, bool with_ema, void* stream, const bt_optim_tensor* d_tensors, int n_tensors,
+                 const bt_optim_chunk* d_chunks, int64_t n_chunks, float* d_grad, float* d_m, float* d_v, float* d_ema, int64_t total,
+                 const bt_optim_hyper* hyper, const float* d_coef, float ema_weight, int ema_copy) {
+  if (const char* e = hyper_error(hyper)) return err(fn, e);
+  if (with_ema && !weight_ok(ema_weight)) return err(fn, WEIGHT_ERROR);
+  if (n_tensors < 0 || n_chunks < 0 || n_chunks > 0x7fffffff || total < 0 || (total & 3))
+    return err(fn, "negative count, or a flat length that is no multiple of 4");
+  if (n_chunks == 0) return BT_OK;
+  if (!d_tensors || !d_chunks || !d_grad || !d_m || !d_v || (with_ema && !d_ema)) return err(fn, "null pointer");
+  if (((uintptr_t)d_grad | (uintptr_t)d_m | (uintptr_t)d_v | (uintptr_t)d_ema) & 15) return err(fn, "a flat buffer is not 16-byte aligned");
+  if ((uintptr_t)d_coef & 3) return err(fn, "the coefficient pointer is not 4-byte aligned");
+  const dim3 grid((unsigned)n_chunks), block(THREADS);
+  if (with_ema)
+    hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, (hipStream_t)stream, d_tensors, n_tensors, d_chunks, d_grad, d_m, d_v, total,
+                       *hyper, d_coef, d_ema, ema_weight, ema_copy);
+  else
+    hipLaunchKernelGGL(adamw_kernel<false>, grid, block, 0, (hipStream_t)stream, d_tensors, n_tensors, d_chunks, d_grad, d_m, d_v, total,
+                       *hyper, d_coef, (float*)nullptr, 0.0f, 0);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return bt_set_error_external(BT_ERR_HIP, (std::string(fn) + ": " + hipGetErrorString(e)).c_str());
+  return BT_OK;
+}
+
+// the host twins: the tables are validated entry by entry, then the chunks in table order
+int adamw_host(const char* fn, bool with_ema, const bt_optim_tensor* tensors, int n_tensors, const bt_optim_chunk* chunks,
+               int64_t n_chunks, float* grad, float* m, float* v, float* ema, int64_t total, const bt_optim_hyper* hyper,
+               const float* coef, float ema_weight, int ema_copy) {
+  if (const char* e = hyper_error(hyper)) return err(fn, e);
+  if (with_ema && !weight_ok(ema_weight)) return err(fn, WEIGHT_ERROR);
+  if (n_tensors < 0 || n_chunks < 0 || total < 0 || (total & 3)) return err(fn, "negative count, or a flat length that is no multiple of 4");
+  if (n_chunks == 0) return BT_OK;
+  if (!tensors || !chunks || !grad || !m || !v || (with_ema && !ema)) return err(fn, "null pointer");
+  if (((uintptr_t)grad | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) return err(fn, "a flat buffer is not 16-byte aligned");
+  for (int i = 0; i < n_tensors; ++i)
+    if (!tensor_ok(tensors[i], hyper->n_groups, total))
+      return err(fn, "tensor " + std::to_string(i) + ": numel < 0, a null or misaligned pointer, a group index out of range or a "
+                     "range outside the flat buffers");
+  for (int64_t c = 0; c < n_chunks; ++c)
+    if (chunks[c].tensor < 0 || chunks[c].tensor >= n_tensors || chunks[c].chunk < 0 ||
+        (int64_t)chunks[c].chunk * CHUNK >= tensors[chunks[c].tensor].numel)
+      return err(fn, "chunk " + std::to_string(c) + " points outside its tensor");
+  const float gs = coef ? hyper->grad_scale * coef[0] : hyper->grad_scale;
+  for (int64_t c = 0; c < n_chunks; ++c) {
+    const bt_optim_tensor& t = tensors[chunks[c].tensor];
+    const bt_optim_group& hg = hyper->g[t.group];
+    const int64_t begin = (int64_t)chunks[c].chunk * CHUNK;
+    const int64_t n = t.numel - begin < CHUNK ? t.numel - begin : CHUNK;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t f = t.offset + begin + i;
+      adamw_one(t.param[begin + i], m[f], v[f], grad[f], gs, hg);
+      if (hyper->zero_grads) grad[f] = 0.0f;
+      if (with_ema) {
+        if (ema_copy)
+          ema[f] = t.param[begin + i];
+        else
+          ema_one(ema[f], t.param[begin + i], ema_weight);
+      }
+    }
+  }
+  return BT_OK;
 }
 
 }  // namespace
@@ -266,16 +398,27 @@ int bt_grad_norm(void* stream, const float* d_grad, int64_t total, float grad_sc
 
 int bt_adamw_step(void* stream, const bt_optim_tensor* d_tensors, int n_tensors, const bt_optim_chunk* d_chunks, int64_t n_chunks,
                   float* d_grad, float* d_m, float* d_v, int64_t total, const bt_optim_hyper* hyper, const float* d_coef) {
-  const char* fn = "bt_adamw_step";
-  if (const char* e = hyper_error(hyper)) return err(fn, e);
+  return adamw_launch("bt_adamw_step", false, stream, d_tensors, n_tensors, d_chunks, n_chunks, d_grad, d_m, d_v, nullptr, total, hyper,
+                      d_coef, 0.0f, 0);
+}
+
+int bt_adamw_ema_step(void* stream, const bt_optim_tensor* d_tensors, int n_tensors, const bt_optim_chunk* d_chunks, int64_t n_chunks,
+                      float* d_grad, float* d_m, float* d_v, float* d_ema, int64_t total, const bt_optim_hyper* hyper,
+                      const float* d_coef, float ema_weight, int ema_copy) {
+  return adamw_launch("bt_adamw_ema_step", true, stream, d_tensors, n_tensors, d_chunks, n_chunks, d_grad, d_m, d_v, d_ema, total, hyper,
+                      d_coef, ema_weight, ema_copy);
+}
+
+int bt_ema_exchange(void* stream, const bt_optim_tensor* d_tensors, int n_tensors, const bt_optim_chunk* d_chunks, int64_t n_chunks,
+                    float* d_ema, int64_t total) {
+  const char* fn = "bt_ema_exchange";
   if (n_tensors < 0 || n_chunks < 0 || n_chunks > 0x7fffffff || total < 0 || (total & 3))
     return err(fn, "negative count, or a flat length that is no multiple of 4");
   if (n_chunks == 0) return BT_OK;
-  if (!d_tensors || !d_chunks || !d_grad || !d_m || !d_v) return err(fn, "null pointer");
-  if (((uintptr_t)d_grad | (uintptr_t)d_m | (uintptr_t)d_v) & 15) return err(fn, "a flat buffer is not 16-byte aligned");
-  if ((uintptr_t)d_coef & 3) return err(fn, "the coefficient pointer is not 4-byte aligned");
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)n_chunks), dim3(THREADS), 0, (hipStream_t)stream, d_tensors, n_tensors, d_chunks,
-                     d_grad, d_m, d_v, total, *hyper, d_coef);
+  if (!d_tensors || !d_chunks || !d_ema) return err(fn, "null pointer");
+  if ((uintptr_t)d_ema & 15) return err(fn, "the flat buffer of the averages is not 16-byte aligned");
+  hipLaunchKernelGGL(ema_exchange_kernel, dim3((unsigned)n_chunks), dim3(THREADS), 0, (hipStream_t)stream, d_tensors, n_tensors,
+                     d_chunks, d_ema, total);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return bt_set_error_external(BT_ERR_HIP, (std::string(fn) + ": " + hipGetErrorString(e)).c_str());
   return BT_OK;
@@ -293,33 +436,14 @@ int bt_grad_norm_host(const float* grad, int64_t total, float grad_scale, float 
 
 int bt_adamw_step_host(const bt_optim_tensor* tensors, int n_tensors, const bt_optim_chunk* chunks, int64_t n_chunks, float* grad,
                        float* m, float* v, int64_t total, const bt_optim_hyper* hyper, const float* coef) {
-  const char* fn = "bt_adamw_step_host";
-  if (const char* e = hyper_error(hyper)) return err(fn, e);
-  if (n_tensors < 0 || n_chunks < 0 || total < 0 || (total & 3)) return err(fn, "negative count, or a flat length that is no multiple of 4");
-  if (n_chunks == 0) return BT_OK;
-  if (!tensors || !chunks || !grad || !m || !v) return err(fn, "null pointer");
-  if (((uintptr_t)grad | (uintptr_t)m | (uintptr_t)v) & 15) return err(fn, "a flat buffer is not 16-byte aligned");
-  for (int i = 0; i < n_tensors; ++i)
-    if (!tensor_ok(tensors[i], hyper->n_groups, total))
-      return err(fn, "tensor " + std::to_string(i) + ": numel < 0, a null or misaligned pointer, a group index out of range or a "
-                     "range outside the flat buffers");
-  for (int64_t c = 0; c < n_chunks; ++c)
-    if (chunks[c].tensor < 0 || chunks[c].tensor >= n_tensors || chunks[c].chunk < 0 ||
-        (int64_t)chunks[c].chunk * CHUNK >= tensors[chunks[c].tensor].numel)
-      return err(fn, "chunk " + std::to_string(c) + " points outside its tensor");
-  const float gs = coef ? hyper->grad_scale * coef[0] : hyper->grad_scale;
-  for (int64_t c = 0; c < n_chunks; ++c) {
-    const bt_optim_tensor& t = tensors[chunks[c].tensor];
-    const bt_optim_group& hg = hyper->g[t.group];
-    const int64_t begin = (int64_t)chunks[c].chunk * CHUNK;
-    const int64_t n = t.numel - begin < CHUNK ? t.numel - begin : CHUNK;
-    for (int64_t i = 0; i < n; ++i) {
-      const int64_t f = t.offset + begin + i;
-      adamw_one(t.param[begin + i], m[f], v[f], grad[f], gs, hg);
-      if (hyper->zero_grads) grad[f] = 0.0f;
-    }
-  }
-  return BT_OK;
+  return adamw_host("bt_adamw_step_host", false, tensors, n_tensors, chunks, n_chunks, grad, m, v, nullptr, total, hyper, coef, 0.0f, 0);
+}
+
+int bt_adamw_ema_step_host(const bt_optim_tensor* tensors, int n_tensors, const bt_optim_chunk* chunks, int64_t n_chunks, float* grad,
+                           float* m, float* v, float* ema, int64_t total, const bt_optim_hyper* hyper, const float* coef,
+                           float ema_weight, int ema_copy) {
+  return adamw_host("bt_adamw_ema_step_host", true, tensors, n_tensors, chunks, n_chunks, grad, m, v, ema, total, hyper, coef, ema_weight,
+                    ema_copy);
 }
 
 }  // extern "C"

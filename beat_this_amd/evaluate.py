@@ -2,7 +2,7 @@
 (README "Reproducing metrics from the paper") without Lightning, pandas or mir_eval.
 
     python -m beat_this_amd.evaluate --models final0.ckpt --bundle data/audio/spectrograms/gtzan.npz \\
-        --annotations data/annotations [--dbn] [--eval-trim-beats 5] [--loss] [--dump-predictions preds.npz]
+        --annotations data/annotations [--dbn] [--eval-trim-beats 5] [--loss] [--ema] [--dump-predictions preds.npz]
 
 Each bundle is one dataset (its file stem, e.g. ``gtzan``), holding ``<stem>/track`` spectrograms as the reference's
 preprocessing writes them; the beats of piece ``<stem>`` are read from ``<annotations>/<dataset>/annotations/beats/<stem>.beats``
@@ -192,6 +192,8 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--loss", default=False, action=argparse.BooleanOptionalAction,
                    help="also report the checkpoint's test loss (loss_beat, loss_downbeat, loss_total; its loss_type and "
                         "pos_weights) as the reference's test step logs it")
+    p.add_argument("--ema", default=False, action=argparse.BooleanOptionalAction,
+                   help="score the averaged weights of each checkpoint (its ema_state_dict, written by a run with --ema-decay)")
     p.add_argument("--dump-predictions", metavar="FILENAME", type=str, default=None,
                    help="file to write predictions to, in .npz format (optional; single model only)")
     return p
@@ -204,10 +206,13 @@ def main(argv=None) -> int:
               names=args.names)
     if args.loss:
         kw["loss"] = True
+    checkpoint = lambda path: path
+    if args.ema:   # (the averaged weights of each file: its ema_state_dict in the place of its state_dict)
+        from .inference import averaged_checkpoint as checkpoint
     if len(args.models) == 1:
-        print("Single model prediction for", args.models[0])
+        print("Single model prediction for", args.models[0] + (" (averaged weights)" if args.ema else ""))
         print("Computing predictions ...")
-        res = evaluate_bundle(args.models[0], args.bundle, args.annotations, **kw)
+        res = evaluate_bundle(checkpoint(args.models[0]), args.bundle, args.annotations, **kw)
         print("Metrics")
         for k, v in res["averaged"].items():
             print(f"{k}: {v}")
@@ -226,7 +231,7 @@ def main(argv=None) -> int:
     all_metrics = []
     for ckpt in args.models:
         print("Computing predictions ...")
-        all_metrics.append(evaluate_bundle(ckpt, args.bundle, args.annotations, **kw)["averaged"])
+        all_metrics.append(evaluate_bundle(checkpoint(ckpt), args.bundle, args.annotations, **kw)["averaged"])
     print("Metrics")
     for k in all_metrics[0]:
         vals = [m[k] for m in all_metrics]

@@ -74,6 +74,18 @@ def load_checkpoint(checkpoint_path, device="cpu") -> dict:
             raise ValueError("Could not load the checkpoint given the provided name", checkpoint_path)
 
 
+def averaged_checkpoint(ckpt) -> dict:
+    """A checkpoint of a run with weight averaging (``fit(ema_decay=...)``) -> a checkpoint dict whose ``state_dict`` is the
+    averaged one (``ema_state_dict``: the averaged parameters, the live buffers), for ``load_model``, the inference classes and
+    ``evaluate``.  ``ckpt``: a loaded dict, or what ``load_checkpoint`` takes.  The other entries are shared with the input."""
+    ckpt = ckpt if isinstance(ckpt, dict) else load_checkpoint(ckpt, "cpu")
+    if "ema_state_dict" not in ckpt:
+        raise ValueError("the checkpoint has no 'ema_state_dict': it was not written by a run with weight averaging (ema_decay)")
+    out = {k: v for k, v in ckpt.items() if k != "ema_state_dict"}
+    out["state_dict"] = ckpt["ema_state_dict"]
+    return out
+
+
 def _gpu_device(device) -> torch.device:
     """The device argument of the inference classes: a ROCm GPU, or a clear error right away."""
     dev = torch.device("cuda" if device is None else device)

@@ -1,14 +1,18 @@
 """The optimiser side of fine-tuning: ``AdamW`` (torch.optim.AdamW's default semantics on csrc/optim.hip: one launch for all
 tensors, the global gradient norm and its clip coefficient in two more, nothing read back), ``CosineWarmupScheduler`` (the
 reference's schedule, pl_module.py:342-369) and ``param_groups_for`` (its grouping, pl_module.py:283-296).  DESIGN.md section 14.
-``adamw_step_host`` / ``grad_norm_host`` / ``plan`` expose the library's host twins and its planner on numpy arrays.
+``adamw_step_host`` / ``adamw_ema_step_host`` / ``grad_norm_host`` / ``plan`` expose the library's host twins and its planner on
+numpy arrays.  ``AdamW(ema_decay=...)`` keeps an exponential moving average of the weights in the pass of the step (DESIGN.md
+section 22).
 ``LossScaler`` is the dynamic loss scale of 16-mixed training with ``torch.amp.GradScaler``'s rule,
 ``scale_update`` that rule as a pure function.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
+import numbers
 
 import numpy as np
 import torch
@@ -70,6 +74,16 @@ def adamw_step_host(tensors, n_tensors, chunks, n_chunks, grad, m, v, h: _lib.Op
     c = None if coef is None else np.asarray([coef], np.float32)
     _lib.check(_lib.lib().bt_adamw_step_host(tensors, n_tensors, chunks, n_chunks, grad.ctypes.data, m.ctypes.data, v.ctypes.data,
                                              grad.size, C.byref(h), None if c is None else c.ctypes.data))
+
+
+def adamw_ema_step_host(tensors, n_tensors, chunks, n_chunks, grad, m, v, ema, h: _lib.OptimHyper, ema_weight, ema_copy,
+                        coef=None) -> None:
+    """bt_adamw_ema_step_host: ``adamw_step_host`` plus the flat fp32 array of the averages, ``ema_weight`` = 1 - decay (rounded
+    to fp32 once on the way in) and ``ema_copy`` (this step copies the new parameters instead of averaging)"""
+    c = None if coef is None else np.asarray([coef], np.float32)
+    _lib.check(_lib.lib().bt_adamw_ema_step_host(tensors, n_tensors, chunks, n_chunks, grad.ctypes.data, m.ctypes.data, v.ctypes.data,
+                                                 ema.ctypes.data, grad.size, C.byref(h), None if c is None else c.ctypes.data,
+                                                 float(ema_weight), int(bool(ema_copy))))
 
 
 # ---- the loss scale of 16-mixed training ------------------------------------------------------------------------------------------
@@ -150,18 +164,32 @@ class AdamW(torch.optim.Optimizer):
     zero gradient).  A gradient that is no longer the optimiser's view -- ``model.zero_grad(set_to_none=True)`` followed by a
     backward pass, or an assigned tensor -- is copied into the flat buffer at the next step and the view is attached again.
 
+    ``ema_decay`` (a float in [0, 1); None: off, and nothing below exists): the optimiser also owns a fourth flat buffer, the
+    exponential moving average of the parameters with ``torch.optim.swa_utils.AveragedModel``'s semantics under
+    ``get_ema_multi_avg_fn(ema_decay)``: the first step taken copies the new parameters (``n_averaged`` 0 -> 1), every later one
+    does e = e + (p - e) * (1 - decay) in the pass that has just made p.  A step that the ``LossScaler`` skips leaves the
+    average and ``n_averaged`` as they are.  ``ema_parameters()`` are views of the averages; ``with opt.averaged_weights():``
+    exchanges parameters and averages in one launch on entry and again on exit, so that the model computes with the averaged
+    weights in between (``step()`` raises there).  The average travels in ``state_dict()`` under ``"ema"``; the decay is always the
+    constructor's.  BatchNorm buffers are not parameters and are not averaged.
+
     Capturing ``step()`` into a HIP graph is out of scope: the learning rate, the bias corrections and the other scalars travel
     to the kernel by value, so a replay would repeat one step's scalars.  ``state_dict()`` and ``load_state_dict()`` are this
     class's own (the state lives in the flat buffers, not in ``self.state``): torch's state-dict pre- and post-hooks are not run."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, accumulate=1):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, accumulate=1,
+                 ema_decay=None):
         if lr < 0 or eps < 0 or weight_decay < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1:
             raise ValueError(f"invalid AdamW settings: lr {lr}, betas {betas}, eps {eps}, weight_decay {weight_decay}")
         if int(accumulate) < 1:
             raise ValueError(f"accumulate must be a positive number of backward passes, got {accumulate}")
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError(f"max_grad_norm must be positive (or None), got {max_grad_norm}")
+        if ema_decay is not None and not (isinstance(ema_decay, numbers.Real) and not isinstance(ema_decay, bool)
+                                          and 0.0 <= ema_decay < 1.0):   # (numpy's scalars are numbers.Real too)
+            raise ValueError(f"ema_decay must be a float in [0, 1) (or None), got {ema_decay!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.accumulate = int(accumulate)
         if len(self.param_groups) > MAX_GROUPS:
@@ -188,6 +216,8 @@ class AdamW(torch.optim.Optimizer):
         self._grad = torch.zeros(self._total, dtype=torch.float32, device=dev)
         self._m = torch.zeros_like(self._grad)
         self._v = torch.zeros_like(self._grad)
+        self._ema = None if self.ema_decay is None else torch.zeros_like(self._grad)
+        self._n_averaged, self._exchanged = 0, False
         self._norm_ws = torch.empty(_lib.lib().bt_grad_norm_workspace_bytes(self._total), dtype=torch.uint8, device=dev)
         self._record = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)   # {norm, coef}
         self._views = [self._grad[o:o + p.numel()].view(p.shape) for o, p in zip(self._offsets, self._params)]
@@ -241,6 +271,8 @@ class AdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, *, accumulated=None, loss_scaler=None):
+        if self._exchanged:
+            raise RuntimeError("step() inside averaged_weights(): the parameters hold the averages there")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -270,9 +302,16 @@ class AdamW(torch.optim.Optimizer):
                     self.last_step_skipped = True
                     return loss
             self._t += 1
-            _lib.check(L.bt_adamw_step(stream, self._tables[0].data_ptr(), len(self._params), self._tables[1].data_ptr(),
-                                       self._n_chunks, self._grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), self._total,
-                                       C.byref(h), coef))
+            if self._ema is None:
+                _lib.check(L.bt_adamw_step(stream, self._tables[0].data_ptr(), len(self._params), self._tables[1].data_ptr(),
+                                           self._n_chunks, self._grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), self._total,
+                                           C.byref(h), coef))
+            else:   # (1 - decay in fp64; ctypes rounds it to fp32 once)
+                _lib.check(L.bt_adamw_ema_step(stream, self._tables[0].data_ptr(), len(self._params), self._tables[1].data_ptr(),
+                                               self._n_chunks, self._grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
+                                               self._ema.data_ptr(), self._total, C.byref(h), coef, 1.0 - self.ema_decay,
+                                               int(self._n_averaged == 0)))
+                self._n_averaged += 1
         # the kernel wrote the parameters behind autograd's back: bump their versions, so that BeatThis packs its inference
         # engine again and a graph that saved a parameter refuses a stale backward
         torch.autograd.graph.increment_version(self._params)
@@ -281,9 +320,49 @@ class AdamW(torch.optim.Optimizer):
     def flat_state(self) -> dict:
         """The optimiser's own buffers, not copies: ``grad``, ``exp_avg`` and ``exp_avg_sq`` (flat fp32 device tensors of
         ``total`` elements), ``offsets`` (where each parameter starts, in the order of ``param_groups``; multiples of 4, zero
-        padding in between) and ``step`` (the number of steps taken)."""
-        return dict(grad=self._grad, exp_avg=self._m, exp_avg_sq=self._v, offsets=list(self._offsets), total=self._total,
-                    step=self._t)
+        padding in between) and ``step`` (the number of steps taken).  With ``ema_decay`` also ``ema`` (the flat buffer of the
+        averages) and ``n_averaged``."""
+        st = dict(grad=self._grad, exp_avg=self._m, exp_avg_sq=self._v, offsets=list(self._offsets), total=self._total,
+                  step=self._t)
+        if self._ema is not None:
+            st.update(ema=self._ema, n_averaged=self._n_averaged)
+        return st
+
+    # -- weight averaging -----------------------------------------------------------------------------------------------------
+    def _need_ema(self, what: str) -> None:
+        if self._ema is None:
+            raise RuntimeError(f"{what} needs weight averaging: build the optimiser with ema_decay")
+
+    def ema_parameters(self) -> list:
+        """Views of the averages, shaped like the parameters, in the order of ``param_groups`` (inside ``averaged_weights()``
+        they hold the live weights)."""
+        self._need_ema("ema_parameters()")
+        return [self._ema[o:o + p.numel()].view(p.shape) for o, p in zip(self._offsets, self._params)]
+
+    def _exchange(self) -> None:
+        if any(p.data_ptr() != ptr for p, ptr in zip(self._params, self._ptrs)):   # (a parameter's storage moved)
+            self._build_tables()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().bt_ema_exchange(_lib.stream_ptr(self.device), self._tables[0].data_ptr(), len(self._params),
+                                                  self._tables[1].data_ptr(), self._n_chunks, self._ema.data_ptr(), self._total))
+        torch.autograd.graph.increment_version(self._params)   # (BeatThis packs its inference engine again)
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the context the parameters hold the averages (and the optimiser's buffer the live weights): one exchange
+        launch on entry, one on exit, which restores every bit.  Not re-entrant; needs at least one averaged step."""
+        self._need_ema("averaged_weights()")
+        if self._n_averaged == 0:
+            raise RuntimeError("averaged_weights() before the first averaged step: there is no average yet")
+        if self._exchanged:
+            raise RuntimeError("averaged_weights() is not re-entrant")
+        self._exchange()
+        self._exchanged = True
+        try:
+            yield self
+        finally:
+            self._exchange()
+            self._exchanged = False
 
     def last_grad_norm(self) -> float:
         """The global gradient norm (after the 1 / accumulate scaling, before clipping) that the last ``step()`` with
@@ -294,7 +373,11 @@ class AdamW(torch.optim.Optimizer):
 
     def state_dict(self) -> dict:
         """``torch.optim.AdamW``'s layout: per parameter index ``step`` (a float32 scalar tensor), ``exp_avg``, ``exp_avg_sq``
-        (copies, shaped like the parameter), and ``param_groups`` with parameter indices."""
+        (copies, shaped like the parameter), and ``param_groups`` with parameter indices.  With ``ema_decay`` also ``ema``:
+        ``decay``, ``n_averaged`` and ``params`` (per parameter index a copy of its average).  Raises inside
+        ``averaged_weights()``, where weights and averages are exchanged: a state saved there would hold them swapped."""
+        if self._exchanged:
+            raise RuntimeError("state_dict() inside averaged_weights(): the parameters hold the averages there")
         state, groups, k = {}, [], 0
         index = {id(p): i for i, p in enumerate(self._params)}
         for group in self.param_groups:
@@ -306,12 +389,21 @@ class AdamW(torch.optim.Optimizer):
             state[i] = {"step": torch.tensor(float(self._t), dtype=torch.float32),
                         "exp_avg": self._m[o:o + n].view(p.shape).clone(),
                         "exp_avg_sq": self._v[o:o + n].view(p.shape).clone()}
-        return {"state": state, "param_groups": groups}
+        out = {"state": state, "param_groups": groups}
+        if self._ema is not None:
+            out["ema"] = {"decay": self.ema_decay, "n_averaged": self._n_averaged,
+                          "params": {i: e.clone() for i, e in enumerate(self.ema_parameters())}}
+        return out
 
     @torch.no_grad()
     def load_state_dict(self, state_dict: dict) -> None:
         """Takes a state dict of this class or of ``torch.optim.AdamW`` over the same parameters in the same order: the moments
-        are copied into the flat buffers (bit for bit), the groups' settings replace the current ones."""
+        are copied into the flat buffers (bit for bit), the groups' settings replace the current ones.  Weight averaging: an
+        ``"ema"`` entry is restored bit for bit when this optimiser averages (``ema_decay`` stays the constructor's) and ignored
+        when it does not; a state without one starts the average over, the next step copies.  The averages are checked
+        before anything is written: a state whose averages do not fit leaves the optimiser as it was."""
+        if self._exchanged:
+            raise RuntimeError("load_state_dict() inside averaged_weights(): the parameters hold the averages there")
         groups = state_dict["param_groups"]
         if len(groups) != len(self.param_groups) or any(len(g["params"]) != len(mine["params"])
                                                         for g, mine in zip(groups, self.param_groups)):
@@ -319,6 +411,13 @@ class AdamW(torch.optim.Optimizer):
         if any(g.get("amsgrad") or g.get("maximize") for g in groups):
             raise ValueError("beat_this_amd.optim.AdamW has no amsgrad / maximize")
         order = [i for g in groups for i in g["params"]]
+        averages = None
+        if self._ema is not None and state_dict.get("ema") is not None:
+            saved = state_dict["ema"]["params"]
+            averages = [saved.get(i, saved.get(str(i))) for i in range(len(self._params))]
+            for i, (p, src) in enumerate(zip(self._params, averages)):
+                if src is None or tuple(src.shape) != tuple(p.shape):
+                    raise ValueError(f"loaded average of parameter {i} is missing or has the wrong shape")
         state = state_dict.get("state", {})
         steps = set()
         self._m.zero_()
@@ -337,6 +436,13 @@ class AdamW(torch.optim.Optimizer):
         if len(steps) > 1:
             raise ValueError(f"beat_this_amd.optim.AdamW keeps one step count for all parameters, the state has {sorted(steps)}")
         self._t = steps.pop() if steps else 0
+        if self._ema is not None:
+            self._ema.zero_()
+            self._n_averaged = 0
+            if averages is not None:
+                for e, src in zip(self.ema_parameters(), averages):
+                    e.copy_(src)
+                self._n_averaged = int(state_dict["ema"]["n_averaged"])
         for g, mine in zip(groups, self.param_groups):
             for key, val in g.items():
                 if key != "params":

@@ -15,6 +15,7 @@ runs torch's attention), bf16 mixed precision, and the test run after training (
 from __future__ import annotations
 
 import argparse
+import contextlib
 import math
 import os
 import sys
@@ -60,8 +61,12 @@ def save_checkpoint(path, pl_module, optimizer, scheduler, epoch: int, global_st
     """One file with the reference's (Lightning's) top-level keys: ``state_dict`` (``model.`` prefix), ``hyper_parameters``,
     ``optimizer_states`` and ``lr_schedulers`` (one entry each), ``epoch`` (the last finished one), ``global_step`` (optimiser
     steps so far) and ``rng`` (numpy's generator; with dropout enabled also ``rng["dropout"]`` = the model's
-    ``dropout_state()``, which carries the frontend's opt-in when it is set); a 16-mixed run adds ``loss_scaler`` (the ``LossScaler``'s state).  Written next to ``path`` first and
-    then moved over it."""
+    ``dropout_state()``, which carries the frontend's opt-in when it is set); a 16-mixed run adds ``loss_scaler`` (the ``LossScaler``'s state).
+    An optimiser that averages the weights (``ema_decay``) and has taken a step adds ``ema_state_dict``: the whole ``state_dict``
+    with every optimised parameter replaced by its average -- buffers (BatchNorm statistics among them) and frozen parameters
+    are the live ones; ``state_dict`` stays the live weights, and the average itself travels in the optimiser's state (so the
+    file holds the averages twice: it grows by two copies of the trained weights).  Written
+    next to ``path`` first and then moved over it."""
     ckpt = {"state_dict": _to_cpu(dict(pl_module.state_dict())), "hyper_parameters": dict(pl_module.hyper_parameters),
             "optimizer_states": [_to_cpu(optimizer.state_dict())], "lr_schedulers": [_to_cpu(scheduler.state_dict())],
             "epoch": int(epoch), "global_step": int(global_step), "rng": _rng_state()}
@@ -70,6 +75,14 @@ def save_checkpoint(path, pl_module, optimizer, scheduler, epoch: int, global_st
         ckpt["rng"]["dropout"] = dropout
     if loss_scaler is not None:
         ckpt["loss_scaler"] = loss_scaler.state_dict()
+    if getattr(optimizer, "ema_decay", None) is not None and optimizer.flat_state()["n_averaged"] > 0:
+        names = {id(p): n.replace("_orig_mod.", "") for n, p in pl_module.named_parameters()}
+        averaged = dict(ckpt["state_dict"])
+        for p, e in zip((p for g in optimizer.param_groups for p in g["params"]), optimizer.ema_parameters()):
+            if id(p) not in names:
+                raise ValueError("the optimiser averages a parameter that is not one of pl_module's: ema_state_dict cannot name it")
+            averaged[names[id(p)]] = e.detach().cpu()
+        ckpt["ema_state_dict"] = averaged
     path = os.fspath(path)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = path + ".part"
@@ -94,7 +107,7 @@ def validate(pl_module, datamodule) -> dict:
 
 def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
         resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None, frontend_precision=None,
-        frontend_dropout=None) -> dict:
+        frontend_dropout=None, ema_decay=None) -> dict:
     """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
 
     Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
@@ -131,6 +144,15 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     counter stay what they are.  True needs dropout enabled and a trainable frontend (``ValueError`` otherwise).  The opt-in
     travels in ``rng["dropout"]`` of the checkpoint, and ``resume`` restores it with the counter.
 
+    ``ema_decay`` (a float in [0, 1); None: off, and every call is the one of a run without it): the optimiser keeps an
+    exponential moving average of the weights it trains, in the pass of its step (``AdamW(ema_decay=...)``).  ``validate`` then
+    runs on the averaged weights (inside ``optimizer.averaged_weights()``, as Lightning's ``WeightAveraging`` callback does) and
+    the log line says so; the checkpoint gains ``ema_state_dict`` (``save_checkpoint``), which
+    ``beat_this_amd.inference.averaged_checkpoint`` turns into a checkpoint to load.  The average is part of the optimiser's
+    state: a resumed run repeats the uninterrupted one bit for bit, averages included.  ``resume`` with another setting follows
+    ``AdamW.load_state_dict``: a checkpoint without an average starts one, an average is ignored when ``ema_decay`` is None.
+    BatchNorm buffers are not averaged.
+
     A module whose model has dropout enabled or uses batch statistics is put into ``train()`` mode here and stays in it; validation runs under
     ``no_grad`` on the inference path, which never drops.
 
@@ -161,7 +183,9 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     datamodule.setup("fit")   # (returns at once when the caller has set the data up already)
     loader = datamodule.train_dataloader()
     steps_per_epoch = math.ceil(len(loader) / accumulate)
-    conf = pl_module.configure_optimizers(max(1, steps_per_epoch * int(max_epochs)), max_grad_norm=max_grad_norm, accumulate=accumulate)
+    extra = {} if ema_decay is None else {"ema_decay": ema_decay}
+    conf = pl_module.configure_optimizers(max(1, steps_per_epoch * int(max_epochs)), max_grad_norm=max_grad_norm, accumulate=accumulate,
+                                          **extra)
     optimizer, scheduler = conf["optimizer"], conf["lr_scheduler"]["scheduler"]
     device = optimizer.device
     first_epoch, global_step = 0, 0
@@ -212,8 +236,12 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
         history["train_loss"].append(mean)
         line = f"epoch {epoch}: train_loss {mean:.6f}, {global_step} steps, lr {scheduler.get_last_lr()[0]:.3e}"
         if (epoch + 1) % int(val_frequency) == 0:
-            metrics = validate(pl_module, datamodule)
+            averaged = ema_decay is not None and optimizer.flat_state()["n_averaged"] > 0
+            with optimizer.averaged_weights() if averaged else contextlib.nullcontext():
+                metrics = validate(pl_module, datamodule)
             history["val"].append((epoch, metrics))
+            if averaged:
+                line += f", validated on the averaged weights (decay {ema_decay:g})"
             line += "".join(f", {k} {v:.4f}" for k, v in metrics.items())
         if checkpoint_path is not None:
             save_checkpoint(checkpoint_path, pl_module, optimizer, scheduler, epoch, global_step, scaler)
@@ -223,6 +251,13 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
 
 
 # ---- command line (launch_scripts/train.py:135-291) ------------------------------------------------------------------------------
+def _ema_decay(text: str) -> float:
+    value = float(text)
+    if not 0.0 <= value < 1.0:
+        raise argparse.ArgumentTypeError(f"the decay of the weight average must lie in [0, 1), got {text}")
+    return value
+
+
 def get_parser() -> argparse.ArgumentParser:
     from .loss import LOSS_TYPES
 
@@ -268,6 +303,9 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch-statistics", default=False, action=toggle,
                    help="with --train-frontend: the frontend's BatchNorms use each batch's statistics and update their running "
                         "ones, as training from scratch needs (default: frozen running statistics)")
+    p.add_argument("--ema-decay", metavar="D", type=_ema_decay, default=None,
+                   help="keep an exponential moving average of the trained weights with this decay, 0 <= D < 1: validation runs "
+                        "on it and the checkpoint gains ema_state_dict (default: off)")
     p.add_argument("--dbn", default=False, action=toggle, help="DBN post-processing in validation")
     p.add_argument("--eval-trim-beats", metavar="SECONDS", type=float, default=5,
                    help="skip the first seconds of each piece in the metrics (default: %(default)s)")
@@ -340,7 +378,7 @@ def main(argv=None) -> int:
     with torch.cuda.device(device):
         fit(pl_module, datamodule, args.max_epochs, accumulate_grad_batches=args.accumulate_grad_batches,
             val_frequency=args.val_frequency, max_grad_norm=args.max_grad_norm, checkpoint_path=args.output,
-            resume=ckpt if args.resume_checkpoint else None)
+            resume=ckpt if args.resume_checkpoint else None, ema_decay=args.ema_decay)
     print("wrote", args.output)
     return 0
 

@@ -926,6 +926,30 @@ int bt_adamw_step(void* stream, const bt_optim_tensor* d_tensors, int n_tensors,
 int bt_grad_norm_host(const float* grad, int64_t total, float grad_scale, float max_norm, float* record);
 int bt_adamw_step_host(const bt_optim_tensor* tensors, int n_tensors, const bt_optim_chunk* chunks, int64_t n_chunks, float* grad,
                        float* m, float* v, int64_t total, const bt_optim_hyper* hyper, const float* coef);
+/* Weight averaging: the exponential moving average of the parameters that
+ * torch.optim.swa_utils.AveragedModel keeps with get_ema_multi_avg_fn(decay), made in the pass of the step.  The AdamW step
+ * above with a fourth flat fp32 buffer d_ema, laid out, aligned and refused like m and v.  The thread that updates an element
+ * first computes its new p exactly as the plain step does (p, m, v and the cleared gradient have the plain step's bits) and
+ * THEN moves the element's average e from that new p:
+ *     ema_copy != 0:   e = p                        (the first averaged step; the old e is not read)
+ *     ema_copy == 0:   e = e + (p - e) * ema_weight   (a subtraction, a product, a sum: each rounded to fp32 once, no contraction)
+ * ema_weight = 1 - decay, computed by the caller in fp64 and rounded to fp32 once; a value that is not a number in (0, 1] is
+ * BT_ERR_ARG before any launch, whatever ema_copy is.  Only a chunk's owner writes its part of d_ema, the padding between
+ * tensors is never written, a damaged table updates nothing; no atomics, memsets or allocation.
+ * The limit of every fp32 average: once |(p - e) * ema_weight| is below half an ulp of e, e stops moving.  With decay 0.9999
+ * and parameter steps of 1e-5, torch's own fp32 EMA is then about 1e-2 (relative to the displacement of the average) from
+ * an fp64 one; this arithmetic is within a few percent of torch's.  Documented, not repaired.
+ * The exchange swaps p and e element by element over the same tables (16 bytes at a time, one element at a time for a
+ * 4-byte aligned parameter and the tail): a pure move, twice is the identity. */
+int bt_adamw_ema_step(void* stream, const bt_optim_tensor* d_tensors, int n_tensors, const bt_optim_chunk* d_chunks,
+                      int64_t n_chunks, float* d_grad, float* d_m, float* d_v, float* d_ema, int64_t total,
+                      const bt_optim_hyper* hyper, const float* d_coef, float ema_weight, int ema_copy);
+int bt_ema_exchange(void* stream, const bt_optim_tensor* d_tensors, int n_tensors, const bt_optim_chunk* d_chunks, int64_t n_chunks,
+                    float* d_ema, int64_t total);
+/* HOST: the twin of the averaging step, bit-identical to the device */
+int bt_adamw_ema_step_host(const bt_optim_tensor* tensors, int n_tensors, const bt_optim_chunk* chunks, int64_t n_chunks,
+                           float* grad, float* m, float* v, float* ema, int64_t total, const bt_optim_hyper* hyper,
+                           const float* coef, float ema_weight, int ema_copy);
 
 /* ---- building bundles from audio: time stretch, pitch shift, arbitrary-ratio resampling (csrc/stretch.hip, DESIGN.md
  * section 20) -------------------------------------------------------------------------------------------------------------------
