@@ -24,8 +24,11 @@ from .. import _lib
 from . import backward as _bw
 from ..pack import Engine, PackedModel
 from ..weights import random_state_dict, resolve_hparams, state_dict_shapes
+from .settings import DIFFERENTIABLE, ENGINE, MODULES, REFUSE, TrainSettings, decide
 
 _BUFFER_LEAVES = ("running_mean", "running_var", "num_batches_tracked")
+_PARTS = ("frontend", "transformer", "heads")   # of settings.decide, by stage; "frontend" / "transformer" are the keys of ``dropout``
+_SETTERS = {"batch_statistics": "set_batch_statistics()", "train_frontend": "set_frontend_trainable() first"}   # (names in a refusal)
 _TREE_EPOCH = [0]   # bumped whenever a module is assigned to / removed from a node of a BeatThis tree (_hooked_below's cache)
 
 
@@ -105,36 +108,22 @@ class _Stage(_Node):
         object.__setattr__(self, "_root", weakref.ref(root))   # (not a registered sub-module: no cycle)
         self._stage = stage
 
-    def __getstate__(self):  # (copy.deepcopy / pickle: the owner re-binds itself, BeatThis.__setstate__)
-        state = self.__dict__.copy()
-        state.pop("_root", None)
-        return state
-
     def forward(self, x: torch.Tensor):
         root = self._root()
-        if self._stage == 0:
-            if root._frontend_route():
-                return root._frontend_train(x)
-            root._refuse_trainable_frontend()
-        elif root._differentiable(x, self):
-            # the differentiable route (backward.py): the reference's container loop over the units / the head
-            if self._stage == 2:
-                return root._head_train(x)
+        route = root._route(_PARTS[self._stage], self, x, hooks=self._stage < 2)
+        if route.how == ENGINE:
+            out = root._run(x, self._stage, self._stage)
+            return {"beat": out[0], "downbeat": out[1]} if self._stage == 2 else out
+        if self._stage == 1:
+            # the reference's container loop over the units (roformer.py:176-181), each of which takes its own route: the
+            # differentiable one (backward.py), or somebody hooked a sub-module of this stage and the hook has to fire
             for attn, ff in self.layers:
                 x = attn(x) + x
                 x = ff(x) + x
             return self.norm(x)
-        if self._stage < 2 and _hooked_below(self):
-            # somebody hooked a sub-module of this stage: run it through the sub-modules, like the reference's containers
-            # (beat_tracker.py:77-80, roformer.py:176-181), so that the hook fires
-            if self._stage == 0:
-                return self.linear(self.concat(self.blocks(self.stem(x))))
-            for attn, ff in self.layers:
-                x = attn(x) + x
-                x = ff(x) + x
-            return self.norm(x)
-        out = self._root()._run(x, self._stage, self._stage)
-        return {"beat": out[0], "downbeat": out[1]} if self._stage == 2 else out
+        if route.how == MODULES:   # a hook below the frontend: through its sub-modules (beat_tracker.py:77-80)
+            return self.linear(self.concat(self.blocks(self.stem(x))))
+        return root._head_train(x) if self._stage == 2 else root._frontend_train(x, route)
 
 
 def _hooked_below(node: nn.Module) -> bool:
@@ -163,6 +152,13 @@ def _params_of(node: nn.Module) -> tuple:
     return cache[1]
 
 
+def _any_requires_grad(node: nn.Module) -> bool:
+    for p in _params_of(node):
+        if p.requires_grad:
+            return True
+    return False
+
+
 def _attach(root: nn.Module, key: str, value: torch.Tensor) -> None:
     *path, leaf = key.split(".")
     node = root
@@ -185,55 +181,19 @@ class BeatThis(_TracksChildren, nn.Module):
     ``task_heads``, ``layers[l][0]``, ``layers[l][1]`` or ``.norm`` does -- the differentiable route runs: ``forward`` computes
     the frontend on the usual fast path under ``no_grad`` (at the model's own precision), then the six main layers, the final
     RMSNorm and the heads go through ``torch.autograd.Function``s over the library's training kernels, composed like the
-    reference's containers.  Fixed semantics of that route:
-      * its arithmetic is fp32, whatever ``fp32_split_gemms`` says and also under ``torch.autocast``;
-      * ``set_train_precision("16-mixed")`` opts in to the reference's training precision on that route alone: the attention and
-        the feed-forward round both operands of every matrix product to fp16 and accumulate in fp32 (DESIGN.md section 16;
-        parameters, saved tensors, gradients and everything that is no matrix product stay fp32).  Use it with a loss scale
-        (``beat_this_amd.optim.LossScaler``; ``fit(precision="16-mixed")`` does).  ``"32-true"`` is the default and is what the
-        route was before; ``torch.autocast`` selects neither;
-      * dropout is off unless ``enable_dropout(seed)`` was called: then, in ``train()`` mode and with ``dropout["transformer"]``
-        above 0, the main layers drop where the reference's do (the attention probabilities, after ``to_out``, after the GELU,
-        after the feed-forward's second linear) -- the reference's rule plus the opt-in; in ``eval()`` nothing is dropped.  The
-        masks are this package's own (Philox4x32-10 under ``seed``, include/beat_this_amd.h), not torch's generator: every
-        attention / feed-forward call that drops takes the next stream number from a counter (``dropout_state()``), which
-        ``set_dropout_state()`` rewinds to repeat a run bit for bit.  A graph capture with dropout active raises
-        ``RuntimeError`` (a replay would repeat its masks).  ``dropout["frontend"]`` is read only after the second opt-in
-        ``enable_dropout(seed, frontend=True)`` and only where the differentiable frontend runs (below): the frozen frontend
-        always runs the inference path, which never drops;
-      * ``rotary_embed.freqs`` never receives a gradient, as in the reference;
-      * the frontend is frozen unless ``set_frontend_trainable()`` was called: without that opt-in a frontend parameter that
-        requires grad makes a grad-mode forward raise ``NotImplementedError`` rather than silently leaving its ``.grad`` empty
-        (the opt-in is never inferred from ``requires_grad``);
-      * ``set_frontend_trainable()`` -- whole-model fine-tuning: it sets ``requires_grad`` on the frontend's
-        weights and, in grad mode, ``model(x)`` and ``model.frontend(x)`` run the frontend on the differentiable route too (the
-        stem, the three conv units, the projection and the twelve attention / feed-forward leaves of the partial transformers);
-        gradients also reach ``x`` when it requires grad.  That part of the route is fp32 whatever ``set_train_precision`` says
-        (it covers the trunk's units alone) unless ``set_frontend_precision("16-mixed")`` was called: then the conv units, the
-        leaves and the projection round both operands of their matrix products to fp16 and accumulate in fp32 (DESIGN.md section
-        19; the stem and everything that is no matrix product stay fp32); it runs without dropout after ``enable_dropout(seed)``
-        and drops only after ``enable_dropout(seed, frontend=True)``: then, in ``train()`` mode and with
-        ``dropout["frontend"]`` above 0, the twelve leaves drop at that rate at the trunk's four places -- the stem, the conv units
-        and the projection never drop, as in the reference -- and every leaf call takes the next stream number from the same
-        counter, in forward order (block 0 ``attnF``, ``ffF``, ``attnT``, ``ffT``, then blocks 1 and 2, then the trunk's units):
-        a whole-model forward advances ``calls`` by 12 + 2 ``n_layers``;
-        and its BatchNorm statistics are frozen unless ``set_batch_statistics()`` was called: every BatchNorm
-        uses ``running_mean`` / ``running_var``, in ``train()`` as in ``eval()``, and those buffers and
-        ``num_batches_tracked`` never receive a gradient and are never updated.  The callable nodes below ``frontend`` (``stem``, ``blocks[i]``, ``.partial``, ``.linear`` ...) stay
-        inference-only, and the route does not pass through them: forward hooks registered BELOW ``frontend`` do not fire on a
-        grad-mode call with the flag set (hooks on ``frontend`` itself and on the trunk's nodes do; under ``no_grad`` all fire as
-        ever).  ``set_frontend_trainable(False)`` restores the frozen state and drops the engine's packed copies, so the frozen
-        frontend runs on the weights as trained;
-      * ``set_batch_statistics()`` -- training from scratch, a second opt-in on top of
-        ``set_frontend_trainable()`` and never inferred from ``train()``: in ``train()`` mode and grad mode the frontend's five
-        BatchNorms (``stem.bn1d``, ``stem.bn2d``, ``blocks[i].norm``) are torch's training-mode ones (eps 1e-5, momentum 0.1):
-        they normalise with the mean and biased variance of the call's own batch, the backward differentiates through those
-        statistics, and every forward call moves ``running_mean`` / ``running_var`` (unbiased variance) and adds 1 to
-        ``num_batches_tracked`` -- once per call, each micro-batch of an accumulated step on its own.  So the call WRITES to
-        the model's buffers, and a sequence's input gradient is no longer the same alone and inside a batch.  A batch with
-        batch x time = 1 raises torch's ``ValueError`` before any launch.  In ``eval()``, under ``no_grad`` and on the inference
-        paths the running statistics are used as ever (those calls see the moved buffers: the engine packs again);
-      * parameters on the CPU raise the same ``RuntimeError`` as ever.
+    reference's containers.  Its arithmetic is fp32, whatever ``fp32_split_gemms`` says and also under ``torch.autocast``;
+    ``rotary_embed.freqs`` never receives a gradient, as in the reference; parameters on the CPU raise the same ``RuntimeError``
+    as ever.  Which route a call takes is decided in one place (``_route``, over ``settings.decide``).
+
+    Everything else about that route is an opt-in, held in ``self.train_settings``; ``settings.TrainSettings`` says what each means:
+      * ``set_train_precision("16-mixed")`` -> ``train_precision``: the reference's training precision in the trunk;
+      * ``set_frontend_trainable()`` -> ``frontend_trainable``: whole-model fine-tuning; ``False`` restores the frozen state and
+        drops the engine's packed copies, so the frozen frontend runs on the weights as trained;
+      * ``set_frontend_precision("16-mixed")`` -> ``frontend_precision``: fp16 matrix products in that frontend;
+      * ``set_batch_statistics()`` -> ``batch_statistics``: training from scratch; such a forward writes the running buffers;
+      * ``enable_dropout(seed)`` -> ``dropout_rng``: in the main layers in ``train()`` mode; with ``frontend=True`` ->
+        ``frontend_dropout``: in the frontend's leaves too.
+
     The route reads the parameters' storage at call time, so an optimizer step is seen at once.  The inference paths run on
     packed copies: the ``_version`` of every parameter is recorded when they are packed, and a parameter that requires grad
     and was changed in place since makes the next inference call pack again (checked only for parameters that require grad);
@@ -255,13 +215,7 @@ class BeatThis(_TracksChildren, nn.Module):
             _attach(self, key, init[key])
         self._bind_units()
         self.dropout = dict(dropout)
-        self._dropout_rng = None     # enable_dropout(): {"seed", "calls"}
-        self._frontend_dropout = False   # enable_dropout(frontend=True): the leaves of the partial transformers drop too
-        self._train_precision = "32-true"
-        self._frontend_precision = "32-true"   # set_frontend_precision()
-        self._frontend_trainable = False   # set_frontend_trainable()
-        self._batch_statistics = False     # set_batch_statistics()
-        self._stats_moved = False          # a batch-statistics forward wrote the running buffers since the engine was packed
+        self.train_settings = TrainSettings()   # every opt-in of the differentiable route
         self._engine = None
         self._packed_versions = ()   # (is frontend, parameter, its _version when the engine was packed)
         # outside autocast: True = every product of the forward on three half MFMAs over hi + lo operand halves
@@ -280,6 +234,9 @@ class BeatThis(_TracksChildren, nn.Module):
         return state
 
     def __setstate__(self, state):
+        if "train_settings" not in state:   # (pickled when every setting was an attribute of its own; the only place that knows)
+            state = dict(state)
+            state["train_settings"] = TrainSettings.from_loose_attributes(state)
         super().__setstate__(state)
         for name in ("frontend", "transformer_blocks", "task_heads"):
             object.__setattr__(self._modules[name], "_root", weakref.ref(self))
@@ -342,7 +299,7 @@ class BeatThis(_TracksChildren, nn.Module):
         """A parameter that requires grad was changed in place since the engine packed its copy (an optimizer step), or a
         batch-statistics forward moved the running buffers (the kernels write them through raw pointers: no ``_version``
         tells, the route leaves a note instead)."""
-        if getattr(self, "_stats_moved", False):
+        if self.train_settings.stats_moved:
             return True
         for front, p, version in self._packed_versions:
             if p.requires_grad and p._version != version and (front or not frontend_only):
@@ -363,185 +320,101 @@ class BeatThis(_TracksChildren, nn.Module):
             _lib.lib()  # fail loudly if the HIP library is missing
             self._engine = Engine(PackedModel(self.state_dict(), self.hparams, dev))
             self._packed_versions = tuple((name.startswith("frontend."), p, p._version) for name, p in self.named_parameters())
-            self._stats_moved = False
+            self.train_settings.stats_moved = False
         return self._engine
 
-    # -- the differentiable route (backward.py) ------------------------------------------------------------------------------
-    def _differentiable(self, x, node: nn.Module) -> bool:
-        """Grad mode is on and ``x`` (if given) or a parameter below ``node`` requires grad."""
-        if not torch.is_grad_enabled():
-            return False
-        if x is not None and x.requires_grad:
-            return True
-        for p in _params_of(node):
-            if p.requires_grad:
-                return True
-        return False
+    # -- the opt-ins of the differentiable route: delegates to self.train_settings (settings.TrainSettings has the meanings) --------
+    def _set(self, error=ValueError, rates={}, **fields) -> "BeatThis":
+        self.train_settings = self.train_settings.changed("model", error, _SETTERS, rates, **fields)
+        return self
 
-    # -- whole-model fine-tuning: the differentiable frontend (DESIGN.md section 17) -----------------------------------------------
     def set_frontend_trainable(self, flag: bool = True) -> "BeatThis":
-        """The opt-in to the differentiable frontend: ``requires_grad`` of the frontend's weights (not of the rotary tables;
-        ``running_mean``, ``running_var`` and ``num_batches_tracked`` are buffers and stay what they are) becomes ``flag``,
-        and with ``flag`` set a grad-mode ``model(x)`` / ``model.frontend(x)`` runs the frontend on the differentiable route.
-        ``False`` restores the frozen state."""
+        """The opt-in to the differentiable frontend: ``requires_grad`` of the frontend's weights (not of the rotary tables; the
+        BatchNorm buffers stay what they are) becomes ``flag``.  ``False`` restores the frozen state and clears ``batch_statistics``."""
         flag = bool(flag)
         for name, p in self.frontend.named_parameters():
             p.requires_grad_(flag and not name.endswith("rotary_embed.freqs"))
-        self._frontend_trainable = flag
-        if not flag:
-            self._batch_statistics = False
-        # the re-pack check looks at parameters that require grad only: frontend weights trained under the flag and frozen again
-        # would stay on the engine's old packed copies, so the engine is packed anew on its next use
-        self._engine = None
-        return self
+        self._engine = None   # (the re-pack check looks at parameters that require grad only: frozen again, trained weights would stay unpacked)
+        return self._set(frontend_trainable=flag, batch_statistics=flag and self.batch_statistics)
 
-    @property
-    def frontend_trainable(self) -> bool:
-        return getattr(self, "_frontend_trainable", False)
-
-    def _frontend_route(self) -> bool:
-        return self.frontend_trainable and torch.is_grad_enabled()
-
-    # -- batch-statistics BatchNorm on the differentiable frontend (DESIGN.md section 18) ------------------------------------------
     def set_batch_statistics(self, flag: bool = True) -> "BeatThis":
-        """The opt-in to training-mode BatchNorm (never inferred from ``train()``): with it, a grad-mode call in ``train()``
-        mode normalises the frontend's five BatchNorms with the statistics of its own batch and moves ``running_mean``,
-        ``running_var`` and ``num_batches_tracked`` (momentum 0.1).  Needs ``set_frontend_trainable()`` first;
-        ``set_frontend_trainable(False)`` clears it."""
-        flag = bool(flag)
-        if flag and not self.frontend_trainable:
-            raise RuntimeError("batch statistics belong to the differentiable frontend: call set_frontend_trainable() first")
-        self._batch_statistics = flag
-        return self
+        """The opt-in to training-mode BatchNorm in the differentiable frontend; ``RuntimeError`` on a frozen frontend"""
+        return self._set(RuntimeError, batch_statistics=bool(flag))
 
-    @property
-    def batch_statistics(self) -> bool:
-        return getattr(self, "_batch_statistics", False)
-
-    def _batch_route(self) -> bool:
-        """Batch statistics are used iff the opt-in is set, the frontend is trainable, grad mode is on and the model is in
-        ``train()`` mode."""
-        return self.batch_statistics and self._frontend_route() and self.training
-
-    def _frontend_train(self, x: torch.Tensor) -> torch.Tensor:
-        D = self.hparams["transformer_dim"]
-        _lib.require_gpu(x, "stage input")
-        if self.device.type != "cuda":
-            self.engine()   # (raises: no CPU implementation)
-        if x.dim() != 3 or x.shape[2] != self.hparams["spect_dim"]:
-            raise ValueError(f"expected a (batch, time, {self.hparams['spect_dim']}) input, got {tuple(x.shape)}")
-        if x.shape[0] == 0 or x.shape[1] == 0:
-            return _bw.empty_with_graph((x.shape[0], x.shape[1], D), x, _params_of(self.frontend))
-        batch = self._batch_route()
-        if batch:
-            _bw.check_batch_statistics(int(x.shape[0]), int(x.shape[1]))
-        # the leaves' dropout: asked once per leaf call, in forward order (None where nothing drops)
-        drops = (lambda: self._next_dropout("frontend")) if self.frontend_dropout and self.training else None
-        h = _bw.frontend_train(self, x.to(torch.float32), batch, self.frontend_precision == "16-mixed", drops)
-        if batch:   # noted AFTER the call: an engine that ``_rope`` packed half way through it is stale as well
-            self._stats_moved = True
-        return h
-
-    # -- 16-mixed on the differentiable route (DESIGN.md section 16) --------------------------------------------------------------
     def set_train_precision(self, precision: str) -> "BeatThis":
-        """"16-mixed": the attention and the feed-forward of the differentiable route run their matrix products on fp16
-        operands with fp32 accumulation; "32-true" (the default): fp32.  Inference, ``no_grad`` and ``eval()`` validation
-        never look at it."""
-        if precision not in ("16-mixed", "32-true"):
-            raise ValueError(f"train precision must be '16-mixed' or '32-true', got {precision!r}")
-        self._train_precision = precision
-        return self
+        """"16-mixed" or "32-true" (the default) for the trunk's units on the differentiable route"""
+        return self._set(train_precision=precision)
 
-    @property
-    def train_precision(self) -> str:
-        return getattr(self, "_train_precision", "32-true")
-
-    # -- 16-mixed in the differentiable frontend (DESIGN.md section 19) -------------------------------------------------------------
     def set_frontend_precision(self, precision: str) -> "BeatThis":
-        """"16-mixed": the matrix products of the differentiable frontend -- the three conv units, the twelve leaves of the
-        partial transformers and the projection -- run on fp16 operands with fp32 accumulation (the stem, BatchNorm, GELU,
-        parameters, saved tensors and gradients stay fp32); "32-true" (the default): fp32.  Independent of
-        ``set_train_precision``, which covers the trunk alone.  Read only where the differentiable frontend runs (the frontend
-        trainable and grad mode on): inference, ``no_grad`` and validation never look at it."""
-        if precision not in ("16-mixed", "32-true"):
-            raise ValueError(f"frontend precision must be '16-mixed' or '32-true', got {precision!r}")
-        self._frontend_precision = precision
-        return self
+        """"16-mixed" or "32-true" (the default) for the differentiable frontend, independent of ``set_train_precision``"""
+        return self._set(frontend_precision=precision)
 
-    @property
-    def frontend_precision(self) -> str:
-        return getattr(self, "_frontend_precision", "32-true")
-
-    # -- dropout on the differentiable route (DESIGN.md section 15) -------------------------------------------------------------
     def enable_dropout(self, seed: int = 0, frontend: bool = False) -> "BeatThis":
-        """Opt in: in ``train()`` mode the differentiable route drops at rate ``dropout["transformer"]``, with masks drawn
-        under ``seed``; the call counter starts at 0.  ``frontend=True`` is a second opt-in on top of it, never inferred: the
-        twelve leaves of the partial transformers drop at ``dropout["frontend"]`` where the differentiable frontend runs
-        (``set_frontend_trainable()`` and grad mode).  Without it the call means what it always did."""
-        for part in ("transformer", "frontend") if frontend else ("transformer",):
-            p = float(self.dropout.get(part, 0.0))
-            if not 0.0 <= p < 1.0:   # (NaN fails both comparisons)
-                raise ValueError(f"dropout[{part!r}] = {p}: the rate must satisfy 0 <= p < 1")
-        self.set_dropout_state({"seed": seed, "calls": 0, "frontend": bool(frontend)})
-        return self
+        """Opt in to dropout at ``dropout["transformer"]`` under ``seed``, the call counter at 0; ``frontend=True``: a second opt-in,
+        the leaves of the differentiable frontend drop at ``dropout["frontend"]``"""
+        return self._set(rates={part: self.dropout.get(part, 0.0) for part in ("transformer", "frontend")},
+                         dropout_rng={"seed": int(seed), "calls": 0}, frontend_dropout=bool(frontend))
 
     def disable_dropout(self) -> "BeatThis":
-        self._dropout_rng = None
-        self._frontend_dropout = False
-        return self
-
-    @property
-    def frontend_dropout(self) -> bool:
-        """The frontend's leaves are opted in to dropout (``enable_dropout(frontend=True)``)"""
-        return getattr(self, "_dropout_rng", None) is not None and getattr(self, "_frontend_dropout", False)
+        return self._set(dropout_rng=None, frontend_dropout=False)
 
     def dropout_state(self):
         """{"seed", "calls"} -- the seed and how many attention / feed-forward calls have drawn masks so far -- or None when
         dropout is not enabled; with the frontend's opt-in also ``"frontend": True``"""
-        if getattr(self, "_dropout_rng", None) is None:
-            return None
-        state = dict(self._dropout_rng)
-        if self.frontend_dropout:
-            state["frontend"] = True
-        return state
+        s = self.train_settings
+        return None if s.dropout_rng is None else dict(s.dropout_rng, **({"frontend": True} if s.frontend_dropout else {}))
 
     def set_dropout_state(self, state: dict) -> None:
         """Enable dropout at ``state`` (what ``dropout_state()`` returned): the next call that drops takes stream ``calls``.
         ``state["frontend"]``, when present, sets the frontend's opt-in; absent, the opt-in stays what it is."""
-        seed, calls = int(state["seed"]), int(state["calls"])
-        if not (0 <= seed < 1 << 64 and 0 <= calls < 1 << 64):
-            raise ValueError(f"dropout seed and calls must fit 64 unsigned bits, got {seed} and {calls}")
-        if "frontend" in state:
-            if state["frontend"]:
-                p = float(self.dropout.get("frontend", 0.0))
-                if not 0.0 <= p < 1.0:
-                    raise ValueError(f"dropout['frontend'] = {p}: the rate must satisfy 0 <= p < 1")
-            self._frontend_dropout = bool(state["frontend"])
-        self._dropout_rng = {"seed": seed, "calls": calls}
+        self._set(rates={"frontend": self.dropout.get("frontend", 0.0)} if state.get("frontend") else {},
+                  dropout_rng={"seed": int(state["seed"]), "calls": int(state["calls"])},
+                  frontend_dropout=bool(state.get("frontend", self.train_settings.frontend_dropout)))
 
-    def _next_dropout(self, part: str = "transformer"):
-        """(p, seed, stream) for one attention / feed-forward call of the differentiable route, or None: dropout is active
-        iff it is enabled, the model is in ``train()`` mode and the rate ``dropout[part]`` is above 0; ``part`` "frontend" (a
-        leaf of a partial transformer) needs the frontend's opt-in as well.  A call that does not drop takes no number."""
-        rng = getattr(self, "_dropout_rng", None)
-        on = rng is not None and self.training and (part != "frontend" or getattr(self, "_frontend_dropout", False))
-        p = float(self.dropout.get(part, 0.0)) if on else 0.0
-        if not p > 0.0:
+    train_precision = property(lambda self: self.train_settings.train_precision)
+    frontend_precision = property(lambda self: self.train_settings.frontend_precision)
+    frontend_trainable = property(lambda self: self.train_settings.frontend_trainable)
+    batch_statistics = property(lambda self: self.train_settings.batch_statistics)
+    frontend_dropout = property(lambda self: self.train_settings.dropout_rng is not None and self.train_settings.frontend_dropout,
+                                doc="The frontend's leaves are opted in to dropout (``enable_dropout(frontend=True)``)")
+
+    # -- which route a call takes (settings.decide), and the differentiable route (backward.py) ------------------------------------
+    def _route(self, part: str, node: nn.Module = None, x: torch.Tensor = None, hooks: bool = False):
+        """``settings.decide`` for a call of ``part`` issued now, on ``node`` (None: no parameter is asked) with input ``x``;
+        ``hooks``: a hook below ``node`` sends the inference path through the modules.  Raises where a frozen frontend was asked
+        for gradients.  The parameters, the hooks and the rate are looked at only where the answer can depend on them."""
+        s = self.train_settings
+        if not torch.is_grad_enabled():
+            args = (False,)
+        else:
+            x_grad = x is not None and x.requires_grad
+            look = node is not None and not (s.frontend_trainable if part == "frontend" else x_grad)
+            rate = float(self.dropout.get(part, 0.0)) if s.dropout_rng is not None else 0.0
+            args = (True, self.training, x_grad, look and _any_requires_grad(node), False, rate)
+        route = decide(s, part, *args)
+        if hooks and route.how == ENGINE and _hooked_below(node):
+            route = decide(s, part, *args[:4], hooked=True)
+        if route.how == REFUSE:
+            raise NotImplementedError(
+                "the frontend is frozen in this version: only transformer_blocks and task_heads are differentiable; "
+                "call model.frontend.requires_grad_(False) (or run under torch.no_grad())")
+        return route
+
+    def _batch_route(self) -> bool:   # (a frontend call issued now would use batch statistics)
+        return self._route("frontend").batch_statistics
+
+    def _next_dropout(self, part: str, active: bool):
+        """(p, seed, stream) for one attention / feed-forward call of the differentiable route whose ``part``'s dropout is
+        ``active`` (``Route.drop``), else None: a call that does not drop takes no number."""
+        if not active:
             return None
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("dropout is active during a graph capture: seed and stream number travel by value, so every replay "
                                "would repeat the masks of the captured step; capture in eval() or after disable_dropout()")
+        rng = self.train_settings.dropout_rng
         stream = rng["calls"]
         rng["calls"] = stream + 1
-        return p, rng["seed"], stream
-
-    def _refuse_trainable_frontend(self) -> None:
-        if torch.is_grad_enabled():
-            for p in _params_of(self.frontend):
-                if p.requires_grad:
-                    raise NotImplementedError(
-                        "the frontend is frozen in this version: only transformer_blocks and task_heads are differentiable; "
-                        "call model.frontend.requires_grad_(False) (or run under torch.no_grad())")
+        return float(self.dropout[part]), rng["seed"], stream
 
     def _rope(self, T: int):
         """The engine's rotary table for ``T`` frames (the table does not depend on anything that is trained)."""
@@ -549,29 +422,38 @@ class BeatThis(_TracksChildren, nn.Module):
         eng.ensure_positions(T)
         return eng.packed._rope_t, int(eng.packed.desc.rope_len)
 
-    def _unit_train(self, x: torch.Tensor, kind: str, node: nn.Module) -> torch.Tensor:
-        D = self.hparams["transformer_dim"]
-        _lib.require_gpu(x, "sub-module input")
-        if self.device.type != "cuda":
+    def _nothing_to_do(self, x: torch.Tensor, what: str, last=None) -> bool:
+        """What every stage and unit call starts with: a (batch, time, ``last``) input on a GPU (``last`` None: any width, and the
+        model's own device is the engine's to refuse); True for an empty batch or zero frames"""
+        _lib.require_gpu(x, what)
+        if last is not None and self.device.type != "cuda":
             self.engine()   # (raises: no CPU implementation)
-        if x.dim() != 3 or x.shape[2] != D:
-            raise ValueError(f"expected a (batch, time, {D}) input, got {tuple(x.shape)}")
-        if x.shape[0] == 0 or x.shape[1] == 0:
+        if x.dim() != 3 or last not in (None, x.shape[2]):
+            raise ValueError(f"expected a (batch, time, {last or 'features'}) input, got {tuple(x.shape)}")
+        return x.shape[0] == 0 or x.shape[1] == 0
+
+    def _frontend_train(self, x: torch.Tensor, route) -> torch.Tensor:
+        if self._nothing_to_do(x, "stage input", self.hparams["spect_dim"]):
+            return _bw.empty_with_graph((x.shape[0], x.shape[1], self.hparams["transformer_dim"]), x, _params_of(self.frontend))
+        # the leaves' dropout: asked once per leaf call, in forward order (None where nothing drops)
+        drops = (lambda: self._next_dropout("frontend", True)) if route.drop else None
+        h = _bw.frontend_train(self, x.to(torch.float32), route.batch_statistics, route.mixed, drops)
+        if route.batch_statistics:   # noted AFTER the call: an engine that ``_rope`` packed half way through it is stale as well
+            self.train_settings.stats_moved = True
+        return h
+
+    def _unit_train(self, x: torch.Tensor, kind: str, node: nn.Module, route) -> torch.Tensor:
+        if self._nothing_to_do(x, "sub-module input", self.hparams["transformer_dim"]):
             return _bw.empty_with_graph(x.shape, x, _params_of(node))
         x = x.to(torch.float32)
-        mixed = self.train_precision == "16-mixed"
         if kind == "attn":
-            return _bw.attention(node, x, *self._rope(x.shape[1]), self._next_dropout(), mixed)
-        return _bw.feedforward(node, x, self._next_dropout(), mixed) if kind == "ff" else _bw.final_norm(node, x)
+            return _bw.attention(node, x, *self._rope(x.shape[1]), self._next_dropout("transformer", route.drop), route.mixed)
+        if kind == "ff":
+            return _bw.feedforward(node, x, self._next_dropout("transformer", route.drop), route.mixed)
+        return _bw.final_norm(node, x)
 
     def _head_train(self, x: torch.Tensor) -> dict:
-        D = self.hparams["transformer_dim"]
-        _lib.require_gpu(x, "stage input")
-        if self.device.type != "cuda":
-            self.engine()
-        if x.dim() != 3 or x.shape[2] != D:
-            raise ValueError(f"expected a (batch, time, {D}) input, got {tuple(x.shape)}")
-        if x.shape[0] == 0 or x.shape[1] == 0:
+        if self._nothing_to_do(x, "stage input", self.hparams["transformer_dim"]):
             params = _params_of(self.task_heads)
             return {"beat": _bw.empty_with_graph(x.shape[:2], x, params), "downbeat": _bw.empty_with_graph(x.shape[:2], x, params)}
         beat, down = _bw.head(self.task_heads, x.to(torch.float32), self.hparams["sum_head"])
@@ -581,12 +463,12 @@ class BeatThis(_TracksChildren, nn.Module):
         if x.dim() != 3:
             raise ValueError(f"expected (batch, time, {self.hparams['spect_dim']}) input, got {tuple(x.shape)}")
         _lib.require_gpu(x, "model input")
-        if self._frontend_route():
-            # whole-model fine-tuning: the frontend, the trunk and the heads on the differentiable route
-            return self.task_heads(self.transformer_blocks(self.frontend(x)))
         if torch.is_grad_enabled():
-            self._refuse_trainable_frontend()
-            if self._differentiable(None, self.transformer_blocks) or self._differentiable(None, self.task_heads):
+            if self._route("frontend", self.frontend).how == DIFFERENTIABLE:
+                # whole-model fine-tuning: the frontend, the trunk and the heads on the differentiable route
+                return self.task_heads(self.transformer_blocks(self.frontend(x)))
+            if (self._route("transformer", self.transformer_blocks).how == DIFFERENTIABLE
+                    or self._route("heads", self.task_heads).how == DIFFERENTIABLE):
                 # fine-tuning: the frozen frontend on the fast path, the trunk and the heads on the differentiable route
                 with torch.no_grad():
                     h = self.frontend(x)
@@ -610,10 +492,7 @@ class BeatThis(_TracksChildren, nn.Module):
     def _run(self, x: torch.Tensor, first: int, last: int, out=None, prec=None, checks=None):
         """Stages first..last in the engine at ``prec`` (BT_PREC_*; None: follows autocast like the whole forward).  ``out``
         (the logits' tensors) and ``checks`` (where the range flag goes; None: looked at now): see Engine.forward_stages."""
-        if x.dim() != 3:
-            raise ValueError(f"expected a (batch, time, features) input, got {tuple(x.shape)}")
-        _lib.require_gpu(x, "stage input")
-        if x.shape[0] == 0 or x.shape[1] == 0:
+        if self._nothing_to_do(x, "stage input"):
             D = self.hparams["transformer_dim"]
             empty = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
             return (empty, empty.clone()) if last == 2 else torch.empty((x.shape[0], x.shape[1], D), dtype=torch.float32, device=x.device)
@@ -627,9 +506,10 @@ class BeatThis(_TracksChildren, nn.Module):
         if kind in ("attn", "ff", "norm"):
             tb = self.transformer_blocks
             node = tb.norm if kind == "norm" else tb.layers[index][0 if kind == "attn" else 1]
-            if self._differentiable(x, node):
-                return self._unit_train(x, kind, node)
-        elif self._frontend_route():
+            route = self._route("transformer", node, x)
+            if route.how == DIFFERENTIABLE:
+                return self._unit_train(x, kind, node, route)
+        elif self._route("frontend").how == DIFFERENTIABLE:
             raise NotImplementedError(
                 "the sub-modules below frontend are inference-only: with set_frontend_trainable() the differentiable route is "
                 "model(x) / model.frontend(x); call this node under torch.no_grad()")

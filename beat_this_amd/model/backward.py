@@ -8,10 +8,11 @@ copies), so an optimizer step is seen by the next forward.  The arithmetic is fp
 also under ``torch.autocast``.  Gradients are overwritten by the library and handed to autograd, which accumulates into
 ``.grad``; they are bitwise reproducible (no atomics anywhere).
 
-Dropout: the attention and the feed-forward take ``drop`` = None (the calls and launches of a model without dropout) or
-``(p, seed, stream)``, which goes to bt_train_forward_dropout and, from ``ctx``, unchanged to bt_train_backward_dropout: the
-kernels recompute the masks from those three numbers, nothing is stored.  ``BeatThis`` decides when dropout is active and
-hands out the streams.
+Dropout and 16-mixed (DESIGN.md sections 15, 16): the attention and the feed-forward take ``drop`` = None (the calls and launches
+of a model without dropout) or ``(p, seed, stream)``, which goes from ``ctx`` unchanged to the backward -- the kernels recompute
+the masks from those three numbers, nothing is stored -- and ``mixed``: both operands of every matrix product rounded to fp16,
+fp32 accumulation, everything else fp32.  ``_run`` picks the entry points for the two; ``BeatThis._route`` decides both per
+call (``torch.autocast`` does not) and ``BeatThis`` hands out the streams.
 
 The frontend (the lower part of this file): ``StemFn``, ``ConvUnitFn``, ``SwapFn`` and ``ProjectionFn`` over
 bt_front_forward / bt_front_backward (csrc/train_front.hip), composed by ``frontend_train`` with ``AttentionFn`` /
@@ -21,11 +22,6 @@ with ``BeatThis.set_frontend_precision("16-mixed")`` the conv units, the leaves 
 ``BeatThis.set_frontend_trainable`` decides whether it runs.  ``StemBatchFn`` / ``ConvUnitBatchFn`` (section 18, bt_front_bn_*)
 are the same two units on the statistics of the call's batch; their forward moves the running buffers in place
 (``BeatThis.set_batch_statistics``).
-
-16-mixed: the attention and the feed-forward take ``mixed``; True sends the same arguments to
-bt_train_forward_mixed / bt_train_backward_mixed (both operands of every matrix product rounded to fp16, fp32 accumulation,
-everything else fp32), False -- the default -- makes the calls above.  ``BeatThis.set_train_precision`` decides it;
-``torch.autocast`` does not.
 """
 from __future__ import annotations
 
@@ -51,18 +47,6 @@ def _on_device_of(x: torch.Tensor, *tensors) -> None:
                                "move the model and the input to the same ROCm GPU")
 
 
-def _workspace(unit: int, backward: bool, B: int, T: int, D: int, hidden: int, device, drop=None, mixed=False) -> torch.Tensor:
-    if mixed:
-        need = _lib.lib().bt_train_workspace_bytes_mixed(unit, int(backward), B, T, D, hidden, int(drop is not None))
-    else:
-        query = _lib.lib().bt_train_workspace_bytes if drop is None else _lib.lib().bt_train_workspace_bytes_dropout
-        need = query(unit, int(backward), B, T, D, hidden)
-    if need == 0:
-        raise ValueError(f"the differentiable route supports widths that are multiples of 32 from 32 to 1024 and ff_mult 1 .. 16, "
-                         f"got batch {B}, {T} frames, width {D}, hidden width {hidden}")
-    return torch.empty(need, dtype=torch.uint8, device=device)
-
-
 def _args(x: torch.Tensor, hidden: int = 0, rope=None, rope_len: int = 0) -> _lib.TrainArgs:
     if rope is not None and (rope.dim() != 3 or rope.shape[0] < max(int(rope_len), int(x.shape[1])) or tuple(rope.shape[1:]) != (16, 2)):
         raise ValueError(f"rotary table of shape {tuple(rope.shape)} for {int(x.shape[1])} frames (rope_len {rope_len})")
@@ -74,27 +58,26 @@ def _args(x: torch.Tensor, hidden: int = 0, rope=None, rope_len: int = 0) -> _li
     return a
 
 
-def _call(fn, unit: int, a: _lib.TrainArgs, ws: torch.Tensor, device) -> None:
+# (mixed, drop is None) -> the family of entry points (bt_train_forward / _backward / _workspace_bytes + this); the plain one takes
+# no dropout argument, "_dropout" takes (p, seed, stream), "_mixed" takes them or NULL and its workspace query whether they come
+_FAMILY = {(False, True): "", (False, False): "_dropout", (True, True): "_mixed", (True, False): "_mixed"}
+
+
+def _run(backward: bool, unit: int, a: _lib.TrainArgs, device, drop=None, mixed: bool = False) -> None:
+    """One call of a unit of the trunk -- attention, feed-forward, final norm, head -- with its workspace; ``drop``: None or
+    (p, seed, stream); ``mixed``: 16-mixed (the attention and the feed-forward alone take either)"""
+    lib, family = _lib.lib(), _FAMILY[bool(mixed), drop is None]
+    extra = (int(drop is not None),) if mixed else ()
+    need = getattr(lib, "bt_train_workspace_bytes" + family)(unit, int(backward), a.B, a.T, a.dim, a.hidden, *extra)
+    if need == 0:
+        raise ValueError(f"the differentiable route supports widths that are multiples of 32 from 32 to 1024 and ff_mult 1 .. 16, "
+                         f"got batch {a.B}, {a.T} frames, width {a.dim}, hidden width {a.hidden}")
+    ws = torch.empty(need, dtype=torch.uint8, device=device)
     a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
+    d = None if drop is None else C.byref(_lib.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2]))
+    fn = getattr(lib, ("bt_train_backward" if backward else "bt_train_forward") + family)
     with torch.cuda.device(device):
-        _lib.check(fn(_lib.stream_ptr(device), unit, C.byref(a)))
-
-
-def _run(backward: bool, unit: int, a: _lib.TrainArgs, shape, hidden: int, device, drop, mixed=False) -> None:
-    """One attention / feed-forward call: the usual entry point, or with ``drop`` = (p, seed, stream) the dropout one;
-    ``mixed``: the 16-mixed entry point, which takes the dropout or NULL"""
-    B, T, D = shape
-    ws = _workspace(unit, backward, B, T, D, hidden, device, drop, mixed)
-    lib = _lib.lib()
-    if mixed:
-        fn = lib.bt_train_backward_mixed if backward else lib.bt_train_forward_mixed
-        d = None if drop is None else C.byref(_lib.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2]))
-        return _call(lambda stream, u, args: fn(stream, u, args, d), unit, a, ws, device)
-    if drop is None:
-        return _call(lib.bt_train_backward if backward else lib.bt_train_forward, unit, a, ws, device)
-    d = _lib.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2])
-    fn = lib.bt_train_backward_dropout if backward else lib.bt_train_forward_dropout
-    _call(lambda stream, u, args: fn(stream, u, args, C.byref(d)), unit, a, ws, device)
+        _lib.check(fn(_lib.stream_ptr(device), unit, C.byref(a), *((d,) if family else ())))
 
 
 def _grad_like(p: torch.Tensor, wanted: bool):
@@ -118,7 +101,7 @@ class AttentionFn(torch.autograd.Function):
         a.residual = int(bool(residual))
         a.gamma, a.w1, a.w2, a.b2, a.w3 = (p.data_ptr() for p in ps)
         a.y, a.save_o, a.save_lse = y.data_ptr(), o.data_ptr(), lse.data_ptr()
-        _run(False, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, drop, mixed)
+        _run(False, _lib.UNIT_ATTN, a, xf.device, drop, mixed)
         ctx.save_for_backward(xf, o, lse, rope, *ps)
         ctx.rope_len, ctx.drop, ctx.mixed, ctx.residual = rope_len, drop, bool(mixed), int(bool(residual))
         return y
@@ -127,7 +110,6 @@ class AttentionFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         xf, o, lse, rope, gamma, w_qkv, w_gates, b_gates, w_out = ctx.saved_tensors
-        B, T, D = xf.shape
         need = ctx.needs_input_grad
         gyf = _f32(gy)
         gx, g_gamma, g_qkv, g_wg, g_bg, g_out = (_grad_like(t, need[i]) for i, t in
@@ -137,7 +119,7 @@ class AttentionFn(torch.autograd.Function):
         a.gamma, a.w1, a.w2, a.b2, a.w3 = (p.data_ptr() for p in (gamma, w_qkv, w_gates, b_gates, w_out))
         a.save_o, a.save_lse, a.gy = o.data_ptr(), lse.data_ptr(), gyf.data_ptr()
         a.gx, a.g_gamma, a.g_w1, a.g_w2, a.g_b2, a.g_w3 = (_lib.ptr(g) for g in (gx, g_gamma, g_qkv, g_wg, g_bg, g_out))
-        _run(True, _lib.UNIT_ATTN, a, (B, T, D), 0, xf.device, ctx.drop, ctx.mixed)
+        _run(True, _lib.UNIT_ATTN, a, xf.device, ctx.drop, ctx.mixed)
         return gx, g_gamma, g_qkv, g_wg, g_bg, g_out, None, None, None, None, None
 
 
@@ -147,16 +129,14 @@ class FeedForwardFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, w1, b1, w2, b2, drop=None, mixed=False, residual=False):
         xf = _f32(x)
-        B, T, D = xf.shape
         ps = [_f32(p) for p in (gamma, w1, b1, w2, b2)]
         _on_device_of(xf, *ps)
-        hidden = int(ps[1].shape[0])
         y = torch.empty_like(xf)
-        a = _args(xf, hidden=hidden)
+        a = _args(xf, hidden=ps[1].shape[0])
         a.residual = int(bool(residual))
         a.gamma, a.w1, a.b1, a.w2, a.b2 = (p.data_ptr() for p in ps)
         a.y = y.data_ptr()
-        _run(False, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, drop, mixed)
+        _run(False, _lib.UNIT_FF, a, xf.device, drop, mixed)
         ctx.save_for_backward(xf, *ps)
         ctx.drop, ctx.mixed, ctx.residual = drop, bool(mixed), int(bool(residual))
         return y
@@ -165,16 +145,14 @@ class FeedForwardFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         xf, gamma, w1, b1, w2, b2 = ctx.saved_tensors
-        B, T, D = xf.shape
-        hidden = int(w1.shape[0])
         gyf = _f32(gy)
         grads = [_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, gamma, w1, b1, w2, b2))]
-        a = _args(xf, hidden=hidden)
+        a = _args(xf, hidden=w1.shape[0])
         a.residual = ctx.residual
         a.gamma, a.w1, a.b1, a.w2, a.b2 = (p.data_ptr() for p in (gamma, w1, b1, w2, b2))
         a.gy = gyf.data_ptr()
         a.gx, a.g_gamma, a.g_w1, a.g_b1, a.g_w2, a.g_b2 = (_lib.ptr(g) for g in grads)
-        _run(True, _lib.UNIT_FF, a, (B, T, D), hidden, xf.device, ctx.drop, ctx.mixed)
+        _run(True, _lib.UNIT_FF, a, xf.device, ctx.drop, ctx.mixed)
         return (*grads, None, None, None)
 
 
@@ -185,11 +163,10 @@ class NormFn(torch.autograd.Function):
     def forward(ctx, x, gamma):
         xf, g = _f32(x), _f32(gamma)
         _on_device_of(xf, g)
-        B, T, D = xf.shape
         y = torch.empty_like(xf)
         a = _args(xf)
         a.gamma, a.y = g.data_ptr(), y.data_ptr()
-        _call(_lib.lib().bt_train_forward, _lib.UNIT_NORM, a, _workspace(_lib.UNIT_NORM, False, B, T, D, 0, xf.device), xf.device)
+        _run(False, _lib.UNIT_NORM, a, xf.device)
         ctx.save_for_backward(xf, g)
         return y
 
@@ -197,12 +174,11 @@ class NormFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         xf, gamma = ctx.saved_tensors
-        B, T, D = xf.shape
         gyf = _f32(gy)
         gx, g_gamma = _grad_like(xf, ctx.needs_input_grad[0]), _grad_like(gamma, ctx.needs_input_grad[1])
         a = _args(xf)
         a.gamma, a.gy, a.gx, a.g_gamma = gamma.data_ptr(), gyf.data_ptr(), _lib.ptr(gx), _lib.ptr(g_gamma)
-        _call(_lib.lib().bt_train_backward, _lib.UNIT_NORM, a, _workspace(_lib.UNIT_NORM, True, B, T, D, 0, xf.device), xf.device)
+        _run(True, _lib.UNIT_NORM, a, xf.device)
         return gx, g_gamma
 
 
@@ -219,8 +195,7 @@ class HeadFn(torch.autograd.Function):
         a = _args(xf)
         a.sum_head = int(bool(sum_head))
         a.w1, a.b1, a.y, a.y2 = wf.data_ptr(), bf.data_ptr(), beat.data_ptr(), down.data_ptr()
-        _call(_lib.lib().bt_train_forward, _lib.TRAIN_UNIT_HEAD, a, _workspace(_lib.TRAIN_UNIT_HEAD, False, B, T, D, 0, xf.device),
-              xf.device)
+        _run(False, _lib.TRAIN_UNIT_HEAD, a, xf.device)
         ctx.save_for_backward(xf, wf, bf)
         ctx.sum_head = int(bool(sum_head))
         ctx.set_materialize_grads(False)   # (a loss on one of the two outputs: the other's gradient is None, not zeros)
@@ -230,7 +205,6 @@ class HeadFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_beat, g_down):
         xf, w, b = ctx.saved_tensors
-        B, T, D = xf.shape
         gb = None if g_beat is None else _f32(g_beat)
         gd = None if g_down is None else _f32(g_down)
         gx, gw, gbias = (_grad_like(t, ctx.needs_input_grad[i]) for i, t in enumerate((xf, w, b)))
@@ -238,8 +212,7 @@ class HeadFn(torch.autograd.Function):
         a.sum_head = ctx.sum_head
         a.w1, a.b1, a.gy, a.gy2 = w.data_ptr(), b.data_ptr(), _lib.ptr(gb), _lib.ptr(gd)
         a.gx, a.g_w1, a.g_b1 = _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gbias)
-        _call(_lib.lib().bt_train_backward, _lib.TRAIN_UNIT_HEAD, a, _workspace(_lib.TRAIN_UNIT_HEAD, True, B, T, D, 0, xf.device),
-              xf.device)
+        _run(True, _lib.TRAIN_UNIT_HEAD, a, xf.device)
         return gx, gw, gbias, None
 
 

@@ -33,6 +33,11 @@ AUGMENTATIONS = {
 }
 POS_WEIGHT_WIDEN = 3
 CHECKPOINT_KEYS = ("state_dict", "hyper_parameters", "optimizer_states", "lr_schedulers", "epoch", "global_step", "rng")
+# what fit() and the command line call the switches of model.settings.TrainSettings.violations when they refuse a recipe
+_FIT_NAMES = {"frontend_dropout": "frontend_dropout=True", "train_frontend": "a trainable frontend (train_frontend=True)",
+              "dropout": "dropout enabled (PLBeatThis(apply_dropout=True) or model.enable_dropout())"}
+_FLAGS = {"batch_statistics": "--batch-statistics", "frontend_precision": "--frontend-precision", "dropout": "--dropout",
+          "frontend_dropout": "--apply-frontend-dropout", "train_frontend": "--train-frontend"}
 
 
 def _rng_state() -> dict:
@@ -126,23 +131,17 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     unscaled; the scaler's state goes into the checkpoint under ``loss_scaler`` and comes back with ``resume``.  Without
     16-mixed the calls are the ones of an fp32 run.
 
-    ``frontend_precision``: "16-mixed" or "32-true" sets the model's ``set_frontend_precision`` (None leaves it as it is), before
-    the optimiser is built: fp16 matrix products in the differentiable frontend, independent of ``precision``.  The loss scaler
-    exists when either precision is "16-mixed".
-
-    ``train_frontend``: True / False calls the model's ``set_frontend_trainable`` first, before the optimiser is built, so
-    that its state covers the frontend's weights (None leaves the model as it is): whole-model fine-tuning with frozen
-    BatchNorm statistics.  A checkpoint then carries the larger optimiser state, and ``resume`` needs the same setting.
-
-    ``batch_statistics``: True / False calls the model's ``set_batch_statistics`` next (None leaves it as it is; True needs a
-    trainable frontend): the frontend's BatchNorms then normalise with each batch's own statistics and move their running
-    buffers, every micro-batch on its own -- training from scratch.  The buffers travel in the ``state_dict``, so a checkpoint
-    and ``resume`` need nothing new; ``resume`` needs the same setting.
-
-    ``frontend_dropout``: True / False sets the frontend's dropout opt-in of a model whose dropout is enabled
-    (``BeatThis.enable_dropout(frontend=True)``; None leaves it as it is), before the optimiser is built; the seed and the call
-    counter stay what they are.  True needs dropout enabled and a trainable frontend (``ValueError`` otherwise).  The opt-in
-    travels in ``rng["dropout"]`` of the checkpoint, and ``resume`` restores it with the counter.
+    ``train_frontend``, ``batch_statistics``, ``frontend_precision``, ``frontend_dropout``: the model's other settings
+    (``model.settings.TrainSettings`` says what each means), applied in that order after ``precision`` and before the optimiser is
+    built, so that its state covers the frontend's weights; None leaves the model as it is.  ``train_frontend``: True / False
+    calls ``set_frontend_trainable``; a checkpoint then carries the larger optimiser state, and ``resume`` needs the same
+    setting.  ``batch_statistics``: True / False calls ``set_batch_statistics`` (True needs a trainable frontend); the buffers
+    travel in the ``state_dict``, so a checkpoint and ``resume`` need nothing new; ``resume`` needs the same setting.
+    ``frontend_precision``: "16-mixed" or "32-true" calls ``set_frontend_precision``; the loss scaler exists when either precision
+    is "16-mixed".  ``frontend_dropout``: True / False sets the frontend's dropout opt-in of a model whose dropout is enabled
+    (``BeatThis.enable_dropout(frontend=True)``); the seed and the call counter stay what they are.  True needs dropout enabled
+    and a trainable frontend (``ValueError`` otherwise).  The opt-in travels in ``rng["dropout"]`` of the checkpoint, and
+    ``resume`` restores it with the counter.
 
     ``ema_decay`` (a float in [0, 1); None: off, and every call is the one of a run without it): the optimiser keeps an
     exponential moving average of the weights it trains, in the pass of its step (``AdamW(ema_decay=...)``).  ``validate`` then
@@ -160,23 +159,17 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     ``scheduler``, ``loss_scaler`` (None in an fp32 run)."""
     from .optim import LossScaler
 
-    if precision is not None:
-        pl_module.model.set_train_precision(precision)
-    if train_frontend is not None:
-        pl_module.model.set_frontend_trainable(train_frontend)
-    if batch_statistics is not None:
-        pl_module.model.set_batch_statistics(batch_statistics)
-    if frontend_precision is not None:
-        pl_module.model.set_frontend_precision(frontend_precision)
+    model = pl_module.model
+    for value, setter in ((precision, model.set_train_precision), (train_frontend, model.set_frontend_trainable),
+                          (batch_statistics, model.set_batch_statistics), (frontend_precision, model.set_frontend_precision)):
+        if value is not None:   # (None leaves the model as it is; in this order)
+            setter(value)
     if frontend_dropout is not None:
-        state = pl_module.model.dropout_state()
-        if frontend_dropout and state is None:
-            raise ValueError("frontend_dropout=True needs dropout enabled: PLBeatThis(apply_dropout=True) or model.enable_dropout()")
-        if frontend_dropout and not pl_module.model.frontend_trainable:
-            raise ValueError("frontend_dropout=True needs a trainable frontend: train_frontend=True")
+        model.train_settings.changed("recipe", ValueError, _FIT_NAMES, only="frontend_dropout", frontend_dropout=bool(frontend_dropout))
+        state = model.dropout_state()
         if state is not None:
-            pl_module.model.set_dropout_state(dict(state, frontend=bool(frontend_dropout)))
-    scaler = LossScaler() if "16-mixed" in (pl_module.model.train_precision, pl_module.model.frontend_precision) else None
+            model.set_dropout_state(dict(state, frontend=bool(frontend_dropout)))
+    scaler = LossScaler() if "16-mixed" in (model.train_precision, model.frontend_precision) else None
     accumulate = int(accumulate_grad_batches)
     if accumulate < 1 or int(max_epochs) < 0 or int(val_frequency) < 1:
         raise ValueError("accumulate_grad_batches and val_frequency must be at least 1, max_epochs at least 0")
@@ -329,17 +322,16 @@ def get_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     parser = get_parser()
     args = parser.parse_args(argv)
-    if args.batch_statistics and not args.train_frontend:
-        parser.error("--batch-statistics needs --train-frontend: batch statistics belong to the differentiable frontend")
-    if args.frontend_precision != "32-true" and not args.train_frontend:
-        parser.error("--frontend-precision needs --train-frontend: it belongs to the differentiable frontend")
-    if args.apply_frontend_dropout and not args.dropout:
-        parser.error("--apply-frontend-dropout needs --dropout: the frontend's dropout is a second opt-in on top of it")
-    if args.apply_frontend_dropout and not args.train_frontend:
-        parser.error("--apply-frontend-dropout needs --train-frontend: only the differentiable frontend drops")
     from .dataset import BeatDataModule
     from .inference import load_checkpoint
     from .model.pl_module import PLBeatThis
+    from .model.settings import TrainSettings
+
+    asked = TrainSettings(frontend_trainable=args.train_frontend, batch_statistics=args.batch_statistics,
+                          frontend_precision=args.frontend_precision, dropout_rng={"seed": args.seed, "calls": 0} if args.dropout else None,
+                          frontend_dropout=args.apply_frontend_dropout)
+    for violation in asked.violations("recipe"):   # (before the data folder is touched)
+        parser.error(violation.message(_FLAGS))
 
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
