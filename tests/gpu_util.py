@@ -2,6 +2,7 @@
 entry points, and a JSONL report written under gpurun_out/ (merged back by gpurun)."""
 import ctypes as C
 import json
+import math
 import os
 
 import numpy as np
@@ -68,6 +69,39 @@ def run_attn(prec, qkv, gates, out, n_seq, L, heads, o_div=1, o_outer=None, o_in
     a.o_inner, a.o_tok = o_inner, o_tok
     _lib.check(_lib.lib().bt_attention(_lib.stream_ptr(dev()), prec, C.byref(a)))
     torch.cuda.synchronize()
+
+
+# ---- inputs and references the inference kernel tests share --------------------------------------------------------------------
+def _mk(shape, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(shape, generator=g, dtype=torch.float64) * scale
+
+
+def _rel(a, ref):
+    return float((a.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
+
+
+def _attn_ref(q, k, v, gates):
+    # q, k, v: (S, H, L, 32) float64, q already carries log2(e) / sqrt(d): softmax in base 2
+    s = q @ k.transpose(-1, -2) * math.log(2.0)
+    return torch.softmax(s, -1) @ v * gates[..., None]
+
+
+def _pair_sd(dim, seed):
+    """float64 weights of one attention + feed-forward pair of width ``dim``, under "a." and "f." """
+    H = dim // 32
+    g = torch.Generator().manual_seed(seed)
+
+    def rn(*shape, s=1.0):
+        return torch.randn(*shape, generator=g, dtype=torch.float64) * s
+    return {
+        "a.norm.gamma": 1 + 0.1 * rn(dim), "a.to_qkv.weight": rn(3 * dim, dim, s=1.6 / math.sqrt(dim)),
+        "a.to_gates.weight": rn(H, dim, s=0.3), "a.to_gates.bias": rn(H, s=0.3),
+        "a.to_out.0.weight": rn(dim, dim, s=1 / math.sqrt(dim)),
+        "f.net.0.gamma": 1 + 0.1 * rn(dim), "f.net.1.weight": rn(4 * dim, dim, s=1 / math.sqrt(dim)),
+        "f.net.1.bias": rn(4 * dim, s=0.2), "f.net.4.weight": rn(dim, 4 * dim, s=0.5 / math.sqrt(dim)),
+        "f.net.4.bias": rn(dim, s=0.2),
+    }
 
 
 def pad_rows(w, mult=128):

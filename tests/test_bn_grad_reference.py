@@ -1,5 +1,5 @@
 """CPU side of batch-statistics BatchNorm: the binding of the bt_front_bn_* entry points, what they refuse
-before any launch, the opt-in's bookkeeping, the command line, and the yardstick of bn_grad_util.py shown to discriminate the
+before any launch, the opt-in's bookkeeping, the command line, and the yardstick of route_grads.py shown to discriminate the
 three mistakes a training-mode BatchNorm makes most easily."""
 import ctypes as C
 import os
@@ -9,14 +9,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import bn_grad_util as BU
-import front_grad_util as FU
-import trunk_grad_util as U
+import route_cases as RC
+import route_grads as RG
 from conftest import ROOT
+from route_harness import MODEL_KEYS
 from beat_this_amd import weights as W
 
 HP = dict(transformer_dim=64, ff_mult=2, n_layers=2)
-MODEL_KEYS = ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim", "sum_head", "partial_transformers")
 NEW = ("bt_front_bn_struct_sizes", "bt_front_bn_workspace_bytes", "bt_front_bn_forward", "bt_front_bn_backward")
 
 
@@ -167,7 +166,7 @@ def test_the_module_and_the_command_line(capsys):
     assert not plain.model.batch_statistics and batch.model.batch_statistics
     assert "batch_statistics" not in batch.hyper_parameters and batch.hyper_parameters == plain.hyper_parameters
     assert set(batch.state_dict()) == set(plain.state_dict())      # the buffers travel already: no new keys
-    assert sum(k.endswith(FU.STAT_LEAVES) for k in batch.state_dict()) == 15
+    assert sum(k.endswith(RG.STAT_LEAVES) for k in batch.state_dict()) == 15
     with pytest.raises(RuntimeError, match="set_frontend_trainable"):
         PLBeatThis(**kw, batch_statistics=True)
     p = get_parser()
@@ -185,9 +184,9 @@ def test_the_module_and_the_command_line(capsys):
 def case():
     sd = W.random_state_dict(W.resolve_hparams(HP), seed=6, style="lively")
     B, T = 2, 3
-    x = FU.spect(B, T, seed=11)
+    x = RC.spect(B, T, seed=11)
     g = torch.randn(B, T, 64, generator=torch.Generator().manual_seed(12))
-    r32, r64 = (BU.frontend(sd, x, g, dt) for dt in (torch.float32, torch.float64))
+    r32, r64 = (RG.bn_frontend(sd, x, g, dt) for dt in (torch.float32, torch.float64))
     return sd, x, g, r32, r64
 
 
@@ -197,10 +196,10 @@ def test_the_truth_is_torchs_training_mode(case):
 
     sd, x, g, r32, r64 = case
     assert O.batchnorm.__module__ == O.__name__
-    assert set(r64["grads"]) == set(["x"] + FU.frontend_keys(sd)) and len(r64["grads"]) == 77
+    assert set(r64["grads"]) == set(["x"] + RG.frontend_keys(sd)) and len(r64["grads"]) == 77
     assert all(float(v.abs().max()) > 0 for v in r64["grads"].values())
     assert len(r64["stats"]) == 15
-    for p in BU.BN_PREFIXES:
+    for p in RG.BN_PREFIXES:
         assert int(r64["stats"][p + "num_batches_tracked"]) == int(sd[p + "num_batches_tracked"]) + 1
         for leaf in ("running_mean", "running_var"):
             assert not torch.equal(r64["stats"][p + leaf], sd[p + leaf].double()), p + leaf
@@ -211,7 +210,7 @@ def test_the_truth_is_torchs_training_mode(case):
     bn(x.double().transpose(1, 2))
     assert torch.allclose(bn.running_var, r64["stats"][p + "running_var"], rtol=1e-12, atol=0)
     assert torch.allclose(bn.running_mean, r64["stats"][p + "running_mean"], rtol=1e-12, atol=1e-15)
-    e_ref = U.yardstick(r32["grads"], r64["grads"])
+    e_ref = RG.yardstick(r32["grads"], r64["grads"])
     print(f"e_ref = {e_ref:.3e}")
     assert 1e-7 < e_ref < 1e-4, e_ref
 
@@ -241,49 +240,49 @@ def test_the_yardstick_discriminates(case, mistake):
     """Each mistake, made on the fp32 reference, is at least 1000 e_ref from the fp64 truth (100 x the gate of 10 e_ref); the same
     hand-written BatchNorm without a mistake (None) is inside the gate, so the distance is the mistake's."""
     sd, x, g, r32, r64 = case
-    bad = BU.frontend(sd, x, g, torch.float32, batchnorm=_mistaken(mistake))
-    e_ref = U.yardstick(r32["grads"], r64["grads"])
-    e_grad = U.yardstick(bad["grads"], r64["grads"]) / e_ref
+    bad = RG.bn_frontend(sd, x, g, torch.float32, batchnorm=_mistaken(mistake))
+    e_ref = RG.yardstick(r32["grads"], r64["grads"])
+    e_grad = RG.yardstick(bad["grads"], r64["grads"]) / e_ref
     stat_keys = [k for k in r64["stats"] if not k.endswith("num_batches_tracked")]
-    e_stat = max(U.rel(bad["stats"][k], r64["stats"][k]) / max(U.rel(r32["stats"][k], r64["stats"][k]), BU.STAT_FLOOR) for k in stat_keys)
+    e_stat = max(RG.rel(bad["stats"][k], r64["stats"][k]) / max(RG.rel(r32["stats"][k], r64["stats"][k]), RG.STAT_FLOOR) for k in stat_keys)
     print(f"{mistake}: gradients {e_grad:.1f} x e_ref ({e_ref:.3e}), running statistics {e_stat:.1f} x their e_ref")
     if mistake is None:
-        assert e_grad <= U.GATE and e_stat <= U.GATE
+        assert e_grad <= RG.GATE and e_stat <= RG.GATE
     elif mistake == "running_var moved with the biased variance":
-        assert e_grad <= U.GATE and e_stat >= 100 * U.GATE, (e_grad, e_stat)
+        assert e_grad <= RG.GATE and e_stat >= 100 * RG.GATE, (e_grad, e_stat)
     else:
-        assert e_grad >= 100 * U.GATE, (mistake, e_grad)
+        assert e_grad >= 100 * RG.GATE, (mistake, e_grad)
 
 
 @pytest.mark.parametrize("B,T", [(2, 1), (1, 2), (2, 3)])
 def test_the_truth_agrees_with_plain_autograd(B, T):
     """torch's batch_norm backward against autograd through the formula written out, in fp64: the same gradients to 1e-10, also
-    at T = 1, where a permuted upstream gradient has channels-last strides (bn_grad_util._PlainGrad)"""
+    at T = 1, where a permuted upstream gradient has channels-last strides (route_reference._PlainGrad)"""
     sd = W.random_state_dict(W.resolve_hparams(HP), seed=6, style="lively")
-    x, gy = FU.spect(B, T, seed=100 + T), torch.randn(B, T, 32, 32, generator=torch.Generator().manual_seed(200 + T))
-    a, b = BU.stem(sd, x, gy, torch.float64), BU.stem(sd, x, gy, torch.float64, batchnorm=_mistaken(None))
-    assert U.yardstick(a["grads"], b["grads"]) < 1e-10 and U.rel(a["y"], b["y"]) < 1e-12
+    x, gy = RC.spect(B, T, seed=100 + T), torch.randn(B, T, 32, 32, generator=torch.Generator().manual_seed(200 + T))
+    a, b = RG.bn_stem(sd, x, gy, torch.float64), RG.bn_stem(sd, x, gy, torch.float64, batchnorm=_mistaken(None))
+    assert RG.yardstick(a["grads"], b["grads"]) < 1e-10 and RG.rel(a["y"], b["y"]) < 1e-12
     xc = torch.randn(B, T, 16, 64, generator=torch.Generator().manual_seed(1))
     gc = torch.randn(B, T, 8, 128, generator=torch.Generator().manual_seed(2))
-    a, b = BU.conv(sd, 1, xc, gc, torch.float64), BU.conv(sd, 1, xc, gc, torch.float64, batchnorm=_mistaken(None))
-    assert U.yardstick(a["grads"], b["grads"]) < 1e-10
+    a, b = RG.bn_conv(sd, 1, xc, gc, torch.float64), RG.bn_conv(sd, 1, xc, gc, torch.float64, batchnorm=_mistaken(None))
+    assert RG.yardstick(a["grads"], b["grads"]) < 1e-10
 
 
 def test_torchs_fp32_batch_norm_is_a_sound_reference_for_shifted_input():
     """The cancellation case of the GPU tests: the spectrogram shifted by +64 (values in [64, 67)).  torch's fp32 batch_norm on
     the CPU must itself stay close to the fp64 one there, or its error would be no yardstick: its running_var and its output are
     within 1e-5 of fp64, where E[v^2] - mean^2 in fp32 (4225 +- 0.75 at 2^-24 relative: 2.5e-4 absolute) would be 1e-3 off."""
-    x = FU.spect(2, 65, seed=165) + 64
+    x = RC.spect(2, 65, seed=165) + 64
     assert 64 <= float(x.min()) and float(x.max()) < 67
     out = {}
     for dt in (torch.float32, torch.float64):
         mean, var = torch.zeros(128, dtype=dt), torch.ones(128, dtype=dt)
         y = F.batch_norm(x.to(dt).transpose(1, 2), mean, var, None, None, training=True, momentum=0.1, eps=1e-5)
         out[dt] = (y, mean, var)
-    e_y, e_mean, e_var = (U.rel(a, b) for a, b in zip(out[torch.float32], out[torch.float64]))
+    e_y, e_mean, e_var = (RG.rel(a, b) for a, b in zip(out[torch.float32], out[torch.float64]))
     print(f"shift +64: fp32 batch_norm against fp64: y {e_y:.3e}, running_mean {e_mean:.3e}, running_var {e_var:.3e}")
     assert e_y < 1e-5 and e_mean < 1e-6 and e_var < 1e-5
     naive = (x * x).mean((0, 1)) - x.mean((0, 1)) ** 2               # fp32
     true = x.double().var((0, 1), unbiased=False)
-    print(f"           E[v^2] - mean^2 in fp32: {U.rel(naive, true):.3e}")
-    assert U.rel(naive, true) > 100 * e_var
+    print(f"           E[v^2] - mean^2 in fp32: {RG.rel(naive, true):.3e}")
+    assert RG.rel(naive, true) > 100 * e_var

@@ -1,5 +1,5 @@
 """The generator and the mask contract of the training route's dropout, without a GPU: bt_philox4x32_10_host against the
-Random123 known answers, bt_dropout_mask_host against the numpy restatement of the header's mapping (dropout_reference.py),
+Random123 known answers, bt_dropout_mask_host against the numpy restatement of the header's mapping (route_reference.py),
 the kept fraction, the independence of sites / streams / seeds, and the argument checks."""
 import ctypes as C
 import math
@@ -9,10 +9,10 @@ import re
 import numpy as np
 import pytest
 
-import dropout_reference as R
+import route_reference as REF
 from conftest import ROOT
 
-SITES = (R.ATTN_P, R.ATTN_OUT, R.FF_HIDDEN, R.FF_OUT)
+SITES = (REF.ATTN_P, REF.ATTN_OUT, REF.FF_HIDDEN, REF.FF_OUT)
 SIGMAS = 5.0
 
 
@@ -26,7 +26,7 @@ def L():
 def host_mask(p, seed, stream, site, B, T, dim, hidden):
     lib = L()
     d = lib.TrainDropout(p=p, seed=seed, stream=stream)
-    n = B * (dim // 32) * T * T if site == R.ATTN_P else B * T * (hidden if site == R.FF_HIDDEN else dim)
+    n = B * (dim // 32) * T * T if site == REF.ATTN_P else B * T * (hidden if site == REF.FF_HIDDEN else dim)
     out = np.full(n, 7, dtype=np.uint8)
     lib.check(lib.lib().bt_dropout_mask_host(C.byref(d), site, B, T, dim, hidden, out.ctypes.data))
     assert set(np.unique(out)) <= {0, 1}            # every byte was written
@@ -72,7 +72,7 @@ def test_philox_known_answers(ctr, key, want):
     c, k, out = (C.c_uint32 * 4)(*ctr), (C.c_uint32 * 2)(*key), (C.c_uint32 * 4)()
     lib.lib().bt_philox4x32_10_host(c, k, out)
     assert tuple(out) == want, [hex(v) for v in out]
-    assert tuple(int(v) for v in R.philox4x32_10(ctr, key)) == want       # (the restatement stands on the same answers)
+    assert tuple(int(v) for v in REF.philox4x32_10(ctr, key)) == want       # (the restatement stands on the same answers)
 
 
 @pytest.mark.parametrize("dim", [32, 96])
@@ -83,7 +83,7 @@ def test_host_twin_equals_the_numpy_restatement(T, dim):
         for site in SITES:
             seed, stream = 0x1234_5678_9ABC_DEF0 + site, (1 << 40) + 3 * T
             got = host_mask(p, seed, stream, site, B, T, dim, hidden)
-            want = R.mask(p, seed, stream, site, B, T, dim, hidden)
+            want = REF.mask(p, seed, stream, site, B, T, dim, hidden)
             assert np.array_equal(got, want.reshape(-1)), (p, site)
             if p == 0.0:
                 assert got.all()
@@ -113,7 +113,7 @@ def test_sites_streams_and_seeds_are_independent():
                   host_mask(p, base["seed"], base["stream"] + (1 << 32), s, B, T, dim, hidden),
                   host_mask(p, base["seed"] + 1, base["stream"], s, B, T, dim, hidden),
                   host_mask(p, base["seed"] + (1 << 32), base["stream"], s, B, T, dim, hidden)]
-        others += [m[o] for o in (R.ATTN_OUT, R.FF_HIDDEN, R.FF_OUT) if o != s and s != R.ATTN_P]
+        others += [m[o] for o in (REF.ATTN_OUT, REF.FF_HIDDEN, REF.FF_OUT) if o != s and s != REF.ATTN_P]
         for other in others:
             diff = int((m[s] != other).sum())
             assert _within(diff, m[s].size, 2 * p * (1 - p)), (s, diff / m[s].size)
@@ -124,7 +124,7 @@ def test_argument_checks():
     out = np.zeros(4 * 32, dtype=np.uint8)
     for bad in (-0.1, 1.0, 1.5, float("nan"), float("inf")):
         d = lib.TrainDropout(p=bad, seed=0, stream=0)
-        assert lib.lib().bt_dropout_mask_host(C.byref(d), R.ATTN_OUT, 1, 4, 32, 64, out.ctypes.data) == lib.BT_ERR_ARG, bad
+        assert lib.lib().bt_dropout_mask_host(C.byref(d), REF.ATTN_OUT, 1, 4, 32, 64, out.ctypes.data) == lib.BT_ERR_ARG, bad
         with pytest.raises(ValueError):
             lib.check(lib.BT_ERR_ARG)
         a = lib.TrainArgs()
@@ -135,8 +135,8 @@ def test_argument_checks():
                 assert b"0 <= p < 1" in lib.lib().bt_last_error()
     d = lib.TrainDropout(p=0.2, seed=0, stream=0)
     assert lib.lib().bt_dropout_mask_host(C.byref(d), 4, 1, 4, 32, 64, out.ctypes.data) == lib.BT_ERR_ARG
-    assert lib.lib().bt_dropout_mask_host(C.byref(d), R.ATTN_OUT, 1, 4, 48, 64, out.ctypes.data) == lib.BT_ERR_ARG
-    assert lib.lib().bt_dropout_mask_host(None, R.ATTN_OUT, 1, 4, 32, 64, out.ctypes.data) == lib.BT_ERR_ARG
+    assert lib.lib().bt_dropout_mask_host(C.byref(d), REF.ATTN_OUT, 1, 4, 48, 64, out.ctypes.data) == lib.BT_ERR_ARG
+    assert lib.lib().bt_dropout_mask_host(None, REF.ATTN_OUT, 1, 4, 32, 64, out.ctypes.data) == lib.BT_ERR_ARG
     # the norm and the head take no dropout; p = 0 there is no dropout and passes on to the usual checks
     a = lib.TrainArgs()
     a.B, a.T, a.dim, a.hidden, a.rope_len = 1, 8, 64, 128, 1536

@@ -1,11 +1,10 @@
 """CPU side of the trajectory tests (tests/test_gpu_finetune_trajectory.py): the yardstick of the whole fine-tuning loop -- the
-fp32 run of tests/finetune_reference.py against its fp64 run, on ``p_final - p_initial`` of the worst tensor -- shown to tell a
+fp32 run of tests/route_grads.py against its fp64 run, on ``p_final - p_initial`` of the worst tensor -- shown to tell a
 correct loop from each of six one-line deviations by at least ten times the gate."""
 import pytest
 import torch
 
-import finetune_reference as FR
-import trunk_grad_util as U
+import route_grads as RG
 from beat_this_amd import weights as W
 
 HP = dict(transformer_dim=64, ff_mult=2, n_layers=2)
@@ -36,9 +35,9 @@ def synthetic_batches():
 def runs():
     sd = W.random_state_dict(W.resolve_hparams(HP), seed=3, style="lively")
     batches = synthetic_batches()
-    out = {"sd": sd, 64: FR.run(sd, batches, torch.float64, **SETTINGS), 32: FR.run(sd, batches, torch.float32, **SETTINGS)}
-    for mutant in FR.MUTANTS:
-        out[mutant] = FR.run(sd, batches, torch.float64, **SETTINGS, mutant=mutant)
+    out = {"sd": sd, 64: RG.run(sd, batches, torch.float64, **SETTINGS), 32: RG.run(sd, batches, torch.float32, **SETTINGS)}
+    for mutant in RG.MUTANTS:
+        out[mutant] = RG.run(sd, batches, torch.float64, **SETTINGS, mutant=mutant)
     return out
 
 
@@ -51,29 +50,29 @@ def test_the_loop_is_the_one_described(runs):
         assert total == lb + ld and lb > 0
     assert r["losses"][3][1] == 0.0 and r["losses"][8][1] == 0.0          # no downbeat loss without downbeat annotation
     # the first step has rate 0: nothing moves but the moments
-    first = FR.run(runs["sd"], synthetic_batches()[:2], torch.float64, **dict(SETTINGS, epochs=1, batches_per_epoch=2))
-    for k, d in FR.displacement(first["epochs"][0]["params"], runs["sd"]).items():
+    first = RG.run(runs["sd"], synthetic_batches()[:2], torch.float64, **dict(SETTINGS, epochs=1, batches_per_epoch=2))
+    for k, d in RG.displacement(first["epochs"][0]["params"], runs["sd"]).items():
         assert float(d.abs().max()) == 0.0, k
     assert all(float(v.abs().max()) > 0 for v in first["epochs"][0]["exp_avg"].values())
 
 
 def test_the_yardstick_discriminates(runs):
     """Every mutant's worst tensor is at least 100 e_ref from the truth on p_final - p_initial: ten times the gate of
-    trunk_grad_util.py.  A condition on the inputs chosen above, not a tolerance."""
+    route_grads.py.  A condition on the inputs chosen above, not a tolerance."""
     sd = runs["sd"]
     norms = [s["norm"] for s in runs[64]["steps"]]
     clipped = [s["coef"] < 1.0 for s in runs[64]["steps"]]
     print("gradient norms of the fp64 run:", " ".join(f"{n:.4f}" for n in norms), "clipped:", clipped)
     assert any(clipped) and not all(clipped)
-    d64, d32 = (FR.displacement(runs[k]["epochs"][-1]["params"], sd) for k in (64, 32))
-    errs = sorted(U.rel(d32[k], d64[k]) for k in d64)
-    e_ref = U.yardstick(d32, d64)
+    d64, d32 = (RG.displacement(runs[k]["epochs"][-1]["params"], sd) for k in (64, 32))
+    errs = sorted(RG.rel(d32[k], d64[k]) for k in d64)
+    e_ref = RG.yardstick(d32, d64)
     print(f"e_ref = {e_ref:.3e} (median tensor {errs[len(errs) // 2]:.3e})")
     assert 1e-7 < e_ref < 1e-3, e_ref
     ratios = {}
-    for mutant in FR.MUTANTS:
-        dm = FR.displacement(runs[mutant]["epochs"][-1]["params"], sd)
-        ratios[mutant] = max(U.rel(dm[k], d64[k]) for k in d64) / e_ref
+    for mutant in RG.MUTANTS:
+        dm = RG.displacement(runs[mutant]["epochs"][-1]["params"], sd)
+        ratios[mutant] = max(RG.rel(dm[k], d64[k]) for k in d64) / e_ref
         print(f"{mutant}: worst tensor {ratios[mutant]:.0f} x e_ref")
     for mutant, ratio in ratios.items():
-        assert ratio >= 10 * U.GATE, (mutant, ratio)
+        assert ratio >= 10 * RG.GATE, (mutant, ratio)

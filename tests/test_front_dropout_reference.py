@@ -1,4 +1,4 @@
-"""Frontend dropout without a GPU: the CPU restatement front_dropout_reference.py against the oracle and
+"""Frontend dropout without a GPU: the CPU restatement route_reference.py against the oracle and
 against the host twin of the mask contract at the leaves' shapes, the opt-in's state on ``BeatThis``, the new switches of
 ``PLBeatThis`` and of the command line, and the seed of a new model's initial weights."""
 import ctypes as C
@@ -7,10 +7,10 @@ import numpy as np
 import pytest
 import torch
 
-import dropout_reference as DR
-import front_dropout_reference as FD
-import front_grad_util as FU
-import trunk_grad_util as U
+import route_cases as RC
+import route_grads as RG
+import route_reference as REF
+from route_harness import same_bits
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
 
@@ -23,35 +23,31 @@ def state_dict(partial=True):
     return W.random_state_dict(W.resolve_hparams(dict(HP, partial_transformers=partial)), seed=3, style="lively")
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 # ---- the helper -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("partial", [True, False])
 def test_with_every_rate_zero_the_helper_is_the_oracle(partial):
     sd = state_dict(partial)
-    x = FU.spect(2, 9, seed=1)
-    pl, trunk, used = FD.model_plan(sd, 0.0, 0.0, SEED)
+    x = RC.spect(2, 9, seed=1)
+    pl, trunk, used = REF.model_plan(sd, 0.0, 0.0, SEED)
     assert used == 0 and trunk is None and all(v is None for v in pl.values())
     with torch.no_grad():
-        assert same_bits(FD.frontend(x, sd, pl), O.frontend(x, sd))
-        beat, down = FD.model(x, sd, pl, trunk)
+        assert same_bits(REF.frontend(x, sd, pl), O.frontend(x, sd))
+        beat, down = REF.model(x, sd, pl, trunk)
         want = O.model_forward(sd, x)
     assert same_bits(beat, want[0]) and same_bits(down, want[1])
 
 
 def test_the_plan_numbers_the_leaves_in_forward_order():
-    pl = FD.plan(0.1, SEED, first=5)
-    order = [(i, leaf) for i in range(3) for leaf in FD.LEAVES]
+    pl = REF.plan(0.1, SEED, first=5)
+    order = [(i, leaf) for i in range(3) for leaf in REF.LEAVES]
     assert list(pl) == order and [pl[k][2] for k in order] == list(range(5, 17))
     assert all(pl[k][:2] == (0.1, SEED) for k in order)
     sd = state_dict()
-    _, trunk, used = FD.model_plan(sd, 0.1, 0.2, SEED, first=5)
+    _, trunk, used = REF.model_plan(sd, 0.1, 0.2, SEED, first=5)
     assert trunk == (0.2, SEED, 17) and used == 12 + 2 * HP["n_layers"]
-    _, trunk, used = FD.model_plan(sd, 0.0, 0.2, SEED, first=5)                  # a rate of 0 takes no number
+    _, trunk, used = REF.model_plan(sd, 0.0, 0.2, SEED, first=5)                  # a rate of 0 takes no number
     assert trunk == (0.2, SEED, 5) and used == 2 * HP["n_layers"]
-    _, trunk, used = FD.model_plan(state_dict(False), 0.1, 0.2, SEED, first=5)   # no partial transformers: no leaves
+    _, trunk, used = REF.model_plan(state_dict(False), 0.1, 0.2, SEED, first=5)   # no partial transformers: no leaves
     assert trunk == (0.2, SEED, 5) and used == 2 * HP["n_layers"]
 
 
@@ -63,14 +59,14 @@ def test_the_host_twin_gives_the_masks_of_both_directions(i):
 
     _lib.build()
     B, T, p = 2, 3, 0.3
-    F_, C_ = FD.BLOCK_SHAPES[i]
-    assert FD.leaf_shape(i, "attnF", B, T) == (B * T, F_, C_) and FD.leaf_shape(i, "ffT", B, T) == (B * F_, T, C_)
+    F_, C_ = REF.BLOCK_SHAPES[i]
+    assert REF.leaf_shape(i, "attnF", B, T) == (B * T, F_, C_) and REF.leaf_shape(i, "ffT", B, T) == (B * F_, T, C_)
     hidden = 2 * C_
-    for j, leaf in enumerate(FD.LEAVES):
-        Bp, Tp, _ = FD.leaf_shape(i, leaf, B, T)
+    for j, leaf in enumerate(REF.LEAVES):
+        Bp, Tp, _ = REF.leaf_shape(i, leaf, B, T)
         drop = (p, SEED, 100 + 4 * i + j)
-        got = FD.leaf_masks(i, leaf, drop, B, T, hidden)
-        sites = (DR.ATTN_P, DR.ATTN_OUT) if leaf.startswith("attn") else (DR.FF_HIDDEN, DR.FF_OUT)
+        got = REF.leaf_masks(i, leaf, drop, B, T, hidden)
+        sites = (REF.ATTN_P, REF.ATTN_OUT) if leaf.startswith("attn") else (REF.FF_HIDDEN, REF.FF_OUT)
         for m, site in zip(got, sites):
             d = _lib.TrainDropout(p=p, seed=SEED, stream=drop[2])
             out = np.full(m.size, 7, dtype=np.uint8)
@@ -80,12 +76,12 @@ def test_the_host_twin_gives_the_masks_of_both_directions(i):
         # the row order: the mask row of the time direction's (b, f, t) is (b F + f) T + t, of the frequency direction's (b T + t) F + f
         rows = got[1].reshape(Bp * Tp, C_)
         if leaf == "ffT":
-            full = DR.mask(p, SEED, drop[2], DR.FF_OUT, B * F_, T, C_)
+            full = REF.mask(p, SEED, drop[2], REF.FF_OUT, B * F_, T, C_)
             b, f, t = 1, F_ - 1, T - 1
             assert np.array_equal(rows[(b * F_ + f) * T + t], full[(b * F_ + f) * T + t])
             assert np.array_equal(got[1][b * F_ + f, t], full[(b * F_ + f) * T + t])
         if leaf == "ffF":
-            full = DR.mask(p, SEED, drop[2], DR.FF_OUT, B * T, F_, C_)
+            full = REF.mask(p, SEED, drop[2], REF.FF_OUT, B * T, F_, C_)
             b, t, f = 1, T - 1, F_ - 1
             assert np.array_equal(got[1][b * T + t, f], full[(b * T + t) * F_ + f])
 
@@ -95,21 +91,21 @@ def test_dropping_one_leaf_moves_the_output_and_the_truth_tells_leaves_apart():
     the wrong stream, or the rows of the other direction, cannot pass the gate"""
     sd = state_dict()
     i, B, T = 1, 2, 3
-    F_, C_ = FD.BLOCK_SHAPES[i]
+    F_, C_ = REF.BLOCK_SHAPES[i]
     gen = torch.Generator().manual_seed(7)
     x, g = torch.randn(B, T, F_, C_, generator=gen), torch.randn(B, T, F_, C_, generator=gen)
-    drops = {leaf: (0.1, SEED, j) for j, leaf in enumerate(FD.LEAVES)}
-    g32, g64 = (FD.partial_grads(sd, i, x, g, dt, drops) for dt in (torch.float32, torch.float64))
-    keys = FD.grad_keys(g64)
+    drops = {leaf: (0.1, SEED, j) for j, leaf in enumerate(REF.LEAVES)}
+    g32, g64 = (RG.partial_grads(sd, i, x, g, dt, drops=drops) for dt in (torch.float32, torch.float64))
+    keys = RG.grad_keys(g64)
     assert len(keys) == 21
-    e_ref = max(U.rel(g32[k], g64[k]) for k in keys)
+    e_ref = max(RG.rel(g32[k], g64[k]) for k in keys)
     assert 0 < e_ref < 1e-5
-    for leaf in FD.LEAVES:
-        other = FD.partial_grads(sd, i, x, g, torch.float64, dict(drops, **{leaf: (0.1, SEED, 9)}))
-        far = max(U.rel(other[k], g64[k]) for k in keys)
-        assert far > 1e3 * U.GATE * e_ref, (leaf, far, e_ref)
-    plain = FD.partial_grads(sd, i, x, g, torch.float64, {})
-    want = FU.partial_grads(sd, i, x, g, torch.float64)
+    for leaf in REF.LEAVES:
+        other = RG.partial_grads(sd, i, x, g, torch.float64, drops=dict(drops, **{leaf: (0.1, SEED, 9)}))
+        far = max(RG.rel(other[k], g64[k]) for k in keys)
+        assert far > 1e3 * RG.GATE * e_ref, (leaf, far, e_ref)
+    plain = RG.partial_grads(sd, i, x, g, torch.float64, drops={})
+    want = RG.partial_grads(sd, i, x, g, torch.float64)
     for k in want:
         assert torch.equal(plain[k], want[k]), k
 

@@ -1,4 +1,4 @@
-"""The yardstick of 16-mixed in the differentiable frontend (tests/front_mixed_reference.py), on the CPU:
+"""The yardstick of 16-mixed in the differentiable frontend (tests/route_reference.py), on the CPU:
   1. with the rounding switched off the restatement reproduces the oracle's autograd (fp64, 1e-10 relative);
   2. for every case of tests/test_gpu_front_mixed.py the restatement alone, in fp32, is within 1.5 x e_ref16 of the fp64 truth and
      e_ref16 is finite.  The gate on the device is 2.0 (test_gpu_mixed.GATE); the device differs from the restatement only by the
@@ -10,93 +10,94 @@ import math
 import pytest
 import torch
 
-import front_mixed_reference as M
+import route_cases as RC
+import route_grads as RG
 
 D64 = torch.float64
 
 
 def _close(a, b, keys, tol=1e-10):
     for k in keys:
-        err = M.U.rel(a[k], b[k])
+        err = RG.rel(a[k], b[k])
         assert err <= tol, (k, err)
 
 
 # ---- 1. without the rounding: the oracle ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("i", [0, 1, 2])
 def test_conv_restatement_without_rounding_is_the_oracle(i):
-    sd = M.state_dict()
-    x, g = M.conv_inputs(i, 2, 3)
+    sd = RC.model_state_dict()
+    x, g = RC.conv_inputs(i, 2, 3)
     for batch in (False, True):
-        a = M.conv_grads(sd, i, x, g, D64, False, batch=batch)
-        b = M.conv_grads(sd, i, x, g, D64, None, batch=batch)
-        _close(a, b, M.grad_keys(b) + ["y"])
-        assert len(M.grad_keys(b)) == 4
+        a = RG.conv_grads(sd, i, x, g, D64, False, batch=batch)
+        b = RG.conv_grads(sd, i, x, g, D64, None, batch=batch)
+        _close(a, b, RG.grad_keys(b) + ["y"])
+        assert len(RG.grad_keys(b)) == 4
 
 
 def test_partial_and_projection_without_rounding_are_the_oracle():
-    sd = M.state_dict()
-    x, g = M.partial_inputs(1, 2, 3)
-    a, b = (M.partial_grads(sd, 1, x, g, D64, on) for on in (False, None))
-    assert len(M.grad_keys(b)) == 21
-    _close(a, b, M.grad_keys(b) + ["y"])
-    x, g = M.linear_inputs(2, 3)
-    a, b = (M.linear_grads(sd, x, g, D64, on) for on in (False, None))
-    _close(a, b, M.grad_keys(b) + ["y"])
+    sd = RC.model_state_dict()
+    x, g = RC.partial_inputs(1, 2, 3)
+    a, b = (RG.partial_grads(sd, 1, x, g, D64, on) for on in (False, None))
+    assert len(RG.grad_keys(b)) == 21
+    _close(a, b, RG.grad_keys(b) + ["y"])
+    x, g = RC.linear_inputs(2, 3)
+    a, b = (RG.linear_grads(sd, x, g, D64, on) for on in (False, None))
+    _close(a, b, RG.grad_keys(b) + ["y"])
 
 
 @pytest.mark.parametrize("partial", [True, False])
 def test_model_restatement_without_rounding_is_the_oracle(partial):
-    sd = M.state_dict("lively", partial)
-    x, beat, down, mask = M.model_inputs(2, 33, partial)
-    loss_fn = M.R.trunk_loss(beat, down, mask)
-    a, b = (M.model_grads(sd, x, loss_fn, D64, on) for on in (False, None))
-    assert len(M.grad_keys(b)) == (100 if partial else 40)
-    _close(a, b, M.grad_keys(b) + ["beat", "downbeat"])
+    sd = RC.model_state_dict("lively", partial)
+    x, beat, down, mask = RC.model_inputs(2, 33, partial)
+    loss_fn = RG.trunk_loss(beat, down, mask)
+    a, b = (RG.model_grads(sd, x, loss_fn, D64, on) for on in (False, None))
+    assert len(RG.grad_keys(b)) == (100 if partial else 40)
+    _close(a, b, RG.grad_keys(b) + ["beat", "downbeat"])
 
 
 # ---- 2. the contract alone against e_ref16, every GPU case ----------------------------------------------------------------------
 def _check(name, case, got):
     e = case["e_ref16"]
-    err, key = M.worst(got, case["truth"])
+    err, key = RG.worst(got, case["truth"])
     print(f"{name}: e_ref16 = {e:.3e} (scale {case['scale']:g}), the restatement is {err / e:.2f} x e_ref16 ({key})")
     assert math.isfinite(e) and e > 0, name
-    assert err <= M.GATE_CPU * e, (name, key, err / e)
+    assert err <= RC.GATE_CPU * e, (name, key, err / e)
 
 
-@pytest.mark.parametrize("B,T", M.CONV_SIZES)
+@pytest.mark.parametrize("B,T", RC.CONV_SIZES)
 @pytest.mark.parametrize("i", [0, 1, 2])
 def test_conv_cases(i, B, T):
-    case = M.conv_case(i, B, T)
-    _check(f"conv{i} B={B} T={T}", case, M.restate(case, "conv", i))
+    case = RC.conv_case(i, B, T)
+    _check(f"conv{i} B={B} T={T}", case, RC.restate(case, "conv", i))
 
 
-@pytest.mark.parametrize("B,T", M.BN_SIZES)
+@pytest.mark.parametrize("B,T", RC.BN_SIZES)
 @pytest.mark.parametrize("i", [0, 1, 2])
 def test_conv_batch_statistics_cases(i, B, T):
-    case = M.conv_case(i, B, T, batch=True)
-    _check(f"conv{i} batch statistics B={B} T={T}", case, M.restate(case, "conv", i, batch=True))
+    case = RC.conv_case(i, B, T, batch=True)
+    _check(f"conv{i} batch statistics B={B} T={T}", case, RC.restate(case, "conv", i, batch=True))
 
 
-@pytest.mark.parametrize("B,T", M.LINEAR_SIZES)
+@pytest.mark.parametrize("B,T", RC.LINEAR_SIZES)
 def test_projection_cases(B, T):
-    case = M.linear_case(B, T)
-    _check(f"projection B={B} T={T}", case, M.restate(case, "linear"))
+    case = RC.linear_case(B, T)
+    _check(f"projection B={B} T={T}", case, RC.restate(case, "linear"))
 
 
-@pytest.mark.parametrize("B,T", M.PARTIAL_SIZES)
+@pytest.mark.parametrize("B,T", RC.PARTIAL_SIZES)
 @pytest.mark.parametrize("i", [0, 1, 2])
 def test_partial_cases(i, B, T):
-    case = M.partial_case(i, B, T)
-    _check(f"partial{i} B={B} T={T}", case, M.restate(case, "partial", i))
+    case = RC.partial_case(i, B, T)
+    _check(f"partial{i} B={B} T={T}", case, RC.restate(case, "partial", i))
 
 
-@pytest.mark.parametrize("B,T", M.MODEL_SIZES)
+@pytest.mark.parametrize("B,T", RC.MODEL_SIZES)
 @pytest.mark.parametrize("partial", [True, False])
 @pytest.mark.parametrize("style", ["lively", "init0"])
 def test_model_cases(style, partial, B, T):
-    case = M.model_case(style, partial, B, T)
+    case = RC.model_case(style, partial, B, T)
     assert case["scale"] >= 1024.0, case["scale"]
-    _check(f"whole model {style}{'' if partial else ' no partial'} B={B} T={T}", case, M.restate(case, "model"))
+    _check(f"whole model {style}{'' if partial else ' no partial'} B={B} T={T}", case, RC.restate(case, "model"))
 
 
 # ---- 3. the opt-in keeps its books without a GPU ---------------------------------------------------------------------------------

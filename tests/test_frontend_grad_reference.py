@@ -1,5 +1,5 @@
 """CPU side of the differentiable frontend: the binding of the bt_front_* entry points, the opt-in's
-bookkeeping, the wiring through PLBeatThis / param_groups_for / the command line, and the yardstick of front_grad_util.py shown
+bookkeeping, the wiring through PLBeatThis / param_groups_for / the command line, and the yardstick of route_grads.py shown
 to discriminate the three mistakes a conv backward makes most easily."""
 import ctypes as C
 import os
@@ -8,14 +8,14 @@ import re
 import pytest
 import torch
 
-import front_grad_util as FU
-import trunk_grad_util as U
+import route_cases as RC
+import route_grads as RG
 from conftest import ROOT
+from route_harness import MODEL_KEYS
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
 
 HP = dict(transformer_dim=64, ff_mult=2, n_layers=2)
-MODEL_KEYS = ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim", "sum_head", "partial_transformers")
 
 
 def new_model(**more):
@@ -90,12 +90,12 @@ def test_the_opt_in_keeps_its_books_on_a_cpu_model():
     assert not m.frontend_trainable and all(not p.requires_grad for p in m.parameters())
     front = dict(m.frontend.named_parameters())
     weights = [n for n in front if not n.endswith("rotary_embed.freqs")]
-    assert len(weights) == len(FU.frontend_keys(m.state_dict())) == 76
+    assert len(weights) == len(RG.frontend_keys(m.state_dict())) == 76
     assert m.set_frontend_trainable() is m and m.frontend_trainable
     for n, p in front.items():
         assert p.requires_grad == (n in weights), n
     for n, b in m.named_buffers():
-        assert n.endswith(FU.STAT_LEAVES) and not b.requires_grad, n
+        assert n.endswith(RG.STAT_LEAVES) and not b.requires_grad, n
     assert all(not p.requires_grad for n, p in m.named_parameters() if not n.startswith("frontend."))
     # the route has no CPU implementation either
     with pytest.raises(RuntimeError, match="ROCm GPU"):
@@ -129,8 +129,8 @@ def test_the_module_the_groups_and_the_command_line():
     assert not frozen.model.frontend_trainable and whole.model.frontend_trainable
     assert "train_frontend" not in whole.hyper_parameters and whole.hyper_parameters == frozen.hyper_parameters
     sd = whole.model.state_dict()
-    trunk = U.trainable_keys(sd)
-    front = FU.frontend_keys(sd)
+    trunk = RG.trainable_keys(sd)
+    front = RG.frontend_keys(sd)
     count = lambda groups: [len(g["params"]) for g in groups]
     ndim2 = lambda keys: sum(sd[k].ndim >= 2 for k in keys)
     assert count(param_groups_for(frozen, 0.01)) == [ndim2(trunk), len(trunk) - ndim2(trunk)]
@@ -154,17 +154,17 @@ def test_the_module_the_groups_and_the_command_line():
 def case():
     sd = W.random_state_dict(W.resolve_hparams(HP), seed=6, style="lively")
     B, T = 2, 3
-    x = FU.spect(B, T, seed=11)
+    x = RC.spect(B, T, seed=11)
     g = torch.randn(B, T, 64, generator=torch.Generator().manual_seed(12))
-    g32, g64 = (FU.frontend_grads(sd, x, g, dt) for dt in (torch.float32, torch.float64))
+    g32, g64 = (RG.grads_only(RG.frontend_grads(sd, x, g, dt)) for dt in (torch.float32, torch.float64))
     return sd, x, g, g32, g64
 
 
 def test_every_frontend_tensor_has_a_gradient(case):
     sd, x, g, g32, g64 = case
-    assert set(g64) == set(["x"] + FU.frontend_keys(sd)) and len(g64) == 77
+    assert set(g64) == set(["x"] + RG.frontend_keys(sd)) and len(g64) == 77
     assert all(float(v.abs().max()) > 0 for v in g64.values())
-    e_ref = U.yardstick(g32, g64)
+    e_ref = RG.yardstick(g32, g64)
     print(f"e_ref = {e_ref:.3e}")
     assert 1e-7 < e_ref < 1e-4, e_ref   # (2.8e-6 .. 1.6e-5 over the cases of the issue)
 
@@ -192,7 +192,7 @@ def _conv_patch(monkeypatch, variant):
 def test_the_yardstick_discriminates(case, monkeypatch, mistake):
     """Each mistake, made on the fp32 oracle, is at least 1000 e_ref from the fp64 truth."""
     sd, x, g, g32, g64 = case
-    e_ref = U.yardstick(g32, g64)
+    e_ref = RG.yardstick(g32, g64)
     if mistake == "no BatchNorm scale in g_conv":
         real_bn = O.batchnorm
 
@@ -202,12 +202,12 @@ def test_the_yardstick_discriminates(case, monkeypatch, mistake):
         monkeypatch.setattr(O, "batchnorm", batchnorm)
     else:
         _conv_patch(monkeypatch, mistake)
-    bad = FU.frontend_grads(sd, x, g, torch.float32)
+    bad = RG.frontend_grads(sd, x, g, torch.float32)
     monkeypatch.undo()
     changed = [k for k in g64 if not torch.equal(bad[k], g32[k])]
-    worst = U.yardstick(bad, g64)
+    worst = RG.yardstick(bad, g64)
     print(f"{mistake}: {len(changed)} tensors changed, worst {worst:.3e} = {worst / e_ref:.0f} x e_ref")
     assert "x" in changed and len(changed) >= 10, changed
     assert worst >= 1000 * e_ref, (mistake, worst, e_ref)
-    again = FU.frontend_grads(sd, x, g, torch.float32)     # (the patches are gone)
+    again = RG.frontend_grads(sd, x, g, torch.float32)     # (the patches are gone)
     assert all(torch.equal(again[k], g32[k]) for k in g64)

@@ -1,5 +1,5 @@
 """The GPU backward pass of the transformer trunk and the heads (csrc/train.hip, beat_this_amd/model/backward.py) against the
-yardstick of trunk_grad_util.py: fp64 CPU autograd through the oracle is the truth, the fp32 oracle's worst tensor is e_ref,
+yardstick of route_grads.py: fp64 CPU autograd through the oracle is the truth, the fp32 oracle's worst tensor is e_ref,
 and every device gradient has to be within 10 e_ref of the truth.
 
 Tile edges of the kernels, each with a T on both sides (B = 1, so T is the number of rows):
@@ -15,9 +15,12 @@ import numpy as np
 import pytest
 import torch
 
-import trunk_grad_util as U
-from finetune_reference import shift_tolerant_bce
+import route_grads as RG
+import route_harness as H
+from route_grads import shift_tolerant_bce
+import route_reference as REF
 from gpu_util import POISONS, Guarded, assert_intact, dev, report
+from route_harness import make_batch, randn
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
 
@@ -28,32 +31,15 @@ EDGES_64 = [(1, 63), (1, 64)]                   # (65 is in SIZES)
 EDGES_1024 = [(1, 1023), (1, 1024), (1, 1025)]
 BATCH = [(3, 700)]                              # more than two BT_TRAIN_DW_ROWS chunks
 MODELS = {64: dict(transformer_dim=64, ff_mult=2), 192: dict(transformer_dim=192), 256: dict(transformer_dim=256)}
-_CACHE = {}
 
 
 def make_model(D, n_layers=2, style="lively", sum_head=True, seed=3, ff_mult=None):
     """(model on the GPU with the trunk and the heads trainable, its state dict on the CPU), built once per configuration"""
-    from beat_this_amd.model import BeatThis
-
-    key = (D, n_layers, style, sum_head, seed, ff_mult)
-    if key not in _CACHE:
-        hp = dict(MODELS.get(D, dict(transformer_dim=D)), n_layers=n_layers, sum_head=sum_head)
-        if ff_mult is not None:
-            hp["ff_mult"] = ff_mult
-        hp = W.resolve_hparams(hp)
-        sd = W.random_state_dict(hp, seed=seed, style=style)
-        m = BeatThis(**{k: hp[k] for k in ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim", "sum_head",
-                                           "partial_transformers")})
-        m.load_state_dict(sd)
-        m = m.to(dev())
-        m.transformer_blocks.requires_grad_(True)
-        m.task_heads.requires_grad_(True)
-        _CACHE[key] = (m, sd)
-    return _CACHE[key]
-
-
-def randn(*shape, seed=0, scale=1.0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
+    hp = dict(MODELS.get(D, dict(transformer_dim=D)), n_layers=n_layers, sum_head=sum_head)
+    if ff_mult is not None:
+        hp["ff_mult"] = ff_mult
+    sd = H.state_dict(hp, seed, style)
+    return H.make_model(hp, sd, cache=("backward", D, n_layers, style, sum_head, seed, ff_mult)), sd
 
 
 def device_grads(outputs, weights, x, params):
@@ -77,19 +63,19 @@ def unit_case(m, sd, kind, B, T, seed, sum_head=True):
         y = node(xd)
         params = [(prefix + n, p) for n, p in node.named_parameters() if not n.endswith("freqs")]
         got = device_grads([y], [g.to(dev())], xd, params)
-        ref = [U.oracle_unit_grads(kind, sd, prefix, x, g, dt, heads=D // 32) for dt in (torch.float32, torch.float64)]
+        ref = [RG.oracle_unit_grads(kind, sd, prefix, x, g, dt, heads=D // 32) for dt in (torch.float32, torch.float64)]
     elif kind == "norm":
         g = randn(B, T, D, seed=seed + 1)
         y = tb.norm(xd)
         got = device_grads([y], [g.to(dev())], xd, [("transformer_blocks.norm.gamma", tb.norm.gamma)])
-        ref = [U.oracle_unit_grads("norm", sd, "", x, g, dt) for dt in (torch.float32, torch.float64)]
+        ref = [RG.oracle_unit_grads("norm", sd, "", x, g, dt) for dt in (torch.float32, torch.float64)]
         ref = [{k: r[k] for k in ("x", "transformer_blocks.norm.gamma")} for r in ref]
     else:
         g = (randn(B, T, seed=seed + 1), randn(B, T, seed=seed + 2))
         out = m.task_heads(xd)
         params = [("task_heads." + n, p) for n, p in m.task_heads.named_parameters()]
         got = device_grads([out["beat"], out["downbeat"]], [t.to(dev()) for t in g], xd, params)
-        ref = [U.oracle_unit_grads("head", sd, "", x, g, dt, sum_head=sum_head) for dt in (torch.float32, torch.float64)]
+        ref = [RG.oracle_unit_grads("head", sd, "", x, g, dt, sum_head=sum_head) for dt in (torch.float32, torch.float64)]
         ref = [{k: r[k] for k in ["x"] + [n for n, _ in params]} for r in ref]
     return got, ref[0], ref[1]
 
@@ -105,7 +91,7 @@ def test_unit_against_the_yardstick(kind, D, style):
     worst = (0.0, None)
     for i, (B, T) in enumerate(sizes):
         got, g32, g64 = unit_case(m, sd, kind.split("_")[0], B, T, seed=100 + 3 * i, sum_head=sum_head)
-        e_ref, ratio = U.check(f"unit {kind} D={D} {style} B={B} T={T}", got, g32, g64)
+        e_ref, ratio = RG.check(f"unit {kind} D={D} {style} B={B} T={T}", got, g32, g64)
         worst = max(worst, (ratio, (B, T, e_ref)))
     report("backward_unit", kind=kind, D=D, style=style, worst_ratio=worst[0], at=str(worst[1]))
 
@@ -116,8 +102,8 @@ def test_outlier_weights_stay_finite():
     x = randn(B, T, D, seed=7)
     g_b, g_d = randn(B, T, seed=8), randn(B, T, seed=9)
     got = trunk_device(m, x, g_b, g_d)
-    g32, g64 = (U.oracle_trunk_grads(sd, x, g_b, g_d, dt, 2) for dt in (torch.float32, torch.float64))
-    e_ref, ratio = U.check("trunk outlier D=192", got, g32, g64, report)
+    g32, g64 = (RG.oracle_trunk_grads(sd, x, g_b, g_d, dt, 2) for dt in (torch.float32, torch.float64))
+    e_ref, ratio = RG.check("trunk outlier D=192", got, g32, g64, report)
 
 
 # ---- 2. whole trunk plus heads -----------------------------------------------------------------------------------------------
@@ -135,8 +121,8 @@ def test_trunk_and_heads_against_the_yardstick(D, L, B, T):
     x = randn(B, T, D, seed=11)
     g_b, g_d = randn(B, T, seed=12), randn(B, T, seed=13)
     got = trunk_device(m, x, g_b, g_d)
-    g32, g64 = (U.oracle_trunk_grads(sd, x, g_b, g_d, dt, L) for dt in (torch.float32, torch.float64))
-    U.check(f"trunk D={D} L={L} B={B} T={T}", got, g32, g64, report)
+    g32, g64 = (RG.oracle_trunk_grads(sd, x, g_b, g_d, dt, L) for dt in (torch.float32, torch.float64))
+    RG.check(f"trunk D={D} L={L} B={B} T={T}", got, g32, g64, report)
     assert all(p.grad is None for p in m.parameters())   # (autograd.grad: nothing was accumulated)
 
 
@@ -221,18 +207,6 @@ def test_gradients_are_bitwise_reproducible_and_batch_invariant():
 
 
 # ---- 5. through the public interface -----------------------------------------------------------------------------------------
-def make_batch(B, T, seed):
-    """the device entries of a ``ds.batch(...)`` result"""
-    gen = torch.Generator().manual_seed(seed)
-    spect = torch.log1p(torch.rand(B, T, 128, generator=gen) * 30)
-    beat = torch.rand(B, T, generator=gen) < 0.06
-    down = beat & (torch.rand(B, T, generator=gen) < 0.3)
-    mask = torch.ones(B, T, dtype=torch.bool)
-    mask[-1, T - 20:] = False
-    d = dev()
-    return dict(spect=spect.to(d), truth_beat=beat.to(d), truth_downbeat=down.to(d), padding_mask=mask.to(d))
-
-
 def model_loss(m, batch, which=("beat", "downbeat")):
     from beat_this_amd.model.loss import ShiftTolerantBCELoss
 
@@ -258,10 +232,10 @@ def param_grads(m):
 def test_through_the_public_interface():
     m, sd = make_model(64, seed=5)
     batch = make_batch(2, 150, seed=41)
-    trunk = [n for n in U.trainable_keys(sd)]
+    trunk = [n for n in RG.trainable_keys(sd)]
     with torch.no_grad():
         h = m.frontend(batch["spect"])
-    refs = [U.oracle_trunk_grads(sd, h, None, None, dt, 2, loss_fn=oracle_loss_fn(batch, dt)) for dt in (torch.float32, torch.float64)]
+    refs = [RG.oracle_trunk_grads(sd, h, None, None, dt, 2, loss_fn=oracle_loss_fn(batch, dt)) for dt in (torch.float32, torch.float64)]
     refs = [{k: r[k] for k in trunk} for r in refs]
     m.zero_grad(set_to_none=True)
     loss, out = model_loss(m, batch)
@@ -272,7 +246,7 @@ def test_through_the_public_interface():
     for n, p in m.named_parameters():
         if n.startswith("frontend.") or n.endswith("freqs"):
             assert p.grad is None, n
-    U.check("public interface D=64", got, refs[0], refs[1], report)
+    RG.check("public interface D=64", got, refs[0], refs[1], report)
     # the hooked route: the same gradients to within the gate
     seen = []
     hook = m.transformer_blocks.layers[0][0].register_forward_hook(lambda mod, i, o: seen.append(tuple(o.shape)))
@@ -282,7 +256,7 @@ def test_through_the_public_interface():
     finally:
         hook.remove()
     assert seen == [(2, 150, 64)]
-    U.check("public interface, hooked", param_grads(m), refs[0], refs[1], report)
+    RG.check("public interface, hooked", param_grads(m), refs[0], refs[1], report)
     # x.grad of a stage call; a loss on one output only; an expanded upstream gradient
     m.zero_grad(set_to_none=True)
     xd = h.clone().requires_grad_(True)
@@ -293,13 +267,13 @@ def test_through_the_public_interface():
         m.zero_grad(set_to_none=True)
         model_loss(m, batch, which)[0].backward()
         got = param_grads(m)
-        r = [U.oracle_trunk_grads(sd, h, None, None, dt, 2, loss_fn=oracle_loss_fn(batch, dt, which)) for dt in (torch.float32, torch.float64)]
-        U.check(f"public interface, only {which[0]}", got, *[{k: q[k] for k in trunk} for q in r], report)
+        r = [RG.oracle_trunk_grads(sd, h, None, None, dt, 2, loss_fn=oracle_loss_fn(batch, dt, which)) for dt in (torch.float32, torch.float64)]
+        RG.check(f"public interface, only {which[0]}", got, *[{k: q[k] for k in trunk} for q in r], report)
     m.zero_grad(set_to_none=True)
     m(batch["spect"])["beat"].sum().backward()      # (the upstream gradient is an expanded scalar)
     got = param_grads(m)
-    r = [U.oracle_trunk_grads(sd, h, None, None, dt, 2, loss_fn=lambda b, d_: b.sum()) for dt in (torch.float32, torch.float64)]
-    U.check("public interface, expanded gradient", got, *[{k: q[k] for k in trunk} for q in r], report)
+    r = [RG.oracle_trunk_grads(sd, h, None, None, dt, 2, loss_fn=lambda b, d_: b.sum()) for dt in (torch.float32, torch.float64)]
+    RG.check("public interface, expanded gradient", got, *[{k: q[k] for k in trunk} for q in r], report)
     m.zero_grad(set_to_none=True)
     # empty batches and zero frames keep a working backward
     for shape in ((0, 50, 128), (2, 0, 128)):
@@ -377,7 +351,7 @@ def test_three_sgd_steps():
         h = m.frontend(batch["spect"])
     m.transformer_blocks.requires_grad_(True)
     m.task_heads.requires_grad_(True)
-    keys = U.trainable_keys(sd)
+    keys = RG.trainable_keys(sd)
     losses = []
     for _ in range(steps + 1):
         m.zero_grad(set_to_none=True)
@@ -394,8 +368,8 @@ def test_three_sgd_steps():
         cur = {k: (v.to(dt) if v.is_floating_point() else v) for k, v in sd.items()}
         olosses = []
         for _ in range(steps + 1):
-            leaf, _x = U._leaves(cur, h, dt)
-            beat, down = U.oracle_trunk_forward(leaf, h.cpu().to(dt), 2)
+            leaf, _x = RG._leaves(cur, h, dt)
+            beat, down = REF.trunk(leaf, h.cpu().to(dt), 2)
             ol = oracle_loss_fn(batch, dt)(beat, down)
             olosses.append(float(ol.detach()))
             if len(olosses) <= steps:
@@ -410,7 +384,7 @@ def test_three_sgd_steps():
     delta = lambda cur: {k: cur[k].double().cpu() - sd[k].double() for k in keys}
     d32, d64 = delta(finals[torch.float32][0]), delta(finals[torch.float64][0])
     ddev = delta({n: p.detach() for n, p in m.named_parameters()})
-    U.check("three SGD steps, p_final - p_initial", ddev, d32, d64, report)
+    RG.check("three SGD steps, p_final - p_initial", ddev, d32, d64, report)
     m.eval()
     with torch.no_grad():
         after = m(batch["spect"])                        # (the packed weights are stale: the version check packs again)

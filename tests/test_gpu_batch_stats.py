@@ -1,5 +1,5 @@
 """Batch-statistics BatchNorm on the GPU (csrc/train_front.hip: bt_front_bn_*, backward.py: StemBatchFn / ConvUnitBatchFn,
-BeatThis.set_batch_statistics) against the truth of bn_grad_util.py: fp64 CPU autograd through the oracle's
+BeatThis.set_batch_statistics) against the truth of route_grads.py: fp64 CPU autograd through the oracle's
 frontend with torch's training-mode batch_norm, e_ref the same in fp32, every device tensor within 10 e_ref; the moved running
 buffers by the same rule (floor 1e-7), the counters exactly.
 
@@ -16,58 +16,28 @@ import numpy as np
 import pytest
 import torch
 
-import bn_grad_util as BU
-import front_grad_util as FU
-import trunk_grad_util as U
-from gpu_util import POISONS, Guarded, assert_intact, dev, report
-from beat_this_amd import weights as W
+import route_cases as RC
+import route_grads as RG
+import route_harness as H
+from gpu_util import dev, report
+from route_harness import both_poisons, randn, same_bits
+from route_harness import weighted_backward as model_device
 from oracle import beat_this_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 HP = dict(transformer_dim=64, ff_mult=2, n_layers=2)
-MODEL_KEYS = ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim", "sum_head", "partial_transformers")
 SHAPES = ((2, 1), (1, 2), (1, 3), (2, 3), (1, 63), (1, 64), (1, 65), (2, 65), (2, 150))
-_SD = {}
-
-
-def randn(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def same_bits(a, b):
-    if not a.is_floating_point():
-        return torch.equal(a, b)
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def state_dict(style="lively", partial=True, seed=6):
     """lively buffers are not the initial ones, and the counters start at 3: an update that overwrites instead of blending shows"""
-    key = (style, partial, seed)
-    if key not in _SD:
-        sd = W.random_state_dict(W.resolve_hparams(dict(HP, partial_transformers=partial)), seed=seed, style=style)
-        for k in sd:
-            if k.endswith("num_batches_tracked"):
-                sd[k] = sd[k] + 3
-        _SD[key] = sd
-    return _SD[key]
+    return H.state_dict(dict(HP, partial_transformers=partial), seed, style, counters=3)
 
 
 def new_model(style="lively", partial=True, seed=6):
-    from beat_this_amd.model import BeatThis
-
     sd = state_dict(style, partial, seed)
-    hp = W.resolve_hparams(dict(HP, partial_transformers=partial))
-    m = BeatThis(**{k: hp[k] for k in MODEL_KEYS})
-    m.load_state_dict(sd)
-    m = m.to(dev())
-    m.set_frontend_trainable()
-    m.transformer_blocks.requires_grad_(True)
-    m.task_heads.requires_grad_(True)
-    for n, p in m.named_parameters():
-        if n.endswith("rotary_embed.freqs"):
-            p.requires_grad_(False)
-    return m, sd
+    return H.make_model(dict(HP, partial_transformers=partial), sd, frontend=True, freeze_freqs=True), sd
 
 
 # ---- 1. each unit through the C ABI ------------------------------------------------------------------------------------------
@@ -87,84 +57,26 @@ def unit_spec(unit, B, T):
 def abi_unit(sd, unit, B, T, x, gy, poison):
     """forward + backward of one unit through bt_front_bn_*: every output, saved tensor, gradient, running buffer and the
     workspace in guarded, poisoned buffers -> ({"y", "x" (= gx), <key>: gradient}, {<key>: running buffer after the call})"""
-    from beat_this_amd import _lib as L
-
-    code, F_, C_, xs, ys, bns, wkey = unit_spec(unit, B, T)
-    d = dev()
-    keep = []
-
-    def guarded(shape, data=None, dtype=torch.float32):
-        g = Guarded(shape, dtype).fill(poison, data=None if data is None else data.to(d))
-        keep.append(g)
-        return g
-
-    a = L.FrontBnArgs(B=B, T=T, F=F_, C=C_)
-    a.x, a.gy, a.w = guarded(xs, x).ptr(), guarded(ys, gy).ptr(), guarded(sd[wkey].shape, sd[wkey]).ptr()
-    outs = {"y": guarded(ys), "x": guarded(xs), wkey: guarded(sd[wkey].shape)}
-    a.y, a.gx, a.g_w = outs["y"].ptr(), outs["x"].ptr(), outs[wkey].ptr()
-    if code == L.FRONT_CONV:
-        a.save_pre = guarded(ys).ptr()
-    stats = {}
-    for f, p in bns.items():
-        n = sd[p + "weight"].shape
-        setattr(a, f + "_w", guarded(n, sd[p + "weight"]).ptr())
-        setattr(a, f + "_b", guarded(n, sd[p + "bias"]).ptr())
-        stats[p + "running_mean"], stats[p + "running_var"] = guarded(n, sd[p + "running_mean"]), guarded(n, sd[p + "running_var"])
-        stats[p + "num_batches_tracked"] = guarded((1,), sd[p + "num_batches_tracked"].reshape(1), torch.int64)
-        setattr(a, f + "_mean", stats[p + "running_mean"].ptr())
-        setattr(a, f + "_var", stats[p + "running_var"].ptr())
-        setattr(a, f + "_tracked", stats[p + "num_batches_tracked"].ptr())
-        s = "save1" if f == "bn1" else "save"
-        setattr(a, s + "_mean", guarded(n).ptr())
-        setattr(a, s + "_rstd", guarded(n).ptr())
-        outs[p + "weight"], outs[p + "bias"] = guarded(n), guarded(n)
-        setattr(a, f"g_{f}_w", outs[p + "weight"].ptr())
-        setattr(a, f"g_{f}_b", outs[p + "bias"].ptr())
-    after = None
-    for backward, fn in ((0, L.lib().bt_front_bn_forward), (1, L.lib().bt_front_bn_backward)):
-        n = L.lib().bt_front_bn_workspace_bytes(code, backward, B, T, F_, C_)
-        assert n > 0
-        ws = Guarded((n,), torch.uint8).fill(poison)
-        keep.append(ws)
-        a.ws, a.ws_bytes = ws.ptr(), n
-        L.check(fn(L.stream_ptr(d), code, C.byref(a)))
-        torch.cuda.synchronize()
-        if not backward:
-            after = {k: g.t.clone().reshape(sd[k].shape) for k, g in stats.items()}
-    for k, g in stats.items():      # "never in the backward"
-        assert same_bits(g.t.reshape(sd[k].shape), after[k]), f"{unit}: the backward touched {k}"
-    assert_intact(*[(f"{unit} buffer {i}", g) for i, g in enumerate(keep)])
-    return {k: g.t.clone() for k, g in outs.items()}, after
-
-
-def both_poisons(sd, unit, B, T, x, gy):
-    """two runs from the same state under the two poison bytes: bit-identical, nothing of either poison left"""
-    res = [abi_unit(sd, unit, B, T, x, gy, p) for p in POISONS]
-    word = int.from_bytes(bytes([POISONS[1]] * 4), "little")
-    for i in (0, 1):
-        for k in res[0][i]:
-            a, b = res[0][i][k], res[1][i][k]
-            assert same_bits(a, b), f"{unit} B={B} T={T}: {k} differs between two runs (or depends on the poison)"
-            if a.is_floating_point():
-                assert torch.isfinite(a).all(), f"{unit} B={B} T={T}: {k} keeps bytes of the 0xFF poison (or is not finite)"
-                assert not (b.view(torch.int32) == word).any(), f"{unit} B={B} T={T}: {k} keeps words of the 0x7B poison"
-    return res[0]
+    if unit == "stem":
+        return H.abi_front_unit(sd, "stem", None, B, T, x, gy, poison, batch=True)
+    _, F_, C_, *_ = unit_spec(unit, B, T)
+    return H.abi_front_unit(sd, "conv", (f"frontend.blocks.{unit[4]}.", F_, C_), B, T, x, gy, poison, batch=True)
 
 
 def unit_truth(sd, unit, x, gy, dtype):
-    return BU.stem(sd, x, gy, dtype) if unit == "stem" else BU.conv(sd, int(unit[4]), x, gy, dtype)
+    return RG.bn_stem(sd, x, gy, dtype) if unit == "stem" else RG.bn_conv(sd, int(unit[4]), x, gy, dtype)
 
 
 def check_unit(unit, B, T, x, gy, name):
     sd = state_dict()
-    got, stats = both_poisons(sd, unit, B, T, x, gy)
+    got, stats = both_poisons(f"{unit} B={B} T={T}", lambda p: abi_unit(sd, unit, B, T, x, gy, p))
     r32, r64 = (unit_truth(sd, unit, x, gy, dt) for dt in (torch.float32, torch.float64))
     assert all(float(v.abs().max()) > 0 for v in r64["grads"].values()), name
     assert set(stats) == set(r64["stats"])
-    BU.check(name, {k: v for k, v in got.items() if k in r64["grads"]}, stats, r32, r64, report)
-    e_y = max(U.rel(r32["y"], r64["y"]), 1e-7)
-    print(f"{name}: y e_ref = {e_y:.3e}, device error = {U.rel(got['y'], r64['y']):.3e}")
-    assert U.rel(got["y"], r64["y"]) <= U.GATE * e_y, (name, U.rel(got["y"], r64["y"]), e_y)
+    RG.check_batch(name, {k: v for k, v in got.items() if k in r64["grads"]}, stats, r32, r64, report)
+    e_y = max(RG.rel(r32["y"], r64["y"]), 1e-7)
+    print(f"{name}: y e_ref = {e_y:.3e}, device error = {RG.rel(got['y'], r64['y']):.3e}")
+    assert RG.rel(got["y"], r64["y"]) <= RG.GATE * e_y, (name, RG.rel(got["y"], r64["y"]), e_y)
 
 
 @pytest.mark.parametrize("B,T", SHAPES + ((1, 1),))
@@ -179,7 +91,7 @@ def test_unit_against_the_truth(unit, B, T):
         assert L.lib().bt_front_bn_forward(L.stream_ptr(dev()), code, C.byref(a)) == L.BT_ERR_ARG
         assert L.lib().bt_front_bn_backward(L.stream_ptr(dev()), code, C.byref(a)) == L.BT_ERR_ARG
         return
-    x = FU.spect(B, T, seed=100 + T) if unit == "stem" else randn(*xs, seed=100 + T)
+    x = RC.spect(B, T, seed=100 + T) if unit == "stem" else randn(*xs, seed=100 + T)
     check_unit(unit, B, T, x, randn(*ys, seed=200 + T), f"batch statistics {unit} B={B} T={T}")
 
 
@@ -187,22 +99,11 @@ def test_cancellation_with_a_shifted_spectrogram():
     """x in [64, 67): E[v^2] - mean^2 in fp32 would lose bn1d's variance (0.75 against 4225) to cancellation; torch's fp32
     batch_norm does not (tests/test_bn_grad_reference.py), so it is the e_ref here as everywhere"""
     B, T = 2, 65
-    x = FU.spect(B, T, seed=165) + 64
+    x = RC.spect(B, T, seed=165) + 64
     check_unit("stem", B, T, x, randn(B, T, 32, 32, seed=265), "batch statistics stem B=2 T=65 shifted by 64")
 
 
 # ---- 2. the whole model --------------------------------------------------------------------------------------------------------
-def model_device(m, x, g_b, g_d):
-    m.zero_grad(set_to_none=True)
-    xd = x.to(dev()).requires_grad_(True)
-    out = m(xd)
-    (out["beat"] * g_b.to(dev())).sum().add((out["downbeat"] * g_d.to(dev())).sum()).backward()
-    got = {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
-    got["x"] = xd.grad.clone()
-    m.zero_grad(set_to_none=True)
-    return got, out["beat"].detach(), out["downbeat"].detach(), {n: b.detach().clone() for n, b in m.named_buffers()}
-
-
 @pytest.mark.parametrize("B,T", [(2, 150), (2, 1)])
 @pytest.mark.parametrize("style,partial", [("lively", True), ("init0", True), ("lively", False)])
 def test_whole_model_against_the_truth(style, partial, B, T):
@@ -211,17 +112,17 @@ def test_whole_model_against_the_truth(style, partial, B, T):
     of the order 1e8 and the gate says nothing there; the units' own tests cover n = 2.)"""
     m, sd = new_model(style, partial)
     m.train().set_batch_statistics()
-    x = FU.spect(B, T, seed=500 + T)
+    x = RC.spect(B, T, seed=500 + T)
     g_b, g_d = randn(B, T, seed=501), randn(B, T, seed=502)
     got, beat, down, stats = model_device(m, x, g_b, g_d)
-    r32, r64 = (BU.model(sd, x, g_b, g_d, dt) for dt in (torch.float32, torch.float64))
+    r32, r64 = (RG.bn_model(sd, x, RG.weighted_sum(g_b, g_d, dt), dt) for dt in (torch.float32, torch.float64))
     g64 = r64["grads"]
-    assert set(g64) == set(["x"] + FU.all_keys(sd)) and len(g64) == (100 if partial else 40)
+    assert set(g64) == set(["x"] + RG.all_keys(sd)) and len(g64) == (100 if partial else 40)
     assert set(got) == set(g64), sorted(set(g64) ^ set(got))
     assert len(stats) == 15 and set(stats) == set(r64["stats"])
     name = f"batch statistics whole model {style}{'' if partial else ' no partial'} B={B} T={T}"
-    BU.check(name, got, stats, r32, r64, report)
-    for p in BU.BN_PREFIXES:
+    RG.check_batch(name, got, stats, r32, r64, report)
+    for p in RG.BN_PREFIXES:
         assert int(stats[p + "num_batches_tracked"]) == int(sd[p + "num_batches_tracked"]) + 1 == 4
         assert stats[p + "num_batches_tracked"].dtype == torch.int64
         assert not torch.equal(stats[p + "running_mean"].cpu(), sd[p + "running_mean"]), p
@@ -233,7 +134,7 @@ def test_whole_model_against_the_truth(style, partial, B, T):
 def test_one_frame_alone_raises_like_torch():
     m, sd = new_model()
     m.train().set_batch_statistics()
-    x = FU.spect(1, 1, seed=7).to(dev())
+    x = RC.spect(1, 1, seed=7).to(dev())
     for call in (m, m.frontend):
         with pytest.raises(ValueError, match="Expected more than 1 value per channel when training"):
             call(x)
@@ -246,7 +147,7 @@ def test_one_frame_alone_raises_like_torch():
 # ---- 3. bit identities -----------------------------------------------------------------------------------------------------------
 def test_without_batch_statistics_nothing_moves():
     B, T = 2, 65
-    x, g_b, g_d = FU.spect(B, T, seed=31), randn(B, T, seed=32), randn(B, T, seed=33)
+    x, g_b, g_d = RC.spect(B, T, seed=31), randn(B, T, seed=32), randn(B, T, seed=33)
     plain, sd = new_model()
     want = model_device(plain, x, g_b, g_d)
     opted = new_model()[0].set_batch_statistics()             # eval() with grad: the opt-in alone changes nothing
@@ -272,7 +173,7 @@ def test_without_batch_statistics_nothing_moves():
 
 def test_two_runs_from_the_same_state_are_bit_identical():
     B, T = 2, 65
-    x, g_b, g_d = FU.spect(B, T, seed=41), randn(B, T, seed=42), randn(B, T, seed=43)
+    x, g_b, g_d = RC.spect(B, T, seed=41), randn(B, T, seed=42), randn(B, T, seed=43)
     runs = []
     for _ in range(2):
         m, _ = new_model()
@@ -280,7 +181,7 @@ def test_two_runs_from_the_same_state_are_bit_identical():
         first = model_device(m, x, g_b, g_d)
         second = model_device(m, x, g_b, g_d)               # a second call moves the buffers again
         runs.append((first, second))
-        for p in BU.BN_PREFIXES:
+        for p in RG.BN_PREFIXES:
             assert int(second[3][p + "num_batches_tracked"]) == 5
             assert not same_bits(first[3][p + "running_var"], second[3][p + "running_var"])
         # the batch's statistics do not depend on the running ones: outputs and gradients repeat, bit for bit
@@ -315,7 +216,7 @@ def test_the_inference_engine_sees_the_moved_statistics():
     print("losses:", losses)
     assert losses[-1] < losses[0], losses
     now = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    for p in BU.BN_PREFIXES:
+    for p in RG.BN_PREFIXES:
         assert int(now[p + "num_batches_tracked"]) == int(sd[p + "num_batches_tracked"]) + 4
     with torch.no_grad():                                     # train() mode still: no_grad alone selects the running statistics
         after = m(batch["spect"])
@@ -325,7 +226,7 @@ def test_the_inference_engine_sees_the_moved_statistics():
     with torch.no_grad():
         ob, od = O.model_forward(now, x)
         stale = dict(now)
-        stale.update({k: v for k, v in sd.items() if k.endswith(FU.STAT_LEAVES)})
+        stale.update({k: v for k, v in sd.items() if k.endswith(RG.STAT_LEAVES)})
         sb, sdown = O.model_forward(stale, x)
     err = max(float((after["beat"].cpu() - ob).abs().max()), float((after["downbeat"].cpu() - od).abs().max()))
     apart = max(float((ob - sb).abs().max()), float((od - sdown).abs().max()))
@@ -367,7 +268,7 @@ def test_fit_with_batch_statistics_resumes_bit_for_bit(tmp_path):
     for k, v in a["state_dict"].items():
         assert same_bits(v, b["state_dict"][k]), k
     sa, sb = a["optimizer_states"][0], b["optimizer_states"][0]
-    assert len(sa["state"]) == len(sb["state"]) == len(FU.all_keys(pl.model.state_dict()))
+    assert len(sa["state"]) == len(sb["state"]) == len(RG.all_keys(pl.model.state_dict()))
     for i in sa["state"]:
         for k in ("step", "exp_avg", "exp_avg_sq"):
             assert torch.equal(torch.as_tensor(sa["state"][i][k]), torch.as_tensor(sb["state"][i][k])), (i, k)

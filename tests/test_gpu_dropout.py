@@ -1,6 +1,6 @@
 """Dropout on the fine-tuning route (csrc/dropout.h, csrc/train.hip, BeatThis.enable_dropout, fit): the device against fp64
-torch on the CPU that applies the masks of the numpy restatement (dropout_reference.py, finetune_reference.py), with the yardstick of
-trunk_grad_util.py -- e_ref is the same computation in fp32, and the outputs and every gradient have to be within 10 e_ref.
+torch on the CPU that applies the masks of the numpy restatement (route_reference.py), with the yardstick of
+route_grads.py -- e_ref is the same computation in fp32, and the outputs and every gradient have to be within 10 e_ref.
 One wrong mask bit in the forward, the dQ or the dK / dV sweep moves an element by about 1 / T relative, decades over that.
 
 Sizes: T = 1, 63, 64, 65, 130, 257 sit on both sides of the 64-wide attention blocks and GEMM tiles, cover T % 4 != 0 (a
@@ -17,13 +17,16 @@ import numpy as np
 import pytest
 import torch
 
-import trunk_grad_util as U
-from finetune_reference import attention_drop, feedforward_drop, shift_tolerant_bce, unit_masks
+import route_grads as RG
+import route_harness as H
+import route_reference as REF
 from conftest import ROOT
 from dataset_reference import build_data_folder
 from gpu_util import POISONS, Guarded, assert_intact, dev, report
+from route_grads import shift_tolerant_bce
+from route_harness import make_batch, randn, same_bits
+from route_reference import unit_masks
 from beat_this_amd import weights as W
-from oracle import beat_this_oracle as O
 
 pytestmark = pytest.mark.gpu
 
@@ -32,52 +35,30 @@ B = 2
 SEED = 0x5EED_0000_0000_0001          # (beyond 32 bits: both key words are in use)
 FIELDS = dict(attn=dict(gamma="norm.gamma", w1="to_qkv.weight", w2="to_gates.weight", b2="to_gates.bias", w3="to_out.0.weight"),
               ff=dict(gamma="net.0.gamma", w1="net.1.weight", b1="net.1.bias", w2="net.4.weight", b2="net.4.bias"))
-_CACHE = {}
-
-
-def randn(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
 
 def make_model(D, n_layers=2, seed=3):
     """(BeatThis on the GPU with the trunk and the heads trainable, its state dict on the CPU), once per configuration"""
-    from beat_this_amd.model import BeatThis
-
-    if (D, n_layers, seed) not in _CACHE:
-        hp = W.resolve_hparams(dict(transformer_dim=D, ff_mult=2, n_layers=n_layers))
-        sd = W.random_state_dict(hp, seed=seed, style="lively")
-        m = BeatThis(**{k: hp[k] for k in ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim")})
-        m.load_state_dict(sd)
-        m = m.to(dev())
-        m.transformer_blocks.requires_grad_(True)
-        m.task_heads.requires_grad_(True)
-        _CACHE[(D, n_layers, seed)] = (m, sd)
-    return _CACHE[(D, n_layers, seed)]
+    hp = dict(transformer_dim=D, ff_mult=2, n_layers=n_layers)
+    sd = H.state_dict(hp, seed, "lively")
+    return H.make_model(hp, sd, cache=("dropout", D, n_layers, seed)), sd
 
 
 def unit_state_dict(D, ff_mult=2):
     """the ``lively`` weights of a 2-layer trunk of width D and hidden width ff_mult D (a state dict only: the engine's frontend
     cannot be built at D = 96, ff_mult 2, and the unit calls need nothing of it but the rotary table, which does not depend on the
     width)"""
-    if ("sd", D, ff_mult) not in _CACHE:
-        _CACHE[("sd", D, ff_mult)] = W.random_state_dict(W.resolve_hparams(dict(transformer_dim=D, ff_mult=ff_mult, n_layers=2)), seed=3,
-                                                        style="lively")
-    return _CACHE[("sd", D, ff_mult)]
+    return H.state_dict(dict(transformer_dim=D, ff_mult=ff_mult, n_layers=2), 3, "lively")
 
 
 def unit_truth(kind, sd, pfx, x, g, dtype, masks, p, residual):
     """{"y", "x", <state dict key>: ..}: the unit's output and the gradients of sum(y g) in ``dtype`` on the CPU"""
-    leaf, xl = U._leaves(sd, x, dtype)
-    m0, m1 = (torch.from_numpy(m).to(dtype) for m in masks)
-    c = 1.0 / (1.0 - p)
-    if kind == "attn":
-        y = attention_drop(xl, leaf, pfx, x.shape[2] // 32, m0, m1, c)
-    else:
-        y = feedforward_drop(xl, leaf, pfx, m0, m1, c)
+    leaf, xl = RG._leaves(sd, x, dtype)
+    y = REF.unit(kind, xl, leaf, pfx, None, REF.masks_as(masks, dtype), 1.0 / (1.0 - p))
     if residual:
         y = y + xl
     (y * g.to(dtype)).sum().backward()
-    out = U._collect(leaf, xl, [pfx + n for n in FIELDS[kind].values()])
+    out = RG._collect(leaf, xl, [pfx + n for n in FIELDS[kind].values()])
     out["y"] = y.detach()
     return out
 
@@ -164,10 +145,6 @@ class Unit:
         return res
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 # ---- 1. units against the truth ---------------------------------------------------------------------------------------------------
 # D -> (ff_mult, the T of TS, the rates): two and three heads at hidden = 2 D over every size; four heads at the shipped model's
 # ratio hidden = 4 D on both sides of a second 64-row block
@@ -191,7 +168,7 @@ def test_unit_against_the_truth(kind, D):
                 got = u.run((p, SEED, stream))
                 masks = unit_masks(kind, p, SEED, stream, B, T, D, ff_mult * D)
                 g32, g64 = (unit_truth(kind, sd, u.pfx, x, g, dt, masks, p, residual) for dt in (torch.float32, torch.float64))
-                e_ref, ratio = U.check(f"dropout {kind} D={D} T={T} p={p} residual={residual}", got, g32, g64)
+                e_ref, ratio = RG.check(f"dropout {kind} D={D} T={T} p={p} residual={residual}", got, g32, g64)
                 worst = max(worst, (ratio, (T, p, residual, e_ref)))
     report("dropout_unit", kind=kind, D=D, worst_ratio=worst[0], at=str(worst[1]))
 
@@ -235,17 +212,6 @@ def test_determinism_guard_bands_and_poison(kind):
 
 
 # ---- 4. the model -------------------------------------------------------------------------------------------------------------------
-def make_batch(Bn, T, seed):
-    gen = torch.Generator().manual_seed(seed)
-    spect = torch.log1p(torch.rand(Bn, T, 128, generator=gen) * 30)
-    beat = torch.rand(Bn, T, generator=gen) < 0.06
-    down = beat & (torch.rand(Bn, T, generator=gen) < 0.3)
-    mask = torch.ones(Bn, T, dtype=torch.bool)
-    mask[-1, T - 20:] = False
-    d = dev()
-    return dict(spect=spect.to(d), truth_beat=beat.to(d), truth_downbeat=down.to(d), padding_mask=mask.to(d))
-
-
 def model_loss(m, batch):
     from beat_this_amd.model.loss import ShiftTolerantBCELoss
 
@@ -265,21 +231,12 @@ def loss_and_grads(m, batch):
 
 def trunk_truth(sd, h, batch, dtype, n_layers, p, seed, first_stream):
     """gradients of the loss through the trunk with the masks of streams first_stream .. first_stream + 2 L - 1 and the heads"""
-    leaf, xl = U._leaves(sd, h, dtype)
-    Bn, T, D = h.shape
-    c = 1.0 / (1.0 - p)
-    x = xl
-    for l in range(n_layers):
-        pfx = f"transformer_blocks.layers.{l}."
-        ma = [torch.from_numpy(t).to(dtype) for t in unit_masks("attn", p, seed, first_stream + 2 * l, Bn, T, D, 2 * D)]
-        mf = [torch.from_numpy(t).to(dtype) for t in unit_masks("ff", p, seed, first_stream + 2 * l + 1, Bn, T, D, 2 * D)]
-        x = attention_drop(x, leaf, pfx + "0.", D // 32, *ma, c) + x
-        x = feedforward_drop(x, leaf, pfx + "1.", *mf, c) + x
-    beat, down = U.head_outputs(O.rmsnorm(x, leaf["transformer_blocks.norm.gamma"]), leaf, True)
+    leaf, xl = RG._leaves(sd, h, dtype)
+    beat, down = REF.trunk(leaf, xl, n_layers, drop=(p, seed, first_stream))
     t = {k: batch["truth_" + k].cpu().to(dtype) for k in ("beat", "downbeat")}
     mask = batch["padding_mask"].cpu().to(dtype)
     (shift_tolerant_bce(beat, t["beat"], mask) + shift_tolerant_bce(down, t["downbeat"], mask)).backward()
-    out = U._collect(leaf, xl, U.trainable_keys(sd))
+    out = RG._collect(leaf, xl, RG.trainable_keys(sd))
     out.pop("x")
     return out
 
@@ -310,7 +267,7 @@ def test_the_model_opts_in_and_repeats_from_its_state():
         with torch.no_grad():
             h = m.frontend(batch["spect"])
         g32, g64 = (trunk_truth(sd, h, batch, dt, L_, 0.2, SEED, 0) for dt in (torch.float32, torch.float64))
-        U.check("dropout model D=64 L=2 T=130", g_first, g32, g64, report)
+        RG.check("dropout model D=64 L=2 T=130", g_first, g32, g64, report)
         # capture with dropout active is refused; the eval() model captures as ever (tests/test_gpu_backward.py)
         xd = h.clone().requires_grad_(True)
         m.transformer_blocks(xd)                                    # (warm: the rotary table and the allocator have seen the shapes)

@@ -19,7 +19,7 @@ import ema_reference as R
 from dataset_reference import build_data_folder
 from gpu_util import Guarded, assert_intact, dev, report
 from test_gpu_finetune import EPOCHS, new_datamodule, new_module
-from test_gpu_optim import make_batch, make_model, model_loss, new_optimizer
+from test_gpu_optim import bits, make_batch, make_model, model_loss, new_optimizer
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +27,6 @@ DEFAULTS = dict(lr=8e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
 SETTINGS = [dict(DEFAULTS), dict(DEFAULTS, lr=2e-4, weight_decay=0.0)]
 POISON = 0xFF
 DECAY = 0.9
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 def tbits(t):

@@ -1,4 +1,4 @@
-"""``fit()`` end to end against an independent loop (tests/finetune_reference.py): data, model, losses, backward, accumulation,
+"""``fit()`` end to end against an independent loop (tests/route_grads.py): data, model, losses, backward, accumulation,
 clipping, AdamW and the schedule crossed in one run, on the seeded synthetic data folder with the D = 64, 2-layer, ff_mult 2
 model (``lively`` weights of seed 3) at train_length 150 -- two full 64-row attention and GEMM tiles plus a ragged one, one padded
 piece (``a_short``, 97 frames) and one without downbeat annotation (``b_one``).
@@ -6,7 +6,7 @@ piece (``a_short``, 97 frames) and one without downbeat annotation (``b_one``).
 ``fit`` is observed, not changed: the batches it draws are cloned to the CPU, ``training_step`` leaves its losses,
 ``optimizer.step`` its gradient norm and the groups' rates, the ``log`` callback keeps each epoch's checkpoint.  The truth is the
 helper in fp64 over the recorded batches (``h`` = the frozen frontend's output on the device); ``e_ref`` is the helper in fp32,
-worst tensor; the gate is trunk_grad_util.GATE.  tests/test_finetune_reference.py shows what the gate separates.
+worst tensor; the gate is route_grads.GATE.  tests/test_finetune_reference.py shows what the gate separates.
 
 Cases, one ``fit`` of two epochs each:
   A  batch 2, accumulate 1, no clipping, default decay, pos_weights 1, validation after every epoch
@@ -21,9 +21,8 @@ import numpy as np
 import pytest
 import torch
 
-import finetune_reference as FR
+import route_grads as RG
 import metrics_reference as MR
-import trunk_grad_util as U
 from dataset_reference import build_data_folder
 from gpu_util import dev, report
 from beat_this_amd import weights as W
@@ -141,7 +140,7 @@ def observed_fit(case, folder, tmp):
     settings = dict(n_layers=HP["n_layers"], lr=LR, weight_decay=c["weight_decay"], warmup=WARMUP, total_steps=EPOCHS * rec["steps_per_epoch"],
                     accumulate=c["accumulate"], max_grad_norm=c["max_grad_norm"], pos_weights=c["pos_weights"], epochs=EPOCHS,
                     batches_per_epoch=per_epoch, dropout=(0.2, DROPOUT_SEED) if c["dropout"] else None)
-    rec["truth"], rec["yard"] = (FR.run(sd, rec["batches"], dt, **settings) for dt in (torch.float64, torch.float32))
+    rec["truth"], rec["yard"] = (RG.run(sd, rec["batches"], dt, **settings) for dt in (torch.float64, torch.float32))
     return rec
 
 
@@ -173,7 +172,7 @@ def vector(values):
 def test_fit_follows_the_fp64_loop(observed, case):
     rec = observed(case)
     c, sd, truth, yard, history = CASES[case], rec["sd"], rec["truth"], rec["yard"], rec["history"]
-    keys = U.trainable_keys(sd)
+    keys = RG.trainable_keys(sd)
     # ---- what the run was made of -------------------------------------------------------------------------------------------------
     per_epoch, n_steps = rec["per_epoch"], EPOCHS * rec["steps_per_epoch"]
     assert per_epoch == 5 // c["batch_size"] and len(rec["batches"]) == EPOCHS * per_epoch == len(rec["losses"])
@@ -187,7 +186,7 @@ def test_fit_follows_the_fp64_loop(observed, case):
     assert rec["configured"] == [dict(total_steps=n_steps, max_grad_norm=c["max_grad_norm"], accumulate=c["accumulate"])]
     for s, (step, want) in enumerate(zip(rec["steps"], truth["steps"])):
         # the scheduler multiplies the base rate by numpy's cosine, the helper by math's: equal once both are rounded to fp32
-        closed = np.float32(LR * FR.lr_factor(s, WARMUP, n_steps))
+        closed = np.float32(LR * RG.lr_factor(s, WARMUP, n_steps))
         assert closed == np.float32(want["lr"])
         assert [np.float32(r) for r in step["lrs"]] == [closed, closed], (s, step["lrs"], closed)
         assert step["accumulated"] == want["count"], (s, step["accumulated"], want["count"])
@@ -214,24 +213,24 @@ def test_fit_follows_the_fp64_loop(observed, case):
     assert len(rec["checkpoints"]) == EPOCHS
     for e, ckpt in enumerate(rec["checkpoints"]):
         got = {k: ckpt["state_dict"]["model." + k] for k in keys}
-        U.check(f"trajectory {case} epoch {e}: p - p_initial", FR.displacement(got, sd),
-                FR.displacement(yard["epochs"][e]["params"], sd), FR.displacement(truth["epochs"][e]["params"], sd), report)
+        RG.check(f"trajectory {case} epoch {e}: p - p_initial", RG.displacement(got, sd),
+                RG.displacement(yard["epochs"][e]["params"], sd), RG.displacement(truth["epochs"][e]["params"], sd), report)
         state = ckpt["optimizer_states"][0]["state"]
         assert sorted(state) == list(range(len(index)))
         for moment in ("exp_avg", "exp_avg_sq"):
             got = {index[i]: state[i][moment] for i in state}
-            U.check(f"trajectory {case} epoch {e}: {moment}", got, yard["epochs"][e][moment], truth["epochs"][e][moment], report)
+            RG.check(f"trajectory {case} epoch {e}: {moment}", got, yard["epochs"][e][moment], truth["epochs"][e][moment], report)
     # ---- per batch: the losses; per step: the norms and which steps clip -------------------------------------------------------
     for j, which in enumerate(("beat", "downbeat", "total")):
-        U.check(f"trajectory {case}: {which} loss per batch", {which: vector(l[which] for l in rec["losses"])},
+        RG.check(f"trajectory {case}: {which} loss per batch", {which: vector(l[which] for l in rec["losses"])},
                 {which: vector(l[j] for l in yard["losses"])}, {which: vector(l[j] for l in truth["losses"])}, report)
     for b, got, want in zip(rec["batches"], rec["losses"], truth["losses"]):
         if not bool(b["downbeat_mask"].any()):
             assert got["downbeat"] == 0.0 == want[1]
-    e_loss = U.rel(vector(l[2] for l in yard["losses"]), vector(l[2] for l in truth["losses"]))
+    e_loss = RG.rel(vector(l[2] for l in yard["losses"]), vector(l[2] for l in truth["losses"]))
     for e in range(EPOCHS):
         mean = float(np.mean([l["total"] for l in rec["losses"][e * per_epoch:(e + 1) * per_epoch]]))
-        assert abs(history["train_loss"][e] - mean) <= U.GATE * e_loss * abs(mean), (e, history["train_loss"][e], mean)
+        assert abs(history["train_loss"][e] - mean) <= RG.GATE * e_loss * abs(mean), (e, history["train_loss"][e], mean)
     if c["max_grad_norm"] is not None:
         limit = c["max_grad_norm"]
         norms = [s["norm"] for s in truth["steps"]]
@@ -239,7 +238,7 @@ def test_fit_follows_the_fp64_loop(observed, case):
         print("gradient norms, fp64:", norms, "device:", [s["norm"] for s in rec["steps"]])
         assert any(clipped) and not all(clipped)
         assert all(abs(n - limit) > 0.05 * limit for n in norms), norms
-        U.check(f"trajectory {case}: gradient norm per step", {"norm": vector(s["norm"] for s in rec["steps"])},
+        RG.check(f"trajectory {case}: gradient norm per step", {"norm": vector(s["norm"] for s in rec["steps"])},
                 {"norm": vector(s["norm"] for s in yard["steps"])}, {"norm": vector(norms)}, report)
         assert [s["norm"] + 1e-6 > limit for s in rec["steps"]] == clipped
     else:
@@ -254,7 +253,7 @@ def oracle_validation(rec, sd, batches, dtype):
     for b in batches:
         beat, down = O.model_forward(sd, b["spect"], dtype)
         n = b["spect"].shape[0]
-        sums += n * np.array([float(v) for v in FR.batch_losses(beat, down, b, dtype, c["pos_weights"])])
+        sums += n * np.array([float(v) for v in RG.batch_losses(beat, down, b, dtype, c["pos_weights"])])
         count += n
     return dict(zip(("val_loss_beat", "val_loss_downbeat", "val_loss"), sums / count))
 
@@ -320,4 +319,4 @@ def test_validation_against_the_oracle(observed, folder):
             got.setdefault(k, []).append(metrics[k])
             l32.setdefault(k, []).append(o32[k])
             l64.setdefault(k, []).append(o64[k])
-    U.check("trajectory A: validation losses", *({k: vector(v) for k, v in d.items()} for d in (got, l32, l64)), report)
+    RG.check("trajectory A: validation losses", *({k: vector(v) for k, v in d.items()} for d in (got, l32, l64)), report)

@@ -8,23 +8,9 @@ import math
 import pytest
 import torch
 
-from gpu_util import HALF, dev, frag_qk, frag_v, report, run_attn_frag, unfrag_qk, unfrag_v
+from gpu_util import HALF, _attn_ref, _mk, _pair_sd, _rel, dev, frag_qk, frag_v, report, run_attn_frag, unfrag_qk, unfrag_v
 
 pytestmark = pytest.mark.gpu
-
-
-def _mk(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g, dtype=torch.float64) * scale
-
-
-def _rel(a, ref):
-    return float((a.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
-
-
-def _attn_ref(q, k, v, gates):
-    s = q @ k.transpose(-1, -2) * math.log(2.0)  # q carries log2(e)/sqrt(d): softmax in base 2
-    return torch.softmax(s, -1) @ v * gates[..., None]
 
 
 def _is_f16():
@@ -143,22 +129,6 @@ def test_attention_frag_overflow_fallback(L, variant):
         q2[1, 200 % L, 0] = 25.0
         q2 = q2.float().to(HALF()).double()
         assert torch.equal(_run(q2, k, v, gates, SH, L, 1, variant=-2), _run(q2, k, v, gates, SH, L, 1, variant=-1))
-
-
-def _pair_sd(C, seed):
-    H = C // 32
-    g = torch.Generator().manual_seed(seed)
-
-    def rn(*shape, s=1.0):
-        return torch.randn(*shape, generator=g, dtype=torch.float64) * s
-    return {
-        "a.norm.gamma": 1 + 0.1 * rn(C), "a.to_qkv.weight": rn(3 * C, C, s=1.6 / math.sqrt(C)),
-        "a.to_gates.weight": rn(H, C, s=0.3), "a.to_gates.bias": rn(H, s=0.3),
-        "a.to_out.0.weight": rn(C, C, s=1 / math.sqrt(C)),
-        "f.net.0.gamma": 1 + 0.1 * rn(C), "f.net.1.weight": rn(4 * C, C, s=1 / math.sqrt(C)),
-        "f.net.1.bias": rn(4 * C, s=0.2), "f.net.4.weight": rn(C, 4 * C, s=0.5 / math.sqrt(C)),
-        "f.net.4.bias": rn(C, s=0.2),
-    }
 
 
 @pytest.mark.parametrize("C", [32, 64, 128])

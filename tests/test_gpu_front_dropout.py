@@ -1,9 +1,9 @@
 """Frontend dropout on the GPU: the dropout kernels of the training route at the shapes of the frontend's
 leaves -- width 32 with a single head, sequences of 8, 16 and 32 tokens (under the 64-query block of the fp32 sweeps and the 32-wide
 tile of the mixed ones), 130 sequences per call -- then the partial transformers, the whole model, the opt-in's bookkeeping, ``fit``
-and the command line, against front_dropout_reference.py: fp64 torch on the CPU with the masks of the host twin's contract.
+and the command line, against route_reference.py: fp64 torch on the CPU with the masks of the host twin's contract.
 
-Gates: fp32 -- the outputs and every gradient within trunk_grad_util.GATE (10) x e_ref, e_ref the same computation in fp32; 16-mixed
+Gates: fp32 -- the outputs and every gradient within route_grads.GATE (10) x e_ref, e_ref the same computation in fp32; 16-mixed
 -- within 2 x e_ref16, the distance the CPU fp16-autocast run with the same masks, at the loss scale the helper finds, keeps from
 fp64 (tests/test_gpu_mixed.py's gate).  B = 2; T = 3 (a ragged last key group inside one block) and T = 65 (a second 64-query block
 on the fp32 route, a third 32-wide tile on the mixed one).
@@ -20,46 +20,28 @@ import numpy as np
 import pytest
 import torch
 
-import bn_grad_util as BU
-import front_dropout_reference as FD
-import front_mixed_reference as FM
-import mixed_reference as R
-import trunk_grad_util as U
+import route_cases as RC
+import route_grads as RG
+import route_harness as H
+import route_reference as REF
 from conftest import ROOT
 from dataset_reference import build_data_folder
-from gpu_util import POISONS, Guarded, assert_intact, dev, report
-from beat_this_amd import weights as W
+from gpu_util import Guarded, assert_intact, dev, report
+from route_harness import MIXED_GATE, both_poisons, model_device, randn, same_bits
 
 pytestmark = pytest.mark.gpu
 
-MIXED_GATE = 2.0
 B = 2
 SEED = 0x5EED_0000_0000_0021          # (beyond 32 bits: both key words are in use)
 P_FRONT, P_TRUNK = 0.1, 0.2           # the reference's rates
-MODEL_KEYS = ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim", "sum_head", "partial_transformers")
-N_LAYERS = FM.HP["n_layers"]
+N_LAYERS = RC.HP["n_layers"]
 _MODELS = {}
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 def new_model(partial=True, dropout=None):
-    """the D = 64, two-layer model of front_mixed_reference.state_dict on the GPU, everything trainable"""
-    from beat_this_amd.model import BeatThis
-
-    hp = W.resolve_hparams(dict(FM.HP, partial_transformers=partial))
-    m = BeatThis(**{k: hp[k] for k in MODEL_KEYS}, dropout=dropout or {"frontend": P_FRONT, "transformer": P_TRUNK})
-    m.load_state_dict(FM.state_dict("lively", partial))
-    m = m.to(dev())
-    m.set_frontend_trainable()
-    m.transformer_blocks.requires_grad_(True)
-    m.task_heads.requires_grad_(True)
-    for n, p in m.named_parameters():
-        if n.endswith("rotary_embed.freqs"):
-            p.requires_grad_(False)
-    return m
+    """the D = 64, two-layer model of route_cases.model_state_dict on the GPU, everything trainable"""
+    return H.make_model(dict(RC.HP, partial_transformers=partial), RC.model_state_dict("lively", partial), frontend=True, freeze_freqs=True,
+                        dropout=dropout or {"frontend": P_FRONT, "transformer": P_TRUNK})
 
 
 def shared_model():
@@ -79,9 +61,9 @@ class Leaf:
         from beat_this_amd import _lib as L
 
         self.L, self.poison, self.mixed, self.keep = L, poison, mixed, []
-        sd, m = FM.state_dict(), shared_model()
+        sd, m = RC.model_state_dict(), shared_model()
         kind = "attn" if leaf.startswith("attn") else "ff"
-        self.keys = FD.leaf_keys(i, leaf)
+        self.keys = RG.leaf_keys(i, leaf)
         self.unit = L.UNIT_ATTN if kind == "attn" else L.UNIT_FF
         Bn, T, D = x.shape
         self.hidden = int(sd[f"frontend.blocks.{i}.partial.ff{leaf[-1]}.net.1.weight"].shape[0])
@@ -127,28 +109,9 @@ class Leaf:
         return {k: g.t.clone() for k, g in self.outs.items()}
 
 
-def both_poisons(name, run):
-    """run(poison) under both poison bytes: two runs, bit-identical, nothing of either poison left -> the first result"""
-    res = [run(q) for q in POISONS]
-    word = int.from_bytes(bytes([POISONS[1]] * 4), "little")
-    for k in res[0]:
-        assert same_bits(res[0][k], res[1][k]), f"{name}: {k} differs between two runs (or depends on the poison)"
-        assert torch.isfinite(res[0][k]).all(), f"{name}: {k} keeps bytes of the 0xFF poison (or is not finite)"
-        assert not (res[1][k].view(torch.int32) == word).any(), f"{name}: {k} keeps words of the 0x7B poison"
-    return res[0]
-
-
 def mixed_gate(name, got, truth, e_ref16, scale, extra=("y",)):
     """every gradient (and ``extra``) within 2 x e_ref16 of the fp64 truth -> the worst gradient's distance in e_ref16"""
-    keys = FD.grad_keys(truth)
-    assert np.isfinite(e_ref16) and e_ref16 > 0 and set(keys) <= set(got), name
-    errs = {k: U.rel(got[k], truth[k]) for k in list(keys) + list(extra)}
-    k = max(keys, key=errs.get)
-    print(f"{name}: e_ref16 = {e_ref16:.3e} (scale {scale:g}), worst device error = {errs[k]:.3e} ({errs[k] / e_ref16:.2f} x e_ref16, {k})")
-    for key, e in errs.items():
-        assert torch.isfinite(got[key]).all(), f"{name}: {key} is not finite"
-        assert e <= MIXED_GATE * e_ref16, f"{name}: {key} is {e:.3e} from the fp64 truth, the gate is 2 x e_ref16 = {MIXED_GATE * e_ref16:.3e}"
-    return errs[k] / e_ref16
+    return H.mixed_gate(name, got, truth, e_ref16, None, extra, scale)
 
 
 def without_stats(res):
@@ -166,22 +129,22 @@ RATES = (0.1, 0.5)
 @pytest.mark.parametrize("i,direction", LEAF_CASES)
 def test_leaves_at_the_frontends_shapes(i, direction, kind, mixed):
     leaf = kind + direction
-    Bp, Tp, C_ = FD.leaf_shape(i, leaf, B, 65)
+    Bp, Tp, C_ = REF.leaf_shape(i, leaf, B, 65)
     assert (Bp, Tp, C_) == {"F": ((130, 32, 32), (130, 16, 64), (130, 8, 128)), "T": ((64, 65, 32), (32, 65, 64), (16, 65, 128))}[direction][i]
-    sd = FM.state_dict()
+    sd = RC.model_state_dict()
     seed = 3000 + 100 * i + 10 * "FT".index(direction) + (5 if kind == "ff" else 0)
-    x, g = R.randn(Bp, Tp, C_, seed=seed), R.randn(Bp, Tp, C_, seed=seed + 1) * 2.0 ** -14
+    x, g = randn(Bp, Tp, C_, seed=seed), randn(Bp, Tp, C_, seed=seed + 1) * 2.0 ** -14
     worst = 0.0
     for p in RATES:
         drop = (p, SEED, 7000 + seed + int(10 * p))
         name = f"front dropout leaf {leaf}{i} {'mixed' if mixed else 'fp32'} ({Bp}, {Tp}, {C_}) p={p}"
         if not mixed:
             got = both_poisons(name, lambda q: Leaf(i, leaf, x, g, q, False).run(drop))
-            g32, g64 = (without_stats(FD.leaf_grads(sd, i, leaf, x, g, dt, drop)) for dt in (torch.float32, torch.float64))
-            ratio = U.check(name, got, g32, g64)[1]
+            g32, g64 = (without_stats(RG.leaf_grads(sd, i, leaf, x, g, dt, drop)) for dt in (torch.float32, torch.float64))
+            ratio = RG.check(name, got, g32, g64)[1]
         else:
-            truth, _, scale, e_ref16 = FD.mixed_yardstick(
-                lambda dt, s, auto: without_stats(FD.leaf_grads(sd, i, leaf, x, g, dt, drop, None, s, auto)))
+            truth, _, scale, e_ref16 = RG.mixed_yardstick(
+                lambda dt, s, auto: without_stats(RG.leaf_grads(sd, i, leaf, x, g, dt, drop, None, s, auto)))
             got = both_poisons(name, lambda q: Leaf(i, leaf, x, g * scale, q, True).run(drop))
             got = {k: (v if k in ("y", "save_o", "save_lse") else v / scale) for k, v in got.items()}
             ratio = mixed_gate(name, got, truth, e_ref16, scale)
@@ -196,10 +159,10 @@ def test_leaves_at_the_frontends_shapes(i, direction, kind, mixed):
 def test_partial_transformers_with_drops(i, T, mixed):
     from beat_this_amd.model import backward as bw
 
-    m, sd = shared_model(), FM.state_dict()
+    m, sd = shared_model(), RC.model_state_dict()
     node, pfx = m.frontend.blocks[i].partial, f"frontend.blocks.{i}.partial."
-    x, g = FM.partial_inputs(i, B, T)
-    drops = {leaf: (P_FRONT, SEED, 50 + 4 * i + j) for j, leaf in enumerate(FD.LEAVES)}
+    x, g = RC.partial_inputs(i, B, T)
+    drops = {leaf: (P_FRONT, SEED, 50 + 4 * i + j) for j, leaf in enumerate(REF.LEAVES)}
     name = f"front dropout partial{i} {'mixed' if mixed else 'fp32'} B={B} T={T}"
 
     def run(scale, how):
@@ -211,14 +174,14 @@ def test_partial_transformers_with_drops(i, T, mixed):
         res["y"] = y.detach()
         return res
 
-    four = [drops[leaf] for leaf in FD.LEAVES]
+    four = [drops[leaf] for leaf in REF.LEAVES]
     if not mixed:
         got, again = run(1.0, four), run(1.0, iter(four).__next__)          # four values, or a callable that yields them
-        g32, g64 = (without_stats(FD.partial_grads(sd, i, x, g, dt, drops)) for dt in (torch.float32, torch.float64))
-        ratio = U.check(name, got, g32, g64)[1]
+        g32, g64 = (without_stats(RG.partial_grads(sd, i, x, g, dt, drops=drops)) for dt in (torch.float32, torch.float64))
+        ratio = RG.check(name, got, g32, g64)[1]
     else:
-        truth, _, scale, e_ref16 = FD.mixed_yardstick(
-            lambda dt, s, auto: without_stats(FD.partial_grads(sd, i, x, g, dt, drops, None, s, auto)))
+        truth, _, scale, e_ref16 = RG.mixed_yardstick(
+            lambda dt, s, auto: without_stats(RG.partial_grads(sd, i, x, g, dt, None, s, auto, drops=drops)))
         got, again = run(scale, four), run(scale, iter(four).__next__)
         ratio = mixed_gate(name, got, truth, e_ref16, scale)
     assert len(got) == 22 and all(same_bits(got[k], again[k]) for k in got)
@@ -230,35 +193,20 @@ def test_partial_transformers_with_drops(i, T, mixed):
 
 
 # ---- 3. the whole model ------------------------------------------------------------------------------------------------------------
-def model_device(m, x, beat, down, mask, scale=1.0):
-    from beat_this_amd.model.loss import ShiftTolerantBCELoss
-
-    m.zero_grad(set_to_none=True)
-    xd = x.to(dev()).requires_grad_(True)
-    out = m(xd)
-    fn = ShiftTolerantBCELoss().to(dev())
-    loss = fn(out["beat"], beat.to(dev()), mask.to(dev()).bool()) + fn(out["downbeat"], down.to(dev()), mask.to(dev()).bool())
-    (loss * scale).backward()
-    res = {n: p.grad / scale for n, p in m.named_parameters() if p.grad is not None}
-    res.update(x=xd.grad / scale, beat=out["beat"].detach(), downbeat=out["downbeat"].detach())
-    m.zero_grad(set_to_none=True)
-    return res
-
-
 def model_inputs(T=65):
-    x, beat, down, mask = FM.model_inputs(B, T, True)
-    return x, beat, down, mask, R.trunk_loss(beat, down, mask)
+    x, beat, down, mask = RC.model_inputs(B, T, True)
+    return x, beat, down, mask, RG.trunk_loss(beat, down, mask)
 
 
 @pytest.mark.parametrize("variant", ["fp32", "batch_statistics", "mixed"])
 def test_the_whole_model_with_both_opt_ins(variant):
-    sd = FM.state_dict()
+    sd = RC.model_state_dict()
     x, beat, down, mask, loss_fn = model_inputs()
     m = new_model().train()
     m.enable_dropout(seed=SEED, frontend=True)
     first = 3                                                               # (not 0: the streams follow the counter)
     m.set_dropout_state({"seed": SEED, "calls": first})
-    plan, trunk, used = FD.model_plan(sd, P_FRONT, P_TRUNK, SEED, first)
+    plan, trunk, used = REF.model_plan(sd, P_FRONT, P_TRUNK, SEED, first)
     assert used == 12 + 2 * N_LAYERS and trunk == (P_TRUNK, SEED, first + 12)
     batch = variant == "batch_statistics"
     name = f"front dropout whole model {variant} B={B} T=65"
@@ -266,25 +214,25 @@ def test_the_whole_model_with_both_opt_ins(variant):
         m.set_batch_statistics()
     if variant == "mixed":
         m.set_frontend_precision("16-mixed").set_train_precision("16-mixed")
-        truth, auto, scale, e_ref16 = FD.mixed_yardstick(
-            lambda dt, s, a: without_stats(FD.model_grads(sd, x, loss_fn, dt, plan, trunk, None, s, a)), start=FM.SCALE)
+        truth, auto, scale, e_ref16 = RG.mixed_yardstick(
+            lambda dt, s, a: without_stats(RG.model_grads(sd, x, loss_fn, dt, None, s, a, plan_=plan, trunk_drop=trunk)), start=RG.SCALE)
         got = model_device(m, x, beat, down, mask, scale)
-        assert set(FD.grad_keys(truth)) == set(got) - {"beat", "downbeat"} and len(got) == 102
+        assert set(RG.grad_keys(truth)) == set(got) - {"beat", "downbeat"} and len(got) == 102
         ratio = mixed_gate(name, got, truth, e_ref16, scale, extra=())
         for k in ("beat", "downbeat"):
-            e16, e = U.rel(auto[k], truth[k]), U.rel(got[k], truth[k])
+            e16, e = RG.rel(auto[k], truth[k]), RG.rel(got[k], truth[k])
             print(f"{name} {k} logits: autocast {e16:.3e}, device {e:.3e}")
             assert e <= MIXED_GATE * e16, (k, e, e16)
     else:
-        r32, r64 = (FD.model_grads(sd, x, loss_fn, dt, plan, trunk, batch=batch) for dt in (torch.float32, torch.float64))
+        r32, r64 = (RG.model_grads(sd, x, loss_fn, dt, plan_=plan, trunk_drop=trunk, batch=batch) for dt in (torch.float32, torch.float64))
         got = model_device(m, x, beat, down, mask)
-        assert set(FD.grad_keys(r64)) == set(got) - {"beat", "downbeat"} and len(got) == 102
+        assert set(RG.grad_keys(r64)) == set(got) - {"beat", "downbeat"} and len(got) == 102
         if batch:
             stats = {k: v.detach().cpu() for k, v in m.state_dict().items() if k in r64["stats"]}
             as_bu = lambda r: {"grads": without_stats(r), "stats": r["stats"]}
-            ratio = BU.check(name, got, stats, as_bu(r32), as_bu(r64), report)[1]
+            ratio = RG.check_batch(name, got, stats, as_bu(r32), as_bu(r64), report)[1]
         else:
-            ratio = U.check(name, got, without_stats(r32), without_stats(r64), report)[1]
+            ratio = RG.check(name, got, without_stats(r32), without_stats(r64), report)[1]
     assert m.dropout_state() == {"seed": SEED, "calls": first + 12 + 2 * N_LAYERS, "frontend": True}
     report("front_dropout_model", variant=variant, worst_ratio=ratio)
 
@@ -380,7 +328,7 @@ def new_module(frontend_dropout, seed=11):
 
     pl = PLBeatThis(transformer_dim=64, n_layers=2, ff_mult=2, lr=LR, warmup_steps=WARMUP, max_epochs=EPOCHS, eval_trim_beats=0,
                     apply_dropout=True, dropout_seed=seed, train_frontend=True, apply_frontend_dropout=frontend_dropout)
-    pl.load_state_dict({"model." + k: v for k, v in FM.state_dict().items()})
+    pl.load_state_dict({"model." + k: v for k, v in RC.model_state_dict().items()})
     return pl.to(dev())
 
 

@@ -1,6 +1,6 @@
 """16-mixed in the differentiable frontend on the GPU (csrc/train_front_mixed.inc): the fp16 conv GEMMs
 exactly on integers, the fp16 staging, then the units, the partial transformers and the whole model within 2 x e_ref16 of the fp64
-truth (front_mixed_reference.py: e_ref16 is the autocast oracle's own error at the case's loss scale), and the contract and the
+truth (route_reference.py: e_ref16 is the autocast oracle's own error at the case's loss scale), and the contract and the
 plumbing: determinism, isolation, refused arguments, the opt-in, AdamW steps under a LossScaler, ``fit`` and the command line.
 """
 import ctypes as C
@@ -10,22 +10,17 @@ import numpy as np
 import pytest
 import torch
 
-import front_grad_util as FU
-import front_mixed_reference as M
-import trunk_grad_util as U
-from gpu_util import POISONS, Guarded, assert_intact, dev, report
+import route_cases as RC
+import route_grads as RG
+import route_harness as H
+from gpu_util import POISONS, dev, report
+from route_harness import MODEL_KEYS, both_poisons, model_device, same_bits
 from test_gpu_mixed import GATE
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
 
 pytestmark = pytest.mark.gpu
-MODEL_KEYS = ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim", "sum_head", "partial_transformers")
 FAR = 0.25   # a mixed result is at least this many e_ref16 from the truth: the restatement sits at 0.8, the fp32 route at 1e-3
-_MODELS = {}
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # ---- the units through the C ABI, guarded and poisoned -----------------------------------------------------------------------------
@@ -37,113 +32,13 @@ def conv_spec(i=None, F_=None, C_=None):
 
 
 def abi_front(sd, unit, dims, B, T, x, gy, poison, mixed):
-    """forward + backward of BT_FRONT_CONV (dims = (prefix, F, C)) or BT_FRONT_LINEAR (dims = (F, C, dim)) through bt_front_*:
-    every output, saved tensor, gradient and the workspace in guarded, poisoned buffers -> {"y", "save_pre", "x", <key>: gradient}"""
-    from beat_this_amd import _lib as L
-
-    d, keep = dev(), []
-
-    def guarded(shape, data=None):
-        g = Guarded(shape, torch.float32).fill(poison, data=None if data is None else data.to(d))
-        keep.append(g)
-        return g
-
-    a = L.FrontArgs()
-    if unit == "conv":
-        p, F_, C_ = dims
-        code, dim, ys = L.FRONT_CONV, 0, (B, T, F_ // 2, 2 * C_)
-        params = dict(w=p + "conv2d.weight", bn_w=p + "norm.weight", bn_b=p + "norm.bias", bn_mean=p + "norm.running_mean",
-                      bn_var=p + "norm.running_var")
-        grads = dict(g_w=p + "conv2d.weight", g_bn_w=p + "norm.weight", g_bn_b=p + "norm.bias")
-    else:
-        F_, C_, dim = dims
-        code, ys = L.FRONT_LINEAR, (B, T, dim)
-        params = dict(w="frontend.linear.weight", b="frontend.linear.bias")
-        grads = dict(g_w="frontend.linear.weight", g_b="frontend.linear.bias")
-    xs = (B, T, F_, C_)
-    a.B, a.T, a.F, a.C, a.dim, a.mixed = B, T, F_, C_, dim, int(mixed)
-    a.x, a.gy = guarded(xs, x).ptr(), guarded(ys, gy).ptr()
-    for f, k in params.items():
-        setattr(a, f, guarded(sd[k].shape, sd[k]).ptr())
-    outs = {"y": guarded(ys), "x": guarded(xs)}
-    a.y, a.gx = outs["y"].ptr(), outs["x"].ptr()
-    if unit == "conv":
-        outs["save_pre"] = guarded(ys)
-        a.save_pre = outs["save_pre"].ptr()
-    for f, k in grads.items():
-        outs[k] = guarded(sd[k].shape)
-        setattr(a, f, outs[k].ptr())
-    query = L.lib().bt_front_workspace_bytes_mixed if mixed else L.lib().bt_front_workspace_bytes
-    for backward, fn in ((0, L.lib().bt_front_forward), (1, L.lib().bt_front_backward)):
-        n = query(code, backward, B, T, F_, C_, dim)
-        assert n > 0 and (not mixed or n >= L.lib().bt_front_workspace_bytes(code, backward, B, T, F_, C_, dim))
-        ws = Guarded((n,), torch.uint8).fill(poison)
-        keep.append(ws)
-        a.ws, a.ws_bytes = ws.ptr(), n
-        L.check(fn(L.stream_ptr(d), code, C.byref(a)))
-        torch.cuda.synchronize()
-    assert_intact(*[(f"{unit} buffer {i}", g) for i, g in enumerate(keep)])
-    return {k: g.t.clone() for k, g in outs.items()}
+    """forward + backward of BT_FRONT_CONV (dims = (prefix, F, C)) or BT_FRONT_LINEAR (dims = (F, C, dim)) through bt_front_*"""
+    return H.abi_front_unit(sd, unit, dims, B, T, x, gy, poison, mixed)
 
 
 def abi_conv_bn(sd, i, B, T, x, gy, poison, mixed):
-    """the same of conv unit i through bt_front_bn_* -> ({"y", "save_pre", "x", <key>: gradient}, {<key>: running buffer after the
-    forward})"""
-    from beat_this_amd import _lib as L
-
-    p, F_, C_ = conv_spec(i)
-    d, keep = dev(), []
-    xs, ys, n_ch = (B, T, F_, C_), (B, T, F_ // 2, 2 * C_), (2 * C_,)
-
-    def guarded(shape, data=None, dtype=torch.float32):
-        g = Guarded(shape, dtype).fill(poison, data=None if data is None else data.to(d))
-        keep.append(g)
-        return g
-
-    wkey = p + "conv2d.weight"
-    a = L.FrontBnArgs(B=B, T=T, F=F_, C=C_, mixed=int(mixed))
-    a.x, a.gy, a.w = guarded(xs, x).ptr(), guarded(ys, gy).ptr(), guarded(sd[wkey].shape, sd[wkey]).ptr()
-    outs = {"y": guarded(ys), "save_pre": guarded(ys), "x": guarded(xs), wkey: guarded(sd[wkey].shape), p + "norm.weight": guarded(n_ch),
-            p + "norm.bias": guarded(n_ch)}
-    a.y, a.gx, a.g_w, a.g_bn_w, a.g_bn_b = (outs[k].ptr() for k in ("y", "x", wkey, p + "norm.weight", p + "norm.bias"))
-    a.save_pre, a.save_mean, a.save_rstd = outs["save_pre"].ptr(), guarded(n_ch).ptr(), guarded(n_ch).ptr()
-    a.bn_w, a.bn_b = guarded(n_ch, sd[p + "norm.weight"]).ptr(), guarded(n_ch, sd[p + "norm.bias"]).ptr()
-    stats = {p + "norm.running_mean": guarded(n_ch, sd[p + "norm.running_mean"]),
-             p + "norm.running_var": guarded(n_ch, sd[p + "norm.running_var"]),
-             p + "norm.num_batches_tracked": guarded((1,), sd[p + "norm.num_batches_tracked"].reshape(1), torch.int64)}
-    a.bn_mean, a.bn_var, a.bn_tracked = (g.ptr() for g in stats.values())
-    query = L.lib().bt_front_bn_workspace_bytes_mixed if mixed else L.lib().bt_front_bn_workspace_bytes
-    after = None
-    for backward, fn in ((0, L.lib().bt_front_bn_forward), (1, L.lib().bt_front_bn_backward)):
-        n = query(L.FRONT_CONV, backward, B, T, F_, C_)
-        assert n > 0
-        ws = Guarded((n,), torch.uint8).fill(poison)
-        keep.append(ws)
-        a.ws, a.ws_bytes = ws.ptr(), n
-        L.check(fn(L.stream_ptr(d), L.FRONT_CONV, C.byref(a)))
-        torch.cuda.synchronize()
-        if not backward:
-            after = {k: g.t.clone().reshape(sd[k].shape) for k, g in stats.items()}
-    for k, g in stats.items():
-        assert torch.equal(g.t.reshape(sd[k].shape), after[k]), f"conv{i}: the backward touched {k}"
-    assert_intact(*[(f"conv{i} buffer {j}", g) for j, g in enumerate(keep)])
-    return {k: g.t.clone() for k, g in outs.items()}, after
-
-
-def both_poisons(name, run):
-    """run(poison) under both poison bytes: two runs, bit-identical, nothing of either poison left -> the first result"""
-    res = [run(p) for p in POISONS]
-    word = int.from_bytes(bytes([POISONS[1]] * 4), "little")
-    flat = [r if isinstance(r, dict) else {**r[0], **r[1]} for r in res]
-    for k in flat[0]:
-        a, b = flat[0][k], flat[1][k]
-        if not a.is_floating_point():
-            assert torch.equal(a, b), f"{name}: {k}"
-            continue
-        assert same_bits(a, b), f"{name}: {k} differs between two runs (or depends on the poison)"
-        assert torch.isfinite(a).all(), f"{name}: {k} keeps bytes of the 0xFF poison (or is not finite)"
-        assert not (b.view(torch.int32) == word).any(), f"{name}: {k} keeps words of the 0x7B poison"
-    return res[0]
+    """the same of conv unit i through bt_front_bn_* -> (results, {<key>: running buffer after the forward})"""
+    return H.abi_front_unit(sd, "conv", conv_spec(i), B, T, x, gy, poison, mixed, batch=True)
 
 
 # ---- 1. exact on integers ----------------------------------------------------------------------------------------------------------
@@ -219,30 +114,17 @@ def test_operands_are_rounded_to_fp16_as_they_are_staged(F_, Cin):
 # ---- 2. the units against the yardstick --------------------------------------------------------------------------------------------
 def gate(name, got, case, extra=("y",)):
     """every gradient (and y) within GATE x e_ref16 of the fp64 truth; -> the worst gradient's distance in e_ref16"""
-    truth, e = case["truth"], case["e_ref16"]
-    keys = M.grad_keys(truth)
-    assert np.isfinite(e) and e > 0 and set(keys) <= set(got), name
-    errs = {k: U.rel(got[k], truth[k]) for k in keys}
-    k = max(errs, key=errs.get)
-    print(f"{name}: e_ref16 = {e:.3e} (scale {case['scale']:g}), worst device error = {errs[k]:.3e} ({errs[k] / e:.2f} x e_ref16, {k})")
-    for key in extra:
-        errs[key] = U.rel(got[key], truth[key])
-        print(f"{name}: {key} {errs[key]:.3e} ({errs[key] / e:.2f} x e_ref16)")
-    report("front_mixed", case=name, e_ref16=e, worst_ratio=errs[k] / e, worst_tensor=k)
-    for key, err in errs.items():
-        assert torch.isfinite(got[key]).all(), f"{name}: {key} is not finite"
-        assert err <= GATE * e, f"{name}: {key} is {err:.3e} from the fp64 truth, the gate is 2 x e_ref16 = {GATE * e:.3e}"
-    return max(errs[q] for q in keys) / e
+    return H.mixed_gate(name, got, case["truth"], case["e_ref16"], None, extra, case["scale"], report)
 
 
 def unscale(res, scale):
     return {k: (v if k in ("y", "save_pre") else v / scale) for k, v in res.items()}
 
 
-@pytest.mark.parametrize("B,T", M.CONV_SIZES)
+@pytest.mark.parametrize("B,T", RC.CONV_SIZES)
 @pytest.mark.parametrize("i", [0, 1, 2])
 def test_conv_units_within_twice_e_ref16(i, B, T):
-    case = M.conv_case(i, B, T)
+    case = RC.conv_case(i, B, T)
     name = f"mixed conv{i} B={B} T={T}"
     run = lambda p: abi_front(case["sd"], "conv", conv_spec(i), B, T, case["x"], case["g"] * case["scale"], p, True)
     got = unscale(both_poisons(name, run), case["scale"])
@@ -250,13 +132,13 @@ def test_conv_units_within_twice_e_ref16(i, B, T):
     assert away >= FAR, f"{name}: {away:.3f} x e_ref16 from the truth -- the fp32 route's distance, not fp16 products'"
 
 
-@pytest.mark.parametrize("B,T", M.BN_SIZES)
+@pytest.mark.parametrize("B,T", RC.BN_SIZES)
 @pytest.mark.parametrize("i", [0, 1, 2])
 def test_conv_units_with_batch_statistics(i, B, T):
     """The moved running buffers by section 18's rule with the autocast oracle as the reference: within GATE x max(e, 1e-7) of
     the fp64 update, e the autocast oracle's own distance for that buffer (it takes the moments of products of rounded operands
     rounded once more; the device's products are not rounded again)."""
-    case = M.conv_case(i, B, T, batch=True)
+    case = RC.conv_case(i, B, T, batch=True)
     name = f"mixed conv{i} batch statistics B={B} T={T}"
     sd = dict(case["sd"])
     run = lambda p: abi_conv_bn(sd, i, B, T, case["x"], case["g"] * case["scale"], p, True)
@@ -267,15 +149,15 @@ def test_conv_units_with_batch_statistics(i, B, T):
         if k.endswith("num_batches_tracked"):
             assert int(stats[k]) == int(want), k
             continue
-        e = max(U.rel(case["auto"]["stats"][k], want), 1e-7)
-        err = U.rel(stats[k], want)
+        e = max(RG.rel(case["auto"]["stats"][k], want), 1e-7)
+        err = RG.rel(stats[k], want)
         print(f"{name}: {k} autocast {e:.3e}, device {err:.3e} ({err / e:.2f} x)")
         assert torch.isfinite(stats[k]).all() and err <= GATE * e, (name, k, err, e)
 
 
-@pytest.mark.parametrize("B,T", M.LINEAR_SIZES)
+@pytest.mark.parametrize("B,T", RC.LINEAR_SIZES)
 def test_projection_within_twice_e_ref16(B, T):
-    case = M.linear_case(B, T)
+    case = RC.linear_case(B, T)
     name = f"mixed projection B={B} T={T}"
     run = lambda p: abi_front(case["sd"], "linear", (4, 256, 64), B, T, case["x"], case["g"] * case["scale"], p, True)
     got = unscale(both_poisons(name, run), case["scale"])
@@ -283,30 +165,17 @@ def test_projection_within_twice_e_ref16(B, T):
 
 
 def model_on_device(style="lively", partial=True):
-    """the D = 64 model of front_mixed_reference.state_dict on the GPU, everything trainable; one per configuration"""
-    from beat_this_amd.model import BeatThis
-
-    if (style, partial) not in _MODELS:
-        hp = W.resolve_hparams(dict(M.HP, partial_transformers=partial))
-        m = BeatThis(**{k: hp[k] for k in MODEL_KEYS})
-        m.load_state_dict(M.state_dict(style, partial))
-        m = m.to(dev())
-        m.set_frontend_trainable()
-        m.transformer_blocks.requires_grad_(True)
-        m.task_heads.requires_grad_(True)
-        for n, p in m.named_parameters():
-            if n.endswith("rotary_embed.freqs"):
-                p.requires_grad_(False)
-        _MODELS[style, partial] = m
-    return _MODELS[style, partial]
+    """the D = 64 model of route_cases.model_state_dict on the GPU, everything trainable; one per configuration"""
+    return H.make_model(dict(RC.HP, partial_transformers=partial), RC.model_state_dict(style, partial), frontend=True, freeze_freqs=True,
+                        cache=("front_mixed", style, partial))
 
 
-@pytest.mark.parametrize("B,T", M.PARTIAL_SIZES)
+@pytest.mark.parametrize("B,T", RC.PARTIAL_SIZES)
 @pytest.mark.parametrize("i", [0, 1, 2])
 def test_partial_transformers_within_twice_e_ref16(i, B, T):
     from beat_this_amd.model import backward as bw
 
-    case = M.partial_case(i, B, T)
+    case = RC.partial_case(i, B, T)
     m = model_on_device()
     node, p = m.frontend.blocks[i].partial, f"frontend.blocks.{i}.partial."
 
@@ -325,26 +194,11 @@ def test_partial_transformers_within_twice_e_ref16(i, B, T):
 
 
 # ---- 3. the whole model --------------------------------------------------------------------------------------------------------------
-def model_device(m, x, beat, down, mask, scale):
-    from beat_this_amd.model.loss import ShiftTolerantBCELoss
-
-    m.zero_grad(set_to_none=True)
-    xd = x.to(dev()).requires_grad_(True)
-    out = m(xd)
-    fn = ShiftTolerantBCELoss().to(dev())
-    loss = fn(out["beat"], beat.to(dev()), mask.to(dev()).bool()) + fn(out["downbeat"], down.to(dev()), mask.to(dev()).bool())
-    (loss * scale).backward()
-    res = {n: p.grad / scale for n, p in m.named_parameters() if p.grad is not None}
-    res.update(x=xd.grad / scale, beat=out["beat"].detach(), downbeat=out["downbeat"].detach())
-    m.zero_grad(set_to_none=True)
-    return res
-
-
-@pytest.mark.parametrize("B,T", M.MODEL_SIZES)
+@pytest.mark.parametrize("B,T", RC.MODEL_SIZES)
 @pytest.mark.parametrize("partial", [True, False])
 @pytest.mark.parametrize("style", ["lively", "init0"])
 def test_whole_model_within_twice_e_ref16(style, partial, B, T):
-    case = M.model_case(style, partial, B, T)
+    case = RC.model_case(style, partial, B, T)
     m = model_on_device(style, partial)
     name = f"mixed whole model {style}{'' if partial else ' no partial'} B={B} T={T}"
     try:
@@ -352,11 +206,11 @@ def test_whole_model_within_twice_e_ref16(style, partial, B, T):
         got = model_device(m, case["x"], case["beat"], case["down"], case["mask"], case["scale"])
     finally:
         m.set_frontend_precision("32-true").set_train_precision("32-true")
-    keys = M.grad_keys(case["truth"])
+    keys = RG.grad_keys(case["truth"])
     assert set(keys) == set(got) - {"beat", "downbeat"} and len(keys) == (100 if partial else 40)
     gate(name, got, case, extra=())
     for k in ("beat", "downbeat"):
-        e16, e = U.rel(case["auto"][k], case["truth"][k]), U.rel(got[k], case["truth"][k])
+        e16, e = RG.rel(case["auto"][k], case["truth"][k]), RG.rel(got[k], case["truth"][k])
         print(f"{name} {k} logits: autocast {e16:.3e}, device {e:.3e}")
         assert e <= GATE * e16, (k, e, e16)
 
@@ -364,7 +218,7 @@ def test_whole_model_within_twice_e_ref16(style, partial, B, T):
 # ---- 4. the contract and the plumbing --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("i", [0, 2])
 def test_a_sequence_alone_gives_the_same_input_gradient(i):
-    case = M.conv_case(i, 2, 65)
+    case = RC.conv_case(i, 2, 65)
     g = case["g"] * case["scale"]
     both = abi_front(case["sd"], "conv", conv_spec(i), 2, 65, case["x"], g, POISONS[0], True)
     alone = abi_front(case["sd"], "conv", conv_spec(i), 1, 65, case["x"][:1], g[:1], POISONS[1], True)
@@ -378,8 +232,8 @@ def test_save_pre_has_the_same_bits_on_both_statistics(i, B, T, mixed):
     """bt_front_bn_forward runs the conv GEMM of bt_front_forward with its GELU output suppressed: the saved ``pre`` of the same x
     and weight has the same bits on running and on batch statistics, fp32 and mixed.  Unit 0 has 96 and 1040 rows: across the
     64-row tile, no multiple of it, and across 1024."""
-    x, g = M.conv_inputs(i, B, T)
-    sd = M.state_dict()
+    x, g = RC.conv_inputs(i, B, T)
+    sd = RC.model_state_dict()
     running = abi_front(sd, "conv", conv_spec(i), B, T, x, g, POISONS[0], mixed)
     batch, _ = abi_conv_bn(sd, i, B, T, x, g, POISONS[1], mixed)
     assert torch.isfinite(running["save_pre"]).all() and same_bits(batch["save_pre"], running["save_pre"])
@@ -390,12 +244,12 @@ def test_the_autograd_functions_pass_the_flag_on():
     from beat_this_amd.model import BeatThis
     from beat_this_amd.model import backward as bw
 
-    hp = W.resolve_hparams(M.HP)
+    hp = W.resolve_hparams(RC.HP)
     m = BeatThis(**{k: hp[k] for k in MODEL_KEYS})     # (its own: the batch-statistics call moves its running buffers)
-    m.load_state_dict(M.state_dict())
+    m.load_state_dict(RC.model_state_dict())
     m = m.to(dev()).set_frontend_trainable()
     i, B, T = 1, 2, 3
-    case = M.conv_case(i, B, T)
+    case = RC.conv_case(i, B, T)
     blk, p, g = m.frontend.blocks[i], f"frontend.blocks.{i}.", case["g"] * case["scale"]
     for batch in (False, True):
         want = (abi_conv_bn(case["sd"], i, B, T, case["x"], g, POISONS[0], True)[0] if batch else
@@ -406,7 +260,7 @@ def test_the_autograd_functions_pass_the_flag_on():
         got = dict(zip(("x", p + "conv2d.weight", p + "norm.weight", p + "norm.bias"), grads), y=y.detach())
         for k, v in got.items():
             assert same_bits(v, want[k]), (batch, k)
-    case = M.linear_case(B, T)
+    case = RC.linear_case(B, T)
     g = case["g"] * case["scale"]
     want = abi_front(case["sd"], "linear", (4, 256, 64), B, T, case["x"], g, POISONS[0], True)
     xd = case["x"].to(dev()).requires_grad_(True)
@@ -457,26 +311,14 @@ def test_refused_arguments():
 
 
 def fresh_model():
-    from beat_this_amd.model import BeatThis
-
-    hp = W.resolve_hparams(M.HP)
-    m = BeatThis(**{k: hp[k] for k in MODEL_KEYS})
-    m.load_state_dict(M.state_dict("init0"))
-    m = m.to(dev())
-    m.set_frontend_trainable()
-    m.transformer_blocks.requires_grad_(True)
-    m.task_heads.requires_grad_(True)
-    for n, p in m.named_parameters():
-        if n.endswith("rotary_embed.freqs"):
-            p.requires_grad_(False)
-    return m
+    return H.make_model(RC.HP, RC.model_state_dict("init0"), frontend=True, freeze_freqs=True)
 
 
 def test_the_trunk_precision_alone_leaves_the_frontend_as_it_was():
     """set_train_precision("16-mixed") without the new opt-in: the whole-model gradients of a model that never opted in and of
     one that was switched to "16-mixed" and back are the same bits; with the opt-in they are others"""
     never, switched = fresh_model(), fresh_model()
-    x, beat, down, mask = M.model_inputs(2, 33, True)
+    x, beat, down, mask = RC.model_inputs(2, 33, True)
     assert never.frontend_precision == switched.frontend_precision == "32-true"
     never.set_train_precision("16-mixed")
     want = model_device(never, x, beat, down, mask, 1024.0)
@@ -520,9 +362,9 @@ def test_three_adamw_steps_with_a_loss_scaler():
     assert losses[-1] < losses[0], losses
     with torch.no_grad():
         after = m(batch["spect"])
-    sd = dict(M.state_dict("init0"))
+    sd = dict(RC.model_state_dict("init0"))
     moved = [n for n, p in m.named_parameters() if n.startswith("frontend.") and not torch.equal(p.detach().cpu(), sd[n])]
-    assert len(moved) == len(FU.frontend_keys(sd)), "every frontend weight takes part in the step"
+    assert len(moved) == len(RG.frontend_keys(sd)), "every frontend weight takes part in the step"
     sd.update({n: p.detach().cpu() for n, p in m.named_parameters()})
     with torch.no_grad():
         ob, od = O.model_forward(sd, batch["spect"].cpu())
@@ -558,7 +400,7 @@ def test_fit_with_both_precisions_mixed_resumes_bit_for_bit(tmp_path):
     for k, v in a["state_dict"].items():
         assert torch.equal(v, b["state_dict"][k]), k
     sa, sb = a["optimizer_states"][0], b["optimizer_states"][0]
-    assert len(sa["state"]) == len(sb["state"]) == len(FU.all_keys(pl.model.state_dict()))
+    assert len(sa["state"]) == len(sb["state"]) == len(RG.all_keys(pl.model.state_dict()))
     for i in sa["state"]:
         for k in ("step", "exp_avg", "exp_avg_sq"):
             assert torch.equal(torch.as_tensor(sa["state"][i][k]), torch.as_tensor(sb["state"][i][k])), (i, k)

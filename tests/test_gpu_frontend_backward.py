@@ -1,5 +1,5 @@
 """The differentiable frontend on the GPU (csrc/train_front.hip, beat_this_amd/model/backward.py) against
-the yardstick of front_grad_util.py: fp64 CPU autograd through the oracle is the truth, the fp32 oracle's worst tensor is e_ref,
+the yardstick of route_grads.py: fp64 CPU autograd through the oracle is the truth, the fp32 oracle's worst tensor is e_ref,
 and every device gradient has to be within 10 e_ref of the truth.
 
 Shapes of the unit tests, B in {1, 2} x T in {1, 2, 3, 63, 64, 65, 150}:
@@ -9,53 +9,33 @@ Shapes of the unit tests, B in {1, 2} x T in {1, 2, 3, 63, 64, 65, 150}:
   * B = 2, T = 65: the rows cross BT_TRAIN_DW_ROWS = 1024 and BT_TRAIN_CS_ROWS = 64 with a ragged last chunk.
 """
 import copy
-import ctypes as C
 import shutil
 
 import numpy as np
 import pytest
 import torch
 
-import front_grad_util as FU
-import trunk_grad_util as U
-from gpu_util import POISONS, Guarded, assert_intact, dev, report
+import route_cases as RC
+import route_grads as RG
+import route_harness as H
+import route_reference as REF
+from gpu_util import dev, report
+from route_harness import MODEL_KEYS, both_poisons, randn, same_bits
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 HP = dict(transformer_dim=64, ff_mult=2, n_layers=2)
-MODEL_KEYS = ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim", "sum_head", "partial_transformers")
 TS = (1, 2, 3, 63, 64, 65, 150)
 UNITS = ("stem", "conv0", "conv1", "conv2", "linear", "swap")
-_CACHE = {}
-
-
-def randn(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def make_model(style="lively", sum_head=True, partial=True, seed=6, trainable=True):
     """(the model on the GPU, everything trainable behind the opt-in; its state dict on the CPU), once per configuration"""
-    from beat_this_amd.model import BeatThis
-
-    key = (style, sum_head, partial, seed, trainable)
-    if key not in _CACHE:
-        hp = W.resolve_hparams(dict(HP, sum_head=sum_head, partial_transformers=partial))
-        sd = W.random_state_dict(hp, seed=seed, style=style)
-        m = BeatThis(**{k: hp[k] for k in MODEL_KEYS})
-        m.load_state_dict(sd)
-        m = m.to(dev())
-        if trainable:
-            m.set_frontend_trainable()
-            m.transformer_blocks.requires_grad_(True)
-            m.task_heads.requires_grad_(True)
-        _CACHE[key] = (m, sd)
-    return _CACHE[key]
+    hp = dict(HP, sum_head=sum_head, partial_transformers=partial)
+    sd = H.state_dict(hp, seed, style)
+    return H.make_model(hp, sd, frontend=trainable, trunk=trainable, cache=("frontend_backward", style, sum_head, partial, seed, trainable)), sd
 
 
 # ---- 1. each unit through the C ABI ------------------------------------------------------------------------------------------
@@ -88,68 +68,25 @@ def unit_spec(sd, unit, B, T):
 def abi_unit(sd, unit, B, T, x, gy, poison):
     """forward + backward of one unit with every output, saved tensor, gradient and the workspace in guarded, poisoned buffers
     -> {"y", "save_pre" (conv), "x" (= gx), <state dict key>: gradient}"""
-    from beat_this_amd import _lib as L
-
-    code, (F_, C_, dim), xs, ys, params, grads = unit_spec(sd, unit, B, T)
-    d = dev()
-    keep = []
-
-    def guarded(shape, data=None):
-        g = Guarded(shape, torch.float32).fill(poison, data=None if data is None else data.to(d))
-        keep.append(g)
-        return g
-
-    a = L.FrontArgs()
-    a.B, a.T, a.F, a.C, a.dim = B, T, F_, C_, dim
-    gx_ = guarded(xs, x)
-    a.x = gx_.ptr()
-    for f, k in params.items():
-        setattr(a, f, guarded(sd[k].shape, sd[k]).ptr())
-    outs = {"y": guarded(ys), "x": guarded(xs)}
-    a.y, a.gx = outs["y"].ptr(), outs["x"].ptr()
-    if code == L.FRONT_CONV:
-        outs["save_pre"] = guarded(ys)
-        a.save_pre = outs["save_pre"].ptr()
-    a.gy = guarded(ys, gy).ptr()
-    for f, k in grads.items():
-        outs[k] = guarded(sd[k].shape)
-        setattr(a, f, outs[k].ptr())
-    for backward, fn in ((0, L.lib().bt_front_forward), (1, L.lib().bt_front_backward)):
-        n = L.lib().bt_front_workspace_bytes(code, backward, B, T, F_, C_, dim)
-        assert n > 0
-        ws = Guarded((n,), torch.uint8).fill(poison)
-        keep.append(ws)
-        a.ws, a.ws_bytes = ws.ptr(), n
-        L.check(fn(L.stream_ptr(d), code, C.byref(a)))
-        torch.cuda.synchronize()
-    assert_intact(*[(f"{unit} buffer {i}", g) for i, g in enumerate(keep)])
-    return {k: g.t.clone() for k, g in outs.items()}
-
-
-def both_poisons(sd, unit, B, T, x, gy):
-    """the unit under both poison bytes: two runs, bit-identical, nothing of either poison left"""
-    res = [abi_unit(sd, unit, B, T, x, gy, p) for p in POISONS]
-    word = int.from_bytes(bytes([POISONS[1]] * 4), "little")
-    for k in res[0]:
-        assert same_bits(res[0][k], res[1][k]), f"{unit} B={B} T={T}: {k} differs between two runs (or depends on the poison)"
-        assert torch.isfinite(res[0][k]).all(), f"{unit} B={B} T={T}: {k} keeps bytes of the 0xFF poison (or is not finite)"
-        assert not (res[1][k].view(torch.int32) == word).any(), f"{unit} B={B} T={T}: {k} keeps words of the 0x7B poison"
-    return res[0]
+    _, (F_, C_, dim), *_ = unit_spec(sd, unit, B, T)
+    if unit.startswith("conv"):
+        return H.abi_front_unit(sd, "conv", (f"frontend.blocks.{unit[4]}.", F_, C_), B, T, x, gy, poison)
+    return H.abi_front_unit(sd, unit, {"stem": None, "linear": (F_, C_, dim), "swap": (F_, C_)}[unit], B, T, x, gy, poison)
 
 
 def unit_oracle(sd, unit, x, gy, dtype):
     """-> (y in the device's layout, gradients)"""
     if unit == "stem":
         y = O.stem(x.to(dtype), {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}).permute(0, 3, 2, 1)
-        return y, FU.stem_grads(sd, x, gy, dtype)
+        return y, RG.grads_only(RG.stem_grads(sd, x, gy, dtype))
     cast = {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}
     if unit.startswith("conv"):
         i = int(unit[4])
-        y = FU.conv_unit(FU.to_oracle(x.to(dtype)), cast, f"frontend.blocks.{i}.").permute(0, 3, 2, 1)
-        return y, FU.conv_grads(sd, i, x, gy, dtype)
+        y = REF.conv_unit(REF.to_oracle(x.to(dtype)), cast, f"frontend.blocks.{i}.").permute(0, 3, 2, 1)
+        return y, RG.grads_only(RG.conv_grads(sd, i, x, gy, dtype))
     b, t, f, c = x.shape
     rows = x.to(dtype).permute(0, 1, 3, 2).reshape(b, t, c * f)
-    return O._linear(rows, cast["frontend.linear.weight"], cast["frontend.linear.bias"]), FU.linear_grads(sd, x, gy, dtype)
+    return O._linear(rows, cast["frontend.linear.weight"], cast["frontend.linear.bias"]), RG.grads_only(RG.linear_grads(sd, x, gy, dtype))
 
 
 @pytest.mark.parametrize("T", TS)
@@ -158,9 +95,9 @@ def test_unit_against_the_yardstick(unit, T):
     m, sd = make_model()
     for B in (1, 2):
         _, _, xs, ys, _, _ = unit_spec(sd, unit, B, T)
-        x = FU.spect(B, T, seed=100 + T) if unit == "stem" else randn(*xs, seed=100 + T)
+        x = RC.spect(B, T, seed=100 + T) if unit == "stem" else randn(*xs, seed=100 + T)
         gy = randn(*ys, seed=200 + T)
-        got = both_poisons(sd, unit, B, T, x, gy)
+        got = both_poisons(f"{unit} B={B} T={T}", lambda p: abi_unit(sd, unit, B, T, x, gy, p))
         name = f"frontend {unit} B={B} T={T}"
         if unit == "swap":
             assert torch.equal(got["y"].cpu(), x.permute(0, 2, 1, 3)), name
@@ -168,9 +105,9 @@ def test_unit_against_the_yardstick(unit, T):
             continue
         (y32, g32), (y64, g64) = (unit_oracle(sd, unit, x, gy, dt) for dt in (torch.float32, torch.float64))
         assert all(float(v.abs().max()) > 0 for v in g64.values()), name
-        U.check(name, {k: v for k, v in got.items() if k in g64}, g32, g64, report)
-        e_y = max(U.rel(y32, y64), 1e-7)
-        assert U.rel(got["y"], y64) <= U.GATE * e_y, (name, U.rel(got["y"], y64), e_y)
+        RG.check(name, {k: v for k, v in got.items() if k in g64}, g32, g64, report)
+        e_y = max(RG.rel(y32, y64), 1e-7)
+        assert RG.rel(got["y"], y64) <= RG.GATE * e_y, (name, RG.rel(got["y"], y64), e_y)
 
 
 def test_projection_over_several_weight_gradient_chunks():
@@ -179,10 +116,10 @@ def test_projection_over_several_weight_gradient_chunks():
     m, sd = make_model()
     B, T = 2, 600
     x, gy = randn(B, T, 4, 256, seed=260), randn(B, T, 64, seed=261)
-    got = both_poisons(sd, "linear", B, T, x, gy)
+    got = both_poisons(f"linear B={B} T={T}", lambda p: abi_unit(sd, "linear", B, T, x, gy, p))
     (y32, g32), (y64, g64) = (unit_oracle(sd, "linear", x, gy, dt) for dt in (torch.float32, torch.float64))
-    U.check(f"frontend linear B={B} T={T}", {k: v for k, v in got.items() if k in g64}, g32, g64, report)
-    assert U.rel(got["y"], y64) <= U.GATE * max(U.rel(y32, y64), 1e-7)
+    RG.check(f"frontend linear B={B} T={T}", {k: v for k, v in got.items() if k in g64}, g32, g64, report)
+    assert RG.rel(got["y"], y64) <= RG.GATE * max(RG.rel(y32, y64), 1e-7)
 
 
 def test_the_swap_serves_both_directions_at_full_length():
@@ -215,7 +152,7 @@ def test_conv_gemms_are_exact_on_integers(i, B, T):
     gy = ri(-3, 3, B, T, Fo, Cout)
     sd = {p + "conv2d.weight": w.float(), p + "norm.weight": torch.ones(Cout), p + "norm.bias": torch.zeros(Cout),
           p + "norm.running_mean": torch.zeros(Cout), p + "norm.running_var": torch.full((Cout,), 1 - 1e-5)}
-    got = both_poisons(sd, f"conv{i}", B, T, x.float(), gy.float())
+    got = both_poisons(f"conv{i} B={B} T={T}", lambda p: abi_unit(sd, f"conv{i}", B, T, x.float(), gy.float(), p))
     xp = np.zeros((B, T + 2, Fo, 2, Cin), dtype=np.int64)
     xp[:, 1:T + 1] = x.numpy().reshape(B, T, Fo, 2, Cin)
     P = np.stack([xp[:, dt:dt + T] for dt in range(3)], axis=3)            # [b, t, f', dt, df, ci]
@@ -257,24 +194,17 @@ def test_partial_transformer_against_the_yardstick(i, B, T):
 
     (got, y), (again, _) = run(), run()
     assert all(same_bits(got[k], again[k]) for k in got)
-    g32, g64 = (FU.partial_grads(sd, i, x, g, dt) for dt in (torch.float32, torch.float64))
+    g32, g64 = (RG.grads_only(RG.partial_grads(sd, i, x, g, dt)) for dt in (torch.float32, torch.float64))
     assert set(g64) == set(got) and len(got) == 21
-    U.check(f"frontend partial{i} B={B} T={T}", got, g32, g64, report)
+    RG.check(f"frontend partial{i} B={B} T={T}", got, g32, g64, report)
     with torch.no_grad():
-        want = O.partial_ft(FU.to_oracle(x.double()), {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}, p)
-    assert U.rel(y, want.permute(0, 3, 2, 1)) < 1e-5
+        want = O.partial_ft(REF.to_oracle(x.double()), {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}, p)
+    assert RG.rel(y, want.permute(0, 3, 2, 1)) < 1e-5
 
 
 # ---- 4. the whole model ----------------------------------------------------------------------------------------------------------
 def model_device(m, x, g_b, g_d):
-    m.zero_grad(set_to_none=True)
-    xd = x.to(dev()).requires_grad_(True)
-    out = m(xd)
-    (out["beat"] * g_b.to(dev())).sum().add((out["downbeat"] * g_d.to(dev())).sum()).backward()
-    got = {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
-    got["x"] = xd.grad.clone()
-    m.zero_grad(set_to_none=True)
-    return got, out["beat"].detach(), out["downbeat"].detach()
+    return H.weighted_backward(m, x, g_b, g_d)[:3]
 
 
 @pytest.mark.parametrize("B,T", [(2, 150), (1, 1)])
@@ -282,16 +212,16 @@ def model_device(m, x, g_b, g_d):
                                                     ("lively", True, False)])
 def test_whole_model_against_the_yardstick(style, sum_head, partial, B, T):
     m, sd = make_model(style, sum_head, partial)
-    x = FU.spect(B, T, seed=500 + T)
+    x = RC.spect(B, T, seed=500 + T)
     g_b, g_d = randn(B, T, seed=501), randn(B, T, seed=502)
     got, beat, down = model_device(m, x, g_b, g_d)
     assert beat.shape == (B, T)
-    g32, g64 = (FU.model_grads(sd, x, g_b, g_d, dt, sum_head) for dt in (torch.float32, torch.float64))
-    assert set(g64) == set(["x"] + FU.all_keys(sd)) and len(g64) == (100 if partial else 40)
+    g32, g64 = (RG.grads_only(RG.model_grads(sd, x, RG.weighted_sum(g_b, g_d, dt), dt, sum_head=sum_head)) for dt in (torch.float32, torch.float64))
+    assert set(g64) == set(["x"] + RG.all_keys(sd)) and len(g64) == (100 if partial else 40)
     assert all(float(v.abs().max()) > 0 for v in g64.values())
     assert set(got) == set(g64), sorted(set(g64) ^ set(got))
     name = f"whole model {style}{'' if sum_head else ' Head'}{'' if partial else ' no partial'} B={B} T={T}"
-    U.check(name, got, g32, g64, report)
+    RG.check(name, got, g32, g64, report)
     ob, od = O.model_forward(sd, x, sum_head=sum_head)
     err = max(float((beat.cpu() - ob).abs().max()), float((down.cpu() - od).abs().max()))
     print(f"{name}: max |logit - oracle| = {err:.3e}")
@@ -366,7 +296,7 @@ def test_nothing_existing_moved():
     m.set_frontend_trainable(False)
     assert all(not p.requires_grad for p in m.frontend.parameters())
     have_route = trunk_route(m)
-    assert len(have_route) == len(want_route) == 2 + len(U.trainable_keys(sd))
+    assert len(have_route) == len(want_route) == 2 + len(RG.trainable_keys(sd))
     for i, (a, b) in enumerate(zip(have_route, want_route)):
         assert same_bits(a, b), f"trunk-only route: result {i} moved"
 
@@ -382,7 +312,7 @@ def test_a_trained_frontend_frozen_again_runs_on_its_trained_weights():
     m = BeatThis(**{k: hp[k] for k in MODEL_KEYS})
     m.load_state_dict(sd)
     m = m.to(dev())
-    x = FU.spect(2, 150, seed=71).to(dev())
+    x = RC.spect(2, 150, seed=71).to(dev())
     m.set_frontend_trainable()
     m.transformer_blocks.requires_grad_(True)
     m.task_heads.requires_grad_(True)
@@ -441,7 +371,7 @@ def test_three_adamw_steps_on_all_parameters():
     stats = {n: b.clone() for n, b in m.named_buffers()}
     assert len(stats) == 3 * 5
     opt = AdamW(param_groups_for(m, 0.01), lr=2e-3)
-    assert sum(len(g["params"]) for g in opt.param_groups) == len(FU.all_keys(sd))
+    assert sum(len(g["params"]) for g in opt.param_groups) == len(RG.all_keys(sd))
     losses = []
     for _ in range(4):
         opt.zero_grad()
@@ -455,7 +385,7 @@ def test_three_adamw_steps_on_all_parameters():
     for n, b in m.named_buffers():
         assert torch.equal(b, stats[n]) and b.dtype == stats[n].dtype, f"{n} changed in train() mode"
     moved = [n for n, p in m.named_parameters() if n.startswith("frontend.") and not torch.equal(p.detach().cpu(), sd[n])]
-    assert len(moved) == len(FU.frontend_keys(sd)), "every frontend weight takes part in the step"
+    assert len(moved) == len(RG.frontend_keys(sd)), "every frontend weight takes part in the step"
     m.eval()
     with torch.no_grad():
         after = m(batch["spect"])                        # (the packed frontend weights are stale: the version check packs again)
@@ -501,7 +431,7 @@ def test_fit_with_the_frontend_resumes_bit_for_bit(tmp_path):
     for k, v in a["state_dict"].items():
         assert torch.equal(v, b["state_dict"][k]), k
     sa, sb = a["optimizer_states"][0], b["optimizer_states"][0]
-    n_all = len(FU.all_keys(pl.model.state_dict()))
+    n_all = len(RG.all_keys(pl.model.state_dict()))
     assert len(sa["state"]) == len(sb["state"]) == n_all     # (the larger optimiser state: the frontend's weights are in it)
     for i in sa["state"]:
         for k in ("step", "exp_avg", "exp_avg_sq"):
@@ -509,7 +439,7 @@ def test_fit_with_the_frontend_resumes_bit_for_bit(tmp_path):
     fresh = new_module()
     moved = [n for (n, p), q in zip(fresh.model.named_parameters(), pl.model.parameters())
              if n.startswith("frontend.") and not torch.equal(p.detach(), q.detach())]
-    assert len(moved) == len(FU.frontend_keys(fresh.model.state_dict())), len(moved)
+    assert len(moved) == len(RG.frontend_keys(fresh.model.state_dict())), len(moved)
     for (n, p), q in zip(fresh.model.named_buffers(), pl.model.buffers()):
         assert torch.equal(p, q), f"{n} changed during fit"
     loaded = load_model(ck, dev())

@@ -7,18 +7,9 @@ import math
 import pytest
 import torch
 
-from gpu_util import HALF, dev, pad_rows, report, unfrag_qk, unfrag_v
+from gpu_util import HALF, _mk, _rel, dev, pad_rows, report, unfrag_qk, unfrag_v
 
 pytestmark = pytest.mark.gpu
-
-
-def _mk(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g, dtype=torch.float64) * scale
-
-
-def _rel(a, ref):
-    return float((a.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
 
 
 def _ssq_parts(x32):

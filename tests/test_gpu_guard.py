@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_util import (HALF, POISONS, Guarded, assert_intact, dev, gaps_intact, report, workspace_regions)
+from gpu_util import (HALF, POISONS, Guarded, _mk, assert_intact, dev, gaps_intact, report, workspace_regions)
 
 pytestmark = pytest.mark.gpu
 
@@ -476,11 +476,6 @@ def test_public_api_results_survive_repoisoned_engine_workspaces(float16):
 
 
 # ---- single kernels ----------------------------------------------------------------------------------------------------
-def _mk(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g, dtype=torch.float64) * scale
-
-
 def _pad256(w):
     """weight rows padded with zeros to a multiple of 256 (the tile height the kernel reads whole)"""
     out = torch.zeros(((w.shape[0] + 255) // 256 * 256, w.shape[1]), dtype=w.dtype)

@@ -7,21 +7,12 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_util import HALF, dev, pad_rows, report, run_attn, run_gemm, tdtype
+from gpu_util import HALF, _attn_ref, _mk, _pair_sd, _rel, dev, pad_rows, report, run_attn, run_gemm, tdtype
 
 pytestmark = pytest.mark.gpu
 
 F32, BF16 = 0, 1
 TOL = {F32: 2e-5, BF16: 2.5e-2}  # relative to the output's max-abs
-
-
-def _rel(a, ref):
-    return float((a.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
-
-
-def _mk(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g, dtype=torch.float64) * scale
 
 
 @pytest.mark.parametrize("prec", [F32, BF16])
@@ -141,12 +132,6 @@ def test_gemm_conv_gather(prec, Cin):
     assert err < TOL[prec]
 
 
-def _attn_ref(q, k, v, gates):
-    # q,k,v: (S, H, L, 32) float64, q already carries log2e/sqrt(d): softmax in base 2
-    s = q @ k.transpose(-1, -2) * math.log(2.0)
-    return torch.softmax(s, -1) @ v * gates[..., None]
-
-
 @pytest.mark.parametrize("prec", [F32, BF16])
 @pytest.mark.parametrize("n_seq,L,heads", [(3, 1500, 2), (2, 77, 1), (1, 128, 4), (5, 1012, 1)])
 def test_attention_flash(prec, n_seq, L, heads):
@@ -186,21 +171,6 @@ def test_attention_flash_time_direction_rowmap(prec):
     err = _rel(out, ref)
     report("attn_flash_rowmap", prec=prec, rel=err)
     assert err < (2e-5 if prec == F32 else 2e-2)
-
-
-def _pair_sd(C, seed):
-    H = C // 32
-    g = torch.Generator().manual_seed(seed)
-    def rn(*shape, s=1.0):
-        return torch.randn(*shape, generator=g, dtype=torch.float64) * s
-    return {
-        "a.norm.gamma": 1 + 0.1 * rn(C), "a.to_qkv.weight": rn(3 * C, C, s=1.6 / math.sqrt(C)),
-        "a.to_gates.weight": rn(H, C, s=0.3), "a.to_gates.bias": rn(H, s=0.3),
-        "a.to_out.0.weight": rn(C, C, s=1 / math.sqrt(C)),
-        "f.net.0.gamma": 1 + 0.1 * rn(C), "f.net.1.weight": rn(4 * C, C, s=1 / math.sqrt(C)),
-        "f.net.1.bias": rn(4 * C, s=0.2), "f.net.4.weight": rn(C, 4 * C, s=0.5 / math.sqrt(C)),
-        "f.net.4.bias": rn(C, s=0.2),
-    }
 
 
 @pytest.mark.parametrize("prec", [F32, BF16])

@@ -1,5 +1,5 @@
 """The 16-mixed training route on the GPU (csrc/train_mixed.inc): the fp16 MFMA GEMM exactly, the units,
-the trunk with a loss and dropout against the fp64 truth with the yardstick of tests/mixed_reference.py -- every gradient within
+the trunk with a loss and dropout against the fp64 truth with the yardstick of tests/route_reference.py -- every gradient within
 2 x e_ref16, where e_ref16 is the reference's own 16-mixed error (the oracle under CPU fp16 autocast at loss scale 65536) and
 the factor 2 covers that the device and autocast are different roundings of the same size (the contract alone sits at 0.3 .. 0.9
 x e_ref16, tests/test_mixed_reference.py; a wrong tile index, a wrong transposition or a lost remainder moves a tensor by 1e-2
@@ -13,12 +13,14 @@ import numpy as np
 import pytest
 import torch
 
-import mixed_reference as R
-import trunk_grad_util as U
+import route_cases as RC
+import route_grads as RG
+import route_harness as H
 from dataset_reference import build_data_folder
 from gpu_util import POISONS, Guarded, assert_intact, dev, report
+from route_harness import randn, same_bits
 from test_gpu_backward import make_model
-from test_gpu_dropout import Unit, same_bits
+from test_gpu_dropout import Unit
 
 pytestmark = pytest.mark.gpu
 GATE = 2.0
@@ -42,17 +44,11 @@ class MixedUnit(Unit):
 
 def unscaled(res):
     """the gradients of a run whose upstream gradient carried the loss scale, divided by it in fp32"""
-    return {k: (v if k in ("y", "save_o", "save_lse") else v / R.SCALE) for k, v in res.items()}
+    return {k: (v if k in ("y", "save_o", "save_lse") else v / RG.SCALE) for k, v in res.items()}
 
 
 def gate(name, got, truth, e_ref16, keys):
-    errs = {k: U.rel(got[k], truth[k]) for k in keys}
-    k = max(errs, key=errs.get)
-    print(f"{name}: e_ref16 = {e_ref16:.3e}, worst device error = {errs[k]:.3e} ({errs[k] / e_ref16:.2f} x e_ref16, {k})")
-    for key, e in errs.items():
-        assert torch.isfinite(got[key]).all(), f"{name}: {key} is not finite"
-        assert e <= GATE * e_ref16, f"{name}: {key} is {e:.3e} from the fp64 truth, the gate is 2 x e_ref16 = {GATE * e_ref16:.3e}"
-    return errs[k] / e_ref16
+    return H.mixed_gate(name, got, truth, e_ref16, keys)
 
 
 # ---- 1. exact products -------------------------------------------------------------------------------------------------------------
@@ -94,61 +90,50 @@ def test_products_of_small_integers_are_exact(form):
 
 
 # ---- 2. units ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D", sorted(R.UNIT_DIMS))
+@pytest.mark.parametrize("D", sorted(RC.UNIT_DIMS))
 @pytest.mark.parametrize("kind", ["attn", "ff"])
 def test_units_within_twice_e_ref16(kind, D):
     worst, away = (0.0, None), 0.0
-    for i, (B, T) in enumerate(R.UNIT_SIZES):
-        sd, pfx, x, g, _, truth, _, e_ref16 = R.unit_case(kind, D, B, T)
-        got = unscaled(MixedUnit(kind, D, x, g * R.SCALE, 0, poison=POISONS[i % 2], ff_mult=R.UNIT_DIMS[D]).run(None))
-        keys = R.grad_keys(truth)
+    for i, (B, T) in enumerate(RC.UNIT_SIZES):
+        sd, pfx, x, g, _, truth, _, e_ref16 = RC.unit_case(kind, D, B, T)
+        got = unscaled(MixedUnit(kind, D, x, g * RG.SCALE, 0, poison=POISONS[i % 2], ff_mult=RC.UNIT_DIMS[D]).run(None))
+        keys = RG.grad_keys(truth)
         ratio = gate(f"mixed {kind} D={D} B={B} T={T}", got, truth, e_ref16, keys)
         worst = max(worst, (ratio, (B, T)))
         # reported, not gated: how far the device is from the fp32 restatement of its own contract
-        rest = R.unit_grads(kind, sd, pfx, x, g, torch.float32, True, R.SCALE)
-        away = max(away, max(U.rel(got[k], rest[k]) for k in keys))
-        assert U.rel(got["y"], truth["y"]) <= GATE * e_ref16
+        rest = RG.unit_grads(kind, sd, pfx, x, g, torch.float32, True, RG.SCALE)
+        away = max(away, max(RG.rel(got[k], rest[k]) for k in keys))
+        assert RG.rel(got["y"], truth["y"]) <= GATE * e_ref16
     print(f"mixed {kind} D={D}: worst {worst[0]:.2f} x e_ref16 at {worst[1]}, at most {away:.3e} from the restatement")
     report("mixed_unit", kind=kind, D=D, worst_ratio=worst[0], at=str(worst[1]), from_restatement=away)
 
 
 # ---- 3. trunk and heads with a loss -------------------------------------------------------------------------------------------------
 def trunk_device(m, h, beat, down, mask, scale):
-    from beat_this_amd.model.loss import ShiftTolerantBCELoss
-
-    m.zero_grad(set_to_none=True)
-    xd = h.to(dev()).requires_grad_(True)
-    out = m.task_heads(m.transformer_blocks(xd))
-    fn = ShiftTolerantBCELoss().to(dev())
-    loss = fn(out["beat"], beat.to(dev()), mask.to(dev()).bool()) + fn(out["downbeat"], down.to(dev()), mask.to(dev()).bool())
-    (loss * scale).backward()
-    res = {n: p.grad / scale for n, p in m.named_parameters() if p.grad is not None}
-    res.update(x=xd.grad / scale, beat=out["beat"].detach(), downbeat=out["downbeat"].detach())
-    m.zero_grad(set_to_none=True)
-    return res
+    return H.loss_backward(lambda xd: m.task_heads(m.transformer_blocks(xd)), m, h, beat, down, mask, scale)
 
 
 def test_trunk_and_heads_with_a_loss():
-    c = R.TRUNK
+    c = RC.TRUNK
     m, _ = make_model(c["D"], n_layers=c["L"])
-    sd = R.state_dict(c["D"], c["ff_mult"], c["L"])
+    sd = RC.trunk_state_dict(c["D"], c["ff_mult"], c["L"])
     for k, v in m.state_dict().items():
         assert torch.equal(v.cpu(), sd[k]), k
-    h, beat, down, mask = R.trunk_batch()
-    loss = R.trunk_loss(beat, down, mask)
-    truth = R.trunk_grads(sd, h, torch.float64, c["L"], loss, None)
-    auto = R.trunk_grads(sd, h, torch.float32, c["L"], loss, None, R.SCALE, autocast=True)
-    keys = R.grad_keys(truth)
-    e_ref16 = R.worst(auto, truth, keys)[0]
+    h, beat, down, mask = RC.trunk_batch()
+    loss = RG.trunk_loss(beat, down, mask)
+    truth = RG.trunk_grads(sd, h, torch.float64, c["L"], loss, None)
+    auto = RG.trunk_grads(sd, h, torch.float32, c["L"], loss, None, RG.SCALE, autocast=True)
+    keys = RG.grad_keys(truth)
+    e_ref16 = RG.worst(auto, truth, keys)[0]
     assert np.isfinite(e_ref16)
     try:
-        got = trunk_device(m.set_train_precision("16-mixed"), h, beat, down, mask, R.SCALE)
+        got = trunk_device(m.set_train_precision("16-mixed"), h, beat, down, mask, RG.SCALE)
     finally:
         m.set_train_precision("32-true")
     assert set(keys) <= set(got)
     ratio = gate("mixed trunk", got, truth, e_ref16, keys)
     for k in ("beat", "downbeat"):
-        e16, e = U.rel(auto[k], truth[k]), U.rel(got[k], truth[k])
+        e16, e = RG.rel(auto[k], truth[k]), RG.rel(got[k], truth[k])
         print(f"mixed trunk {k} logits: autocast {e16:.3e}, device {e:.3e}")
         assert e <= GATE * e16, (k, e, e16)
     report("mixed_trunk", e_ref16=e_ref16, worst_ratio=ratio)
@@ -157,12 +142,12 @@ def test_trunk_and_heads_with_a_loss():
 # ---- 4. dropout composes -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["attn", "ff"])
 def test_dropout_composes(kind):
-    for i, (B, T) in enumerate(R.DROP_SIZES):
+    for i, (B, T) in enumerate(RC.DROP_SIZES):
         stream = 40 + i
-        sd, pfx, x, g, masks, truth, _, e_ref16 = R.unit_case(kind, 64, B, T, stream)
-        got = unscaled(MixedUnit(kind, 64, x, g * R.SCALE, 0, poison=POISONS[i % 2]).run((R.DROP_P, R.DROP_SEED, stream)))
-        ratio = gate(f"mixed dropout {kind} T={T}", got, truth, e_ref16, R.grad_keys(truth))
-        assert U.rel(got["y"], truth["y"]) <= GATE * e_ref16
+        sd, pfx, x, g, masks, truth, _, e_ref16 = RC.unit_case(kind, 64, B, T, stream)
+        got = unscaled(MixedUnit(kind, 64, x, g * RG.SCALE, 0, poison=POISONS[i % 2]).run((RC.DROP_P, RC.DROP_SEED, stream)))
+        ratio = gate(f"mixed dropout {kind} T={T}", got, truth, e_ref16, RG.grad_keys(truth))
+        assert RG.rel(got["y"], truth["y"]) <= GATE * e_ref16
         report("mixed_dropout", kind=kind, T=T, worst_ratio=ratio)
 
 
@@ -170,9 +155,9 @@ def test_dropout_composes(kind):
 @pytest.mark.parametrize("kind", ["attn", "ff"])
 def test_runs_are_bit_identical_whatever_the_poison(kind):
     D, B, T = 64, 3, 130
-    x, g = R.randn(B, T, D, seed=51), R.randn(B, T, D, seed=52)
+    x, g = randn(B, T, D, seed=51), randn(B, T, D, seed=52)
     word = int.from_bytes(bytes([POISONS[1]] * 4), "little")
-    for drop in (None, (0.2, R.DROP_SEED, 9)):
+    for drop in (None, (0.2, RC.DROP_SEED, 9)):
         res = [MixedUnit(kind, D, x, g, 1, poison=q).run(drop) for q in POISONS]
         again = MixedUnit(kind, D, x, g, 1).run(drop)
         for k in res[0]:
@@ -189,7 +174,7 @@ def test_runs_are_bit_identical_whatever_the_poison(kind):
     assert not same_bits(plain["x"], again["x"])
     u = MixedUnit(kind, D, x, g, 1)
     for backward in (0, 1):
-        for drop in (None, (0.2, R.DROP_SEED, 9)):
+        for drop in (None, (0.2, RC.DROP_SEED, 9)):
             assert u.call(backward, drop, ws_bytes=u.ws_bytes(backward, drop) - 1) == u.L.BT_ERR_WORKSPACE
 
 
@@ -218,16 +203,8 @@ def model_grads(m, spect, beat, down, mask):
 
 def fresh_model():
     """a D = 64, 2-layer model of its own (the tests below switch its precision and step its weights)"""
-    from beat_this_amd import weights as W
-    from beat_this_amd.model import BeatThis
-
-    hp = W.resolve_hparams(dict(transformer_dim=64, ff_mult=2, n_layers=2))
-    m = BeatThis(**{k: hp[k] for k in ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim")})
-    m.load_state_dict(W.random_state_dict(hp, seed=3, style="lively"))
-    m = m.to(dev())
-    m.transformer_blocks.requires_grad_(True)
-    m.task_heads.requires_grad_(True)
-    return m
+    hp = dict(transformer_dim=64, ff_mult=2, n_layers=2)
+    return H.make_model(hp, H.state_dict(hp, 3, "lively"))
 
 
 def small_batch(seed=61):
@@ -246,7 +223,7 @@ def test_switching_back_leaves_the_fp32_route_as_it_was():
     mixed = model_grads(switched, *args)
     assert len(mixed) == len(want) > 20 and any(not same_bits(mixed[k], want[k]) for k in want)
     for k in want:   # (another rounding of the same gradients, not other gradients)
-        assert U.rel(mixed[k], want[k]) < 5e-2, k
+        assert RG.rel(mixed[k], want[k]) < 5e-2, k
     with torch.no_grad():   # inference never looks at the switch
         a, b = never(args[0]), switched(args[0])
     assert same_bits(a["beat"], b["beat"]) and same_bits(a["downbeat"], b["downbeat"])

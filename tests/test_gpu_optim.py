@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from gpu_util import POISONS, Guarded, assert_intact, dev, report
+from route_harness import make_batch
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
 
@@ -109,31 +110,11 @@ def test_device_equals_the_host_twin_bit_for_bit(regime, g_scale):
 # ---- 2. beat_this_amd.optim.AdamW on a small model ---------------------------------------------------------------------------
 def make_model(seed=3):
     """a fresh D = 64, 2-layer, ff_mult 2 model on the GPU with the trunk and the heads trainable, and its state dict (CPU)"""
-    from beat_this_amd.model import BeatThis
+    import route_harness as H
 
-    hp = W.resolve_hparams(dict(transformer_dim=64, ff_mult=2, n_layers=2))
-    sd = W.random_state_dict(hp, seed=seed, style="lively")
-    m = BeatThis(**{k: hp[k] for k in ("spect_dim", "transformer_dim", "ff_mult", "n_layers", "head_dim", "stem_dim", "sum_head",
-                                       "partial_transformers")})
-    m.load_state_dict(sd)
-    m = m.to(dev())
-    m.transformer_blocks.requires_grad_(True)
-    m.task_heads.requires_grad_(True)
-    for n, p in m.named_parameters():
-        if n.endswith("freqs"):
-            p.requires_grad_(False)
-    return m, sd
-
-
-def make_batch(B, T, seed):
-    gen = torch.Generator().manual_seed(seed)
-    spect = torch.log1p(torch.rand(B, T, 128, generator=gen) * 30)
-    beat = torch.rand(B, T, generator=gen) < 0.06
-    down = beat & (torch.rand(B, T, generator=gen) < 0.3)
-    mask = torch.ones(B, T, dtype=torch.bool)
-    mask[-1, T - 20:] = False
-    d = dev()
-    return dict(spect=spect.to(d), truth_beat=beat.to(d), truth_downbeat=down.to(d), padding_mask=mask.to(d))
+    hp = dict(transformer_dim=64, ff_mult=2, n_layers=2)
+    sd = dict(H.state_dict(hp, seed, "lively"))
+    return H.make_model(hp, sd, freeze_freqs=True), sd
 
 
 def model_loss(m, batch, rows=slice(None)):

@@ -4,7 +4,7 @@ roformer.py:138-181) against the oracle's functions of the same names, in the re
 import pytest
 import torch
 
-from gpu_util import dev, report
+from gpu_util import _rel, dev, report
 
 pytestmark = pytest.mark.gpu
 HP = dict(transformer_dim=256, n_layers=2)   # (small model: the sub-module entry runs the generic kernels)
@@ -22,10 +22,6 @@ def _model(style="lively", **hp):
     # since round 5 -- these tests compare like with like, the last one also checks the default against the hooked chain)
     m.fp32_split_gemms = False
     return m.to(dev()).eval(), {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}, h
-
-
-def _rel(a, ref):
-    return float((a.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
 
 
 def test_frontend_submodules_match_the_oracle():

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from gpu_util import dev
+from route_harness import same_bits
 from beat_this_amd import weights as W
 
 pytestmark = pytest.mark.gpu
@@ -25,10 +26,6 @@ B, T = 2, 48
 SEED = 0x5EED_0000_0000_0022
 P_FRONT, P_TRUNK = 0.1, 0.2
 _BASE = {}
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.reshape(-1).view(torch.uint8), b.reshape(-1).view(torch.uint8))
 
 
 def base():

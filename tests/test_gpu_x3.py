@@ -9,18 +9,9 @@ import math
 import pytest
 import torch
 
-from gpu_util import HL8_ACT_SHIFT, dev, frag_x3, from_hl32, hl8_matmul, hl8_parts, pad_rows, report, to_hl8, to_hl8a, to_hl32, unfrag_x3
+from gpu_util import HL8_ACT_SHIFT, _attn_ref, _mk, _rel, dev, frag_x3, from_hl32, hl8_matmul, hl8_parts, pad_rows, report, to_hl8, to_hl8a, to_hl32, unfrag_x3
 
 pytestmark = pytest.mark.gpu
-
-
-def _mk(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g, dtype=torch.float64) * scale
-
-
-def _rel(a, ref):
-    return float((a.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
 
 
 def _ssq_parts(x32):
@@ -338,11 +329,6 @@ def test_gemm3_x3_range_flag():
 
 
 # ---- attention ----------------------------------------------------------------------------------------------------------
-def _attn_ref(q, k, v, gates):
-    s = q @ k.transpose(-1, -2) * math.log(2.0)  # q carries log2(e)/sqrt(d): softmax in base 2
-    return torch.softmax(s, -1) @ v * gates[..., None]
-
-
 def _run_attn(q, k, v, gates, n_seq, L, heads, out_f32, variant=1, raw=False, status_out=None, **omap):
     from beat_this_amd import _lib as Lb
 

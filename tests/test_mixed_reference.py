@@ -1,4 +1,4 @@
-"""The yardstick of the 16-mixed route without a GPU (tests/mixed_reference.py).
+"""The yardstick of the 16-mixed route without a GPU (tests/route_reference.py).
 
 1. The hand-written backward formulas of the restatement: with the rounding switched off, its fp64 gradients are the oracle's
    autograd to 1e-12 relative.
@@ -13,89 +13,90 @@ import math
 import pytest
 import torch
 
-import mixed_reference as R
-import trunk_grad_util as U
+import route_cases as RC
+import route_grads as RG
+import route_reference as REF
 
 _TRUNK = {}
 
 
 def trunk_truth():
     if not _TRUNK:
-        c = R.TRUNK
-        sd = R.state_dict(c["D"], c["ff_mult"], c["L"])
-        h, beat, down, mask = R.trunk_batch()
-        loss = R.trunk_loss(beat, down, mask)
-        _TRUNK.update(sd=sd, h=h, loss=loss, truth=R.trunk_grads(sd, h, torch.float64, c["L"], loss, None))
+        c = RC.TRUNK
+        sd = RC.trunk_state_dict(c["D"], c["ff_mult"], c["L"])
+        h, beat, down, mask = RC.trunk_batch()
+        loss = RG.trunk_loss(beat, down, mask)
+        _TRUNK.update(sd=sd, h=h, loss=loss, truth=RG.trunk_grads(sd, h, torch.float64, c["L"], loss, None))
     return _TRUNK
 
 
 # ---- 1. the backward formulas --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["attn", "ff"])
-@pytest.mark.parametrize("D", sorted(R.UNIT_DIMS))
+@pytest.mark.parametrize("D", sorted(RC.UNIT_DIMS))
 def test_unrounded_restatement_is_the_oracle(kind, D):
-    sd, pfx = R.state_dict(D, R.UNIT_DIMS[D]), R.PFX[kind]
+    sd, pfx = RC.trunk_state_dict(D, RC.UNIT_DIMS[D]), RC.PFX[kind]
     for B, T in ((3, 33), (1, 65)):
-        x, g = R.unit_inputs(kind, D, B, T)
-        want = U.oracle_unit_grads(kind, sd, pfx, x, g, torch.float64, heads=D // 32)
-        got = R.unit_grads(kind, sd, pfx, x, g, torch.float64, False)
+        x, g = RC.unit_inputs(kind, D, B, T)
+        want = RG.oracle_unit_grads(kind, sd, pfx, x, g, torch.float64, heads=D // 32)
+        got = RG.unit_grads(kind, sd, pfx, x, g, torch.float64, False)
         assert set(want) <= set(got)
         for k in want:
-            assert U.rel(got[k], want[k]) <= 1e-12, (kind, D, B, T, k, U.rel(got[k], want[k]))
-    # with masks: finetune_reference's masked units
-    B, T = R.DROP_SIZES[0]
-    masks = R.unit_masks(kind, R.DROP_P, R.DROP_SEED, 3, B, T, D, R.UNIT_DIMS[D] * D)
-    x, g = R.unit_inputs(kind, D, B, T)
-    want = R.unit_grads(kind, sd, pfx, x, g, torch.float64, None, masks=masks, p=R.DROP_P)
-    got = R.unit_grads(kind, sd, pfx, x, g, torch.float64, False, masks=masks, p=R.DROP_P)
+            assert RG.rel(got[k], want[k]) <= 1e-12, (kind, D, B, T, k, RG.rel(got[k], want[k]))
+    # with masks: route_reference's masked units
+    B, T = RC.DROP_SIZES[0]
+    masks = REF.unit_masks(kind, RC.DROP_P, RC.DROP_SEED, 3, B, T, D, RC.UNIT_DIMS[D] * D)
+    x, g = RC.unit_inputs(kind, D, B, T)
+    want = RG.unit_grads(kind, sd, pfx, x, g, torch.float64, None, masks=masks, p=RC.DROP_P)
+    got = RG.unit_grads(kind, sd, pfx, x, g, torch.float64, False, masks=masks, p=RC.DROP_P)
     for k in want:
-        assert U.rel(got[k], want[k]) <= 1e-12, (kind, D, "dropout", k, U.rel(got[k], want[k]))
+        assert RG.rel(got[k], want[k]) <= 1e-12, (kind, D, "dropout", k, RG.rel(got[k], want[k]))
 
 
 def test_unrounded_trunk_is_the_oracle():
-    t, c = trunk_truth(), R.TRUNK
-    want = U.oracle_trunk_grads(t["sd"], t["h"], None, None, torch.float64, c["L"], loss_fn=t["loss"])
-    got = R.trunk_grads(t["sd"], t["h"], torch.float64, c["L"], t["loss"], False)
+    t, c = trunk_truth(), RC.TRUNK
+    want = RG.oracle_trunk_grads(t["sd"], t["h"], None, None, torch.float64, c["L"], loss_fn=t["loss"])
+    got = RG.trunk_grads(t["sd"], t["h"], torch.float64, c["L"], t["loss"], False)
     for k in want:
-        assert U.rel(got[k], want[k]) <= 1e-12, (k, U.rel(got[k], want[k]))
-        assert U.rel(t["truth"][k], want[k]) <= 1e-12, k
+        assert RG.rel(got[k], want[k]) <= 1e-12, (k, RG.rel(got[k], want[k]))
+        assert RG.rel(t["truth"][k], want[k]) <= 1e-12, k
 
 
 # ---- 2. the contract alone stays within e_ref16 ----------------------------------------------------------------------------------
 def contract_ratio(name, kind, D, B, T, stream=None):
-    sd, pfx, x, g, masks, truth, auto, e_ref16 = R.unit_case(kind, D, B, T, stream)
-    got = R.unit_grads(kind, sd, pfx, x, g, torch.float32, True, R.SCALE, masks, R.DROP_P)
-    err, key = R.worst(got, truth, R.grad_keys(truth))
+    sd, pfx, x, g, masks, truth, auto, e_ref16 = RC.unit_case(kind, D, B, T, stream)
+    got = RG.unit_grads(kind, sd, pfx, x, g, torch.float32, True, RG.SCALE, masks, RC.DROP_P)
+    err, key = RG.worst(got, truth, RG.grad_keys(truth))
     print(f"{name}: e_ref16 = {e_ref16:.3e}, contract = {err:.3e} ({err / e_ref16:.2f} x e_ref16, {key})")
     return err, e_ref16
 
 
 @pytest.mark.parametrize("kind", ["attn", "ff"])
-@pytest.mark.parametrize("D", sorted(R.UNIT_DIMS))
+@pytest.mark.parametrize("D", sorted(RC.UNIT_DIMS))
 def test_contract_within_e_ref16_units(kind, D):
-    for B, T in R.UNIT_SIZES:
+    for B, T in RC.UNIT_SIZES:
         err, e_ref16 = contract_ratio(f"{kind} D={D} B={B} T={T}", kind, D, B, T)
         assert err <= 1.0 * e_ref16, (kind, D, B, T, err, e_ref16)
 
 
 @pytest.mark.parametrize("kind", ["attn", "ff"])
 def test_contract_within_e_ref16_dropout(kind):
-    for i, (B, T) in enumerate(R.DROP_SIZES):
+    for i, (B, T) in enumerate(RC.DROP_SIZES):
         err, e_ref16 = contract_ratio(f"dropout {kind} T={T}", kind, 64, B, T, stream=40 + i)
         assert err <= 1.0 * e_ref16, (kind, B, T, err, e_ref16)
 
 
 def test_contract_within_e_ref16_trunk():
-    t, c = trunk_truth(), R.TRUNK
-    auto = R.trunk_grads(t["sd"], t["h"], torch.float32, c["L"], t["loss"], None, R.SCALE, autocast=True)
-    got = R.trunk_grads(t["sd"], t["h"], torch.float32, c["L"], t["loss"], True, R.SCALE)
-    keys = R.grad_keys(t["truth"])
-    e_ref16, err = R.worst(auto, t["truth"], keys)[0], R.worst(got, t["truth"], keys)
+    t, c = trunk_truth(), RC.TRUNK
+    auto = RG.trunk_grads(t["sd"], t["h"], torch.float32, c["L"], t["loss"], None, RG.SCALE, autocast=True)
+    got = RG.trunk_grads(t["sd"], t["h"], torch.float32, c["L"], t["loss"], True, RG.SCALE)
+    keys = RG.grad_keys(t["truth"])
+    e_ref16, err = RG.worst(auto, t["truth"], keys)[0], RG.worst(got, t["truth"], keys)
     print(f"trunk: e_ref16 = {e_ref16:.3e}, contract = {err[0]:.3e} ({err[0] / e_ref16:.2f} x e_ref16, {err[1]})")
     assert err[0] <= 1.0 * e_ref16
     # (reported only: the same arithmetic without the loss scale; on this batch the gradients are large enough not to lose
     # more to fp16's subnormals than to its rounding)
-    bare = R.trunk_grads(t["sd"], t["h"], torch.float32, c["L"], t["loss"], True, 1.0)
-    print(f"trunk without a loss scale: {R.worst(bare, t['truth'], keys)[0]:.3e}")
+    bare = RG.trunk_grads(t["sd"], t["h"], torch.float32, c["L"], t["loss"], True, 1.0)
+    print(f"trunk without a loss scale: {RG.worst(bare, t['truth'], keys)[0]:.3e}")
 
 
 # ---- 3. the loss scaler ------------------------------------------------------------------------------------------------------------

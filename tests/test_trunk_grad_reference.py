@@ -1,4 +1,4 @@
-"""CPU side of the trunk's backward pass: the yardstick (trunk_grad_util.py) pinned to the reference's own gradients
+"""CPU side of the trunk's backward pass: the yardstick (route_grads.py) pinned to the reference's own gradients
 (tests/golden/trunk_grads.npz, recorded by tools/make_trunk_grad_golden.py), shown to discriminate, and the binding of the
 training entry points (bt_train_*), none of which needs a GPU for its argument checks."""
 import ctypes as C
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-import trunk_grad_util as U
+import route_grads as RG
 from conftest import GOLDEN, ROOT
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
@@ -24,8 +24,8 @@ def golden_case():
     sd = W.random_state_dict(W.resolve_hparams(HP), seed=3, style="lively")
     x, g_b, g_d = (torch.from_numpy(z[k]) for k in ("x", "g_b", "g_d"))
     gold = {k[5:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("grad.")}
-    g32 = U.oracle_trunk_grads(sd, x, g_b, g_d, torch.float32, 1)
-    g64 = U.oracle_trunk_grads(sd, x, g_b, g_d, torch.float64, 1)
+    g32 = RG.oracle_trunk_grads(sd, x, g_b, g_d, torch.float32, 1)
+    g64 = RG.oracle_trunk_grads(sd, x, g_b, g_d, torch.float64, 1)
     return sd, x, g_b, g_d, gold, g32, g64
 
 
@@ -33,9 +33,9 @@ def test_golden_against_the_oracle(golden_case):
     """The fp32 oracle is no further from the reference's recorded gradients than those are from the fp64 oracle, per tensor in
     relative L2: the yardstick's fp32 leg stands for what the reference's training computes."""
     sd, x, g_b, g_d, gold, g32, g64 = golden_case
-    assert set(gold) == set(g64) == set(["x"] + U.trainable_keys(sd))
+    assert set(gold) == set(g64) == set(["x"] + RG.trainable_keys(sd))
     for k in gold:
-        to_oracle, to_truth = U.rel(g32[k], gold[k]), U.rel(gold[k], g64[k])
+        to_oracle, to_truth = RG.rel(g32[k], gold[k]), RG.rel(gold[k], g64[k])
         print(f"{k}: |oracle32 - golden| = {to_oracle:.3e}, |golden - oracle64| = {to_truth:.3e}")
         assert to_truth < 1e-5, (k, to_truth)
         assert to_oracle <= to_truth, (k, to_oracle, to_truth)
@@ -45,18 +45,18 @@ def test_the_yardstick_discriminates(golden_case, monkeypatch):
     """An RMSNorm whose norm is detached (its backward loses the norm's own term): every gradient tensor that changes misses the
     10 e_ref gate by at least a factor of 100."""
     sd, x, g_b, g_d, gold, g32, g64 = golden_case
-    e_ref = U.yardstick(g32, g64)
+    e_ref = RG.yardstick(g32, g64)
 
     def rmsnorm_detached(x, gamma):
         nrm = x.norm(dim=-1, keepdim=True).clamp_min(1e-12).detach()
         return x / nrm * math.sqrt(x.shape[-1]) * gamma
 
     monkeypatch.setattr(O, "rmsnorm", rmsnorm_detached)
-    bad = U.oracle_trunk_grads(sd, x, g_b, g_d, torch.float32, 1)
+    bad = RG.oracle_trunk_grads(sd, x, g_b, g_d, torch.float32, 1)
     changed = [k for k in g64 if not torch.equal(bad[k], g32[k])]
     assert "x" in changed and len(changed) >= 10, changed
     for k in changed:
-        assert U.rel(bad[k], g64[k]) >= 100 * U.GATE * e_ref, (k, U.rel(bad[k], g64[k]), e_ref)
+        assert RG.rel(bad[k], g64[k]) >= 100 * RG.GATE * e_ref, (k, RG.rel(bad[k], g64[k]), e_ref)
     monkeypatch.undo()
     assert 2e-7 < e_ref < 1e-5, e_ref   # (the golden's case: 1.15e-6 when the issue was written)
 
