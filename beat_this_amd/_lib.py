@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "stretch.hip", "engine.hip"]
+           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "stretch.hip", "pcm.hip", "engine.hip"]
 HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "train_front_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
@@ -156,6 +156,10 @@ class FrontBnArgs(C.Structure):   # bt_front_bn_args
                 ("ws_bytes", C.c_size_t)]
 
 
+class PcmSpan(C.Structure):   # bt_pcm_span
+    _fields_ = [("d_src", C.c_void_p), ("n_frames", C.c_int64), ("d_out", C.c_void_p), ("format", C.c_int32), ("channels", C.c_int32)]
+
+
 class OptimTensor(C.Structure):   # bt_optim_tensor
     _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int64), ("group", C.c_int32), ("reserved", C.c_int32)]
 
@@ -187,6 +191,10 @@ DROP_ATTN_P, DROP_ATTN_OUT, DROP_FF_HIDDEN, DROP_FF_OUT = range(4)   # BT_DROP_*
 OPTIM_CHUNK, OPTIM_NORM_SLICE = 4096, 4096                 # BT_OPTIM_CHUNK / _NORM_SLICE: elements per workgroup (likewise)
 STRETCH_MAX_SAMPLES, STRETCH_SCAN_BLOCK, STRETCH_TABLE_DOUBLES = 1 << 26, 64, 6146   # BT_STRETCH_* (csrc/stretch.hip)
 RESAMPLE_RATIO_TAPS, RESAMPLE_RATIO_CROSSINGS = 4096, 116   # BT_RESAMPLE_RATIO_*: the layout of tables.resample_ratio_table
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # BT_PCM_*: sample formats of csrc/pcm.hip
+PCM_SAMPLE_BYTES = (1, 2, 3, 4, 4, 8)
+PCM_MAX_CHANNELS_INT, PCM_MAX_CHANNELS_FLOAT, PCM_MAX_TRACKS = 8, 7, 65535
+PCM_THREAD_FRAMES, PCM_BLOCK_FRAMES = 4, 1024               # frames per thread / per workgroup (tests sit on both sides of them)
 
 EXPORTS = {
     "bt_last_error": (C.c_char_p, []),
@@ -320,6 +328,9 @@ EXPORTS = {
     "bt_stretch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p,
                              C.c_size_t]),
     "bt_resample_ratio": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_int64]),
+    "bt_pcm_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64]),
+    "bt_pcm_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "bt_pcm_decode_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
 }
 
 
@@ -341,7 +352,9 @@ FLAGS_BY_SOURCE = {"tail.hip": ["-Xclang", "-target-feature", "-Xclang", "-packe
                    # the AdamW step and the gradient norm must have the same bits on the host and the device (the host twins)
                    "optim.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # frame positions, output lengths and filter arguments are fp64 expressions that numpy evaluates too
-                   "stretch.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
+                   "stretch.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
+                   # the channel mean is numpy's fp64 sum and division, operation by operation, on the host and the device
+                   "pcm.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
 # compile-time switches: BT_DEFINES in the environment of build() (e.g. "-DBT_HALF_BF16"); every one of them builds a correct library
 EXTRA_DEFINES = os.environ.get("BT_DEFINES", "").split()
 

@@ -9,6 +9,10 @@ Differences that matter for speed, not for results:
   * ``Audio2Beats.many`` / ``Audio2Frames.signal2spect_many`` / ``Spect2Frames.spect2frames_batch`` (extensions):
     a whole list of tracks per call -- ONE launch per stage (resample, log-mel, chunk gather, forward slices,
     aggregation, peak picking) and ONE device-to-host copy for all tracks.
+  * ``File2Beats.many`` / ``many_async`` / ``Audio2Frames.files2waves`` (extensions) and ``device_decode=True`` (opt-in): PCM
+    WAV files go to the GPU as the bytes they are and are decoded there (csrc/pcm.hip: the channel mean in fp64 exactly as
+    numpy computes it, so the waveform has the bits of ``load_audio`` + ``mean(1)``); a file ``wav.probe`` does not fully
+    recognise takes ``load_audio`` as before.
 
 Precision (the ``float16`` argument of the inference classes):
   * ``False`` (the reference's default): fp32 activations and fp32-class results -- framewise logits within 1e-3 of the
@@ -25,6 +29,7 @@ Limits of the drop-in (there is no CPU implementation in this package):
 from __future__ import annotations
 
 import inspect
+import threading
 
 import numpy as np
 import torch
@@ -57,6 +62,53 @@ def _copy_stream(dev):
     if key not in _SIDE_STREAMS:
         _SIDE_STREAMS[key] = torch.cuda.Stream(dev)
     return _SIDE_STREAMS[key]
+
+
+READ_THREADS = 4   # host threads that read files into pinned buffers (files2waves); never sized from the machine's CPU count
+_READ_POOL = None
+_RAW_POOL: list = []        # [(pinned uint8 tensor, event of the upload that last read it)]
+_RAW_POOL_MAX = 16
+_RAW_LOCK = threading.Lock()
+
+
+def _read_pool():
+    global _READ_POOL
+    if _READ_POOL is None:
+        from concurrent.futures import ThreadPoolExecutor
+
+        _READ_POOL = ThreadPoolExecutor(max_workers=READ_THREADS, thread_name_prefix="bt-read")
+    return _READ_POOL
+
+
+def _raw_pinned(nbytes: int) -> torch.Tensor:
+    """A pinned uint8 host buffer of at least ``nbytes`` for a file's raw bytes (page-locking 50 MB costs milliseconds: buffers
+    are pooled).  A buffer of the pool is handed out once the upload that last read it has run."""
+    with _RAW_LOCK:
+        fits = [i for i, (t, _) in enumerate(_RAW_POOL) if t.numel() >= nbytes]
+        entry = _RAW_POOL.pop(min(fits, key=lambda i: _RAW_POOL[i][0].numel())) if fits else None
+    if entry is None:
+        return torch.empty((max(nbytes, 1 << 16),), dtype=torch.uint8, pin_memory=True)
+    if entry[1] is not None:
+        entry[1].synchronize()
+    return entry[0]
+
+
+def _return_raw(bufs, event) -> None:
+    with _RAW_LOCK:
+        for t in bufs:
+            if len(_RAW_POOL) >= _RAW_POOL_MAX:   # (drop the smallest: the pool keeps what the longest files need)
+                _RAW_POOL.sort(key=lambda e: e[0].numel())
+                _RAW_POOL.pop(0)
+            _RAW_POOL.append((t, event))
+
+
+def _host_mono(signal) -> np.ndarray:
+    """``load_audio``'s signal -> the mono fp32 waveform of ``signal2spect`` (inference.py:269-277): numpy's channel mean"""
+    if signal.ndim == 2:
+        signal = signal.mean(1)
+    elif signal.ndim != 1:
+        raise ValueError(f"Expected 1D or 2D signal, got shape {signal.shape}")
+    return np.ascontiguousarray(signal, dtype=np.float32)
 
 
 def load_checkpoint(checkpoint_path, device="cpu") -> dict:
@@ -339,7 +391,10 @@ class Audio2Frames(Spect2Frames):
             signal = signal.mean(1)
         elif signal.ndim != 1:
             raise ValueError(f"Expected 1D or 2D signal, got shape {signal.shape}")
-        signal = torch.tensor(signal, dtype=torch.float32, device=self.device)
+        if isinstance(signal, torch.Tensor):   # (a waveform decoded on the device: File2Beats(device_decode=True))
+            signal = signal.to(device=self.device, dtype=torch.float32)
+        else:
+            signal = torch.tensor(signal, dtype=torch.float32, device=self.device)
         if sr != 22050:
             signal = resample_gpu(signal, sr, 22050)
         return self.spect(signal)
@@ -414,6 +469,93 @@ class Audio2Frames(Spect2Frames):
             _lib.check(lib.bt_logmel_batch(st, C.byref(self.spect._get_tables()), d_table[1].data_ptr(), n, int(n_fr.max()),
                                            spect.data_ptr()))
         return spect, frame_off
+
+    def files2waves(self, paths):
+        """Extension: audio files -> [(mono fp32 waveform on the device, sample rate)] in the order of ``paths``.  PCM WAV
+        files (``wav.probe``) are read as they are into pooled pinned buffers -- by up to READ_THREADS host threads that do
+        nothing else; only the calling thread touches the GPU --, uploaded on the copy stream and decoded by ONE
+        bt_pcm_decode_batch launch: bit for bit the waveform ``load_audio`` + ``mean(1)`` + the fp32 conversion give on the
+        host.  Any other file takes exactly that host route (and raises what ``load_audio`` raises)."""
+        from . import wav
+
+        dev = self.device
+        paths = list(paths)
+        out = [None] * len(paths)
+        infos = [wav.probe(p) for p in paths]
+        idx = [k for k, i in enumerate(infos) if i is not None]
+        bufs = [_raw_pinned(infos[k].raw_span[1]) for k in idx]        # (allocated here, by the caller; the threads only fill them)
+        if len(idx) > 1:
+            jobs = [_read_pool().submit(wav.read_raw, infos[k], paths[k], b) for k, b in zip(idx, bufs)]
+        else:
+            jobs = [_Done(wav.read_raw, infos[k], paths[k], b) for k, b in zip(idx, bufs)]
+        ok, pay = [], {}
+        for k, b, job in zip(idx, bufs, jobs):
+            try:
+                pay[k] = job.result()
+                ok.append((k, b))
+            except OSError:      # (the file changed under us: let load_audio say what it says today)
+                infos[k] = None
+        if ok:
+            cur = torch.cuda.current_stream(dev)
+            copy = _copy_stream(dev)
+            with torch.cuda.device(dev):
+                raws = []
+                with torch.cuda.stream(copy):
+                    for k, b in ok:
+                        d = b[: infos[k].raw_span[1]].to(dev, non_blocking=True)
+                        d.record_stream(cur)
+                        raws.append(d)
+                ev = torch.cuda.Event()
+                ev.record(copy)
+                cur.wait_event(ev)
+                n_fr = np.array([infos[k].n_frames for k, _ in ok], dtype=np.int64)
+                off = np.concatenate([[0], np.cumsum((n_fr + 3) // 4 * 4)])       # every track 16-byte aligned
+                big = torch.empty(int(off[-1]), dtype=torch.float32, device=dev)
+                table = np.zeros((len(ok), 4), dtype=np.int64)                    # bt_pcm_span
+                table[:, 0] = [d.data_ptr() + pay[k] for d, (k, _) in zip(raws, ok)]
+                table[:, 1] = n_fr
+                table[:, 2] = big.data_ptr() + 4 * off[:-1]
+                table[:, 3] = [infos[k].format | (infos[k].channels << 32) for k, _ in ok]
+                d_table = _lib.upload(table, dev)
+                _lib.check(_lib.lib().bt_pcm_decode_batch(_lib.stream_ptr(dev), d_table.data_ptr(), len(ok), int(n_fr.max())))
+            _return_raw(bufs, ev)
+            for j, (k, _) in enumerate(ok):
+                out[k] = (big[int(off[j]): int(off[j]) + int(n_fr[j])], infos[k].sample_rate)
+        else:
+            _return_raw(bufs, None)
+        for k, p in enumerate(paths):
+            if out[k] is None:
+                signal, sr = load_audio(p)
+                out[k] = (torch.from_numpy(_host_mono(signal)).to(dev), sr)
+        return out
+
+    def file2wave(self, path):
+        """One PCM WAV file -> (mono fp32 waveform on the device, sample rate) by bt_pcm_decode, or None where ``wav.probe``
+        declines the file (the caller then decodes it on the host, as before).  No device table, no second stream: this is
+        the latency path of ``File2Beats(device_decode=True)``."""
+        from . import wav
+
+        info = wav.probe(path)
+        if info is None:
+            return None
+        dev = self.device
+        buf = _raw_pinned(info.raw_span[1])
+        ev = None
+        try:
+            try:
+                pay = wav.read_raw(info, path, buf)
+            except OSError:
+                return None
+            with torch.cuda.device(dev):
+                raw = buf[: info.raw_span[1]].to(dev, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(dev))
+                wave = torch.empty(info.n_frames, dtype=torch.float32, device=dev)
+                _lib.check(_lib.lib().bt_pcm_decode(_lib.stream_ptr(dev), raw.data_ptr() + pay, info.format, info.channels,
+                                                    info.n_frames, wave.data_ptr()))
+        finally:
+            _return_raw([buf], ev)
+        return wave, info.sample_rate
 
     def many(self, signals, sr):
         """Extension: [(beat_logits, downbeat_logits)] for a list of waveforms, batched per stage."""
@@ -558,10 +700,81 @@ class _GuardedPending:
         return out
 
 
+class _Done:
+    """a call made right away, with the ``result()`` of a future (one file needs no thread)"""
+
+    def __init__(self, fn, *args):
+        try:
+            self._out, self._exc = fn(*args), None
+        except Exception as e:
+            self._out, self._exc = None, e
+
+    def result(self):
+        if self._exc is not None:
+            raise self._exc
+        return self._out
+
+
+class PendingFiles:
+    """Handle of ``File2Beats.many_async``: ``result()`` -> [(beats, downbeats)] in the order of the paths; ``logits``: the
+    batch's framewise logits (beat, downbeat, frame_off), concatenated in that order."""
+
+    def __init__(self, n, groups):
+        self._n, self._groups = n, groups      # groups: [(indices into the paths, pending result of that sample rate)]
+
+    def result(self):
+        out = [None] * self._n
+        for idx, pending in self._groups:
+            for k, r in zip(idx, pending.result()):
+                out[k] = r
+        return out
+
+    @property
+    def logits(self):
+        if len(self._groups) == 1:             # (one sample rate: the tracks lie in the order of the paths already)
+            return self._groups[0][1].logits
+        parts = [None] * self._n
+        for idx, pending in self._groups:
+            beat, down, off = pending.logits
+            for j, k in enumerate(idx):
+                parts[k] = (beat[off[j]: off[j + 1]], down[off[j]: off[j + 1]])
+        frame_off = np.concatenate([[0], np.cumsum([len(p[0]) for p in parts])]).astype(np.int64)
+        if not parts:                          # (no paths)
+            return torch.empty(0), torch.empty(0), frame_off
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), frame_off
+
+
 class File2Beats(Audio2Beats):
+    def __init__(self, checkpoint_path="final0", device="cuda", float16=False, dbn=False, device_decode=False):
+        super().__init__(checkpoint_path, device, float16, dbn)
+        # opt-in: ``__call__`` decodes PCM WAV files on the GPU (``file2wave``).  Off, ``__call__`` is the reference's body.
+        # (Where load_audio goes through torchaudio, s32 and f64 samples are rounded to fp32 BEFORE the mono mix there, and
+        # the device route may differ from it in the last bit of the waveform: INTEGRATION.md.)
+        self.device_decode = bool(device_decode)
+
     def __call__(self, audio_path):
+        if self.device_decode:
+            wave = self.file2wave(audio_path)
+            if wave is not None:
+                return super().__call__(*wave)
         signal, sr = load_audio(audio_path)
         return super().__call__(signal, sr)
+
+    def many(self, paths):
+        """Extension: [(beats, downbeats)] for a list of audio files, in the order of ``paths``: ``files2waves`` (PCM WAV
+        files decoded on the GPU by one launch), then ``Audio2Beats.many``'s stages once per distinct sample rate."""
+        return self.many_async(paths).result()
+
+    def many_async(self, paths):
+        """``many`` without the final wait (see ``Audio2Beats.many_async``): the files are read, uploaded and decoded, all
+        GPU work is enqueued; ``.result()`` of the returned handle waits and runs the host step, ``.logits`` are the batch's
+        framewise logits.  Submitting batch i + 1 before collecting batch i overlaps its file reads with batch i's GPU work."""
+        waves = self.files2waves(paths)
+        by_rate: dict = {}
+        for k, (_, sr) in enumerate(waves):
+            by_rate.setdefault(int(sr), []).append(k)
+        groups = [(idx, Audio2Beats.many_async(self, [waves[k][0] for k in idx], sr)) for sr, idx in by_rate.items()]
+        return PendingFiles(len(waves), groups)
 
 
 class File2File(File2Beats):

@@ -1005,6 +1005,48 @@ int bt_stretch(void* stream, const double* d_tables, const float* d_in, int64_t 
 int bt_resample_ratio(void* stream, const float* d_in, int64_t n_in, double step, const float* d_table, float* d_out,
                       int64_t n_out);
 
+/* ---- PCM decode (csrc/pcm.hip): the `data` chunk of a little-endian RIFF/WAVE file -> the mono fp32 waveform, on the device.
+ * Input: interleaved frames of C channels in one of six sample formats; every sample has an exact real value s:
+ *   BT_PCM_U8   s = (v - 128) / 128          BT_PCM_S32  s = v / 2^31
+ *   BT_PCM_S16  s = v / 2^15                 BT_PCM_F32  s = the sample
+ *   BT_PCM_S24  s = v / 2^23 (3 bytes)       BT_PCM_F64  s = the sample
+ * all exact in fp64.
+ *   C = 1: out = fp32(s), round to nearest even (an f32 sample is copied as it is; -0 stays -0).
+ *   C > 1: acc = (+0.0) + s[0]; acc = acc + s[c] for c = 1 .. C-1 in that order; acc = acc / C (IEEE division); out =
+ *          fp32(acc); all in fp64.  This is numpy's `signal.mean(1)` of the float64 (frames, C) array followed by the fp32
+ *          conversion (preprocessing.load_audio through scipy or soundfile, Audio2Frames.signal2spect): numpy (2.2) starts the
+ *          row sum at +0.0 and adds the contiguous channel axis left to right up to 7 channels, in an unrolled order from 8 on.
+ *          The leading +0.0 only matters for the sign of zero: a frame of -0.0 in every channel gives +0.0 where C > 1.
+ * Channels: 1 .. BT_PCM_MAX_CHANNELS_INT for the integer formats (their sums are exact in any order), 1 ..
+ * BT_PCM_MAX_CHANNELS_FLOAT for f32 / f64.  No multiply-add contraction changes a result (the source is built with
+ * -ffp-contract=off), results that are fp32 subnormals keep gradual underflow, NaN stays NaN (its payload and sign are not
+ * part of the contract).
+ * Pointers: d_src may have ANY byte alignment (the data chunk of a real file starts 44, 46, 58, 68 ... bytes into the upload).
+ * The kernel reads only inside the aligned 16-byte windows that enclose [d_src, d_src + n_frames C bytes_per_sample); the caller
+ * guarantees that those windows lie inside its allocation; no result depends on a byte outside the payload.  d_out is 16-byte
+ * aligned; exactly n_frames floats are written.  A track of 0 frames is legal and writes nothing.  No atomics, no workspace:
+ * runs are bit-identical.  BT_ERR_ARG, before any launch: a null pointer, an unknown format, a channel count outside the
+ * contract, a negative count, more than BT_PCM_MAX_TRACKS tracks. */
+#define BT_PCM_U8 0
+#define BT_PCM_S16 1
+#define BT_PCM_S24 2
+#define BT_PCM_S32 3
+#define BT_PCM_F32 4
+#define BT_PCM_F64 5
+#define BT_PCM_MAX_CHANNELS_INT 8
+#define BT_PCM_MAX_CHANNELS_FLOAT 7
+#define BT_PCM_MAX_TRACKS 65535
+#define BT_PCM_THREAD_FRAMES 4      /* frames per thread: one 16-byte store */
+#define BT_PCM_BLOCK_FRAMES 1024    /* frames per workgroup */
+typedef struct { const uint8_t* d_src; int64_t n_frames; float* d_out; int32_t format; int32_t channels; } bt_pcm_span;
+/* one launch for a ragged list of tracks (a DEVICE table; formats may differ between tracks); max_frames = the largest n_frames.
+ * The table's entries are checked by the caller: the launch trusts them (the host cannot read a device table without a copy). */
+int bt_pcm_decode_batch(void* stream, const bt_pcm_span* d_tracks, int n_tracks, int64_t max_frames);
+/* one track without a device table (the single-file latency path) */
+int bt_pcm_decode(void* stream, const uint8_t* d_src, int format, int channels, int64_t n_frames, float* d_out);
+/* the host twin: plain sequential C++ over the same inline helpers; src and out in HOST memory, any alignment of src */
+int bt_pcm_decode_host(const uint8_t* src, int format, int channels, int64_t n_frames, float* out);
+
 #ifdef __cplusplus
 }
 #endif
