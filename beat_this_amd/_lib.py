@@ -22,6 +22,8 @@ SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "at
 HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "train_front_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
+OPERAND_F16, OPERAND_BF16 = 0, 1   # BT_OPERAND_*: the operand format of a 16-mixed call (``operand`` of the three training structs)
+OPERANDS = {"fp16": OPERAND_F16, "bf16": OPERAND_BF16}
 ABI_VERSION = 600   # BT_ABI_VERSION of include/beat_this_amd.h this binding was written against
 PREC_F32, PREC_HALF, PREC_F32X3 = 0, 1, 3   # (2 was the withdrawn e4m3 experiment)
 OPT_X3_ATTN_P16, OPT_X3_GEMM_FP8, OPT_WS_GUARD = 1, 2, 3   # BT_OPT_* (bt_engine_set_option)
@@ -122,7 +124,7 @@ class TrainPart(C.Structure):   # bt_train_part
 
 class TrainArgs(C.Structure):   # bt_train_args
     _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("dim", C.c_int32), ("hidden", C.c_int32), ("rope_len", C.c_int32),
-                ("residual", C.c_int32), ("sum_head", C.c_int32), ("reserved", C.c_int32), ("rope", C.c_void_p),
+                ("residual", C.c_int32), ("sum_head", C.c_int32), ("operand", C.c_int32), ("rope", C.c_void_p),
                 ("gamma", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
                 ("w3", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p), ("save_o", C.c_void_p),
                 ("save_lse", C.c_void_p), ("gy", C.c_void_p), ("gy2", C.c_void_p), ("gx", C.c_void_p), ("g_gamma", C.c_void_p),
@@ -136,7 +138,7 @@ class TrainDropout(C.Structure):   # bt_train_dropout
 
 class FrontArgs(C.Structure):   # bt_front_args
     _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("dim", C.c_int32),
-                ("mixed", C.c_int32), ("reserved1", C.c_int32), ("reserved2", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p),
+                ("mixed", C.c_int32), ("operand", C.c_int32), ("reserved2", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p),
                 ("bn_w", C.c_void_p), ("bn_b", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p), ("bn1_w", C.c_void_p),
                 ("bn1_b", C.c_void_p), ("bn1_mean", C.c_void_p), ("bn1_var", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
                 ("save_pre", C.c_void_p), ("gy", C.c_void_p), ("gx", C.c_void_p), ("g_w", C.c_void_p), ("g_b", C.c_void_p),
@@ -146,7 +148,7 @@ class FrontArgs(C.Structure):   # bt_front_args
 
 class FrontBnArgs(C.Structure):   # bt_front_bn_args
     _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("mixed", C.c_int32),
-                ("reserved1", C.c_int32), ("reserved2", C.c_int32), ("reserved3", C.c_int32), ("w", C.c_void_p),
+                ("operand", C.c_int32), ("reserved2", C.c_int32), ("reserved3", C.c_int32), ("w", C.c_void_p),
                 ("bn_w", C.c_void_p), ("bn_b", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p),
                 ("bn_tracked", C.c_void_p), ("bn1_w", C.c_void_p), ("bn1_b", C.c_void_p), ("bn1_mean", C.c_void_p),
                 ("bn1_var", C.c_void_p), ("bn1_tracked", C.c_void_p), ("save_mean", C.c_void_p), ("save_rstd", C.c_void_p),

@@ -26,7 +26,7 @@
 // instantiations without dropout are the code and the launches they were before.  The order of every sum is the same.
 //
 // 16-mixed: the *_mixed entry points run the same unit code with `mixed` set, which sends the GEMMs and
-// the three attention sweeps to the fp16 MFMA kernels of train_mixed.inc; every other launch, and every launch of the entry
+// the three attention sweeps to the fp16 MFMA kernels of train_mixed.inc (bt_train_args.operand = BT_OPERAND_BF16, section 24: their bfloat16 instantiations); every other launch, and every launch of the entry
 // points that existed before, is unchanged.
 #include <hip/hip_runtime.h>
 
@@ -104,14 +104,18 @@ __global__ __launch_bounds__(256) void gemm_drop_kernel(const GemmP p, const Dro
 
 unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
-// What every launch helper below needs to know of the call it serves: the stream, the route (mixed: the fp16 MFMA kernels of
-// train_mixed.inc), and the dropout of the call (null: none, otherwise p > 0).
+// What every launch helper below needs to know of the call it serves: the stream, the route (mixed: 0 = the fp32 kernels of this
+// file, MIXED_F16 / MIXED_BF16 = the MFMA kernels of train_mixed.inc on fp16 / bfloat16 operands), and the dropout of the call
+// (null: none, otherwise p > 0).
+constexpr int MIXED_F16 = 1 + BT_OPERAND_F16, MIXED_BF16 = 1 + BT_OPERAND_BF16;
 struct Launch {
   hipStream_t s;
-  bool mixed;
+  int mixed;
   const bt_train_dropout* dp;
   bool drop() const { return dp != nullptr; }
   DropSite site(int id) const { return drop_site(dp->p, dp->seed, dp->stream, id); }
+  // the kernel of the call's route among the three forms of one launch
+  template <typename K> K pick(K f32, K f16, K bf16) const { return mixed == MIXED_BF16 ? bf16 : mixed ? f16 : f32; }
 };
 constexpr int NO_SITE = -1;   // linear_fwd: a result that no dropout site covers
 
@@ -121,7 +125,7 @@ dim3 gemm_grid(const Launch& lc, const GemmP& p, int chunks) {
 }
 
 template <bool AT, bool BT> void launch_gemm(const Launch& lc, const GemmP& p, int chunks) {
-  const auto kernel = lc.mixed ? mx_gemm_kernel<AT, BT> : gemm_kernel<AT, BT>;
+  const auto kernel = lc.pick(gemm_kernel<AT, BT>, mx_gemm_kernel<_Float16, AT, BT>, mx_gemm_kernel<__bf16, AT, BT>);
   hipLaunchKernelGGL(kernel, gemm_grid(lc, p, chunks), dim3(256), 0, lc.s, p);
 }
 
@@ -133,7 +137,7 @@ void linear_fwd(const Launch& lc, const float* A, const float* W, const float* b
   p.A = A; p.lda = K; p.B = W; p.ldb = K; p.M = (int)M; p.N = N; p.K = K; p.kchunk = K;
   p.C = Y; p.ldc = N; p.bias = bias; p.resid = resid; p.ldr = N; p.accum = accum; p.act = act; p.ldact = N;
   if (!lc.drop() || site == NO_SITE) return launch_gemm<false, false>(lc, p, 1);
-  const auto kernel = lc.mixed ? mx_gemm_drop_kernel : gemm_drop_kernel;
+  const auto kernel = lc.pick(gemm_drop_kernel, mx_gemm_drop_kernel<_Float16>, mx_gemm_drop_kernel<__bf16>);
   hipLaunchKernelGGL(kernel, gemm_grid(lc, p, 1), dim3(256), 0, lc.s, p, lc.site(site), drop_act);
 }
 
@@ -680,9 +684,10 @@ int finish(const char* fn) {
 void attn_fwd_sweep(const Launch& lc, const float* qkv, int B, int T, int D, float* O, float* lse) {
   const dim3 grid(blocks_of(T, lc.mixed ? XB : AB), D / 32, B), block(lc.mixed ? 64 : AB);
   if (!lc.drop()) {
-    hipLaunchKernelGGL(lc.mixed ? mx_attn_fwd_kernel : attn_fwd_kernel, grid, block, 0, lc.s, qkv, T, D, O, lse);
+    const auto kernel = lc.pick(attn_fwd_kernel, mx_attn_fwd_kernel<_Float16>, mx_attn_fwd_kernel<__bf16>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, lc.s, qkv, T, D, O, lse);
   } else {
-    const auto kernel = lc.mixed ? mx_attn_fwd_drop_kernel : attn_fwd_drop_kernel;
+    const auto kernel = lc.pick(attn_fwd_drop_kernel, mx_attn_fwd_drop_kernel<_Float16>, mx_attn_fwd_drop_kernel<__bf16>);
     hipLaunchKernelGGL(kernel, grid, block, 0, lc.s, qkv, T, D, O, lse, lc.site(BT_DROP_ATTN_P));
   }
 }
@@ -693,12 +698,16 @@ void attn_bwd_sweeps(const Launch& lc, const float* qkv, const float* dO, const 
                      float* dqkv) {
   const dim3 grid(blocks_of(T, lc.mixed ? XB : AB), D / 32, B), block(lc.mixed ? 64 : AB);
   if (!lc.drop()) {
-    hipLaunchKernelGGL(lc.mixed ? mx_attn_dkv_kernel : attn_dkv_kernel, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv);
-    hipLaunchKernelGGL(lc.mixed ? mx_attn_dq_kernel : attn_dq_kernel, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv);
+    const auto dkv = lc.pick(attn_dkv_kernel, mx_attn_dkv_kernel<_Float16>, mx_attn_dkv_kernel<__bf16>);
+    const auto dq = lc.pick(attn_dq_kernel, mx_attn_dq_kernel<_Float16>, mx_attn_dq_kernel<__bf16>);
+    hipLaunchKernelGGL(dkv, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv);
+    hipLaunchKernelGGL(dq, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv);
   } else {
     const DropSite pd = lc.site(BT_DROP_ATTN_P);
-    hipLaunchKernelGGL(lc.mixed ? mx_attn_dkv_drop_kernel : attn_dkv_drop_kernel, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv, pd);
-    hipLaunchKernelGGL(lc.mixed ? mx_attn_dq_drop_kernel : attn_dq_drop_kernel, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv, pd);
+    const auto dkv = lc.pick(attn_dkv_drop_kernel, mx_attn_dkv_drop_kernel<_Float16>, mx_attn_dkv_drop_kernel<__bf16>);
+    const auto dq = lc.pick(attn_dq_drop_kernel, mx_attn_dq_drop_kernel<_Float16>, mx_attn_dq_drop_kernel<__bf16>);
+    hipLaunchKernelGGL(dkv, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv, pd);
+    hipLaunchKernelGGL(dq, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv, pd);
   }
 }
 
@@ -779,8 +788,9 @@ int bt_train_forward(void* stream, int unit, const bt_train_args* ap) { return b
 
 int bt_train_backward(void* stream, int unit, const bt_train_args* ap) { return bt_train_backward_dropout(stream, unit, ap, nullptr); }
 
-// mixed: the 16-mixed route (train_mixed.inc) -- the GEMMs and the attention sweeps on fp16 MFMAs, everything else as it is
-static int train_forward(const char* fn, void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp, bool mixed) {
+// mixed (Launch): the 16-mixed route (train_mixed.inc) -- the GEMMs and the attention sweeps on fp16 or bfloat16 MFMAs, everything
+// else as it is
+static int train_forward(const char* fn, void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp, int mixed) {
   if (!ap) return fail(fn, "null argument");
   const bt_train_args& a = *ap;
   if (const char* e = check_shape(unit, a.B, a.T, a.dim, a.hidden, a.rope_len)) return fail(fn, e);
@@ -824,10 +834,10 @@ static int train_forward(const char* fn, void* stream, int unit, const bt_train_
 }
 
 int bt_train_forward_dropout(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
-  return train_forward(dp ? "bt_train_forward_dropout" : "bt_train_forward", stream, unit, ap, dp, false);
+  return train_forward(dp ? "bt_train_forward_dropout" : "bt_train_forward", stream, unit, ap, dp, 0);
 }
 
-static int train_backward(const char* fn, void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp, bool mixed) {
+static int train_backward(const char* fn, void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp, int mixed) {
   if (!ap) return fail(fn, "null argument");
   const bt_train_args& a = *ap;
   if (const char* e = check_shape(unit, a.B, a.T, a.dim, a.hidden, a.rope_len)) return fail(fn, e);
@@ -934,7 +944,7 @@ static int train_backward(const char* fn, void* stream, int unit, const bt_train
 }
 
 int bt_train_backward_dropout(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
-  return train_backward(dp ? "bt_train_backward_dropout" : "bt_train_backward", stream, unit, ap, dp, false);
+  return train_backward(dp ? "bt_train_backward_dropout" : "bt_train_backward", stream, unit, ap, dp, 0);
 }
 
 // ---- the 16-mixed route: the attention and the feed-forward only ---------------------------------------
@@ -944,14 +954,24 @@ size_t bt_train_workspace_bytes_mixed(int unit, int backward, int B, int T, int 
   return layout(unit, backward != 0, (long)B * T, dim, hidden, with_dropout != 0).total * sizeof(float);
 }
 
+// what the two entry points below refuse ahead of everything the fp32 ones check; *mixed: the route of bt_train_args.operand
+static const char* check_mixed_call(int unit, const bt_train_args* ap, int* mixed) {
+  if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return "unit must be BT_UNIT_ATTN or BT_UNIT_FF";
+  if (ap && ap->operand != BT_OPERAND_F16 && ap->operand != BT_OPERAND_BF16) return "operand must be BT_OPERAND_F16 or BT_OPERAND_BF16";
+  *mixed = ap ? 1 + ap->operand : MIXED_F16;
+  return nullptr;
+}
+
 int bt_train_forward_mixed(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
-  if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return fail("bt_train_forward_mixed", "unit must be BT_UNIT_ATTN or BT_UNIT_FF");
-  return train_forward("bt_train_forward_mixed", stream, unit, ap, dp, true);
+  int mixed = 0;
+  if (const char* e = check_mixed_call(unit, ap, &mixed)) return fail("bt_train_forward_mixed", e);
+  return train_forward("bt_train_forward_mixed", stream, unit, ap, dp, mixed);
 }
 
 int bt_train_backward_mixed(void* stream, int unit, const bt_train_args* ap, const bt_train_dropout* dp) {
-  if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return fail("bt_train_backward_mixed", "unit must be BT_UNIT_ATTN or BT_UNIT_FF");
-  return train_backward("bt_train_backward_mixed", stream, unit, ap, dp, true);
+  int mixed = 0;
+  if (const char* e = check_mixed_call(unit, ap, &mixed)) return fail("bt_train_backward_mixed", e);
+  return train_backward("bt_train_backward_mixed", stream, unit, ap, dp, mixed);
 }
 
 int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B, int M, int N, int K, float* C) {
@@ -959,7 +979,7 @@ int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B
   if (!A || !B || !C) return fail(fn, "null argument");
   if (form < 0 || form > 2) return fail(fn, "form must be 0 (A W^T), 1 (dY W) or 2 (dY^T A)");
   if (const char* e = check_mnk(M, N, K)) return fail(fn, e);
-  const Launch lc{(hipStream_t)stream, true, nullptr};
+  const Launch lc{(hipStream_t)stream, MIXED_F16, nullptr};
   if (form == 0) {          // A [M, K], B [N, K]
     linear_fwd(lc, A, B, nullptr, M, N, K, C, nullptr, nullptr);
   } else if (form == 1) {   // A [M, K], B [K, N]
@@ -985,6 +1005,7 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
                     const float* bias, const float* resid, int accum, float* act, const bt_train_dropout* dp, int site,
                     int drop_act, void* ws, size_t ws_bytes) {
   const char* fn = "bt_train_matmul";
+  if (mixed < 0 || mixed > MIXED_BF16) return fail(fn, "mixed must be 0 (fp32), 1 (fp16 operands) or 2 (bfloat16 operands)");
   if (!A || !B || !C) return fail(fn, "null argument");
   if (form < 0 || form > 2) return fail(fn, "form must be 0 (A W^T), 1 (dY W) or 2 (dY^T A)");
   if (const char* e = check_mnk(M, N, K)) return fail(fn, e);
@@ -995,7 +1016,7 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
   if (drop && (site < BT_DROP_ATTN_OUT || site > BT_DROP_FF_OUT)) return fail(fn, "site must be one of the row sites of BT_DROP_*");
   if (drop && N % 4) return fail(fn, "with dropout N must be a multiple of 4");
   if (drop && drop_act && !act) return fail(fn, "drop_act masks act, which is null");
-  const Launch lc{(hipStream_t)stream, mixed != 0, drop ? dp : nullptr};
+  const Launch lc{(hipStream_t)stream, mixed, drop ? dp : nullptr};
   if (form == 0) {          // A [M, K], B [N, K]
     linear_fwd(lc, A, B, bias, M, N, K, C, resid, act, site, drop_act, accum != 0);
   } else if (form == 1) {   // A [M, K], B [K, N]
@@ -1011,6 +1032,7 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
 int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int dim, const float* qkv,
                        const bt_train_dropout* dp, float* O, float* lse, const float* dO, const float* delta, float* dqkv) {
   const char* fn = "bt_train_attention";
+  if (mixed < 0 || mixed > MIXED_BF16) return fail(fn, "mixed must be 0 (fp32), 1 (fp16 operands) or 2 (bfloat16 operands)");
   if (const char* e = check_width(dim)) return fail(fn, e);
   if (B < 1 || B > 65535 || T < 1 || (long)B * T > (1L << 22)) return fail(fn, "need 1 <= B <= 65535, T >= 1 and B T <= 2^22");
   if (!qkv || !lse || (backward ? !dO || !delta || !dqkv : !O)) return fail(fn, "null argument");
@@ -1018,7 +1040,7 @@ int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int 
     return fail(fn, "qkv, O, dO and dqkv must be 16-byte aligned");
   bool drop = false;
   if (const char* e = check_p(dp, &drop)) return fail(fn, e);
-  const Launch lc{(hipStream_t)stream, mixed != 0, drop ? dp : nullptr};
+  const Launch lc{(hipStream_t)stream, mixed, drop ? dp : nullptr};
   if (!backward)
     attn_fwd_sweep(lc, qkv, B, T, dim, O, lse);
   else

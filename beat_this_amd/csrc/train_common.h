@@ -14,6 +14,26 @@ namespace {
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
+// The operand element type of the 16-mixed kernels (DESIGN.md sections 16, 19 and 24), _Float16 or __bf16: its fragments of four
+// and eight and its 32x32x16 MFMA.  Lane maps and rates are the same for both; float -> E is the compiler's conversion (round to
+// nearest even; fp16 overflows to inf, bf16 has fp32's exponent range).
+template <typename E> struct Operand;
+template <> struct Operand<_Float16> {
+  typedef _Float16 x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 x8 __attribute__((ext_vector_type(8)));
+  static __device__ inline f32x16 mfma(x8 a, x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+template <> struct Operand<__bf16> {
+  typedef __bf16 x4 __attribute__((ext_vector_type(4)));
+  typedef __bf16 x8 __attribute__((ext_vector_type(8)));
+  static __device__ inline f32x16 mfma(x8 a, x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <typename E> using h16x4 = typename Operand<E>::x4;
+template <typename E> using h16x8 = typename Operand<E>::x8;
+
+template <typename E>
+__device__ inline h16x4<E> to_h4(f32x4 v) { return h16x4<E>{(E)v[0], (E)v[1], (E)v[2], (E)v[3]}; }
+
 constexpr float QK_SCALE = 0.17677669529663687f;            // 32^-0.5
 constexpr float QK_SCALE_LOG2E = 0.2550348616841918f;       // 32^-0.5 * log2(e)
 

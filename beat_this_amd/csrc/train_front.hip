@@ -27,7 +27,8 @@
 // the stem (K = 12, vector unit) recomputes it.
 // With `mixed = 1` in the argument struct the same three products run on v_mfma_f32_32x32x16_f16 with both
 // operands rounded to fp16 as they are staged (train_front_mixed.inc) and the projection's GEMMs take bt_train_matmul's mixed
-// route; everything around the products is the code below either way.
+// route; `operand = BT_OPERAND_BF16` beside it (section 24) rounds to bfloat16 on v_mfma_f32_32x32x16_bf16 instead; everything
+// around the products is the code below either way.
 //
 // Reproducibility, as in train.hip: no atomics; every output element is written by one thread of one launch; a GEMM element
 // sums k ascending; weight gradients over chunks of DW_ROWS rows and column sums over chunks of CS_ROWS rows, partials added in
@@ -210,7 +211,7 @@ struct ConvP {
   float* out2;
   int T, Fo, Cin, Cout;
   long M;              // B T Fo
-  const _Float16* wh;  // 16-mixed: the packed fp16 weight of the launch's MODE (train_front_mixed.inc)
+  const void* wh;      // 16-mixed: the packed fp16 / bfloat16 weight of the launch's MODE (train_front_mixed.inc)
 };
 
 // implicit A of the forward: row m = (b, t, fo), column k = dt 2 Cin + (df Cin + ci); zeros at t + dt - 1 outside [0, T)
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvP p) {
   conv_store<MODE>(p, tile, acc, wm, wn, lr, g);
 }
 
-#include "train_front_mixed.inc"   // conv_pack_kernel, conv_gemm_mixed_kernel<MODE>: the same three products on fp16 MFMAs
+#include "train_front_mixed.inc"   // conv_pack_kernel<E>, conv_gemm_mixed_kernel<E, MODE>: the same three products on 16-bit MFMAs
 
 // gw [Cout][Cin][2][3] = the partials [chunk][Cout][dt 2 Cin + df Cin + ci] added in chunk order
 __global__ __launch_bounds__(256) void conv_dw_reduce_kernel(const float* part, int Cout, int Cin, int chunks, float* gw) {
@@ -557,11 +558,13 @@ const char* bn_check_shape(int unit, int B, int T, int F, int C) {
   return nullptr;
 }
 
-// 16-mixed: the units that have a mixed form (the projection's is bt_train_matmul's, which bt_front_bn_args does not reach)
-const char* check_mixed(int unit, int mixed, bool linear_too) {
+// 16-mixed: the units that have a mixed form (the projection's is bt_train_matmul's, which bt_front_bn_args does not reach), and
+// the operand format, which only a mixed call reads
+const char* check_mixed(int unit, int mixed, int operand, bool linear_too) {
   if (mixed != 0 && mixed != 1) return "mixed must be 0 or 1";
   if (mixed && unit != BT_FRONT_CONV && !(linear_too && unit == BT_FRONT_LINEAR))
     return "mixed = 1 belongs to BT_FRONT_CONV and (bt_front_args) BT_FRONT_LINEAR: the other units have no product worth an MFMA";
+  if (mixed && operand != BT_OPERAND_F16 && operand != BT_OPERAND_BF16) return "mixed = 1: operand must be BT_OPERAND_F16 or BT_OPERAND_BF16";
   return nullptr;
 }
 
@@ -588,7 +591,7 @@ struct Bn {
 
 struct Call {
   int B, T, F, C, dim;
-  int mixed;   // as the caller gave it: check_mixed refuses everything but 0 and 1
+  int mixed, operand;   // as the caller gave them: check_mixed refuses what it does not know
   bool batch, backward;
   Bn bn, bn1;  // bn2d or blocks.i.norm; the stem's bn1d
   const float *w, *b, *x, *gy;
@@ -598,7 +601,7 @@ struct Call {
 };
 
 Call describe(const bt_front_args& a, bool backward) {
-  Call c{a.B, a.T, a.F, a.C, a.dim, a.mixed, false, backward};
+  Call c{a.B, a.T, a.F, a.C, a.dim, a.mixed, a.operand, false, backward};
   // (running statistics: the two buffers are only read)
   c.bn = Bn{a.bn_w, a.bn_b, const_cast<float*>(a.bn_mean), const_cast<float*>(a.bn_var), nullptr, nullptr, nullptr, a.g_bn_w, a.g_bn_b};
   c.bn1 = Bn{a.bn1_w, a.bn1_b, const_cast<float*>(a.bn1_mean), const_cast<float*>(a.bn1_var), nullptr, nullptr, nullptr, a.g_bn1_w, a.g_bn1_b};
@@ -609,7 +612,7 @@ Call describe(const bt_front_args& a, bool backward) {
 }
 
 Call describe(const bt_front_bn_args& a, bool backward) {
-  Call c{a.B, a.T, a.F, a.C, 0, a.mixed, true, backward};
+  Call c{a.B, a.T, a.F, a.C, 0, a.mixed, a.operand, true, backward};
   c.bn = Bn{a.bn_w, a.bn_b, a.bn_mean, a.bn_var, a.bn_tracked, a.save_mean, a.save_rstd, a.g_bn_w, a.g_bn_b};
   c.bn1 = Bn{a.bn1_w, a.bn1_b, a.bn1_mean, a.bn1_var, a.bn1_tracked, a.save1_mean, a.save1_rstd, a.g_bn1_w, a.g_bn1_b};
   c.w = a.w, c.x = a.x, c.gy = a.gy;
@@ -650,7 +653,7 @@ const char* check_pointers(int unit, const Call& c) {
 // The preamble of the four entry points, before any launch.  The order: shape, mixed, required pointers, alignment, workspace size.
 int prepare(const char* fn, int unit, const Call& c, Layout& L) {
   const char* e = c.batch ? bn_check_shape(unit, c.B, c.T, c.F, c.C) : check_shape(unit, c.B, c.T, c.F, c.C, c.dim);
-  if (!e) e = check_mixed(unit, c.mixed, !c.batch);
+  if (!e) e = check_mixed(unit, c.mixed, c.operand, !c.batch);
   if (!e) e = check_pointers(unit, c);
   if (!e && c.batch && !c.backward && (uintptr_t)c.ws % 8) e = "the workspace must be 8-byte aligned";   // (the moments are doubles)
   if (!e && c.mixed && (uintptr_t)c.ws % 16) e = "mixed = 1: the workspace must be 16-byte aligned";
@@ -738,16 +741,24 @@ void stem_backward(hipStream_t s, const Call& c, const Layout& L) {
 
 dim3 conv_grid(long GM, int GN, int chunks) { return dim3(blocks_of(GN, GT), blocks_of(GM, GT), (unsigned)chunks); }
 
-// One conv GEMM.  wimg: the workspace of the fp16 weight image (16-mixed), null = the fp32 kernel.  MODE 0 and 1 read the weight
-// from the image, which a launch ahead of the GEMM packs ([co][k] for MODE 0, transposed for MODE 1); MODE 2 has no weight operand.
-template <int MODE>
-void launch_conv(hipStream_t s, ConvP p, float* wimg, dim3 grid) {
+// One conv GEMM.  wimg: the workspace of the 16-bit weight image (16-mixed, elements E), null = the fp32 kernel.  MODE 0 and 1
+// read the weight from the image, which a launch ahead of the GEMM packs ([co][k] for MODE 0, transposed for MODE 1); MODE 2 has
+// no weight operand.
+template <typename E, int MODE>
+void launch_conv_as(hipStream_t s, ConvP p, float* wimg, dim3 grid) {
   if (wimg && MODE != 2) {
-    hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_of((long)p.Cout * 6 * p.Cin, 256)), dim3(256), 0, s, p.w, p.Cout, p.Cin, MODE,
-                       (_Float16*)wimg);
-    p.wh = (const _Float16*)wimg;
+    hipLaunchKernelGGL(conv_pack_kernel<E>, dim3(blocks_of((long)p.Cout * 6 * p.Cin, 256)), dim3(256), 0, s, p.w, p.Cout, p.Cin, MODE,
+                       (E*)wimg);
+    p.wh = wimg;
   }
-  hipLaunchKernelGGL(wimg ? conv_gemm_mixed_kernel<MODE> : conv_gemm_kernel<MODE>, grid, dim3(256), 0, s, p);
+  const auto kernel = wimg ? conv_gemm_mixed_kernel<E, MODE> : conv_gemm_kernel<MODE>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, p);
+}
+// ... with the operand format of the call (read only where wimg is given)
+template <int MODE>
+void launch_conv(hipStream_t s, const Call& c, const ConvP& p, float* wimg, dim3 grid) {
+  if (wimg && c.operand == BT_OPERAND_BF16) launch_conv_as<__bf16, MODE>(s, p, wimg, grid);
+  else launch_conv_as<_Float16, MODE>(s, p, wimg, grid);
 }
 
 void conv_forward(hipStream_t s, const Call& c, const Layout& L) {
@@ -757,7 +768,7 @@ void conv_forward(hipStream_t s, const Call& c, const Layout& L) {
   const float* f2 = ws + L.fold;
   // batch statistics: the GEMM writes pre alone (no GELU output), the table comes from pre's moments, then the GELU
   if (!c.batch) fold_table(s, c, c.bn, Cout, nullptr, 0, L, ws + L.fold);
-  launch_conv<0>(s, ConvP{c.x, c.w, nullptr, f2, c.save_pre, c.batch ? nullptr : c.y, c.T, Fo, c.C, Cout, M},
+  launch_conv<0>(s, c, ConvP{c.x, c.w, nullptr, f2, c.save_pre, c.batch ? nullptr : c.y, c.T, Fo, c.C, Cout, M},
                  c.mixed ? ws + L.wimg : nullptr, conv_grid(M, Cout, 1));
   if (c.batch) {
     fold_table(s, c, c.bn, Cout, c.save_pre, M, L, ws + L.fold);
@@ -781,22 +792,25 @@ void conv_backward(hipStream_t s, const Call& c, const Layout& L) {
   ConvP p{c.x, c.w, ws + L.a, f2, nullptr, nullptr, c.T, Fo, c.C, Cout, M};
   if (c.gx) {
     p.out = c.gx;
-    launch_conv<1>(s, p, wimg, conv_grid(M, 2 * c.C, 1));
+    launch_conv<1>(s, c, p, wimg, conv_grid(M, 2 * c.C, 1));
   }
   if (c.g_w) {
     const int chunks = dw_chunks(M);
     p.out = part;
-    launch_conv<2>(s, p, wimg, conv_grid(Cout, 6 * c.C, chunks));
+    launch_conv<2>(s, c, p, wimg, conv_grid(Cout, 6 * c.C, chunks));
     hipLaunchKernelGGL(conv_dw_reduce_kernel, dim3(blocks_of((long)Cout * 6 * c.C, 256)), dim3(256), 0, s, (const float*)part, Cout, c.C,
                        chunks, c.g_w);
   }
 }
 
+// the projection's `mixed` of bt_train_matmul: 0, or 1 + the operand format
+int matmul_route(const Call& c) { return c.mixed ? 1 + c.operand : 0; }
+
 int linear_forward(void* stream, const Call& c, const Layout& L) {
   float* ws = (float*)c.ws;
   const long BT = (long)c.B * c.T;
   swap((hipStream_t)stream, c.x, BT, c.F, c.C, 1, ws + L.a);   // (f c) -> (c f)
-  return bt_train_matmul(stream, c.mixed, 0, ws + L.a, c.w, (int)BT, c.dim, c.F * c.C, c.y, c.b, nullptr, 0, nullptr, nullptr, 0, 0,
+  return bt_train_matmul(stream, matmul_route(c), 0, ws + L.a, c.w, (int)BT, c.dim, c.F * c.C, c.y, c.b, nullptr, 0, nullptr, nullptr, 0, 0,
                          nullptr, 0);
 }
 
@@ -808,12 +822,12 @@ int linear_backward(void* stream, const Call& c, const Layout& L) {
   if (c.g_b) colsum(s, c.gy, BT, c.dim, ws + L.part, c.g_b);
   if (c.g_w) {
     swap(s, c.x, BT, c.F, c.C, 1, ws + L.a);
-    if (int rc = bt_train_matmul(stream, c.mixed, 2, c.gy, ws + L.a, c.dim, K, (int)BT, c.g_w, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
+    if (int rc = bt_train_matmul(stream, matmul_route(c), 2, c.gy, ws + L.a, c.dim, K, (int)BT, c.g_w, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
                                  ws + L.part, (L.total - L.part) * sizeof(float)))
       return rc;
   }
   if (c.gx) {
-    if (int rc = bt_train_matmul(stream, c.mixed, 1, c.gy, c.w, (int)BT, K, c.dim, ws + L.b, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
+    if (int rc = bt_train_matmul(stream, matmul_route(c), 1, c.gy, c.w, (int)BT, K, c.dim, ws + L.b, nullptr, nullptr, 0, nullptr, nullptr, 0, 0,
                                  nullptr, 0))
       return rc;
     swap(s, ws + L.b, BT, c.C, c.F, 1, c.gx);   // (c f) -> (f c)
@@ -844,7 +858,7 @@ int run(const char* fn, void* stream, int unit, const Call& c) {
 
 size_t workspace_bytes(int unit, int backward, bool batch, bool mixed, int B, int T, int F, int C, int dim) {
   if (batch ? bn_check_shape(unit, B, T, F, C) : check_shape(unit, B, T, F, C, dim)) return 0;
-  if (mixed && check_mixed(unit, 1, !batch)) return 0;
+  if (mixed && check_mixed(unit, 1, BT_OPERAND_F16, !batch)) return 0;
   return layout(unit, backward != 0, batch, mixed, (long)B * T, F, C, dim).total * sizeof(float);
 }
 

@@ -4,6 +4,9 @@
 // THE CONTRACT is section 16's: both operands of pre = A W^T, g_x = G W and g_W = G^T A are rounded to IEEE fp16 (to nearest
 // even, beyond its range: inf) as they are staged, G = g_pre s being multiplied in fp32 first, and the products accumulate in
 // fp32 on v_mfma_f32_32x32x16_f16.  Nothing clamps.  Everything around the products is the fp32 code of train_front.hip.
+// The kernels are templates over the operand element type E (Operand<E>, train_common.h): _Float16 is the above, __bf16 (section
+// 24) rounds to bfloat16 instead -- NaN stays NaN, nothing overflows -- on v_mfma_f32_32x32x16_bf16, the weight image in the
+// same bytes.
 //
 // Lane maps of the 32x32x16 fp16 MFMA (train_mixed.inc): lane l, r = l & 31, h = l >> 5, element j = 0 .. 7 of a fragment is
 // A[row r][k = 8 h + j] and B[k = 8 h + j][col r]; C / D register i is row (i & 3) + 8 (i >> 2) + 4 h, col r.  Both operand tiles
@@ -23,20 +26,17 @@
 // g_W sums the rows ascending in steps of 16 inside each chunk of BT_TRAIN_DW_ROWS rows, and conv_dw_reduce_kernel adds the
 // chunks in order.  No atomics, one thread of one launch per output byte, a row's results depend on its own sequence only.
 
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int MK = 32;         // k per staging step: two MFMA steps
 constexpr int MLD = MK + 8;    // halves per LDS row (80 bytes)
 
-__device__ inline h16x4 to_h4(f32x4 v) { return h16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]}; }
 __device__ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 __device__ inline f32x4 load4(const float* p, bool vec) {
   return vec ? *reinterpret_cast<const f32x4*>(p) : f32x4{p[0], p[1], p[2], p[3]};
 }
 
-// img [Cout][6 Cin] (transposed == 0: k = dt 2 Cin + df Cin + ci) or [2 Cin][3 Cout] (k = dt Cout + co) = fp16(w[co][ci][df][dt])
-__global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, int Cout, int Cin, int transposed, _Float16* img) {
+// img [Cout][6 Cin] (transposed == 0: k = dt 2 Cin + df Cin + ci) or [2 Cin][3 Cout] (k = dt Cout + co) = E(w[co][ci][df][dt])
+template <typename E>
+__global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, int Cout, int Cin, int transposed, E* img) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= Cout * 6 * Cin) return;
   int co, j, dt;
@@ -52,14 +52,14 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, int Cout
     co = k - dt * Cout;
   }
   const int df = j / Cin, ci = j - df * Cin;
-  img[i] = (_Float16)w[((long)co * Cin + ci) * 6 + df * 3 + dt];
+  img[i] = (E)w[((long)co * Cin + ci) * 6 + df * 3 + dt];
 }
 
-// conv_gemm_kernel<MODE> with fp16 operands: the same grid, tile and epilogue.  p.wh: the packed weight (MODE 0 and 1).
-template <int MODE>
+// conv_gemm_kernel<MODE> with operands of type E: the same grid, tile and epilogue.  p.wh: the packed weight (MODE 0 and 1).
+template <typename E, int MODE>
 __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
-  __shared__ __attribute__((aligned(16))) _Float16 As[GT][MLD];
-  __shared__ __attribute__((aligned(16))) _Float16 Bs[GT][MLD];
+  __shared__ __attribute__((aligned(16))) E As[GT][MLD];
+  __shared__ __attribute__((aligned(16))) E Bs[GT][MLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 5, lr = lane & 31, wm = wave >> 1, wn = wave & 1;
   const ConvTile<MODE> tile(p);
@@ -79,8 +79,8 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
   }
   const int dt2 = tile.n0 / tile.C2, j2 = tile.n0 - dt2 * tile.C2;   // MODE 2: the run and the first column of this tile of the implicit A
 
-  h16x4 ra[2], rb[2];
-  h16x8 rw;
+  h16x4<E> ra[2], rb[2];
+  h16x8<E> rw;
   auto fetch = [&](long k0) {
     if constexpr (MODE != 2) {
       const int dt = (int)(k0 / run), j0 = (int)(k0 - (long)dt * run);
@@ -98,11 +98,11 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
             for (int c = 0; c < 4; ++c) v[c] *= p.fold[j0 + kk + c];
           }
         }
-        ra[i] = to_h4(v);
+        ra[i] = to_h4<E>(v);
       }
       const int gn = tile.n0 + (tid >> 2);
-      rw = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (gn < tile.GN) rw = *reinterpret_cast<const h16x8*>(p.wh + (long)gn * KW + k0 + (tid & 3) * 8);
+      rw = h16x8<E>{0, 0, 0, 0, 0, 0, 0, 0};
+      if (gn < tile.GN) rw = *reinterpret_cast<const h16x8<E>*>((const E*)p.wh + (long)gn * KW + k0 + (tid & 3) * 8);
     } else {
       const int c4 = (tid & 15) * 4;
 #pragma unroll
@@ -118,16 +118,16 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
           const int t = (int)((gk / p.Fo) % p.T) + dt2 - 1;
           if (tile.n0 + c4 < tile.GN && t >= 0 && t < p.T) b = load4(p.x + (gk + (long)(dt2 - 1) * p.Fo) * tile.C2 + j2 + c4, vx);
         }
-        ra[i] = to_h4(a);
-        rb[i] = to_h4(b);
+        ra[i] = to_h4<E>(a);
+        rb[i] = to_h4<E>(b);
       }
     }
   };
   auto commit = [&]() {
     if constexpr (MODE != 2) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i) *reinterpret_cast<h16x4*>(&As[i * 32 + (tid >> 3)][(tid & 7) * 4]) = ra[i];
-      *reinterpret_cast<h16x8*>(&Bs[tid >> 2][(tid & 3) * 8]) = rw;
+      for (int i = 0; i < 2; ++i) *reinterpret_cast<h16x4<E>*>(&As[i * 32 + (tid >> 3)][(tid & 7) * 4]) = ra[i];
+      *reinterpret_cast<h16x8<E>*>(&Bs[tid >> 2][(tid & 3) * 8]) = rw;
     } else {
       const int c4 = (tid & 15) * 4;
 #pragma unroll
@@ -152,8 +152,8 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
     if (k0 + MK < tile.ke) fetch(k0 + MK);
 #pragma unroll
     for (int s = 0; s < MK / 16; ++s)
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h16x8*>(&As[wm * 32 + lr][16 * s + 8 * g]),
-                                                   *reinterpret_cast<const h16x8*>(&Bs[wn * 32 + lr][16 * s + 8 * g]), acc, 0, 0, 0);
+      acc = Operand<E>::mfma(*reinterpret_cast<const h16x8<E>*>(&As[wm * 32 + lr][16 * s + 8 * g]),
+                             *reinterpret_cast<const h16x8<E>*>(&Bs[wn * 32 + lr][16 * s + 8 * g]), acc);
     __syncthreads();
   }
   conv_store<MODE>(p, tile, acc, wm, wn, lr, g);

@@ -3,6 +3,10 @@
 // THE CONTRACT: both operands of every matrix product are rounded to IEEE fp16 (round to nearest even) as they are staged, and
 // the product accumulates in fp32 on v_mfma_f32_32x32x16_f16.  Everything else of the route is the fp32 code of train.hip.  A
 // value beyond fp16's range becomes inf and propagates: nothing clamps, the loss scaler sees it in the gradient norm.
+// Every kernel below is a template over the operand element type E (Operand<E>, train_common.h): E = _Float16 is that contract,
+// E = __bf16 (DESIGN.md section 24) is the same with one word changed -- both operands rounded to bfloat16, to nearest even, NaN
+// stays NaN, nothing overflows by rounding -- on v_mfma_f32_32x32x16_bf16.  Staging, lane maps, orders of summation and the mask
+// mapping do not depend on E.
 //
 // Lane maps of the 32x32x16 fp16 MFMA (lane l, r = l & 31, h = l >> 5, element j = 0 .. 7 of a fragment):
 //   A[row r][k = 8 h + j],  B[k = 8 h + j][col r],  C / D register i: row = (i & 3) + 8 (i >> 2) + 4 h, col = r.
@@ -18,21 +22,16 @@
 
 namespace {
 
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int MT = 128;        // GEMM tile: MT x MT outputs per workgroup of four waves (2 x 2 waves of 2 x 2 MFMA tiles)
 constexpr int MK = 32;         // k per staging step
 constexpr int MLD = MK + 8;    // halves per LDS row: 80 bytes, so the 16-byte fragment reads of 32 rows spread over the banks
 constexpr int XB = 32;         // attention: queries (keys) per wave and keys (queries) per tile
 
-__device__ inline h16x4 to_h4(f32x4 v) { return h16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]}; }
-
 // Stage rows [r0, r0 + MT) x k [k0, k0 + MK) of an operand as fp16 into S[row][k].  TR: the operand is stored [k][row].  What
 // lies behind row R or behind k = ke is zero and is never read; `vec`: 16-byte loads are possible (alignment of the base, the
 // leading dimension and the chunk's first k).
-template <bool TR>
-__device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k0, long ke, bool vec, _Float16 (*S)[MLD], int tid) {
+template <typename E, bool TR>
+__device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k0, long ke, bool vec, E (*S)[MLD], int tid) {
 #pragma unroll
   for (int i = 0; i < MT * MK / 4 / 256; ++i) {
     const int gi = tid + i * 256;
@@ -50,7 +49,7 @@ __device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k
             if (gk + c < ke) v[c] = p[c];
         }
       }
-      *reinterpret_cast<h16x4*>(&S[row][kk]) = to_h4(v);
+      *reinterpret_cast<h16x4<E>*>(&S[row][kk]) = to_h4<E>(v);
     } else {
       const int kk = gi >> 5, row = (gi & 31) * 4;
       const long gr = r0 + row, gk = k0 + kk;
@@ -65,7 +64,7 @@ __device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k
         }
       }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) S[row + c][kk] = (_Float16)v[c];
+      for (int c = 0; c < 4; ++c) S[row + c][kk] = (E)v[c];
     }
   }
 }
@@ -73,10 +72,10 @@ __device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k
 __device__ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // gemm_body with fp16 operands: the same GemmP, the same epilogue (bias, residual, +=, GELU into a second output, dropout)
-template <bool AT, bool BT, bool DROP>
+template <typename E, bool AT, bool BT, bool DROP>
 __device__ inline void mx_gemm_body(const GemmP& p, const DropSite& ds, int drop_act) {
-  __shared__ __attribute__((aligned(16))) _Float16 As[MT][MLD];
-  __shared__ __attribute__((aligned(16))) _Float16 Bs[MT][MLD];
+  __shared__ __attribute__((aligned(16))) E As[MT][MLD];
+  __shared__ __attribute__((aligned(16))) E Bs[MT][MLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 5, lr = lane & 31, wm = wave >> 1, wn = wave & 1;
   const long m0 = (long)blockIdx.y * MT, n0 = (long)blockIdx.x * MT;
@@ -91,21 +90,21 @@ __device__ inline void mx_gemm_body(const GemmP& p, const DropSite& ds, int drop
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
   for (long k0 = kb; k0 < ke; k0 += MK) {
-    mx_stage<AT>(p.A, p.lda, m0, p.M, k0, ke, va, As, tid);
-    mx_stage<BT>(p.B, p.ldb, n0, p.N, k0, ke, vb, Bs, tid);
+    mx_stage<E, AT>(p.A, p.lda, m0, p.M, k0, ke, va, As, tid);
+    mx_stage<E, BT>(p.B, p.ldb, n0, p.N, k0, ke, vb, Bs, tid);
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < MK / 16; ++s) {
-      h16x8 a[2], b[2];
+      h16x8<E> a[2], b[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        a[i] = *reinterpret_cast<const h16x8*>(&As[wm * 64 + i * 32 + lr][16 * s + 8 * g]);
-        b[i] = *reinterpret_cast<const h16x8*>(&Bs[wn * 64 + i * 32 + lr][16 * s + 8 * g]);
+        a[i] = *reinterpret_cast<const h16x8<E>*>(&As[wm * 64 + i * 32 + lr][16 * s + 8 * g]);
+        b[i] = *reinterpret_cast<const h16x8<E>*>(&Bs[wn * 64 + i * 32 + lr][16 * s + 8 * g]);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < 2; ++j) acc[i][j] = Operand<E>::mfma(a[i], b[j], acc[i][j]);
     }
     __syncthreads();
   }
@@ -116,63 +115,67 @@ __device__ inline void mx_gemm_body(const GemmP& p, const DropSite& ds, int drop
   gemm_epilogue<DROP>(p, ds, drop_act, C, acc[1][1], m0 + wm * 64 + 32, n0 + wn * 64 + 32 + lr, lane);
 }
 
-template <bool AT, bool BT>
+template <typename E, bool AT, bool BT>
 __global__ __launch_bounds__(256) void mx_gemm_kernel(const GemmP p) {
-  mx_gemm_body<AT, BT, false>(p, DropSite{}, 0);
+  mx_gemm_body<E, AT, BT, false>(p, DropSite{}, 0);
 }
 
+template <typename E>
 __global__ __launch_bounds__(256) void mx_gemm_drop_kernel(const GemmP p, const DropSite ds, const int drop_act) {
-  mx_gemm_body<false, false, true>(p, ds, drop_act);
+  mx_gemm_body<E, false, false, true>(p, ds, drop_act);
 }
 
 // ---- attention, head dim 32, one wave per workgroup: XB own rows against tiles of XB rows of the other side -------------------
 // Stage rows [t0, t0 + XB) of a [T, 32] slice (row stride ld) as fp16: R[row][d] and / or Tt[d][row]; rows >= T are zeros.
-__device__ inline void mx_stage32(const float* base, long ld, int t0, int T, _Float16 (*R)[MLD], _Float16 (*Tt)[MLD], int lane) {
+template <typename E>
+__device__ inline void mx_stage32(const float* base, long ld, int t0, int T, E (*R)[MLD], E (*Tt)[MLD], int lane) {
 #pragma unroll
   for (int i = 0; i < XB * 8 / 64; ++i) {
     const int idx = i * 64 + lane, row = idx >> 3, part = idx & 7;
     const int t = t0 + row;
     const f32x4 v = t < T ? reinterpret_cast<const f32x4*>(base + (long)t * ld)[part] : f32x4{0.f, 0.f, 0.f, 0.f};
-    if (R) *reinterpret_cast<h16x4*>(&R[row][4 * part]) = to_h4(v);
+    if (R) *reinterpret_cast<h16x4<E>*>(&R[row][4 * part]) = to_h4<E>(v);
     if (Tt) {
 #pragma unroll
-      for (int c = 0; c < 4; ++c) Tt[4 * part + c][row] = (_Float16)v[c];
+      for (int c = 0; c < 4; ++c) Tt[4 * part + c][row] = (E)v[c];
     }
   }
 }
 
 // the own side's row r as the B operand [k = d][col r] of both k-steps
-__device__ inline void mx_own_frag(const float* row, bool ok, int h, h16x8 (&f)[2]) {
+template <typename E>
+__device__ inline void mx_own_frag(const float* row, bool ok, int h, h16x8<E> (&f)[2]) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const f32x4 lo = ok ? reinterpret_cast<const f32x4*>(row + 16 * s + 8 * h)[0] : f32x4{0.f, 0.f, 0.f, 0.f};
     const f32x4 hi = ok ? reinterpret_cast<const f32x4*>(row + 16 * s + 8 * h)[1] : f32x4{0.f, 0.f, 0.f, 0.f};
-    f[s] = h16x8{(_Float16)lo[0], (_Float16)lo[1], (_Float16)lo[2], (_Float16)lo[3],
-                 (_Float16)hi[0], (_Float16)hi[1], (_Float16)hi[2], (_Float16)hi[3]};
+    f[s] = h16x8<E>{(E)lo[0], (E)lo[1], (E)lo[2], (E)lo[3], (E)hi[0], (E)hi[1], (E)hi[2], (E)hi[3]};
   }
 }
 
 // X[tile row][own col] = sum_d R[tile row][d] own[col][d]
-__device__ inline f32x16 mx_first(const _Float16 (*R)[MLD], const h16x8 (&own)[2], int r, int h) {
+template <typename E>
+__device__ inline f32x16 mx_first(const E (*R)[MLD], const h16x8<E> (&own)[2], int r, int h) {
   f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
 #pragma unroll
   for (int s = 0; s < 2; ++s)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h16x8*>(&R[r][16 * s + 8 * h]), own[s], acc, 0, 0, 0);
+    acc = Operand<E>::mfma(*reinterpret_cast<const h16x8<E>*>(&R[r][16 * s + 8 * h]), own[s], acc);
   return acc;
 }
 
 // acc[d][own col] += sum_rows Tt[d][tile row] X[tile row][own col], X = the sixteen fp32 values of a lane, rounded here
-__device__ inline void mx_second(const _Float16 (*Tt)[MLD], const float (&x)[16], int r, int h, f32x16& acc) {
+template <typename E>
+__device__ inline void mx_second(const E (*Tt)[MLD], const float (&x)[16], int r, int h, f32x16& acc) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const h16x4 a0 = *reinterpret_cast<const h16x4*>(&Tt[r][16 * s + 4 * h]);
-    const h16x4 a1 = *reinterpret_cast<const h16x4*>(&Tt[r][16 * s + 8 + 4 * h]);
-    const h16x8 a = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-    const h16x8 b = {(_Float16)x[8 * s], (_Float16)x[8 * s + 1], (_Float16)x[8 * s + 2], (_Float16)x[8 * s + 3],
-                     (_Float16)x[8 * s + 4], (_Float16)x[8 * s + 5], (_Float16)x[8 * s + 6], (_Float16)x[8 * s + 7]};
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
+    const h16x4<E> a0 = *reinterpret_cast<const h16x4<E>*>(&Tt[r][16 * s + 4 * h]);
+    const h16x4<E> a1 = *reinterpret_cast<const h16x4<E>*>(&Tt[r][16 * s + 8 + 4 * h]);
+    const h16x8<E> a = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+    const h16x8<E> b = {(E)x[8 * s], (E)x[8 * s + 1], (E)x[8 * s + 2], (E)x[8 * s + 3],
+                        (E)x[8 * s + 4], (E)x[8 * s + 5], (E)x[8 * s + 6], (E)x[8 * s + 7]};
+    acc = Operand<E>::mfma(a, b, acc);
   }
 }
 
@@ -187,27 +190,27 @@ __device__ inline void mx_store_t(float* out, const f32x16& acc, int h, float sc
 // O = softmax(q k^T / sqrt(32)) v before the gate and lse, as attn_fwd_body: the scores of a key tile are S^T[key][query] (the
 // query on the lane), the running maximum and sum are per lane, and P^T -- relative to the running maximum, times the mask and
 // 1 / (1 - p) with DROP, rounded to fp16 -- is the B operand of O^T += V^T P^T.
-template <bool DROP>
+template <typename E, bool DROP>
 __device__ inline void mx_attn_fwd_body(const float* qkv, int T, int D, float* O, float* lse, const DropSite& ds) {
-  __shared__ __attribute__((aligned(16))) _Float16 Kr[XB][MLD];
-  __shared__ __attribute__((aligned(16))) _Float16 Vt[XB][MLD];
+  __shared__ __attribute__((aligned(16))) E Kr[XB][MLD];
+  __shared__ __attribute__((aligned(16))) E Vt[XB][MLD];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5, hd = blockIdx.y, b = blockIdx.z, H = D / 32;
   const int t = blockIdx.x * XB + r;
   const bool ok = t < T;
   const long ld = 3L * D;
   const float* base = qkv + (long)b * T * ld + hd * 32;
-  h16x8 qf[2];
-  mx_own_frag(base + (long)(ok ? t : 0) * ld, ok, h, qf);
+  h16x8<E> qf[2];
+  mx_own_frag<E>(base + (long)(ok ? t : 0) * ld, ok, h, qf);
   f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
   float mx = -INFINITY, l = 0.0f;   // (l: this lane's half of the keys; the halves meet at the end)
   for (int k0 = 0; k0 < T; k0 += XB) {
     __syncthreads();
-    mx_stage32(base + D, ld, k0, T, Kr, nullptr, lane);
-    mx_stage32(base + 2 * D, ld, k0, T, nullptr, Vt, lane);
+    mx_stage32<E>(base + D, ld, k0, T, Kr, nullptr, lane);
+    mx_stage32<E>(base + 2 * D, ld, k0, T, nullptr, Vt, lane);
     __syncthreads();
-    const f32x16 st = mx_first(Kr, qf, r, h);
+    const f32x16 st = mx_first<E>(Kr, qf, r, h);
     float sc[16], tm = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -233,7 +236,7 @@ __device__ inline void mx_attn_fwd_body(const float* qkv, int T, int D, float* O
         sc[4 * gq + jj] = DROP ? (w.w[jj] >= ds.thr ? p * ds.scale : 0.0f) : p;
       }
     }
-    mx_second(Vt, sc, r, h, acc);
+    mx_second<E>(Vt, sc, r, h, acc);
   }
   l += __shfl_xor(l, 32, 64);
   if (!ok) return;
@@ -242,40 +245,42 @@ __device__ inline void mx_attn_fwd_body(const float* qkv, int T, int D, float* O
   if (h == 0) lse[m * H + hd] = mx + log2f(l);
 }
 
+template <typename E>
 __global__ __launch_bounds__(64) void mx_attn_fwd_kernel(const float* qkv, int T, int D, float* O, float* lse) {
-  mx_attn_fwd_body<false>(qkv, T, D, O, lse, DropSite{});
+  mx_attn_fwd_body<E, false>(qkv, T, D, O, lse, DropSite{});
 }
+template <typename E>
 __global__ __launch_bounds__(64) void mx_attn_fwd_drop_kernel(const float* qkv, int T, int D, float* O, float* lse, const DropSite ds) {
-  mx_attn_fwd_body<true>(qkv, T, D, O, lse, ds);
+  mx_attn_fwd_body<E, true>(qkv, T, D, O, lse, ds);
 }
 
 // dq of XB queries: key tiles in ascending order.  S^T and dP^T = V dO^T have the query on the lane; dS^T = P^T (dP^T - delta)
 // in fp32, rounded, is the B operand of dQ^T += K^T dS^T.
-template <bool DROP>
+template <typename E, bool DROP>
 __device__ inline void mx_attn_dq_body(const float* qkv, const float* dO, const float* lse, const float* delta, int T, int D,
                                        float* dqkv, const DropSite& ds) {
-  __shared__ __attribute__((aligned(16))) _Float16 Kr[XB][MLD];
-  __shared__ __attribute__((aligned(16))) _Float16 Kt[XB][MLD];
-  __shared__ __attribute__((aligned(16))) _Float16 Vr[XB][MLD];
+  __shared__ __attribute__((aligned(16))) E Kr[XB][MLD];
+  __shared__ __attribute__((aligned(16))) E Kt[XB][MLD];
+  __shared__ __attribute__((aligned(16))) E Vr[XB][MLD];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5, hd = blockIdx.y, b = blockIdx.z, H = D / 32;
   const int t = blockIdx.x * XB + r;
   const bool ok = t < T;
   const long ld = 3L * D, m = (long)b * T + (ok ? t : 0);
   const float* base = qkv + (long)b * T * ld + hd * 32;
-  h16x8 qf[2], gf[2];
-  mx_own_frag(base + (long)(ok ? t : 0) * ld, ok, h, qf);
-  mx_own_frag(dO + m * D + hd * 32, ok, h, gf);
+  h16x8<E> qf[2], gf[2];
+  mx_own_frag<E>(base + (long)(ok ? t : 0) * ld, ok, h, qf);
+  mx_own_frag<E>(dO + m * D + hd * 32, ok, h, gf);
   const float ls = ok ? lse[m * H + hd] : 0.0f, dl = ok ? delta[m * H + hd] : 0.0f;
   f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
   for (int k0 = 0; k0 < T; k0 += XB) {
     __syncthreads();
-    mx_stage32(base + D, ld, k0, T, Kr, Kt, lane);
-    mx_stage32(base + 2 * D, ld, k0, T, Vr, nullptr, lane);
+    mx_stage32<E>(base + D, ld, k0, T, Kr, Kt, lane);
+    mx_stage32<E>(base + 2 * D, ld, k0, T, Vr, nullptr, lane);
     __syncthreads();
-    const f32x16 st = mx_first(Kr, qf, r, h);
-    const f32x16 dp = mx_first(Vr, gf, r, h);
+    const f32x16 st = mx_first<E>(Kr, qf, r, h);
+    const f32x16 dp = mx_first<E>(Vr, gf, r, h);
     float dst[16];
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
@@ -290,30 +295,32 @@ __device__ inline void mx_attn_dq_body(const float* qkv, const float* dO, const 
         dst[i] = p * (d - dl);
       }
     }
-    mx_second(Kt, dst, r, h, acc);
+    mx_second<E>(Kt, dst, r, h, acc);
   }
   if (ok) mx_store_t(dqkv + ((long)b * T + t) * ld + hd * 32, acc, h, QK_SCALE);
 }
 
+template <typename E>
 __global__ __launch_bounds__(64) void mx_attn_dq_kernel(const float* qkv, const float* dO, const float* lse, const float* delta, int T,
                                                         int D, float* dqkv) {
-  mx_attn_dq_body<false>(qkv, dO, lse, delta, T, D, dqkv, DropSite{});
+  mx_attn_dq_body<E, false>(qkv, dO, lse, delta, T, D, dqkv, DropSite{});
 }
+template <typename E>
 __global__ __launch_bounds__(64) void mx_attn_dq_drop_kernel(const float* qkv, const float* dO, const float* lse, const float* delta,
                                                              int T, int D, float* dqkv, const DropSite ds) {
-  mx_attn_dq_body<true>(qkv, dO, lse, delta, T, D, dqkv, ds);
+  mx_attn_dq_body<E, true>(qkv, dO, lse, delta, T, D, dqkv, ds);
 }
 
 // dk and dv of XB keys: query tiles in ascending order.  S and dP = dO V^T have the key on the lane and the queries in the
 // registers; P (masked and scaled with DROP) and dS, rounded, are the B operands of dV^T += dO^T P and dK^T += Q^T dS.  The four
 // keys of a quad of lanes are one mask group of every query: the lanes evaluate four queries' groups and exchange the words.
-template <bool DROP>
+template <typename E, bool DROP>
 __device__ inline void mx_attn_dkv_body(const float* qkv, const float* dO, const float* lse, const float* delta, int T, int D,
                                         float* dqkv, const DropSite& ds) {
-  __shared__ __attribute__((aligned(16))) _Float16 Qr[XB][MLD];
-  __shared__ __attribute__((aligned(16))) _Float16 Qt[XB][MLD];
-  __shared__ __attribute__((aligned(16))) _Float16 Gr[XB][MLD];
-  __shared__ __attribute__((aligned(16))) _Float16 Gt[XB][MLD];
+  __shared__ __attribute__((aligned(16))) E Qr[XB][MLD];
+  __shared__ __attribute__((aligned(16))) E Qt[XB][MLD];
+  __shared__ __attribute__((aligned(16))) E Gr[XB][MLD];
+  __shared__ __attribute__((aligned(16))) E Gt[XB][MLD];
   __shared__ float Ls[XB], Ds[XB];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5, hd = blockIdx.y, b = blockIdx.z, H = D / 32;
   const int t = blockIdx.x * XB + r;
@@ -321,16 +328,16 @@ __device__ inline void mx_attn_dkv_body(const float* qkv, const float* dO, const
   const long ld = 3L * D;
   const float* base = qkv + (long)b * T * ld + hd * 32;
   const float* gbase = dO + (long)b * T * D + hd * 32;
-  h16x8 kf[2], vf[2];
-  mx_own_frag(base + D + (long)(ok ? t : 0) * ld, ok, h, kf);
-  mx_own_frag(base + 2 * D + (long)(ok ? t : 0) * ld, ok, h, vf);
+  h16x8<E> kf[2], vf[2];
+  mx_own_frag<E>(base + D + (long)(ok ? t : 0) * ld, ok, h, kf);
+  mx_own_frag<E>(base + 2 * D + (long)(ok ? t : 0) * ld, ok, h, vf);
   f32x16 dk, dv;
 #pragma unroll
   for (int i = 0; i < 16; ++i) dk[i] = dv[i] = 0.0f;
   for (int q0 = 0; q0 < T; q0 += XB) {
     __syncthreads();
-    mx_stage32(base, ld, q0, T, Qr, Qt, lane);
-    mx_stage32(gbase, D, q0, T, Gr, Gt, lane);
+    mx_stage32<E>(base, ld, q0, T, Qr, Qt, lane);
+    mx_stage32<E>(gbase, D, q0, T, Gr, Gt, lane);
     if (lane < XB) {
       const int tq = q0 + lane;
       const long mq = (long)b * T + tq;
@@ -338,8 +345,8 @@ __device__ inline void mx_attn_dkv_body(const float* qkv, const float* dO, const
       Ds[lane] = tq < T ? delta[mq * H + hd] : 0.0f;
     }
     __syncthreads();
-    const f32x16 st = mx_first(Qr, kf, r, h);
-    const f32x16 dp = mx_first(Gr, vf, r, h);
+    const f32x16 st = mx_first<E>(Qr, kf, r, h);
+    const f32x16 dp = mx_first<E>(Gr, vf, r, h);
     float pm[16], dst[16];
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
@@ -360,8 +367,8 @@ __device__ inline void mx_attn_dkv_body(const float* qkv, const float* dO, const
         dst[i] = p * ((kept ? dp[i] * c : 0.0f) - Ds[row]);
       }
     }
-    mx_second(Gt, pm, r, h, dv);
-    mx_second(Qt, dst, r, h, dk);
+    mx_second<E>(Gt, pm, r, h, dv);
+    mx_second<E>(Qt, dst, r, h, dk);
   }
   if (!ok) return;
   float* out = dqkv + ((long)b * T + t) * ld + hd * 32;
@@ -369,13 +376,15 @@ __device__ inline void mx_attn_dkv_body(const float* qkv, const float* dO, const
   mx_store_t(out + 2 * D, dv, h, 1.0f);
 }
 
+template <typename E>
 __global__ __launch_bounds__(64) void mx_attn_dkv_kernel(const float* qkv, const float* dO, const float* lse, const float* delta, int T,
                                                          int D, float* dqkv) {
-  mx_attn_dkv_body<false>(qkv, dO, lse, delta, T, D, dqkv, DropSite{});
+  mx_attn_dkv_body<E, false>(qkv, dO, lse, delta, T, D, dqkv, DropSite{});
 }
+template <typename E>
 __global__ __launch_bounds__(64) void mx_attn_dkv_drop_kernel(const float* qkv, const float* dO, const float* lse, const float* delta,
                                                               int T, int D, float* dqkv, const DropSite ds) {
-  mx_attn_dkv_body<true>(qkv, dO, lse, delta, T, D, dqkv, ds);
+  mx_attn_dkv_body<E, true>(qkv, dO, lse, delta, T, D, dqkv, ds);
 }
 
 }  // namespace

@@ -28,7 +28,9 @@ from .settings import DIFFERENTIABLE, ENGINE, MODULES, REFUSE, TrainSettings, de
 
 _BUFFER_LEAVES = ("running_mean", "running_var", "num_batches_tracked")
 _PARTS = ("frontend", "transformer", "heads")   # of settings.decide, by stage; "frontend" / "transformer" are the keys of ``dropout``
-_SETTERS = {"batch_statistics": "set_batch_statistics()", "train_frontend": "set_frontend_trainable() first"}   # (names in a refusal)
+_SETTERS = {"batch_statistics": "set_batch_statistics()", "train_frontend": "set_frontend_trainable() first",   # (names in a refusal)
+            "train_operand": "operand='bf16'", "train_mixed": "set_train_precision('16-mixed')",
+            "frontend_operand": "operand='bf16'", "frontend_mixed": "set_frontend_precision('16-mixed')"}
 _TREE_EPOCH = [0]   # bumped whenever a module is assigned to / removed from a node of a BeatThis tree (_hooked_below's cache)
 
 
@@ -186,7 +188,9 @@ class BeatThis(_TracksChildren, nn.Module):
     as ever.  Which route a call takes is decided in one place (``_route``, over ``settings.decide``).
 
     Everything else about that route is an opt-in, held in ``self.train_settings``; ``settings.TrainSettings`` says what each means:
-      * ``set_train_precision("16-mixed")`` -> ``train_precision``: the reference's training precision in the trunk;
+      * ``set_train_precision("16-mixed")`` -> ``train_precision``: the reference's training precision in the trunk; with
+        ``operand="bf16"`` -> ``train_operand``: its products on bfloat16 operands, which need no loss scale (likewise
+        ``set_frontend_precision`` -> ``frontend_operand``);
       * ``set_frontend_trainable()`` -> ``frontend_trainable``: whole-model fine-tuning; ``False`` restores the frozen state and
         drops the engine's packed copies, so the frozen frontend runs on the weights as trained;
       * ``set_frontend_precision("16-mixed")`` -> ``frontend_precision``: fp16 matrix products in that frontend;
@@ -341,13 +345,25 @@ class BeatThis(_TracksChildren, nn.Module):
         """The opt-in to training-mode BatchNorm in the differentiable frontend; ``RuntimeError`` on a frozen frontend"""
         return self._set(RuntimeError, batch_statistics=bool(flag))
 
-    def set_train_precision(self, precision: str) -> "BeatThis":
-        """"16-mixed" or "32-true" (the default) for the trunk's units on the differentiable route"""
-        return self._set(train_precision=precision)
+    def _operand_for(self, which: str, precision: str, operand) -> str:
+        """The operand format a precision setter leaves: the one asked for; with None the present one while the part stays
+        "16-mixed", else the default "fp16" again"""
+        s = self.train_settings
+        if operand is not None:
+            return operand
+        stays = precision == "16-mixed" and getattr(s, which + "_precision") == "16-mixed"
+        return getattr(s, which + "_operand") if stays else "fp16"
 
-    def set_frontend_precision(self, precision: str) -> "BeatThis":
-        """"16-mixed" or "32-true" (the default) for the differentiable frontend, independent of ``set_train_precision``"""
-        return self._set(frontend_precision=precision)
+    def set_train_precision(self, precision: str, operand: str = None) -> "BeatThis":
+        """"16-mixed" or "32-true" (the default) for the trunk's units on the differentiable route.  ``operand``: "fp16" or "bf16",
+        the format the 16-mixed products round their operands to (``train_operand``); None keeps it while the precision stays
+        "16-mixed" and otherwise resets it to "fp16"; "bf16" with "32-true" is a ``ValueError``"""
+        return self._set(train_precision=precision, train_operand=self._operand_for("train", precision, operand))
+
+    def set_frontend_precision(self, precision: str, operand: str = None) -> "BeatThis":
+        """"16-mixed" or "32-true" (the default) for the differentiable frontend, independent of ``set_train_precision``;
+        ``operand`` as there (``frontend_operand``)"""
+        return self._set(frontend_precision=precision, frontend_operand=self._operand_for("frontend", precision, operand))
 
     def enable_dropout(self, seed: int = 0, frontend: bool = False) -> "BeatThis":
         """Opt in to dropout at ``dropout["transformer"]`` under ``seed``, the call counter at 0; ``frontend=True``: a second opt-in,
@@ -373,6 +389,8 @@ class BeatThis(_TracksChildren, nn.Module):
 
     train_precision = property(lambda self: self.train_settings.train_precision)
     frontend_precision = property(lambda self: self.train_settings.frontend_precision)
+    train_operand = property(lambda self: self.train_settings.train_operand)
+    frontend_operand = property(lambda self: self.train_settings.frontend_operand)
     frontend_trainable = property(lambda self: self.train_settings.frontend_trainable)
     batch_statistics = property(lambda self: self.train_settings.batch_statistics)
     frontend_dropout = property(lambda self: self.train_settings.dropout_rng is not None and self.train_settings.frontend_dropout,
@@ -437,7 +455,7 @@ class BeatThis(_TracksChildren, nn.Module):
             return _bw.empty_with_graph((x.shape[0], x.shape[1], self.hparams["transformer_dim"]), x, _params_of(self.frontend))
         # the leaves' dropout: asked once per leaf call, in forward order (None where nothing drops)
         drops = (lambda: self._next_dropout("frontend", True)) if route.drop else None
-        h = _bw.frontend_train(self, x.to(torch.float32), route.batch_statistics, route.mixed, drops)
+        h = _bw.frontend_train(self, x.to(torch.float32), route.batch_statistics, route.mixed_operand, drops)
         if route.batch_statistics:   # noted AFTER the call: an engine that ``_rope`` packed half way through it is stale as well
             self.train_settings.stats_moved = True
         return h
@@ -447,9 +465,9 @@ class BeatThis(_TracksChildren, nn.Module):
             return _bw.empty_with_graph(x.shape, x, _params_of(node))
         x = x.to(torch.float32)
         if kind == "attn":
-            return _bw.attention(node, x, *self._rope(x.shape[1]), self._next_dropout("transformer", route.drop), route.mixed)
+            return _bw.attention(node, x, *self._rope(x.shape[1]), self._next_dropout("transformer", route.drop), route.mixed_operand)
         if kind == "ff":
-            return _bw.feedforward(node, x, self._next_dropout("transformer", route.drop), route.mixed)
+            return _bw.feedforward(node, x, self._next_dropout("transformer", route.drop), route.mixed_operand)
         return _bw.final_norm(node, x)
 
     def _head_train(self, x: torch.Tensor) -> dict:

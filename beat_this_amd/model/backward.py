@@ -11,7 +11,7 @@ also under ``torch.autocast``.  Gradients are overwritten by the library and han
 Dropout and 16-mixed (DESIGN.md sections 15, 16): the attention and the feed-forward take ``drop`` = None (the calls and launches
 of a model without dropout) or ``(p, seed, stream)``, which goes from ``ctx`` unchanged to the backward -- the kernels recompute
 the masks from those three numbers, nothing is stored -- and ``mixed``: both operands of every matrix product rounded to fp16,
-fp32 accumulation, everything else fp32.  ``_run`` picks the entry points for the two; ``BeatThis._route`` decides both per
+fp32 accumulation, everything else fp32 (True or "fp16"; "bf16" rounds them to bfloat16 instead, section 24: ``_operand``).  ``_run`` picks the entry points for the two; ``BeatThis._route`` decides both per
 call (``torch.autocast`` does not) and ``BeatThis`` hands out the streams.
 
 The frontend (the lower part of this file): ``StemFn``, ``ConvUnitFn``, ``SwapFn`` and ``ProjectionFn`` over
@@ -63,10 +63,20 @@ def _args(x: torch.Tensor, hidden: int = 0, rope=None, rope_len: int = 0) -> _li
 _FAMILY = {(False, True): "", (False, False): "_dropout", (True, True): "_mixed", (True, False): "_mixed"}
 
 
-def _run(backward: bool, unit: int, a: _lib.TrainArgs, device, drop=None, mixed: bool = False) -> None:
+def _operand(mixed) -> int:
+    """BT_OPERAND_* of a ``mixed`` value: False (fp32: the field is not read), True or "fp16", or "bf16" (section 24)"""
+    if mixed is True or not mixed:
+        return _lib.OPERAND_F16
+    if mixed not in _lib.OPERANDS:
+        raise ValueError(f"mixed must be False, True, 'fp16' or 'bf16', got {mixed!r}")
+    return _lib.OPERANDS[mixed]
+
+
+def _run(backward: bool, unit: int, a: _lib.TrainArgs, device, drop=None, mixed=False) -> None:
     """One call of a unit of the trunk -- attention, feed-forward, final norm, head -- with its workspace; ``drop``: None or
-    (p, seed, stream); ``mixed``: 16-mixed (the attention and the feed-forward alone take either)"""
+    (p, seed, stream); ``mixed``: 16-mixed (the attention and the feed-forward alone take either), True or the operand format"""
     lib, family = _lib.lib(), _FAMILY[bool(mixed), drop is None]
+    a.operand = _operand(mixed)
     extra = (int(drop is not None),) if mixed else ()
     need = getattr(lib, "bt_train_workspace_bytes" + family)(unit, int(backward), a.B, a.T, a.dim, a.hidden, *extra)
     if need == 0:
@@ -103,7 +113,7 @@ class AttentionFn(torch.autograd.Function):
         a.y, a.save_o, a.save_lse = y.data_ptr(), o.data_ptr(), lse.data_ptr()
         _run(False, _lib.UNIT_ATTN, a, xf.device, drop, mixed)
         ctx.save_for_backward(xf, o, lse, rope, *ps)
-        ctx.rope_len, ctx.drop, ctx.mixed, ctx.residual = rope_len, drop, bool(mixed), int(bool(residual))
+        ctx.rope_len, ctx.drop, ctx.mixed, ctx.residual = rope_len, drop, mixed, int(bool(residual))
         return y
 
     @staticmethod
@@ -138,7 +148,7 @@ class FeedForwardFn(torch.autograd.Function):
         a.y = y.data_ptr()
         _run(False, _lib.UNIT_FF, a, xf.device, drop, mixed)
         ctx.save_for_backward(xf, *ps)
-        ctx.drop, ctx.mixed, ctx.residual = drop, bool(mixed), int(bool(residual))
+        ctx.drop, ctx.mixed, ctx.residual = drop, mixed, int(bool(residual))
         return y
 
     @staticmethod
@@ -272,8 +282,8 @@ def _front_args(B, T, F, Cc, dim=0, mixed=False, batch=False):
     """The argument struct of bt_front_forward / _backward or, with ``batch`` (the stem and the conv unit on
     the statistics of the call's batch), of bt_front_bn_forward / _backward, which has no ``dim``"""
     if batch:
-        return _lib.FrontBnArgs(B=int(B), T=int(T), F=int(F), C=int(Cc), mixed=int(bool(mixed)))
-    return _lib.FrontArgs(B=int(B), T=int(T), F=int(F), C=int(Cc), dim=int(dim), mixed=int(bool(mixed)))
+        return _lib.FrontBnArgs(B=int(B), T=int(T), F=int(F), C=int(Cc), mixed=int(bool(mixed)), operand=_operand(mixed))
+    return _lib.FrontArgs(B=int(B), T=int(T), F=int(F), C=int(Cc), dim=int(dim), mixed=int(bool(mixed)), operand=_operand(mixed))
 
 
 def _front_call(backward: bool, unit: int, a, device) -> None:
@@ -403,7 +413,7 @@ class ConvUnitFn(torch.autograd.Function):
         _on_device_of(xf, *ps)
         y, pre = _conv_forward(ConvUnitFn._args(xf, *ps, mixed), xf, ps[0])
         ctx.save_for_backward(xf, pre, *ps)
-        ctx.mixed = bool(mixed)
+        ctx.mixed = mixed
         return y
 
     @staticmethod
@@ -472,7 +482,7 @@ class ConvUnitBatchFn(torch.autograd.Function):
         a.bn_mean, a.bn_var, a.bn_tracked = _running(nm, nv, nn_, Cout)
         y, pre = _conv_forward(a, xf, ps[0])
         ctx.save_for_backward(xf, pre, *ps, *stats)
-        ctx.mixed = bool(mixed)
+        ctx.mixed = mixed
         return y
 
     @staticmethod
@@ -527,7 +537,7 @@ class ProjectionFn(torch.autograd.Function):
         a.x, a.y, a.w, a.b = xf.data_ptr(), y.data_ptr(), wf.data_ptr(), bf.data_ptr()
         _front_call(False, _lib.FRONT_LINEAR, a, xf.device)
         ctx.save_for_backward(xf, wf, bf)
-        ctx.mixed = bool(mixed)
+        ctx.mixed = mixed
         return y
 
     @staticmethod
@@ -597,11 +607,12 @@ def frontend_train(model, x, batch_statistics=False, mixed=None, drops=None):
     """``BeatThis.frontend`` on the differentiable route, in the reference's order (beat_tracker.py:54-80, 290-301): stem, three
     times (partial transformer, conv unit), projection.  (B, T, 128) -> (B, T, D).  ``batch_statistics``: the five BatchNorms
     normalise with this call's batch and move their running buffers (section 18).  ``mixed``: the conv units, the leaves and the
-    projection on fp16 operands (section 19); None reads ``model.frontend_precision``.  The stem is fp32 either way.  ``drops``:
+    projection on fp16 operands (section 19), or with "bf16" on bfloat16 ones (section 24); None reads ``model.frontend_precision``
+    and ``model.frontend_operand``.  The stem is fp32 either way.  ``drops``:
     None, or a callable that yields the ``drop`` of the next leaf call (section 21: ``BeatThis`` hands out the streams in forward
     order); the stem, the conv units and the projection never drop."""
     if mixed is None:
-        mixed = model.frontend_precision == "16-mixed"
+        mixed = model.frontend_precision == "16-mixed" and model.frontend_operand
     fr = model.frontend
     check_front_limits(int(x.shape[0]), int(x.shape[1]))
     if batch_statistics:

@@ -49,7 +49,9 @@ class PLBeatThis(nn.Module):
     ``batch_statistics`` (``set_batch_statistics``: what training from scratch needs) and ``frontend_precision`` ("16-mixed" or
     "32-true"; None leaves the model's default, "32-true"; ``set_frontend_precision``); ``precision`` ("32-true", the default, or
     "16-mixed", the reference's trainer setting: ``set_train_precision``, and ``fit`` then scales the loss with an
-    ``optim.LossScaler``); ``apply_dropout`` (``enable_dropout`` under ``dropout_seed``: the main layers drop at
+    ``optim.LossScaler``); ``mixed_operand`` / ``frontend_mixed_operand`` ("fp16", "bf16" or None = "fp16": the ``operand`` of those
+    two setters -- the format a 16-mixed part rounds its products' operands to; "bf16" needs no loss scale and is a ``ValueError``
+    on a part that is not "16-mixed"); ``apply_dropout`` (``enable_dropout`` under ``dropout_seed``: the main layers drop at
     ``dropout["transformer"]`` like the reference's, with this package's own masks) and on top of it and of ``train_frontend``
     (``ValueError`` without either) ``apply_frontend_dropout`` (``enable_dropout(frontend=True)``: the frontend's leaves drop at
     ``dropout["frontend"]`` too, the reference's full recipe; without it that rate stays unused).  With dropout or batch
@@ -63,10 +65,12 @@ class PLBeatThis(nn.Module):
                  pos_weights={"beat": 1, "downbeat": 1}, head_dim=32, loss_type="shift_tolerant_weighted_bce",
                  warmup_steps=1000, max_epochs=100, use_dbn=False, eval_trim_beats=5, sum_head=True, partial_transformers=True,
                  apply_dropout=False, dropout_seed=0, precision="32-true", train_frontend=False,
-                 batch_statistics=False, frontend_precision=None, apply_frontend_dropout=False, init_seed=0):
+                 batch_statistics=False, frontend_precision=None, apply_frontend_dropout=False, init_seed=0,
+                 mixed_operand=None, frontend_mixed_operand=None):
         given = {k: v for k, v in locals().items()
                  if k not in ("self", "__class__", "apply_dropout", "dropout_seed", "precision", "train_frontend",
-                              "batch_statistics", "frontend_precision", "apply_frontend_dropout", "init_seed")}
+                              "batch_statistics", "frontend_precision", "apply_frontend_dropout", "init_seed", "mixed_operand",
+                              "frontend_mixed_operand")}
         # what is asked for, checked as a recipe before anything is built (batch statistics: the model's own refusal, below)
         want =TrainSettings().changed(
             "recipe", ValueError, _SWITCHES, only="frontend_dropout", train_precision=precision,
@@ -81,9 +85,10 @@ class PLBeatThis(nn.Module):
             self.model.init_weights(init_seed)
         if want.dropout_rng is not None:   # (applied in this order: init_weights and the requires_grad loop sit in between)
             self.model.enable_dropout(seed=dropout_seed, frontend=want.frontend_dropout)
-        self.model.set_train_precision(want.train_precision)
-        if frontend_precision is not None:   # BeatThis.set_frontend_precision; no hyper-parameter, like precision
-            self.model.set_frontend_precision(frontend_precision)
+        self.model.set_train_precision(want.train_precision, mixed_operand)
+        if frontend_precision is not None or frontend_mixed_operand is not None:   # BeatThis.set_frontend_precision; no hyper-parameter, like precision
+            self.model.set_frontend_precision(self.model.frontend_precision if frontend_precision is None else frontend_precision,
+                                              frontend_mixed_operand)
         # trainable: the trunk and the heads, without the rotary tables (fixed in the reference too); frozen: the frontend
         for name, p in self.model.named_parameters():
             p.requires_grad_(not name.startswith("frontend.") and not name.endswith("rotary_embed.freqs"))

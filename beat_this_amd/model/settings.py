@@ -10,7 +10,8 @@ from typing import NamedTuple, Optional
 
 class Violation(NamedTuple):
     """The switch ``what`` needs the switch ``needs`` because of ``why``, or (``needs`` None) a value is out of range and ``why``
-    says it all.  The switches: "batch_statistics", "frontend_precision", "frontend_dropout", "dropout", "train_frontend"."""
+    says it all.  The switches: "batch_statistics", "frontend_precision", "frontend_dropout", "dropout", "train_frontend",
+    "train_operand", "frontend_operand" and, as what those need, "train_mixed", "frontend_mixed" (the part on "16-mixed")."""
     what: str
     needs: Optional[str]
     why: str
@@ -39,6 +40,11 @@ class TrainSettings:
 
     ``frontend_precision`` (``set_frontend_precision``, section 19): the same two values, independent of ``train_precision``, for
     the matrix products of the differentiable frontend's conv units, twelve partial-transformer leaves and projection, not its stem.
+
+    ``train_operand`` / ``frontend_operand`` (the ``operand`` argument of the two setters above, section 24): the 16-bit format both
+    operands of a 16-mixed part's products are rounded to, "fp16" (the default: the reference's ``16-mixed``) or "bf16" (what
+    Lightning calls ``bf16-mixed``: fp32's exponent range, so nothing overflows by rounding and no loss scale is needed).  Read
+    only where the part's precision is "16-mixed"; "bf16" beside "32-true" is refused.
 
     ``batch_statistics`` (``set_batch_statistics``, section 18): training from scratch; needs ``frontend_trainable``.  Without
     it the frontend's BatchNorms use ``running_mean`` / ``running_var``, in ``train()`` as in ``eval()``, and never update them.
@@ -70,6 +76,13 @@ class TrainSettings:
     dropout_rng: Optional[dict] = None
     frontend_dropout: bool = False
     stats_moved: bool = False
+    train_operand: str = "fp16"
+    frontend_operand: str = "fp16"
+
+    def needs_loss_scale(self) -> bool:
+        """Some part is 16-mixed with fp16 operands: its gradients can overflow, so the recipe scales the loss (section 24)"""
+        return any(precision == "16-mixed" and operand == "fp16" for precision, operand in
+                   ((self.train_precision, self.train_operand), (self.frontend_precision, self.frontend_operand)))
 
     @classmethod
     def from_loose_attributes(cls, state: dict) -> "TrainSettings":
@@ -85,6 +98,7 @@ class TrainSettings:
         if self.batch_statistics and not self.frontend_trainable:
             found.append(Violation("batch_statistics", "train_frontend", "batch statistics belong to the differentiable frontend"))
         if level == "recipe":
+            found += self._operand_violations()
             if self.frontend_precision != "32-true" and not self.frontend_trainable:   # (the command line alone insists on it)
                 found.append(Violation("frontend_precision", "train_frontend", "it belongs to the differentiable frontend"))
             if self.frontend_dropout and self.dropout_rng is None:
@@ -95,12 +109,25 @@ class TrainSettings:
         for which, value in (("train", self.train_precision), ("frontend", self.frontend_precision)):
             if value not in ("16-mixed", "32-true"):
                 found.append(Violation(which + "_precision", None, f"{which} precision must be '16-mixed' or '32-true', got {value!r}"))
+        found += self._operand_violations()
         for part, p in rates.items():
             if (part != "frontend" or self.frontend_dropout) and not 0.0 <= float(p) < 1.0:   # (NaN fails both comparisons)
                 found.append(Violation("dropout", None, f"dropout[{part!r}] = {float(p)}: the rate must satisfy 0 <= p < 1"))
         rng = self.dropout_rng or {"seed": 0, "calls": 0}
         if not (0 <= rng["seed"] < 1 << 64 and 0 <= rng["calls"] < 1 << 64):
             found.append(Violation("dropout", None, f"dropout seed and calls must fit 64 unsigned bits, got {rng['seed']} and {rng['calls']}"))
+        return found
+
+    def _operand_violations(self) -> list:
+        """An operand format nobody knows, or "bf16" on a part that is not 16-mixed (the same at both levels)"""
+        found = []
+        for which in ("train", "frontend"):
+            operand, precision = getattr(self, which + "_operand"), getattr(self, which + "_precision")
+            if operand not in ("fp16", "bf16"):
+                found.append(Violation(which + "_operand", None, f"{which} operand must be 'fp16' or 'bf16', got {operand!r}"))
+            elif operand == "bf16" and precision != "16-mixed":
+                found.append(Violation(which + "_operand", which + "_mixed",
+                                       "bf16 is the operand format of 16-mixed products; a 32-true part rounds nothing"))
         return found
 
     def changed(self, level: str, error: type, names: dict, rates: dict = {}, only: str = None, **fields) -> "TrainSettings":
@@ -120,11 +147,18 @@ DIFFERENTIABLE, ENGINE, MODULES, REFUSE = "differentiable", "engine", "modules",
 class Route(NamedTuple):
     """``how``: DIFFERENTIABLE (backward.py), ENGINE (the inference path), MODULES (that path through the sub-modules, so that a
     hook below fires) or REFUSE (a frozen frontend was asked for gradients).  The rest is False unless ``how`` is DIFFERENTIABLE:
-    the frontend's BatchNorms use this call's batch; this part's calls draw dropout masks; its unit calls are 16-mixed."""
+    the frontend's BatchNorms use this call's batch; this part's calls draw dropout masks; its unit calls are 16-mixed;
+    ``operand``: "fp16" unless they are 16-mixed on "bf16" operands."""
     how: str
     batch_statistics: bool = False
     drop: bool = False
     mixed: bool = False
+    operand: str = "fp16"
+
+    @property
+    def mixed_operand(self):
+        """What backward.py takes as ``mixed``: False, or the operand format of the 16-mixed calls"""
+        return self.operand if self.mixed else False
 
 
 _PLAIN = {how: Route(how) for how in (ENGINE, MODULES, REFUSE)}   # (built once: the inference path builds nothing per call)
@@ -144,8 +178,9 @@ def decide(s: TrainSettings, part: str, grad: bool, training: bool = False, x_gr
         if part == "heads":
             return Route(DIFFERENTIABLE)
         drop = s.dropout_rng is not None and training and rate > 0.0 and (s.frontend_dropout or not frontend)
-        return Route(DIFFERENTIABLE, frontend and s.batch_statistics and training, drop,
-                     (s.frontend_precision if frontend else s.train_precision) == "16-mixed")
+        mixed = (s.frontend_precision if frontend else s.train_precision) == "16-mixed"
+        return Route(DIFFERENTIABLE, frontend and s.batch_statistics and training, drop, mixed,
+                     (s.frontend_operand if frontend else s.train_operand) if mixed else "fp16")
     if grad and frontend and param_grad:
         return _PLAIN[REFUSE]
     return _PLAIN[MODULES if hooked and part != "heads" else ENGINE]

@@ -3,14 +3,15 @@
 up in launch_scripts/train.py:118-131 -- epochs over the training loader, gradient accumulation, one optimiser and scheduler
 step per accumulated batch group, validation with the package's own metrics every few epochs, one checkpoint per epoch -- and
 ``python -m beat_this_amd.train`` is the command line around it.  Every step's arithmetic runs in the package's kernels: the
-differentiable route of ``BeatThis`` (fp32 or, with ``precision="16-mixed"``, fp16 matrix products under a dynamic loss scale;
+differentiable route of ``BeatThis`` (fp32 or, with ``precision="16-mixed"``, fp16 matrix products under a dynamic loss scale, or
+with ``mixed_operand="bf16"`` bfloat16 ones, which need none;
 frozen frontend or, with ``train_frontend``, the whole model, its frontend in fp32 or with ``frontend_precision="16-mixed"`` on
 fp16 products too; dropout in the main layers when enabled and, with ``frontend_dropout``, in the leaves of the frontend's
 partial transformers as well), the losses, and the fused AdamW of ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
 and ``load_model`` read as it is.
 
 Not offered: the reference's wandb logger, ``--compile`` and ``--force-flash-attention`` (nothing here is compiled by torch or
-runs torch's attention), bf16 mixed precision, and the test run after training (``beat_this_amd.evaluate`` scores a checkpoint).
+runs torch's attention), and the test run after training (``beat_this_amd.evaluate`` scores a checkpoint).
 """
 from __future__ import annotations
 
@@ -37,7 +38,9 @@ CHECKPOINT_KEYS = ("state_dict", "hyper_parameters", "optimizer_states", "lr_sch
 _FIT_NAMES = {"frontend_dropout": "frontend_dropout=True", "train_frontend": "a trainable frontend (train_frontend=True)",
               "dropout": "dropout enabled (PLBeatThis(apply_dropout=True) or model.enable_dropout())"}
 _FLAGS = {"batch_statistics": "--batch-statistics", "frontend_precision": "--frontend-precision", "dropout": "--dropout",
-          "frontend_dropout": "--apply-frontend-dropout", "train_frontend": "--train-frontend"}
+          "frontend_dropout": "--apply-frontend-dropout", "train_frontend": "--train-frontend", "train_operand": "--mixed-operand",
+          "train_mixed": "--precision 16-mixed", "frontend_operand": "--frontend-mixed-operand",
+          "frontend_mixed": "--frontend-precision 16-mixed"}
 
 
 def _rng_state() -> dict:
@@ -112,7 +115,7 @@ def validate(pl_module, datamodule) -> dict:
 
 def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
         resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None, frontend_precision=None,
-        frontend_dropout=None, ema_decay=None) -> dict:
+        frontend_dropout=None, ema_decay=None, mixed_operand=None, frontend_mixed_operand=None) -> dict:
     """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
 
     Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
@@ -130,6 +133,14 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     schedule steps with every optimiser call, skipped or not, as the reference's trainer does.  The losses reported are
     unscaled; the scaler's state goes into the checkpoint under ``loss_scaler`` and comes back with ``resume``.  Without
     16-mixed the calls are the ones of an fp32 run.
+
+    ``mixed_operand``, ``frontend_mixed_operand``: "fp16" or "bf16", the ``operand`` of ``set_train_precision`` /
+    ``set_frontend_precision``, set together with ``precision`` / ``frontend_precision`` (None with a
+    precision follows the setter's rule: kept while the part stays "16-mixed", else "fp16"; given alone it re-sets the part's
+    present precision with that operand; "bf16" on a part that is not "16-mixed" is a ``ValueError``).  bfloat16 operands
+    cannot overflow by rounding, so the ``LossScaler`` exists only if some part is 16-mixed on fp16 operands: a run whose mixed
+    parts are all bf16 makes the calls of an fp32 run -- no scaler, no scaled loss, no ``loss_scaler`` in the checkpoint, None in
+    the returned dictionary.  ``resume`` needs the same settings.
 
     ``train_frontend``, ``batch_statistics``, ``frontend_precision``, ``frontend_dropout``: the model's other settings
     (``model.settings.TrainSettings`` says what each means), applied in that order after ``precision`` and before the optimiser is
@@ -160,8 +171,13 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     from .optim import LossScaler
 
     model = pl_module.model
-    for value, setter in ((precision, model.set_train_precision), (train_frontend, model.set_frontend_trainable),
-                          (batch_statistics, model.set_batch_statistics), (frontend_precision, model.set_frontend_precision)):
+    if precision is None and mixed_operand is not None:
+        precision = model.train_precision
+    if frontend_precision is None and frontend_mixed_operand is not None:
+        frontend_precision = model.frontend_precision
+    for value, setter in ((precision, lambda v: model.set_train_precision(v, mixed_operand)),
+                          (train_frontend, model.set_frontend_trainable), (batch_statistics, model.set_batch_statistics),
+                          (frontend_precision, lambda v: model.set_frontend_precision(v, frontend_mixed_operand))):
         if value is not None:   # (None leaves the model as it is; in this order)
             setter(value)
     if frontend_dropout is not None:
@@ -169,7 +185,7 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
         state = model.dropout_state()
         if state is not None:
             model.set_dropout_state(dict(state, frontend=bool(frontend_dropout)))
-    scaler = LossScaler() if "16-mixed" in (model.train_precision, model.frontend_precision) else None
+    scaler = LossScaler() if model.train_settings.needs_loss_scale() else None   # (16-mixed on fp16 operands somewhere)
     accumulate = int(accumulate_grad_batches)
     if accumulate < 1 or int(max_epochs) < 0 or int(val_frequency) < 1:
         raise ValueError("accumulate_grad_batches and val_frequency must be at least 1, max_epochs at least 0")
@@ -287,12 +303,17 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", type=str, default="32-true", choices=["32-true", "16-mixed"],
                    help="16-mixed: the reference's training precision -- fp16 matrix products in the main layers, fp32 master "
                         "weights, a dynamic loss scale (default: %(default)s)")
+    p.add_argument("--mixed-operand", type=str, default=None, choices=["fp16", "bf16"],
+                   help="with --precision 16-mixed: the format its matrix products round their operands to; bf16 has fp32's "
+                        "exponent range and needs no loss scale (default: fp16)")
     p.add_argument("--train-frontend", default=False, action=toggle,
                    help="whole-model fine-tuning: also train the frontend (frozen BatchNorm statistics unless --batch-statistics, "
                         "no frontend dropout unless --apply-frontend-dropout, fp32 frontend unless --frontend-precision 16-mixed; default: the frontend stays frozen)")
     p.add_argument("--frontend-precision", type=str, default="32-true", choices=["32-true", "16-mixed"],
                    help="with --train-frontend: 16-mixed runs the matrix products of the frontend's conv units, partial "
                         "transformers and projection on fp16 operands too, under the same loss scale (default: %(default)s)")
+    p.add_argument("--frontend-mixed-operand", type=str, default=None, choices=["fp16", "bf16"],
+                   help="with --frontend-precision 16-mixed: the same choice for the frontend's products (default: fp16)")
     p.add_argument("--batch-statistics", default=False, action=toggle,
                    help="with --train-frontend: the frontend's BatchNorms use each batch's statistics and update their running "
                         "ones, as training from scratch needs (default: frozen running statistics)")
@@ -328,10 +349,17 @@ def main(argv=None) -> int:
     from .model.settings import TrainSettings
 
     asked = TrainSettings(frontend_trainable=args.train_frontend, batch_statistics=args.batch_statistics,
-                          frontend_precision=args.frontend_precision, dropout_rng={"seed": args.seed, "calls": 0} if args.dropout else None,
+                          train_precision=args.precision, train_operand=args.mixed_operand or "fp16",
+                          frontend_precision=args.frontend_precision, frontend_operand=args.frontend_mixed_operand or "fp16",
+                          dropout_rng={"seed": args.seed, "calls": 0} if args.dropout else None,
                           frontend_dropout=args.apply_frontend_dropout)
     for violation in asked.violations("recipe"):   # (before the data folder is touched)
         parser.error(violation.message(_FLAGS))
+    for flag, operand, part, precision in (("--mixed-operand", args.mixed_operand, "--precision", args.precision),
+                                           ("--frontend-mixed-operand", args.frontend_mixed_operand, "--frontend-precision",
+                                            args.frontend_precision)):
+        if operand is not None and precision != "16-mixed":   # (fp16 too: the flag says nothing about a 32-true part)
+            parser.error(f"{flag} needs {part} 16-mixed: it is the operand format of 16-mixed products")
 
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
@@ -363,6 +391,7 @@ def main(argv=None) -> int:
                            warmup_steps=args.warmup_steps, max_epochs=args.max_epochs, use_dbn=args.dbn,
                            eval_trim_beats=args.eval_trim_beats, precision=args.precision, train_frontend=args.train_frontend,
                            batch_statistics=args.batch_statistics, frontend_precision=args.frontend_precision,
+                           mixed_operand=args.mixed_operand, frontend_mixed_operand=args.frontend_mixed_operand,
                            apply_frontend_dropout=args.apply_frontend_dropout, init_seed=0 if ckpt is not None else args.init_seed)
     if ckpt is not None and not args.resume_checkpoint:   # (a resumed run's weights are restored by fit() with the rest)
         pl_module.load_state_dict(ckpt["state_dict"])

@@ -627,7 +627,8 @@ int bt_layer_tail(void* stream, const bt_pair_weights* w, int hidden, const void
 #define BT_TRAIN_CS_ROWS 64
 #define BT_TRAIN_ATTN_BLOCK 64
 typedef struct {
-  int32_t B, T, dim, hidden, rope_len, residual, sum_head, reserved;
+  int32_t B, T, dim, hidden, rope_len, residual, sum_head;
+  int32_t operand;   /* read by bt_train_forward_mixed / bt_train_backward_mixed alone: BT_OPERAND_* (below); ignored elsewhere */
   const float* rope;
   const float* gamma; const float* w1; const float* b1; const float* w2; const float* b2; const float* w3;
   const float* x; float* y; float* y2; float* save_o; float* save_lse;
@@ -716,17 +717,27 @@ int bt_dropout_mask_host(const bt_train_dropout* dropout, int site, int B, int T
  * batch; no launch reads workspace bytes that its own call has not written; no call synchronises, allocates or clears memory.
  * The dropout mask contract is unchanged.  Units other than BT_UNIT_ATTN and BT_UNIT_FF are BT_ERR_ARG (workspace query: 0):
  * the final norm and the head have no matrix product worth an MFMA and stay on the fp32 entries.  The workspace is that of the
- * fp32 route (with_dropout != 0: that of the dropout entries). */
+ * fp32 route (with_dropout != 0: that of the dropout entries).
+ * THE OPERAND FORMAT.  bt_train_args.operand -- the struct's former reserved int32, same offset -- picks the
+ * 16-bit format of that contract: BT_OPERAND_F16 (0) is everything above, launch for launch.  BT_OPERAND_BF16 (1) is the same
+ * contract with one word changed: both operands of every listed product are rounded to bfloat16, round to nearest even, as they
+ * are staged, and accumulate in fp32 on v_mfma_f32_32x32x16_bf16.  NaN stays NaN; no value overflows by rounding (the exponent
+ * range is fp32's), so this format needs no loss scale.  Staging, lane maps, summation orders, the mask mapping, the workspace
+ * and everything that is kept are those of fp16.  Any other value is BT_ERR_ARG before any launch ("operand" in bt_last_error()).
+ * The fp32 and dropout entry points above never read the field. */
+#define BT_OPERAND_F16 0
+#define BT_OPERAND_BF16 1
 size_t bt_train_workspace_bytes_mixed(int unit, int backward, int B, int T, int dim, int hidden, int with_dropout);
 int bt_train_forward_mixed(void* stream, int unit, const bt_train_args* a, const bt_train_dropout* dropout_or_null);
 int bt_train_backward_mixed(void* stream, int unit, const bt_train_args* a, const bt_train_dropout* dropout_or_null);
-/* DIAGNOSTIC: the raw GEMM of the mixed route, fp32 in and out, C [M, N] contiguous, 1 <= M, N, K <= 2^22:
+/* DIAGNOSTIC: the raw GEMM of the mixed route on fp16 operands, fp32 in and out, C [M, N] contiguous, 1 <= M, N, K <= 2^22:
  *   form 0: C = A B^T, A [M, K], B [N, K]   (Y = A W^T)
  *   form 1: C = A B,   A [M, K], B [K, N]   (dA = dY W)
  *   form 2: C = A^T B, A [K, M], B [K, N]   (dW = dY^T A; K = the summed rows, taken BT_TRAIN_DW_ROWS at a time and the chunks
  *                                            added into C in chunk order, one launch per chunk) */
 int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B, int M, int N, int K, float* C);
-/* The GEMM of either training route (mixed = 0: the fp32 MFMA kernels, 1: the fp16 ones) through the host helpers
+/* The GEMM of either training route (mixed = 0: the fp32 MFMA kernels, 1: the fp16 ones, 2: the same on bfloat16 operands -- 1 +
+ * BT_OPERAND_*; anything else is BT_ERR_ARG ahead of every other check) through the host helpers
  * the unit calls launch it with.  A diagnostic for the trunk's units, and PRODUCTION for the frontend's projection:
  * bt_front_forward / bt_front_backward (BT_FRONT_LINEAR) call forms 0, 1 and 2 with their own `mixed` and size their workspace with
  * bt_train_matmul_workspace_bytes, so what this entry computes, and in which order it sums, is part of section 17's contract.
@@ -748,7 +759,8 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
 /* DIAGNOSTIC: the attention sweeps of either route on their own, launched as the unit calls launch them (blocks of
  * BT_TRAIN_ATTN_BLOCK queries on the fp32 route, of 32 on the mixed one).  qkv [B T, 3 dim] is what the sweeps read after RoPE:
  * q | k | v, head h in columns 32 h of each section; dim a multiple of 32 from 32 to 1024, B <= 65535, B T <= 2^22; qkv, O, dO
- * and dqkv 16-byte aligned.  dropout (or NULL, or p == 0: none) is the BT_DROP_ATTN_P site.
+ * and dqkv 16-byte aligned.  dropout (or NULL, or p == 0: none) is the BT_DROP_ATTN_P site.  `mixed` as bt_train_matmul's: 0, 1
+ * (fp16 operands) or 2 (bfloat16 operands), anything else is BT_ERR_ARG ahead of every other check.
  *   backward == 0: writes O [B T, dim] (before the gate; the dropped output with dropout) and lse [B T, dim / 32]
  *   backward != 0: reads dO [B T, dim], lse and delta [B T, dim / 32] (= sum_d dO O per row and head), runs the dK / dV sweep and
  *                  the dQ sweep and writes every element of dqkv [B T, 3 dim], the gradient before the backward RoPE
@@ -791,7 +803,9 @@ int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int 
 #define BT_FRONT_LINEAR 2
 #define BT_FRONT_SWAP 3
 typedef struct {
-  int32_t B, T, F, C, dim, mixed, reserved1, reserved2;
+  int32_t B, T, F, C, dim, mixed;
+  int32_t operand;   /* read only when mixed == 1: BT_OPERAND_F16 or BT_OPERAND_BF16 (section 24) */
+  int32_t reserved2;
   const float* w; const float* b;
   const float* bn_w; const float* bn_b; const float* bn_mean; const float* bn_var;
   const float* bn1_w; const float* bn1_b; const float* bn1_mean; const float* bn1_var;
@@ -829,7 +843,9 @@ int bt_front_backward(void* stream, int unit, const bt_front_args* a);
  * n = 1 (torch: "Expected more than 1 value per channel when training") is BT_ERR_ARG before any launch, like every shape the
  * calls above refuse and every NULL among the required pointers; the workspace query then returns 0. */
 typedef struct {
-  int32_t B, T, F, C, mixed, reserved1, reserved2, reserved3;
+  int32_t B, T, F, C, mixed;
+  int32_t operand;   /* read only when mixed == 1: BT_OPERAND_F16 or BT_OPERAND_BF16 (section 24) */
+  int32_t reserved2, reserved3;
   const float* w;
   const float* bn_w; const float* bn_b; float* bn_mean; float* bn_var; int64_t* bn_tracked;
   const float* bn1_w; const float* bn1_b; float* bn1_mean; float* bn1_var; int64_t* bn1_tracked;
@@ -869,7 +885,13 @@ int bt_front_bn_backward(void* stream, int unit, const bt_front_bn_args* a);
  * mixed = 1 with BT_FRONT_STEM or BT_FRONT_SWAP (or BT_FRONT_LINEAR in bt_front_bn_args), and any value other than 0 and 1, is
  * BT_ERR_ARG before any launch.  mixed = 1 needs a 16-byte aligned workspace of the size the two queries below return (the
  * fp32 size plus the weight image); they take the parameters of the fp32 queries, whose values are unchanged, and return 0 for
- * unsupported shapes and for units that have no mixed form. */
+ * unsupported shapes and for units that have no mixed form.
+ * `operand`, the int32 behind `mixed` in both structs (their former reserved1, same offsets), is read only
+ * when mixed == 1 and checked together with it: BT_OPERAND_F16 is everything above; BT_OPERAND_BF16 rounds both operands of the
+ * same products to bfloat16 (to nearest even, NaN stays NaN, nothing overflows by rounding) on v_mfma_f32_32x32x16_bf16, the
+ * weight image holding bfloat16 in the same bytes, BT_FRONT_LINEAR calling bt_train_matmul with mixed = 2; any other value is
+ * BT_ERR_ARG before any launch ("operand" in bt_last_error()).  With mixed == 0 the field is ignored.  The workspace queries do
+ * not depend on it. */
 size_t bt_front_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C, int dim);
 size_t bt_front_bn_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C);
 
