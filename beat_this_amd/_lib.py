@@ -24,6 +24,7 @@ HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "t
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
 OPERAND_F16, OPERAND_BF16 = 0, 1   # BT_OPERAND_*: the operand format of a 16-mixed call (``operand`` of the three training structs)
 OPERANDS = {"fp16": OPERAND_F16, "bf16": OPERAND_BF16}
+OPERAND_BF16X3 = 3                 # BT_OPERAND_BF16X3: the split operands of a "32-high" call (no choice of a 16-mixed part: not in OPERANDS)
 ABI_VERSION = 600   # BT_ABI_VERSION of include/beat_this_amd.h this binding was written against
 PREC_F32, PREC_HALF, PREC_F32X3 = 0, 1, 3   # (2 was the withdrawn e4m3 experiment)
 OPT_X3_ATTN_P16, OPT_X3_GEMM_FP8, OPT_WS_GUARD = 1, 2, 3   # BT_OPT_* (bt_engine_set_option)
@@ -303,11 +304,13 @@ EXPORTS = {
     "bt_front_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "bt_front_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bt_front_workspace_bytes_mixed": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bt_front_workspace_bytes_x3": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bt_front_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontArgs)]),
     "bt_front_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontArgs)]),
     "bt_front_bn_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "bt_front_bn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bt_front_bn_workspace_bytes_mixed": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bt_front_bn_workspace_bytes_x3": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bt_front_bn_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontBnArgs)]),
     "bt_front_bn_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrontBnArgs)]),
     "bt_optim_struct_sizes": (None, [C.POINTER(C.c_int32)]),

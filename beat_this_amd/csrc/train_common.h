@@ -14,25 +14,86 @@ namespace {
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-// The operand element type of the 16-mixed kernels (DESIGN.md sections 16, 19 and 24), _Float16 or __bf16: its fragments of four
-// and eight and its 32x32x16 MFMA.  Lane maps and rates are the same for both; float -> E is the compiler's conversion (round to
-// nearest even; fp16 overflows to inf, bf16 has fp32's exponent range).
+// The operand format of the 16-mixed kernels (DESIGN.md sections 16, 19, 24 and 25): _Float16, __bf16, or bf16x3 -- the 32-high
+// format, every fp32 operand as two bfloat16 images.  `el` is the element type of an image, NI the number of images, x4 / x8 the
+// fragments of four and eight and `mfma` the 32x32x16 MFMA.  Lane maps and rates are the same for all; float -> el is the
+// compiler's conversion (round to nearest even; fp16 overflows to inf, bf16 has fp32's exponent range).
+// A product is NT MFMAs into the one accumulator: term t multiplies image ta(t) of A with image tb(t) of B.  bf16x3 (image 0 = hi,
+// 1 = lo) issues lo hi, hi lo, hi hi -- the small terms first -- and drops lo lo.
+struct bf16x3 {};
 template <typename E> struct Operand;
 template <> struct Operand<_Float16> {
+  typedef _Float16 el;
   typedef _Float16 x4 __attribute__((ext_vector_type(4)));
   typedef _Float16 x8 __attribute__((ext_vector_type(8)));
+  static constexpr int NI = 1, NT = 1;
+  static constexpr int ta(int) { return 0; }
+  static constexpr int tb(int) { return 0; }
   static __device__ inline f32x16 mfma(x8 a, x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 template <> struct Operand<__bf16> {
+  typedef __bf16 el;
   typedef __bf16 x4 __attribute__((ext_vector_type(4)));
   typedef __bf16 x8 __attribute__((ext_vector_type(8)));
+  static constexpr int NI = 1, NT = 1;
+  static constexpr int ta(int) { return 0; }
+  static constexpr int tb(int) { return 0; }
   static __device__ inline f32x16 mfma(x8 a, x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 };
+template <> struct Operand<bf16x3> : Operand<__bf16> {
+  static constexpr int NI = 2, NT = 3;
+  static constexpr int ta(int t) { return t == 0; }
+  static constexpr int tb(int t) { return t == 1; }
+};
+template <typename E> using el16 = typename Operand<E>::el;
 template <typename E> using h16x4 = typename Operand<E>::x4;
 template <typename E> using h16x8 = typename Operand<E>::x8;
+// the NI images of four / eight consecutive elements
+template <typename E> struct Img4 { h16x4<E> v[Operand<E>::NI]; };
+template <typename E> struct Img8 { h16x8<E> v[Operand<E>::NI]; };
 
+// The images of one fp32 value.  NI = 1: the rounded value.  bf16x3: hi = bf16(a), lo = bf16(a - hi), the subtraction exact in
+// fp32; where hi is not finite (a is inf or NaN, or rounds to inf) lo = 0, so that no inf meets a -inf in the partial products.
 template <typename E>
-__device__ inline h16x4<E> to_h4(f32x4 v) { return h16x4<E>{(E)v[0], (E)v[1], (E)v[2], (E)v[3]}; }
+__device__ inline void to_img(float a, el16<E> (&o)[Operand<E>::NI]) {
+  o[0] = (el16<E>)a;
+  if constexpr (Operand<E>::NI == 2) {
+    const float hi = (float)o[0];
+    const bool finite = (__float_as_uint(hi) & 0x7f800000u) != 0x7f800000u;
+    o[1] = (el16<E>)(finite ? a - hi : 0.0f);
+  }
+}
+template <typename E>
+__device__ inline Img4<E> to_h4(f32x4 v) {
+  Img4<E> o;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    el16<E> e[Operand<E>::NI];
+    to_img<E>(v[c], e);
+#pragma unroll
+    for (int n = 0; n < Operand<E>::NI; ++n) o.v[n][c] = e[n];
+  }
+  return o;
+}
+template <typename E>
+__device__ inline Img8<E> to_h8(const float (&x)[8]) {
+  Img8<E> o;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    el16<E> e[Operand<E>::NI];
+    to_img<E>(x[c], e);
+#pragma unroll
+    for (int n = 0; n < Operand<E>::NI; ++n) o.v[n][c] = e[n];
+  }
+  return o;
+}
+// acc += a b, term by term in the format's order
+template <typename E>
+__device__ inline f32x16 mfma_terms(const Img8<E>& a, const Img8<E>& b, f32x16 acc) {
+#pragma unroll
+  for (int t = 0; t < Operand<E>::NT; ++t) acc = Operand<E>::mfma(a.v[Operand<E>::ta(t)], b.v[Operand<E>::tb(t)], acc);
+  return acc;
+}
 
 constexpr float QK_SCALE = 0.17677669529663687f;            // 32^-0.5
 constexpr float QK_SCALE_LOG2E = 0.2550348616841918f;       // 32^-0.5 * log2(e)

@@ -27,7 +27,8 @@
 // the stem (K = 12, vector unit) recomputes it.
 // With `mixed = 1` in the argument struct the same three products run on v_mfma_f32_32x32x16_f16 with both
 // operands rounded to fp16 as they are staged (train_front_mixed.inc) and the projection's GEMMs take bt_train_matmul's mixed
-// route; `operand = BT_OPERAND_BF16` beside it (section 24) rounds to bfloat16 on v_mfma_f32_32x32x16_bf16 instead; everything
+// route; `operand = BT_OPERAND_BF16` beside it (section 24) rounds to bfloat16 on v_mfma_f32_32x32x16_bf16 instead, and
+// `BT_OPERAND_BF16X3` (section 25) splits every operand into two bfloat16 images for three such MFMAs per product; everything
 // around the products is the code below either way.
 //
 // Reproducibility, as in train.hip: no atomics; every output element is written by one thread of one launch; a GEMM element
@@ -469,8 +470,10 @@ struct Layout {
 // The one layout of every route.  batch (section 18) adds the column sums of the backward (its centring needs them whether the
 // caller wants them or not) and, to the forward, the stem's staged pre and the chunks' moments (two doubles per column: four floats
 // of the workspace); mixed (section 19) adds the conv unit's fp16 weight image (Cout 6 Cin halves; the forward's, or the
-// backward-data's transposed one).
-Layout layout(int unit, bool backward, bool batch, bool mixed, long BT, int F, int C, int dim) {
+// backward-data's transposed one) `images` times: one for fp16 or bfloat16 operands, the hi and the lo image for the split ones
+// of section 25.
+int images_of(int mixed, int operand) { return !mixed ? 0 : operand == BT_OPERAND_BF16X3 ? 2 : 1; }
+Layout layout(int unit, bool backward, bool batch, int images, long BT, int F, int C, int dim) {
   Layout L{};
   size_t at = 0;
   auto take = [&](size_t n) { const size_t o = at; at += up64(n); return o; };
@@ -506,7 +509,7 @@ Layout layout(int unit, bool backward, bool batch, bool mixed, long BT, int F, i
       } else if (batch) {
         L.part = take(4 * (size_t)cs_chunks(M) * Cout);
       }
-      if (mixed) L.wimg = take(Cout * 3 * C);
+      if (images) L.wimg = take(images * Cout * 3 * C);
       break;
     }
     case BT_FRONT_LINEAR: {
@@ -564,7 +567,8 @@ const char* check_mixed(int unit, int mixed, int operand, bool linear_too) {
   if (mixed != 0 && mixed != 1) return "mixed must be 0 or 1";
   if (mixed && unit != BT_FRONT_CONV && !(linear_too && unit == BT_FRONT_LINEAR))
     return "mixed = 1 belongs to BT_FRONT_CONV and (bt_front_args) BT_FRONT_LINEAR: the other units have no product worth an MFMA";
-  if (mixed && operand != BT_OPERAND_F16 && operand != BT_OPERAND_BF16) return "mixed = 1: operand must be BT_OPERAND_F16 or BT_OPERAND_BF16";
+  if (mixed && operand != BT_OPERAND_F16 && operand != BT_OPERAND_BF16 && operand != BT_OPERAND_BF16X3)
+    return "mixed = 1: operand must be BT_OPERAND_F16, BT_OPERAND_BF16 or BT_OPERAND_BF16X3";
   return nullptr;
 }
 
@@ -658,7 +662,7 @@ int prepare(const char* fn, int unit, const Call& c, Layout& L) {
   if (!e && c.batch && !c.backward && (uintptr_t)c.ws % 8) e = "the workspace must be 8-byte aligned";   // (the moments are doubles)
   if (!e && c.mixed && (uintptr_t)c.ws % 16) e = "mixed = 1: the workspace must be 16-byte aligned";
   if (e) return fail(fn, e);
-  L = layout(unit, c.backward, c.batch, c.mixed != 0, (long)c.B * c.T, c.F, c.C, c.dim);
+  L = layout(unit, c.backward, c.batch, images_of(c.mixed, c.operand), (long)c.B * c.T, c.F, c.C, c.dim);
   if (c.ws_bytes < L.total * sizeof(float)) return fail(fn, "workspace too small", BT_ERR_WORKSPACE);
   return BT_OK;
 }
@@ -741,14 +745,14 @@ void stem_backward(hipStream_t s, const Call& c, const Layout& L) {
 
 dim3 conv_grid(long GM, int GN, int chunks) { return dim3(blocks_of(GN, GT), blocks_of(GM, GT), (unsigned)chunks); }
 
-// One conv GEMM.  wimg: the workspace of the 16-bit weight image (16-mixed, elements E), null = the fp32 kernel.  MODE 0 and 1
-// read the weight from the image, which a launch ahead of the GEMM packs ([co][k] for MODE 0, transposed for MODE 1); MODE 2 has
-// no weight operand.
+// One conv GEMM.  wimg: the workspace of the 16-bit weight image (16-mixed, operand format E: one image, or hi then lo), null =
+// the fp32 kernel.  MODE 0 and 1 read the weight from the image, which a launch ahead of the GEMM packs ([co][k] for MODE 0,
+// transposed for MODE 1); MODE 2 has no weight operand.
 template <typename E, int MODE>
 void launch_conv_as(hipStream_t s, ConvP p, float* wimg, dim3 grid) {
   if (wimg && MODE != 2) {
     hipLaunchKernelGGL(conv_pack_kernel<E>, dim3(blocks_of((long)p.Cout * 6 * p.Cin, 256)), dim3(256), 0, s, p.w, p.Cout, p.Cin, MODE,
-                       (E*)wimg);
+                       (el16<E>*)wimg);
     p.wh = wimg;
   }
   const auto kernel = wimg ? conv_gemm_mixed_kernel<E, MODE> : conv_gemm_kernel<MODE>;
@@ -757,7 +761,8 @@ void launch_conv_as(hipStream_t s, ConvP p, float* wimg, dim3 grid) {
 // ... with the operand format of the call (read only where wimg is given)
 template <int MODE>
 void launch_conv(hipStream_t s, const Call& c, const ConvP& p, float* wimg, dim3 grid) {
-  if (wimg && c.operand == BT_OPERAND_BF16) launch_conv_as<__bf16, MODE>(s, p, wimg, grid);
+  if (wimg && c.operand == BT_OPERAND_BF16X3) launch_conv_as<bf16x3, MODE>(s, p, wimg, grid);
+  else if (wimg && c.operand == BT_OPERAND_BF16) launch_conv_as<__bf16, MODE>(s, p, wimg, grid);
   else launch_conv_as<_Float16, MODE>(s, p, wimg, grid);
 }
 
@@ -856,10 +861,10 @@ int run(const char* fn, void* stream, int unit, const Call& c) {
   return finish(fn);
 }
 
-size_t workspace_bytes(int unit, int backward, bool batch, bool mixed, int B, int T, int F, int C, int dim) {
+size_t workspace_bytes(int unit, int backward, bool batch, int images, int B, int T, int F, int C, int dim) {
   if (batch ? bn_check_shape(unit, B, T, F, C) : check_shape(unit, B, T, F, C, dim)) return 0;
-  if (mixed && check_mixed(unit, 1, BT_OPERAND_F16, !batch)) return 0;
-  return layout(unit, backward != 0, batch, mixed, (long)B * T, F, C, dim).total * sizeof(float);
+  if (images && check_mixed(unit, 1, BT_OPERAND_F16, !batch)) return 0;
+  return layout(unit, backward != 0, batch, images, (long)B * T, F, C, dim).total * sizeof(float);
 }
 
 }  // namespace
@@ -889,16 +894,22 @@ void bt_front_bn_struct_sizes(int32_t* out) {
 }
 
 size_t bt_front_workspace_bytes(int unit, int backward, int B, int T, int F, int C, int dim) {
-  return workspace_bytes(unit, backward, false, false, B, T, F, C, dim);
+  return workspace_bytes(unit, backward, false, 0, B, T, F, C, dim);
 }
 size_t bt_front_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C, int dim) {
-  return workspace_bytes(unit, backward, false, true, B, T, F, C, dim);
+  return workspace_bytes(unit, backward, false, 1, B, T, F, C, dim);
+}
+size_t bt_front_workspace_bytes_x3(int unit, int backward, int B, int T, int F, int C, int dim) {
+  return workspace_bytes(unit, backward, false, 2, B, T, F, C, dim);
 }
 size_t bt_front_bn_workspace_bytes(int unit, int backward, int B, int T, int F, int C) {
-  return workspace_bytes(unit, backward, true, false, B, T, F, C, 0);
+  return workspace_bytes(unit, backward, true, 0, B, T, F, C, 0);
 }
 size_t bt_front_bn_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C) {
-  return workspace_bytes(unit, backward, true, true, B, T, F, C, 0);
+  return workspace_bytes(unit, backward, true, 1, B, T, F, C, 0);
+}
+size_t bt_front_bn_workspace_bytes_x3(int unit, int backward, int B, int T, int F, int C) {
+  return workspace_bytes(unit, backward, true, 2, B, T, F, C, 0);
 }
 
 // running statistics and batch statistics (section 18): adapter, shared preamble, dispatch

@@ -6,7 +6,8 @@
 // fp32 on v_mfma_f32_32x32x16_f16.  Nothing clamps.  Everything around the products is the fp32 code of train_front.hip.
 // The kernels are templates over the operand element type E (Operand<E>, train_common.h): _Float16 is the above, __bf16 (section
 // 24) rounds to bfloat16 instead -- NaN stays NaN, nothing overflows -- on v_mfma_f32_32x32x16_bf16, the weight image in the
-// same bytes.
+// same bytes.  bf16x3 (section 25) keeps two bfloat16 images of every operand, hi and lo (to_img, train_common.h): the packed
+// weight is a hi image followed by a lo image, the staged tiles are pairs, and a k-step issues lo hi, hi lo, hi hi.
 //
 // Lane maps of the 32x32x16 fp16 MFMA (train_mixed.inc): lane l, r = l & 31, h = l >> 5, element j = 0 .. 7 of a fragment is
 // A[row r][k = 8 h + j] and B[k = 8 h + j][col r]; C / D register i is row (i & 3) + 8 (i >> 2) + 4 h, col r.  Both operand tiles
@@ -35,8 +36,9 @@ __device__ inline f32x4 load4(const float* p, bool vec) {
 }
 
 // img [Cout][6 Cin] (transposed == 0: k = dt 2 Cin + df Cin + ci) or [2 Cin][3 Cout] (k = dt Cout + co) = E(w[co][ci][df][dt])
+// (bf16x3: the lo image follows the hi image, Cout 6 Cin elements further)
 template <typename E>
-__global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, int Cout, int Cin, int transposed, E* img) {
+__global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, int Cout, int Cin, int transposed, el16<E>* img) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= Cout * 6 * Cin) return;
   int co, j, dt;
@@ -52,14 +54,18 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, int Cout
     co = k - dt * Cout;
   }
   const int df = j / Cin, ci = j - df * Cin;
-  img[i] = (E)w[((long)co * Cin + ci) * 6 + df * 3 + dt];
+  el16<E> e[Operand<E>::NI];
+  to_img<E>(w[((long)co * Cin + ci) * 6 + df * 3 + dt], e);
+#pragma unroll
+  for (int n = 0; n < Operand<E>::NI; ++n) img[(long)n * Cout * 6 * Cin + i] = e[n];
 }
 
 // conv_gemm_kernel<MODE> with operands of type E: the same grid, tile and epilogue.  p.wh: the packed weight (MODE 0 and 1).
 template <typename E, int MODE>
 __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
-  __shared__ __attribute__((aligned(16))) E As[GT][MLD];
-  __shared__ __attribute__((aligned(16))) E Bs[GT][MLD];
+  constexpr int NI = Operand<E>::NI;
+  __shared__ __attribute__((aligned(16))) el16<E> As[NI][GT][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Bs[NI][GT][MLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 5, lr = lane & 31, wm = wave >> 1, wn = wave & 1;
   const ConvTile<MODE> tile(p);
@@ -79,8 +85,8 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
   }
   const int dt2 = tile.n0 / tile.C2, j2 = tile.n0 - dt2 * tile.C2;   // MODE 2: the run and the first column of this tile of the implicit A
 
-  h16x4<E> ra[2], rb[2];
-  h16x8<E> rw;
+  Img4<E> ra[2], rb[2];
+  Img8<E> rw;
   auto fetch = [&](long k0) {
     if constexpr (MODE != 2) {
       const int dt = (int)(k0 / run), j0 = (int)(k0 - (long)dt * run);
@@ -101,8 +107,12 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
         ra[i] = to_h4<E>(v);
       }
       const int gn = tile.n0 + (tid >> 2);
-      rw = h16x8<E>{0, 0, 0, 0, 0, 0, 0, 0};
-      if (gn < tile.GN) rw = *reinterpret_cast<const h16x8<E>*>((const E*)p.wh + (long)gn * KW + k0 + (tid & 3) * 8);
+#pragma unroll
+      for (int n = 0; n < NI; ++n) {
+        rw.v[n] = h16x8<E>{0, 0, 0, 0, 0, 0, 0, 0};
+        if (gn < tile.GN)
+          rw.v[n] = *reinterpret_cast<const h16x8<E>*>((const el16<E>*)p.wh + (long)n * p.Cout * 6 * p.Cin + (long)gn * KW + k0 + (tid & 3) * 8);
+      }
     } else {
       const int c4 = (tid & 15) * 4;
 #pragma unroll
@@ -126,18 +136,23 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
   auto commit = [&]() {
     if constexpr (MODE != 2) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i) *reinterpret_cast<h16x4<E>*>(&As[i * 32 + (tid >> 3)][(tid & 7) * 4]) = ra[i];
-      *reinterpret_cast<h16x8<E>*>(&Bs[tid >> 2][(tid & 3) * 8]) = rw;
+      for (int n = 0; n < NI; ++n) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) *reinterpret_cast<h16x4<E>*>(&As[n][i * 32 + (tid >> 3)][(tid & 7) * 4]) = ra[i].v[n];
+        *reinterpret_cast<h16x8<E>*>(&Bs[n][tid >> 2][(tid & 3) * 8]) = rw.v[n];
+      }
     } else {
       const int c4 = (tid & 15) * 4;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int kk = i * 16 + (tid >> 4);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          As[c4 + c][kk] = ra[i][c];
-          Bs[c4 + c][kk] = rb[i][c];
-        }
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int n = 0; n < NI; ++n) {
+            As[n][c4 + c][kk] = ra[i].v[n][c];
+            Bs[n][c4 + c][kk] = rb[i].v[n][c];
+          }
       }
     }
   };
@@ -151,9 +166,15 @@ __global__ __launch_bounds__(256) void conv_gemm_mixed_kernel(const ConvP p) {
     __syncthreads();
     if (k0 + MK < tile.ke) fetch(k0 + MK);
 #pragma unroll
-    for (int s = 0; s < MK / 16; ++s)
-      acc = Operand<E>::mfma(*reinterpret_cast<const h16x8<E>*>(&As[wm * 32 + lr][16 * s + 8 * g]),
-                             *reinterpret_cast<const h16x8<E>*>(&Bs[wn * 32 + lr][16 * s + 8 * g]), acc);
+    for (int s = 0; s < MK / 16; ++s) {
+      Img8<E> a, b;
+#pragma unroll
+      for (int n = 0; n < NI; ++n) {
+        a.v[n] = *reinterpret_cast<const h16x8<E>*>(&As[n][wm * 32 + lr][16 * s + 8 * g]);
+        b.v[n] = *reinterpret_cast<const h16x8<E>*>(&Bs[n][wn * 32 + lr][16 * s + 8 * g]);
+      }
+      acc = mfma_terms<E>(a, b, acc);
+    }
     __syncthreads();
   }
   conv_store<MODE>(p, tile, acc, wm, wn, lr, g);

@@ -7,6 +7,9 @@
 // E = __bf16 (DESIGN.md section 24) is the same with one word changed -- both operands rounded to bfloat16, to nearest even, NaN
 // stays NaN, nothing overflows by rounding -- on v_mfma_f32_32x32x16_bf16.  Staging, lane maps, orders of summation and the mask
 // mapping do not depend on E.
+// E = bf16x3 (DESIGN.md section 25, "32-high") keeps every staged operand as two bfloat16 images, hi = bf16(a) and lo = bf16(a - hi)
+// (to_img, train_common.h), and every product becomes A_lo B_hi + A_hi B_lo + A_hi B_hi, three MFMAs in that order into the one
+// accumulator.  The operands rounded in registers (P, dS, the own side's fragments) are split in registers the same way.
 //
 // Lane maps of the 32x32x16 fp16 MFMA (lane l, r = l & 31, h = l >> 5, element j = 0 .. 7 of a fragment):
 //   A[row r][k = 8 h + j],  B[k = 8 h + j][col r],  C / D register i: row = (i & 3) + 8 (i >> 2) + 4 h, col = r.
@@ -31,7 +34,7 @@ constexpr int XB = 32;         // attention: queries (keys) per wave and keys (q
 // lies behind row R or behind k = ke is zero and is never read; `vec`: 16-byte loads are possible (alignment of the base, the
 // leading dimension and the chunk's first k).
 template <typename E, bool TR>
-__device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k0, long ke, bool vec, E (*S)[MLD], int tid) {
+__device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k0, long ke, bool vec, el16<E> (*S)[MT][MLD], int tid) {
 #pragma unroll
   for (int i = 0; i < MT * MK / 4 / 256; ++i) {
     const int gi = tid + i * 256;
@@ -49,7 +52,9 @@ __device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k
             if (gk + c < ke) v[c] = p[c];
         }
       }
-      *reinterpret_cast<h16x4<E>*>(&S[row][kk]) = to_h4<E>(v);
+      const Img4<E> q = to_h4<E>(v);
+#pragma unroll
+      for (int n = 0; n < Operand<E>::NI; ++n) *reinterpret_cast<h16x4<E>*>(&S[n][row][kk]) = q.v[n];
     } else {
       const int kk = gi >> 5, row = (gi & 31) * 4;
       const long gr = r0 + row, gk = k0 + kk;
@@ -64,7 +69,12 @@ __device__ inline void mx_stage(const float* P, long ld, long r0, long R, long k
         }
       }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) S[row + c][kk] = (E)v[c];
+      for (int c = 0; c < 4; ++c) {
+        el16<E> e[Operand<E>::NI];
+        to_img<E>(v[c], e);
+#pragma unroll
+        for (int n = 0; n < Operand<E>::NI; ++n) S[n][row + c][kk] = e[n];
+      }
     }
   }
 }
@@ -74,8 +84,8 @@ __device__ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 
 // gemm_body with fp16 operands: the same GemmP, the same epilogue (bias, residual, +=, GELU into a second output, dropout)
 template <typename E, bool AT, bool BT, bool DROP>
 __device__ inline void mx_gemm_body(const GemmP& p, const DropSite& ds, int drop_act) {
-  __shared__ __attribute__((aligned(16))) E As[MT][MLD];
-  __shared__ __attribute__((aligned(16))) E Bs[MT][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> As[Operand<E>::NI][MT][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Bs[Operand<E>::NI][MT][MLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 5, lr = lane & 31, wm = wave >> 1, wn = wave & 1;
   const long m0 = (long)blockIdx.y * MT, n0 = (long)blockIdx.x * MT;
@@ -95,16 +105,22 @@ __device__ inline void mx_gemm_body(const GemmP& p, const DropSite& ds, int drop
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < MK / 16; ++s) {
-      h16x8<E> a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        a[i] = *reinterpret_cast<const h16x8<E>*>(&As[wm * 64 + i * 32 + lr][16 * s + 8 * g]);
-        b[i] = *reinterpret_cast<const h16x8<E>*>(&Bs[wn * 64 + i * 32 + lr][16 * s + 8 * g]);
-      }
+      Img8<E> a[2], b[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = Operand<E>::mfma(a[i], b[j], acc[i][j]);
+        for (int n = 0; n < Operand<E>::NI; ++n) {
+          a[i].v[n] = *reinterpret_cast<const h16x8<E>*>(&As[n][wm * 64 + i * 32 + lr][16 * s + 8 * g]);
+          b[i].v[n] = *reinterpret_cast<const h16x8<E>*>(&Bs[n][wn * 64 + i * 32 + lr][16 * s + 8 * g]);
+        }
+      // term-major over the four accumulators: consecutive MFMAs never depend on each other, each accumulator sees its terms in order
+#pragma unroll
+      for (int t = 0; t < Operand<E>::NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[i][j] = Operand<E>::mfma(a[i].v[Operand<E>::ta(t)], b[j].v[Operand<E>::tb(t)], acc[i][j]);
     }
     __syncthreads();
   }
@@ -128,54 +144,66 @@ __global__ __launch_bounds__(256) void mx_gemm_drop_kernel(const GemmP p, const 
 // ---- attention, head dim 32, one wave per workgroup: XB own rows against tiles of XB rows of the other side -------------------
 // Stage rows [t0, t0 + XB) of a [T, 32] slice (row stride ld) as fp16: R[row][d] and / or Tt[d][row]; rows >= T are zeros.
 template <typename E>
-__device__ inline void mx_stage32(const float* base, long ld, int t0, int T, E (*R)[MLD], E (*Tt)[MLD], int lane) {
+__device__ inline void mx_stage32(const float* base, long ld, int t0, int T, el16<E> (*R)[XB][MLD], el16<E> (*Tt)[XB][MLD], int lane) {
 #pragma unroll
   for (int i = 0; i < XB * 8 / 64; ++i) {
     const int idx = i * 64 + lane, row = idx >> 3, part = idx & 7;
     const int t = t0 + row;
     const f32x4 v = t < T ? reinterpret_cast<const f32x4*>(base + (long)t * ld)[part] : f32x4{0.f, 0.f, 0.f, 0.f};
-    if (R) *reinterpret_cast<h16x4<E>*>(&R[row][4 * part]) = to_h4<E>(v);
-    if (Tt) {
+    const Img4<E> q = to_h4<E>(v);
 #pragma unroll
-      for (int c = 0; c < 4; ++c) Tt[4 * part + c][row] = (E)v[c];
+    for (int n = 0; n < Operand<E>::NI; ++n) {
+      if (R) *reinterpret_cast<h16x4<E>*>(&R[n][row][4 * part]) = q.v[n];
+      if (Tt) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) Tt[n][4 * part + c][row] = q.v[n][c];
+      }
     }
   }
 }
 
 // the own side's row r as the B operand [k = d][col r] of both k-steps
 template <typename E>
-__device__ inline void mx_own_frag(const float* row, bool ok, int h, h16x8<E> (&f)[2]) {
+__device__ inline void mx_own_frag(const float* row, bool ok, int h, Img8<E> (&f)[2]) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const f32x4 lo = ok ? reinterpret_cast<const f32x4*>(row + 16 * s + 8 * h)[0] : f32x4{0.f, 0.f, 0.f, 0.f};
     const f32x4 hi = ok ? reinterpret_cast<const f32x4*>(row + 16 * s + 8 * h)[1] : f32x4{0.f, 0.f, 0.f, 0.f};
-    f[s] = h16x8<E>{(E)lo[0], (E)lo[1], (E)lo[2], (E)lo[3], (E)hi[0], (E)hi[1], (E)hi[2], (E)hi[3]};
+    const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    f[s] = to_h8<E>(x);
   }
 }
 
 // X[tile row][own col] = sum_d R[tile row][d] own[col][d]
 template <typename E>
-__device__ inline f32x16 mx_first(const E (*R)[MLD], const h16x8<E> (&own)[2], int r, int h) {
+__device__ inline f32x16 mx_first(const el16<E> (*R)[XB][MLD], const Img8<E> (&own)[2], int r, int h) {
   f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
 #pragma unroll
-  for (int s = 0; s < 2; ++s)
-    acc = Operand<E>::mfma(*reinterpret_cast<const h16x8<E>*>(&R[r][16 * s + 8 * h]), own[s], acc);
+  for (int s = 0; s < 2; ++s) {
+    Img8<E> a;
+#pragma unroll
+    for (int n = 0; n < Operand<E>::NI; ++n) a.v[n] = *reinterpret_cast<const h16x8<E>*>(&R[n][r][16 * s + 8 * h]);
+    acc = mfma_terms<E>(a, own[s], acc);
+  }
   return acc;
 }
 
 // acc[d][own col] += sum_rows Tt[d][tile row] X[tile row][own col], X = the sixteen fp32 values of a lane, rounded here
 template <typename E>
-__device__ inline void mx_second(const E (*Tt)[MLD], const float (&x)[16], int r, int h, f32x16& acc) {
+__device__ inline void mx_second(const el16<E> (*Tt)[XB][MLD], const float (&x)[16], int r, int h, f32x16& acc) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const h16x4<E> a0 = *reinterpret_cast<const h16x4<E>*>(&Tt[r][16 * s + 4 * h]);
-    const h16x4<E> a1 = *reinterpret_cast<const h16x4<E>*>(&Tt[r][16 * s + 8 + 4 * h]);
-    const h16x8<E> a = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-    const h16x8<E> b = {(E)x[8 * s], (E)x[8 * s + 1], (E)x[8 * s + 2], (E)x[8 * s + 3],
-                        (E)x[8 * s + 4], (E)x[8 * s + 5], (E)x[8 * s + 6], (E)x[8 * s + 7]};
-    acc = Operand<E>::mfma(a, b, acc);
+    Img8<E> a;
+#pragma unroll
+    for (int n = 0; n < Operand<E>::NI; ++n) {
+      const h16x4<E> a0 = *reinterpret_cast<const h16x4<E>*>(&Tt[n][r][16 * s + 4 * h]);
+      const h16x4<E> a1 = *reinterpret_cast<const h16x4<E>*>(&Tt[n][r][16 * s + 8 + 4 * h]);
+      a.v[n] = h16x8<E>{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+    }
+    const float xs[8] = {x[8 * s], x[8 * s + 1], x[8 * s + 2], x[8 * s + 3], x[8 * s + 4], x[8 * s + 5], x[8 * s + 6], x[8 * s + 7]};
+    acc = mfma_terms<E>(a, to_h8<E>(xs), acc);
   }
 }
 
@@ -192,14 +220,14 @@ __device__ inline void mx_store_t(float* out, const f32x16& acc, int h, float sc
 // 1 / (1 - p) with DROP, rounded to fp16 -- is the B operand of O^T += V^T P^T.
 template <typename E, bool DROP>
 __device__ inline void mx_attn_fwd_body(const float* qkv, int T, int D, float* O, float* lse, const DropSite& ds) {
-  __shared__ __attribute__((aligned(16))) E Kr[XB][MLD];
-  __shared__ __attribute__((aligned(16))) E Vt[XB][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Kr[Operand<E>::NI][XB][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Vt[Operand<E>::NI][XB][MLD];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5, hd = blockIdx.y, b = blockIdx.z, H = D / 32;
   const int t = blockIdx.x * XB + r;
   const bool ok = t < T;
   const long ld = 3L * D;
   const float* base = qkv + (long)b * T * ld + hd * 32;
-  h16x8<E> qf[2];
+  Img8<E> qf[2];
   mx_own_frag<E>(base + (long)(ok ? t : 0) * ld, ok, h, qf);
   f32x16 acc;
 #pragma unroll
@@ -259,15 +287,15 @@ __global__ __launch_bounds__(64) void mx_attn_fwd_drop_kernel(const float* qkv, 
 template <typename E, bool DROP>
 __device__ inline void mx_attn_dq_body(const float* qkv, const float* dO, const float* lse, const float* delta, int T, int D,
                                        float* dqkv, const DropSite& ds) {
-  __shared__ __attribute__((aligned(16))) E Kr[XB][MLD];
-  __shared__ __attribute__((aligned(16))) E Kt[XB][MLD];
-  __shared__ __attribute__((aligned(16))) E Vr[XB][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Kr[Operand<E>::NI][XB][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Kt[Operand<E>::NI][XB][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Vr[Operand<E>::NI][XB][MLD];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5, hd = blockIdx.y, b = blockIdx.z, H = D / 32;
   const int t = blockIdx.x * XB + r;
   const bool ok = t < T;
   const long ld = 3L * D, m = (long)b * T + (ok ? t : 0);
   const float* base = qkv + (long)b * T * ld + hd * 32;
-  h16x8<E> qf[2], gf[2];
+  Img8<E> qf[2], gf[2];
   mx_own_frag<E>(base + (long)(ok ? t : 0) * ld, ok, h, qf);
   mx_own_frag<E>(dO + m * D + hd * 32, ok, h, gf);
   const float ls = ok ? lse[m * H + hd] : 0.0f, dl = ok ? delta[m * H + hd] : 0.0f;
@@ -317,10 +345,10 @@ __global__ __launch_bounds__(64) void mx_attn_dq_drop_kernel(const float* qkv, c
 template <typename E, bool DROP>
 __device__ inline void mx_attn_dkv_body(const float* qkv, const float* dO, const float* lse, const float* delta, int T, int D,
                                         float* dqkv, const DropSite& ds) {
-  __shared__ __attribute__((aligned(16))) E Qr[XB][MLD];
-  __shared__ __attribute__((aligned(16))) E Qt[XB][MLD];
-  __shared__ __attribute__((aligned(16))) E Gr[XB][MLD];
-  __shared__ __attribute__((aligned(16))) E Gt[XB][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Qr[Operand<E>::NI][XB][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Qt[Operand<E>::NI][XB][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Gr[Operand<E>::NI][XB][MLD];
+  __shared__ __attribute__((aligned(16))) el16<E> Gt[Operand<E>::NI][XB][MLD];
   __shared__ float Ls[XB], Ds[XB];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5, hd = blockIdx.y, b = blockIdx.z, H = D / 32;
   const int t = blockIdx.x * XB + r;
@@ -328,7 +356,7 @@ __device__ inline void mx_attn_dkv_body(const float* qkv, const float* dO, const
   const long ld = 3L * D;
   const float* base = qkv + (long)b * T * ld + hd * 32;
   const float* gbase = dO + (long)b * T * D + hd * 32;
-  h16x8<E> kf[2], vf[2];
+  Img8<E> kf[2], vf[2];
   mx_own_frag<E>(base + D + (long)(ok ? t : 0) * ld, ok, h, kf);
   mx_own_frag<E>(base + 2 * D + (long)(ok ? t : 0) * ld, ok, h, vf);
   f32x16 dk, dv;

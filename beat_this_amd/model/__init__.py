@@ -355,13 +355,15 @@ class BeatThis(_TracksChildren, nn.Module):
         return getattr(s, which + "_operand") if stays else "fp16"
 
     def set_train_precision(self, precision: str, operand: str = None) -> "BeatThis":
-        """"16-mixed" or "32-true" (the default) for the trunk's units on the differentiable route.  ``operand``: "fp16" or "bf16",
-        the format the 16-mixed products round their operands to (``train_operand``); None keeps it while the precision stays
-        "16-mixed" and otherwise resets it to "fp16"; "bf16" with "32-true" is a ``ValueError``"""
+        """"16-mixed", "32-high" or "32-true" (the default) for the trunk's units on the differentiable route.  "32-high": every
+        product of "16-mixed" with each fp32 operand as the sum of two bfloat16 numbers, on three bfloat16 MFMAs (DESIGN.md section
+        25).  ``operand``: "fp16" or "bf16", the format the 16-mixed products round their operands to (``train_operand``); None
+        keeps it while the precision stays "16-mixed" and otherwise resets it to "fp16"; "bf16" with "32-true" or "32-high" is a
+        ``ValueError``"""
         return self._set(train_precision=precision, train_operand=self._operand_for("train", precision, operand))
 
     def set_frontend_precision(self, precision: str, operand: str = None) -> "BeatThis":
-        """"16-mixed" or "32-true" (the default) for the differentiable frontend, independent of ``set_train_precision``;
+        """"16-mixed", "32-high" or "32-true" (the default) for the differentiable frontend, independent of ``set_train_precision``;
         ``operand`` as there (``frontend_operand``)"""
         return self._set(frontend_precision=precision, frontend_operand=self._operand_for("frontend", precision, operand))
 

@@ -64,11 +64,14 @@ _FAMILY = {(False, True): "", (False, False): "_dropout", (True, True): "_mixed"
 
 
 def _operand(mixed) -> int:
-    """BT_OPERAND_* of a ``mixed`` value: False (fp32: the field is not read), True or "fp16", or "bf16" (section 24)"""
+    """BT_OPERAND_* of a ``mixed`` value: False (fp32: the field is not read), True or "fp16", "bf16" (section 24) or "bf16x3"
+    (section 25: the split operands of "32-high")"""
     if mixed is True or not mixed:
         return _lib.OPERAND_F16
+    if mixed == "bf16x3":
+        return _lib.OPERAND_BF16X3
     if mixed not in _lib.OPERANDS:
-        raise ValueError(f"mixed must be False, True, 'fp16' or 'bf16', got {mixed!r}")
+        raise ValueError(f"mixed must be False, True, 'fp16', 'bf16' or 'bf16x3', got {mixed!r}")
     return _lib.OPERANDS[mixed]
 
 
@@ -291,7 +294,8 @@ def _front_call(backward: bool, unit: int, a, device) -> None:
     batch = isinstance(a, _lib.FrontBnArgs)
     family = "bt_front_bn" if batch else "bt_front"
     shape = (a.B, a.T, a.F, a.C) if batch else (a.B, a.T, a.F, a.C, a.dim)
-    need = getattr(_lib.lib(), f"{family}_workspace_bytes_mixed" if a.mixed else f"{family}_workspace_bytes")(unit, int(backward), *shape)
+    query = "" if not a.mixed else "_x3" if a.operand == _lib.OPERAND_BF16X3 else "_mixed"   # (the split format has two weight images)
+    need = getattr(_lib.lib(), f"{family}_workspace_bytes{query}")(unit, int(backward), *shape)
     if need == 0:
         check_front_limits(a.B, a.T)
         if batch:
@@ -607,12 +611,12 @@ def frontend_train(model, x, batch_statistics=False, mixed=None, drops=None):
     """``BeatThis.frontend`` on the differentiable route, in the reference's order (beat_tracker.py:54-80, 290-301): stem, three
     times (partial transformer, conv unit), projection.  (B, T, 128) -> (B, T, D).  ``batch_statistics``: the five BatchNorms
     normalise with this call's batch and move their running buffers (section 18).  ``mixed``: the conv units, the leaves and the
-    projection on fp16 operands (section 19), or with "bf16" on bfloat16 ones (section 24); None reads ``model.frontend_precision``
+    projection on fp16 operands (section 19), with "bf16" on bfloat16 ones (section 24), with "bf16x3" on split ones (section 25); None reads ``model.frontend_precision``
     and ``model.frontend_operand``.  The stem is fp32 either way.  ``drops``:
     None, or a callable that yields the ``drop`` of the next leaf call (section 21: ``BeatThis`` hands out the streams in forward
     order); the stem, the conv units and the projection never drop."""
     if mixed is None:
-        mixed = model.frontend_precision == "16-mixed" and model.frontend_operand
+        mixed = {"16-mixed": model.frontend_operand, "32-high": "bf16x3"}.get(model.frontend_precision, False)
     fr = model.frontend
     check_front_limits(int(x.shape[0]), int(x.shape[1]))
     if batch_statistics:

@@ -46,10 +46,10 @@ class PLBeatThis(nn.Module):
     The six main layers, the final RMSNorm and the task heads are trainable; everything else about the training route is a
     switch that maps onto one field of the model's ``settings.TrainSettings``, which says what it means: ``train_frontend``
     (``BeatThis.set_frontend_trainable``: whole-model fine-tuning, else the frontend is frozen), on top of it
-    ``batch_statistics`` (``set_batch_statistics``: what training from scratch needs) and ``frontend_precision`` ("16-mixed" or
-    "32-true"; None leaves the model's default, "32-true"; ``set_frontend_precision``); ``precision`` ("32-true", the default, or
-    "16-mixed", the reference's trainer setting: ``set_train_precision``, and ``fit`` then scales the loss with an
-    ``optim.LossScaler``); ``mixed_operand`` / ``frontend_mixed_operand`` ("fp16", "bf16" or None = "fp16": the ``operand`` of those
+    ``batch_statistics`` (``set_batch_statistics``: what training from scratch needs) and ``frontend_precision`` ("16-mixed", "32-high" or
+    "32-true"; None leaves the model's default, "32-true"; ``set_frontend_precision``); ``precision`` ("32-true", the default,
+    "32-high" -- fp32 products on three bfloat16 MFMAs, no loss scale -- or "16-mixed", the reference's trainer setting:
+    ``set_train_precision``, and ``fit`` then scales the loss with an ``optim.LossScaler``); ``mixed_operand`` / ``frontend_mixed_operand`` ("fp16", "bf16" or None = "fp16": the ``operand`` of those
     two setters -- the format a 16-mixed part rounds its products' operands to; "bf16" needs no loss scale and is a ``ValueError``
     on a part that is not "16-mixed"); ``apply_dropout`` (``enable_dropout`` under ``dropout_seed``: the main layers drop at
     ``dropout["transformer"]`` like the reference's, with this package's own masks) and on top of it and of ``train_frontend``

@@ -8,6 +8,10 @@ import dataclasses
 from typing import NamedTuple, Optional
 
 
+PRECISIONS = ("16-mixed", "32-high", "32-true")   # what ``train_precision`` and ``frontend_precision`` take
+X3_OPERAND = "bf16x3"                             # the operand format of a "32-high" part's calls (BT_OPERAND_BF16X3)
+
+
 class Violation(NamedTuple):
     """The switch ``what`` needs the switch ``needs`` because of ``why``, or (``needs`` None) a value is out of range and ``why``
     says it all.  The switches: "batch_statistics", "frontend_precision", "frontend_dropout", "dropout", "train_frontend",
@@ -44,7 +48,11 @@ class TrainSettings:
     ``train_operand`` / ``frontend_operand`` (the ``operand`` argument of the two setters above, section 24): the 16-bit format both
     operands of a 16-mixed part's products are rounded to, "fp16" (the default: the reference's ``16-mixed``) or "bf16" (what
     Lightning calls ``bf16-mixed``: fp32's exponent range, so nothing overflows by rounding and no loss scale is needed).  Read
-    only where the part's precision is "16-mixed"; "bf16" beside "32-true" is refused.
+    only where the part's precision is "16-mixed"; "bf16" beside "32-true" or "32-high" is refused.
+
+    "32-high" (section 25), a third value of both precisions: the same products as "16-mixed", each fp32 operand multiplied as the
+    sum of two bfloat16 numbers on three bfloat16 MFMAs (what ``torch.set_float32_matmul_precision("high")`` names) -- about
+    2^-17 of an operand kept, fp32's exponent range, no loss scale.  The operand field is not read beside it.
 
     ``batch_statistics`` (``set_batch_statistics``, section 18): training from scratch; needs ``frontend_trainable``.  Without
     it the frontend's BatchNorms use ``running_mean`` / ``running_var``, in ``train()`` as in ``eval()``, and never update them.
@@ -107,8 +115,9 @@ class TrainSettings:
                 found.append(Violation("frontend_dropout", "train_frontend", "only the differentiable frontend drops"))
             return found
         for which, value in (("train", self.train_precision), ("frontend", self.frontend_precision)):
-            if value not in ("16-mixed", "32-true"):
-                found.append(Violation(which + "_precision", None, f"{which} precision must be '16-mixed' or '32-true', got {value!r}"))
+            if value not in PRECISIONS:
+                found.append(Violation(which + "_precision", None,
+                                       f"{which} precision must be '16-mixed', '32-high' or '32-true', got {value!r}"))
         found += self._operand_violations()
         for part, p in rates.items():
             if (part != "frontend" or self.frontend_dropout) and not 0.0 <= float(p) < 1.0:   # (NaN fails both comparisons)
@@ -148,7 +157,8 @@ class Route(NamedTuple):
     """``how``: DIFFERENTIABLE (backward.py), ENGINE (the inference path), MODULES (that path through the sub-modules, so that a
     hook below fires) or REFUSE (a frozen frontend was asked for gradients).  The rest is False unless ``how`` is DIFFERENTIABLE:
     the frontend's BatchNorms use this call's batch; this part's calls draw dropout masks; its unit calls are 16-mixed;
-    ``operand``: "fp16" unless they are 16-mixed on "bf16" operands."""
+    ``operand``: "fp16" unless they are 16-mixed on "bf16" operands; a "32-high" part's calls are mixed calls whose operand is
+    "bf16x3"."""
     how: str
     batch_statistics: bool = False
     drop: bool = False
@@ -178,9 +188,10 @@ def decide(s: TrainSettings, part: str, grad: bool, training: bool = False, x_gr
         if part == "heads":
             return Route(DIFFERENTIABLE)
         drop = s.dropout_rng is not None and training and rate > 0.0 and (s.frontend_dropout or not frontend)
-        mixed = (s.frontend_precision if frontend else s.train_precision) == "16-mixed"
-        return Route(DIFFERENTIABLE, frontend and s.batch_statistics and training, drop, mixed,
-                     (s.frontend_operand if frontend else s.train_operand) if mixed else "fp16")
+        precision = s.frontend_precision if frontend else s.train_precision
+        mixed = precision in ("16-mixed", "32-high")
+        operand = X3_OPERAND if precision == "32-high" else (s.frontend_operand if frontend else s.train_operand) if mixed else "fp16"
+        return Route(DIFFERENTIABLE, frontend and s.batch_statistics and training, drop, mixed, operand)
     if grad and frontend and param_grad:
         return _PLAIN[REFUSE]
     return _PLAIN[MODULES if hooked and part != "heads" else ENGINE]

@@ -127,7 +127,9 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     optimiser, schedule, counters and numpy's generator are restored and the run continues with the next epoch, bit for bit
     as if it had not stopped (with dropout enabled also the model's seed and call counter, when the checkpoint has them).
 
-    ``precision``: "16-mixed" or "32-true" sets the model's ``set_train_precision`` first (None leaves it as it is).  A 16-mixed
+    ``precision``: "16-mixed", "32-high" or "32-true" sets the model's ``set_train_precision`` first (None leaves it as it is).
+    "32-high" (fp32 products on three bfloat16 MFMAs) needs no loss scale and makes an fp32 run's calls
+    around the model, like bf16 operands below.  A 16-mixed
     run multiplies the loss by a ``LossScaler``'s scale before ``backward()`` and hands the scaler to every optimiser step, which
     unscales, skips a step whose gradients are not finite and moves the scale (one 4-byte read per step, ``AdamW.step``); the
     schedule steps with every optimiser call, skipped or not, as the reference's trainer does.  The losses reported are
@@ -148,7 +150,7 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     calls ``set_frontend_trainable``; a checkpoint then carries the larger optimiser state, and ``resume`` needs the same
     setting.  ``batch_statistics``: True / False calls ``set_batch_statistics`` (True needs a trainable frontend); the buffers
     travel in the ``state_dict``, so a checkpoint and ``resume`` need nothing new; ``resume`` needs the same setting.
-    ``frontend_precision``: "16-mixed" or "32-true" calls ``set_frontend_precision``; the loss scaler exists when either precision
+    ``frontend_precision``: "16-mixed", "32-high" or "32-true" calls ``set_frontend_precision``; the loss scaler exists when either precision
     is "16-mixed".  ``frontend_dropout``: True / False sets the frontend's dropout opt-in of a model whose dropout is enabled
     (``BeatThis.enable_dropout(frontend=True)``); the seed and the call counter stay what they are.  True needs dropout enabled
     and a trainable frontend (``ValueError`` otherwise).  The opt-in travels in ``rng["dropout"]`` of the checkpoint, and
@@ -300,18 +302,20 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--apply-frontend-dropout", default=False, action=toggle,
                    help="with --dropout and --train-frontend: the attention / feed-forward leaves of the frontend's partial "
                         "transformers drop too, at --frontend-dropout (default: off)")
-    p.add_argument("--precision", type=str, default="32-true", choices=["32-true", "16-mixed"],
+    p.add_argument("--precision", type=str, default="32-true", choices=["32-true", "32-high", "16-mixed"],
                    help="16-mixed: the reference's training precision -- fp16 matrix products in the main layers, fp32 master "
-                        "weights, a dynamic loss scale (default: %(default)s)")
+                        "weights, a dynamic loss scale; 32-high: the same products with every fp32 operand as two bfloat16 "
+                        "halves on three bfloat16 MFMAs, no loss scale (default: %(default)s)")
     p.add_argument("--mixed-operand", type=str, default=None, choices=["fp16", "bf16"],
                    help="with --precision 16-mixed: the format its matrix products round their operands to; bf16 has fp32's "
                         "exponent range and needs no loss scale (default: fp16)")
     p.add_argument("--train-frontend", default=False, action=toggle,
                    help="whole-model fine-tuning: also train the frontend (frozen BatchNorm statistics unless --batch-statistics, "
                         "no frontend dropout unless --apply-frontend-dropout, fp32 frontend unless --frontend-precision 16-mixed; default: the frontend stays frozen)")
-    p.add_argument("--frontend-precision", type=str, default="32-true", choices=["32-true", "16-mixed"],
+    p.add_argument("--frontend-precision", type=str, default="32-true", choices=["32-true", "32-high", "16-mixed"],
                    help="with --train-frontend: 16-mixed runs the matrix products of the frontend's conv units, partial "
-                        "transformers and projection on fp16 operands too, under the same loss scale (default: %(default)s)")
+                        "transformers and projection on fp16 operands too, under the same loss scale; 32-high: on split "
+                        "bfloat16 operands (default: %(default)s)")
     p.add_argument("--frontend-mixed-operand", type=str, default=None, choices=["fp16", "bf16"],
                    help="with --frontend-precision 16-mixed: the same choice for the frontend's products (default: fp16)")
     p.add_argument("--batch-statistics", default=False, action=toggle,

@@ -724,9 +724,20 @@ int bt_dropout_mask_host(const bt_train_dropout* dropout, int site, int B, int T
  * are staged, and accumulate in fp32 on v_mfma_f32_32x32x16_bf16.  NaN stays NaN; no value overflows by rounding (the exponent
  * range is fp32's), so this format needs no loss scale.  Staging, lane maps, summation orders, the mask mapping, the workspace
  * and everything that is kept are those of fp16.  Any other value is BT_ERR_ARG before any launch ("operand" in bt_last_error()).
- * The fp32 and dropout entry points above never read the field. */
+ * The fp32 and dropout entry points above never read the field.
+ * BT_OPERAND_BF16X3 (3; DESIGN.md section 25, "32-high") multiplies fp32 values as split bfloat16 operands.  For an fp32 value a:
+ *   hi = bf16(a), rounded to nearest even;  lo = bf16(a - hi), the subtraction being exact in fp32;
+ *   where hi is not finite (a is +-inf or NaN, or a finite value that rounds to inf) lo = 0 -- otherwise inf would meet -inf in
+ *   the partial products and turn an overflow into NaN (3.4e38 - bf16(3.4e38) is -inf).
+ * Every product listed above becomes A_lo B_hi + A_hi B_lo + A_hi B_hi; the lo lo term is dropped.  Per accumulator and per k-step
+ * of 16 the three v_mfma_f32_32x32x16_bf16 are issued in that order, the small terms first, into the one fp32 accumulator.  The
+ * operands that the other formats round in registers (P after mask and 1 / (1 - p), dS, the own side's fragments) are split in
+ * registers.  About 2^-17 of an operand is kept where bfloat16 keeps 2^-9; the exponent range is fp32's: no range flag, no loss
+ * scale, no fallback.  Everything else, every summation order, the workspace and everything that is kept are those of the other
+ * formats.  Value 2 is unassigned and refused. */
 #define BT_OPERAND_F16 0
 #define BT_OPERAND_BF16 1
+#define BT_OPERAND_BF16X3 3
 size_t bt_train_workspace_bytes_mixed(int unit, int backward, int B, int T, int dim, int hidden, int with_dropout);
 int bt_train_forward_mixed(void* stream, int unit, const bt_train_args* a, const bt_train_dropout* dropout_or_null);
 int bt_train_backward_mixed(void* stream, int unit, const bt_train_args* a, const bt_train_dropout* dropout_or_null);
@@ -736,8 +747,9 @@ int bt_train_backward_mixed(void* stream, int unit, const bt_train_args* a, cons
  *   form 2: C = A^T B, A [K, M], B [K, N]   (dW = dY^T A; K = the summed rows, taken BT_TRAIN_DW_ROWS at a time and the chunks
  *                                            added into C in chunk order, one launch per chunk) */
 int bt_train_matmul_mixed(void* stream, int form, const float* A, const float* B, int M, int N, int K, float* C);
-/* The GEMM of either training route (mixed = 0: the fp32 MFMA kernels, 1: the fp16 ones, 2: the same on bfloat16 operands -- 1 +
- * BT_OPERAND_*; anything else is BT_ERR_ARG ahead of every other check) through the host helpers
+/* The GEMM of either training route (mixed = 0: the fp32 MFMA kernels, 1: the fp16 ones, 2: the same on bfloat16 operands, 4: on
+ * split bfloat16 operands -- 1 + BT_OPERAND_*; anything else, 3 included, is BT_ERR_ARG ahead of every other check) through the
+ * host helpers
  * the unit calls launch it with.  A diagnostic for the trunk's units, and PRODUCTION for the frontend's projection:
  * bt_front_forward / bt_front_backward (BT_FRONT_LINEAR) call forms 0, 1 and 2 with their own `mixed` and size their workspace with
  * bt_train_matmul_workspace_bytes, so what this entry computes, and in which order it sums, is part of section 17's contract.
@@ -760,7 +772,7 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
  * BT_TRAIN_ATTN_BLOCK queries on the fp32 route, of 32 on the mixed one).  qkv [B T, 3 dim] is what the sweeps read after RoPE:
  * q | k | v, head h in columns 32 h of each section; dim a multiple of 32 from 32 to 1024, B <= 65535, B T <= 2^22; qkv, O, dO
  * and dqkv 16-byte aligned.  dropout (or NULL, or p == 0: none) is the BT_DROP_ATTN_P site.  `mixed` as bt_train_matmul's: 0, 1
- * (fp16 operands) or 2 (bfloat16 operands), anything else is BT_ERR_ARG ahead of every other check.
+ * (fp16 operands), 2 (bfloat16 operands) or 4 (split bfloat16 operands), anything else is BT_ERR_ARG ahead of every other check.
  *   backward == 0: writes O [B T, dim] (before the gate; the dropped output with dropout) and lse [B T, dim / 32]
  *   backward != 0: reads dO [B T, dim], lse and delta [B T, dim / 32] (= sum_d dO O per row and head), runs the dK / dV sweep and
  *                  the dQ sweep and writes every element of dqkv [B T, 3 dim], the gradient before the backward RoPE
@@ -804,7 +816,7 @@ int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int 
 #define BT_FRONT_SWAP 3
 typedef struct {
   int32_t B, T, F, C, dim, mixed;
-  int32_t operand;   /* read only when mixed == 1: BT_OPERAND_F16 or BT_OPERAND_BF16 (section 24) */
+  int32_t operand;   /* read only when mixed == 1: BT_OPERAND_F16, _BF16 (section 24) or _BF16X3 (section 25) */
   int32_t reserved2;
   const float* w; const float* b;
   const float* bn_w; const float* bn_b; const float* bn_mean; const float* bn_var;
@@ -844,7 +856,7 @@ int bt_front_backward(void* stream, int unit, const bt_front_args* a);
  * calls above refuse and every NULL among the required pointers; the workspace query then returns 0. */
 typedef struct {
   int32_t B, T, F, C, mixed;
-  int32_t operand;   /* read only when mixed == 1: BT_OPERAND_F16 or BT_OPERAND_BF16 (section 24) */
+  int32_t operand;   /* read only when mixed == 1: BT_OPERAND_F16, _BF16 (section 24) or _BF16X3 (section 25) */
   int32_t reserved2, reserved3;
   const float* w;
   const float* bn_w; const float* bn_b; float* bn_mean; float* bn_var; int64_t* bn_tracked;
@@ -891,9 +903,16 @@ int bt_front_bn_backward(void* stream, int unit, const bt_front_bn_args* a);
  * same products to bfloat16 (to nearest even, NaN stays NaN, nothing overflows by rounding) on v_mfma_f32_32x32x16_bf16, the
  * weight image holding bfloat16 in the same bytes, BT_FRONT_LINEAR calling bt_train_matmul with mixed = 2; any other value is
  * BT_ERR_ARG before any launch ("operand" in bt_last_error()).  With mixed == 0 the field is ignored.  The workspace queries do
- * not depend on it. */
+ * not depend on it.
+ * BT_OPERAND_BF16X3 (section 25) runs the same products on split bfloat16 operands, as described at the define: the packing
+ * launch writes a hi and a lo weight image, activations and G are split while staged, BT_FRONT_LINEAR calls bt_train_matmul
+ * with mixed = 4.  Because the image doubles, its workspace comes from the two *_x3 queries: the parameters of the fp32 queries,
+ * the fp32 size plus both images, 0 for unsupported shapes and for units that have no mixed form.  A workspace smaller than that
+ * is BT_ERR_WORKSPACE.  The *_mixed queries and their values are unchanged. */
 size_t bt_front_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C, int dim);
 size_t bt_front_bn_workspace_bytes_mixed(int unit, int backward, int B, int T, int F, int C);
+size_t bt_front_workspace_bytes_x3(int unit, int backward, int B, int T, int F, int C, int dim);
+size_t bt_front_bn_workspace_bytes_x3(int unit, int backward, int B, int T, int F, int C);
 
 /* ---- training: the optimiser step (csrc/optim.hip) ------------------------------------------------------
  * Multi-tensor AdamW with torch.optim.AdamW's default semantics (decoupled decay, no amsgrad, no maximize), all fp32.  With
