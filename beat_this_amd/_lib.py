@@ -22,9 +22,12 @@ SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "at
 HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "train_front_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
-OPERAND_F16, OPERAND_BF16 = 0, 1   # BT_OPERAND_*: the operand format of a 16-mixed call (``operand`` of the three training structs)
-OPERANDS = {"fp16": OPERAND_F16, "bf16": OPERAND_BF16}
-OPERAND_BF16X3 = 3                 # BT_OPERAND_BF16X3: the split operands of a "32-high" call (no choice of a 16-mixed part: not in OPERANDS)
+# The operand formats of the training route (``operand`` of the three training structs): name -> (BT_OPERAND_*, the suffix of the
+# bt_front[_bn]_workspace_bytes query that sizes a frontend call on it).  `mixed` of bt_train_matmul / bt_train_attention is 1 + the value.
+OPERAND_FORMATS = {"fp16": (0, "_mixed"), "bf16": (1, "_mixed"), "bf16x3": (3, "_x3")}
+OPERAND_F16, OPERAND_BF16, OPERAND_BF16X3 = (OPERAND_FORMATS[k][0] for k in ("fp16", "bf16", "bf16x3"))
+# the choice of a 16-mixed part ("bf16x3" is the "32-high" precision, no operand of "16-mixed")
+OPERANDS = {k: v for k, (v, _) in OPERAND_FORMATS.items() if k != "bf16x3"}
 ABI_VERSION = 600   # BT_ABI_VERSION of include/beat_this_amd.h this binding was written against
 PREC_F32, PREC_HALF, PREC_F32X3 = 0, 1, 3   # (2 was the withdrawn e4m3 experiment)
 OPT_X3_ATTN_P16, OPT_X3_GEMM_FP8, OPT_WS_GUARD = 1, 2, 3   # BT_OPT_* (bt_engine_set_option)

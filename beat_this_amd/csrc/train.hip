@@ -105,12 +105,11 @@ __global__ __launch_bounds__(256) void gemm_drop_kernel(const GemmP p, const Dro
 
 unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
-// What every launch helper below needs to know of the call it serves: the stream, the route (mixed: 0 = the fp32 kernels of this
-// file, MIXED_F16 / MIXED_BF16 / MIXED_BF16X3 = the MFMA kernels of train_mixed.inc on fp16 / bfloat16 / split bfloat16 operands),
-// and the dropout of the call
-// (null: none, otherwise p > 0).
-constexpr int MIXED_F16 = 1 + BT_OPERAND_F16, MIXED_BF16 = 1 + BT_OPERAND_BF16, MIXED_BF16X3 = 1 + BT_OPERAND_BF16X3;
-bool known_route(int mixed) { return mixed == 0 || mixed == MIXED_F16 || mixed == MIXED_BF16 || mixed == MIXED_BF16X3; }
+// What every launch helper below needs to know of the call it serves: the stream, the route (mixed: train_common.h's route_of:
+// 0 = the fp32 kernels of this file, else the MFMA kernels of train_mixed.inc on the operand format mixed - 1), and the dropout
+// of the call (null: none, otherwise p > 0).
+constexpr int MIXED_F16 = route_of(1, BT_OPERAND_F16);
+const char* const BAD_ROUTE = "mixed must be 0 (fp32), 1 (fp16 operands), 2 (bfloat16 operands) or 4 (split bfloat16 operands)";
 struct Launch {
   hipStream_t s;
   int mixed;
@@ -118,9 +117,7 @@ struct Launch {
   bool drop() const { return dp != nullptr; }
   DropSite site(int id) const { return drop_site(dp->p, dp->seed, dp->stream, id); }
   // the kernel of the call's route among the four forms of one launch
-  template <typename K> K pick(K f32, K f16, K bf16, K x3) const {
-    return mixed == MIXED_BF16X3 ? x3 : mixed == MIXED_BF16 ? bf16 : mixed ? f16 : f32;
-  }
+  template <typename K> K pick(K f32, K f16, K bf16, K x3) const { return pick_route(mixed, f32, f16, bf16, x3); }
 };
 constexpr int NO_SITE = -1;   // linear_fwd: a result that no dropout site covers
 
@@ -130,8 +127,7 @@ dim3 gemm_grid(const Launch& lc, const GemmP& p, int chunks) {
 }
 
 template <bool AT, bool BT> void launch_gemm(const Launch& lc, const GemmP& p, int chunks) {
-  const auto kernel = lc.pick(gemm_kernel<AT, BT>, mx_gemm_kernel<_Float16, AT, BT>, mx_gemm_kernel<__bf16, AT, BT>,
-                              mx_gemm_kernel<bf16x3, AT, BT>);
+  const auto kernel = lc.pick(gemm_kernel<AT, BT>, BT_FOR_OPERANDS(mx_gemm_kernel, AT, BT));
   hipLaunchKernelGGL(kernel, gemm_grid(lc, p, chunks), dim3(256), 0, lc.s, p);
 }
 
@@ -143,8 +139,7 @@ void linear_fwd(const Launch& lc, const float* A, const float* W, const float* b
   p.A = A; p.lda = K; p.B = W; p.ldb = K; p.M = (int)M; p.N = N; p.K = K; p.kchunk = K;
   p.C = Y; p.ldc = N; p.bias = bias; p.resid = resid; p.ldr = N; p.accum = accum; p.act = act; p.ldact = N;
   if (!lc.drop() || site == NO_SITE) return launch_gemm<false, false>(lc, p, 1);
-  const auto kernel = lc.pick(gemm_drop_kernel, mx_gemm_drop_kernel<_Float16>, mx_gemm_drop_kernel<__bf16>,
-                              mx_gemm_drop_kernel<bf16x3>);
+  const auto kernel = lc.pick(gemm_drop_kernel, BT_FOR_OPERANDS(mx_gemm_drop_kernel));
   hipLaunchKernelGGL(kernel, gemm_grid(lc, p, 1), dim3(256), 0, lc.s, p, lc.site(site), drop_act);
 }
 
@@ -691,12 +686,10 @@ int finish(const char* fn) {
 void attn_fwd_sweep(const Launch& lc, const float* qkv, int B, int T, int D, float* O, float* lse) {
   const dim3 grid(blocks_of(T, lc.mixed ? XB : AB), D / 32, B), block(lc.mixed ? 64 : AB);
   if (!lc.drop()) {
-    const auto kernel = lc.pick(attn_fwd_kernel, mx_attn_fwd_kernel<_Float16>, mx_attn_fwd_kernel<__bf16>,
-                                mx_attn_fwd_kernel<bf16x3>);
+    const auto kernel = lc.pick(attn_fwd_kernel, BT_FOR_OPERANDS(mx_attn_fwd_kernel));
     hipLaunchKernelGGL(kernel, grid, block, 0, lc.s, qkv, T, D, O, lse);
   } else {
-    const auto kernel = lc.pick(attn_fwd_drop_kernel, mx_attn_fwd_drop_kernel<_Float16>, mx_attn_fwd_drop_kernel<__bf16>,
-                                mx_attn_fwd_drop_kernel<bf16x3>);
+    const auto kernel = lc.pick(attn_fwd_drop_kernel, BT_FOR_OPERANDS(mx_attn_fwd_drop_kernel));
     hipLaunchKernelGGL(kernel, grid, block, 0, lc.s, qkv, T, D, O, lse, lc.site(BT_DROP_ATTN_P));
   }
 }
@@ -707,18 +700,14 @@ void attn_bwd_sweeps(const Launch& lc, const float* qkv, const float* dO, const 
                      float* dqkv) {
   const dim3 grid(blocks_of(T, lc.mixed ? XB : AB), D / 32, B), block(lc.mixed ? 64 : AB);
   if (!lc.drop()) {
-    const auto dkv = lc.pick(attn_dkv_kernel, mx_attn_dkv_kernel<_Float16>, mx_attn_dkv_kernel<__bf16>,
-                             mx_attn_dkv_kernel<bf16x3>);
-    const auto dq = lc.pick(attn_dq_kernel, mx_attn_dq_kernel<_Float16>, mx_attn_dq_kernel<__bf16>,
-                            mx_attn_dq_kernel<bf16x3>);
+    const auto dkv = lc.pick(attn_dkv_kernel, BT_FOR_OPERANDS(mx_attn_dkv_kernel));
+    const auto dq = lc.pick(attn_dq_kernel, BT_FOR_OPERANDS(mx_attn_dq_kernel));
     hipLaunchKernelGGL(dkv, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv);
     hipLaunchKernelGGL(dq, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv);
   } else {
     const DropSite pd = lc.site(BT_DROP_ATTN_P);
-    const auto dkv = lc.pick(attn_dkv_drop_kernel, mx_attn_dkv_drop_kernel<_Float16>, mx_attn_dkv_drop_kernel<__bf16>,
-                             mx_attn_dkv_drop_kernel<bf16x3>);
-    const auto dq = lc.pick(attn_dq_drop_kernel, mx_attn_dq_drop_kernel<_Float16>, mx_attn_dq_drop_kernel<__bf16>,
-                            mx_attn_dq_drop_kernel<bf16x3>);
+    const auto dkv = lc.pick(attn_dkv_drop_kernel, BT_FOR_OPERANDS(mx_attn_dkv_drop_kernel));
+    const auto dq = lc.pick(attn_dq_drop_kernel, BT_FOR_OPERANDS(mx_attn_dq_drop_kernel));
     hipLaunchKernelGGL(dkv, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv, pd);
     hipLaunchKernelGGL(dq, grid, block, 0, lc.s, qkv, dO, lse, delta, T, D, dqkv, pd);
   }
@@ -970,9 +959,8 @@ size_t bt_train_workspace_bytes_mixed(int unit, int backward, int B, int T, int 
 // what the two entry points below refuse ahead of everything the fp32 ones check; *mixed: the route of bt_train_args.operand
 static const char* check_mixed_call(int unit, const bt_train_args* ap, int* mixed) {
   if (unit != BT_UNIT_ATTN && unit != BT_UNIT_FF) return "unit must be BT_UNIT_ATTN or BT_UNIT_FF";
-  if (ap && ap->operand != BT_OPERAND_F16 && ap->operand != BT_OPERAND_BF16 && ap->operand != BT_OPERAND_BF16X3)
-    return "operand must be BT_OPERAND_F16, BT_OPERAND_BF16 or BT_OPERAND_BF16X3";
-  *mixed = ap ? 1 + ap->operand : MIXED_F16;
+  if (ap && !known_operand(ap->operand)) return "operand must be BT_OPERAND_F16, BT_OPERAND_BF16 or BT_OPERAND_BF16X3";
+  *mixed = ap ? route_of(1, ap->operand) : MIXED_F16;
   return nullptr;
 }
 
@@ -1019,7 +1007,7 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
                     const float* bias, const float* resid, int accum, float* act, const bt_train_dropout* dp, int site,
                     int drop_act, void* ws, size_t ws_bytes) {
   const char* fn = "bt_train_matmul";
-  if (!known_route(mixed)) return fail(fn, "mixed must be 0 (fp32), 1 (fp16 operands), 2 (bfloat16 operands) or 4 (split bfloat16 operands)");
+  if (!known_route(mixed)) return fail(fn, BAD_ROUTE);
   if (!A || !B || !C) return fail(fn, "null argument");
   if (form < 0 || form > 2) return fail(fn, "form must be 0 (A W^T), 1 (dY W) or 2 (dY^T A)");
   if (const char* e = check_mnk(M, N, K)) return fail(fn, e);
@@ -1046,7 +1034,7 @@ int bt_train_matmul(void* stream, int mixed, int form, const float* A, const flo
 int bt_train_attention(void* stream, int mixed, int backward, int B, int T, int dim, const float* qkv,
                        const bt_train_dropout* dp, float* O, float* lse, const float* dO, const float* delta, float* dqkv) {
   const char* fn = "bt_train_attention";
-  if (!known_route(mixed)) return fail(fn, "mixed must be 0 (fp32), 1 (fp16 operands), 2 (bfloat16 operands) or 4 (split bfloat16 operands)");
+  if (!known_route(mixed)) return fail(fn, BAD_ROUTE);
   if (const char* e = check_width(dim)) return fail(fn, e);
   if (B < 1 || B > 65535 || T < 1 || (long)B * T > (1L << 22)) return fail(fn, "need 1 <= B <= 65535, T >= 1 and B T <= 2^22");
   if (!qkv || !lse || (backward ? !dO || !delta || !dqkv : !O)) return fail(fn, "null argument");

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "../../include/beat_this_amd.h"   // BT_OPERAND_*
 #include "dropout.h"
 
 namespace {
@@ -48,6 +49,21 @@ template <> struct Operand<bf16x3> : Operand<__bf16> {
 template <typename E> using el16 = typename Operand<E>::el;
 template <typename E> using h16x4 = typename Operand<E>::x4;
 template <typename E> using h16x8 = typename Operand<E>::x8;
+template <typename E> constexpr int operand_images = Operand<E>::NI;
+
+// The list of the formats for the host code of train.hip and train_front.hip (a new one: a specialisation above, an entry in
+// known_operand, BT_FOR_OPERANDS and pick_route, and a branch of train_front.hip's launch_conv).  A call's route is 0 for the
+// fp32 kernels, else 1 + BT_OPERAND_*: the `mixed` of bt_train_matmul / bt_train_attention.
+constexpr bool known_operand(int operand) { return operand == BT_OPERAND_F16 || operand == BT_OPERAND_BF16 || operand == BT_OPERAND_BF16X3; }
+constexpr int route_of(int mixed, int operand) { return mixed ? 1 + operand : 0; }
+constexpr bool known_route(int route) { return route == 0 || known_operand(route - 1); }
+// the instantiations of a template K<E, ...> over the formats, in the order pick_route takes them
+#define BT_FOR_OPERANDS(K, ...) K<_Float16, ##__VA_ARGS__>, K<__bf16, ##__VA_ARGS__>, K<bf16x3, ##__VA_ARGS__>
+// what belongs to a known route among the fp32 form and the three of BT_FOR_OPERANDS
+template <typename K> K pick_route(int route, K f32, K f16, K bf16, K x3) {
+  return route == route_of(1, BT_OPERAND_BF16X3) ? x3 : route == route_of(1, BT_OPERAND_BF16) ? bf16 : route ? f16 : f32;
+}
+
 // the NI images of four / eight consecutive elements
 template <typename E> struct Img4 { h16x4<E> v[Operand<E>::NI]; };
 template <typename E> struct Img8 { h16x8<E> v[Operand<E>::NI]; };

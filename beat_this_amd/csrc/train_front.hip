@@ -472,7 +472,7 @@ struct Layout {
 // of the workspace); mixed (section 19) adds the conv unit's fp16 weight image (Cout 6 Cin halves; the forward's, or the
 // backward-data's transposed one) `images` times: one for fp16 or bfloat16 operands, the hi and the lo image for the split ones
 // of section 25.
-int images_of(int mixed, int operand) { return !mixed ? 0 : operand == BT_OPERAND_BF16X3 ? 2 : 1; }
+int images_of(int mixed, int operand) { return pick_route(route_of(mixed, operand), 0, BT_FOR_OPERANDS(operand_images)); }
 Layout layout(int unit, bool backward, bool batch, int images, long BT, int F, int C, int dim) {
   Layout L{};
   size_t at = 0;
@@ -567,8 +567,7 @@ const char* check_mixed(int unit, int mixed, int operand, bool linear_too) {
   if (mixed != 0 && mixed != 1) return "mixed must be 0 or 1";
   if (mixed && unit != BT_FRONT_CONV && !(linear_too && unit == BT_FRONT_LINEAR))
     return "mixed = 1 belongs to BT_FRONT_CONV and (bt_front_args) BT_FRONT_LINEAR: the other units have no product worth an MFMA";
-  if (mixed && operand != BT_OPERAND_F16 && operand != BT_OPERAND_BF16 && operand != BT_OPERAND_BF16X3)
-    return "mixed = 1: operand must be BT_OPERAND_F16, BT_OPERAND_BF16 or BT_OPERAND_BF16X3";
+  if (mixed && !known_operand(operand)) return "mixed = 1: operand must be BT_OPERAND_F16, BT_OPERAND_BF16 or BT_OPERAND_BF16X3";
   return nullptr;
 }
 
@@ -758,7 +757,8 @@ void launch_conv_as(hipStream_t s, ConvP p, float* wimg, dim3 grid) {
   const auto kernel = wimg ? conv_gemm_mixed_kernel<E, MODE> : conv_gemm_kernel<MODE>;
   hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, p);
 }
-// ... with the operand format of the call (read only where wimg is given)
+// ... with the operand format of the call (read only where wimg is given).  The chain is written out, not pick_route over
+// BT_FOR_OPERANDS: this order of first use is the order of the conv kernels in the code object.
 template <int MODE>
 void launch_conv(hipStream_t s, const Call& c, const ConvP& p, float* wimg, dim3 grid) {
   if (wimg && c.operand == BT_OPERAND_BF16X3) launch_conv_as<bf16x3, MODE>(s, p, wimg, grid);
@@ -809,7 +809,7 @@ void conv_backward(hipStream_t s, const Call& c, const Layout& L) {
 }
 
 // the projection's `mixed` of bt_train_matmul: 0, or 1 + the operand format
-int matmul_route(const Call& c) { return c.mixed ? 1 + c.operand : 0; }
+int matmul_route(const Call& c) { return route_of(c.mixed, c.operand); }
 
 int linear_forward(void* stream, const Call& c, const Layout& L) {
   float* ws = (float*)c.ws;

@@ -64,15 +64,12 @@ _FAMILY = {(False, True): "", (False, False): "_dropout", (True, True): "_mixed"
 
 
 def _operand(mixed) -> int:
-    """BT_OPERAND_* of a ``mixed`` value: False (fp32: the field is not read), True or "fp16", "bf16" (section 24) or "bf16x3"
-    (section 25: the split operands of "32-high")"""
-    if mixed is True or not mixed:
-        return _lib.OPERAND_F16
-    if mixed == "bf16x3":
-        return _lib.OPERAND_BF16X3
-    if mixed not in _lib.OPERANDS:
+    """BT_OPERAND_* of a ``mixed`` value, by _lib.OPERAND_FORMATS: False (fp32: the field is not read), True or "fp16", "bf16"
+    (section 24) or "bf16x3" (section 25: the split operands of "32-high")"""
+    name = "fp16" if mixed is True or not mixed else mixed
+    if name not in _lib.OPERAND_FORMATS:
         raise ValueError(f"mixed must be False, True, 'fp16', 'bf16' or 'bf16x3', got {mixed!r}")
-    return _lib.OPERANDS[mixed]
+    return _lib.OPERAND_FORMATS[name][0]
 
 
 def _run(backward: bool, unit: int, a: _lib.TrainArgs, device, drop=None, mixed=False) -> None:
@@ -294,7 +291,7 @@ def _front_call(backward: bool, unit: int, a, device) -> None:
     batch = isinstance(a, _lib.FrontBnArgs)
     family = "bt_front_bn" if batch else "bt_front"
     shape = (a.B, a.T, a.F, a.C) if batch else (a.B, a.T, a.F, a.C, a.dim)
-    query = "" if not a.mixed else "_x3" if a.operand == _lib.OPERAND_BF16X3 else "_mixed"   # (the split format has two weight images)
+    query = dict(_lib.OPERAND_FORMATS.values())[a.operand] if a.mixed else ""   # (BT_OPERAND_* -> suffix: the split format has two weight images)
     need = getattr(_lib.lib(), f"{family}_workspace_bytes{query}")(unit, int(backward), *shape)
     if need == 0:
         check_front_limits(a.B, a.T)

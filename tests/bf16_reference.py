@@ -9,6 +9,9 @@ route_grads.py serves unchanged:
 ``e_ref_bf16`` of a case is the worst relative distance of the autocast oracle's gradients from the fp64 oracle; the gate is the
 project's ``MIXED_GATE`` = 2: the device within 2 x e_ref_bf16 on every gradient key, ``y`` and the logits.  The cases are
 route_cases.py's, with its inputs; the fp64 truth does not depend on the operand format.
+
+This module and tests/x3_reference.py have one shape, which tests/test_gpu_train_formats.py runs over: the constants below, the
+case constructors, ``case["yard"]`` (the yardstick's own run) with ``case["e"]`` (its error), and ``gate``.
 """
 import contextlib
 
@@ -20,6 +23,9 @@ import route_grads as G
 import route_reference as REF
 from route_harness import MIXED_GATE as GATE
 
+FORMAT = "bf16"                   # the name in _lib.OPERAND_FORMATS: ``mixed`` of model.backward, ``operand`` of the harness
+PRECISION = ("16-mixed", "bf16")  # the arguments of set_train_precision / set_frontend_precision that put a part on it
+LABEL, RECORD, E_NAME = "bf16", "bf16", "e_ref_bf16"   # in printed lines; the prefix of the report records; the field of case["e"] in them
 _CASES = {}
 
 
@@ -71,13 +77,13 @@ def bfloat16():
 
 
 def yardstick(run):
-    """run(dtype, on, autocast) -> a ``*_grads`` result at loss scale 1.  -> dict(truth (fp64 oracle), auto (the oracle under
-    bfloat16 autocast), twin (the contract in fp32), e_ref = e_ref_bf16)"""
+    """run(dtype, on, autocast) -> a ``*_grads`` result at loss scale 1.  -> dict(truth (fp64 oracle), yard (the oracle under
+    bfloat16 autocast), twin (the contract in fp32), e = e_ref_bf16)"""
     truth = run(torch.float64, None, False)
     with bfloat16():
         auto = run(torch.float32, None, True)
         twin = run(torch.float32, True, False)
-    return dict(truth=truth, auto=auto, twin=twin, e_ref=G.worst(auto, truth)[0])
+    return dict(truth=truth, yard=auto, twin=twin, e=G.worst(auto, truth)[0])
 
 
 def _case(key, make):
@@ -88,7 +94,7 @@ def _case(key, make):
 
 # ---- the trunk's units and the trunk (the cases of section 16) ----------------------------------------------------------------------
 def unit_case(kind, D, B, T, drop_stream=None):
-    """-> dict(sd, pfx, x, g, masks or None, truth, auto, twin, e_ref): ``RC.unit_case``'s inputs under the bfloat16 yardstick"""
+    """-> dict(sd, pfx, x, g, masks or None, truth, yard, twin, e): ``RC.unit_case``'s inputs under the bfloat16 yardstick"""
     def make():
         sd, pfx = RC.trunk_state_dict(D, RC.UNIT_DIMS[D]), RC.PFX[kind]
         x, g = RC.unit_inputs(kind, D, B, T)
@@ -99,7 +105,7 @@ def unit_case(kind, D, B, T, drop_stream=None):
 
 
 def trunk_case():
-    """``RC.TRUNK`` with ``RC.trunk_batch`` and the shift-tolerant loss -> dict(sd, h, beat, down, mask, truth, auto, twin, e_ref)"""
+    """``RC.TRUNK`` with ``RC.trunk_batch`` and the shift-tolerant loss -> dict(sd, h, beat, down, mask, truth, yard, twin, e)"""
     def make():
         c = RC.TRUNK
         sd = RC.trunk_state_dict(c["D"], c["ff_mult"], c["L"])
@@ -163,10 +169,12 @@ def outputs_of(truth):
     return [k for k in ("y", "beat", "downbeat") if k in truth]
 
 
-def gate(name, got, case, report=None):
-    """every gradient key of the truth, ``y`` and the logits within GATE x e_ref_bf16 of the fp64 truth and finite.  Prints every
-    figure before it asserts -> the worst distance in e_ref_bf16"""
-    truth, e_ref = case["truth"], case["e_ref"]
+def gate(name, got, case, report=None, capped=()):
+    """every gradient key of the truth, ``y`` and the logits within GATE x e_ref_bf16 of the fp64 truth and finite (``capped``:
+    x3_reference.gate's; this format has no cap, so no key can be gated at it alone).  Prints every figure before it asserts ->
+    the worst distance in e_ref_bf16"""
+    truth, e_ref = case["truth"], case["e"]
+    assert not capped, f"{name}: bfloat16 has no cap to gate {capped} at"
     keys = G.grad_keys(truth) + outputs_of(truth)
     assert e_ref > 0 and e_ref < float("inf"), f"{name}: e_ref_bf16 = {e_ref}"
     missing = [k for k in keys if k not in got]

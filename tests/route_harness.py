@@ -1,7 +1,8 @@
-"""The device side of the training route's GPU tests (test_gpu_backward, _dropout, _mixed, _frontend_backward, _batch_stats,
-_front_mixed, _front_dropout, _train_route, _finetune*, _ema, _optim): random inputs, the bit comparison, the run under both
-poison bytes, the model factory, the whole-model backward and the 16-mixed gate.  Where the tests' own copies differed in
-strength, this is the strongest of them.  The comparisons work on CPU tensors too (tests/test_route_harness.py)."""
+"""The device side of the training route's GPU tests (test_gpu_backward, _dropout, _mixed, _train_formats, _bf16, _train_high,
+_frontend_backward, _batch_stats, _front_mixed, _front_dropout, _train_route, _finetune*, _ema, _optim): random inputs, the bit
+comparison, the run under both poison bytes, the model factory, the whole-model backward, one frontend unit and one trunk unit
+through the C ABI on any operand format, the raw GEMM, the fit-and-resume run and the 16-mixed gate.  Where the tests' own copies
+differed in strength, this is the strongest of them.  The comparisons work on CPU tensors too (tests/test_route_harness.py)."""
 import ctypes as C
 
 import numpy as np
@@ -140,9 +141,11 @@ def model_device(m, x, beat, down, mask, scale=1.0):
 
 
 # ---- one frontend unit through the C ABI ----------------------------------------------------------------------------------------------
-def abi_front_unit(sd, unit, dims, B, T, x, gy, poison, mixed=False, batch=False):
+def abi_front_unit(sd, unit, dims, B, T, x, gy, poison, operand=None, batch=False, *, mixed=None):
     """Forward + backward of one frontend unit through bt_front_* (running statistics) or, with ``batch``, bt_front_bn_* (batch
-    statistics), fp32 or 16-mixed.  unit, dims: "stem", None; "conv", (key prefix, F, C); "linear", (F, C, dim); "swap", (F, C).
+    statistics).  ``operand``: None = fp32, else a format name of _lib.OPERAND_FORMATS: the struct's ``mixed`` and ``operand`` and
+    the workspace query follow from it (``mixed`` = False beside a format: the call that has to ignore its operand).
+    unit, dims: "stem", None; "conv", (key prefix, F, C); "linear", (F, C, dim); "swap", (F, C).
     Every input, parameter, running buffer, saved tensor, output, gradient and the workspaces are ``Guarded`` buffers filled with
     ``poison``; their bands are checked once, after the backward.
     -> {"y", "save_pre" (conv), "x" (= gx), <state dict key>: gradient}; with ``batch`` a pair of that and {<key>: running
@@ -174,7 +177,10 @@ def abi_front_unit(sd, unit, dims, B, T, x, gy, poison, mixed=False, batch=False
     a = L.FrontBnArgs(B=B, T=T, F=F_, C=C_) if batch else L.FrontArgs()
     if not batch:
         a.B, a.T, a.F, a.C, a.dim = B, T, F_, C_, dim
+    mixed = operand is not None if mixed is None else mixed
     a.mixed = int(mixed)
+    value, suffix = L.OPERAND_FORMATS[operand] if operand is not None else (0, "")
+    a.operand = value
     a.x, a.gy = guarded(xs, x).ptr(), guarded(ys, gy).ptr()
     outs = {"y": guarded(ys), "x": guarded(xs)}
     a.y, a.gx = outs["y"].ptr(), outs["x"].ptr()
@@ -202,15 +208,11 @@ def abi_front_unit(sd, unit, dims, B, T, x, gy, poison, mixed=False, batch=False
             save = "save1" if f == "bn1" else "save"
             setattr(a, save + "_mean", guarded(n).ptr())
             setattr(a, save + "_rstd", guarded(n).ptr())
-    lib = L.lib()
-    if batch:
-        size = lambda query, backward: query(code, backward, B, T, F_, C_)
-        query, plain = (lib.bt_front_bn_workspace_bytes_mixed if mixed else lib.bt_front_bn_workspace_bytes), None
-        calls = (lib.bt_front_bn_forward, lib.bt_front_bn_backward)
-    else:
-        size = lambda query, backward: query(code, backward, B, T, F_, C_, dim)
-        query, plain = (lib.bt_front_workspace_bytes_mixed, lib.bt_front_workspace_bytes) if mixed else (lib.bt_front_workspace_bytes, None)
-        calls = (lib.bt_front_forward, lib.bt_front_backward)
+    lib, family = L.lib(), "bt_front_bn" if batch else "bt_front"
+    size = lambda query, backward: query(code, backward, B, T, F_, C_, *(() if batch else (dim,)))
+    query = getattr(lib, f"{family}_workspace_bytes{suffix if mixed else ''}")
+    plain = lib.bt_front_workspace_bytes if mixed and not batch else None
+    calls = (getattr(lib, family + "_forward"), getattr(lib, family + "_backward"))
     after = None
     for backward, fn in enumerate(calls):
         n = size(query, backward)
@@ -226,6 +228,271 @@ def abi_front_unit(sd, unit, dims, B, T, x, gy, poison, mixed=False, batch=False
     assert_intact(*[(f"{unit} buffer {i}", g) for i, g in enumerate(keep)])
     res = {k: g.t.clone() for k, g in outs.items()}
     return (res, after) if batch else res
+
+
+# ---- one unit of the trunk through the C ABI ----------------------------------------------------------------------------------------
+FIELDS = dict(attn=dict(gamma="norm.gamma", w1="to_qkv.weight", w2="to_gates.weight", b2="to_gates.bias", w3="to_out.0.weight"),
+              ff=dict(gamma="net.0.gamma", w1="net.1.weight", b1="net.1.bias", w2="net.4.weight", b2="net.4.bias"))
+
+
+def unit_state_dict(D, ff_mult=2):
+    """the ``lively`` weights of a 2-layer trunk of width D and hidden width ff_mult D (a state dict only: the engine's frontend
+    cannot be built at D = 96, ff_mult 2, and the unit calls need nothing of it but the rotary table, which does not depend on the
+    width)"""
+    return state_dict(dict(transformer_dim=D, ff_mult=ff_mult, n_layers=2), 3, "lively")
+
+
+class Plain:
+    def __init__(self, shape, dtype, data=None):
+        self.t = torch.empty(shape, dtype=dtype, device=dev()) if data is None else data.to(dev(), dtype).contiguous()
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+
+class Unit:
+    """The operands of one attention / feed-forward call (layer 1 of unit_state_dict), optionally in guarded buffers filled
+    with ``poison``; ``run`` does the forward and the backward and returns the outputs by state-dict key"""
+
+    def __init__(self, kind, D, x, gy, residual, poison=None, ff_mult=2):
+        from beat_this_amd import _lib as L
+
+        self.L, self.kind, self.poison, self.keep = L, kind, poison, []
+        hp = dict(transformer_dim=64, ff_mult=2, n_layers=2)   # (the model that lends its rotary table: test_gpu_dropout's D = 64 one)
+        m, sd = make_model(hp, state_dict(hp, 3, "lively"), cache=("dropout", 64, 2, 3)), unit_state_dict(D, ff_mult)
+        self.sd, self.pfx = sd, f"transformer_blocks.layers.1.{0 if kind == 'attn' else 1}."
+        self.unit = L.UNIT_ATTN if kind == "attn" else L.UNIT_FF
+        Bn, T = x.shape[:2]
+        self.shape, self.hidden = (Bn, T, D), ff_mult * D
+        eng = m.engine()
+        eng.ensure_positions(T)
+        self.rope = eng.packed._rope_t
+        a = self.a = L.TrainArgs()
+        a.B, a.T, a.dim, a.hidden, a.rope_len, a.residual = Bn, T, D, self.hidden, eng.packed.desc.rope_len, int(residual)
+        a.rope = self.rope.data_ptr()
+        self.x, self.gy = self.buf((Bn, T, D), x), self.buf((Bn, T, D), gy)
+        a.x, a.gy = self.x.ptr(), self.gy.ptr()
+        self.params = {f: self.buf(sd[self.pfx + n].shape, sd[self.pfx + n]) for f, n in FIELDS[kind].items()}
+        self.outs = {"y": self.buf((Bn, T, D))}
+        if kind == "attn":
+            self.outs["save_o"], self.outs["save_lse"] = self.buf((Bn, T, D)), self.buf((Bn, T, D // 32))
+        self.grads = {"gx": self.buf((Bn, T, D))}
+        for f, g in self.params.items():
+            self.grads["g_" + f] = self.buf(g.t.shape)
+        for f, g in list(self.params.items()) + list(self.outs.items()) + list(self.grads.items()):
+            setattr(a, f, g.ptr())
+
+    def buf(self, shape, data=None, dtype=torch.float32):
+        if self.poison is None:
+            b = Plain(shape, dtype, data)
+        else:
+            b = Guarded(shape, dtype).fill(self.poison, data=None if data is None else data.to(dev()))
+        self.keep.append(b)
+        return b
+
+    def ws_bytes(self, backward, drop):
+        lib = self.L.lib()
+        query = lib.bt_train_workspace_bytes_dropout if drop is not None and drop[0] > 0 else lib.bt_train_workspace_bytes
+        return query(self.unit, backward, *self.shape, self.hidden)
+
+    def call(self, backward, drop, entry, ws_bytes=None):
+        """one entry point -> its return code.  entry "plain": bt_train_forward / _backward (drop must be None); "dropout": the
+        *_dropout ones with NULL (drop None) or (p, seed, stream)"""
+        L, lib = self.L, self.L.lib()
+        n = self.ws_bytes(backward, drop) if ws_bytes is None else ws_bytes
+        ws = self.buf((max(n, 1),), dtype=torch.uint8)
+        self.a.ws, self.a.ws_bytes = ws.ptr(), n
+        if entry == "plain":
+            assert drop is None
+            return (lib.bt_train_backward if backward else lib.bt_train_forward)(L.stream_ptr(dev()), self.unit, C.byref(self.a))
+        d = None if drop is None else C.byref(L.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2]))
+        fn = lib.bt_train_backward_dropout if backward else lib.bt_train_forward_dropout
+        return fn(L.stream_ptr(dev()), self.unit, C.byref(self.a), d)
+
+    def run(self, drop, entry="dropout"):
+        for backward in (0, 1):
+            self.L.check(self.call(backward, drop, entry))
+        torch.cuda.synchronize()
+        if self.poison is not None:
+            assert_intact(*[(f"{self.kind} buffer {i}", g) for i, g in enumerate(self.keep)])
+        res = {"y": self.outs["y"].t.clone(), "x": self.grads["gx"].t.clone()}
+        for f, n in FIELDS[self.kind].items():
+            res[self.pfx + n] = self.grads["g_" + f].t.clone()
+        for k in ("save_o", "save_lse"):
+            if k in self.outs:
+                res[k] = self.outs[k].t.clone()
+        return res
+
+
+class MixedUnit(Unit):
+    """Unit on the *_mixed entry points (drop: None or (p, seed, stream)); ``operand``: a format name of _lib.OPERAND_FORMATS for
+    bt_train_args.operand, None leaves the field as the struct is born (0: fp16)"""
+
+    def __init__(self, *args, operand=None, **kw):
+        super().__init__(*args, **kw)
+        if operand is not None:
+            self.a.operand = self.L.OPERAND_FORMATS[operand][0]
+
+    def ws_bytes(self, backward, drop):
+        return self.L.lib().bt_train_workspace_bytes_mixed(self.unit, backward, *self.shape, self.hidden, int(drop is not None))
+
+    def call(self, backward, drop, entry="mixed", ws_bytes=None):
+        L, lib = self.L, self.L.lib()
+        n = self.ws_bytes(backward, drop) if ws_bytes is None else ws_bytes
+        ws = self.buf((max(n, 1),), dtype=torch.uint8)
+        self.a.ws, self.a.ws_bytes = ws.ptr(), n
+        d = None if drop is None else C.byref(L.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2]))
+        fn = lib.bt_train_backward_mixed if backward else lib.bt_train_forward_mixed
+        return fn(L.stream_ptr(dev()), self.unit, C.byref(self.a), d)
+
+
+# ---- the raw GEMM on guarded buffers, and the shapes the exact-product tests walk -------------------------------------------------------
+EDGES = (1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200)   # the issue's sizes and the wave's 64-wide share of the 128-wide tile
+KS = (1, 15, 16, 17, 33, 64, 100)
+
+
+def guarded(arr, poison):
+    t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
+    return Guarded(t.shape, torch.float32).fill(poison, data=t.to(dev()))
+
+
+def matmul(mixed, form, a, b, M, N, K, poison):
+    """bt_train_matmul (``mixed``: 0, or 1 + BT_OPERAND_*) on guarded buffers (form 2 with its workspace) -> C as numpy"""
+    from beat_this_amd import _lib as L
+
+    lib = L.lib()
+    ga, gb, gc = guarded(a, poison), guarded(b, poison), Guarded((M, N), torch.float32).fill(poison)
+    n = lib.bt_train_matmul_workspace_bytes(form, M, N, K)
+    ws = Guarded((max(n, 1),), torch.uint8).fill(poison)
+    L.check(lib.bt_train_matmul(L.stream_ptr(dev()), mixed, form, ga.ptr(), gb.ptr(), M, N, K, gc.ptr(), None, None, 0, None, None, 0, 0,
+                                ws.ptr() if n else None, n))
+    torch.cuda.synchronize()
+    assert_intact(("A", ga), ("B", gb), ("C", gc), ("workspace", ws))
+    return gc.t.cpu().numpy()
+
+
+# ---- the frontend's shapes and the whole model of route_cases ------------------------------------------------------------------------------
+def conv_dims(i):
+    """conv unit i of the frontend -> (key prefix, F, C), the ``dims`` of abi_front_unit"""
+    return f"frontend.blocks.{i}.", 32 >> i, 32 << i
+
+
+def front_model(cache):
+    """the D = 64 model of route_cases.model_state_dict on the GPU, everything trainable"""
+    import route_cases as RC
+
+    return make_model(RC.HP, RC.model_state_dict("lively", True), frontend=True, freeze_freqs=True, cache=cache)
+
+
+def model_loss(m, batch, which=("beat", "downbeat")):
+    from beat_this_amd.model.loss import ShiftTolerantBCELoss
+
+    out = m(batch["spect"])
+    fn = ShiftTolerantBCELoss().to(dev())
+    return sum(fn(out[k], batch["truth_" + k].float(), batch["padding_mask"]) for k in which), out
+
+
+# ---- what the tests of the operand formats share (test_gpu_train_formats, test_gpu_bf16, test_gpu_train_high) ---------------------------
+def walk(form, seed0):
+    """(M, N, K, seed) over the tile edges: three of the N per M, all of them over the M; form 2 also with the summed rows on both
+    sides of a BT_TRAIN_DW_ROWS chunk"""
+    n = 0
+    for i, M in enumerate(EDGES):
+        for j in range(3):
+            N = EDGES[(i + 4 * j + form) % len(EDGES)]
+            for K in KS:
+                yield M, N, K, seed0 * form + n
+                n += 1
+    if form == 2:
+        for K in (1023, 1024, 1025):
+            yield 33, 129, K, K
+
+
+def unit_run(kind, operand, poison=None, drop=None, rows=slice(None)):
+    """the D = 64 unit with its residual on the (3, 130) inputs of the bit-identity tests (or ``rows`` of them), on ``operand``"""
+    x, g = randn(3, 130, 64, seed=51), randn(3, 130, 64, seed=52)
+    return MixedUnit(kind, 64, x[rows], g[rows], 1, poison=poison, operand=operand).run(drop)
+
+
+def both_parts(m, precision, operand=None):
+    """the trunk and the frontend of ``m`` on one precision (and operand)"""
+    return m.set_train_precision(precision, operand).set_frontend_precision(precision, operand)
+
+
+def switching():
+    """two models of the same weights, one never switched; -> (never, switched, run, x, the fp32 and the fp16 16-mixed results)"""
+    import route_cases as RC
+
+    fresh = lambda: make_model(RC.HP, RC.model_state_dict("init0"), frontend=True, freeze_freqs=True)
+    never, switched = fresh(), fresh()
+    x, beat, down, mask = RC.model_inputs(2, 33, True)
+    run = lambda m: model_device(m, x, beat, down, mask, 1024.0)
+    want32 = run(never)
+    want16 = run(both_parts(never, "16-mixed"))
+    return never, switched, run, x, want32, want16
+
+
+def inference_never_looks_at_the_switch(never, switched, x):
+    with torch.no_grad():
+        a, b = never(x.to(dev())), switched(x.to(dev()))
+    assert same_bits(a["beat"], b["beat"]) and same_bits(a["downbeat"], b["downbeat"])
+
+
+# ---- fit ------------------------------------------------------------------------------------------------------------------------------
+LR, WARMUP, EPOCHS = 2e-3, 2, 2
+
+
+def new_module():
+    from beat_this_amd import weights as W
+    from beat_this_amd.model.pl_module import PLBeatThis
+
+    pl = PLBeatThis(transformer_dim=64, n_layers=2, ff_mult=2, lr=LR, warmup_steps=WARMUP, max_epochs=EPOCHS, eval_trim_beats=0)
+    sd = W.random_state_dict(W.resolve_hparams(dict(transformer_dim=64, ff_mult=2, n_layers=2)), seed=3, style="lively")
+    pl.load_state_dict({"model." + k: v for k, v in sd.items()})
+    return pl.to(dev())
+
+
+def new_datamodule(root):
+    from beat_this_amd.dataset import BeatDataModule
+
+    return BeatDataModule(root, batch_size=2, train_length=150, augmentations={}, device=dev())
+
+
+def fit_and_resume(tmp_path, **kw):
+    """``fit`` for EPOCHS epochs on the seeded data folder, keeping the checkpoint of epoch 0, then a second module under another numpy
+    seed that resumes from it: the two final checkpoints hold the same weights and the same optimiser state, bit for bit.
+    -> dict(root, pl, h (the first run's history), h2 (the resumed one's), a, b (the two final checkpoints), first (epoch 0's))"""
+    import shutil
+
+    from beat_this_amd.inference import load_checkpoint
+    from beat_this_amd.train import fit
+    from dataset_reference import build_data_folder
+
+    root = build_data_folder(str(tmp_path / "data"))
+    ck, first, ck2 = (str(tmp_path / n) for n in ("run.ckpt", "epoch0.ckpt", "resumed.ckpt"))
+
+    def log(line):
+        if line.startswith("epoch 0:"):
+            shutil.copy(ck, first)
+
+    pl = new_module()
+    np.random.seed(0)
+    h = fit(pl, new_datamodule(root), EPOCHS, val_frequency=1, checkpoint_path=ck, log=log, **kw)
+    pl2 = new_module()
+    np.random.seed(99)
+    h2 = fit(pl2, new_datamodule(root), EPOCHS, val_frequency=1, checkpoint_path=ck2, resume=first, log=lambda s: None, **kw)
+    a, b = load_checkpoint(ck), load_checkpoint(ck2)
+    assert set(a) == set(b)
+    for k, v in a["state_dict"].items():
+        assert torch.equal(v, b["state_dict"][k]), k
+    sa, sb = a["optimizer_states"][0], b["optimizer_states"][0]
+    assert len(sa["state"]) == len(sb["state"]) > 0
+    for i in sa["state"]:
+        for k in ("step", "exp_avg", "exp_avg_sq"):
+            assert same_bits(torch.as_tensor(sa["state"][i][k]), torch.as_tensor(sb["state"][i][k])), (i, k)
+    # the run moved the weights
+    assert sum(not torch.equal(p.detach(), q.detach()) for p, q in zip(new_module().parameters(), pl.parameters())) > 20
+    return dict(root=root, pl=pl, h=h, h2=h2, a=a, b=b, first=load_checkpoint(first))
 
 
 # ---- the 16-mixed gate --------------------------------------------------------------------------------------------------------------

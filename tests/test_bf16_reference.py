@@ -1,6 +1,6 @@
 """The bfloat16 operand format of the 16-mixed routes without a GPU: the settings on every surface that takes
 them, the struct layouts, the parser, and the yardstick of tests/bf16_reference.py held against its own contract twin on every case
-the GPU tests (tests/test_gpu_bf16.py) run -- a finite, non-zero e_ref_bf16 and the twin within the gate.
+the GPU tests (tests/test_gpu_train_formats.py) run -- a finite, non-zero e_ref_bf16 and the twin within the gate.
 """
 import pickle
 

@@ -34,6 +34,23 @@ def test_library_exports_every_declared_symbol():
     assert handle.bt_version() == L.ABI_VERSION == 600   # (BT_ABI_VERSION of include/beat_this_amd.h)
 
 
+def test_the_operand_format_table_agrees_with_the_header_and_the_binding():
+    """_lib.OPERAND_FORMATS is the one list of the training route's operand formats: every value is the header's #define, every
+    query suffix names a bound function of both frontend families, and the constants beside it are derived from it"""
+    from beat_this_amd import _lib as L
+
+    header = open(os.path.join(ROOT, "include", "beat_this_amd.h")).read()
+    defines = {name: int(v) for name, v in re.findall(r"^#define BT_OPERAND_(\w+) (\d+)\s*$", header, re.M)}
+    names = {"fp16": "F16", "bf16": "BF16", "bf16x3": "BF16X3"}
+    assert set(L.OPERAND_FORMATS) == set(names) and set(defines) == set(names.values())
+    for fmt, (value, suffix) in L.OPERAND_FORMATS.items():
+        assert value == defines[names[fmt]] == getattr(L, "OPERAND_" + names[fmt]), fmt
+        for family in ("bt_front_workspace_bytes", "bt_front_bn_workspace_bytes"):
+            assert suffix and family + suffix in L.EXPORTS, (fmt, family + suffix)
+    assert L.OPERANDS == {k: v for k, (v, _) in L.OPERAND_FORMATS.items() if k != "bf16x3"}
+    assert len({v for v, _ in L.OPERAND_FORMATS.values()}) == len(L.OPERAND_FORMATS)   # (backward._front_call maps values back to suffixes)
+
+
 def test_argument_errors_map_to_exceptions():
     L = _lib()
     import pytest

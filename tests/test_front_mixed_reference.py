@@ -1,7 +1,7 @@
 """The yardstick of 16-mixed in the differentiable frontend (tests/route_reference.py), on the CPU:
   1. with the rounding switched off the restatement reproduces the oracle's autograd (fp64, 1e-10 relative);
   2. for every case of tests/test_gpu_front_mixed.py the restatement alone, in fp32, is within 1.5 x e_ref16 of the fp64 truth and
-     e_ref16 is finite.  The gate on the device is 2.0 (test_gpu_mixed.GATE); the device differs from the restatement only by the
+     e_ref16 is finite.  The gate on the device is 2.0 (route_harness.MIXED_GATE); the device differs from the restatement only by the
      order of its fp32 sums.  This is a condition on the cases, not a measurement: a case that failed it would get another seed,
      recorded in section 19.
 """

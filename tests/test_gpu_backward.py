@@ -20,7 +20,7 @@ import route_harness as H
 from route_grads import shift_tolerant_bce
 import route_reference as REF
 from gpu_util import POISONS, Guarded, assert_intact, dev, report
-from route_harness import make_batch, randn
+from route_harness import make_batch, model_loss, randn
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
 
@@ -207,14 +207,6 @@ def test_gradients_are_bitwise_reproducible_and_batch_invariant():
 
 
 # ---- 5. through the public interface -----------------------------------------------------------------------------------------
-def model_loss(m, batch, which=("beat", "downbeat")):
-    from beat_this_amd.model.loss import ShiftTolerantBCELoss
-
-    out = m(batch["spect"])
-    fn = ShiftTolerantBCELoss().to(dev())
-    return sum(fn(out[k], batch["truth_" + k].float(), batch["padding_mask"]) for k in which), out
-
-
 def oracle_loss_fn(batch, dtype, which=("beat", "downbeat")):
     t = {k: batch["truth_" + k].cpu().to(dtype) for k in ("beat", "downbeat")}
     mask = batch["padding_mask"].cpu().to(dtype)

@@ -7,7 +7,6 @@ Sizes: T = 1, 63, 64, 65, 130, 257 sit on both sides of the 64-wide attention bl
 query's last group of keys is ragged) and more than one block; D = 64 and 96 (two and three heads), ff_mult 2, B = 2; the units
 also at D = 128 (four heads), ff_mult 4 -- the shipped model's hidden = 4 D -- for T = 65 and 130."""
 import copy
-import ctypes as C
 import os
 import shutil
 import subprocess
@@ -22,9 +21,9 @@ import route_harness as H
 import route_reference as REF
 from conftest import ROOT
 from dataset_reference import build_data_folder
-from gpu_util import POISONS, Guarded, assert_intact, dev, report
+from gpu_util import POISONS, dev, report
 from route_grads import shift_tolerant_bce
-from route_harness import make_batch, randn, same_bits
+from route_harness import FIELDS, Unit, make_batch, randn, same_bits, unit_state_dict
 from route_reference import unit_masks
 from beat_this_amd import weights as W
 
@@ -33,8 +32,6 @@ pytestmark = pytest.mark.gpu
 TS = (1, 63, 64, 65, 130, 257)
 B = 2
 SEED = 0x5EED_0000_0000_0001          # (beyond 32 bits: both key words are in use)
-FIELDS = dict(attn=dict(gamma="norm.gamma", w1="to_qkv.weight", w2="to_gates.weight", b2="to_gates.bias", w3="to_out.0.weight"),
-              ff=dict(gamma="net.0.gamma", w1="net.1.weight", b1="net.1.bias", w2="net.4.weight", b2="net.4.bias"))
 
 
 def make_model(D, n_layers=2, seed=3):
@@ -42,13 +39,6 @@ def make_model(D, n_layers=2, seed=3):
     hp = dict(transformer_dim=D, ff_mult=2, n_layers=n_layers)
     sd = H.state_dict(hp, seed, "lively")
     return H.make_model(hp, sd, cache=("dropout", D, n_layers, seed)), sd
-
-
-def unit_state_dict(D, ff_mult=2):
-    """the ``lively`` weights of a 2-layer trunk of width D and hidden width ff_mult D (a state dict only: the engine's frontend
-    cannot be built at D = 96, ff_mult 2, and the unit calls need nothing of it but the rotary table, which does not depend on the
-    width)"""
-    return H.state_dict(dict(transformer_dim=D, ff_mult=ff_mult, n_layers=2), 3, "lively")
 
 
 def unit_truth(kind, sd, pfx, x, g, dtype, masks, p, residual):
@@ -61,88 +51,6 @@ def unit_truth(kind, sd, pfx, x, g, dtype, masks, p, residual):
     out = RG._collect(leaf, xl, [pfx + n for n in FIELDS[kind].values()])
     out["y"] = y.detach()
     return out
-
-
-# ---- the C ABI directly -----------------------------------------------------------------------------------------------------------
-class Plain:
-    def __init__(self, shape, dtype, data=None):
-        self.t = torch.empty(shape, dtype=dtype, device=dev()) if data is None else data.to(dev(), dtype).contiguous()
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-
-class Unit:
-    """The operands of one attention / feed-forward call (layer 1 of unit_state_dict), optionally in guarded buffers filled
-    with ``poison``; ``run`` does the forward and the backward and returns the outputs by state-dict key"""
-
-    def __init__(self, kind, D, x, gy, residual, poison=None, ff_mult=2):
-        from beat_this_amd import _lib as L
-
-        self.L, self.kind, self.poison, self.keep = L, kind, poison, []
-        m, sd = make_model(64)[0], unit_state_dict(D, ff_mult)
-        self.sd, self.pfx = sd, f"transformer_blocks.layers.1.{0 if kind == 'attn' else 1}."
-        self.unit = L.UNIT_ATTN if kind == "attn" else L.UNIT_FF
-        Bn, T = x.shape[:2]
-        self.shape, self.hidden = (Bn, T, D), ff_mult * D
-        eng = m.engine()
-        eng.ensure_positions(T)
-        self.rope = eng.packed._rope_t
-        a = self.a = L.TrainArgs()
-        a.B, a.T, a.dim, a.hidden, a.rope_len, a.residual = Bn, T, D, self.hidden, eng.packed.desc.rope_len, int(residual)
-        a.rope = self.rope.data_ptr()
-        self.x, self.gy = self.buf((Bn, T, D), x), self.buf((Bn, T, D), gy)
-        a.x, a.gy = self.x.ptr(), self.gy.ptr()
-        self.params = {f: self.buf(sd[self.pfx + n].shape, sd[self.pfx + n]) for f, n in FIELDS[kind].items()}
-        self.outs = {"y": self.buf((Bn, T, D))}
-        if kind == "attn":
-            self.outs["save_o"], self.outs["save_lse"] = self.buf((Bn, T, D)), self.buf((Bn, T, D // 32))
-        self.grads = {"gx": self.buf((Bn, T, D))}
-        for f, g in self.params.items():
-            self.grads["g_" + f] = self.buf(g.t.shape)
-        for f, g in list(self.params.items()) + list(self.outs.items()) + list(self.grads.items()):
-            setattr(a, f, g.ptr())
-
-    def buf(self, shape, data=None, dtype=torch.float32):
-        if self.poison is None:
-            b = Plain(shape, dtype, data)
-        else:
-            b = Guarded(shape, dtype).fill(self.poison, data=None if data is None else data.to(dev()))
-        self.keep.append(b)
-        return b
-
-    def ws_bytes(self, backward, drop):
-        lib = self.L.lib()
-        query = lib.bt_train_workspace_bytes_dropout if drop is not None and drop[0] > 0 else lib.bt_train_workspace_bytes
-        return query(self.unit, backward, *self.shape, self.hidden)
-
-    def call(self, backward, drop, entry, ws_bytes=None):
-        """one entry point -> its return code.  entry "plain": bt_train_forward / _backward (drop must be None); "dropout": the
-        *_dropout ones with NULL (drop None) or (p, seed, stream)"""
-        L, lib = self.L, self.L.lib()
-        n = self.ws_bytes(backward, drop) if ws_bytes is None else ws_bytes
-        ws = self.buf((max(n, 1),), dtype=torch.uint8)
-        self.a.ws, self.a.ws_bytes = ws.ptr(), n
-        if entry == "plain":
-            assert drop is None
-            return (lib.bt_train_backward if backward else lib.bt_train_forward)(L.stream_ptr(dev()), self.unit, C.byref(self.a))
-        d = None if drop is None else C.byref(L.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2]))
-        fn = lib.bt_train_backward_dropout if backward else lib.bt_train_forward_dropout
-        return fn(L.stream_ptr(dev()), self.unit, C.byref(self.a), d)
-
-    def run(self, drop, entry="dropout"):
-        for backward in (0, 1):
-            self.L.check(self.call(backward, drop, entry))
-        torch.cuda.synchronize()
-        if self.poison is not None:
-            assert_intact(*[(f"{self.kind} buffer {i}", g) for i, g in enumerate(self.keep)])
-        res = {"y": self.outs["y"].t.clone(), "x": self.grads["gx"].t.clone()}
-        for f, n in FIELDS[self.kind].items():
-            res[self.pfx + n] = self.grads["g_" + f].t.clone()
-        for k in ("save_o", "save_lse"):
-            if k in self.outs:
-                res[k] = self.outs[k].t.clone()
-        return res
 
 
 # ---- 1. units against the truth ---------------------------------------------------------------------------------------------------

@@ -12,29 +12,10 @@ import torch
 
 from conftest import ROOT
 from dataset_reference import build_data_folder
+from gpu_util import dev
+from route_harness import EPOCHS, new_datamodule, new_module   # (and for the modules that take them from here)
 
 gpu = pytest.mark.gpu
-LR, WARMUP, EPOCHS = 2e-3, 2, 2
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def new_module():
-    from beat_this_amd import weights as W
-    from beat_this_amd.model.pl_module import PLBeatThis
-
-    pl = PLBeatThis(transformer_dim=64, n_layers=2, ff_mult=2, lr=LR, warmup_steps=WARMUP, max_epochs=EPOCHS, eval_trim_beats=0)
-    sd = W.random_state_dict(W.resolve_hparams(dict(transformer_dim=64, ff_mult=2, n_layers=2)), seed=3, style="lively")
-    pl.load_state_dict({"model." + k: v for k, v in sd.items()})
-    return pl.to(dev())
-
-
-def new_datamodule(root):
-    from beat_this_amd.dataset import BeatDataModule
-
-    return BeatDataModule(root, batch_size=2, train_length=150, augmentations={}, device=dev())
 
 
 @pytest.fixture(scope="module")

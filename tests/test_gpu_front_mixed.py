@@ -4,7 +4,6 @@ truth (route_reference.py: e_ref16 is the autocast oracle's own error at the cas
 plumbing: determinism, isolation, refused arguments, the opt-in, AdamW steps under a LossScaler, ``fit`` and the command line.
 """
 import ctypes as C
-import shutil
 
 import numpy as np
 import pytest
@@ -14,8 +13,7 @@ import route_cases as RC
 import route_grads as RG
 import route_harness as H
 from gpu_util import POISONS, dev, report
-from route_harness import MODEL_KEYS, both_poisons, model_device, same_bits
-from test_gpu_mixed import GATE
+from route_harness import MIXED_GATE as GATE, MODEL_KEYS, both_poisons, make_batch, model_device, model_loss, new_datamodule, new_module, same_bits
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
 
@@ -32,13 +30,14 @@ def conv_spec(i=None, F_=None, C_=None):
 
 
 def abi_front(sd, unit, dims, B, T, x, gy, poison, mixed):
-    """forward + backward of BT_FRONT_CONV (dims = (prefix, F, C)) or BT_FRONT_LINEAR (dims = (F, C, dim)) through bt_front_*"""
-    return H.abi_front_unit(sd, unit, dims, B, T, x, gy, poison, mixed)
+    """forward + backward of BT_FRONT_CONV (dims = (prefix, F, C)) or BT_FRONT_LINEAR (dims = (F, C, dim)) through bt_front_*,
+    fp32 or (``mixed``) on fp16 operands"""
+    return H.abi_front_unit(sd, unit, dims, B, T, x, gy, poison, "fp16" if mixed else None)
 
 
 def abi_conv_bn(sd, i, B, T, x, gy, poison, mixed):
     """the same of conv unit i through bt_front_bn_* -> (results, {<key>: running buffer after the forward})"""
-    return H.abi_front_unit(sd, "conv", conv_spec(i), B, T, x, gy, poison, mixed, batch=True)
+    return H.abi_front_unit(sd, "conv", conv_spec(i), B, T, x, gy, poison, "fp16" if mixed else None, batch=True)
 
 
 # ---- 1. exact on integers ----------------------------------------------------------------------------------------------------------
@@ -342,7 +341,6 @@ def test_the_trunk_precision_alone_leaves_the_frontend_as_it_was():
 
 
 def test_three_adamw_steps_with_a_loss_scaler():
-    from test_gpu_backward import make_batch, model_loss
     from beat_this_amd.optim import AdamW, LossScaler, param_groups_for
 
     m = fresh_model().set_frontend_precision("16-mixed").set_train_precision("16-mixed")
@@ -374,36 +372,14 @@ def test_three_adamw_steps_with_a_loss_scaler():
 
 
 def test_fit_with_both_precisions_mixed_resumes_bit_for_bit(tmp_path):
-    from dataset_reference import build_data_folder
-    from beat_this_amd.inference import load_checkpoint
     from beat_this_amd.train import CHECKPOINT_KEYS, fit
-    from test_gpu_finetune import EPOCHS, new_datamodule, new_module
 
-    root = build_data_folder(str(tmp_path / "data"))
-    ck, first, ck2 = (str(tmp_path / n) for n in ("run.ckpt", "epoch0.ckpt", "resumed.ckpt"))
-
-    def log(line):
-        if line.startswith("epoch 0:"):
-            shutil.copy(ck, first)
-
-    kw = dict(val_frequency=1, train_frontend=True, precision="16-mixed", frontend_precision="16-mixed")
-    pl = new_module()
-    np.random.seed(0)
-    h = fit(pl, new_datamodule(root), EPOCHS, checkpoint_path=ck, log=log, **kw)
+    r = H.fit_and_resume(tmp_path, train_frontend=True, precision="16-mixed", frontend_precision="16-mixed")
+    pl, h, h2, a, b, root = (r[k] for k in ("pl", "h", "h2", "a", "b", "root"))
     assert pl.model.frontend_precision == "16-mixed" and pl.model.train_precision == "16-mixed" and h["loss_scaler"] is not None
     assert all(np.isfinite(v) for v in h["train_loss"])
-    pl2 = new_module()
-    np.random.seed(99)
-    h2 = fit(pl2, new_datamodule(root), EPOCHS, checkpoint_path=ck2, resume=first, log=lambda s: None, **kw)
-    a, b = load_checkpoint(ck), load_checkpoint(ck2)
     assert set(a) == set(CHECKPOINT_KEYS) | {"loss_scaler"} and a["loss_scaler"] == b["loss_scaler"] == h2["loss_scaler"].state_dict()
-    for k, v in a["state_dict"].items():
-        assert torch.equal(v, b["state_dict"][k]), k
-    sa, sb = a["optimizer_states"][0], b["optimizer_states"][0]
-    assert len(sa["state"]) == len(sb["state"]) == len(RG.all_keys(pl.model.state_dict()))
-    for i in sa["state"]:
-        for k in ("step", "exp_avg", "exp_avg_sq"):
-            assert torch.equal(torch.as_tensor(sa["state"][i][k]), torch.as_tensor(sb["state"][i][k])), (i, k)
+    assert len(a["optimizer_states"][0]["state"]) == len(RG.all_keys(pl.model.state_dict()))
     # the frontend opt-in alone creates the scaler too, and PLBeatThis takes the setting
     from beat_this_amd.model.pl_module import PLBeatThis
 

@@ -7,7 +7,6 @@ or more) -- then determinism and isolation, the loss scaler in the optimiser ste
 
 Every device entry is called on gpu_util.Guarded buffers: guard bands on both sides, both poison patterns."""
 import ctypes as C
-import shutil
 
 import numpy as np
 import pytest
@@ -16,30 +15,10 @@ import torch
 import route_cases as RC
 import route_grads as RG
 import route_harness as H
-from dataset_reference import build_data_folder
 from gpu_util import POISONS, Guarded, assert_intact, dev, report
-from route_harness import randn, same_bits
-from test_gpu_backward import make_model
-from test_gpu_dropout import Unit
+from route_harness import EDGES, EPOCHS, KS, MIXED_GATE as GATE, MixedUnit, Unit, new_datamodule, new_module, randn, same_bits
 
 pytestmark = pytest.mark.gpu
-GATE = 2.0
-
-
-class MixedUnit(Unit):
-    """test_gpu_dropout.Unit on the *_mixed entry points (drop: None or (p, seed, stream))"""
-
-    def ws_bytes(self, backward, drop):
-        return self.L.lib().bt_train_workspace_bytes_mixed(self.unit, backward, *self.shape, self.hidden, int(drop is not None))
-
-    def call(self, backward, drop, entry="mixed", ws_bytes=None):
-        L, lib = self.L, self.L.lib()
-        n = self.ws_bytes(backward, drop) if ws_bytes is None else ws_bytes
-        ws = self.buf((max(n, 1),), dtype=torch.uint8)
-        self.a.ws, self.a.ws_bytes = ws.ptr(), n
-        d = None if drop is None else C.byref(L.TrainDropout(p=drop[0], seed=drop[1], stream=drop[2]))
-        fn = lib.bt_train_backward_mixed if backward else lib.bt_train_forward_mixed
-        return fn(L.stream_ptr(dev()), self.unit, C.byref(self.a), d)
 
 
 def unscaled(res):
@@ -52,10 +31,6 @@ def gate(name, got, truth, e_ref16, keys):
 
 
 # ---- 1. exact products -------------------------------------------------------------------------------------------------------------
-EDGES = (1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200)   # the issue's sizes and the wave's 64-wide share of the 128-wide tile
-KS = (1, 15, 16, 17, 33, 64, 100)
-
-
 def matmul_exact(form, M, N, K, poison, seed):
     from beat_this_amd import _lib as L
 
@@ -115,7 +90,8 @@ def trunk_device(m, h, beat, down, mask, scale):
 
 def test_trunk_and_heads_with_a_loss():
     c = RC.TRUNK
-    m, _ = make_model(c["D"], n_layers=c["L"])
+    hp = dict(transformer_dim=c["D"], ff_mult=c["ff_mult"], n_layers=c["L"])
+    m = H.make_model(hp, H.state_dict(hp, 3, "lively"))
     sd = RC.trunk_state_dict(c["D"], c["ff_mult"], c["L"])
     for k, v in m.state_dict().items():
         assert torch.equal(v.cpu(), sd[k]), k
@@ -295,36 +271,15 @@ def test_the_optimiser_skips_a_step_with_non_finite_gradients():
 def test_fit_in_16_mixed_resumes_bit_for_bit(tmp_path):
     from beat_this_amd.inference import load_checkpoint, load_model
     from beat_this_amd.train import CHECKPOINT_KEYS, fit
-    from test_gpu_finetune import EPOCHS, new_datamodule, new_module
 
-    root = build_data_folder(str(tmp_path / "data"))
-    ck, first, ck2, ck32 = (str(tmp_path / n) for n in ("run.ckpt", "epoch0.ckpt", "resumed.ckpt", "fp32.ckpt"))
-
-    def log(line):
-        if line.startswith("epoch 0:"):
-            shutil.copy(ck, first)
-
-    pl = new_module()
-    np.random.seed(0)
-    h = fit(pl, new_datamodule(root), EPOCHS, val_frequency=1, checkpoint_path=ck, log=log, precision="16-mixed")
+    r = H.fit_and_resume(tmp_path, precision="16-mixed")
+    pl, h, h2, a, b, root = (r[k] for k in ("pl", "h", "h2", "a", "b", "root"))
+    ck, ck32 = str(tmp_path / "run.ckpt"), str(tmp_path / "fp32.ckpt")
     assert pl.model.train_precision == "16-mixed" and h["loss_scaler"].scale == 65536.0 and h["loss_scaler"].growth_tracker == 4
     assert all(np.isfinite(v) and v < 10 for v in h["train_loss"])   # (reported unscaled)
-    pl2 = new_module()
-    np.random.seed(99)
-    h2 = fit(pl2, new_datamodule(root), EPOCHS, val_frequency=1, checkpoint_path=ck2, resume=first, log=lambda s: None,
-             precision="16-mixed")
-    a, b = load_checkpoint(ck), load_checkpoint(ck2)
     assert set(a) == set(CHECKPOINT_KEYS) | {"loss_scaler"} and a["loss_scaler"] == b["loss_scaler"] == h2["loss_scaler"].state_dict()
-    assert load_checkpoint(first)["loss_scaler"]["_growth_tracker"] == 2
-    for k, v in a["state_dict"].items():
-        assert torch.equal(v, b["state_dict"][k]), k
-    sa, sb = a["optimizer_states"][0], b["optimizer_states"][0]
-    for i in sa["state"]:
-        for k in ("step", "exp_avg", "exp_avg_sq"):
-            assert same_bits(sa["state"][i][k], sb["state"][i][k]), (i, k)
-    # the route moved the weights elsewhere than fp32 does, and the checkpoint is an ordinary one
-    fresh = new_module()
-    assert sum(not torch.equal(p.detach(), q.detach()) for p, q in zip(fresh.parameters(), pl.parameters())) > 20
+    assert r["first"]["loss_scaler"]["_growth_tracker"] == 2
+    # the checkpoint is an ordinary one
     loaded = load_model(ck, dev())
     x = torch.log1p(torch.rand(1, 150, 128, generator=torch.Generator().manual_seed(5)) * 30).to(dev())
     with torch.no_grad():

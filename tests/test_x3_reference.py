@@ -1,6 +1,6 @@
 """The "32-high" training precision without a GPU: the split of an fp32 value into two bfloat16 halves, the
 contract twin of tests/x3_reference.py held against the fp64 truth and against bfloat16 autocast on every case the GPU tests
-(tests/test_gpu_train_high.py) run -- e_x3 <= e_ref_bf16 / 64 -- and the setting on every surface that takes it.
+(tests/test_gpu_train_formats.py) run -- e_x3 <= e_ref_bf16 / 64 -- and the setting on every surface that takes it.
 """
 import copy
 import pickle
@@ -81,7 +81,7 @@ def test_the_product_drops_the_lo_lo_term_and_nothing_else():
 # ---- 2. the twin sits where the issue's table says --------------------------------------------------------------------------------------
 def check(name, case):
     """the twin within e_ref_bf16 / 64 of the fp64 truth (CAP_EXEMPT: printed alone), both figures finite and non-zero"""
-    e_x3, e_bf = case["e_x3"], case["e_ref_bf16"]
+    e_x3, e_bf = case["e"], case["e_ref_bf16"]
     print(f"x3 twin {name}: e_x3 = {e_x3:.3e}, e_ref_bf16 = {e_bf:.3e}, e_ref_bf16 / e_x3 = {e_bf / e_x3:.0f}")
     assert 0 < e_x3 < float("inf") and 0 < e_bf < float("inf")
     assert case["name"] == name
@@ -107,7 +107,7 @@ def test_the_four_unit_cases_sit_where_the_table_of_section_25_says():
     for (kind, D), (e_x3, e_bf) in TABLE.items():
         case = X3.unit_case(kind, D, 2, 40)
         ratio = check(f"{kind} D={D} B=2 T=40", case)
-        assert abs(case["e_x3"] / e_x3 - 1) < 0.03 and abs(case["e_ref_bf16"] / e_bf - 1) < 0.03, (kind, D, case["e_x3"], case["e_ref_bf16"])
+        assert abs(case["e"] / e_x3 - 1) < 0.03 and abs(case["e_ref_bf16"] / e_bf - 1) < 0.03, (kind, D, case["e"], case["e_ref_bf16"])
         assert 625 <= ratio < 795, (kind, D, ratio)
 
 

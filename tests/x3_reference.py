@@ -9,7 +9,7 @@ every ``*_grads`` function of route_grads.py serves unchanged.
 ``yardstick`` gives the fp64 truth, the twin, ``e_x3`` -- the twin's worst relative distance from the truth over every gradient
 key -- and ``e_ref_bf16``, bf16_reference.py's (the oracle under CPU bfloat16 autocast).  The gate of the device is
 ``MIXED_GATE`` = 2 x e_x3 and the cap ``e_ref_bf16 / CAP`` on every gradient key, ``y`` and the logits.  The cases are
-bf16_reference.py's, truth and e_ref_bf16 computed once and shared with it.
+bf16_reference.py's, truth and e_ref_bf16 computed once and shared with it.  The module has bf16_reference.py's shape (see there).
 """
 import contextlib
 
@@ -24,6 +24,9 @@ from route_harness import MIXED_GATE as GATE
 
 CAP = 64.0           # e_x3 and the device within e_ref_bf16 / 64: the halves keep 2^-17 of an operand where bfloat16 keeps 2^-9
 CAP_EXEMPT = ()      # names of the cases that miss the cap on the CPU (test_x3_reference.py prints their ratios); never the gate
+FORMAT = "bf16x3"
+PRECISION = ("32-high", None)
+LABEL, RECORD, E_NAME = "32-high", "high", "e_x3"
 _CASES = {}
 
 
@@ -119,16 +122,16 @@ def high():
 
 def yardstick(run, bf_case):
     """run(dtype, on, autocast) -> a ``*_grads`` result at loss scale 1; ``bf_case``: bf16_reference.py's case of the same inputs.
-    -> dict(truth (fp64 oracle), twin (the contract in fp32), e_x3, e_ref_bf16)"""
+    -> dict(truth (fp64 oracle), yard (the twin: the contract in fp32), e = e_x3, e_ref_bf16)"""
     truth = bf_case["truth"]
     with high():
         twin = run(torch.float32, True, False)
-    return dict(truth=truth, twin=twin, e_x3=G.worst(twin, truth)[0], e_ref_bf16=bf_case["e_ref"])
+    return dict(truth=truth, yard=twin, e=G.worst(twin, truth)[0], e_ref_bf16=bf_case["e"])
 
 
 def _case(key, bf_case, run):
     if key not in _CASES:
-        _CASES[key] = dict({k: v for k, v in bf_case.items() if k not in ("auto", "twin", "e_ref")}, **yardstick(run, bf_case), name=key)
+        _CASES[key] = dict({k: v for k, v in bf_case.items() if k not in ("yard", "twin", "e")}, **yardstick(run, bf_case), name=key)
     return _CASES[key]
 
 
@@ -185,11 +188,11 @@ def gpu_cases():
 
 
 # ---- the gate ---------------------------------------------------------------------------------------------------------------------
-def gate(name, got, case, report=None, capped_keys=()):
+def gate(name, got, case, report=None, capped=()):
     """every gradient key of the truth, ``y`` and the logits finite, within GATE x e_x3 of the fp64 truth and within e_ref_bf16 /
-    CAP (unless the case is in CAP_EXEMPT).  ``capped_keys``: keys gated at the cap alone (a finding recorded in DESIGN.md section
+    CAP (unless the case is in CAP_EXEMPT).  ``capped``: keys gated at the cap alone (a finding recorded in DESIGN.md section
     25).  Prints every figure before it asserts -> the worst distance in e_x3"""
-    truth, e_x3, e_bf = case["truth"], case["e_x3"], case["e_ref_bf16"]
+    truth, e_x3, e_bf = case["truth"], case["e"], case["e_ref_bf16"]
     keys = G.grad_keys(truth) + BF.outputs_of(truth)
     assert 0 < e_x3 < float("inf") and 0 < e_bf < float("inf"), f"{name}: e_x3 = {e_x3}, e_ref_bf16 = {e_bf}"
     missing = [k for k in keys if k not in got]
@@ -197,14 +200,14 @@ def gate(name, got, case, report=None, capped_keys=()):
     errs = {k: G.rel(got[k], truth[k]) for k in keys}
     k = max(errs, key=errs.get)
     print(f"{name}: e_x3 = {e_x3:.3e}, e_ref_bf16 = {e_bf:.3e} ({e_bf / e_x3:.0f} x), worst error = {errs[k]:.3e} "
-          f"({errs[k] / e_x3:.2f} x e_x3, {k}; the twin's own {G.rel(case['twin'][k], truth[k]):.3e})")
+          f"({errs[k] / e_x3:.2f} x e_x3, {k}; the twin's own {G.rel(case['yard'][k], truth[k]):.3e})")
     for key in BF.outputs_of(truth):
         print(f"{name}: {key} {errs[key]:.3e} ({errs[key] / e_x3:.2f} x e_x3)")
     if report is not None:
         report("high", case=name, e_x3=e_x3, e_ref_bf16=e_bf, worst_ratio=errs[k] / e_x3, worst_tensor=k)
     for key, e in errs.items():
         assert torch.isfinite(got[key]).all(), f"{name}: {key} is not finite"
-        if key not in capped_keys:
+        if key not in capped:
             assert e <= GATE * e_x3, f"{name}: {key} is {e:.3e} from the fp64 truth, the gate is 2 x e_x3 = {GATE * e_x3:.3e}"
         if case["name"] not in CAP_EXEMPT:
             assert e <= e_bf / CAP, f"{name}: {key} is {e:.3e} from the fp64 truth, the cap is e_ref_bf16 / 64 = {e_bf / CAP:.3e}"
