@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "stretch.hip", "pcm.hip", "engine.hip"]
+           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "reduce.hip", "stretch.hip", "pcm.hip", "engine.hip"]
 HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "train_front_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
@@ -201,6 +201,7 @@ PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # BT_PCM_*: sam
 PCM_SAMPLE_BYTES = (1, 2, 3, 4, 4, 8)
 PCM_MAX_CHANNELS_INT, PCM_MAX_CHANNELS_FLOAT, PCM_MAX_TRACKS = 8, 7, 65535
 PCM_THREAD_FRAMES, PCM_BLOCK_FRAMES = 4, 1024               # frames per thread / per workgroup (tests sit on both sides of them)
+REDUCE_MAX_WORLD, REDUCE_CHUNK = 16, 4096                  # BT_REDUCE_*: ranks of one bt_grad_rank_sum / elements per workgroup
 
 EXPORTS = {
     "bt_last_error": (C.c_char_p, []),
@@ -339,6 +340,8 @@ EXPORTS = {
     "bt_pcm_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64]),
     "bt_pcm_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "bt_pcm_decode_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "bt_grad_rank_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p]),
+    "bt_grad_rank_sum_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p]),
 }
 
 
@@ -359,6 +362,8 @@ FLAGS_BY_SOURCE = {"tail.hip": ["-Xclang", "-target-feature", "-Xclang", "-packe
                    "data.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # the AdamW step and the gradient norm must have the same bits on the host and the device (the host twins)
                    "optim.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
+                   # the rank-ordered gradient sum is a chain of single fp32 adds, the same on the host and the device
+                   "reduce.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # frame positions, output lengths and filter arguments are fp64 expressions that numpy evaluates too
                    "stretch.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # the channel mean is numpy's fp64 sum and division, operation by operation, on the host and the device

@@ -238,17 +238,26 @@ class BeatTrackingDataset(torch.utils.data.Dataset):
         self.is_resident = bool(resident)
         self._store = (store,)
 
-    def batch(self, indices, out=None, spect_dtype=torch.float32):
+    def plan_batch(self, indices):
+        """The host-side draws of a batch, item by item in the order of ``indices``: what ``batch`` draws when it is not
+        handed a plan.  Touches no device; advances numpy's generator exactly as building the batch would."""
+        return [self._plan(int(i)) for i in indices]
+
+    def batch(self, indices, out=None, spect_dtype=torch.float32, planned=None):
         """The collated batch of ``ds[i] for i in indices`` on the device, from ONE launch: spect (B, L, 128) of
         ``spect_dtype`` (float32 or float16), truth_beat / truth_downbeat / padding_mask (B, L) and downbeat_mask (B,) as
         torch.bool; truth_orig_beat / truth_orig_downbeat, dataset, spect_path and start_frame as lists with one entry per
         item.  ``out``: a dict with tensors to fill instead of new ones (any of the five device entries).  With
-        train_length None all items must have the same number of frames."""
+        train_length None all items must have the same number of frames.  ``planned``: the ``plan_batch(indices)`` of this
+        batch, drawn earlier (nothing is drawn here then)."""
         self._ensure_store()
         indices = [int(i) for i in indices]
         if not indices:
             raise ValueError("an empty batch")
-        planned = [self._plan(i) for i in indices]
+        if planned is None:
+            planned = self.plan_batch(indices)
+        elif len(planned) != len(indices):
+            raise ValueError(f"a plan of {len(planned)} items for a batch of {len(indices)}")
         L = self.train_length if self.train_length is not None else planned[0][3]
         if any(p[3] > L or (self.train_length is None and p[3] != L) for p in planned):
             raise ValueError("train_length=None batches whole pieces: they must have the same number of frames "
@@ -303,6 +312,49 @@ class BatchLoader:
         order = np.random.permutation(n) if self.shuffle else np.arange(n)
         for i in range(len(self)):
             yield self.dataset.batch(order[i * self.batch_size:(i + 1) * self.batch_size], spect_dtype=self.spect_dtype)
+
+    def shard(self, rank: int, world: int) -> "ShardedBatchLoader":
+        """This loader for rank ``rank`` of ``world`` data-parallel ranks: the same global sequence of batches, of which the
+        rank builds every ``world``-th (``ShardedBatchLoader``)."""
+        return ShardedBatchLoader(self, rank, world)
+
+
+class ShardedBatchLoader:
+    """A ``BatchLoader`` seen from one of ``world`` data-parallel ranks.  Every rank draws what the unsharded loader draws, in
+    its order -- the permutation when an iteration starts, then every batch's plan (``BeatTrackingDataset.plan_batch``) -- so
+    numpy's generator is in the single-process state on every rank after every batch.  Global batch ``j`` belongs to rank
+    ``j % world``; only its owner builds it.  Iterating yields ``(j, batch)`` for the owned batches; ``len()`` is the GLOBAL
+    number of batches."""
+
+    def __init__(self, loader: BatchLoader, rank: int, world: int):
+        rank, world = int(rank), int(world)
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"rank {rank} of a world of {world}")
+        self.loader, self.rank, self.world = loader, rank, world
+
+    def __len__(self):
+        return len(self.loader)
+
+    def _planned(self):
+        """(j, owner, indices, planned) for every global batch; the draws happen as the iteration advances"""
+        lo = self.loader
+        n = len(lo.dataset)
+        order = np.random.permutation(n) if lo.shuffle else np.arange(n)
+        for j in range(len(lo)):
+            indices = order[j * lo.batch_size:(j + 1) * lo.batch_size]
+            yield j, j % self.world, indices, lo.dataset.plan_batch(indices)
+
+    def iter_plans(self):
+        """Host only: ``(j, owner, planned)`` for every global batch, in order, with all of an iteration's draws and no
+        device work (what the rank would build is the entries with ``owner == rank``)."""
+        for j, owner, _, planned in self._planned():
+            yield j, owner, planned
+
+    def __iter__(self):
+        lo = self.loader
+        for j, owner, indices, planned in self._planned():
+            if owner == self.rank:
+                yield j, lo.dataset.batch(indices, spect_dtype=lo.spect_dtype, planned=planned)
 
 
 # the training sets of "Modeling Beats and Downbeats with a Time-Frequency Transformer" (Hung et al.)

@@ -175,13 +175,15 @@ class PLBeatThis(nn.Module):
         metrics = self._compute_metrics(batch, *self._postprocess(prediction, None), step="test")
         return metrics, prediction, batch["dataset"], batch["spect_path"]
 
-    def configure_optimizers(self, total_steps, max_grad_norm=None, accumulate=1, ema_decay=None):
+    def configure_optimizers(self, total_steps, max_grad_norm=None, accumulate=1, ema_decay=None, process_group=None, staged=False):
         """The reference's optimiser and schedule (pl_module.py:279-306) on this package's kernels: AdamW at ``lr`` with
         ``weight_decay`` on the matrices only, and the cosine schedule with ``warmup_steps`` over ``total_steps`` optimiser
         steps (what Lightning's ``estimated_stepping_batches`` is there), stepped once per optimiser step.  ``ema_decay``: the
-        optimiser also keeps an exponential moving average of the weights (``AdamW(ema_decay=...)``)."""
+        optimiser also keeps an exponential moving average of the weights (``AdamW(ema_decay=...)``).  ``process_group``,
+        ``staged``: the optimiser sums the gradients over that group's ranks at every step (``AdamW(process_group=...)``)."""
+        extra = {} if process_group is None else {"process_group": process_group, "staged": staged}
         optimizer = _optim.AdamW(_optim.param_groups_for(self, self.weight_decay), lr=self.lr, max_grad_norm=max_grad_norm,
-                                 accumulate=accumulate, ema_decay=ema_decay)
+                                 accumulate=accumulate, ema_decay=ema_decay, **extra)
         self.lr_scheduler = _optim.CosineWarmupScheduler(optimizer, self.warmup_steps, total_steps)
         return {"optimizer": optimizer, "lr_scheduler": {"scheduler": self.lr_scheduler, "interval": "step"}}
 

@@ -173,12 +173,19 @@ class AdamW(torch.optim.Optimizer):
     weights in between (``step()`` raises there).  The average travels in ``state_dict()`` under ``"ema"``; the decay is always the
     constructor's.  BatchNorm buffers are not parameters and are not averaged.
 
+    ``process_group`` (a ``torch.distributed`` group; None: none of this exists): data-parallel training.  Every rank holds the
+    same parameters and calls ``step()`` at the same points; after the gradients are attached and before anything reads them,
+    the ranks' flat gradient buffers are added in rank order (``parallel.GradientExchange``, csrc/reduce.hip), so the norm,
+    the clip coefficient, the loss scaler's decision and the update are computed from the same bits on every rank.
+    ``accumulate`` and ``accumulated`` count the backward passes of ALL ranks.  ``staged``: the collectives go through host
+    copies (gloo).  ``state_dict()`` and ``load_state_dict()`` are unchanged.  DESIGN.md section 26.
+
     Capturing ``step()`` into a HIP graph is out of scope: the learning rate, the bias corrections and the other scalars travel
     to the kernel by value, so a replay would repeat one step's scalars.  ``state_dict()`` and ``load_state_dict()`` are this
     class's own (the state lives in the flat buffers, not in ``self.state``): torch's state-dict pre- and post-hooks are not run."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, accumulate=1,
-                 ema_decay=None):
+                 ema_decay=None, process_group=None, staged=False):
         if lr < 0 or eps < 0 or weight_decay < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1:
             raise ValueError(f"invalid AdamW settings: lr {lr}, betas {betas}, eps {eps}, weight_decay {weight_decay}")
         if int(accumulate) < 1:
@@ -213,7 +220,14 @@ class AdamW(torch.optim.Optimizer):
         self._tables = None
         self._build_tables()
         dev = self.device
-        self._grad = torch.zeros(self._total, dtype=torch.float32, device=dev)
+        self._reducer = None
+        if process_group is None:
+            self._grad = torch.zeros(self._total, dtype=torch.float32, device=dev)
+        else:   # (the gradient buffer is the head of the exchange's store: the collectives need no staging copy)
+            from .parallel import GradientExchange
+
+            self._reducer = GradientExchange(process_group, self._total, dev, staged=staged)
+            self._grad = self._reducer.flat
         self._m = torch.zeros_like(self._grad)
         self._v = torch.zeros_like(self._grad)
         self._ema = None if self.ema_decay is None else torch.zeros_like(self._grad)
@@ -278,6 +292,8 @@ class AdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         self._attach()
+        if self._reducer is not None:   # (the sum over the ranks, in rank order: everything below sees the same bits on every rank)
+            self._reducer.reduce_(self._grad)
         count = self.accumulate if accumulated is None else int(accumulated)
         if count < 1:
             raise ValueError(f"accumulated must be a positive number of backward passes, got {accumulated}")

@@ -152,3 +152,85 @@ def audio2frames_sharded(signals, sr, frames_fn, group=None, device=None):
             out.append((full[r, 0, pos: pos + frames[k]], full[r, 1, pos: pos + frames[k]]))
             pos += frames[k]
     return out
+
+
+# ---- data-parallel training: the gradient exchange -------------------------------------------------------
+def grad_rank_sum_host(parts: np.ndarray, world: int, n: int, stride: int | None = None, out: np.ndarray | None = None):
+    """bt_grad_rank_sum_host on a flat fp32 array holding ``world`` parts of ``n`` elements, ``stride`` elements apart (default
+    ``n``) -> ``out`` (a new array, or the one given; ``out is parts`` sums in place over rank 0's part)"""
+    from . import _lib
+
+    stride = n if stride is None else stride
+    if parts.dtype != np.float32 or not parts.flags.c_contiguous or parts.size < ((world - 1) * stride + n if world >= 1 else 0):
+        raise ValueError("parts must be a contiguous float32 array that holds every part")
+    if out is None:
+        out = np.empty(max(n, 0), np.float32)
+    _lib.check(_lib.lib().bt_grad_rank_sum_host(parts.ctypes.data, stride, world, n, out.ctypes.data))
+    return out
+
+
+def segment_length(total: int, world: int) -> int:
+    """Elements per rank's segment of a flat buffer of ``total``: ceil(total / world), rounded up to a multiple of 4"""
+    return (-(-int(total) // int(world)) + 3) // 4 * 4
+
+
+class GradientExchange:
+    """The one gradient exchange of a data-parallel optimiser step.  The flat gradient buffer (``total`` fp32 elements) is the
+    head of a store of ``world * per`` elements, ``per = segment_length(total, world)``; the tail padding is zero and stays
+    zero.  ``reduce_(flat)``: one ``all_to_all_single`` hands every rank all ranks' copies of its segment, ``bt_grad_rank_sum``
+    adds them IN RANK ORDER (csrc/reduce.hip), one ``all_gather_into_tensor`` returns the summed segments to every rank's
+    store.  The traffic is a ring all-reduce's; the result is the same on every rank and is, bit for bit, what autograd's
+    in-place accumulation of the ranks' gradients in rank order would have left -- whatever algorithm RCCL picks, because the
+    collectives only move data.
+
+    ``self.flat`` is the buffer to accumulate into (``AdamW`` makes it its gradient buffer, so nothing is staged); a foreign
+    ``flat`` handed to ``reduce_`` is copied in and out, one extra pass each way.  ``staged=True``: the collectives go through
+    host copies (gloo, development runs whose ranks share one GPU); the sum still runs on the GPU."""
+
+    def __init__(self, group, total: int, device, staged: bool = False):
+        from . import _lib
+
+        self.group, self.total, self.device, self.staged = group, int(total), torch.device(device), bool(staged)
+        self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+        if not 1 <= self.world <= _lib.REDUCE_MAX_WORLD:
+            raise ValueError(f"a gradient exchange over {self.world} ranks: at most {_lib.REDUCE_MAX_WORLD} are supported")
+        self.per = segment_length(self.total, self.world)
+        self.store = torch.zeros(self.world * self.per, dtype=torch.float32, device=self.device)
+        self.flat = self.store[:self.total]
+        self._recv = torch.zeros_like(self.store)   # row r: rank r's copy of this rank's segment
+
+    def _collect(self) -> None:
+        if self.staged:
+            recv = torch.empty(self.store.shape, dtype=torch.float32)
+            dist.all_to_all_single(recv, self.store.cpu(), group=self.group)
+            self._recv.copy_(recv)
+        else:
+            dist.all_to_all_single(self._recv, self.store, group=self.group)
+
+    def _distribute(self, segment: torch.Tensor) -> None:
+        if self.staged:
+            full = torch.empty(self.store.shape, dtype=torch.float32)
+            dist.all_gather_into_tensor(full, segment.cpu(), group=self.group)
+            self.store.copy_(full)
+        else:
+            dist.all_gather_into_tensor(self.store, segment, group=self.group)
+
+    @torch.no_grad()
+    def reduce_(self, flat: torch.Tensor) -> torch.Tensor:
+        """``flat`` (``total`` fp32 elements on the device) becomes the rank-ordered sum of all ranks' ``flat``; every rank of
+        the group calls it, in the same order"""
+        from . import _lib
+
+        own = flat.data_ptr() == self.store.data_ptr()
+        if flat.numel() != self.total or flat.dtype != torch.float32 or flat.device != self.store.device or not flat.is_contiguous():
+            raise ValueError(f"reduce_ takes a contiguous float32 tensor of {self.total} elements on {self.device}")
+        if not own:
+            self.flat.copy_(flat)
+        self._collect()
+        with torch.cuda.device(self.device):   # in place over row 0, which is then this rank's summed segment
+            _lib.check(_lib.lib().bt_grad_rank_sum(_lib.stream_ptr(self.device), self._recv.data_ptr(), self.per, self.world, self.per,
+                                                   self._recv.data_ptr()))
+        self._distribute(self._recv[:self.per])
+        if not own:
+            flat.copy_(self.flat)
+        return flat

@@ -10,6 +10,10 @@ fp16 products too; dropout in the main layers when enabled and, with ``frontend_
 partial transformers as well), the losses, and the fused AdamW of ``beat_this_amd.optim``.  The checkpoint is a plain dictionary that ``torch.load(..., weights_only=True)``, ``load_checkpoint``
 and ``load_model`` read as it is.
 
+``fit(..., process_group=...)`` and ``--gpus N`` train data-parallel, one process per GPU: the ranks' gradients are added in rank
+order (csrc/reduce.hip), so N ranks with one batch each per step repeat the single-process run with N accumulated batches bit
+for bit.
+
 Not offered: the reference's wandb logger, ``--compile`` and ``--force-flash-attention`` (nothing here is compiled by torch or
 runs torch's attention), and the test run after training (``beat_this_amd.evaluate`` scores a checkpoint).
 """
@@ -17,7 +21,6 @@ from __future__ import annotations
 
 import argparse
 import contextlib
-import math
 import os
 import sys
 
@@ -98,24 +101,75 @@ def save_checkpoint(path, pl_module, optimizer, scheduler, epoch: int, global_st
     os.replace(tmp, path)
 
 
-def validate(pl_module, datamodule) -> dict:
+def _validation_values(pl_module, batch, i):
+    """one validation batch -> (its size, {name: value as a Python float})"""
+    losses, metrics = pl_module.validation_step(batch, i)
+    values = {"val_loss": losses["total"], "val_loss_beat": losses["beat"], "val_loss_downbeat": losses["downbeat"]}
+    values.update({f"val_{k}": v for k, v in metrics.items()})
+    return int(batch["spect"].shape[0]), {k: float(v) for k, v in values.items()}
+
+
+def validate(pl_module, datamodule, process_group=None) -> dict:
     """The mean over the validation set (weighted by batch size) of the losses and of what the reference's ``step="val"``
-    reports: F-measure and Cemgil for beats and downbeats."""
+    reports: F-measure and Cemgil for beats and downbeats.  ``process_group``: batch ``j`` is computed by rank ``j % world``,
+    the per-batch values are gathered and every rank adds them in batch order -- the single-process numbers exactly, on
+    every rank."""
+    if process_group is None:
+        per_batch = [_validation_values(pl_module, batch, i) for i, batch in enumerate(datamodule.val_dataloader())]
+    else:
+        import torch.distributed as dist
+
+        world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+        mine = {j: _validation_values(pl_module, batch, j) for j, batch in datamodule.val_dataloader().shard(rank, world)}
+        gathered = [None] * world
+        dist.all_gather_object(gathered, mine, group=process_group)
+        merged = {j: v for part in gathered for j, v in part.items()}
+        per_batch = [merged[j] for j in sorted(merged)]
     sums, count = {}, 0
-    for i, batch in enumerate(datamodule.val_dataloader()):
-        losses, metrics = pl_module.validation_step(batch, i)
-        n = int(batch["spect"].shape[0])
-        values = {"val_loss": losses["total"], "val_loss_beat": losses["beat"], "val_loss_downbeat": losses["downbeat"]}
-        values.update({f"val_{k}": v for k, v in metrics.items()})
+    for n, values in per_batch:
         for k, v in values.items():
-            sums[k] = sums.get(k, 0.0) + n * float(v)
+            sums[k] = sums.get(k, 0.0) + n * v
         count += n
     return {k: v / count for k, v in sums.items()} if count else {}
 
 
+def step_groups(batches: int, accumulate: int, world: int = 1) -> list:
+    """The optimiser steps of one epoch of ``batches`` global batches on ``world`` ranks: [(first, count)], consecutive runs of
+    ``accumulate * world`` global batches and, last, the remainder with its own count.  Global batch ``j`` is rank
+    ``j % world``'s; a rank that owns none of a group's batches still takes part in the group's step."""
+    size = int(accumulate) * int(world)
+    if size < 1 or batches < 0:
+        raise ValueError("accumulate and world must be at least 1, batches at least 0")
+    return [(first, min(size, batches - first)) for first in range(0, batches, size)]
+
+
+def _broadcast(tensors, group, staged: bool) -> None:
+    """rank 0's values into every rank's ``tensors`` (in place)"""
+    import torch.distributed as dist
+
+    src = dist.get_global_rank(group, 0)
+    with torch.no_grad():
+        for t in tensors:
+            if staged:
+                host = t.detach().cpu()
+                dist.broadcast(host, src, group=group)
+                t.copy_(host)
+            else:
+                dist.broadcast(t.detach(), src, group=group)
+                torch.autograd.graph.increment_version(t)   # (written behind autograd's back, as the optimiser's step is)
+
+
+def _fingerprint(optimizer) -> tuple:
+    """A cheap bit fingerprint of a rank's training state: exp_avg's bits summed as integers, and where numpy's generator is"""
+    kind, keys, pos, has_gauss, cached = np.random.get_state()
+    moments = int(optimizer.flat_state()["exp_avg"].view(torch.int32).sum(dtype=torch.int64))
+    return moments, int(pos), int(np.asarray(keys, dtype=np.uint64).sum()), int(has_gauss)
+
+
 def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
         resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None, frontend_precision=None,
-        frontend_dropout=None, ema_decay=None, mixed_operand=None, frontend_mixed_operand=None) -> dict:
+        frontend_dropout=None, ema_decay=None, mixed_operand=None, frontend_mixed_operand=None, process_group=None,
+        staged=False) -> dict:
     """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
 
     Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
@@ -165,6 +219,32 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     ``AdamW.load_state_dict``: a checkpoint without an average starts one, an average is ignored when ``ema_decay`` is None.
     BatchNorm buffers are not averaged.
 
+    ``process_group`` (a ``torch.distributed`` group, one rank per process, every rank with the same module settings, the same
+    numpy seed and, with ``resume``, the same file; None: none of the following exists and every call is the one of a
+    single-process run), ``staged`` (the collectives go through host copies: gloo, ranks that share one GPU): data-parallel
+    training, DESIGN.md section 26.  Every rank draws the whole sequence of global batches (``BatchLoader.shard``) and builds
+    and runs batch ``j`` iff ``j % world == rank``.  One optimiser step closes a GROUP of ``accumulate_grad_batches * world``
+    consecutive global batches (the epoch's remainder with its own count; ``step_groups``): every rank calls
+    ``step(accumulated=<the group's global count>)``, in which the ranks' gradient buffers are added in rank order -- a rank
+    that owns no batch of a group contributes the zeros the previous step left.  The schedule spans
+    ``max_epochs * ceil(batches / (accumulate_grad_batches * world))`` steps.
+    THE ASSOCIATION: a rank first sums its own batches of the group (autograd, in batch order), then the ranks' sums are added
+    in rank order.  With ``accumulate_grad_batches == 1`` that is ``((0 + g0) + g1) + ...`` over the group's batches in global
+    order: a W-rank run is, bit for bit, the single-process run with ``accumulate_grad_batches = W`` -- parameters, optimiser
+    state, loss scale, averages, losses, validation values and the checkpoint.  With ``accumulate_grad_batches = A > 1`` the
+    sum is ``(g0 + gW + ...) + (g1 + gW+1 + ...) + ...``, another association of the same terms than the single process's
+    with ``A W``: equal up to fp32 rounding, not bit for bit; steps, counts and rates are the same.
+    Dropout: the forward of global batch ``j`` draws the streams the single-process run draws for it (the model's call
+    counter is set from ``j`` before every training forward: a forward advances it by 2 ``n_layers``, by 12 more with frontend
+    dropout); at an epoch's end every rank holds the single-process counter.  Rank 0's parameters and buffers are broadcast
+    once before the first step.  Batch statistics follow torch's DistributedDataParallel without SyncBatchNorm: each rank's
+    running buffers move with its own batches, rank 0's are broadcast at every epoch's end (before validation and the
+    checkpoint); training forwards never read them, so only the BatchNorms' running buffers differ from the single-process
+    run.  The per-batch losses stay on the device, are gathered once per epoch and added in global batch order in fp32;
+    ``validate`` shards its batches the same way.  At every epoch's end the ranks compare a bit fingerprint of their state
+    (``exp_avg`` and numpy's generator) and all raise ``RuntimeError`` if it differs.  Rank 0 writes the checkpoint (today's
+    keys), a barrier follows; the returned history is the same on every rank.
+
     A module whose model has dropout enabled or uses batch statistics is put into ``train()`` mode here and stays in it; validation runs under
     ``no_grad`` on the inference path, which never drops.
 
@@ -193,10 +273,17 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
         raise ValueError("accumulate_grad_batches and val_frequency must be at least 1, max_epochs at least 0")
     datamodule.setup("fit")   # (returns at once when the caller has set the data up already)
     loader = datamodule.train_dataloader()
-    steps_per_epoch = math.ceil(len(loader) / accumulate)
+    world = 1
+    if process_group is not None:
+        import torch.distributed as dist
+
+        world = dist.get_world_size(process_group)
+    steps_per_epoch = len(step_groups(len(loader), accumulate, world))
     extra = {} if ema_decay is None else {"ema_decay": ema_decay}
-    conf = pl_module.configure_optimizers(max(1, steps_per_epoch * int(max_epochs)), max_grad_norm=max_grad_norm, accumulate=accumulate,
-                                          **extra)
+    if process_group is not None:
+        extra.update(process_group=process_group, staged=staged)
+    conf = pl_module.configure_optimizers(max(1, steps_per_epoch * int(max_epochs)), max_grad_norm=max_grad_norm,
+                                          accumulate=accumulate * world, **extra)
     optimizer, scheduler = conf["optimizer"], conf["lr_scheduler"]["scheduler"]
     device = optimizer.device
     first_epoch, global_step = 0, 0
@@ -222,6 +309,9 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     history = {"train_loss": [], "val": [], "optimizer": optimizer, "scheduler": scheduler, "loss_scaler": scaler}
     step = optimizer.step if scaler is None else (lambda accumulated: optimizer.step(accumulated=accumulated, loss_scaler=scaler))
     optimizer.zero_grad()
+    if process_group is not None:
+        return _fit_sharded(pl_module, datamodule, loader, int(max_epochs), first_epoch, global_step, accumulate, int(val_frequency),
+                            checkpoint_path, log, ema_decay, optimizer, scheduler, scaler, step, history, process_group, staged)
     for epoch in range(first_epoch, int(max_epochs)):
         loss_sum = torch.zeros((), dtype=torch.float32, device=device)
         batches = pending = 0
@@ -261,6 +351,82 @@ def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_freque
     return history
 
 
+def _fit_sharded(pl_module, datamodule, loader, max_epochs, first_epoch, global_step, accumulate, val_frequency, checkpoint_path, log,
+                 ema_decay, optimizer, scheduler, scaler, step, history, group, staged) -> dict:
+    """``fit``'s epochs on the ranks of ``group`` (its docstring has the rules); everything before the first epoch is done"""
+    import torch.distributed as dist
+
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    model, device = pl_module.model, optimizer.device
+    _broadcast(list(pl_module.parameters()) + list(pl_module.buffers()), group, staged)
+    sharded = loader.shard(rank, world)
+    groups = step_groups(len(loader), accumulate, world)
+
+    def close(count):
+        step(accumulated=count)
+        scheduler.step()
+
+    for epoch in range(first_epoch, max_epochs):
+        losses = torch.zeros(max(len(loader), 1), dtype=torch.float32, device=device)
+        rng = model.train_settings.dropout_rng   # (None, or the live {"seed", "calls"})
+        calls0 = None if rng is None else int(rng["calls"])
+        advance = 0 if rng is None else 2 * len(model.transformer_blocks.layers) + (12 if model.frontend_dropout else 0)
+        done = 0
+        for j, batch in sharded:
+            while j >= groups[done][0] + groups[done][1]:
+                close(groups[done][1])
+                done += 1
+            if rng is not None:
+                rng["calls"] = calls0 + j * advance
+            loss = pl_module.training_step(batch, j)
+            if rng is not None and rng["calls"] != calls0 + (j + 1) * advance:
+                raise RuntimeError(f"a training forward drew {rng['calls'] - calls0 - j * advance} dropout streams, {advance} were "
+                                   "expected: the ranks' streams would not be the single-process ones")
+            if scaler is None:
+                loss.backward()
+            else:
+                (loss * scaler.scale).backward()
+            losses[j] = loss.detach()
+        while done < len(groups):
+            close(groups[done][1])
+            done += 1
+        global_step += len(groups)
+        if rng is not None:
+            rng["calls"] = calls0 + len(loader) * advance
+        if model.batch_statistics:
+            _broadcast(list(pl_module.buffers()), group, staged)
+        # the epoch's read-back: the ranks' losses, merged and added in global batch order as the single process adds them
+        gathered = [None] * world
+        dist.all_gather_object(gathered, (losses.cpu().numpy(), _fingerprint(optimizer)), group=group)
+        prints = [g[1] for g in gathered]
+        if any(p != prints[0] for p in prints):
+            odd = [r for r, p in enumerate(prints) if p != prints[0]]
+            raise RuntimeError(f"epoch {epoch}: ranks {odd} have diverged from rank 0 (optimiser moments or numpy's generator): "
+                               f"fingerprints {prints}")
+        total = np.float32(0.0)
+        for j in range(len(loader)):
+            total = total + gathered[j % world][0][j]
+        mean = float(total) / max(len(loader), 1)
+        history["train_loss"].append(mean)
+        line = f"epoch {epoch}: train_loss {mean:.6f}, {global_step} steps, lr {scheduler.get_last_lr()[0]:.3e}, {world} ranks"
+        if (epoch + 1) % val_frequency == 0:
+            averaged = ema_decay is not None and optimizer.flat_state()["n_averaged"] > 0
+            with optimizer.averaged_weights() if averaged else contextlib.nullcontext():
+                metrics = validate(pl_module, datamodule, group)
+            history["val"].append((epoch, metrics))
+            if averaged:
+                line += f", validated on the averaged weights (decay {ema_decay:g})"
+            line += "".join(f", {k} {v:.4f}" for k, v in metrics.items())
+        if checkpoint_path is not None:
+            if rank == 0:
+                save_checkpoint(checkpoint_path, pl_module, optimizer, scheduler, epoch, global_step, scaler)
+            dist.barrier(group=group)
+        if rank == 0:
+            log(line)
+    history["epoch"], history["global_step"] = max(first_epoch, max_epochs) - 1, global_step
+    return history
+
+
 # ---- command line (launch_scripts/train.py:135-291) ------------------------------------------------------------------------------
 def _ema_decay(text: str) -> float:
     value = float(text)
@@ -281,6 +447,13 @@ def get_parser() -> argparse.ArgumentParser:
                    help="checkpoint (name, path or URL) to start from; default: a new model with the reference's initialisation")
     p.add_argument("--output", type=str, required=True, help="where the checkpoint is written at each epoch's end")
     p.add_argument("--gpu", type=int, default=0, help="index of the GPU to use (default: %(default)s)")
+    p.add_argument("--gpus", metavar="N", type=int, default=1,
+                   help="data-parallel training on N GPUs of this node, one process each: the run launches itself under "
+                        "torch.distributed.run (a run already started by torchrun is taken as it is); one optimiser step then "
+                        "closes --accumulate-grad-batches x N batches (default: %(default)s, a single process without a process group)")
+    p.add_argument("--share-gpu", action="store_true",
+                   help="development / tests, with --gpus N > 1: all N ranks run on --gpu and the collectives go over gloo through "
+                        "host copies -- the N-rank code path on a node with one GPU; not a measurement")
     p.add_argument("--n-layers", type=int, default=6, help="main transformer layers of a new model (default: %(default)s)")
     p.add_argument("--transformer-dim", type=int, default=512, help="width of a new model (default: %(default)s)")
     p.add_argument("--lr", type=float, default=0.0008)
@@ -344,12 +517,92 @@ def get_parser() -> argparse.ArgumentParser:
     return p
 
 
+def _free_port() -> int:
+    import socket
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _launch_ranks(args, argv) -> int:
+    """--gpus N outside torchrun: check the node's GPUs, then run this command line once per rank under torch.distributed.run"""
+    import subprocess
+
+    have = torch.cuda.device_count()
+    if have < args.gpus and not (args.share_gpu and have >= 1):
+        raise SystemExit(f"beat_this_amd.train: --gpus {args.gpus} but this node shows {have} GPU(s) (torch.cuda.device_count()); "
+                         "run with --gpus <= that, one process per GPU")
+    env = dict(os.environ)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # (the ranks import the package this process runs)
+    env["PYTHONPATH"] = os.pathsep.join([root] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), "-m", "beat_this_amd.train", *(sys.argv[1:] if argv is None else argv)]
+    return subprocess.run(cmd, env=env).returncode
+
+
+def _join_ranks(args):
+    """A rank of a --gpus N run under torchrun: its device, its share of the cores, and the process group -> (device, group,
+    rank); the rules are bench.py's"""
+    import torch.distributed as dist
+    from datetime import timedelta
+
+    world, rank, local_rank = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
+    if world != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    index = args.gpu if args.share_gpu else local_rank
+    if index >= torch.cuda.device_count():
+        raise SystemExit(f"beat_this_amd.train: LOCAL_RANK {local_rank} but this node shows {torch.cuda.device_count()} GPU(s)")
+    try:   # every rank its own slice of the cores, torch's intra-op pool sized to it
+        cores = sorted(os.sched_getaffinity(0))
+        per_rank = max(1, len(cores) // int(os.environ.get("LOCAL_WORLD_SIZE", world)))
+        mine = cores[local_rank * per_rank: (local_rank + 1) * per_rank] or cores
+        os.sched_setaffinity(0, mine)
+        torch.set_num_threads(max(1, min(len(mine), 16)))
+    except (AttributeError, OSError) as e:   # (no affinity interface: leave the scheduler alone)
+        print(f"rank {rank}: host threads not pinned ({type(e).__name__})", file=sys.stderr)
+    torch.cuda.set_device(index)
+    device = torch.device("cuda", index)
+    # (a collective whose peer died is aborted after three minutes; a rank that RAISES takes the job down at once, see main)
+    if args.share_gpu:
+        dist.init_process_group("gloo", timeout=timedelta(seconds=180))
+    else:
+        dist.init_process_group("nccl", device_id=device, timeout=timedelta(seconds=180))
+    return device, dist.group.WORLD, rank
+
+
 def main(argv=None) -> int:
     parser = get_parser()
     args = parser.parse_args(argv)
-    from .dataset import BeatDataModule
-    from .inference import load_checkpoint
-    from .model.pl_module import PLBeatThis
+    if args.gpus < 1:
+        parser.error(f"--gpus must be at least 1, got {args.gpus}")
+    if args.share_gpu and args.gpus < 2:
+        parser.error("--share-gpu needs --gpus N with N > 1: it puts the N ranks of a data-parallel run on one GPU")
+    _check_recipe(parser, args)
+    if args.gpus > 1 and "RANK" not in os.environ:
+        return _launch_ranks(args, argv)
+    if args.gpus == 1:
+        return _run(args)
+    return run_rank(lambda: _run(args, ranks=True))
+
+
+def run_rank(body):
+    """``body()`` as one rank of a multi-process job.  A rank that raises takes the whole job down AT ONCE (bench.py's rule):
+    the traceback is printed and the process leaves through ``os._exit``, without the interpreter's teardown -- which would
+    wait for the process group, while the peers wait in a collective for this rank -- so the launcher sees a dead rank and
+    ends the others."""
+    try:
+        return body()
+    except BaseException:   # noqa: BLE001
+        import traceback
+
+        traceback.print_exc()
+        sys.stderr.flush()
+        sys.stdout.flush()
+        os._exit(1)
+
+
+def _check_recipe(parser, args) -> None:
     from .model.settings import TrainSettings
 
     asked = TrainSettings(frontend_trainable=args.train_frontend, batch_statistics=args.batch_statistics,
@@ -365,13 +618,25 @@ def main(argv=None) -> int:
         if operand is not None and precision != "16-mixed":   # (fp16 too: the flag says nothing about a 32-true part)
             parser.error(f"{flag} needs {part} 16-mixed: it is the operand format of 16-mixed products")
 
+
+def _run(args, ranks: bool = False) -> int:
+    """the run of one process: the whole of a --gpus 1 run, or (``ranks``) one rank of a data-parallel one"""
+    from .dataset import BeatDataModule
+    from .inference import load_checkpoint
+    from .model.pl_module import PLBeatThis
+
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     if not torch.cuda.is_available():
         print("beat_this_amd.train needs a ROCm GPU: this package has no CPU path", file=sys.stderr)
         return 2
-    device = torch.device(f"cuda:{args.gpu}")
-    print("Starting a run with:", vars(args))
+    group, rank = None, 0
+    if ranks:
+        device, group, rank = _join_ranks(args)
+    else:
+        device = torch.device(f"cuda:{args.gpu}")
+    say = print if rank == 0 else (lambda *a, **k: None)   # (only rank 0 prints the run's lines)
+    say("Starting a run with:", vars(args))
     enabled = {name: dict(settings) for name, settings in AUGMENTATIONS.items() if getattr(args, f"{name}_augmentation")}
     datamodule = BeatDataModule(args.data_dir, batch_size=args.batch_size, train_length=args.train_length, spect_fps=FPS,
                                 test_dataset="gtzan", length_based_oversampling_factor=args.length_based_oversampling_factor,
@@ -379,7 +644,7 @@ def main(argv=None) -> int:
                                 device=device)
     datamodule.setup("fit")   # (the class weights below need the training set; fit()'s own setup call then returns at once)
     pos_weights = datamodule.get_train_positive_weights(widen_target_mask=POS_WEIGHT_WIDEN)
-    print("Using positive weights:", pos_weights)
+    say("Using positive weights:", pos_weights)
     start = args.resume_checkpoint or args.checkpoint
     ckpt = load_checkpoint(start, "cpu") if start else None
     arch = dict(transformer_dim=args.transformer_dim, n_layers=args.n_layers)
@@ -400,11 +665,18 @@ def main(argv=None) -> int:
     if ckpt is not None and not args.resume_checkpoint:   # (a resumed run's weights are restored by fit() with the rest)
         pl_module.load_state_dict(ckpt["state_dict"])
     pl_module.to(device)
+    extra = {}
+    if group is not None:
+        extra.update(process_group=group, staged=args.share_gpu)
     with torch.cuda.device(device):
         fit(pl_module, datamodule, args.max_epochs, accumulate_grad_batches=args.accumulate_grad_batches,
             val_frequency=args.val_frequency, max_grad_norm=args.max_grad_norm, checkpoint_path=args.output,
-            resume=ckpt if args.resume_checkpoint else None, ema_decay=args.ema_decay)
-    print("wrote", args.output)
+            resume=ckpt if args.resume_checkpoint else None, ema_decay=args.ema_decay, log=say, **extra)
+    say("wrote", args.output)
+    if group is not None:
+        import torch.distributed as dist
+
+        dist.destroy_process_group()
     return 0
 
 

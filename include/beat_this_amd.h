@@ -1088,6 +1088,25 @@ int bt_pcm_decode(void* stream, const uint8_t* d_src, int format, int channels, 
 /* the host twin: plain sequential C++ over the same inline helpers; src and out in HOST memory, any alignment of src */
 int bt_pcm_decode_host(const uint8_t* src, int format, int channels, int64_t n_frames, float* out);
 
+/* ---- data-parallel training: the rank-ordered gradient sum (csrc/reduce.hip) ----------------------------
+ * `world` fp32 arrays of n elements, rank r's at d_parts + r * stride (elements), are added element by element in RANK ORDER,
+ * one rounded fp32 add at a time and nothing else:
+ *     out[i] = (((parts[0 * stride + i] + parts[1 * stride + i]) + parts[2 * stride + i]) + ...) + parts[(world - 1) * stride + i]
+ * for i = 0 .. n - 1.  That is the chain autograd's in-place accumulation forms over the same gradients in the same order, so
+ * a sum over ranks has the bits of an accumulation over batches.  NaN and +-inf propagate as IEEE addition propagates them;
+ * denormals are kept; world == 1 copies.  The device and the host twin agree bit for bit.
+ * d_out may be exactly d_parts (rank 0's part is overwritten in place); any other overlap of [d_out, d_out + n) with the parts is
+ * BT_ERR_ARG.  Also BT_ERR_ARG, before any launch: world outside 1 .. BT_REDUCE_MAX_WORLD, n < 0, stride < n with world > 1, a
+ * null or not 4-byte aligned pointer.  n == 0 launches nothing.
+ * One workgroup of 256 threads sums one chunk of BT_REDUCE_CHUNK elements; 16 bytes per access when d_parts and d_out are
+ * 16-byte aligned and stride is a multiple of 4 (or world == 1), one element per lane otherwise and for the tail n % 4.  Only
+ * out[0 .. n) is written; the parts are only read.  No workspace, no atomics, no synchronisation. */
+#define BT_REDUCE_MAX_WORLD 16
+#define BT_REDUCE_CHUNK 4096
+int bt_grad_rank_sum(void* stream, const float* d_parts, int64_t stride, int world, int64_t n, float* d_out);
+/* HOST: the same adds in the same order on host arrays */
+int bt_grad_rank_sum_host(const float* parts, int64_t stride, int world, int64_t n, float* out);
+
 #ifdef __cplusplus
 }
 #endif
