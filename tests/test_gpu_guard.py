@@ -700,11 +700,12 @@ def test_peaks_single_and_batch_guarded_and_poisoned():
     assert np.array_equal(res["idx"].numpy(), np.concatenate([_peaks_host(two[0]), _peaks_host(two[1])]))
 
 
-@pytest.mark.parametrize("sr", [44100, 48000])
+@pytest.mark.parametrize("sr", [44100, 48000, 16000, 88200, 110250, 352800])
 def test_resample_single_and_batch_guarded_and_poisoned(sr):
     """bt_resample and bt_resample_batch (66 ragged tracks, each in its own guarded allocation: a read past a track's end
     meets its band) against the float64 polyphase restatement test_gpu_kernels.py uses (scipy resample_poly via the oracle's
-    soxr shim), relative 5e-6"""
+    soxr shim), relative 5e-6.  352.8 kHz (3001 taps per output, the input read from global memory) runs 24 shorter tracks.
+    Some tracks start at an odd output offset: decimate_kernel then stores its outputs one by one, not as two 16-byte words."""
     import importlib.util
     import os
     from math import gcd
@@ -721,12 +722,16 @@ def test_resample_single_and_batch_guarded_and_poisoned(sr):
     up, down = 22050 // g, sr // g
     h, half = _resample_filter(up, down, dev())
     rng = np.random.default_rng(sr)
-    lens = [64, 65, 1000, sr * 3 + 777] + [int(v) for v in rng.integers(100, 20000, 62)]
+    if sr == 352800:
+        lens = [64, 65, 1000, sr // 3 + 777] + [int(v) for v in rng.integers(100, 40000, 20)]
+    else:
+        lens = [64, 65, 1000, sr * 3 + 777] + [int(v) for v in rng.integers(100, 20000, 62)]
     xs = [torch.from_numpy(rng.normal(0, 0.3, n).astype(np.float32)) for n in lens]
     n_out = [-(-n * up // down) for n in lens]
     refs = [torch.from_numpy(shim.resample(x.double().numpy(), sr, 22050)) for x in xs]
     assert [len(r) for r in refs] == n_out
     out_off = np.concatenate([[0], np.cumsum(n_out)])
+    assert any(int(o) % 2 == 1 and n > 8 for o, n in zip(out_off[:-1], n_out))   # a track on no 16-byte boundary
 
     def call(p):
         tab = torch.tensor([[p[f"x{i}"], lens[i], int(out_off[i]), n_out[i]] for i in range(len(lens))], dtype=torch.int64).to(dev())

@@ -232,10 +232,11 @@ def test_gemm2_resid_writes_shadow():
     assert err < 1e-5
 
 
-@pytest.mark.parametrize("sr_in", [44100, 48000, 16000, 32000, 11025])
+@pytest.mark.parametrize("sr_in", [44100, 48000, 16000, 32000, 11025, 8000, 66150, 88200, 96000, 110250, 176400, 352800])
 def test_resample_gpu_matches_polyphase_oracle(sr_in):
     """bt_resample against the oracle's soxr stand-in (oracle/shims/soxr: the same published HQ specification
-    restated with scipy.signal.firwin / resample_poly in float64); ragged length, both directions, prime-ish ratios."""
+    restated with scipy.signal.firwin / resample_poly in float64); ragged length, both directions, prime-ish ratios, every
+    decimator and every staging route of launch_resample (a third of a second of the rates above 48 kHz)."""
     import importlib.util
     import os
     from conftest import ROOT
@@ -245,7 +246,7 @@ def test_resample_gpu_matches_polyphase_oracle(sr_in):
     shim = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(shim)
 
-    n = sr_in * 3 + 777
+    n = sr_in * 3 + 777 if sr_in <= 48000 else sr_in // 3 + 777
     x = (_mk((n,), 120 + sr_in, 0.3)).float()
     y = resample_gpu(x.to(dev()), sr_in, 22050).cpu().double()
     ref = torch.from_numpy(shim.resample(x.double().numpy(), sr_in, 22050))

@@ -782,7 +782,8 @@ def test_audio2beats_one_call_is_bit_identical_to_the_stage_by_stage_path(mode):
     a2b = Audio2Beats(checkpoint_path=None, device=dev(), float16=mode, dbn=False)
     a2b.model = _model("small0", 4, "lively")
     cases = [(7.0, 22050, 1), (29.75, 22050, 1), (29.77, 22050, 1), (40.0, 22050, 1), (41.3, 22050, 1), (65.3, 44100, 1),
-             (12.0, 48000, 2), (40.0, 22050, 1), (100.0, 44100, 1), (7.0, 22050, 1)]
+             (12.0, 48000, 2), (40.0, 22050, 1), (100.0, 44100, 1), (7.0, 22050, 1),
+             (3.0, 16000, 1), (3.0, 88200, 1)]      # (the plan with up > down, and with a decimator other than <2>)
     n_fast = 0
     for secs, sr, ch in cases:
         sig = W.synthetic_audio(secs, seed=int(secs * 10) + sr // 1000, sr=sr)
