@@ -130,8 +130,23 @@ def hmms(fps=50):
     return _HMMS[fps]
 
 
-def dbn(act, fps=50):
-    """DBNDownBeatTrackingProcessor.process: (T, 2) activation -> (N, 2) rows (beat time, beat number)"""
+_MODELS = {}
+
+
+def models_for(fps=50, **kw):
+    """the BarHMM list of one table set: PARAMS with `fps` and the overrides in `kw` (such as num_tempi=20)"""
+    p = dict(PARAMS, fps=fps, **kw)
+    key = tuple(sorted(p.items()))
+    if key not in _MODELS:
+        iv = beat_intervals(p["fps"], p["min_bpm"], p["max_bpm"], p["num_tempi"])
+        _MODELS[key] = [BarHMM(nb, iv, p["transition_lambda"], p["observation_lambda"]) for nb in p["beats_per_bar"]]
+    return _MODELS[key]
+
+
+def dbn(act, fps=50, models=None):
+    """DBNDownBeatTrackingProcessor.process: (T, 2) activation -> (N, 2) rows (beat time, beat number); `models`: the
+    list of BarHMM to decode with (default hmms(fps))"""
+    models = hmms(fps) if models is None else models
     act = np.asarray(act, dtype=np.float64)
     first = 0
     idx = np.nonzero(act >= PARAMS["threshold"])[0]
@@ -144,12 +159,12 @@ def dbn(act, fps=50):
     if not act.any():
         return np.empty((0, 2))
     dens = log_densities(act, PARAMS["observation_lambda"])
-    results = [viterbi(h, dens) for h in hmms(fps)]
+    results = [viterbi(h, dens) for h in models]
     best = int(np.argmax([r[1] for r in results]))
     path, logp = results[best]
     if len(path) == 0:
         return np.empty((0, 2))
-    hmm = hmms(fps)[best]
+    hmm = models[best]
     beat_numbers = hmm.positions[path].astype(int) + 1
     beat_range = hmm.pointers[path] >= 1
     idx = np.nonzero(np.diff(beat_range.astype(int)))[0] + 1
@@ -174,7 +189,7 @@ def combined_act(beat, downbeat):
     return np.vstack((np.maximum(bp - dp, eps / 2), dp)).T
 
 
-def postp_dbn(beat, downbeat, fps=50):
+def postp_dbn(beat, downbeat, fps=50, models=None):
     """(beat times, downbeat times) of one track of logits, as Postprocessor(type="dbn") returns them"""
-    out = dbn(combined_act(beat, downbeat), fps)
+    out = dbn(combined_act(beat, downbeat), fps, models)
     return out[:, 0], out[out[:, 1] == 1][:, 0]

@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+import dbn_cases as D
 import dbn_reference as R
+from dbn_cases import _pulses
 
 
 def _pp(fps=50):
@@ -40,15 +42,48 @@ def test_tables_equal_the_oracle_state_space_and_transitions():
     assert t["spb"] == 1449 and t["n_hmm"] == 2 and list(t["beats"][:2]) == [3, 4]
     assert list(t["num_states"][:2]) == [4347, 5796]
     assert t["obs_norm"] == 15.0 and t["threshold"] == 0.05
-    for h, hmm in enumerate(R.hmms()):
+    assert t["nnz"] == 880   # tempo transitions per beat boundary at 50 fps
+    _compare_tables(t, R.hmms())
+
+
+@pytest.mark.parametrize("ts", D.table_sets()[1:], ids=D.set_id)
+def test_tables_equal_the_oracle_on_the_other_table_sets(ts):
+    """25 fps, 60 fps (8036 of the kernel's 8192 states, 1216 of its 1536 transitions) and the log-spaced interval branch
+    (num_tempi=20 at 50 fps): every constant comes from the oracle"""
+    from beat_this_amd.postprocessor import dbn_tables
+
+    fps, kw = ts
+    _pp()
+    models = R.models_for(fps, **kw)
+    iv = R.beat_intervals(fps, num_tempi=kw.get("num_tempi", 60))
+    t = _parse(dbn_tables(fps, **kw))
+    K = t["K"]
+    assert K == len(iv) and np.array_equal(t["intervals"][:K], iv)
+    assert t["spb"] == iv.sum() and t["n_hmm"] == 2 and list(t["beats"][:2]) == [3, 4]
+    assert list(t["num_states"][:2]) == [3 * iv.sum(), 4 * iv.sum()]
+    assert t["obs_norm"] == 15.0 and t["threshold"] == 0.05
+    if fps == 60:
+        assert (K, t["num_states"][1], t["nnz"]) == (49, 8036, 1216)
+    if fps == 25:
+        assert (K, t["num_states"][1]) == (21, 1428)
+    if kw:   # the log-spaced branch: at least num_tempi intervals, not all consecutive
+        assert K >= kw["num_tempi"] and K < 42 and (np.diff(iv) > 1).any()
+    _compare_tables(t, models)
+
+
+def _compare_tables(t, models):
+    """the parsed blob against the oracle's BarHMM list: states, transitions bit for bit, observation pointers"""
+    K = t["K"]
+    iv = t["intervals"][:K]
+    for h, hmm in enumerate(models):
         assert hmm.num_states == t["num_states"][h]
         assert t["init"][h] == hmm.init   # bit for bit
         # first / last states of every beat
         for b in range(hmm.num_beats):
             assert np.array_equal(hmm.first_states[b], b * t["spb"] + t["first"][:K])
             assert np.array_equal(hmm.last_states[b], b * t["spb"] + t["first"][:K] + iv - 1)
-        # tempo transitions: 880 per beat boundary at 50 fps, same predecessors in the same order, same log probabilities
-        assert hmm.tempo_nnz == t["nnz"] == 880
+        # tempo transitions: same predecessors in the same order, same log probabilities
+        assert hmm.tempo_nnz == t["nnz"]
         for b in range(hmm.num_beats):
             for j in range(K):
                 s = hmm.first_states[b][j]
@@ -85,19 +120,6 @@ def test_viterbi_host_matches_oracle_on_given_densities():
                                                       C.byref(lp)))
             op, ol = R.viterbi(hmm, dens)
             assert lp.value == ol and np.array_equal(path, op), (T, h)
-
-
-def _pulses(T, period, beats_per_bar, phase=3, hi=6.0, lo=-6.0, seed=0):
-    rng = np.random.default_rng(seed)
-    beat = np.full(T, lo) + rng.normal(size=T) * 0.5
-    down = np.full(T, lo) + rng.normal(size=T) * 0.5
-    for n, f in enumerate(np.arange(phase, T, period)):
-        f = int(round(f))
-        if f < T:
-            beat[f] = hi
-            if n % beats_per_bar == 0:
-                down[f] = hi
-    return torch.from_numpy(beat).float(), torch.from_numpy(down).float()
 
 
 def _check(pp, beat, down, mask=None):
@@ -187,3 +209,131 @@ def test_unsupported_parameters_raise():
         dbn_tables(50, min_bpm=1.0, num_tempi=1000)
     with pytest.raises(ValueError):
         dbn_tables(50, beats_per_bar=(3, 4, 5, 6, 7))
+
+
+def test_postprocessor_accepts_6_to_60_fps():
+    from beat_this_amd.postprocessor import Postprocessor
+
+    _pp()
+    for fps in (6, 25, 60):
+        assert Postprocessor(type="dbn", fps=fps).fps == fps
+    with pytest.raises(ValueError, match="8568 states"):
+        Postprocessor(type="dbn", fps=61)
+    for fps in (1, 5):
+        with pytest.raises(ValueError):
+            Postprocessor(type="dbn", fps=fps)
+
+
+def _with_tables(pp, ts):
+    """`pp` on the tables of one table set (num_tempi is not a Postprocessor argument: its tables are swapped)"""
+    from beat_this_amd.postprocessor import DBN, dbn_tables
+
+    fps, kw = ts
+    assert pp.fps == fps
+    if kw:
+        pp._dbn_tables, pp._dbn_dev = dbn_tables(fps, **kw), {}
+        pp.dbn = DBN(pp._dbn_tables, fps)
+    return pp
+
+
+def _pp_for(ts):
+    return _with_tables(_pp(ts[0]), ts)
+
+
+def _host_rows(pp, beat, down):
+    """bt_dbn_host: the (frame, beat number) int32 rows of one track"""
+    from beat_this_amd import _lib
+
+    lb, ld = np.ascontiguousarray(beat.double().numpy()), np.ascontiguousarray(down.double().numpy())
+    rows = np.zeros((max(len(lb), 1), 2), np.int32)
+    n = C.c_int32(0)
+    _lib.check(_lib.lib().bt_dbn_host(pp._dbn_tables.ctypes.data, lb.ctypes.data, ld.ctypes.data, len(lb), rows.ctypes.data, C.byref(n)))
+    return rows[: n.value]
+
+
+_SETS = list(enumerate(D.table_sets()))
+
+
+@pytest.mark.parametrize("name", list(D.cases(50)))
+@pytest.mark.parametrize("si,ts", _SETS, ids=[D.set_id(ts) for _, ts in _SETS])
+def test_case_table_host_decoder_matches_oracle(si, ts, name):
+    """every case of tests/dbn_cases.py through Postprocessor on CPU tensors, bt_dbn_host and bt_dbn_host_act: rows
+    identical to the oracle's (beat times, beat numbers), outputs float64"""
+    pp = _pp_for(ts)
+    fps = ts[0]
+    beat, down = D.cases(fps)[name]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        want = D.expected(si, name)
+        wb, wd = D.split(want)
+        gb, gd = pp(beat, down)
+        assert gb.dtype == np.float64 and gd.dtype == np.float64
+        assert np.array_equal(gb, wb) and np.array_equal(gd, wd)
+        rows = _host_rows(pp, beat, down)
+        assert np.array_equal(rows[:, 0] / float(fps), want[:, 0]) and np.array_equal(rows[:, 1], want[:, 1])
+        act = pp.dbn(R.combined_act(beat, down))
+        assert act.dtype == np.float64 and np.array_equal(act, want)
+
+
+def test_case_table_does_not_degenerate():
+    """guards on the oracle's own output at 50 fps: each case still exercises what it was written for"""
+    e = lambda name: D.expected(0, name)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for name in ("silent", "lone0", "all_sat", "nan_down"):
+            assert len(e(name)) == 0, name
+        assert set(D.EMPTY) == {"silent", "lone0", "all_sat", "nan_down"}
+        assert np.array_equal(e("lone17")[:, 0] * 50, [17]) and np.array_equal(e("lone_last")[:, 0] * 50, [299])
+        assert len(e("lead_tail")) == 16 and e("lead_tail")[0, 0] * 50 == 140
+        assert e("fill_m1000")[0, 0] * 50 >= 50
+        for bpm in (56, 90, 120, 200):
+            assert e(f"bpm{bpm}_3")[:, 1].max() == 3 and e(f"bpm{bpm}_4")[:, 1].max() == 4, bpm
+        assert len(e("nan_beat")) == 16 and len(e("inf_beat")) == 16
+    # the trim is real: lead_tail keeps 16 periods of a 748-frame track
+    beat, down = D.cases(50)["lead_tail"]
+    assert len(beat) == 137 + 400 + 211
+    # sat40 / all_sat really make the no-beat density -inf, fill_m1000 really underflows the sigmoid to eps / 2
+    act = R.combined_act(*D.cases(50)["all_sat"])
+    assert (1.0 - act.sum(1) == 0).all()
+    act = R.combined_act(*D.cases(50)["sat40"])
+    assert (1.0 - act.sum(1) == 0).any()
+    act = R.combined_act(*D.cases(50)["fill_m1000"])
+    assert (act[:50] == 0.5e-5).all()
+
+
+@pytest.mark.parametrize("si,ts", _SETS, ids=[D.set_id(ts) for _, ts in _SETS])
+def test_viterbi_host_matches_oracle_on_non_finite_densities(si, ts):
+    """10 % of the entries -inf, one NaN entry, the no-beat column all -inf, and a NaN in the last frame (the final argmax's
+    NaN rule): path and log probability equal the oracle's (== or both NaN)"""
+    from beat_this_amd import _lib
+
+    pp = _pp_for(ts)
+    fps, kw = ts
+    for kind in D.DENSITY_KINDS:
+        for T in (40, 300):
+            dens = D.densities(kind, T)
+            for h, hmm in enumerate(R.models_for(fps, **kw)):
+                path = np.zeros(T, np.int32)
+                lp = C.c_double()
+                _lib.check(_lib.lib().bt_dbn_viterbi_host(pp._dbn_tables.ctypes.data, h, dens.ctypes.data, T, path.ctypes.data,
+                                                          C.byref(lp)))
+                op, ol = R.viterbi(hmm, dens)
+                assert lp.value == ol or (np.isnan(lp.value) and np.isnan(ol)), (kind, T, h)
+                assert np.array_equal(path[: len(op)], op), (kind, T, h)
+                if kind in ("inf10", "col0"):
+                    assert ol == -np.inf and len(op) == 0, (kind, T, h)
+                elif kind == "nan1":
+                    assert np.isfinite(ol) and len(op) == T, (kind, T, h)
+                else:
+                    assert np.isnan(ol) and len(op) == T, (kind, T, h)
+
+
+@pytest.mark.parametrize("P,bpb,phase", D.clean_trains())
+def test_clean_train_decodes_to_its_own_beats(P, bpb, phase):
+    """spec level, no oracle: a clean train of period P frames (215 .. 55 bpm at 50 fps) decodes to exactly its beat frames,
+    numbered 1 .. beats_per_bar from the first one.  (Default tables only: at 25 and 60 fps the slowest 3/4 trains decode
+    at double tempo, the model's own octave choice, and the oracle agrees with it.)"""
+    pp = _pp()
+    beat, down, frames, numbers = D.clean_train(P, bpb, phase)
+    rows = _host_rows(pp, beat, down)
+    assert np.array_equal(rows[:, 0], frames) and np.array_equal(rows[:, 1], numbers)
+    gb, gd = pp(beat, down)
+    assert np.array_equal(gb, frames / 50.0) and np.array_equal(gd, frames[numbers == 1] / 50.0)

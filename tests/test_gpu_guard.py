@@ -783,7 +783,8 @@ def test_logmel_single_and_batch_guarded_and_poisoned():
 
 
 def test_dbn_decode_and_viterbi_guarded():
-    """bt_dbn_decode over 68 ragged tracks (one-frame and 1488 .. 1501-frame ones among them) and bt_dbn_viterbi, against the
+    """bt_dbn_decode over 71 ragged tracks (one-frame and 1488 .. 1501-frame ones among them, and an all-silent track, a lone
+    frame 0 and 100 silent leading frames: a count of 0 and a large trim offset) and bt_dbn_viterbi, against the
     host decoder bt_dbn_host / bt_dbn_viterbi_host (test_dbn.py holds those to tests/dbn_reference.py bit for bit).
     The DBN workspace is zero-filled in every run, its bands poisoned: its info, state and backpointer words are indices
     (dbn.hip ws_layout: a backpointer selects an interval of a beat and, during the backtrack, the next backpointer to read),
@@ -798,10 +799,16 @@ def test_dbn_decode_and_viterbi_guarded():
     d_tab = pp._dbn_device_tables(dev())
     rng = np.random.default_rng(9)
     frames = [1, 1488, 1489, 1500, 1501, 13, 14] + [int(v) for v in rng.integers(2, 900, 61)]
+    quiet = {20: 300, 40: 200, 60: 400}   # position -> frames: all silent, a lone frame 0, 100 silent leading frames
+    for k in sorted(quiet):
+        frames.insert(k, quiet[k])
     n, total = len(frames), sum(frames)
     off = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
     beat = (rng.normal(size=total) * 3 - 1).astype(np.float32)
     down = (rng.normal(size=total) * 3 - 3).astype(np.float32)
+    for k, head in ((20, 300), (40, 200), (60, 100)):   # the count-0 and large-`first` writes, between ordinary tracks
+        beat[off[k]:off[k] + head] = down[off[k]:off[k] + head] = -8.0
+    beat[off[40]] = 8.0
     spans = np.stack([off[:-1], total + off[:-1], np.asarray(frames), off[:-1]], 1).astype(np.int32)
     wsb = lib.bt_dbn_workspace_bytes(tables, n, total)
 
@@ -820,6 +827,7 @@ def test_dbn_decode_and_viterbi_guarded():
         rows = np.zeros((max(hi - lo, 1), 2), np.int32)
         cnt = C.c_int32(0)
         L.check(lib.bt_dbn_host(tables, lb.ctypes.data, ld.ctypes.data, hi - lo, rows.ctypes.data, C.byref(cnt)))
+        assert (cnt.value == 0) if k in (20, 40) else (k != 60 or (cnt.value > 0 and rows[0, 0] >= 100)), (k, cnt.value)
         assert int(res["counts"][k]) == cnt.value, (k, hi - lo)
         assert np.array_equal(res["rows"][pos:pos + 2 * cnt.value].numpy(), rows[:cnt.value].reshape(-1)), (k, hi - lo)
         pos += 2 * cnt.value
