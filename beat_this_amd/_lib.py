@@ -271,6 +271,12 @@ EXPORTS = {
                                   C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bt_beat_metrics_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
                                        C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "bt_beat_metrics_ext_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64]),
+    "bt_beat_metrics_ext": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                      C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
+    "bt_beat_metrics_ext_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                           C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
     "bt_bce_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "bt_bce_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                               C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,

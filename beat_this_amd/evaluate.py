@@ -2,14 +2,17 @@
 (README "Reproducing metrics from the paper") without Lightning, pandas or mir_eval.
 
     python -m beat_this_amd.evaluate --models final0.ckpt --bundle data/audio/spectrograms/gtzan.npz \\
-        --annotations data/annotations [--dbn] [--eval-trim-beats 5] [--loss] [--ema] [--dump-predictions preds.npz]
+        --annotations data/annotations [--dbn] [--eval-trim-beats 5] [--loss] [--ema] [--all-metrics]
+        [--dump-predictions preds.npz]
 
 Each bundle is one dataset (its file stem, e.g. ``gtzan``), holding ``<stem>/track`` spectrograms as the reference's
 preprocessing writes them; the beats of piece ``<stem>`` are read from ``<annotations>/<dataset>/annotations/beats/<stem>.beats``
 (dataset.py:108-124).  Predictions go through predict_bundle and the Postprocessor (minimal or DBN), and beats and downbeats are
 scored in one bt_beat_metrics call each (metrics.py).  With ``--loss`` the test loss of the reference's PLBeatThis.test_step
 (pl_module.py:99-114, 222-229) joins the metrics: the checkpoint's loss pair (loss.losses_from_hparams) on framewise targets
-built as the reference's prepare_annotations builds them, each piece scored alone in one bt_bce_loss call per target."""
+built as the reference's prepare_annotations builds them, each piece scored alone in one bt_bce_loss call per target.
+With ``--all-metrics`` the rest of mir_eval.beat (Goto, P-score, Information gain) joins them, from one bt_beat_metrics_ext
+call per target."""
 from __future__ import annotations
 
 import argparse
@@ -21,6 +24,7 @@ import numpy as np
 
 FPS = 50
 TARGET_KEYS = ("F-measure", "Cemgil", "CMLt", "AMLt")
+EXTENDED_KEYS = ("Goto", "P-score", "Information gain")   # evaluate_bundle(extended=True), --all-metrics
 
 
 def load_beat_annotations(path):
@@ -84,7 +88,7 @@ def _bundle_pieces(bundle, names):
 
 
 def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float16=True, dbn=False, eval_trim_beats=5,
-                    device="cuda", spect2frames=None, loss=False, hyper_parameters=None):
+                    device="cuda", spect2frames=None, loss=False, hyper_parameters=None, extended=False):
     """Predict and score every piece of one bundle (or of a list of bundles, one dataset each).
 
     checkpoint: what Spect2Frames accepts (a local checkpoint file or a loaded checkpoint dict); ``spect2frames``: an
@@ -99,10 +103,16 @@ def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float1
     loss_total, the checkpoint's test loss per piece -- the loss type and pos_weights from ``hyper_parameters``, default the
     checkpoint's), "averaged" and "dataset_metrics" (the means
     the script prints), "predictions" ([(beats, downbeats)]), "truth" ([(beats, downbeats)] within [0, frames / fps)) and
-    "raw" (beat_metrics_many's full output for "beat" and "downbeat")."""
+    "raw" (beat_metrics_many's full output for "beat" and "downbeat").
+
+    extended: also mir_eval.beat's goto, p_score and information_gain with its default arguments, as Goto_beat, P-score_beat,
+    Information gain_beat and the _downbeat ones in "metrics", "averaged" and "dataset_metrics"; "raw" then carries
+    beat_metrics_many's extended columns.  A piece whose P-score is undefined (all its reference beats in one 10 ms index,
+    where mir_eval raises) has NaN there, the averages of that key are np.nanmean's, and "p_score_undefined" lists such
+    pieces per target."""
     from .bundle import SpectBundle, predict_bundle
     from .inference import Spect2Frames
-    from .metrics import beat_metrics_many
+    from .metrics import STATUS_PSCORE, beat_metrics_many, invalid_tracks_error
     from .postprocessor import Postprocessor
 
     s2f = spect2frames if spect2frames is not None else Spect2Frames(checkpoint, device, float16=float16)
@@ -132,14 +142,27 @@ def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float1
                     targets.append(framewise_targets(ann, frames, has_db))
     raw = {}
     metrics = {}
+    undefined = {}
     for t, target in enumerate(("beat", "downbeat")):
-        res = beat_metrics_many([x[t] for x in truths], [x[t] for x in preds], eval_trim_beats=eval_trim_beats,
-                                device=s2f.device)
+        if extended:   # (an undefined P-score is no invalid piece here: it is reported, and every other status raises)
+            res = beat_metrics_many([x[t] for x in truths], [x[t] for x in preds], eval_trim_beats=eval_trim_beats,
+                                    device=s2f.device, extended=True, raise_on_invalid=False)
+            err = invalid_tracks_error(res["status_ext"], ignore=STATUS_PSCORE)
+            if err is not None:
+                raise err
+            undefined[target] = [pieces[i] for i in np.nonzero(res["status_ext"])[0]]
+        else:
+            res = beat_metrics_many([x[t] for x in truths], [x[t] for x in preds], eval_trim_beats=eval_trim_beats,
+                                    device=s2f.device)
         raw[target] = res
         metrics[f"F-measure_{target}"] = res["F-measure"]
         metrics[f"Cemgil_{target}"] = res["Cemgil_reported"]
         metrics[f"CMLt_{target}"] = res["CMLt"]
         metrics[f"AMLt_{target}"] = res["AMLt"]
+    if extended:
+        for target in ("beat", "downbeat"):
+            for k in EXTENDED_KEYS:
+                metrics[f"{k}_{target}"] = raw[target][k]
     if loss:
         from .loss import losses_from_hparams, piece_losses
 
@@ -150,10 +173,19 @@ def evaluate_bundle(checkpoint, bundle_path, annotation_root, names=None, float1
                                                 masks=[np.full(t[1].size, t[2], np.float32) for t in targets], names=pieces)
         metrics["loss_total"] = metrics["loss_beat"] + metrics["loss_downbeat"]
     dataset = np.asarray(datasets)
-    averaged = {k: np.mean(v) for k, v in metrics.items()}
-    dataset_metrics = {k: {d: np.mean(v[dataset == d]) for d in np.unique(dataset)} for k, v in metrics.items()}
-    return dict(piece=np.asarray(pieces), dataset=dataset, metrics=metrics, averaged=averaged, dataset_metrics=dataset_metrics,
-                predictions=preds, truth=truths, raw=raw)
+
+    def mean(k, v):   # (only the P-score can be undefined on a valid piece)
+        if not k.startswith("P-score_") or not np.isnan(v).any():
+            return np.mean(v)
+        return np.nanmean(v) if not np.isnan(v).all() else np.nan
+
+    averaged = {k: mean(k, v) for k, v in metrics.items()}
+    dataset_metrics = {k: {d: mean(k, v[dataset == d]) for d in np.unique(dataset)} for k, v in metrics.items()}
+    out = dict(piece=np.asarray(pieces), dataset=dataset, metrics=metrics, averaged=averaged, dataset_metrics=dataset_metrics,
+               predictions=preds, truth=truths, raw=raw)
+    if extended:
+        out["p_score_undefined"] = undefined
+    return out
 
 
 def write_predictions(fn, preds, piece):
@@ -192,6 +224,8 @@ def get_parser() -> argparse.ArgumentParser:
     p.add_argument("--loss", default=False, action=argparse.BooleanOptionalAction,
                    help="also report the checkpoint's test loss (loss_beat, loss_downbeat, loss_total; its loss_type and "
                         "pos_weights) as the reference's test step logs it")
+    p.add_argument("--all-metrics", dest="all_metrics", default=False, action="store_true",
+                   help="also report the rest of mir_eval.beat: Goto, P-score and Information gain, per target")
     p.add_argument("--ema", default=False, action=argparse.BooleanOptionalAction,
                    help="score the averaged weights of each checkpoint (its ema_state_dict, written by a run with --ema-decay)")
     p.add_argument("--dump-predictions", metavar="FILENAME", type=str, default=None,
@@ -206,6 +240,8 @@ def main(argv=None) -> int:
               names=args.names)
     if args.loss:
         kw["loss"] = True
+    if args.all_metrics:
+        kw["extended"] = True
     checkpoint = lambda path: path
     if args.ema:   # (the averaged weights of each file: its ema_state_dict in the place of its state_dict)
         from .inference import averaged_checkpoint as checkpoint
@@ -216,6 +252,10 @@ def main(argv=None) -> int:
         print("Metrics")
         for k, v in res["averaged"].items():
             print(f"{k}: {v}")
+        for target, names in res.get("p_score_undefined", {}).items():
+            for name in names:
+                print(f"P-score_{target} is undefined for {name} (its reference beats share one 10 ms index): left out of "
+                      "the P-score averages")
         print("Dataset metrics")
         for k, v in res["dataset_metrics"].items():
             print(k)

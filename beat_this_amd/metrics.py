@@ -1,10 +1,12 @@
-"""Beat-tracking metrics of the paper (the reference's Metrics, pl_module.py:320-339): mir_eval.beat's trim_beats,
-f_measure, cemgil and continuity, restated in csrc/metrics.hip.  mir_eval is never imported.
+"""mir_eval.beat on the library's code: the paper's metrics (the reference's Metrics, pl_module.py:320-339: trim_beats,
+f_measure, cemgil, continuity) and the rest of the module (goto, p_score, information_gain, evaluate;
+DESIGN.md section 28), restated in csrc/metrics.hip.  mir_eval is never imported, and nothing here is pinned against it.
 
-Drop-in forms (``trim_beats``, ``f_measure``, ``cemgil``, ``continuity``, ``Metrics``) take mir_eval's arguments, return what
-it returns, raise ``ValueError`` where its ``validate`` raises (and, in addition, on non-finite times) and warn on empty input
-as it does; they run the library's host code (bt_beat_metrics_host).  ``beat_metrics_many`` scores many tracks in one device
-call (bt_beat_metrics)."""
+Drop-in forms (``trim_beats``, ``validate``, ``f_measure``, ``cemgil``, ``goto``, ``p_score``, ``continuity``,
+``information_gain``, ``evaluate``, and the reference's ``Metrics``) take mir_eval's arguments, return what it returns, raise
+``ValueError`` where it raises (and, in addition, on non-finite times) and warn where it warns; they run the library's host
+code (bt_beat_metrics_host, bt_beat_metrics_ext_host).  ``beat_metrics_many`` scores many tracks on the device: one
+bt_beat_metrics call, and with ``extended=True`` one bt_beat_metrics_ext call on the same upload."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,6 +23,13 @@ DEFAULTS = dict(f_measure_threshold=0.07, cemgil_sigma=0.04, continuity_phase_th
                 continuity_period_threshold=0.175)
 # BT_METRICS_* status bits (include/beat_this_amd.h); those of the estimates are shifted left by 3
 STATUS_NONFINITE, STATUS_UNSORTED, STATUS_LATE, STATUS_NEAREST, STATUS_OFFSETS = 1, 2, 4, 64, 128
+STATUS_PSCORE = 256   # bt_beat_metrics_ext only: p_score undefined (no interval between distinct reference indices)
+EXT_COLUMNS = ("Goto", "PScore", "InfoGain", "GotoCriteria", "GotoTrackLen", "GotoMean", "GotoStd", "PWindow", "PHits",
+               "EntropyFwd", "EntropyBwd", "status")
+EXT_DEFAULTS = dict(goto_threshold=0.35, goto_mu=0.2, goto_sigma=0.2, p_score_threshold=0.2, bins=41)
+# beat_metrics_many(extended=True)'s keys for the columns of a bt_beat_metrics_ext row
+EXT_KEYS = ("Goto", "P-score", "Information gain", "GotoCriteria", "GotoTrackLen", "GotoMean", "GotoStd", "PWindow", "PHits",
+            "EntropyFwd", "EntropyBwd", "status_ext")
 
 
 def _thresholds(kw):
@@ -81,6 +90,9 @@ def _status_text(status: int) -> str:
         parts.append("nearest annotation not monotone in the estimates (events closer than the rounding of their distances)")
     if status & STATUS_OFFSETS:
         parts.append("bad track offsets")
+    if status & STATUS_PSCORE:
+        parts.append("p_score undefined: all reference beats fall into one 10 ms index (mir_eval: cannot convert float NaN "
+                     "to integer)")
     return "; ".join(parts) or f"status {status}"
 
 
@@ -116,6 +128,86 @@ def continuity(reference_beats, estimated_beats, continuity_phase_threshold=0.17
     return tuple(float(v) for v in row[5:9])
 
 
+def _ext_args(kw):
+    t = {**EXT_DEFAULTS, **kw}
+    bins = t["bins"]
+    if int(bins) != bins:
+        raise ValueError(f"bins must be an integer, not {bins!r}")
+    return (float(t["goto_threshold"]), float(t["goto_mu"]), float(t["goto_sigma"]), float(t["p_score_threshold"]), int(bins))
+
+
+def _host_row_ext(ref, est, min_beat_time=-np.inf, **kw) -> np.ndarray:
+    """one bt_beat_metrics_ext_host row; ValueError on every status but STATUS_PSCORE, which the caller reads"""
+    ref, est = _events(ref, "reference"), _events(est, "estimated")
+    out = np.zeros(len(EXT_COLUMNS), np.float64)
+    roff = np.array([0, ref.size], np.int64)
+    eoff = np.array([0, est.size], np.int64)
+    _lib.check(_lib.lib().bt_beat_metrics_ext_host(ref.ctypes.data, roff.ctypes.data, est.ctypes.data, eoff.ctypes.data, 1,
+                                                   float(min_beat_time), *_ext_args(kw), out.ctypes.data))
+    if int(out[11]) & ~STATUS_PSCORE:
+        raise ValueError(_status_text(int(out[11])))
+    return out
+
+
+def _warn_single(reference_beats, estimated_beats):
+    if np.size(reference_beats) == 1:
+        warnings.warn("Only one reference beat was provided, so beat intervals cannot be computed.")
+    if np.size(estimated_beats) == 1:
+        warnings.warn("Only one estimated beat was provided, so beat intervals cannot be computed.")
+
+
+def goto(reference_beats, estimated_beats, goto_threshold=0.35, goto_mu=0.2, goto_sigma=0.2):
+    """mir_eval.beat.goto -> 1.0 or 0.0.  (With goto_threshold >= 1 no beat counts as incorrect and mir_eval raises
+    IndexError; this returns 0.0.)"""
+    validate(reference_beats, estimated_beats)
+    return float(_host_row_ext(reference_beats, estimated_beats, goto_threshold=goto_threshold, goto_mu=goto_mu,
+                               goto_sigma=goto_sigma)[0])
+
+
+def p_score(reference_beats, estimated_beats, p_score_threshold=0.2):
+    """mir_eval.beat.p_score; ValueError, as in mir_eval, when no two reference beats differ by a 10 ms index"""
+    validate(reference_beats, estimated_beats)
+    _warn_single(reference_beats, estimated_beats)
+    row = _host_row_ext(reference_beats, estimated_beats, p_score_threshold=p_score_threshold)
+    if int(row[11]) & STATUS_PSCORE:
+        raise ValueError(_status_text(STATUS_PSCORE))
+    return float(row[1])
+
+
+def information_gain(reference_beats, estimated_beats, bins=41):
+    """mir_eval.beat.information_gain (``bins``: 1 .. 1024)"""
+    validate(reference_beats, estimated_beats)
+    if not bins % 2:
+        warnings.warn("bins parameter is even, so there will not be a bin centered at zero.")
+    _warn_single(reference_beats, estimated_beats)
+    return float(_host_row_ext(reference_beats, estimated_beats, bins=bins)[2])
+
+
+def _filtered(fn, names, args, kwargs):
+    """mir_eval.util.filter_kwargs: call fn with those of kwargs that it takes"""
+    return fn(*args, **{k: v for k, v in kwargs.items() if k in names})
+
+
+def evaluate(reference_beats, estimated_beats, **kwargs):
+    """mir_eval.beat.evaluate: trim both arrays (``min_beat_time``, default 5.0), then every metric under mir_eval's keys in
+    mir_eval's order.  Keyword names that no metric takes are ignored."""
+    import collections
+
+    reference_beats = _filtered(trim_beats, ("min_beat_time",), (reference_beats,), kwargs)
+    estimated_beats = _filtered(trim_beats, ("min_beat_time",), (estimated_beats,), kwargs)
+    both = (reference_beats, estimated_beats)
+    scores = collections.OrderedDict()
+    scores["F-measure"] = _filtered(f_measure, ("f_measure_threshold",), both, kwargs)
+    scores["Cemgil"], scores["Cemgil Best Metric Level"] = _filtered(cemgil, ("cemgil_sigma",), both, kwargs)
+    scores["Goto"] = _filtered(goto, ("goto_threshold", "goto_mu", "goto_sigma"), both, kwargs)
+    scores["P-score"] = _filtered(p_score, ("p_score_threshold",), both, kwargs)
+    (scores["Correct Metric Level Continuous"], scores["Correct Metric Level Total"], scores["Any Metric Level Continuous"],
+     scores["Any Metric Level Total"]) = _filtered(continuity, ("continuity_phase_threshold", "continuity_period_threshold"),
+                                                   both, kwargs)
+    scores["Information gain"] = _filtered(information_gain, ("bins",), both, kwargs)
+    return scores
+
+
 class Metrics:
     """The reference's Metrics (pl_module.py:320-339): trim both arrays to ``eval_trim_beats`` seconds, then
     ``{"F-measure", "Cemgil"}`` for step "val" and ``{"F-measure", "Cemgil", "CMLt", "AMLt"}`` for step "test"; "Cemgil" is
@@ -146,7 +238,17 @@ def _csr(tracks, what):
     return flat, off
 
 
-def beat_metrics_many(truths, preds, eval_trim_beats=5, device="cuda", raise_on_invalid=True, **thresholds) -> dict:
+def invalid_tracks_error(status, ignore=0):
+    """the ValueError that names the first track whose status has a bit outside ``ignore``, or None"""
+    bad = np.nonzero(np.asarray(status).astype(np.int64) & ~ignore)[0]
+    if not bad.size:
+        return None
+    return ValueError(f"track {int(bad[0])}: {_status_text(int(status[bad[0]]))}"
+                      + (f" (and {bad.size - 1} more tracks)" if bad.size > 1 else ""))
+
+
+def beat_metrics_many(truths, preds, eval_trim_beats=5, device="cuda", raise_on_invalid=True, extended=False,
+                      goto_threshold=0.35, goto_mu=0.2, goto_sigma=0.2, p_score_threshold=0.2, bins=41, **thresholds) -> dict:
     """Metrics of many tracks in ONE bt_beat_metrics call: one upload (truths, predictions and offsets in one pinned buffer),
     one launch pair, one device-to-host copy.  ``truths`` / ``preds``: sequences of 1-d beat-time arrays of equal length;
     ``eval_trim_beats``: trim_beats' min_beat_time (None keeps every beat); ``thresholds``: mir_eval's keyword names
@@ -157,16 +259,26 @@ def beat_metrics_many(truths, preds, eval_trim_beats=5, device="cuda", raise_on_
     compute_paper_metrics.py prints as "Cemgil": Metrics returns mir_eval's (cemgil, cemgil_max) tuple per piece, and the
     np.mean over pieces (pl_module.py:156-160) averages both values of every tuple.
     A track whose status is non-zero (where mir_eval's validate raises) raises ValueError, or, with
-    ``raise_on_invalid=False``, keeps NaN metrics and its status bits."""
+    ``raise_on_invalid=False``, keeps NaN metrics and its status bits.
+
+    ``extended=True``: one bt_beat_metrics_ext call more on the same upload, with mir_eval's ``goto_threshold``, ``goto_mu``,
+    ``goto_sigma``, ``p_score_threshold`` and ``bins`` (unused otherwise).  It adds "Goto", "P-score", "Information gain", the
+    quantities behind them ("GotoCriteria", "GotoTrackLen", "GotoMean", "GotoStd", "PWindow", "PHits", "EntropyFwd",
+    "EntropyBwd"; include/beat_this_amd.h) and "status_ext": "status", or STATUS_PSCORE where mir_eval's p_score raises (NaN
+    "P-score", "PWindow" and "PHits"; such a track is invalid too)."""
     if len(truths) != len(preds):
         raise ValueError(f"{len(truths)} truth arrays but {len(preds)} prediction arrays")
     n = len(truths)
     th = _thresholds(thresholds)
+    ext = _ext_args(dict(goto_threshold=goto_threshold, goto_mu=goto_mu, goto_sigma=goto_sigma,
+                         p_score_threshold=p_score_threshold, bins=bins)) if extended else None
     keys = ("F-measure", "Precision", "Recall", "Cemgil", "CemgilMax", "CMLc", "CMLt", "AMLc", "AMLt", "n_ref", "n_est",
             "status")
     if n == 0:
         out = {k: np.zeros(0) for k in keys}
         out["Cemgil_reported"] = np.zeros(0)
+        if extended:
+            out.update({k: np.zeros(0) for k in EXT_KEYS})
         return out
     ref, roff = _csr(truths, "truth")
     est, eoff = _csr(preds, "prediction")
@@ -187,11 +299,21 @@ def beat_metrics_many(truths, preds, eval_trim_beats=5, device="cuda", raise_on_
     with torch.cuda.device(dev):
         _lib.check(L.bt_beat_metrics(_lib.stream_ptr(dev), d_ref, d_roff, d_est, d_eoff, n, mbt, *th, ws.data_ptr(), ws_bytes,
                                      d_out.data_ptr()))
+        if extended:
+            xws_bytes = L.bt_beat_metrics_ext_workspace_bytes(n, int(roff[-1]), int(eoff[-1]))
+            xws = torch.empty(max(xws_bytes, 1), dtype=torch.uint8, device=dev)
+            d_xout = torch.empty((n, len(EXT_KEYS)), dtype=torch.float64, device=dev)
+            _lib.check(L.bt_beat_metrics_ext(_lib.stream_ptr(dev), d_ref, d_roff, d_est, d_eoff, n, mbt, *ext, xws.data_ptr(),
+                                             xws_bytes, d_xout.data_ptr()))
     rows = d_out.cpu().numpy()
     out = {k: rows[:, i].copy() for i, k in enumerate(keys)}
     out["Cemgil_reported"] = (out["Cemgil"] + out["CemgilMax"]) / 2
-    bad = np.nonzero(out["status"])[0]
-    if raise_on_invalid and bad.size:
-        raise ValueError(f"track {int(bad[0])}: {_status_text(int(out['status'][bad[0]]))}"
-                         + (f" (and {bad.size - 1} more tracks)" if bad.size > 1 else ""))
+    status = out["status"]
+    if extended:
+        xrows = d_xout.cpu().numpy()
+        out.update({k: xrows[:, i].copy() for i, k in enumerate(EXT_KEYS)})
+        status = (status.astype(np.int64) | out["status_ext"].astype(np.int64)).astype(np.float64)
+    err = invalid_tracks_error(status) if raise_on_invalid else None
+    if err is not None:
+        raise err
     return out

@@ -367,6 +367,34 @@ int bt_beat_metrics_host(const double* ref, const int64_t* ref_off, const double
                          double min_beat_time, double f_window, double cemgil_sigma, double phase_thr, double period_thr,
                          double* out);
 
+/* The rest of mir_eval.beat: goto, p_score and information_gain (mir_eval 0.7's beat.py restated; csrc/metrics.hip and the
+ * DESIGN.md section on the extended metrics; not pinned against mir_eval).  Input, trimming, validation and the status bits
+ * are bt_beat_metrics's.  goto_threshold / goto_mu / goto_sigma (mir_eval: 0.35, 0.2, 0.2), p_score_threshold (0.2), bins
+ * (41; 1 .. 1024, else BT_ERR_ARG).  Output: n_tracks rows of BT_METRICS_EXT_COLS doubles
+ *   Goto, PScore, InfoGain, GotoCriteria, GotoTrackLen, GotoMean, GotoStd, PWindow, PHits, EntropyFwd, EntropyBwd, status
+ * Goto is 0.0 or 1.0; columns 3 .. 10 are the quantities behind the three metrics: goto's criteria (0, 1 or 3), the length
+ * of its slice `track` (0: none), mean(abs(track)) and std(track, ddof = 1) (NaN for no track, an empty one or, the std, one
+ * element), p_score's win_size and the integer sum of its truncated correlation, and the two entropies of information_gain.
+ * A metric that returns early (an empty side for goto, fewer than two beats on a side for the others) writes 0 there.
+ * A non-zero status of bt_beat_metrics's kinds makes columns 0 .. 10 NaN.  BT_METRICS_PSCORE alone: both sides have two or
+ * more kept beats but every kept reference beat falls into one 10 ms index, where mir_eval's p_score raises ValueError (the
+ * median of no intervals); then only columns 1, 7 and 8 are NaN. */
+#define BT_METRICS_EXT_COLS 12
+#define BT_METRICS_PSCORE 256
+/* device workspace of bt_beat_metrics_ext (it depends on n_tracks only) */
+size_t bt_beat_metrics_ext_workspace_bytes(int n_tracks, int64_t total_ref, int64_t total_est);
+/* all pointers device memory, d_out n_tracks x BT_METRICS_EXT_COLS doubles.  Two launches on the stream, no synchronisation;
+ * two calls on the same input give the same bits. */
+int bt_beat_metrics_ext(void* stream, const double* d_ref, const int64_t* d_ref_off, const double* d_est,
+                        const int64_t* d_est_off, int n_tracks, double min_beat_time, double goto_threshold, double goto_mu,
+                        double goto_sigma, double p_score_threshold, int bins, void* d_ws, size_t ws_bytes, double* d_out);
+/* HOST: the same rows from host memory by mir_eval's sequential loops (p_score by counting pairs of distinct indices).
+ * GotoMean, GotoStd, the entropies and InfoGain may differ from the device's in the last bits (sums in another order, another
+ * log2); the other columns are bit-identical unless a Goto mean or std lies within that rounding of its threshold. */
+int bt_beat_metrics_ext_host(const double* ref, const int64_t* ref_off, const double* est, const int64_t* est_off, int n_tracks,
+                             double min_beat_time, double goto_threshold, double goto_mu, double goto_sigma,
+                             double p_score_threshold, int bins, double* out);
+
 /* Training losses (the reference's beat_this/model/loss.py: MaskedBCELoss, ShiftTolerantBCELoss, SplittedShiftTolerantBCELoss;
  * csrc/loss.hip) with their gradients in the logits.  Rows come in CSR form: row r is elements
  * offsets[r] .. offsets[r + 1] of logits, targets and mask (int64 offsets, n_rows + 1 of them; a (B, T) batch has equal

@@ -5,12 +5,14 @@
          insertions), scored as the evaluator does: beats and downbeats, trimmed at 5 s;
   long:  100 tracks of 300 s (about 600 beats each).
 
-    python tools/metrics_speed.py [--reps 10] [--oracle-tracks 50] [--json out.json]
+    python tools/metrics_speed.py [--reps 10] [--oracle-tracks 50] [--extended] [--json out.json]
 
 Prints one JSON line: per workload, the device call (one bt_beat_metrics on inputs already on the device, beats and downbeats
 each, CUDA events, median of --reps), beat_metrics_many end to end (upload, call, copy back), bt_beat_metrics_host on one
 thread, and the numpy oracle (tests/metrics_reference.py, which has mir_eval's loops) timed on --oracle-tracks tracks and
-scaled to the whole workload."""
+scaled to the whole workload.  With --extended the same four legs for the rest of mir_eval.beat (goto, p_score,
+information_gain) join them under ext_* keys: one bt_beat_metrics_ext alone, beat_metrics_many(extended=True) end to end (both
+device calls), bt_beat_metrics_ext_host on one thread, and tests/metrics_ext_reference.py."""
 import argparse
 import json
 import os
@@ -25,6 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 TH = (0.07, 0.04, 0.175, 0.175)
+EXT = (0.35, 0.2, 0.2, 0.2, 41)
 
 
 def workload(n, dur, seed):
@@ -50,7 +53,7 @@ def csr(pairs, side):
     return np.concatenate(arrs + [np.zeros(1)]), off
 
 
-def time_device(pairs, reps):
+def time_device(pairs, reps, extended=False):
     from beat_this_amd import _lib
 
     dev = torch.device("cuda")
@@ -59,14 +62,16 @@ def time_device(pairs, reps):
     t = {k: torch.from_numpy(v).to(dev) for k, v in dict(ref=ref, roff=roff, est=est, eoff=eoff).items()}
     n = len(pairs)
     L = _lib.lib()
-    wsb = L.bt_beat_metrics_workspace_bytes(n, int(roff[-1]), int(eoff[-1]))
+    wsb = (L.bt_beat_metrics_ext_workspace_bytes if extended else L.bt_beat_metrics_workspace_bytes)(
+        n, int(roff[-1]), int(eoff[-1]))
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     out = torch.empty((n, 12), dtype=torch.float64, device=dev)
     st = _lib.stream_ptr(dev)
 
     def call():
-        _lib.check(L.bt_beat_metrics(st, t["ref"].data_ptr(), t["roff"].data_ptr(), t["est"].data_ptr(), t["eoff"].data_ptr(),
-                                     n, 5.0, *TH, ws.data_ptr(), wsb, out.data_ptr()))
+        fn, args = (L.bt_beat_metrics_ext, EXT) if extended else (L.bt_beat_metrics, TH)
+        _lib.check(fn(st, t["ref"].data_ptr(), t["roff"].data_ptr(), t["est"].data_ptr(), t["eoff"].data_ptr(), n, 5.0, *args,
+                      ws.data_ptr(), wsb, out.data_ptr()))
 
     call()
     torch.cuda.synchronize()
@@ -81,20 +86,20 @@ def time_device(pairs, reps):
     return float(np.median(ms)), float(np.min(ms))
 
 
-def time_many(pairs, reps):
+def time_many(pairs, reps, extended=False):
     from beat_this_amd.metrics import beat_metrics_many
 
-    beat_metrics_many([p[0] for p in pairs], [p[1] for p in pairs])
+    beat_metrics_many([p[0] for p in pairs], [p[1] for p in pairs], extended=extended)
     ms = []
     for _ in range(reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        beat_metrics_many([p[0] for p in pairs], [p[1] for p in pairs])
+        beat_metrics_many([p[0] for p in pairs], [p[1] for p in pairs], extended=extended)
         ms.append((time.perf_counter() - t0) * 1e3)
     return float(np.median(ms))
 
 
-def time_host(pairs, reps):
+def time_host(pairs, reps, extended=False):
     from beat_this_amd import _lib
 
     ref, roff = csr(pairs, 0)
@@ -103,19 +108,22 @@ def time_host(pairs, reps):
     ms = []
     for _ in range(max(1, reps // 2)):
         t0 = time.perf_counter()
-        _lib.check(_lib.lib().bt_beat_metrics_host(ref.ctypes.data, roff.ctypes.data, est.ctypes.data, eoff.ctypes.data,
-                                                   len(pairs), 5.0, *TH, out.ctypes.data))
+        fn, args = (_lib.lib().bt_beat_metrics_ext_host, EXT) if extended else (_lib.lib().bt_beat_metrics_host, TH)
+        _lib.check(fn(ref.ctypes.data, roff.ctypes.data, est.ctypes.data, eoff.ctypes.data, len(pairs), 5.0, *args,
+                      out.ctypes.data))
         ms.append((time.perf_counter() - t0) * 1e3)
     return float(np.median(ms))
 
 
-def time_oracle(pairs, k):
+def time_oracle(pairs, k, extended=False):
+    import metrics_ext_reference as X
     import metrics_reference as R
 
+    row = X.row_ext if extended else R.row
     sub = pairs[:k]
     t0 = time.perf_counter()
     for r, e in sub:
-        R.row(r, e, 5.0)
+        row(r, e, 5.0)
     return (time.perf_counter() - t0) * 1e3 / len(sub) * len(pairs)
 
 
@@ -123,6 +131,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--oracle-tracks", type=int, default=50)
+    ap.add_argument("--extended", action="store_true", help="also time goto, p_score and information_gain (ext_* keys)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0)}
@@ -136,6 +145,13 @@ def main():
             r[f"many_ms_{target}"] = round(time_many(pairs, args.reps), 3)
             r[f"host_1thread_ms_{target}"] = round(time_host(pairs, args.reps), 3)
             r[f"oracle_ms_{target}"] = round(time_oracle(pairs, min(args.oracle_tracks, n)), 1)
+            if args.extended:
+                med, best = time_device(pairs, args.reps, True)
+                r[f"ext_device_ms_{target}"] = round(med, 4)
+                r[f"ext_device_min_ms_{target}"] = round(best, 4)
+                r[f"ext_many_ms_{target}"] = round(time_many(pairs, args.reps, True), 3)
+                r[f"ext_host_1thread_ms_{target}"] = round(time_host(pairs, args.reps, True), 3)
+                r[f"ext_oracle_ms_{target}"] = round(time_oracle(pairs, min(args.oracle_tracks, n), True), 1)
         res[name] = r
     line = json.dumps(res)
     print(line)
