@@ -230,6 +230,47 @@ def unfrag_x3(fr, L, kind):
     return u(fr[:, :, 0].contiguous(), L).double() + u(fr[:, :, 1].contiguous(), L).double()
 
 
+def run_attn_x3(q, k, v, gates, n_seq, L, heads, out_f32, variant=1, raw=False, status_out=None, **omap):
+    """bt_attention_frag on x3 operands: q, k, v [SH, L, 32] fp32-valued, gates [SH, L]; out_f32: 0 = hl32 rows, 1 = fp32 rows,
+    2 = hl8 rows; variant = bt_attn_frag_args.x3; omap: o_div / o_outer / o_inner / o_tok of the row map.  Returns the rows as
+    float64 (raw: as the kernel stored them)."""
+    from beat_this_amd import _lib as Lb
+
+    nbp = Lb.lib().bt_attn_frag_blocks(L)
+    SH = n_seq * heads
+    gh = torch.zeros((SH, nbp * 32), dtype=torch.float32)
+    gh[:, :L] = gates.float()
+    rows = n_seq * L
+    inner = heads * 32
+    out = torch.zeros((rows, inner), dtype=torch.float32, device=dev()) if int(out_f32) == 1 else \
+        torch.zeros((rows, 2 * inner), dtype=torch.float16, device=dev())
+    qf, kf, vf = frag_x3(q, nbp, "qk"), frag_x3(k, nbp, "qk"), frag_x3(v, nbp, "v")
+    nblk = (L + 31) // 32
+    kf[:, nblk:] = float("nan")   # padding blocks beyond ceil(L / 32) must never be consumed
+    vf[:, nblk:] = float("nan")
+    a = Lb.AttnFragArgs()
+    qd, kd, vd, gd = qf.to(dev()), kf.to(dev()), vf.to(dev()), gh.to(dev())
+    st = torch.zeros(1, dtype=torch.int32, device=dev())
+    a.q, a.k, a.v, a.gates, a.out = qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), gd.data_ptr(), out.data_ptr()
+    a.n_seq, a.L, a.heads, a.inner, a.nbp, a.o_div = n_seq, L, heads, inner, nbp, omap.get("o_div", 1)
+    a.o_outer, a.o_inner, a.o_tok = omap.get("o_outer", L), omap.get("o_inner", 0), omap.get("o_tok", 1)
+    a.x3, a.out_f32, a.status = variant, int(out_f32), st.data_ptr()
+    scratch = torch.full((SH, nbp), -1, dtype=torch.int32, device=dev())   # the launch's overflow map (stale bits must not matter)
+    a.scratch = scratch.data_ptr()
+    Lb.check(Lb.lib().bt_attention_frag(Lb.stream_ptr(dev()), C.byref(a)))
+    torch.cuda.synchronize()
+    if status_out is not None:   # (the caller looks at the range flag itself)
+        status_out.append(int(st.item()))
+    else:
+        assert int(st.item()) == 0
+    if raw:
+        return out.cpu()
+    if int(out_f32) == 2:   # hl8 rows: hi halves + what the lo bytes stand for
+        hi, _, l8 = hl8_parts(out.cpu(), act=True)
+        return hi + l8
+    return out.double().cpu() if int(out_f32) == 1 else from_hl32(out.cpu())
+
+
 # ---- guard bands and poisoned memory (tests/test_gpu_guard.py) -------------------------------------------------------
 GUARD_BAND = 2 << 20   # bytes on each side of a guarded buffer: more than a whole 128-row tile of 2048 fp32 columns (1 MiB)
 POISONS = (0xFF, 0x7B)  # 0xFF: NaN in fp32 / fp16 / bf16, -1 as int32;  0x7B: large finite (fp32 ~1.3e36, fp16 61280, bf16 ~1.3e36)

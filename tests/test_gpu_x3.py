@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from gpu_util import HL8_ACT_SHIFT, _attn_ref, _mk, _rel, dev, frag_x3, from_hl32, hl8_matmul, hl8_parts, pad_rows, report, to_hl8, to_hl8a, to_hl32, unfrag_x3
+from gpu_util import run_attn_x3 as _run_attn
 
 pytestmark = pytest.mark.gpu
 
@@ -329,44 +330,6 @@ def test_gemm3_x3_range_flag():
 
 
 # ---- attention ----------------------------------------------------------------------------------------------------------
-def _run_attn(q, k, v, gates, n_seq, L, heads, out_f32, variant=1, raw=False, status_out=None, **omap):
-    from beat_this_amd import _lib as Lb
-
-    nbp = Lb.lib().bt_attn_frag_blocks(L)
-    SH = n_seq * heads
-    gh = torch.zeros((SH, nbp * 32), dtype=torch.float32)
-    gh[:, :L] = gates.float()
-    rows = n_seq * L
-    inner = heads * 32
-    out = torch.zeros((rows, inner), dtype=torch.float32, device=dev()) if int(out_f32) == 1 else \
-        torch.zeros((rows, 2 * inner), dtype=torch.float16, device=dev())
-    qf, kf, vf = frag_x3(q, nbp, "qk"), frag_x3(k, nbp, "qk"), frag_x3(v, nbp, "v")
-    nblk = (L + 31) // 32
-    kf[:, nblk:] = float("nan")   # padding blocks beyond ceil(L / 32) must never be consumed
-    vf[:, nblk:] = float("nan")
-    a = Lb.AttnFragArgs()
-    qd, kd, vd, gd = qf.to(dev()), kf.to(dev()), vf.to(dev()), gh.to(dev())
-    st = _status()
-    a.q, a.k, a.v, a.gates, a.out = qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), gd.data_ptr(), out.data_ptr()
-    a.n_seq, a.L, a.heads, a.inner, a.nbp, a.o_div = n_seq, L, heads, inner, nbp, omap.get("o_div", 1)
-    a.o_outer, a.o_inner, a.o_tok = omap.get("o_outer", L), omap.get("o_inner", 0), omap.get("o_tok", 1)
-    a.x3, a.out_f32, a.status = variant, int(out_f32), st.data_ptr()
-    scratch = torch.full((SH, nbp), -1, dtype=torch.int32, device=dev())   # the launch's overflow map (stale bits must not matter)
-    a.scratch = scratch.data_ptr()
-    Lb.check(Lb.lib().bt_attention_frag(Lb.stream_ptr(dev()), C.byref(a)))
-    torch.cuda.synchronize()
-    if status_out is not None:   # (the caller looks at the range flag itself)
-        status_out.append(int(st.item()))
-    else:
-        assert int(st.item()) == 0
-    if raw:
-        return out.cpu()
-    if int(out_f32) == 2:   # hl8 rows: hi halves + what the lo bytes stand for
-        hi, _, l8 = hl8_parts(out.cpu(), act=True)
-        return hi + l8
-    return out.double().cpu() if int(out_f32) == 1 else from_hl32(out.cpu())
-
-
 @pytest.mark.parametrize("variant", [1, 2, 5])   # bt_attn_frag_args.x3: keys per LDS tile / 5 = the hand-scheduled two-query-block kernel, forced (4 = by launch size; attn2.hip)
 @pytest.mark.parametrize("out_f32", [False, True])
 @pytest.mark.parametrize("n_seq,L,heads", [(3, 1500, 2), (2, 77, 1), (1, 128, 4), (5, 1012, 1), (2, 1, 1), (2, 33, 2),
