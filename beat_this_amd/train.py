@@ -109,24 +109,33 @@ def _validation_values(pl_module, batch, i):
     return int(batch["spect"].shape[0]), {k: float(v) for k, v in values.items()}
 
 
+def _ranks(group) -> tuple:
+    """(world, rank) of this process in ``group``; (1, 0) without one -- and without importing torch.distributed"""
+    if group is None:
+        return 1, 0
+    import torch.distributed as dist
+
+    return dist.get_world_size(group), dist.get_rank(group)
+
+
 def validate(pl_module, datamodule, process_group=None) -> dict:
     """The mean over the validation set (weighted by batch size) of the losses and of what the reference's ``step="val"``
     reports: F-measure and Cemgil for beats and downbeats.  ``process_group``: batch ``j`` is computed by rank ``j % world``,
     the per-batch values are gathered and every rank adds them in batch order -- the single-process numbers exactly, on
     every rank."""
-    if process_group is None:
-        per_batch = [_validation_values(pl_module, batch, i) for i, batch in enumerate(datamodule.val_dataloader())]
-    else:
+    world, rank = _ranks(process_group)
+    loader = datamodule.val_dataloader()
+    own = enumerate(loader) if process_group is None else loader.shard(rank, world)
+    per_batch = {j: _validation_values(pl_module, batch, j) for j, batch in own}
+    if process_group is not None:
         import torch.distributed as dist
 
-        world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
-        mine = {j: _validation_values(pl_module, batch, j) for j, batch in datamodule.val_dataloader().shard(rank, world)}
         gathered = [None] * world
-        dist.all_gather_object(gathered, mine, group=process_group)
-        merged = {j: v for part in gathered for j, v in part.items()}
-        per_batch = [merged[j] for j in sorted(merged)]
+        dist.all_gather_object(gathered, per_batch, group=process_group)
+        per_batch = {j: v for part in gathered for j, v in part.items()}
     sums, count = {}, 0
-    for n, values in per_batch:
+    for j in sorted(per_batch):
+        n, values = per_batch[j]
         for k, v in values.items():
             sums[k] = sums.get(k, 0.0) + n * v
         count += n
@@ -166,213 +175,134 @@ def _fingerprint(optimizer) -> tuple:
     return moments, int(pos), int(np.asarray(keys, dtype=np.uint64).sum()), int(has_gauss)
 
 
-def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
-        resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None, frontend_precision=None,
-        frontend_dropout=None, ema_decay=None, mixed_operand=None, frontend_mixed_operand=None, process_group=None,
-        staged=False) -> dict:
-    """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.
-
-    Every batch: loss, ``backward()``; every ``accumulate_grad_batches`` batches (and for the remainder at the end of an epoch,
-    with its own count) one ``optimizer.step()`` and ``scheduler.step()`` -- the 1 / count scaling and, with ``max_grad_norm``,
-    the clipping to that global gradient norm happen inside the optimiser's kernels.  The schedule spans all
-    ``max_epochs * ceil(batches / accumulate_grad_batches)`` steps.  The epoch's mean training loss is accumulated on the
-    device and read once per epoch.  After every ``val_frequency``-th epoch ``validate`` runs.  At each epoch's end a
-    checkpoint goes to ``checkpoint_path`` (if given).  ``resume``: such a checkpoint (path or loaded dict) -- weights,
-    optimiser, schedule, counters and numpy's generator are restored and the run continues with the next epoch, bit for bit
-    as if it had not stopped (with dropout enabled also the model's seed and call counter, when the checkpoint has them).
-
-    ``precision``: "16-mixed", "32-high" or "32-true" sets the model's ``set_train_precision`` first (None leaves it as it is).
-    "32-high" (fp32 products on three bfloat16 MFMAs) needs no loss scale and makes an fp32 run's calls
-    around the model, like bf16 operands below.  A 16-mixed
-    run multiplies the loss by a ``LossScaler``'s scale before ``backward()`` and hands the scaler to every optimiser step, which
-    unscales, skips a step whose gradients are not finite and moves the scale (one 4-byte read per step, ``AdamW.step``); the
-    schedule steps with every optimiser call, skipped or not, as the reference's trainer does.  The losses reported are
-    unscaled; the scaler's state goes into the checkpoint under ``loss_scaler`` and comes back with ``resume``.  Without
-    16-mixed the calls are the ones of an fp32 run.
-
-    ``mixed_operand``, ``frontend_mixed_operand``: "fp16" or "bf16", the ``operand`` of ``set_train_precision`` /
-    ``set_frontend_precision``, set together with ``precision`` / ``frontend_precision`` (None with a
-    precision follows the setter's rule: kept while the part stays "16-mixed", else "fp16"; given alone it re-sets the part's
-    present precision with that operand; "bf16" on a part that is not "16-mixed" is a ``ValueError``).  bfloat16 operands
-    cannot overflow by rounding, so the ``LossScaler`` exists only if some part is 16-mixed on fp16 operands: a run whose mixed
-    parts are all bf16 makes the calls of an fp32 run -- no scaler, no scaled loss, no ``loss_scaler`` in the checkpoint, None in
-    the returned dictionary.  ``resume`` needs the same settings.
-
-    ``train_frontend``, ``batch_statistics``, ``frontend_precision``, ``frontend_dropout``: the model's other settings
-    (``model.settings.TrainSettings`` says what each means), applied in that order after ``precision`` and before the optimiser is
-    built, so that its state covers the frontend's weights; None leaves the model as it is.  ``train_frontend``: True / False
-    calls ``set_frontend_trainable``; a checkpoint then carries the larger optimiser state, and ``resume`` needs the same
-    setting.  ``batch_statistics``: True / False calls ``set_batch_statistics`` (True needs a trainable frontend); the buffers
-    travel in the ``state_dict``, so a checkpoint and ``resume`` need nothing new; ``resume`` needs the same setting.
-    ``frontend_precision``: "16-mixed", "32-high" or "32-true" calls ``set_frontend_precision``; the loss scaler exists when either precision
-    is "16-mixed".  ``frontend_dropout``: True / False sets the frontend's dropout opt-in of a model whose dropout is enabled
-    (``BeatThis.enable_dropout(frontend=True)``); the seed and the call counter stay what they are.  True needs dropout enabled
-    and a trainable frontend (``ValueError`` otherwise).  The opt-in travels in ``rng["dropout"]`` of the checkpoint, and
-    ``resume`` restores it with the counter.
-
-    ``ema_decay`` (a float in [0, 1); None: off, and every call is the one of a run without it): the optimiser keeps an
-    exponential moving average of the weights it trains, in the pass of its step (``AdamW(ema_decay=...)``).  ``validate`` then
-    runs on the averaged weights (inside ``optimizer.averaged_weights()``, as Lightning's ``WeightAveraging`` callback does) and
-    the log line says so; the checkpoint gains ``ema_state_dict`` (``save_checkpoint``), which
-    ``beat_this_amd.inference.averaged_checkpoint`` turns into a checkpoint to load.  The average is part of the optimiser's
-    state: a resumed run repeats the uninterrupted one bit for bit, averages included.  ``resume`` with another setting follows
-    ``AdamW.load_state_dict``: a checkpoint without an average starts one, an average is ignored when ``ema_decay`` is None.
-    BatchNorm buffers are not averaged.
-
-    ``process_group`` (a ``torch.distributed`` group, one rank per process, every rank with the same module settings, the same
-    numpy seed and, with ``resume``, the same file; None: none of the following exists and every call is the one of a
-    single-process run), ``staged`` (the collectives go through host copies: gloo, ranks that share one GPU): data-parallel
-    training, DESIGN.md section 26.  Every rank draws the whole sequence of global batches (``BatchLoader.shard``) and builds
-    and runs batch ``j`` iff ``j % world == rank``.  One optimiser step closes a GROUP of ``accumulate_grad_batches * world``
-    consecutive global batches (the epoch's remainder with its own count; ``step_groups``): every rank calls
-    ``step(accumulated=<the group's global count>)``, in which the ranks' gradient buffers are added in rank order -- a rank
-    that owns no batch of a group contributes the zeros the previous step left.  The schedule spans
-    ``max_epochs * ceil(batches / (accumulate_grad_batches * world))`` steps.
-    THE ASSOCIATION: a rank first sums its own batches of the group (autograd, in batch order), then the ranks' sums are added
-    in rank order.  With ``accumulate_grad_batches == 1`` that is ``((0 + g0) + g1) + ...`` over the group's batches in global
-    order: a W-rank run is, bit for bit, the single-process run with ``accumulate_grad_batches = W`` -- parameters, optimiser
-    state, loss scale, averages, losses, validation values and the checkpoint.  With ``accumulate_grad_batches = A > 1`` the
-    sum is ``(g0 + gW + ...) + (g1 + gW+1 + ...) + ...``, another association of the same terms than the single process's
-    with ``A W``: equal up to fp32 rounding, not bit for bit; steps, counts and rates are the same.
-    Dropout: the forward of global batch ``j`` draws the streams the single-process run draws for it (the model's call
-    counter is set from ``j`` before every training forward: a forward advances it by 2 ``n_layers``, by 12 more with frontend
-    dropout); at an epoch's end every rank holds the single-process counter.  Rank 0's parameters and buffers are broadcast
-    once before the first step.  Batch statistics follow torch's DistributedDataParallel without SyncBatchNorm: each rank's
-    running buffers move with its own batches, rank 0's are broadcast at every epoch's end (before validation and the
-    checkpoint); training forwards never read them, so only the BatchNorms' running buffers differ from the single-process
-    run.  The per-batch losses stay on the device, are gathered once per epoch and added in global batch order in fp32;
-    ``validate`` shards its batches the same way.  At every epoch's end the ranks compare a bit fingerprint of their state
-    (``exp_avg`` and numpy's generator) and all raise ``RuntimeError`` if it differs.  Rank 0 writes the checkpoint (today's
-    keys), a barrier follows; the returned history is the same on every rank.
-
-    A module whose model has dropout enabled or uses batch statistics is put into ``train()`` mode here and stays in it; validation runs under
-    ``no_grad`` on the inference path, which never drops.
-
-    -> dict: ``train_loss`` (one mean per epoch run), ``val`` ([(epoch, metrics)]), ``epoch``, ``global_step``, ``optimizer``,
-    ``scheduler``, ``loss_scaler`` (None in an fp32 run)."""
-    from .optim import LossScaler
-
-    model = pl_module.model
+def _apply_settings(model, *, precision, mixed_operand, train_frontend, batch_statistics, frontend_precision, frontend_mixed_operand,
+                    frontend_dropout) -> None:
+    """``fit``'s requests to the model, in ``fit``'s order; None leaves a setting as it is"""
     if precision is None and mixed_operand is not None:
         precision = model.train_precision
     if frontend_precision is None and frontend_mixed_operand is not None:
         frontend_precision = model.frontend_precision
-    for value, setter in ((precision, lambda v: model.set_train_precision(v, mixed_operand)),
-                          (train_frontend, model.set_frontend_trainable), (batch_statistics, model.set_batch_statistics),
-                          (frontend_precision, lambda v: model.set_frontend_precision(v, frontend_mixed_operand))):
-        if value is not None:   # (None leaves the model as it is; in this order)
-            setter(value)
+    if precision is not None:
+        model.set_train_precision(precision, mixed_operand)
+    if train_frontend is not None:
+        model.set_frontend_trainable(train_frontend)
+    if batch_statistics is not None:
+        model.set_batch_statistics(batch_statistics)
+    if frontend_precision is not None:
+        model.set_frontend_precision(frontend_precision, frontend_mixed_operand)
     if frontend_dropout is not None:
         model.train_settings.changed("recipe", ValueError, _FIT_NAMES, only="frontend_dropout", frontend_dropout=bool(frontend_dropout))
         state = model.dropout_state()
         if state is not None:
             model.set_dropout_state(dict(state, frontend=bool(frontend_dropout)))
+
+
+def _restore(resume, pl_module, optimizer, scheduler, scaler, log) -> tuple:
+    """``resume`` (a checkpoint of ``fit``: path or loaded dict) into the run's objects and numpy's generator -> (the epoch to
+    go on with, the optimiser steps so far)"""
+    from .inference import load_checkpoint
+
+    ckpt = resume if isinstance(resume, dict) else load_checkpoint(resume, "cpu")
+    missing = [k for k in CHECKPOINT_KEYS if k not in ckpt]
+    if missing:
+        raise ValueError(f"cannot resume: the checkpoint has no {missing} (written by fit()?)")
+    pl_module.load_state_dict(ckpt["state_dict"])
+    optimizer.load_state_dict(ckpt["optimizer_states"][0])
+    scheduler.load_state_dict(ckpt["lr_schedulers"][0])
+    _set_rng_state(ckpt["rng"])
+    if "dropout" in ckpt["rng"] and pl_module.model.dropout_state() is not None:
+        pl_module.model.set_dropout_state(ckpt["rng"]["dropout"])
+    if scaler is not None and "loss_scaler" in ckpt:
+        scaler.load_state_dict(ckpt["loss_scaler"])
+    log(f"resumed after epoch {ckpt['epoch']} ({int(ckpt['global_step'])} optimiser steps)")
+    return int(ckpt["epoch"]) + 1, int(ckpt["global_step"])
+
+
+def fit(pl_module, datamodule, max_epochs, accumulate_grad_batches=1, val_frequency=5, max_grad_norm=None, checkpoint_path=None,
+        resume=None, log=print, precision=None, train_frontend=None, batch_statistics=None, frontend_precision=None,
+        frontend_dropout=None, ema_decay=None, mixed_operand=None, frontend_mixed_operand=None, process_group=None,
+        staged=False) -> dict:
+    """Train ``pl_module`` (on a ROCm GPU) for ``max_epochs`` epochs over ``datamodule.train_dataloader()``.  The rules behind
+    each argument are DESIGN.md's: the loop in section 14, then the section named with the argument.
+
+    ``accumulate_grad_batches``: one ``optimizer.step()`` and ``scheduler.step()`` per that many batches, and one for an
+    epoch's remainder with its own count (``step_groups``); the schedule spans ``max_epochs`` times an epoch's steps.
+    ``max_grad_norm``: the optimiser clips to that global gradient norm (None: no clipping).
+    ``val_frequency``: ``validate`` runs after every that-many-th epoch.
+    ``checkpoint_path``: ``save_checkpoint`` writes there at each epoch's end (None: nowhere).
+    ``resume``: such a checkpoint, path or loaded dict: the run continues with the next epoch, bit for bit as if it had not
+    stopped; it needs the settings of the run that wrote it.
+    ``log``: called with one line per epoch (and one after a resume).
+    ``precision`` ("16-mixed", "32-high", "32-true"), ``train_frontend``, ``batch_statistics`` (True / False),
+    ``frontend_precision`` (as ``precision``), ``frontend_dropout`` (True / False; True needs dropout enabled and a trainable
+    frontend, ``ValueError`` otherwise): the model's settings, applied in this order before the optimiser is built; None leaves
+    the model as it is.  Sections 16 and 25, 17, 18, 19, 21; ``model.settings.TrainSettings`` says what each means.  A
+    ``LossScaler`` scales the loss iff some part is 16-mixed on fp16 operands; the losses reported are unscaled.
+    ``mixed_operand``, ``frontend_mixed_operand``: "fp16" or "bf16", the ``operand`` of ``set_train_precision`` /
+    ``set_frontend_precision``, set together with the part's precision (given alone: with the precision the part has).
+    Section 24.
+    ``ema_decay``: a float in [0, 1): the optimiser averages the weights it trains, ``validate`` runs on the averages and the
+    checkpoint gains ``ema_state_dict``; None: off, and every call is the one of a run without it.  Section 22.
+    ``process_group``: a ``torch.distributed`` group, one rank per process, every rank with the same module settings, the same
+    numpy seed and, with ``resume``, the same file: data-parallel training, in which rank ``j % world`` runs global batch ``j``
+    and one step closes ``accumulate_grad_batches * world`` batches.  ``staged``: its collectives go through host copies
+    (gloo, ranks that share one GPU).  None: ``torch.distributed`` is not imported, and the run is the ``world = 1`` case of
+    the same loop.  Section 26.
+
+    A module whose model has dropout enabled or uses batch statistics is put into ``train()`` mode here and stays in it.  A
+    training loader that yields another number of batches than its ``len()`` is a ``RuntimeError``.
+
+    -> dict: ``train_loss`` (one mean per epoch run), ``val`` ([(epoch, metrics)]), ``epoch``, ``global_step``, ``optimizer``,
+    ``scheduler``, ``loss_scaler`` (None without a loss scale); in a group the same on every rank."""
+    from .optim import LossScaler
+
+    model, group = pl_module.model, process_group
+    _apply_settings(model, precision=precision, mixed_operand=mixed_operand, train_frontend=train_frontend,
+                    batch_statistics=batch_statistics, frontend_precision=frontend_precision,
+                    frontend_mixed_operand=frontend_mixed_operand, frontend_dropout=frontend_dropout)
     scaler = LossScaler() if model.train_settings.needs_loss_scale() else None   # (16-mixed on fp16 operands somewhere)
-    accumulate = int(accumulate_grad_batches)
-    if accumulate < 1 or int(max_epochs) < 0 or int(val_frequency) < 1:
+    accumulate, max_epochs, val_frequency = int(accumulate_grad_batches), int(max_epochs), int(val_frequency)
+    if accumulate < 1 or max_epochs < 0 or val_frequency < 1:
         raise ValueError("accumulate_grad_batches and val_frequency must be at least 1, max_epochs at least 0")
     datamodule.setup("fit")   # (returns at once when the caller has set the data up already)
     loader = datamodule.train_dataloader()
-    world = 1
-    if process_group is not None:
-        import torch.distributed as dist
-
-        world = dist.get_world_size(process_group)
-    steps_per_epoch = len(step_groups(len(loader), accumulate, world))
+    world, rank = _ranks(group)
+    batches = len(loader)
+    groups = step_groups(batches, accumulate, world)
     extra = {} if ema_decay is None else {"ema_decay": ema_decay}
-    if process_group is not None:
-        extra.update(process_group=process_group, staged=staged)
-    conf = pl_module.configure_optimizers(max(1, steps_per_epoch * int(max_epochs)), max_grad_norm=max_grad_norm,
+    if group is not None:
+        extra.update(process_group=group, staged=staged)
+    conf = pl_module.configure_optimizers(max(1, len(groups) * max_epochs), max_grad_norm=max_grad_norm,
                                           accumulate=accumulate * world, **extra)
     optimizer, scheduler = conf["optimizer"], conf["lr_scheduler"]["scheduler"]
-    device = optimizer.device
-    first_epoch, global_step = 0, 0
-    if resume is not None:
-        from .inference import load_checkpoint
-
-        ckpt = resume if isinstance(resume, dict) else load_checkpoint(resume, "cpu")
-        missing = [k for k in CHECKPOINT_KEYS if k not in ckpt]
-        if missing:
-            raise ValueError(f"cannot resume: the checkpoint has no {missing} (written by fit()?)")
-        pl_module.load_state_dict(ckpt["state_dict"])
-        optimizer.load_state_dict(ckpt["optimizer_states"][0])
-        scheduler.load_state_dict(ckpt["lr_schedulers"][0])
-        _set_rng_state(ckpt["rng"])
-        if "dropout" in ckpt["rng"] and pl_module.model.dropout_state() is not None:
-            pl_module.model.set_dropout_state(ckpt["rng"]["dropout"])
-        if scaler is not None and "loss_scaler" in ckpt:
-            scaler.load_state_dict(ckpt["loss_scaler"])
-        first_epoch, global_step = int(ckpt["epoch"]) + 1, int(ckpt["global_step"])
-        log(f"resumed after epoch {ckpt['epoch']} ({global_step} optimiser steps)")
-    if pl_module.model.dropout_state() is not None or pl_module.model.batch_statistics:
+    first_epoch, global_step = (0, 0) if resume is None else _restore(resume, pl_module, optimizer, scheduler, scaler, log)
+    if model.dropout_state() is not None or model.batch_statistics:
         pl_module.train()
     history = {"train_loss": [], "val": [], "optimizer": optimizer, "scheduler": scheduler, "loss_scaler": scaler}
-    step = optimizer.step if scaler is None else (lambda accumulated: optimizer.step(accumulated=accumulated, loss_scaler=scaler))
     optimizer.zero_grad()
-    if process_group is not None:
-        return _fit_sharded(pl_module, datamodule, loader, int(max_epochs), first_epoch, global_step, accumulate, int(val_frequency),
-                            checkpoint_path, log, ema_decay, optimizer, scheduler, scaler, step, history, process_group, staged)
-    for epoch in range(first_epoch, int(max_epochs)):
-        loss_sum = torch.zeros((), dtype=torch.float32, device=device)
-        batches = pending = 0
-        for i, batch in enumerate(loader):
-            loss = pl_module.training_step(batch, i)
-            if scaler is None:
-                loss.backward()
-            else:
-                (loss * scaler.scale).backward()
-            loss_sum += loss.detach()
-            batches += 1
-            pending += 1
-            if pending == accumulate:
-                step(accumulated=pending)
-                scheduler.step()
-                global_step += 1
-                pending = 0
-        if pending:   # the remainder of the epoch: stepped with its own count
-            step(accumulated=pending)
-            scheduler.step()
-            global_step += 1
-        mean = float(loss_sum) / max(batches, 1)   # (the epoch's only read-back)
-        history["train_loss"].append(mean)
-        line = f"epoch {epoch}: train_loss {mean:.6f}, {global_step} steps, lr {scheduler.get_last_lr()[0]:.3e}"
-        if (epoch + 1) % int(val_frequency) == 0:
-            averaged = ema_decay is not None and optimizer.flat_state()["n_averaged"] > 0
-            with optimizer.averaged_weights() if averaged else contextlib.nullcontext():
-                metrics = validate(pl_module, datamodule)
-            history["val"].append((epoch, metrics))
-            if averaged:
-                line += f", validated on the averaged weights (decay {ema_decay:g})"
-            line += "".join(f", {k} {v:.4f}" for k, v in metrics.items())
-        if checkpoint_path is not None:
-            save_checkpoint(checkpoint_path, pl_module, optimizer, scheduler, epoch, global_step, scaler)
-        log(line)
-    history["epoch"], history["global_step"] = max(first_epoch, int(max_epochs)) - 1, global_step
-    return history
+    if group is not None:
+        import torch.distributed as dist
 
+        _broadcast(list(pl_module.parameters()) + list(pl_module.buffers()), group, staged)
 
-def _fit_sharded(pl_module, datamodule, loader, max_epochs, first_epoch, global_step, accumulate, val_frequency, checkpoint_path, log,
-                 ema_decay, optimizer, scheduler, scaler, step, history, group, staged) -> dict:
-    """``fit``'s epochs on the ranks of ``group`` (its docstring has the rules); everything before the first epoch is done"""
-    import torch.distributed as dist
-
-    world, rank = dist.get_world_size(group), dist.get_rank(group)
-    model, device = pl_module.model, optimizer.device
-    _broadcast(list(pl_module.parameters()) + list(pl_module.buffers()), group, staged)
-    sharded = loader.shard(rank, world)
-    groups = step_groups(len(loader), accumulate, world)
+    scaled = {} if scaler is None else {"loss_scaler": scaler}
 
     def close(count):
-        step(accumulated=count)
+        optimizer.step(accumulated=count, **scaled)
         scheduler.step()
 
     for epoch in range(first_epoch, max_epochs):
-        losses = torch.zeros(max(len(loader), 1), dtype=torch.float32, device=device)
-        rng = model.train_settings.dropout_rng   # (None, or the live {"seed", "calls"})
-        calls0 = None if rng is None else int(rng["calls"])
-        advance = 0 if rng is None else 2 * len(model.transformer_blocks.layers) + (12 if model.frontend_dropout else 0)
-        done = 0
-        for j, batch in sharded:
+        losses = torch.zeros(max(batches, 1), dtype=torch.float32, device=optimizer.device)
+        # in a group the forward of global batch j draws the single process's streams: the model's counter follows j
+        rng = None if group is None else model.train_settings.dropout_rng   # (None, or the live {"seed", "calls"})
+        if rng is not None:
+            calls0 = int(rng["calls"])
+            advance = 2 * len(model.transformer_blocks.layers) + (12 if model.frontend_dropout else 0)
+        done = seen = 0
+        mine = len(range(rank, batches, world))   # (how many of the epoch's batches are this process's)
+        for j, batch in (enumerate(loader) if group is None else loader.shard(rank, world)):
+            if j >= batches:
+                raise RuntimeError(f"the training loader has {batches} batches (len) and yielded batch {j}")
             while j >= groups[done][0] + groups[done][1]:
                 close(groups[done][1])
                 done += 1
@@ -382,33 +312,36 @@ def _fit_sharded(pl_module, datamodule, loader, max_epochs, first_epoch, global_
             if rng is not None and rng["calls"] != calls0 + (j + 1) * advance:
                 raise RuntimeError(f"a training forward drew {rng['calls'] - calls0 - j * advance} dropout streams, {advance} were "
                                    "expected: the ranks' streams would not be the single-process ones")
-            if scaler is None:
-                loss.backward()
-            else:
-                (loss * scaler.scale).backward()
+            (loss if scaler is None else loss * scaler.scale).backward()
             losses[j] = loss.detach()
-        while done < len(groups):
-            close(groups[done][1])
-            done += 1
+            seen += 1
+        if seen != mine:
+            raise RuntimeError(f"the training loader has {batches} batches (len), {mine} of them this process's, and ended after {seen}")
+        for _, count in groups[done:]:   # the groups no batch of this process came after: the epoch's last, with its own count
+            close(count)
         global_step += len(groups)
         if rng is not None:
-            rng["calls"] = calls0 + len(loader) * advance
-        if model.batch_statistics:
+            rng["calls"] = calls0 + batches * advance
+        if group is not None and model.batch_statistics:
             _broadcast(list(pl_module.buffers()), group, staged)
-        # the epoch's read-back: the ranks' losses, merged and added in global batch order as the single process adds them
-        gathered = [None] * world
-        dist.all_gather_object(gathered, (losses.cpu().numpy(), _fingerprint(optimizer)), group=group)
-        prints = [g[1] for g in gathered]
-        if any(p != prints[0] for p in prints):
-            odd = [r for r, p in enumerate(prints) if p != prints[0]]
-            raise RuntimeError(f"epoch {epoch}: ranks {odd} have diverged from rank 0 (optimiser moments or numpy's generator): "
-                               f"fingerprints {prints}")
+        # the epoch's only read-back: every process's losses, added in global batch order as a chain of fp32 additions from 0
+        parts = [losses.cpu().numpy()]
+        if group is not None:
+            gathered = [None] * world
+            dist.all_gather_object(gathered, (parts[0], _fingerprint(optimizer)), group=group)
+            parts, prints = [g[0] for g in gathered], [g[1] for g in gathered]
+            if any(p != prints[0] for p in prints):
+                odd = [r for r, p in enumerate(prints) if p != prints[0]]
+                raise RuntimeError(f"epoch {epoch}: ranks {odd} have diverged from rank 0 (optimiser moments or numpy's generator): "
+                                   f"fingerprints {prints}")
         total = np.float32(0.0)
-        for j in range(len(loader)):
-            total = total + gathered[j % world][0][j]
-        mean = float(total) / max(len(loader), 1)
+        for j in range(batches):
+            total = total + parts[j % world][j]
+        mean = float(total) / max(batches, 1)
         history["train_loss"].append(mean)
-        line = f"epoch {epoch}: train_loss {mean:.6f}, {global_step} steps, lr {scheduler.get_last_lr()[0]:.3e}, {world} ranks"
+        line = f"epoch {epoch}: train_loss {mean:.6f}, {global_step} steps, lr {scheduler.get_last_lr()[0]:.3e}"
+        if group is not None:
+            line += f", {world} ranks"
         if (epoch + 1) % val_frequency == 0:
             averaged = ema_decay is not None and optimizer.flat_state()["n_averaged"] > 0
             with optimizer.averaged_weights() if averaged else contextlib.nullcontext():
@@ -420,7 +353,8 @@ def _fit_sharded(pl_module, datamodule, loader, max_epochs, first_epoch, global_
         if checkpoint_path is not None:
             if rank == 0:
                 save_checkpoint(checkpoint_path, pl_module, optimizer, scheduler, epoch, global_step, scaler)
-            dist.barrier(group=group)
+            if group is not None:
+                dist.barrier(group=group)
         if rank == 0:
             log(line)
     history["epoch"], history["global_step"] = max(first_epoch, max_epochs) - 1, global_step

@@ -48,13 +48,16 @@ def new_datamodule(root):
     return BeatDataModule(root, batch_size=1, train_length=150, augmentations={}, device=H.dev())
 
 
-def observe_steps(pl, steps, fail_step=None):
+def observe_steps(pl, steps, fail_step=None, configured=None):
     """every optimiser step leaves its groups' rates (as they are BEFORE the step), its count and, with clipping, its norm in
-    ``steps``; ``fail_step``: the step with that number raises instead"""
+    ``steps``; ``fail_step``: the step with that number raises instead; ``configured``: a list that receives the arguments of
+    every ``configure_optimizers`` call.  (Shared with tests/test_gpu_finetune_trajectory.py, like the loader below.)"""
     configure = pl.configure_optimizers
 
     def configure_optimizers(total_steps, **kw):
         conf = configure(total_steps, **kw)
+        if configured is not None:
+            configured.append(dict(total_steps=total_steps, **kw))
         opt = conf["optimizer"]
         step = opt.step
 

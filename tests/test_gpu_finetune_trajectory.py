@@ -24,6 +24,7 @@ import torch
 import route_grads as RG
 import metrics_reference as MR
 from dataset_reference import build_data_folder
+from ddp_worker import TENSORS, RecordingLoader, observe_steps
 from gpu_util import dev, report
 from beat_this_amd import weights as W
 from oracle import beat_this_oracle as O
@@ -43,7 +44,6 @@ CASES = {
     "C": dict(batch_size=1, accumulate=2, max_grad_norm=0.68, weight_decay=0.05, pos_weights={"beat": 2.5, "downbeat": 6.0},
               val_frequency=EPOCHS + 1, dropout=True),
 }
-TENSORS = ("spect", "truth_beat", "truth_downbeat", "padding_mask", "downbeat_mask")
 _RUNS = {}
 
 
@@ -54,21 +54,6 @@ def initial_state_dict():
 @pytest.fixture(scope="module")
 def folder(tmp_path_factory):
     return build_data_folder(str(tmp_path_factory.mktemp("trajectory") / "data"))
-
-
-class RecordingLoader:
-    """the training loader, every batch it yields cloned to the CPU on the way"""
-
-    def __init__(self, loader, seen):
-        self.loader, self.seen = loader, seen
-
-    def __len__(self):
-        return len(self.loader)
-
-    def __iter__(self):
-        for batch in self.loader:
-            self.seen.append({k: batch[k].detach().cpu().clone() for k in TENSORS})
-            yield batch
 
 
 def observed_fit(case, folder, tmp):
@@ -99,26 +84,7 @@ def observed_fit(case, folder, tmp):
         return loss
 
     pl.training_step = recording_training_step
-    configure_optimizers = pl.configure_optimizers
-
-    def recording_configure_optimizers(total_steps, **kw):
-        conf = configure_optimizers(total_steps, **kw)
-        opt = conf["optimizer"]
-        rec["configured"].append(dict(total_steps=total_steps, **kw))
-        rec["optimizer"] = opt
-        step = opt.step
-
-        def recording_step(*args, **kwargs):
-            result = step(*args, **kwargs)
-            rec["steps"].append(dict(lrs=[g["lr"] for g in opt.param_groups], accumulated=kwargs.get("accumulated"),
-                                     norm=opt.last_grad_norm() if opt.max_grad_norm is not None else None))
-            return result
-
-        recording_step._wrapped_by_lr_sched = True   # (the scheduler's own wrapper is inside: it still sees every step)
-        opt.step = recording_step
-        return conf
-
-    pl.configure_optimizers = recording_configure_optimizers
+    observe_steps(pl, rec["steps"], configured=rec["configured"])
     ck = str(tmp / f"{case}.ckpt")
 
     def log(line):   # (called after the epoch's checkpoint is written)
@@ -130,6 +96,7 @@ def observed_fit(case, folder, tmp):
     np.random.seed(0)
     rec["history"] = fit(pl, dm, EPOCHS, accumulate_grad_batches=c["accumulate"], val_frequency=c["val_frequency"],
                          max_grad_norm=c["max_grad_norm"], checkpoint_path=ck, log=log)
+    rec["optimizer"] = rec["history"]["optimizer"]
     rec["checkpoint_paths"] = [str(tmp / f"{case}.epoch{e}.ckpt") for e in range(EPOCHS)]
     # the helper's inputs: the frozen frontend's output for every recorded batch, and its two runs
     with torch.no_grad():
