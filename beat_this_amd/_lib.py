@@ -18,8 +18,8 @@ LIB_PATH = os.path.join(PKG_DIR, "libbeat_this_amd.so")
 if os.environ.get("BT_DEV") == "1" and os.environ.get("BT_LIB_PATH"):  # development only (tools/ab.sh: A/B of two builds)
     LIB_PATH = os.environ["BT_LIB_PATH"]
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm_mx8.hip", "attn.hip", "attn2.hip", "fused.hip", "fused2.hip", "qkv_front.hip", "frontend.hip", "logmel.hip",
-           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "reduce.hip", "stretch.hip", "pcm.hip", "engine.hip"]
-HEADERS = ["common.h", "chain.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "train_front_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
+           "tail.hip", "dbn.hip", "metrics.hip", "loss.hip", "data.hip", "train.hip", "train_front.hip", "optim.hip", "reduce.hip", "stretch.hip", "pcm.hip", "flac.hip", "engine.hip"]
+HEADERS = ["common.h", "chain.h", "flac_bits.h", "kernels.h", "dropout.h", "train_common.h", "train_mixed.inc", "train_front_mixed.inc", "attn_x3_loop.inc", "attn_hq2_loop.inc", os.path.join("..", "..", "include", "beat_this_amd.h")]
 
 BT_OK, BT_ERR_ARG, BT_ERR_HIP, BT_ERR_WORKSPACE = 0, -1, -2, -3
 # The operand formats of the training route (``operand`` of the three training structs): name -> (BT_OPERAND_*, the suffix of the
@@ -166,6 +166,21 @@ class PcmSpan(C.Structure):   # bt_pcm_span
     _fields_ = [("d_src", C.c_void_p), ("n_frames", C.c_int64), ("d_out", C.c_void_p), ("format", C.c_int32), ("channels", C.c_int32)]
 
 
+class FlacInfo(C.Structure):   # bt_flac_info
+    _fields_ = [("sample_rate", C.c_int32), ("channels", C.c_int32), ("bps", C.c_int32), ("blocking", C.c_int32),
+                ("min_block", C.c_int32), ("max_block", C.c_int32), ("total_samples", C.c_int64), ("first_frame", C.c_int64),
+                ("n_bytes", C.c_int64), ("md5", C.c_uint8 * 16)]
+
+
+class FlacStatus(C.Structure):   # bt_flac_status
+    _fields_ = [("code", C.c_int32), ("n_frames", C.c_int32), ("n_samples", C.c_int64), ("where", C.c_int64)]
+
+
+class FlacSpan(C.Structure):   # bt_flac_span
+    _fields_ = [("d_src", C.c_void_p), ("d_out", C.c_void_p), ("d_ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+                ("d_status", C.c_void_p), ("info", FlacInfo)]
+
+
 class OptimTensor(C.Structure):   # bt_optim_tensor
     _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int64), ("group", C.c_int32), ("reserved", C.c_int32)]
 
@@ -201,6 +216,8 @@ PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # BT_PCM_*: sam
 PCM_SAMPLE_BYTES = (1, 2, 3, 4, 4, 8)
 PCM_MAX_CHANNELS_INT, PCM_MAX_CHANNELS_FLOAT, PCM_MAX_TRACKS = 8, 7, 65535
 PCM_THREAD_FRAMES, PCM_BLOCK_FRAMES = 4, 1024               # frames per thread / per workgroup (tests sit on both sides of them)
+FLAC_OK, FLAC_BROKEN, FLAC_LENGTH, FLAC_CANDIDATES = range(4)   # BT_FLAC_*: a track's status code (csrc/flac.hip)
+FLAC_MAX_TRACKS, FLAC_THREAD_SAMPLES, FLAC_BLOCK_SAMPLES, FLAC_SCAN_BYTES = 65535, 4, 1024, 256
 REDUCE_MAX_WORLD, REDUCE_CHUNK = 16, 4096                  # BT_REDUCE_*: ranks of one bt_grad_rank_sum / elements per workgroup
 
 EXPORTS = {
@@ -346,6 +363,11 @@ EXPORTS = {
     "bt_pcm_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64]),
     "bt_pcm_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "bt_pcm_decode_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "bt_flac_probe_host": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(FlacInfo)]),
+    "bt_flac_decode_host": (C.c_int, [C.c_void_p, C.POINTER(FlacInfo), C.c_void_p, C.c_void_p, C.POINTER(FlacStatus)]),
+    "bt_flac_workspace_bytes": (C.c_size_t, [C.POINTER(FlacInfo)]),
+    "bt_flac_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "bt_flac_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FlacInfo), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bt_grad_rank_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p]),
     "bt_grad_rank_sum_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p]),
 }
@@ -373,7 +395,9 @@ FLAGS_BY_SOURCE = {"tail.hip": ["-Xclang", "-target-feature", "-Xclang", "-packe
                    # frame positions, output lengths and filter arguments are fp64 expressions that numpy evaluates too
                    "stretch.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
                    # the channel mean is numpy's fp64 sum and division, operation by operation, on the host and the device
-                   "pcm.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
+                   "pcm.hip": HIPCC_FLAGS + ["-ffp-contract=off"],
+                   # the same channel mean over the integers a FLAC stream decodes to: a FLAC and a WAV of one audio agree bit for bit
+                   "flac.hip": HIPCC_FLAGS + ["-ffp-contract=off"]}
 # compile-time switches: BT_DEFINES in the environment of build() (e.g. "-DBT_HALF_BF16"); every one of them builds a correct library
 EXTRA_DEFINES = os.environ.get("BT_DEFINES", "").split()
 

@@ -6,8 +6,8 @@
 Differences: ``--gpu -1`` (CPU) is refused, there is no CPU path in this package; with a ROCm device present
 ``--gpu N`` selects ``cuda:N`` exactly like the reference.
 
-Extensions, both opt-in: ``--device-decode`` decodes PCM WAV files on the GPU (csrc/pcm.hip; any other file is decoded as
-before), ``--batch N`` processes up to N files per batch through ``File2Beats.many_async``.  Without them the loop below is
+Extensions, both opt-in: ``--device-decode`` decodes PCM WAV and FLAC files on the GPU (csrc/pcm.hip, csrc/flac.hip; any other file
+is decoded as before), ``--batch N`` processes up to N files per batch through ``File2Beats.many_async``.  Without them the loop below is
 the reference's.
 """
 from __future__ import annotations
@@ -37,7 +37,7 @@ OPTIONS = (
     (("--activations",), dict(action="store_true", help="also save the raw logits as .npy")),
     # extensions (absent from the parsed arguments unless given: ``run``'s defaults are today's behaviour)
     (("--device-decode",), dict(action="store_true", default=argparse.SUPPRESS,
-                                help="decode PCM WAV files on the GPU (any other file is decoded as before)")),
+                                help="decode PCM WAV and FLAC files on the GPU (any other file is decoded as before)")),
     (("--batch",), dict(type=int, default=argparse.SUPPRESS, metavar="N",
                         help="process up to N files per batch: files of batch i + 1 are read while batch i computes (default: 1)")),
 )
@@ -83,13 +83,16 @@ def collect_tasks(inputs, output, suffix, append, skip_existing):
 
 
 def batch_cost(audiofile: Path):
-    """(file bytes, an upper estimate of the 50 fps frames) of one input, for the caps of a batch: exact for a PCM WAV file;
-    for anything else 50 frames per kilobyte (an 8 kbit/s stream), so that the byte cap bounds the frames as well"""
-    from . import wav
+    """(file bytes, an upper estimate of the 50 fps frames) of one input, for the caps of a batch: exact for a PCM WAV file,
+    the decoded PCM bytes for a FLAC file the device decodes; for anything else 50 frames per kilobyte (an 8 kbit/s stream), so that the byte cap bounds the frames as well"""
+    from . import flac, wav
 
     info = wav.probe(audiofile)
     if info is not None:
         return info.data_bytes, 50 * info.n_frames // info.sample_rate + 2
+    info = flac.probe(audiofile)
+    if info is not None:      # (the bytes it decodes to, not the file's: the workspace holds the decoded integers)
+        return info.decoded_bytes, 50 * info.total_samples // info.sample_rate + 2
     try:
         size = audiofile.stat().st_size
     except OSError:

@@ -11,8 +11,9 @@ Differences that matter for speed, not for results:
     aggregation, peak picking) and ONE device-to-host copy for all tracks.
   * ``File2Beats.many`` / ``many_async`` / ``Audio2Frames.files2waves`` (extensions) and ``device_decode=True`` (opt-in): PCM
     WAV files go to the GPU as the bytes they are and are decoded there (csrc/pcm.hip: the channel mean in fp64 exactly as
-    numpy computes it, so the waveform has the bits of ``load_audio`` + ``mean(1)``); a file ``wav.probe`` does not fully
-    recognise takes ``load_audio`` as before.
+    numpy computes it, so the waveform has the bits of ``load_audio`` + ``mean(1)``), and so do FLAC files (csrc/flac.hip:
+    frame search, Rice and LPC decode on the device, the same channel mean); a file neither ``wav.probe`` nor ``flac.probe``
+    fully recognises takes ``load_audio`` as before.
 
 Precision (the ``float16`` argument of the inference classes):
   * ``False`` (the reference's default): fp32 activations and fp32-class results -- framewise logits within 1e-3 of the
@@ -475,13 +476,21 @@ class Audio2Frames(Spect2Frames):
         files (``wav.probe``) are read as they are into pooled pinned buffers -- by up to READ_THREADS host threads that do
         nothing else; only the calling thread touches the GPU --, uploaded on the copy stream and decoded by ONE
         bt_pcm_decode_batch launch: bit for bit the waveform ``load_audio`` + ``mean(1)`` + the fp32 conversion give on the
-        host.  Any other file takes exactly that host route (and raises what ``load_audio`` raises)."""
-        from . import wav
+        host.  FLAC files inside the device decoder's subset (``flac.probe``) go up whole and are decoded -- frame search,
+        Rice, LPC, channel mean -- by ONE bt_flac_decode_batch call (csrc/flac.hip); that call reads the tracks' statuses back:
+        one small copy and one synchronisation per batch.  Any other file, and a FLAC track whose status is not OK, takes
+        exactly the host route (and raises what ``load_audio`` raises)."""
+        from . import flac, wav
 
         dev = self.device
         paths = list(paths)
         out = [None] * len(paths)
         infos = [wav.probe(p) for p in paths]
+        flacs = [(k, flac.probe(p)) for k, p in enumerate(paths) if infos[k] is None]
+        flacs = [(k, i) for k, i in flacs if i is not None]
+        if flacs:
+            for (k, _), w in zip(flacs, self._flac2waves([(paths[k], i) for k, i in flacs])):
+                out[k] = w
         idx = [k for k, i in enumerate(infos) if i is not None]
         bufs = [_raw_pinned(infos[k].raw_span[1]) for k in idx]        # (allocated here, by the caller; the threads only fill them)
         if len(idx) > 1:
@@ -529,15 +538,81 @@ class Audio2Frames(Spect2Frames):
                 out[k] = (torch.from_numpy(_host_mono(signal)).to(dev), sr)
         return out
 
+    def _flac2waves(self, items):
+        """[(path, flac.FlacInfo)] -> [(mono fp32 waveform on the device, sample rate), or None for a track whose file could
+        not be read or whose status is not OK].  The files go up as they are (pooled pinned buffers, the copy stream); one
+        bt_flac_decode_batch call (bt_flac_decode for a single track: no device table) finds and decodes the frames of all
+        of them; then the statuses are read back -- one small copy and one synchronisation per call."""
+        import ctypes as C
+
+        from . import flac
+
+        dev = self.device
+        result = [None] * len(items)
+        bufs = [_raw_pinned(i.n_bytes) for _, i in items]
+        if len(items) > 1:
+            jobs = [_read_pool().submit(flac.read_raw, i, p, b) for (p, i), b in zip(items, bufs)]
+        else:
+            jobs = [_Done(flac.read_raw, i, p, b) for (p, i), b in zip(items, bufs)]
+        ok = []
+        for j, job in enumerate(jobs):
+            try:
+                job.result()
+                ok.append(j)
+            except OSError:      # (the file changed under us: let load_audio say what it says today)
+                pass
+        ev = None
+        if ok:
+            lib = _lib.lib()
+            cur = torch.cuda.current_stream(dev)
+            copy = _copy_stream(dev)
+            with torch.cuda.device(dev):
+                raws = []
+                with torch.cuda.stream(copy):
+                    for j in ok:
+                        d = bufs[j][: items[j][1].n_bytes].to(dev, non_blocking=True)
+                        d.record_stream(cur)
+                        raws.append(d)
+                ev = torch.cuda.Event()
+                ev.record(copy)
+                cur.wait_event(ev)
+                infos = [items[j][1].c_info() for j in ok]
+                n = np.array([i.total_samples for i in infos], dtype=np.int64)
+                off = np.concatenate([[0], np.cumsum((n + 3) // 4 * 4)])          # every track 16-byte aligned
+                ws_n = np.array([lib.bt_flac_workspace_bytes(C.byref(i)) for i in infos], dtype=np.int64)
+                ws_off = np.concatenate([[0], np.cumsum((ws_n + 255) // 256 * 256)])
+                big = torch.empty(int(off[-1]), dtype=torch.float32, device=dev)
+                ws = torch.empty(int(ws_off[-1]), dtype=torch.uint8, device=dev)
+                status = torch.empty((len(ok), 3), dtype=torch.int64, device=dev)   # bt_flac_status
+                spans = (_lib.FlacSpan * len(ok))()
+                for t, (d, i) in enumerate(zip(raws, infos)):
+                    spans[t] = _lib.FlacSpan(d.data_ptr(), big.data_ptr() + 4 * int(off[t]), ws.data_ptr() + int(ws_off[t]), int(ws_n[t]),
+                                             status.data_ptr() + 24 * t, i)
+                if len(ok) == 1:
+                    sp = spans[0]
+                    _lib.check(lib.bt_flac_decode(_lib.stream_ptr(dev), sp.d_src, C.byref(infos[0]), sp.d_out, sp.d_ws, sp.ws_bytes, sp.d_status))
+                else:
+                    d_table = _lib.upload(np.frombuffer(bytes(spans), dtype=np.uint8), dev)
+                    _lib.check(lib.bt_flac_decode_batch(_lib.stream_ptr(dev), spans, d_table.data_ptr(), len(ok)))
+                codes = status.view(torch.int32)[:, 0].cpu().numpy()                # (the synchronisation)
+            for t, j in enumerate(ok):
+                if codes[t] == _lib.FLAC_OK:
+                    result[j] = (big[int(off[t]): int(off[t]) + int(n[t])], infos[t].sample_rate)
+        _return_raw(bufs, ev)
+        return result
+
     def file2wave(self, path):
         """One PCM WAV file -> (mono fp32 waveform on the device, sample rate) by bt_pcm_decode, or None where ``wav.probe``
         declines the file (the caller then decodes it on the host, as before).  No device table, no second stream: this is
-        the latency path of ``File2Beats(device_decode=True)``."""
-        from . import wav
+        the latency path of ``File2Beats(device_decode=True)``.  A FLAC file ``flac.probe`` takes is decoded by
+        bt_flac_decode (``_flac2waves``: its status is read back, one synchronisation); None as well where that status is
+        not OK."""
+        from . import flac, wav
 
         info = wav.probe(path)
         if info is None:
-            return None
+            finfo = flac.probe(path)
+            return None if finfo is None else self._flac2waves([(path, finfo)])[0]
         dev = self.device
         buf = _raw_pinned(info.raw_span[1])
         ev = None

@@ -1116,6 +1116,69 @@ int bt_pcm_decode(void* stream, const uint8_t* d_src, int format, int channels, 
 /* the host twin: plain sequential C++ over the same inline helpers; src and out in HOST memory, any alignment of src */
 int bt_pcm_decode_host(const uint8_t* src, int format, int channels, int64_t n_frames, float* out);
 
+/* ---- FLAC decode (csrc/flac.hip, csrc/flac_bits.h): a FLAC file's bytes -> the mono fp32 waveform, on
+ * the device, frame search included.  The format facts are RFC 9639's.
+ * Accepted: native FLAC (the `fLaC` marker), optionally behind an ID3v2 tag; any metadata blocks before the audio (skipped by
+ * their lengths; STREAMINFO first); 1 .. 8 channels; 4 .. 24 bits per sample; any block size up to 65535; fixed and variable
+ * blocking; total_samples > 0; bytes behind the last frame are ignored.  Declined (the probe returns 0): Ogg FLAC,
+ * total_samples == 0, 25 .. 32 bits per sample.  The device entry points also refuse (BT_ERR_ARG) a file of 2^31 bytes or
+ * more and a stream of 2^31 samples or more.
+ * Arithmetic: the decoded integers v are exact; a sample's value is s = v / 2^(bps-1), exact in fp64 (what soundfile and
+ * torchaudio hand to load_audio).  One channel: out = fp32(s).  C channels: acc = (+0.0) + s[0]; acc = acc + s[c] left to
+ * right; acc = acc / C; all in fp64, then one rounding to fp32 -- BT_PCM_S16 / BT_PCM_S24's words above, so a FLAC file and a
+ * WAV file that hold the same integers decode to the same bits.  Integer sums of up to 8 channels are exact in any order.
+ * The source is built with -ffp-contract=off.
+ * Frames: a FLAC frame has no length field.  A frame is accepted only as a link of the chain that starts at first_frame: it
+ * begins where the previous frame ended, its header is one of this stream (sync, the stream's blocking bit, no reserved
+ * code, channels / sample size / rate as STREAMINFO has them, block size <= max_block, a well-formed coded number, CRC-8),
+ * it carries the number that follows its predecessor's (frame index, or running sample count), its subframes, zero padding
+ * and CRC-16 hold, and it does not pass total_samples.  The chain must end exactly at total_samples.  Checksums alone accept
+ * nothing: a verbatim subframe may hold a complete valid frame as payload.  Anything else sets the track's status and writes
+ * no output sample.
+ * Status, per track: code BT_FLAC_OK, or BT_FLAC_BROKEN (no valid frame with the expected number at byte `where`),
+ * BT_FLAC_LENGTH (the frame at `where` would pass total_samples), BT_FLAC_CANDIDATES (device only: more frame-header
+ * candidates than the workspace provides for, n / 8 + 64 of them -- a valid stream without false headers cannot have more:
+ * a frame has at least 9 bytes); n_frames / n_samples: what the chain had accepted; `where`: the byte at which the chain
+ * broke, or the byte behind the last frame.
+ * Device: a call decodes a ragged list of tracks in a number of launches that does not depend on the list (scan, prefix,
+ * compact, measure, link, decode, mix; blockIdx.y = track).  No read leaves a track's [d_src, d_src + n_bytes); d_src may
+ * have any alignment.  Writes: exactly total_samples floats at d_out (16-byte aligned) where the status is BT_FLAC_OK, none
+ * otherwise; the status; and bytes of [d_ws, d_ws + the workspace query) (d_ws 16-byte aligned).  A workspace smaller than the
+ * query is BT_ERR_WORKSPACE before any launch.  No atomics: output and status are bit-identical between runs, and between a
+ * track alone and the same track in a batch.  The device and the host twin agree bit for bit in output and status. */
+#define BT_FLAC_OK 0
+#define BT_FLAC_BROKEN 1
+#define BT_FLAC_LENGTH 2
+#define BT_FLAC_CANDIDATES 3
+#define BT_FLAC_MAX_TRACKS 65535
+#define BT_FLAC_THREAD_SAMPLES 4     /* output samples per thread of the mix: one 16-byte store */
+#define BT_FLAC_BLOCK_SAMPLES 1024   /* output samples per workgroup of the mix */
+#define BT_FLAC_SCAN_BYTES 256       /* byte offsets per workgroup of the scan */
+typedef struct {
+  int32_t sample_rate, channels, bps, blocking;   /* blocking: the blocking bit of the first frame */
+  int32_t min_block, max_block;
+  int64_t total_samples, first_frame, n_bytes;    /* first_frame: byte offset of the first frame; n_bytes: the file's length */
+  uint8_t md5[16];                                /* of the interleaved little-endian PCM (STREAMINFO) */
+} bt_flac_info;
+typedef struct { int32_t code; int32_t n_frames; int64_t n_samples; int64_t where; } bt_flac_status;
+typedef struct { const uint8_t* d_src; float* d_out; void* d_ws; size_t ws_bytes; bt_flac_status* d_status; bt_flac_info info; } bt_flac_span;
+/* HOST: marker, ID3v2 skip, metadata walk, STREAMINFO, the first frame's offset and blocking bit -> 1, or 0 for a file
+ * outside the subset (or a null argument) */
+int bt_flac_probe_host(const uint8_t* bytes, int64_t n_bytes, bt_flac_info* info);
+/* HOST: the sequential twin over the same parser: out_f32 gets total_samples floats and pcm_i32_or_null (if given) the
+ * total_samples x channels interleaved integers -- both only where the status is BT_FLAC_OK.  BT_ERR_ARG: a null argument,
+ * an info outside the subset. */
+int bt_flac_decode_host(const uint8_t* src, const bt_flac_info* info, float* out_f32, int32_t* pcm_i32_or_null,
+                        bt_flac_status* status);
+/* device workspace of one track (0 for an info outside the subset) */
+size_t bt_flac_workspace_bytes(const bt_flac_info* info);
+/* one call for a ragged list of tracks: h_tracks (HOST, read before the launches: sizes and checks) and d_tracks (DEVICE,
+ * the same n_tracks entries: what the kernels read) */
+int bt_flac_decode_batch(void* stream, const bt_flac_span* h_tracks, const bt_flac_span* d_tracks, int n_tracks);
+/* one track without a device table */
+int bt_flac_decode(void* stream, const uint8_t* d_src, const bt_flac_info* info, float* d_out, void* d_ws, size_t ws_bytes,
+                   bt_flac_status* d_status);
+
 /* ---- data-parallel training: the rank-ordered gradient sum (csrc/reduce.hip) ----------------------------
  * `world` fp32 arrays of n elements, rank r's at d_parts + r * stride (elements), are added element by element in RANK ORDER,
  * one rounded fp32 add at a time and nothing else:
